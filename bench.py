@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- linear-layer tokens/s of the low-bit Llama / Mixtral linears on MI355X (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run measures the headline alone: set-up, W warm-up steps, K timed steps, the line (metric, value, unit, ms_per_step, ...).
+--dump-outputs DIR writes what the timed path returned in its last step as DIR/<module>.npy (float32; see dump_outputs).
+--full adds everything else below: the roofline, the other module layout, the subclass / stack baselines, the secondary configs,
+the CPU baselines and, with N > 1 ranks or --force-tp, the TP leg.
 
 Headline (the ONE JSON line's metric / value / roofline / cpu_baseline) = BASELINE.json configs[1]:
 Int4WeightOnlyConfig(group_size=128), Llama-3-8B linear shapes, bs=1 seq=1.  One "step" = one token through every
@@ -97,6 +102,9 @@ def parse_args():
     ap.add_argument("--no-subclass-graph", action="store_true", help="skip the quantize_()-subclass + F.linear graph timing (a13)")
     ap.add_argument("--tp-timeout", type=int, default=int(os.environ.get("AO_BENCH_TP_TIMEOUT", "240")), help="seconds the TP leg of a multi-GPU run may take before every rank leaves and rank 0 prints the line without it")
     ap.add_argument("--tp-one-shot", action="store_true", help="TP config: accumulator all-reduces of <= 1 MiB through the symmetric-memory one-shot path (prototype; default RCCL)")
+    ap.add_argument("--full", action="store_true", help="also the roofline, the other layout, the baselines, the secondary configs and the TP leg "
+                                                         "(a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<module>.npy (float32)")
     return ap.parse_args()
 
 
@@ -283,6 +291,37 @@ def run_int4(model, batch, steps, warmup, stream, device, use_graph, dist=None):
     cur = lambda: torch.cuda.current_stream().cuda_stream  # noqa: E731
     run, graphed = capture(lambda: model.step(batch, cur()), stream, use_graph)
     return time_steps(run, stream, device, steps, warmup, dist), graphed
+
+
+DUMP_BUDGET_BYTES = 60_000_000  # array data of one --dump-outputs, under 64 MB with the .npy headers
+
+
+def dump_outputs(model, batch, out_dir):
+    """What a caller of the timed path receives from its last step: every linear's bf16 output, as float32, one file per module
+    name with the layers stacked ([layers, rows, n]).  The inputs come from seeded generators, so the same arguments give the
+    same files on every run.  Beyond DUMP_BUDGET_BYTES in all, a fixed seeded sample of rows (then of layers) is written, the
+    same sample for every module.  Returns ({name: shape written}, rows written, layers written)."""
+    os.makedirs(out_dir, exist_ok=True)
+    keep, lst = model.io[batch]
+    by_name = {}
+    for (_, y), launch in zip(keep, lst):
+        by_name.setdefault(launch[-1], []).append(y)
+    layers = len(next(iter(by_name.values())))
+    row_bytes = 4 * sum(len(ys) * ys[0].shape[1] for ys in by_name.values())  # one row of every output of every layer
+    rng = np.random.default_rng(0)
+    rows = np.arange(batch)
+    if batch * row_bytes > DUMP_BUDGET_BYTES:
+        rows = np.sort(rng.choice(batch, max(1, DUMP_BUDGET_BYTES // row_bytes), replace=False))
+    lays = np.arange(layers)
+    if len(rows) * row_bytes > DUMP_BUDGET_BYTES:
+        lays = np.sort(rng.choice(layers, max(1, DUMP_BUDGET_BYTES * layers // row_bytes), replace=False))
+    rows_t = torch.from_numpy(rows).to(model.device)
+    shapes = {}
+    for name, ys in by_name.items():
+        a = torch.stack([ys[i].index_select(0, rows_t) for i in lays]).float().cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes, rows.tolist(), lays.tolist()
 
 
 def int4_kernel_table(model, batch, stream):
@@ -1092,13 +1131,15 @@ def main():
     tokens_per_s = args.batch * world * args.steps / elapsed
 
     _dbg("headline timed")
-    roof = int4_roofline(model, args.batch, stream) if rank == 0 else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(model, args.batch, args.dump_outputs)
+    roof = int4_roofline(model, args.batch, stream) if rank == 0 and args.full else None
     _dbg("roofline done")
 
     # the other module layout, for the record (rank 0 of a 1-GPU run only: it doubles resident weights); then both layouts
     # replayed alternately (median / best / worst of 5 rounds), the subclass + F.linear path (a13) and the same-box stack baseline
     other_tok_s, stats, subclass, stack, merged_cfg = None, None, None, None, None
-    if rank == 0 and world == 1 and not args.no_second_layout:
+    if args.full and rank == 0 and world == 1 and not args.no_second_layout:
         m2 = Int4Linears(device, args.layers, LLAMA3_8B_UNMERGED if merged else LLAMA3_8B_MERGED)
         steps2 = min(args.steps, 20)
         e2, _ = run_int4(m2, args.batch, steps2, min(args.warmup, 3), stream, device, not args.no_graph)
@@ -1121,7 +1162,7 @@ def main():
                 merged_cfg = {"error": repr(e)}
         del m2
         torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and args.batch == 1 and not args.no_graph:
+    if args.full and rank == 0 and world == 1 and args.batch == 1 and not args.no_graph:
         if not args.no_subclass_graph:
             try:
                 subclass = subclass_graph_tokens_per_s(model, stream, device)
@@ -1133,7 +1174,7 @@ def main():
     configs = {}
     if merged_cfg is not None:
         configs["int4_bs1_merged"] = merged_cfg
-    want = set() if args.no_configs else set(args.configs.split(","))
+    want = set() if args.no_configs or not args.full else set(args.configs.split(","))
     if rank == 0 and world == 1 and args.batch == 1:
         for key, fn in (("int4_bs128", lambda: config_int4_bs128(model, stream, device, args)),
                         ("int8", lambda: config_int8(stream, device, args)),
@@ -1181,7 +1222,7 @@ def main():
         }
         if stack is not None:
             out["stack_baseline"] = stack
-        if not args.no_cpu_baseline and world == 1:  # rank 0 at N = 1 only: the other ranks of a multi-GPU run would sit in the barrier
+        if args.full and not args.no_cpu_baseline and world == 1:  # rank 0 at N = 1 only: the other ranks of a multi-GPU run would sit in the barrier
             port = cpu_baseline_int4(args.batch)
             ref = reference_cpu_baseline_int4() if args.batch == 1 else None
             if ref is not None and "value" in ref:
@@ -1242,6 +1283,9 @@ def main():
                 flat["mxfp8_mixtral_uniform16_tokens_per_s"] = c["mxfp8_mixtral_bs64"]["uniform16"]["value"]
                 flat["mxfp8_mixtral_uniform16_frac_of_hbm_peak"] = c["mxfp8_mixtral_bs64"]["uniform16"]["roofline"]["frac"]
         out.update({k_: v for k_, v in flat.items() if v is not None})
+        if not args.full:  # a plain line names only what the run measured (vs_baseline stays: it is part of the line's contract)
+            out["config"] = {k_: v for k_, v in out["config"].items() if v is not None}
+            out = {k_: v for k_, v in out.items() if v is not None or k_ == "vs_baseline"}
     if (world > 1 or args.force_tp) and "tp" in want and args.batch == 1:
         # The TP leg is the only part of a multi-GPU run with collectives in it.  It runs LAST, with the headline line already assembled,
         # under a watchdog: should a rank hang in it (a rendezvous or a peer mapping that this code has never seen on the node at hand), every

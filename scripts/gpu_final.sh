@@ -11,7 +11,7 @@ timeout 90 python -c "import torch; torch.zeros(1, device='cuda').add_(1).item()
 O=$R/gpurun_out/${1:-final}
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-HEAD_CMD="python $R/bench.py --warmup 1 --no-cpu-baseline --no-second-layout --no-configs"
+HEAD_CMD="python $R/bench.py --full --warmup 1 --no-cpu-baseline --no-second-layout --no-configs"
 echo "== rocprof stats, headline =="
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_stats -o int4 -- $HEAD_CMD --steps 10 > $O/rocprof_stats.log 2>&1
 f=$(find $O/prof_stats -name "*kernel_stats.csv" 2>/dev/null | head -1)
@@ -39,7 +39,7 @@ for lay, name in (("five", f"int4_pmc_{ROUND}.json"), ("merged", f"int4_pmc_merg
         print("pmc summary not usable for", lay, repr(e))
 PY
 echo "== rocprof pmc + stats, secondary configs =="
-CFG_CMD="python $R/bench.py --warmup 1 --steps 2 --no-cpu-baseline --no-second-layout --no-stack-baseline --no-subclass-graph"
+CFG_CMD="python $R/bench.py --full --warmup 1 --steps 2 --no-cpu-baseline --no-second-layout --no-stack-baseline --no-subclass-graph"
 for c in int4_bs128 int8 mx fp8; do
   EXTRA=""; [ $c = fp8 ] && EXTRA="--fp8-layers 4"
   timeout 500 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/prof_cfg_${c}_fetch -o cfg -- $CFG_CMD --configs $c $EXTRA > $O/rocprof_cfg_${c}_fetch.log 2>&1
@@ -98,16 +98,16 @@ timeout 500 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCL
 ( cd $R; python scripts/pmc_mfma_summary.py $O/prof_gemm_pmc -o profiles/gemm8_p8_pmc_mfma_$ROUND.json --source "rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES ... -- tools/bench_8bit.py --which int8,fp8l --m 8192 (round 6: the persistent 256 x 256 form takes these shapes)" )
 find $O -name "*counter_collection.csv" -size +4M -delete 2>/dev/null; find $O -name "*kernel_trace.csv" -size +4M -delete 2>/dev/null
 cd $R
-echo "== full bench ==" ; ( time timeout 1200 python bench.py ) 2>$O/bench.err > $O/bench.json; tail -4 $O/bench.err; cut -c1-300 $O/bench.json; cp $O/bench.json $R/profiles/bench_$ROUND.json
+echo "== full bench ==" ; ( time timeout 1200 python bench.py --full ) 2>$O/bench.err > $O/bench.json; tail -4 $O/bench.err; cut -c1-300 $O/bench.json; cp $O/bench.json $R/profiles/bench_$ROUND.json
 echo "== pytest gpu ==" ; timeout 1200 python -m pytest tests -m gpu -q --timeout 600 --durations=15 2>&1 | tee $O/pytest_gpu.log | tail -4; cp $O/pytest_gpu.log $R/profiles/pytest_gpu_$ROUND.log
 echo "== smoke ==" ; timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2
-echo "== TP over RCCL, world 1 ==" ; timeout 400 python bench.py --force-tp --configs tp --no-second-layout --no-cpu-baseline --steps 5 2>$O/tp.err > $O/bench_tp.json; python -c "
+echo "== TP over RCCL, world 1 ==" ; timeout 400 python bench.py --full --force-tp --configs tp --no-second-layout --no-cpu-baseline --steps 5 2>$O/tp.err > $O/bench_tp.json; python -c "
 import json; d=json.loads(open('$O/bench_tp.json').read().strip().splitlines()[-1]); json.dump({'fp8_tp': d['configs']['fp8_tp']}, open('$R/profiles/bench_${ROUND}_tp_world1.json','w'), indent=1); print({k: round(v['per_gpu_TFLOPs']) for k, v in d['configs']['fp8_tp']['by_M'].items()})"
 echo "== N = 2 code path, dry run (two ranks sharing the GPU over gloo; numbers meaningless) =="
-AO_BENCH_ONE_SHOT=1 AO_BENCH_SHARE_GPU=1 AO_BENCH_BACKEND=gloo timeout 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29519 bench.py --gpus 2 --steps 5 --warmup 2 > $O/bench_n2_dryrun.json 2>$O/n2.err; cp $O/bench_n2_dryrun.json $R/profiles/bench_${ROUND}_n2_dryrun_gloo.json; python -c "
+AO_BENCH_ONE_SHOT=1 AO_BENCH_SHARE_GPU=1 AO_BENCH_BACKEND=gloo timeout 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29519 bench.py --full --gpus 2 --steps 5 --warmup 2 > $O/bench_n2_dryrun.json 2>$O/n2.err; cp $O/bench_n2_dryrun.json $R/profiles/bench_${ROUND}_n2_dryrun_gloo.json; python -c "
 import json; out=open('$O/bench_n2_dryrun.json').read().strip().splitlines(); d=json.loads(out[-1]); print('stdout lines', len(out), 'n_gpus', d['n_gpus'], 'fp8_tp keys', sorted(d['configs']['fp8_tp'].get('by_M', d['configs']['fp8_tp'])))"
 echo "== the watchdog: a TP leg that cannot finish in 1 s must still leave ONE line =="
-timeout 300 python bench.py --force-tp --configs tp --no-second-layout --no-cpu-baseline --steps 5 --tp-timeout 1 2>/dev/null | python -c "
+timeout 300 python bench.py --full --force-tp --configs tp --no-second-layout --no-cpu-baseline --steps 5 --tp-timeout 1 2>/dev/null | python -c "
 import sys, json; out=sys.stdin.read().strip().splitlines(); d=json.loads(out[-1]); print('lines', len(out), 'value', round(d['value']), 'fp8_tp', str(d['configs']['fp8_tp'])[:90])"
 mkdir -p $R/gpurun_out/profiles_out; cp $R/profiles/*_$ROUND* $R/gpurun_out/profiles_out/ 2>/dev/null
 du -sh $O

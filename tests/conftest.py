@@ -28,6 +28,15 @@ def pytest_collection_modifyitems(config, items):
             item.add_marker(skip)
 
 
+def require_gpu_processes(n):
+    """Skip, before any work, a test that would have n processes of its own on the GPU next to this one when that is more than the
+    node allows.  Shared GPU nodes cap how many processes may hold a device at once; AO_TEST_MAX_GPU_PROCS (default 6) is that cap,
+    the pytest process included.  A node of one's own can raise it to run the 8-rank single-GPU worlds."""
+    cap = int(os.environ.get("AO_TEST_MAX_GPU_PROCS", "6"))
+    if n + 1 > cap:
+        pytest.skip(f"needs {n + 1} processes on the GPU at once ({n} ranks and pytest), the node allows {cap} (AO_TEST_MAX_GPU_PROCS)")
+
+
 def bf16_bits_to_f32(b):
     return (np.asarray(b, dtype=np.uint16).astype(np.uint32) << 16).view(np.float32)
 

@@ -1,7 +1,5 @@
 """GPU: the EP dispatch on the HIP cast + RCCL (a world of one: the collective path is real, the exchange degenerate) and the
 pre-quantized-token entry of the grouped GEMM (reference: MXTensor input of _to_mxfp8_then_scaled_grouped_mm)."""
-import os
-import socket
 
 import numpy as np
 import pytest
@@ -15,18 +13,12 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
 
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
 @pytest.fixture()
 def world1():
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(_free_port())
+    # a world of one rendezvouses in memory: a TCP store would need a free port, which another process can take between
+    # looking it up and binding it
     torch.cuda.set_device(0)
-    dist.init_process_group("nccl", rank=0, world_size=1)
+    dist.init_process_group("nccl", store=dist.HashStore(), rank=0, world_size=1)
     try:
         yield
     finally:

@@ -18,8 +18,9 @@ import pytest
 import torch
 import torch.distributed as dist
 
+_N_GPUS = torch.cuda.device_count()
 pytestmark = [pytest.mark.gpu,
-              pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs >= 2 GPUs: one process per GPU over RCCL / xGMI")]
+              pytest.mark.skipif(_N_GPUS < 2, reason=f"needs >= 2 GPUs (one process per GPU over RCCL / xGMI), found {_N_GPUS}")]
 
 
 def _world():

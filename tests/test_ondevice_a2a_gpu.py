@@ -140,6 +140,9 @@ def _worker(rank, world, port, q):
 
 @pytest.mark.parametrize("world", [2, 4, 8])
 def test_on_device_all_to_all_v_processes_share_one_gpu(world):
+    from conftest import require_gpu_processes
+
+    require_gpu_processes(world)
     port = _free_port()
     ctx = mp.get_context("spawn")
     q = ctx.Queue()

@@ -138,6 +138,9 @@ def _run(world, target, args=(), timeout=600):
 
 @pytest.mark.parametrize("world", [2, 4, 8])
 def test_oneshot_allreduce_processes_share_one_gpu(world):
+    from conftest import require_gpu_processes
+
+    require_gpu_processes(world)
     for o in _run(world, _worker):
         assert "error" not in o, o
         assert o["ok"], f"one-shot set-up failed: {o['why']}"
