@@ -14,6 +14,15 @@ namespace ao {
 void set_error(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
 int hip_failed(hipError_t e, const char* what);  // sets message, returns AO_ERR_HIP
 
+// The A/B overrides of ao_int4_set_tuning (int4_kernels.hip; default-constructed: the product dispatch): waves per workgroup of the
+// per-tile kernel, the int4 mm's forced form (int4_forced_route), and the fp8-act x int4 forms of modes 961 - 974.
+struct Int4Force {
+  int wpb = 0, mode = 0;
+  int fp8_mt = 0;        // m-tiles per workgroup forced (1, 2, 4; 0 = by M)
+  bool fp8_nt1 = false;  // one n-tile per workgroup
+};
+const Int4Force& int4_force();  // the calling thread's
+
 // opt a kernel into > 48 KiB of dynamic LDS on the current device (once per kernel and device; runtime.hip)
 int ensure_dynamic_lds(const void* kernel, size_t bytes, const char* what);
 

@@ -23,13 +23,13 @@
 //     sees the same products in the same MFMA as before; rows >= M of the A operand alias row 0 (their outputs are never stored);
 //   * one barrier for the cross-wave reduction (wave order: reproducible), the reference's epilogues in fp32, bf16 out.
 #include "common.h"
+#include "gemm8_route.h"
 #include "quant_math.h"
 
 #include <algorithm>
 #include <type_traits>
 
 namespace ao {
-thread_local int g_dec8_mode = 0;  // ao_gemm8_set_variant 200 + d: force ring depth d; 290: half-line loads (no LDS transposition); 291 / 292: 8-row tiles never / always; 299: never this kernel
 namespace {
 
 typedef int i32x8 __attribute__((ext_vector_type(8)));
@@ -276,11 +276,6 @@ __global__ __launch_bounds__(1024) void dec8_kernel(Dec8Args p) {
   }
 }
 
-struct Dec8Shape {
-  int waves, depth;
-  bool loop;  // K does not factor: the ring is refilled in a loop (depth 4)
-};
-
 // K = 128 * depth * waves: the deepest ring of {8, 7, 4, 2, 1} that leaves at most 16 waves.  (Measured on the 70B / TP8 fp8 shards and the
 // Llama-3-8B int8 shapes, profiles/dec8_forms_r04.txt: the deeper ring wins at every K, down to ONE wave x 8 steps for K = 1024 --
 // fewer waves mean fewer partials to reduce and more workgroups per CU.)
@@ -307,14 +302,10 @@ size_t dec8_lds(int64_t M, int64_t K, int waves) {
   return (size_t)((M * (K + 16) + 15) & ~(int64_t)15) + (size_t)waves * kSlab + (size_t)(waves * 256 + waves * 16 + 16) * sizeof(float);
 }
 
-// 8-row tiles where 16-row tiles would leave more than half of the chip's CUs without a workgroup (N / 16 < 128) -- the straight-line
-// form with more than one wave only (a one-wave workgroup streams 1 KiB per step as it is)
-bool dec8_rows8(int64_t N, int waves) { return g_dec8_mode != 291 && (g_dec8_mode == 292 || N / 16 < 128) && N % 8 == 0 && waves >= 2; }
-
 template <bool INT8, bool DYN, int DEPTH, bool XFAST>
-int launch_dec8_h(const Dec8Args& p, int waves, bool half, hipStream_t stream) {
+int launch_dec8_h(const Dec8Args& p, int waves, bool half, bool rows8, hipStream_t stream) {
   const size_t smem = dec8_lds(p.M, p.K, waves);
-  if (!half && dec8_rows8(p.N, waves)) {
+  if (rows8) {
     auto kern = dec8_kernel<INT8, DYN, DEPTH, XFAST, false, false, true>;
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), smem, "hipFuncSetAttribute(dec8_kernel)")) return rc;
     ao::launch(kern, dim3((unsigned)(p.N / 8)), dim3(waves * 64), smem, stream, p);
@@ -344,10 +335,10 @@ template <bool INT8, bool DYN>
 int launch_dec8(const Dec8Args& p, const Dec8Shape& s, hipStream_t stream) {
   if (s.loop) return launch_dec8_loop<INT8, DYN>(p, s.waves, stream);
   const bool xfast = DYN ? (p.M == 1) : (p.M * s.depth * 8 <= kXV * 64);
-  const bool half = g_dec8_mode == 290;
 #define AO_DEC8_CASE(D)                                                                      \
   case D:                                                                                    \
-    return xfast ? launch_dec8_h<INT8, DYN, D, true>(p, s.waves, half, stream) : launch_dec8_h<INT8, DYN, D, false>(p, s.waves, half, stream);
+    return xfast ? launch_dec8_h<INT8, DYN, D, true>(p, s.waves, s.half, s.rows8, stream)        \
+                 : launch_dec8_h<INT8, DYN, D, false>(p, s.waves, s.half, s.rows8, stream);
   switch (s.depth) {
     AO_DEC8_CASE(8)
     AO_DEC8_CASE(7)
@@ -360,14 +351,17 @@ int launch_dec8(const Dec8Args& p, const Dec8Shape& s, hipStream_t stream) {
   return AO_ERR_INVALID_ARGUMENT;
 }
 
+}  // namespace
+
 // Whether the straight-line decode kernel takes this problem: M <= 16, the codes of the activation + the slabs within the CU's LDS,
 // K = 128 x depth x waves.  A function of the shape only, so that the fused (cast inside) and the two-launch forms of one linear pick
-// the same wave split and give the same bits.
-bool dec8_takes_shape(int64_t M, int64_t N, int64_t K, Dec8Shape* shape) {
-  if (g_dec8_mode == 299) return false;
+// the same wave split and give the same bits.  mode (ao_gemm8_set_variant): 200 + d force ring depth d; 290 half-line loads (no LDS
+// transposition); 291 / 292 8-row tiles never / always; 293 the round-4 bound of 64 KiB of codes; 299 never this kernel.
+bool dec8_plan(int64_t M, int64_t N, int64_t K, int mode, Dec8Shape* shape) {
+  if (mode == 299) return false;
   if (M < 1 || M > 16 || N % 16 != 0 || K % 128 != 0 || N >= (1ll << 31) || K >= (1ll << 24)) return false;
   Dec8Shape s;
-  const int forced = (g_dec8_mode > 200 && g_dec8_mode <= 208) ? g_dec8_mode - 200 : 0;
+  const int forced = (mode > 200 && mode <= 208) ? mode - 200 : 0;
   if (!dec8_shape(K, forced, &s)) return false;
   // Round 6: 9 .. 16 rows pick the ring by occupancy.  The deepest ring (round 4's rule, measured at M = 1) means the fewest waves per workgroup;
   // with many rows the activation codes cap the workgroups per CU, and on narrow weights there are few workgroups to begin with -- o shard
@@ -381,7 +375,7 @@ bool dec8_takes_shape(int64_t M, int64_t N, int64_t K, Dec8Shape* shape) {
   // profiles/dec8_small_m_forms_r06.jsonl (fp8, cold, 20 shapes, M = 6 / 8): o shard 8192 x 1024 4.5 / 4.7 -> 3.9 us, 8192 x 2048 6.1 / 6.3 ->
   // 5.2 / 5.3, qkv shard 1280 x 8192 5.3 / 5.4 -> 4.9 / 5.1, gate_up shard at 8 rows 15.4 -> 14.2 (at 6: 13.4 -> 14.0, the one cell behind),
   // 37888 x 3584 at 8 rows 28.6 -> 25.6; level elsewhere.  Up to 4 rows the deepest ring is ahead on every shape (round 4's rule holds).
-  if (forced == 0 && !s.loop && M >= 5 && M <= 8 && M * s.depth > 32 && g_dec8_mode != 293) {
+  if (forced == 0 && !s.loop && M >= 5 && M <= 8 && M * s.depth > 32 && mode != 293) {
     const int ksteps = (int)(K / 128);
     static const int depths[] = {8, 7, 4, 2, 1};
     for (int d : depths) {
@@ -392,7 +386,7 @@ bool dec8_takes_shape(int64_t M, int64_t N, int64_t K, Dec8Shape* shape) {
       break;
     }
   }
-  if (forced == 0 && !s.loop && M >= 9 && g_dec8_mode != 293) {
+  if (forced == 0 && !s.loop && M >= 9 && mode != 293) {
     const int ksteps = (int)(K / 128);
     const int64_t wgs = N / 16, offered = std::max<int64_t>(1, wgs / 256);
     static const int depths[] = {8, 7, 4, 2, 1};
@@ -430,39 +424,29 @@ bool dec8_takes_shape(int64_t M, int64_t N, int64_t K, Dec8Shape* shape) {
   // codes (the fused-cast kernel's bound; variant 293 keeps it for A/B), which sent M = 8 .. 16 on K = 8192 to the per-tile streaming kernel:
   // qkv shard 1280 x 8192 9.1 - 10.6 us -> 5.6 - 6.4, gate_up shard 19 - 21 -> 15.6 - 17.5, qkv 6144 x 4096 at M = 16 11.8 -> 8.9,
   // down 4096 x 14336 at M = 4 .. 8 16.3 - 17.3 -> 12.8 - 15.7, no cell slower (profiles/dec8_lds_cap_ab_r06.jsonl, cold weights, same bits)
-  if (g_dec8_mode == 293) {
+  if (mode == 293) {
     if (dec8_lds(M, K, s.waves) > 64 * 1024 + 24 * 1024 || M * (K + 16) > 64 * 1024) return false;
   } else if (dec8_lds(M, K, s.waves) > 160 * 1024) {
     return false;
   }
-  if (shape != nullptr) *shape = s;
+  s.half = mode == 290;
+  // 8-row tiles where 16-row tiles would leave more than half of the chip's CUs without a workgroup (N / 16 < 128) -- the straight-line
+  // form with more than one wave only (a one-wave workgroup streams 1 KiB per step as it is)
+  s.rows8 = !s.half && !s.loop && mode != 291 && (mode == 292 || N / 16 < 128) && N % 8 == 0 && s.waves >= 2;
+  *shape = s;
   return true;
 }
 
-}  // namespace
-
-bool dec8_takes(int64_t M, int64_t N, int64_t K) { return dec8_takes_shape(M, N, K, nullptr); }
-
 // xq . wq^T with the scale epilogue, activation already cast (aten::_int_mm + scales / aten::_scaled_mm rowwise at decode sizes)
 int dec8_scaled(bool int8, const void* xq, const float* x_scale, const void* wq, const float* w_scale, const uint16_t* bias, uint16_t* y,
-                int64_t M, int64_t N, int64_t K, hipStream_t stream) {
-  Dec8Shape s;
-  if (!dec8_takes_shape(M, N, K, &s)) {
-    set_error("dec8_scaled: shape M=%lld N=%lld K=%lld not covered", (long long)M, (long long)N, (long long)K);
-    return AO_ERR_INVALID_ARGUMENT;
-  }
+                int64_t M, int64_t N, int64_t K, const Dec8Shape& s, hipStream_t stream) {
   Dec8Args p{xq, x_scale, reinterpret_cast<const uint8_t*>(wq), w_scale, bias, y, (int)M, (int)N, (int)K};
   return int8 ? launch_dec8<true, false>(p, s, stream) : launch_dec8<false, false>(p, s, stream);
 }
 
 // the dynamic-activation linear with the cast fused in
 int dec8_dynamic(bool int8, const uint16_t* x, const void* wq, const float* w_scale, const uint16_t* bias, uint16_t* y, int64_t M, int64_t N,
-                 int64_t K, hipStream_t stream) {
-  Dec8Shape s;
-  if (!dec8_takes_shape(M, N, K, &s)) {
-    set_error("dec8_dynamic: shape M=%lld N=%lld K=%lld not covered", (long long)M, (long long)N, (long long)K);
-    return AO_ERR_INVALID_ARGUMENT;
-  }
+                 int64_t K, const Dec8Shape& s, hipStream_t stream) {
   Dec8Args p{x, nullptr, reinterpret_cast<const uint8_t*>(wq), w_scale, bias, y, (int)M, (int)N, (int)K};
   return int8 ? launch_dec8<true, true>(p, s, stream) : launch_dec8<false, true>(p, s, stream);
 }

@@ -12,19 +12,18 @@
 // its MFMAs from there; rows are K + 16 bytes apart so that the 16-byte operand reads of different rows hit different
 // banks.  Same bits as cast + matmul (int8 bit-exact end to end).
 #include "common.h"
+#include "gemm8_route.h"
 #include "quant_math.h"
 
 #include <algorithm>
 
 namespace ao {
 // dec8_kernels.hip (round 4): the same linear with the weights as full lines in a register ring and the cast under their flight
-bool dec8_takes(int64_t M, int64_t N, int64_t K);
 int dec8_dynamic(bool int8, const uint16_t* x, const void* wq, const float* w_scale, const uint16_t* bias, uint16_t* y, int64_t M, int64_t N,
-                 int64_t K, hipStream_t stream);
+                 int64_t K, const Dec8Shape& s, hipStream_t stream);
 // mid8_kernels.hip (round 4): 16 < M <= 256 with few output tiles -- the per-row cast shared out among the workgroups of the same launch
-bool mid8_takes_fused(int64_t M, int64_t N, int64_t K);
 int mid8_dynamic(bool int8, const uint16_t* x, const void* b, const float* scale_b, const uint16_t* bias, uint16_t* y, int64_t M, int64_t N, int64_t K,
-                 hipStream_t stream);
+                 const Mid8Plan& plan, hipStream_t stream);
 namespace {
 
 typedef int i32x8 __attribute__((ext_vector_type(8)));
@@ -149,14 +148,25 @@ int launch_dyn8(const Dyn8Args& p, hipStream_t stream) {
   return AO_OK;
 }
 
-int check_dyn(const char* fn, int64_t M, int64_t N, int64_t K) {
+// validates the shape and routes it once (*r: the route of the calling thread's overrides)
+int check_dyn(const char* fn, bool int8, int64_t M, int64_t N, int64_t K, Gemm8Route* r) {
   AO_REQUIRE(M >= 0 && N > 0 && K > 0, "%s: bad shape M=%lld N=%lld K=%lld", fn, (long long)M, (long long)N, (long long)K);
   AO_REQUIRE(N % 16 == 0 && K % 128 == 0, "%s: N=%lld must be a multiple of 16 and K=%lld of 128", fn, (long long)N, (long long)K);
-  AO_REQUIRE((M <= kMaxRows && M * (K + 16) <= 64 * 1024) || (M > kMaxRows && mid8_takes_fused(M, N, K)),
+  *r = gemm8_route(int8 ? Gemm8Entry::Int8Dyn : Gemm8Entry::Fp8Dyn, M, N, K, true, gemm8_force());
+  AO_REQUIRE(M == 0 || r->kernel != Gemm8Kernel::Invalid,
              "%s: the fused form holds the cast activation in LDS: M <= 16 and M * (K + 16) <= 65536 (or 16 < M <= 256 on a weight with "
              "few output tiles and K %% 512 == 0), got M=%lld K=%lld (use the cast + matmul entry points)", fn, (long long)M, (long long)K);
   AO_REQUIRE(N < (1ll << 31) && K < (1ll << 31), "%s: dimension too large", fn);
   return AO_OK;
+}
+
+template <bool INT8>
+int dyn_linear(const Gemm8Route& r, const uint16_t* x, const uint8_t* wq, const float* w_scale, const uint16_t* bias, uint16_t* y, int64_t M,
+               int64_t N, int64_t K, hipStream_t stream) {
+  if (r.kernel == Gemm8Kernel::Mid8) return mid8_dynamic(INT8, x, wq, w_scale, bias, y, M, N, K, r.mid, stream);
+  if (r.kernel == Gemm8Kernel::Dec8) return dec8_dynamic(INT8, x, wq, w_scale, bias, y, M, N, K, r.dec, stream);
+  Dyn8Args p{x, wq, w_scale, bias, y, (int)M, (int)N, (int)K};
+  return launch_dyn8<INT8>(p, stream);
 }
 
 }  // namespace
@@ -165,34 +175,29 @@ int check_dyn(const char* fn, int64_t M, int64_t N, int64_t K) {
 using namespace ao;
 
 extern "C" int ao_dyn_linear_fits(int64_t M, int64_t N, int64_t K) {
-  if (M > kMaxRows) return mid8_takes_fused(M, N, K) ? 1 : 0;
-  return (M > 0 && M <= kMaxRows && M * (K + 16) <= 64 * 1024 && N % 16 == 0 && K % 128 == 0) ? 1 : 0;
+  return gemm8_route(Gemm8Entry::Int8Dyn, M, N, K, true, gemm8_force()).kernel != Gemm8Kernel::Invalid ? 1 : 0;
 }
 
 extern "C" int ao_int8_dynamic_linear(const uint16_t* x, const int8_t* wq, const float* w_scale, const uint16_t* bias, uint16_t* y,
                                       int64_t M, int64_t N, int64_t K, void* stream) {
-  if (int rc = check_dyn(__func__, M, N, K)) return rc;
+  Gemm8Route r;
+  if (int rc = check_dyn(__func__, true, M, N, K, &r)) return rc;
   if (M == 0) return AO_OK;
   AO_REQUIRE_PTR(x);
   AO_REQUIRE_PTR(wq);
   AO_REQUIRE_PTR(w_scale);
   AO_REQUIRE_PTR(y);
-  if (M > kMaxRows) return mid8_dynamic(true, x, wq, w_scale, bias, y, M, N, K, (hipStream_t)stream);
-  if (dec8_takes(M, N, K)) return dec8_dynamic(true, x, wq, w_scale, bias, y, M, N, K, (hipStream_t)stream);
-  Dyn8Args p{x, reinterpret_cast<const uint8_t*>(wq), w_scale, bias, y, (int)M, (int)N, (int)K};
-  return launch_dyn8<true>(p, (hipStream_t)stream);
+  return dyn_linear<true>(r, x, reinterpret_cast<const uint8_t*>(wq), w_scale, bias, y, M, N, K, (hipStream_t)stream);
 }
 
 extern "C" int ao_fp8_dynamic_linear(const uint16_t* x, const uint8_t* wq, const float* w_scale, const uint16_t* bias, uint16_t* y,
                                      int64_t M, int64_t N, int64_t K, void* stream) {
-  if (int rc = check_dyn(__func__, M, N, K)) return rc;
+  Gemm8Route r;
+  if (int rc = check_dyn(__func__, false, M, N, K, &r)) return rc;
   if (M == 0) return AO_OK;
   AO_REQUIRE_PTR(x);
   AO_REQUIRE_PTR(wq);
   AO_REQUIRE_PTR(w_scale);
   AO_REQUIRE_PTR(y);
-  if (M > kMaxRows) return mid8_dynamic(false, x, wq, w_scale, bias, y, M, N, K, (hipStream_t)stream);
-  if (dec8_takes(M, N, K)) return dec8_dynamic(false, x, wq, w_scale, bias, y, M, N, K, (hipStream_t)stream);
-  Dyn8Args p{x, wq, w_scale, bias, y, (int)M, (int)N, (int)K};
-  return launch_dyn8<false>(p, (hipStream_t)stream);
+  return dyn_linear<false>(r, x, wq, w_scale, bias, y, M, N, K, (hipStream_t)stream);
 }

@@ -26,8 +26,6 @@ namespace ao {
 namespace {
 
 typedef long i64_t;
-thread_local int g_fp8_int4_mt = 0;  // A/B: m-tiles per workgroup forced (1, 2, 4); 0 = by M
-thread_local bool g_fp8_int4_nt1 = false;  // A/B: one n-tile per workgroup
 
 // FUSE (round 4, SURVEY 8 f1 for this path): the per-row e4m3 cast of the activation inside the launch -- x arrives as bf16 [M][K]
 // (M <= 16, M (K + 16) <= 64 KiB), is cast ONCE per workgroup into an LDS copy of the codes with quant_math.h's arithmetic (the bits of
@@ -316,10 +314,11 @@ int launch_fp8_int4(const uint8_t* xq, const float* x_scale, const int32_t* qdat
     // (down_proj 4096 x 14336 at M = 128 / 256 / 512: 47.4 -> 33.8, 90.4 -> 67.0, 177 -> 132; qkv at M = 512 76.4 -> 73.5; at M <= 64 on
     // K = 4096 the halved grid costs 1 us).  Four m-tiles x one n-tile (2-deep ring: the x stages of a deeper one cost the occupancy;
     // 3-deep measured 5 - 12 % slower) lose to 2 x 2 in every cell from 64 rows and stay a tuning form; 4 x 2 spills.
-    // g_fp8_int4_mt / g_fp8_int4_nt1 (ao_int4_set_tuning modes 961 / 962 / 964, 972 / 974) force a form for A/B runs.
-    const bool forced = g_fp8_int4_mt == 1 || g_fp8_int4_mt == 2 || g_fp8_int4_mt == 4;
-    const int mt = forced ? g_fp8_int4_mt : fp8_int4_m_tiles(M);
-    const bool nt2 = forced ? ((N % 32 == 0) && !g_fp8_int4_nt1) : (!g_fp8_int4_nt1 && fp8_int4_n_tiles(M, N, K, G) == 2);
+    // Int4Force::fp8_mt / fp8_nt1 (ao_int4_set_tuning modes 961 / 962 / 964, 970 / 972 / 974) force a form for A/B runs.
+    const Int4Force& f = int4_force();
+    const bool forced = f.fp8_mt == 1 || f.fp8_mt == 2 || f.fp8_mt == 4;
+    const int mt = forced ? f.fp8_mt : fp8_int4_m_tiles(M);
+    const bool nt2 = forced ? ((N % 32 == 0) && !f.fp8_nt1) : (!f.fp8_nt1 && fp8_int4_n_tiles(M, N, K, G) == 2);
     const size_t slab = (size_t)wpb * 16 * (128 + 16), redb = (size_t)wpb * 1024;
     auto go = [&](auto kern, int mtv, int ntv) -> int {
       const size_t sm = slab * mtv + redb * mtv * ntv;
@@ -365,7 +364,6 @@ int fp8_int4_check(const char* fn, int64_t M, int64_t N, int64_t K, int group_si
 }
 
 }  // namespace
-void fp8_int4_set_mt(int mt, bool nt1) { g_fp8_int4_mt = mt; g_fp8_int4_nt1 = nt1; }
 }  // namespace ao
 
 using namespace ao;

@@ -11,48 +11,21 @@
 // K step.  4 waves as 2x2, each 64x64 = 2x2 MFMA tiles of 32x32.
 // The epilogue applies the reference's scaling sequence in registers and stores
 // bf16 (or raw int32 for _int_mm).
-#include <string>
-
 #include "common.h"
+#include "gemm8_route.h"
 
 namespace ao {
-bool gemm8_p8_fits(int64_t M, int64_t N, int64_t K);  // gemm8_p8_kernels.hip (epi numbering = enum Epilogue)
-void gemm8_p8_set_group_rows(int v);
-void gemm8_p8_set_split(int v);
-void gemm8_p8_set_persistent(int v);
-bool gemm8_p8_persistent_shape(int64_t M, int64_t N, int64_t K);  // the persistent form's product rule (shape part; 16-byte-aligned scales assumed)
-void gemm8_p8h_set_form(int v);
+// the launchers: each takes the launch shape gemm8_route picked (epi numbering of gemm8_p8 / gemm8_p8h = enum Epilogue)
 int gemm8_p8(int epi, const uint8_t* a, const uint8_t* b, const float* row_scale, const float* col_scale, const uint16_t* bias, void* out,
-             int64_t M, int64_t N, int64_t K, hipStream_t stream);
-
-// rb8_kernels.hip: weight-streaming kernels for problems with few output tiles
+             int64_t M, int64_t N, int64_t K, bool persistent, hipStream_t stream);  // gemm8_p8_kernels.hip
 int gemm8_p8h(int epi, const uint8_t* a, const uint8_t* b, const float* row_scale, const float* col_scale, const uint16_t* bias, void* out,
-              int64_t M, int64_t N, int64_t K, hipStream_t stream);
-bool gemm8_p8h_band(int64_t M, int64_t N, int64_t K);
-int gemm8_p8h_parts(int64_t M, int64_t N, int64_t K);
-void rb8_plan_query(int64_t M, int64_t N, int64_t K, int* bm, int* bn, int* split);
-bool fp8_rowwise_rb_preferred(int64_t M, int64_t N, int64_t K);
-bool rb8_small_m_preferred(int64_t M, int64_t N, int64_t K);  // rb8_kernels.hip: 8 .. 64 rows on weights the decode kernels leave
-void rb8_set_wave_grid(bool two_by_four);  // rb8_kernels.hip
-void rb8_set_tuning(int bn, int split, int ablate);
-void rb8_set_slab_rows(int rows);
-void fp8_rowwise_rb_set_mode(int mode);
-bool fp8_rowwise_rb_forced();
-extern thread_local int g_mx_variant;  // stream8_kernels.hip
-extern thread_local int g_dec8_mode;   // dec8_kernels.hip
-extern thread_local int g_mid8_mode;   // mid8_kernels.hip
-bool mid8_takes(int64_t M, int64_t N, int64_t K);
+              int64_t M, int64_t N, int64_t K, int split, hipStream_t stream);
+int rb8_scaled(bool int8, const void* a, const void* b, const float* scale_a, const float* scale_b, const uint16_t* bias, uint16_t* y, int64_t M,
+               int64_t N, int64_t K, int bm, int bn, int split, hipStream_t stream);  // rb8_kernels.hip
 int mid8_scaled(bool int8, const void* a, const float* scale_a, const void* b, const float* scale_b, const uint16_t* bias, uint16_t* y, int64_t M,
-                int64_t N, int64_t K, hipStream_t stream);
-bool dec8_takes(int64_t M, int64_t N, int64_t K);
+                int64_t N, int64_t K, const Mid8Plan& plan, hipStream_t stream);  // mid8_kernels.hip
 int dec8_scaled(bool int8, const void* xq, const float* x_scale, const void* wq, const float* w_scale, const uint16_t* bias, uint16_t* y,
-                int64_t M, int64_t N, int64_t K, hipStream_t stream);
-void mx_rb_set_stream(int mode, bool quad);
-void mx_stream_set_tuning(int proto);
-int fp8_rowwise_rb(const uint8_t* a, const uint8_t* b, const float* scale_a, const float* scale_b, const uint16_t* bias, uint16_t* y,
-                   int64_t M, int64_t N, int64_t K, hipStream_t stream);
-int int8_scaled_rb(const int8_t* a, const int8_t* b, const float* scale_a, const float* scale_b, const uint16_t* bias, uint16_t* y,
-                   int64_t M, int64_t N, int64_t K, hipStream_t stream);
+                int64_t M, int64_t N, int64_t K, const Dec8Shape& s, hipStream_t stream);  // dec8_kernels.hip
 int int8_scaled_stream(const int8_t* a, const int8_t* b, const float* scale_a, const float* scale_b, const uint16_t* bias, uint16_t* y,
                        int64_t M, int64_t N, int64_t K, hipStream_t stream);
 int fp8_rowwise_stream(const uint8_t* a, const uint8_t* b, const float* scale_a, const float* scale_b,
@@ -393,13 +366,8 @@ __global__ __launch_bounds__(128 * WN) void gemm8_dma_kernel(Gemm8Args p) {
     }
 }
 
-thread_local bool g_gemm8_force_regstage = false;  // profiling: ao_gemm8_set_variant(1)
-thread_local bool g_gemm8_tiled_only = false;      // profiling / A-B tests: ao_gemm8_set_variant(100) -- never a weight-streaming kernel
-
-thread_local int g_gemm8_tm = 0;  // profiling: 0 = by shape, 2 / 4 = force
-
 template <int EPI, int TM, int WN, int TNJ = 2>
-int launch_gemm8_dma_tm(const Gemm8Args& p, hipStream_t stream) {
+int launch_gemm8_dma(const Gemm8Args& p, hipStream_t stream) {
   constexpr int WGM = TM * 64, WGN = WN * TNJ * 32;
   dim3 grid((unsigned)((p.N + WGN - 1) / WGN), (unsigned)((p.M + WGM - 1) / WGM)), block(128 * WN);
   const size_t smem = 2 * (size_t)(WGM + WGN) * BK;  // 64 KiB (128 x 128) ... 128 KiB (256 x 256)
@@ -409,44 +377,64 @@ int launch_gemm8_dma_tm(const Gemm8Args& p, hipStream_t stream) {
   return AO_OK;
 }
 
-// the shapes the phase-interleaved 256 x 256 kernel takes from the two-stage tile kernels (product rule; see launch_gemm8_dma)
+// the tiled GEMMs: the kernel of a route that reached the tiled forms
+template <int EPI>
+int launch_gemm8(const Gemm8Route& r, const Gemm8Args& p, hipStream_t stream) {
+  switch (r.kernel) {
+    case Gemm8Kernel::Dma128: return launch_gemm8_dma<EPI, 2, 2>(p, stream);
+    case Gemm8Kernel::Dma256: return launch_gemm8_dma<EPI, 4, 4>(p, stream);
+    case Gemm8Kernel::Dma256x128: return launch_gemm8_dma<EPI, 4, 2>(p, stream);
+    case Gemm8Kernel::Dma256x256w4: return launch_gemm8_dma<EPI, 4, 2, 4>(p, stream);
+    case Gemm8Kernel::P8h: return gemm8_p8h((int)EPI, p.a, p.b, p.row_scale, p.col_scale, p.bias, p.out, p.M, p.N, p.K, r.k_parts, stream);
+    case Gemm8Kernel::P8:
+    case Gemm8Kernel::P8p:
+      return gemm8_p8((int)EPI, p.a, p.b, p.row_scale, p.col_scale, p.bias, p.out, p.M, p.N, p.K, r.kernel == Gemm8Kernel::P8p, stream);
+    case Gemm8Kernel::RegStage: {
+      dim3 grid((unsigned)((p.N + BN - 1) / BN), (unsigned)((p.M + BM - 1) / BM)), block(THREADS);
+      const size_t smem = 2 * 2 * TILE_BYTES;  // 73,728 B
+      if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(gemm8_kernel<EPI>), smem, "hipFuncSetAttribute(gemm8_kernel)")) return rc;
+      ao::launch(gemm8_kernel<EPI>, grid, block, smem, stream, p);
+      AO_LAUNCH_CHECK("gemm8_kernel launch");
+      return AO_OK;
+    }
+    default:
+      set_error("gemm8: M=%d N=%d K=%d routed to no tiled kernel", p.M, p.N, p.K);
+      return AO_ERR_INVALID_ARGUMENT;
+  }
+}
+
+// the shapes the phase-interleaved 256 x 256 kernel takes from the two-stage tile kernels (product rule; see tiled_route)
 bool gemm8_p8_band(int64_t M, int64_t N, int64_t K) {
   const int64_t big = ((N + 255) / 256) * ((M + 255) / 256), t128 = ((N + 127) / 128) * ((M + 127) / 128);
   return big >= 160 || (big >= 128 && (K <= 4096 || t128 > 512));
 }
 
-template <int EPI>
-int launch_gemm8_dma(const Gemm8Args& p, hipStream_t stream) {
-  // variants (ao_gemm8_set_variant): 2 = 128 x 128 tile / 4 waves; 4 = 256 x 128 / 4 waves (one wave per SIMD:
-  // measured 0.75-0.95x, nothing hides its ds_read -> MFMA latency); 8 = 256 x 256 / 8 waves.
-  if (g_gemm8_tm == 4) return launch_gemm8_dma_tm<EPI, 4, 2>(p, stream);
-  if (g_gemm8_tm == 16) return launch_gemm8_dma_tm<EPI, 4, 2, 4>(p, stream);  // 256 x 256, 4 waves of 128 x 128
+// The tiled GEMMs (every entry's last resort; the only path of the raw entries).  Variants: 1 the register-staged kernel; 2 / 4 / 8 / 16 the
+// LDS-DMA kernel with 128 x 128 / 256 x 128 (4 waves: one wave per SIMD, measured 0.75-0.95x, nothing hides its ds_read -> MFMA latency) /
+// 256 x 256 (8 waves) / 256 x 256 (4 waves of 128 x 128) tiles; 32 / 33 the phase-interleaved 256 x 256 / 256 x 128 kernels.
+Gemm8Route tiled_route(int64_t M, int64_t N, int64_t K, bool aligned, const Gemm8Force& f) {
+  if (K % BK != 0 || f.regstage) return Gemm8Route{Gemm8Kernel::RegStage, 128, 128};  // the LDS-DMA kernels need K % 128 == 0
+  if (f.tile == 4) return Gemm8Route{Gemm8Kernel::Dma256x128, 256, 128};
+  if (f.tile == 16) return Gemm8Route{Gemm8Kernel::Dma256x256w4, 256, 256};
   // (A 4-stage, 64-byte-K-step pipeline with hand-counted vmcnt was measured at 0.94-0.97x of these two-stage
   // kernels at both tile shapes, profiles/bench_8bit_r01_gemm.txt: the loop is LDS-read bound, not latency bound.)
-  const int64_t big = (int64_t)((p.N + 255) / 256) * ((p.M + 255) / 256);
-  // The phase-interleaved 256 x 256 kernel (gemm8_p8_kernels.hip; variant 32 forces it) once the problem has >= 160 such tiles.
+  const int64_t big = ((N + 255) / 256) * ((M + 255) / 256);
+  // The phase-interleaved 256 x 256 kernel (gemm8_p8_kernels.hip) once the problem has >= 160 such tiles.
   // Measured on the Llama-3-8B shapes (profiles/gemm8_variants_r02.txt, TOP/s int8, this kernel vs the two-stage kernels):
   // M = 8192: 2046 / 2084 / 2492 / 2796 vs 1557 / 1508 / 1777 / 2153; M = 2048: qkv (192 tiles) 1832 vs 1210, gate_up 2148 vs 1566,
   // but o / down (128 tiles: half the CUs idle) 1350 / 1710 vs 1330 / 1834; M = 512: gate_up (224 tiles) 2122 vs 1231.
   // Round 4 (profiles/gemm8_p8_band_r04.jsonl, cold weights): at 128 .. 159 such tiles it also wins while K <= 4096 (1024 x 8192 x 1024: 24.3 -> 20.2 us;
   // K = 8192 / 14336: 2 - 7 % behind) and whenever the 128 x 128 grid would need a second round of the chip (> 512 tiles: 1280 x 7168 x 8192 129 -> 84 us)
-  if ((g_gemm8_tm == 33 && gemm8_p8_fits(p.M, p.N, p.K)) || (g_gemm8_tm == 0 && gemm8_p8h_band(p.M, p.N, p.K)))  // the 256 x 128 phase-interleaved form (33 forces it)
-    return gemm8_p8h((int)EPI, p.a, p.b, p.row_scale, p.col_scale, p.bias, p.out, p.M, p.N, p.K, stream);
-  if ((g_gemm8_tm == 32 || (g_gemm8_tm == 0 && gemm8_p8_band(p.M, p.N, p.K))) && gemm8_p8_fits(p.M, p.N, p.K))
-    return gemm8_p8((int)EPI, p.a, p.b, p.row_scale, p.col_scale, p.bias, p.out, p.M, p.N, p.K, stream);
-  if (g_gemm8_tm == 8 || (g_gemm8_tm == 0 && big >= 512)) return launch_gemm8_dma_tm<EPI, 4, 4>(p, stream);
-  return launch_gemm8_dma_tm<EPI, 2, 2>(p, stream);
-}
-
-template <int EPI>
-int launch_gemm8(const Gemm8Args& p, hipStream_t stream) {
-  if (p.K % BK == 0 && !g_gemm8_force_regstage) return launch_gemm8_dma<EPI>(p, stream);  // K % 128 == 0 (the pipelined kernels need K % 64)
-  dim3 grid((unsigned)((p.N + BN - 1) / BN), (unsigned)((p.M + BM - 1) / BM)), block(THREADS);
-  const size_t smem = 2 * 2 * TILE_BYTES;  // 73,728 B
-  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(gemm8_kernel<EPI>), smem, "hipFuncSetAttribute(gemm8_kernel)")) return rc;
-  ao::launch(gemm8_kernel<EPI>, grid, block, smem, stream, p);
-  AO_LAUNCH_CHECK("gemm8_kernel launch");
-  return AO_OK;
+  if ((f.tile == 33 && gemm8_p8_fits(M, N, K)) || (f.tile == 0 && gemm8_p8h_band(M, N, K)))  // the 256 x 128 form
+    return Gemm8Route{Gemm8Kernel::P8h, 256, 128, gemm8_p8h_parts(M, N, K, f.p8_split)};
+  if ((f.tile == 32 || (f.tile == 0 && gemm8_p8_band(M, N, K))) && gemm8_p8_fits(M, N, K)) {
+    // the persistent form (tuning key 6: 1 never, 2 wherever the shape allows) needs full tiles and aligned scales / output
+    const bool full = M % 256 == 0 && N % 256 == 0 && K >= 256;
+    const bool persistent = f.p8_persist != 1 && aligned && full && (f.p8_persist == 2 || gemm8_p8_persistent_shape(M, N, K));
+    return Gemm8Route{persistent ? Gemm8Kernel::P8p : Gemm8Kernel::P8, 256, 256};
+  }
+  if (f.tile == 8 || (f.tile == 0 && big >= 512)) return Gemm8Route{Gemm8Kernel::Dma256, 256, 256};
+  return Gemm8Route{Gemm8Kernel::Dma128, 128, 128};
 }
 
 int check_gemm_shape(const char* fn, int64_t M, int64_t N, int64_t K) {
@@ -457,42 +445,149 @@ int check_gemm_shape(const char* fn, int64_t M, int64_t N, int64_t K) {
   return AO_OK;
 }
 
+bool aligned16(const void* row_scale, const void* col_scale, const void* bias, const void* out) {
+  return (((uintptr_t)row_scale | (uintptr_t)col_scale | (uintptr_t)out) & 15) == 0 && ((uintptr_t)bias & 3) == 0;
+}
+
+thread_local Gemm8Force g_force;  // ao_gemm8_set_variant / ao_gemm8_set_tuning
+
 }  // namespace
+
+const Gemm8Force& gemm8_force() { return g_force; }
+
+Gemm8Route gemm8_route(Gemm8Entry entry, int64_t M, int64_t N, int64_t K, bool aligned, const Gemm8Force& f) {
+  const Gemm8Route invalid{};
+  if (M <= 0 || N <= 0 || K <= 0 || K % 16 != 0) return invalid;
+  Gemm8Route r;  // the per-tile streaming kernels: 16-wide n-tiles, K split among the waves of a workgroup
+  switch (entry) {
+    case Gemm8Entry::Int32Raw:
+    case Gemm8Entry::Fp8Raw:
+      return tiled_route(M, N, K, aligned, f);
+    case Gemm8Entry::Int8Dyn:
+    case Gemm8Entry::Fp8Dyn:
+      // the fused form holds the cast activation in LDS: up to 16 rows of at most 64 KiB of codes (the decode kernel, else the round-3
+      // GEMV), or 16 < M <= 256 through the mid-M kernel (two launches; K <= 16384)
+      if (N % 16 != 0 || K % 128 != 0) return invalid;
+      if (M <= 16) {
+        if (M * (K + 16) > 64 * 1024) return invalid;
+        r.kernel = dec8_plan(M, N, K, f.dec8, &r.dec) ? Gemm8Kernel::Dec8 : Gemm8Kernel::Dyn8;
+        return r;
+      }
+      if (K > 16384 || !mid8_plan(M, N, K, f.mid8, &r.mid)) return invalid;
+      r.kernel = Gemm8Kernel::Mid8;
+      return r;
+    case Gemm8Entry::Int8Scaled:
+    case Gemm8Entry::Fp8Scaled:
+      break;
+  }
+  const bool int8 = entry == Gemm8Entry::Int8Scaled;
+  if (!int8 && N % 16 != 0) return invalid;
+  // Weight-bandwidth-bound sizes stream the weights once instead of tiling a GEMM (Llama-70B TP8 shards, us per call,
+  // profiles/bench_8bit_r01_fp8.jsonl):
+  //   * M <= 16: the straight-line decode kernel; 16 < M <= 256, few output tiles, long K: the register-ring mid-M kernel (round 4);
+  //   * M <= 32: stream8_kernels.hip -- activations straight from L2 per wave, no LDS staging, no split-K
+  //     (gate_up 7168x8192: 15 us at M = 1, 20 at 16; the LDS-staged kernel below needs 23);
+  //   * 32 < M and too few 128 x 128 tiles to fill the chip: rb8_kernels.hip (24 us at M = 64 where the kernel above
+  //     needs 40; 27 us at M = 128 where the tiled GEMM needs 55); Llama-3-8B down_proj at M = 1 took 77 us through the tiled GEMM;
+  //   * otherwise the tiled LDS-DMA GEMM.
+  // Variants: 100 never a weight-streaming kernel; 101 / 102 always rb8 where the shape allows; an explicit tile variant never rb8.
+  const bool rb_forced = f.rb >= 2, streaming = !rb_forced && !f.tiled_only, by_shape = !f.tiled_only && f.tile == 0 && !f.regstage;
+  if (M <= 16 && streaming && dec8_plan(M, N, K, f.dec8, &r.dec)) {
+    r.kernel = Gemm8Kernel::Dec8;
+    return r;
+  }
+  if (M > 16 && streaming && by_shape && mid8_plan(M, N, K, f.mid8, &r.mid)) {
+    r.kernel = Gemm8Kernel::Mid8;
+    return r;
+  }
+  const bool rb_small = by_shape && rb8_small_m_preferred(M, N, K, f.rb);  // round 6
+  bool rb;
+  if (int8) {
+    if (N % 16 == 0 && K % 128 == 0 && M <= 32 && !rb_small && streaming) r.kernel = Gemm8Kernel::Stream8;
+    rb = N % 16 == 0 && (rb_small || rb8_preferred(M, N, K, f.rb));
+  } else {
+    // (at 32 < M <= 64 rb8 only wins once K is long enough to amortise its start-up and split-K meeting: o_proj shard 8192x1024 8.5 vs 10.9 us)
+    // (round 4, cold weights -- every call of the replay reads another copy: the LDS-staged kernel wins from 33 rows on at every K of the
+    // 70B / TP8 shards, down 8192 x 3584 at M = 64: 14.0 us against 20.9 through the per-tile kernel, o 8192 x 1024: 8.5 against 9.2; the
+    // round-1 rule -- "only from K >= 4096 at 32 < M <= 64" -- had been measured on ONE re-used weight, i.e. out of the Infinity Cache)
+    rb = rb_small || (rb8_preferred(M, N, K, f.rb) && (M > 32 || rb_forced));
+    if (K % 128 == 0 && ((M <= 32 && !rb_small) || (M <= 64 && !rb)) && !(rb_forced && rb) && !f.tiled_only) r.kernel = Gemm8Kernel::Stream8;
+  }
+  if (r.kernel == Gemm8Kernel::Stream8) return r;
+  if (rb) {
+    r.kernel = Gemm8Kernel::Rb8;
+    rb8_launch_plan(M, N, K, f, &r.tile_rows, &r.tile_cols, &r.k_parts);
+    return r;
+  }
+  return tiled_route(M, N, K, aligned, f);
+}
+
 }  // namespace ao
 
 using namespace ao;
 
 extern "C" int ao_gemm8_set_variant(int variant) {
-  g_gemm8_force_regstage = (variant == 1);
-  g_gemm8_tiled_only = (variant == 100);
-  g_mx_variant = (variant == 110) ? 1 : (variant == 111) ? 2 : 0;
-  // MX decode groups: 113 one workgroup per tile (the form of larger groups); 129 the stream-K kernel's per-step-scales form (8 waves, two per CU:
-  // what K % 512 != 0 takes) on every K
-  mx_rb_set_stream(variant == 113 ? 0 : 1, variant != 129);
-  // the straight-line decode kernel (dec8_kernels.hip): 201 / 202 / 204 / 207 / 208 force its ring depth, 290 half-line loads, 299 never
-  g_dec8_mode = (variant >= 200 && variant <= 299) ? variant : 0;
-  // the register-ring mid-M kernel (mid8_kernels.hip): 300 never, 301 wherever the shape allows, 310 + S: S K-parts forced
-  g_mid8_mode = (variant >= 300 && variant <= 329) ? variant : 0;
-  g_gemm8_tm = (variant == 2 || variant == 4 || variant == 8 || variant == 16 || variant == 32 || variant == 33) ? variant : 0;
-  // the fp8 weight-streaming mid-M kernel: 101 always, 100 or any explicit GEMM variant never, 0 by shape
-  fp8_rowwise_rb_set_mode(variant == 101 ? 2 : variant == 102 ? 3 : (variant != 0 && variant < 110 && variant != 103) ? 1 : 0);
-  rb8_set_wave_grid(variant != 103);  // 103: the weight-streaming kernel's round-3 wave arrangement (1 x 8), product dispatch otherwise
+  Gemm8Force& f = g_force;
+  f.regstage = variant == 1;
+  f.tiled_only = variant == 100;
+  f.tile = (variant == 2 || variant == 4 || variant == 8 || variant == 16 || variant == 32 || variant == 33) ? variant : 0;
+  f.rb = variant == 101 ? 2 : variant == 102 ? 3 : (variant != 0 && variant < 110 && variant != 103) ? 1 : 0;
+  f.rb8_1x8 = variant == 103;
+  f.mx = (variant == 110) ? 1 : (variant == 111) ? 2 : 0;
+  f.mx_stream = variant != 113;
+  f.mx_quad = variant != 129;
+  f.dec8 = (variant >= 200 && variant <= 299) ? variant : 0;
+  f.mid8 = (variant >= 300 && variant <= 329) ? variant : 0;
   return AO_OK;
 }
 
-namespace ao { namespace { thread_local int g_tune[16] = {0}; } }
 extern "C" int ao_gemm8_set_tuning(int key, int value) {
+  static int Gemm8Force::*const kKeys[] = {nullptr, &Gemm8Force::rb8_bn, &Gemm8Force::rb8_split, &Gemm8Force::rb8_bm, &Gemm8Force::p8_group_rows,
+                                           &Gemm8Force::rb8_ablate, &Gemm8Force::p8_persist, &Gemm8Force::p8_split, &Gemm8Force::p8h_form,
+                                           &Gemm8Force::mx_proto};
   AO_REQUIRE(key >= 1 && key <= 9, "ao_gemm8_set_tuning: unknown key %d", key);
-  g_tune[key] = value;
-  mx_stream_set_tuning(g_tune[9]);
-  rb8_set_tuning(g_tune[1], g_tune[2], g_tune[5]);
-  rb8_set_slab_rows(g_tune[3]);
-  gemm8_p8_set_group_rows(g_tune[4]);
-  gemm8_p8_set_split(g_tune[7]);
-  gemm8_p8_set_persistent(g_tune[6]);
-  gemm8_p8h_set_form(g_tune[8]);
+  g_force.*kKeys[key] = value;
   return AO_OK;
 }
+
+namespace {
+
+// the rowwise scaled entries: activation codes x weight codes, the scale epilogue, bf16 out
+int gemm8_scaled(bool int8, const void* a, const float* scale_a, const void* b, const float* scale_b, const uint16_t* bias, uint16_t* y, int64_t M,
+                 int64_t N, int64_t K, hipStream_t stream) {
+  const Gemm8Route r = gemm8_route(int8 ? Gemm8Entry::Int8Scaled : Gemm8Entry::Fp8Scaled, M, N, K, aligned16(scale_a, scale_b, bias, y), g_force);
+  switch (r.kernel) {
+    case Gemm8Kernel::Dec8: return dec8_scaled(int8, a, scale_a, b, scale_b, bias, y, M, N, K, r.dec, stream);
+    case Gemm8Kernel::Mid8: return mid8_scaled(int8, a, scale_a, b, scale_b, bias, y, M, N, K, r.mid, stream);
+    case Gemm8Kernel::Rb8: return rb8_scaled(int8, a, b, scale_a, scale_b, bias, y, M, N, K, r.tile_rows, r.tile_cols, r.k_parts, stream);
+    case Gemm8Kernel::Stream8:
+      return int8 ? int8_scaled_stream(static_cast<const int8_t*>(a), static_cast<const int8_t*>(b), scale_a, scale_b, bias, y, M, N, K, stream)
+                  : fp8_rowwise_stream(static_cast<const uint8_t*>(a), static_cast<const uint8_t*>(b), scale_a, scale_b, bias, y, M, N, K, stream);
+    default: break;
+  }
+  const Gemm8Args p{static_cast<const uint8_t*>(a), static_cast<const uint8_t*>(b), scale_a, scale_b, bias, y, (int)M, (int)N, (int)K};
+  return int8 ? launch_gemm8<EPI_INT8_SCALED>(r, p, stream) : launch_gemm8<EPI_FP8_ROWWISE>(r, p, stream);
+}
+
+const char* const kGemm8KernelNames[] = {"invalid", "dec8_kernel", "mid8_kernel", "stream8_kernel", "rb8_kernel", "gemm8_p8h_kernel",
+                                         "gemm8_p8_kernel", "gemm8_p8p_kernel", "gemm8_dma_kernel<128x128>", "gemm8_dma_kernel<256x256>",
+                                         "gemm8_dma_kernel<256x128>", "gemm8_dma_kernel<256x256,4 waves>", "gemm8_kernel", "dyn8_kernel"};
+static_assert(sizeof(kGemm8KernelNames) / sizeof(kGemm8KernelNames[0]) == (size_t)Gemm8Kernel::Dyn8 + 1, "one name per Gemm8Kernel");
+
+Gemm8Route product_route(int int8, int64_t M, int64_t N, int64_t K) {
+  return gemm8_route(int8 ? Gemm8Entry::Int8Scaled : Gemm8Entry::Fp8Scaled, M, N, K, true, Gemm8Force{});
+}
+
+int gemm8_plan3(int int8, int64_t M, int64_t N, int64_t K, int* tile_rows, int* tile_cols, int* k_parts) {
+  const Gemm8Route r = product_route(int8, M, N, K);
+  AO_REQUIRE(r.kernel != Gemm8Kernel::Invalid, "ao_gemm8_plan: no kernel takes M=%lld N=%lld K=%lld", (long long)M, (long long)N, (long long)K);
+  *tile_rows = r.tile_rows;
+  *tile_cols = r.tile_cols;
+  *k_parts = r.k_parts;
+  return AO_OK;
+}
+
+}  // namespace
 
 extern "C" int ao_int8_scaled_mm(const int8_t* xq, const float* x_scale, const int8_t* wq, const float* w_scale,
                                  const uint16_t* bias, uint16_t* y, int64_t M, int64_t N, int64_t K, void* stream) {
@@ -503,67 +598,22 @@ extern "C" int ao_int8_scaled_mm(const int8_t* xq, const float* x_scale, const i
   AO_REQUIRE_PTR(wq);
   AO_REQUIRE_PTR(w_scale);
   AO_REQUIRE_PTR(y);
-  // weight-bandwidth-bound sizes stream the weights once, as for fp8 below: M <= 32 per-tile streaming kernel
-  // (stream8_kernels.hip), few output tiles the LDS-staged one (rb8_kernels.hip); Llama-3-8B down_proj at M = 1 took 77 us
-  // through the tiled GEMM
-  if (M <= 16 && !fp8_rowwise_rb_forced() && !g_gemm8_tiled_only && dec8_takes(M, N, K))
-    return dec8_scaled(true, xq, x_scale, wq, w_scale, bias, y, M, N, K, (hipStream_t)stream);  // round 4: full-line register ring
-  if (M > 16 && !fp8_rowwise_rb_forced() && !g_gemm8_tiled_only && g_gemm8_tm == 0 && !g_gemm8_force_regstage && mid8_takes(M, N, K))
-    return mid8_scaled(true, xq, x_scale, wq, w_scale, bias, y, M, N, K, (hipStream_t)stream);  // round 4: 16 < M <= 256, few output tiles
-  const bool rb_small = !g_gemm8_tiled_only && g_gemm8_tm == 0 && !g_gemm8_force_regstage && rb8_small_m_preferred(M, N, K);  // round 6
-  if (N % 16 == 0 && K % 128 == 0 && M <= 32 && !rb_small && !fp8_rowwise_rb_forced() && !g_gemm8_tiled_only)
-    return int8_scaled_stream(xq, wq, x_scale, w_scale, bias, y, M, N, K, (hipStream_t)stream);
-  if (N % 16 == 0 && (rb_small || fp8_rowwise_rb_preferred(M, N, K))) return int8_scaled_rb(xq, wq, x_scale, w_scale, bias, y, M, N, K, (hipStream_t)stream);
-  Gemm8Args p{reinterpret_cast<const uint8_t*>(xq), reinterpret_cast<const uint8_t*>(wq), x_scale, w_scale, bias, y,
-              (int)M, (int)N, (int)K};
-  return launch_gemm8<EPI_INT8_SCALED>(p, (hipStream_t)stream);
+  return gemm8_scaled(true, xq, x_scale, wq, w_scale, bias, y, M, N, K, (hipStream_t)stream);
 }
 
-// Which kernel the product dispatch of ao_fp8_scaled_mm / ao_int8_scaled_mm takes for a shape (host logic only: no launch, no GPU) -- the
-// rules of the two entry points above and below, restated without the tuning overrides.  tests/test_host_dispatch.py pins the table.
+// Which kernel ao_fp8_scaled_mm / ao_int8_scaled_mm launch for a shape with 16-byte-aligned operands and no override set (host logic
+// only: no launch, no GPU).  tests/test_host_dispatch.py pins the table.
 extern "C" const char* ao_gemm8_kernel_name(int int8, int64_t M, int64_t N, int64_t K) {
-  if (M <= 0 || N <= 0 || K <= 0 || K % 16 != 0) return "invalid";
-  if (M <= 16 && dec8_takes(M, N, K)) return "dec8_kernel";
-  if (M > 16 && mid8_takes(M, N, K)) return "mid8_kernel";
-  const bool rb_small = rb8_small_m_preferred(M, N, K);
-  const bool rb_shape = N % 16 == 0 && (rb_small || fp8_rowwise_rb_preferred(M, N, K));
-  if (int8) {
-    if (N % 16 == 0 && K % 128 == 0 && M <= 32 && !rb_small) return "stream8_kernel";
-    if (rb_shape) return "rb8_kernel";
-  } else {
-    if (N % 16 != 0) return "invalid";
-    const bool rb = rb_shape && (M > 32 || rb_small);
-    if (K % 128 == 0 && ((M <= 32 && !rb_small) || (M <= 64 && !rb))) return "stream8_kernel";
-    if (rb) return "rb8_kernel";
-  }
-  if (K % BK != 0) return "gemm8_kernel";  // register-staged tiles (K % 128 != 0)
-  const int64_t big = ((N + 255) / 256) * ((M + 255) / 256);
-  if (gemm8_p8h_band(M, N, K)) return "gemm8_p8h_kernel";
-  if (gemm8_p8_band(M, N, K) && gemm8_p8_fits(M, N, K)) return gemm8_p8_persistent_shape(M, N, K) ? "gemm8_p8p_kernel" : "gemm8_p8_kernel";
-  return big >= 512 ? "gemm8_dma_kernel<256x256>" : "gemm8_dma_kernel<128x128>";
+  return kGemm8KernelNames[(int)product_route(int8, M, N, K).kernel];
 }
 
-// The launch shape behind ao_gemm8_kernel_name: tile rows, column-tile width and K parts of the product dispatch (host logic only).
-// rb8_kernel: the cost model's pick (64- / 128-row slabs, 32 / 64 / 128 columns, 1 .. 8 parts); gemm8_p8h_kernel: 256 x 128, 1 .. 4 parts;
-// every other kernel: its tile, one part.
-static int gemm8_plan3(int int8, int64_t M, int64_t N, int64_t K, int* tile_rows, int* tile_cols, int* k_parts) {
-  const std::string name = ao_gemm8_kernel_name(int8, M, N, K);
-  AO_REQUIRE(name != "invalid", "ao_gemm8_plan: no kernel takes M=%lld N=%lld K=%lld", (long long)M, (long long)N, (long long)K);
-  *k_parts = 1;
-  if (name == "rb8_kernel") rb8_plan_query(M, N, K, tile_rows, tile_cols, k_parts);
-  else if (name == "gemm8_p8h_kernel") { *tile_rows = 256; *tile_cols = 128; *k_parts = gemm8_p8h_parts(M, N, K); }
-  else if (name == "gemm8_p8_kernel" || name == "gemm8_p8p_kernel" || name == "gemm8_dma_kernel<256x256>") *tile_rows = *tile_cols = 256;
-  else if (name == "gemm8_dma_kernel<128x128>" || name == "gemm8_kernel") *tile_rows = *tile_cols = 128;
-  else { *tile_rows = 16; *tile_cols = 16; }  // the per-tile streaming kernels (dec8 / mid8 / stream8): 16-wide n-tiles, K split among the waves of a workgroup
-  return AO_OK;
-}
+// The launch shape of that route: tile rows, column-tile width and K parts (host logic only).
 extern "C" int ao_gemm8_plan(int int8, int64_t M, int64_t N, int64_t K, int* tile_cols, int* k_parts) {
   AO_REQUIRE_PTR(tile_cols);
   AO_REQUIRE_PTR(k_parts);
   int rows = 0;
   return gemm8_plan3(int8, M, N, K, &rows, tile_cols, k_parts);
 }
-// (round 6) the tile's rows as well: the weight-streaming kernel's slab height is part of the plan since 64-row slabs serve M > 64
 extern "C" int ao_gemm8_plan_rows(int int8, int64_t M, int64_t N, int64_t K, int* tile_rows) {
   AO_REQUIRE_PTR(tile_rows);
   int cols = 0, parts = 0;
@@ -577,9 +627,10 @@ extern "C" int ao_int8_int_mm(const int8_t* a, const int8_t* b_t, int32_t* c, in
   AO_REQUIRE_PTR(a);
   AO_REQUIRE_PTR(b_t);
   AO_REQUIRE_PTR(c);
+  const Gemm8Route r = gemm8_route(Gemm8Entry::Int32Raw, M, N, K, aligned16(nullptr, nullptr, nullptr, c), g_force);
   Gemm8Args p{reinterpret_cast<const uint8_t*>(a), reinterpret_cast<const uint8_t*>(b_t), nullptr, nullptr, nullptr, c,
               (int)M, (int)N, (int)K};
-  return launch_gemm8<EPI_INT32>(p, (hipStream_t)stream);
+  return launch_gemm8<EPI_INT32>(r, p, (hipStream_t)stream);
 }
 
 // Unscaled e4m3 x e4m3 products, fp32 out: the partial sums a K-sharded (row-parallel) fp8 linear all-reduces before
@@ -590,8 +641,9 @@ extern "C" int ao_fp8_mm_f32(const uint8_t* a, const uint8_t* b, float* c, int64
   AO_REQUIRE_PTR(a);
   AO_REQUIRE_PTR(b);
   AO_REQUIRE_PTR(c);
+  const Gemm8Route r = gemm8_route(Gemm8Entry::Fp8Raw, M, N, K, aligned16(nullptr, nullptr, nullptr, c), g_force);
   Gemm8Args p{a, b, nullptr, nullptr, nullptr, c, (int)M, (int)N, (int)K};
-  return launch_gemm8<EPI_FP8_RAW>(p, (hipStream_t)stream);
+  return launch_gemm8<EPI_FP8_RAW>(r, p, (hipStream_t)stream);
 }
 
 extern "C" int ao_fp8_scaled_mm(const uint8_t* a, const uint8_t* b, const float* scale_a, const float* scale_b,
@@ -604,26 +656,5 @@ extern "C" int ao_fp8_scaled_mm(const uint8_t* a, const uint8_t* b, const float*
   AO_REQUIRE_PTR(scale_a);
   AO_REQUIRE_PTR(scale_b);
   AO_REQUIRE_PTR(y);
-  // Weight-bandwidth-bound sizes stream the weights once instead of tiling a GEMM (Llama-70B TP8 shards, us per call,
-  // profiles/bench_8bit_r01_fp8.jsonl):
-  //   * M <= 32: stream8_kernels.hip -- activations straight from L2 per wave, no LDS staging, no split-K
-  //     (gate_up 7168x8192: 15 us at M = 1, 20 at 16; the LDS-staged kernel below needs 23);
-  //   * 32 < M and too few 128 x 128 tiles to fill the chip: rb8_kernels.hip (24 us at M = 64 where the kernel above
-  //     needs 40; 27 us at M = 128 where the tiled GEMM needs 55);
-  //   * otherwise the tiled LDS-DMA GEMM.
-  // (at 32 < M <= 64 it only wins once K is long enough to amortise its start-up and split-K meeting: o_proj shard 8192x1024 8.5 vs 10.9 us)
-  if (M <= 16 && !fp8_rowwise_rb_forced() && !g_gemm8_tiled_only && dec8_takes(M, N, K))
-    return dec8_scaled(false, a, scale_a, b, scale_b, bias, y, M, N, K, (hipStream_t)stream);  // round 4: full-line register ring
-  if (M > 16 && !fp8_rowwise_rb_forced() && !g_gemm8_tiled_only && g_gemm8_tm == 0 && !g_gemm8_force_regstage && mid8_takes(M, N, K))
-    return mid8_scaled(false, a, scale_a, b, scale_b, bias, y, M, N, K, (hipStream_t)stream);  // round 4: 16 < M <= 256, few output tiles
-  // (round 4, cold weights -- every call of the replay reads another copy: the LDS-staged kernel wins from 33 rows on at every K of the
-  // 70B / TP8 shards, down 8192 x 3584 at M = 64: 14.0 us against 20.9 through the per-tile kernel, o 8192 x 1024: 8.5 against 9.2; the
-  // round-1 rule -- "only from K >= 4096 at 32 < M <= 64" -- had been measured on ONE re-used weight, i.e. out of the Infinity Cache)
-  const bool rb_small = !g_gemm8_tiled_only && g_gemm8_tm == 0 && !g_gemm8_force_regstage && rb8_small_m_preferred(M, N, K);  // round 6
-  const bool rb = rb_small || (fp8_rowwise_rb_preferred(M, N, K) && (M > 32 || fp8_rowwise_rb_forced()));
-  if (K % 128 == 0 && ((M <= 32 && !rb_small) || (M <= 64 && !rb)) && !(fp8_rowwise_rb_forced() && rb) && !g_gemm8_tiled_only)
-    return fp8_rowwise_stream(a, b, scale_a, scale_b, bias, y, M, N, K, (hipStream_t)stream);
-  if (rb) return fp8_rowwise_rb(a, b, scale_a, scale_b, bias, y, M, N, K, (hipStream_t)stream);
-  Gemm8Args p{a, b, scale_a, scale_b, bias, y, (int)M, (int)N, (int)K};
-  return launch_gemm8<EPI_FP8_ROWWISE>(p, (hipStream_t)stream);
+  return gemm8_scaled(false, a, scale_a, b, scale_b, bias, y, M, N, K, (hipStream_t)stream);
 }

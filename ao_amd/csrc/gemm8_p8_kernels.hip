@@ -20,6 +20,7 @@
 //   * epilogue: scales applied in registers with the reference's rounding sequence, tile transposed through the (now free)
 //     LDS so that every lane stores 16 contiguous bytes (128-byte rows per 8 lanes) instead of 2.
 #include "common.h"
+#include "gemm8_route.h"
 #include "lds_dma.h"
 #include "splitk.h"
 
@@ -45,9 +46,6 @@ struct P8Args {
   unsigned* tickets;
 };
 
-thread_local int g_p8_group_rows = 0;  // 0 = 4 (product)
-thread_local int g_p8h_form = 0;      // lab: loop forms of gemm8_p8h_kernel (fp8 rowwise only)
-thread_local int g_p8_split = 0;       // 0 = by shape (p8_split below), n = n K parts wherever they fit
 constexpr int kHalf = 16384;          // one half tile: 128 rows x 128 B
 constexpr int kBuf = 4 * kHalf;       // A-lo, A-hi, B-lo, B-hi of one K tile
 constexpr int kEpiStride = 144;       // bytes per row of a wave's 128 x 64 bf16 staging region (128 + 16: conflict-free b16 writes)
@@ -864,36 +862,36 @@ int p8h_split_rule(int64_t M, int64_t N, int64_t K) {
   const int64_t S = std::min<int64_t>(4, 256 / tiles);
   return (S >= 2 && tiles * S >= 128) ? (int)S : 1;
 }
-int p8h_split(int64_t M, int64_t N, int64_t K) {
-  const int64_t tiles = ((M + 255) / 256) * ((N + 127) / 128), ktiles = K / 128;
-  const int64_t fit = std::min<int64_t>({256 / tiles, ktiles, 16, (int64_t)(kSplitSlotFloats / ((size_t)tiles * 256 * 128)) * 4 / 5,
-                                         (int64_t)kSplitMaxTickets / (tiles * 5)});
-  if (g_p8_split > 0) return (int)std::max<int64_t>(1, std::min<int64_t>(g_p8_split, fit));
-  return (int)std::max<int64_t>(1, std::min<int64_t>(p8h_split_rule(M, N, K), fit));
+
+// tile rows an XCD's consecutive workgroups walk together: 4 (product), or ao_gemm8_set_tuning key 4
+int p8_group_rows() {
+  const int v = gemm8_force().p8_group_rows;
+  return (v >= 1 && v <= 64) ? v : 4;
 }
 
 template <int EPI>
-int launch_p8h(P8Args p, hipStream_t stream) {
+int launch_p8h(P8Args p, int split, hipStream_t stream) {
   p.tiles_m = (p.M + 255) / 256;
   p.tiles_n = (p.N + 127) / 128;
-  p.group_rows = (g_p8_group_rows >= 1 && g_p8_group_rows <= 64) ? g_p8_group_rows : 4;
-  p.split = p8h_split(p.M, p.N, p.K);
+  p.group_rows = p8_group_rows();
+  p.split = split;
   if (p.split > 1) {
     const int NG = (p.split + 3) / 4;
     if (int rc = splitk_workspace(stream, &p.ws, &p.tickets, (size_t)p.tiles_m * p.tiles_n * (p.split + NG) * 256 * 128, p.split)) return rc;
   }
 #ifdef AO_LAB  // the measured-and-rejected loop forms (profiles/p8h_loop_forms_r05.jsonl) only exist in the laboratory build
-  if (EPI == P8_FP8_ROWWISE && g_p8h_form == 1) {
+  const int form = gemm8_force().p8h_form;  // ao_gemm8_set_tuning key 8
+  if (EPI == P8_FP8_ROWWISE && form == 1) {
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(gemm8_p8h_kernel<P8_FP8_ROWWISE, 1>), kHSmem, "hipFuncSetAttribute(gemm8_p8h_kernel)")) return rc;
     ao::launch(gemm8_p8h_kernel<P8_FP8_ROWWISE, 1>, dim3((unsigned)(p.tiles_m * p.tiles_n * p.split)), dim3(512), kHSmem, stream, p);
     return AO_OK;
   }
-  if (EPI == P8_FP8_ROWWISE && g_p8h_form == 3) {
+  if (EPI == P8_FP8_ROWWISE && form == 3) {
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(gemm8_p8h_kernel<P8_FP8_ROWWISE, 3>), kHSmem, "hipFuncSetAttribute(gemm8_p8h_kernel)")) return rc;
     ao::launch(gemm8_p8h_kernel<P8_FP8_ROWWISE, 3>, dim3((unsigned)(p.tiles_m * p.tiles_n * p.split)), dim3(512), kHSmem, stream, p);
     return AO_OK;
   }
-  if (EPI == P8_FP8_ROWWISE && g_p8h_form == 2) {
+  if (EPI == P8_FP8_ROWWISE && form == 2) {
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(gemm8_p8h_kernel<P8_FP8_ROWWISE, 2>), kHSmem, "hipFuncSetAttribute(gemm8_p8h_kernel)")) return rc;
     ao::launch(gemm8_p8h_kernel<P8_FP8_ROWWISE, 2>, dim3((unsigned)(p.tiles_m * p.tiles_n * p.split)), dim3(512), kHSmem, stream, p);
     return AO_OK;
@@ -905,7 +903,6 @@ int launch_p8h(P8Args p, hipStream_t stream) {
   return AO_OK;
 }
 
-thread_local int g_p8_persist = 0;  // (ao_gemm8_set_tuning key 6) 0 product rule, 1 never, 2 wherever the shape allows
 constexpr int kP8ChipCUs = 256;     // MI355X: one persistent workgroup per CU, 32 per XCD
 
 // The persistent form takes full tiles when there are more tiles than CUs, and any tile count at K < 4096, where its register-only epilogue and
@@ -919,20 +916,13 @@ constexpr int kP8ChipCUs = 256;     // MI355X: one persistent workgroup per CU, 
 bool p8_persistent_shape(int64_t M, int64_t N, int64_t K) {
   return M % 256 == 0 && N % 256 == 0 && K >= 256 && K % 128 == 0 && ((M / 256) * (N / 256) > kP8ChipCUs || K < 4096);
 }
-bool p8_persistent_takes(const P8Args& p) {
-  if (g_p8_persist == 1) return false;
-  const bool fits = p.M % 256 == 0 && p.N % 256 == 0 && p.K >= 256 && (reinterpret_cast<uintptr_t>(p.row_scale) & 15) == 0 &&
-                    (reinterpret_cast<uintptr_t>(p.col_scale) & 15) == 0 && (reinterpret_cast<uintptr_t>(p.bias) & 3) == 0 &&
-                    (reinterpret_cast<uintptr_t>(p.out) & 15) == 0;
-  return fits && (g_p8_persist == 2 || p8_persistent_shape(p.M, p.N, p.K));
-}
 
 template <int EPI>
-int launch_p8(P8Args p, hipStream_t stream) {
+int launch_p8(P8Args p, bool persistent, hipStream_t stream) {
   p.tiles_m = (p.M + 255) / 256;
   p.tiles_n = (p.N + 255) / 256;
-  if (p8_persistent_takes(p)) {
-    p.group_rows = (g_p8_group_rows >= 1 && g_p8_group_rows <= 64) ? g_p8_group_rows : 4;
+  if (persistent) {
+    p.group_rows = p8_group_rows();
     p.split = 1;
     const int64_t tiles = (int64_t)p.tiles_m * p.tiles_n;
     const unsigned grid = (unsigned)std::min<int64_t>(kP8ChipCUs, (tiles + 7) / 8 * 8);
@@ -943,7 +933,7 @@ int launch_p8(P8Args p, hipStream_t stream) {
   }
   // round 5 sweep (profiles/p8_group_rows_r05.jsonl): 4 tile rows per group measured 0 .. 7 % ahead of 8 on the Llama-3-8B int8 shapes at
   // M = 16384 (an XCD's L2 then holds 4 MB of A panels, its size, instead of 8 MB) and level elsewhere
-  p.group_rows = (g_p8_group_rows >= 1 && g_p8_group_rows <= 64) ? g_p8_group_rows : 4;
+  p.group_rows = p8_group_rows();
   p.split = 1;
   if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(gemm8_p8_kernel<EPI>), kSmem, "hipFuncSetAttribute(gemm8_p8_kernel)")) return rc;
   ao::launch(gemm8_p8_kernel<EPI>, dim3((unsigned)(p.tiles_m * p.tiles_n)), dim3(512), kSmem, stream, p);
@@ -970,33 +960,37 @@ bool gemm8_p8h_band(int64_t M, int64_t N, int64_t K) {
   if (p8h_split_rule(M, N, K) > 1) return true;  // (the rule: with K parts, above)
   return tiles > 128 && tiles <= 256 && !(slabs <= 256 && K >= 4096);
 }
-int gemm8_p8h_parts(int64_t M, int64_t N, int64_t K) { return p8h_split_rule(M, N, K); }  // (product rule; host logic only)
-void gemm8_p8_set_group_rows(int v) { g_p8_group_rows = v; }
-void gemm8_p8_set_split(int v) { g_p8_split = v; }
-void gemm8_p8_set_persistent(int v) { g_p8_persist = v; }
+// K parts of a 256 x 128 launch: the rule above (forced > 0: that count, ao_gemm8_set_tuning key 7), clamped to one round of the chip and
+// the split-K workspace
+int gemm8_p8h_parts(int64_t M, int64_t N, int64_t K, int forced) {
+  const int64_t tiles = ((M + 255) / 256) * ((N + 127) / 128), ktiles = K / 128;
+  const int64_t fit = std::min<int64_t>({256 / tiles, ktiles, 16, (int64_t)(kSplitSlotFloats / ((size_t)tiles * 256 * 128)) * 4 / 5,
+                                         (int64_t)kSplitMaxTickets / (tiles * 5)});
+  return (int)std::max<int64_t>(1, std::min<int64_t>(forced > 0 ? forced : p8h_split_rule(M, N, K), fit));
+}
 bool gemm8_p8_persistent_shape(int64_t M, int64_t N, int64_t K) { return p8_persistent_shape(M, N, K); }
-void gemm8_p8h_set_form(int v) { g_p8h_form = v; }
 
-// the 256 x 128 form (same epi numbering and shape limits)
+// the 256 x 128 form with `split` K parts (same epi numbering and shape limits)
 int gemm8_p8h(int epi, const uint8_t* a, const uint8_t* b, const float* row_scale, const float* col_scale, const uint16_t* bias, void* out,
-              int64_t M, int64_t N, int64_t K, hipStream_t stream) {
+              int64_t M, int64_t N, int64_t K, int split, hipStream_t stream) {
   P8Args p{a, b, row_scale, col_scale, bias, out, (int)M, (int)N, (int)K, 0, 0, 0, 1, nullptr, nullptr};
   switch (epi) {
-    case P8_INT8_SCALED: return launch_p8h<P8_INT8_SCALED>(p, stream);
-    case P8_INT32: return launch_p8h<P8_INT32>(p, stream);
-    case P8_FP8_ROWWISE: return launch_p8h<P8_FP8_ROWWISE>(p, stream);
-    default: return launch_p8h<P8_FP8_RAW>(p, stream);
+    case P8_INT8_SCALED: return launch_p8h<P8_INT8_SCALED>(p, split, stream);
+    case P8_INT32: return launch_p8h<P8_INT32>(p, split, stream);
+    case P8_FP8_ROWWISE: return launch_p8h<P8_FP8_ROWWISE>(p, split, stream);
+    default: return launch_p8h<P8_FP8_RAW>(p, split, stream);
   }
 }
 
+// persistent: the gemm8_p8p_kernel form (full 256 x 256 tiles, 16-byte-aligned scales and output)
 int gemm8_p8(int epi, const uint8_t* a, const uint8_t* b, const float* row_scale, const float* col_scale, const uint16_t* bias, void* out,
-             int64_t M, int64_t N, int64_t K, hipStream_t stream) {
+             int64_t M, int64_t N, int64_t K, bool persistent, hipStream_t stream) {
   P8Args p{a, b, row_scale, col_scale, bias, out, (int)M, (int)N, (int)K, 0, 0, 0, 1, nullptr, nullptr};
   switch (epi) {
-    case P8_INT8_SCALED: return launch_p8<P8_INT8_SCALED>(p, stream);
-    case P8_INT32: return launch_p8<P8_INT32>(p, stream);
-    case P8_FP8_ROWWISE: return launch_p8<P8_FP8_ROWWISE>(p, stream);
-    default: return launch_p8<P8_FP8_RAW>(p, stream);
+    case P8_INT8_SCALED: return launch_p8<P8_INT8_SCALED>(p, persistent, stream);
+    case P8_INT32: return launch_p8<P8_INT32>(p, persistent, stream);
+    case P8_FP8_ROWWISE: return launch_p8<P8_FP8_ROWWISE>(p, persistent, stream);
+    default: return launch_p8<P8_FP8_RAW>(p, persistent, stream);
   }
 }
 

@@ -661,7 +661,6 @@ __global__ __launch_bounds__(64 * WAVES * (PROD ? 2 : 1), (WAVES == 4 && !PROD) 
 }
 
 thread_local unsigned long long* g_mm_trace = nullptr;  // profiling only (ao_int4_set_trace)
-thread_local int g_tune_wpb = 0;
 // 128 x 256 tiles (64-column wave tiles) of the batched kernel.  Round 6, first fit (Llama-3-8B shapes): M >= 512 and tiles that fill >= 7/8 of every
 // round of the 256 CUs.  Re-fitted on 16 shapes of four models x M = 256 / 512 / 1024 x 7 forms (profiles/int4_forms_big_r06.jsonl): within ONE round
 // they are ahead from 144 tiles on (qkv 6144 x 4096 at M = 1024, 192 tiles: 70.3 -> 61.3 us; 5120^2, 160: 84.9 -> 71.6; 4608 x 3584, 144: 60.7 -> 52.9;
@@ -1152,11 +1151,12 @@ __global__ __launch_bounds__(64) void int4_quantize_kernel(const uint16_t* __res
   }
 }
 
-thread_local int g_tune_mode = 0;  // profiling only (ao_int4_set_tuning): 95-99 small-M A/B builds, 600-699 batched kernel (parts, ablation / trace builds)
+thread_local Int4Force g_int4_force;  // ao_int4_set_tuning
 
+// forced_wpb: waves per workgroup of ao_int4_set_tuning (4 .. 16; else the rule below)
 template <int G, int MAXM, int DEPTH = 4>
 int launch_mm(const uint16_t* x, const int32_t* qdata, const uint16_t* sz, uint16_t* y, int64_t M,
-              int64_t N, int64_t K, hipStream_t stream, bool straight = false) {
+              int64_t N, int64_t K, hipStream_t stream, bool straight, int forced_wpb) {
   constexpr int ROWSTRIDE = (MAXM <= 4) ? 256 : 272;
   constexpr int SLAB = (MAXM + 1) * ROWSTRIDE;
   const int kblocks = (int)(K >> 7);
@@ -1166,7 +1166,7 @@ int launch_mm(const uint16_t* x, const int32_t* qdata, const uint16_t* sz, uint1
   // 4 waves 800, 8 waves 868, 16 waves 705 tok/s), else 4 (>= 256 threads for the epilogue)
   int wpb = (kblocks >= 16) ? 8 : 4;
   if (ntiles * mslabs >= 2048 && wpb > 4 && MAXM > 1) wpb /= 2;
-  if (g_tune_wpb >= 4 && g_tune_wpb <= 16) wpb = g_tune_wpb;
+  if (forced_wpb >= 4 && forced_wpb <= 16) wpb = forced_wpb;
   if (straight && kblocks % DEPTH == 0 && kblocks / DEPTH >= 4 && kblocks / DEPTH <= 16) wpb = kblocks / DEPTH;  // straight-line form
   if (MAXM > 4 && wpb > 8) wpb = 8;  // 16-row variant is built for <= 512 threads
   if (wpb > kblocks) wpb = kblocks < 4 ? 4 : kblocks;
@@ -1191,164 +1191,85 @@ int launch_mm(const uint16_t* x, const int32_t* qdata, const uint16_t* sz, uint1
   return AO_OK;
 }
 
-template <int G>
-int dispatch_mm(const uint16_t* x, const int32_t* qdata, const uint16_t* sz, uint16_t* y, int64_t M,
-                int64_t N, int64_t K, hipStream_t stream) {
-  // M <= 16: one workgroup per 16-wide n-tile, waves split K (int4_mm_kernel, built for 1, 4 or 16 rows).  In the hipGraph
-  // bench the single-row build beat both purpose-built decode kernels this round tried (a persistent balanced streaming kernel
-  // with hand-counted LDS-DMA rings and a per-tile kernel with workgroup-shared x): 868 vs 732 tok/s.
-  // At 4 < M <= 16 the per-tile kernel re-reads x for every 16 output columns (4 KiB of x per 1 KiB of weights at 16 rows): fine
-  // for the narrow projections, 1.5x the M = 1 time on wide ones -- weights of >= 1024 n-tiles (merged gate_up_proj, lm_head) take
-  // the batched kernel below with 16-row slabs, where 4 n-tiles share one staged x tile (gate_up_proj at M = 16: 32 -> 21.8 us).
-  // (At M <= 4 the same switch measured 16.2 vs 17.4 us on one box and 19.7 vs 14.2 us on another: not taken.)
-  // Modes 93-99: A/B builds for profiling (94 never / 93 always the batched kernel on wide weights at M <= 16, 97 the ring kernel at M = 1
-  // whatever K, 98 the 4-row build at M = 1, 99 the 16-row build at any M).
-  const bool wide = (N >> 4) >= 1024 && g_tune_mode != 94;
-  if (M == 1 && g_tune_mode == 98) return launch_mm<G, 4>(x, qdata, sz, y, M, N, K, stream);
-  if (g_tune_mode == 99) return launch_mm<G, 16>(x, qdata, sz, y, M, N, K, stream);
-  // Round 6 (profiles/int4_forms_r06.jsonl, int4_forms_parts_r06.jsonl: 16 shapes of four models x M = 5 .. 16 x 9 forms, cold): the 16-row per-tile
-  // build (9 .. 16 rows) is 1.3 - 1.6 x the 8-row build's time, and from 288 n-tiles on the batched kernel's 16-row slabs with K parts pass it --
-  // gate 14336 x 4096 at M = 12 / 16 19.0 / 19.4 -> 14.1 us, 15360 x 5120 25.1 / 26.5 -> 16.6 / 16.8, 5120 x 13824 25.7 -> 17.4, 10240 x 8192
-  // 24.0 / 25.3 -> 17.5 / 17.9, qkv 6144 x 4096 10.0 / 10.2 -> 9.5; at 224 - 256 n-tiles (o 4096^2: 6.2 against 8.5) and up to 8 rows the per-tile
-  // kernel stays ahead.
-  const bool tall = M > 8 && (N >> 4) >= 288 && g_tune_mode != 94;
-  if (M <= 16 && g_tune_mode < 600 && !tall && !(wide && (M > 4 || g_tune_mode == 93))) {
-    if (M == 1 && g_tune_mode != 97) {
-      // round 3: when the weight's K divides into (waves <= 16) x (2 | 4 | 7 | 14 blocks), every block of the tile is requested in the
-      // prologue and the kernel is straight-line code (58 - 64 VGPRs: four 8-wave workgroups per CU, so gate / up's 896 tiles are
-      // resident at once; down_proj as 16 waves x 7 blocks has its whole weight in flight).  Llama-3-8B, same run, five shapes /
-      // merged: 765 -> 818 / 846 -> 906 tok/s (profiles/int4_modes_r03.jsonl); mode 97 = the ring kernel everywhere
-      const int64_t kbl = K >> 7;
-      if (kbl % 4 == 0 && kbl / 4 >= 4 && kbl / 4 <= 16) return launch_mm<G, 1, 4>(x, qdata, sz, y, M, N, K, stream, true);
-      if (kbl % 7 == 0 && kbl / 7 >= 4 && kbl / 7 <= 16) return launch_mm<G, 1, 7>(x, qdata, sz, y, M, N, K, stream, true);
-      if (kbl % 14 == 0 && kbl / 14 >= 4 && kbl / 14 <= 16) return launch_mm<G, 1, 14>(x, qdata, sz, y, M, N, K, stream, true);
-      if (kbl % 2 == 0 && kbl / 2 >= 4 && kbl / 2 <= 16) return launch_mm<G, 1, 2>(x, qdata, sz, y, M, N, K, stream, true);
-      // round 6: K of other models that none of the four factors -- 8 blocks (K = 10240 / 12288 / 16384: 10 / 12 / 16 waves) and 9 (K = 13824,
-      // Llama-2-13B's down_proj: 12 waves) -- had fallen to the ring kernel (mode 97 = that, for A/B: profiles/int4_depth_other_r06.jsonl)
-      // Ahead on weights of up to 768 n-tiles (4096 x 12288 10.3 -> 9.1 us, 5120 x 13824 17.1 -> 16.0, 12288^2 22.8 -> 21.8, 6144 x 16384 19.5 -> 19.0),
-      // behind on wider ones (13824 x 10240 23.7 -> 27.2, 14336 x 16384 35.2 -> 37.7: 10 - 16 waves per workgroup x 864+ workgroups), which keep the ring.
-      if ((N >> 4) <= 768) {
-        if (kbl % 8 == 0 && kbl / 8 >= 4 && kbl / 8 <= 16) return launch_mm<G, 1, 8>(x, qdata, sz, y, M, N, K, stream, true);
-        if (kbl % 9 == 0 && kbl / 9 >= 4 && kbl / 9 <= 16) return launch_mm<G, 1, 9>(x, qdata, sz, y, M, N, K, stream, true);
-      }
-    }
-    if (M == 1) return launch_mm<G, 1>(x, qdata, sz, y, M, N, K, stream);
-    if (M <= 4) return launch_mm<G, 4>(x, qdata, sz, y, M, N, K, stream);
-    // round 4: an 8-row build between the 4- and the 16-row one (half the x requests, LDS staging and slab of the 16-row build for batches
-    // of 5 .. 8; mode 88 = the 16-row build as before, for A/B)
-    if (M <= 8 && g_tune_mode != 88) return launch_mm<G, 8>(x, qdata, sz, y, M, N, K, stream);
-    return launch_mm<G, 16>(x, qdata, sz, y, M, N, K, stream);
+// The form of an int4 matmul launch.  Tile: int4_mm_kernel, `rows` the build (1, 4, 8 or 16 rows), its ring depth, straight-line or
+// not, waves per workgroup forced (0: by rule).  Rb: int4_mm_rb_kernel<WAVES, NT, MT, ABL, PROD> with `split` K parts.  W32:
+// int4_mm_w32_kernel<PROD, ABL, CG> (CG 1: 128 x 128 tiles, 2: 128 x 256) with `split` K parts.
+struct Int4Route {
+  enum Form { Tile, Rb, W32 } form = Tile;
+  int rows = 1, depth = 4, wpb = 0;
+  bool straight = false;
+  int waves = 4, nt = 1, mt = 1, abl = 0, cg = 1, split = 1;
+  bool prod = false;
+};
+
+Int4Route tile_form(int rows, int depth = 4, bool straight = false) {
+  Int4Route r;
+  r.rows = rows; r.depth = depth; r.straight = straight;
+  return r;
+}
+Int4Route rb_form(int waves, int nt, int mt, int split, int abl = 0, bool prod = false) {
+  Int4Route r;
+  r.form = Int4Route::Rb; r.waves = waves; r.nt = nt; r.mt = mt; r.split = split; r.abl = abl; r.prod = prod;
+  return r;
+}
+Int4Route w32_form(int cg, bool prod, int split, int abl = 0) {
+  Int4Route r;
+  r.form = Int4Route::W32; r.cg = cg; r.prod = prod; r.split = split; r.abl = abl;
+  return r;
+}
+
+// M <= 16 on the per-tile kernel.  ring_only: mode 97 (the ring kernel at M = 1 whatever K); rows8: the 8-row build (mode 88: never).
+Int4Route tile_route(int64_t M, int64_t N, int64_t K, bool ring_only = false, bool rows8 = true) {
+  if (M == 1 && !ring_only) {
+    // round 3: when the weight's K divides into (waves <= 16) x (2 | 4 | 7 | 14 blocks), every block of the tile is requested in the
+    // prologue and the kernel is straight-line code (58 - 64 VGPRs: four 8-wave workgroups per CU, so gate / up's 896 tiles are
+    // resident at once; down_proj as 16 waves x 7 blocks has its whole weight in flight).  Llama-3-8B, same run, five shapes /
+    // merged: 765 -> 818 / 846 -> 906 tok/s (profiles/int4_modes_r03.jsonl); mode 97 = the ring kernel everywhere
+    const int64_t kbl = K >> 7;
+    for (int d : {4, 7, 14, 2})
+      if (kbl % d == 0 && kbl / d >= 4 && kbl / d <= 16) return tile_form(1, d, true);
+    // round 6: K of other models that none of the four factors -- 8 blocks (K = 10240 / 12288 / 16384: 10 / 12 / 16 waves) and 9 (K = 13824,
+    // Llama-2-13B's down_proj: 12 waves) -- had fallen to the ring kernel (mode 97 = that, for A/B: profiles/int4_depth_other_r06.jsonl)
+    // Ahead on weights of up to 768 n-tiles (4096 x 12288 10.3 -> 9.1 us, 5120 x 13824 17.1 -> 16.0, 12288^2 22.8 -> 21.8, 6144 x 16384 19.5 -> 19.0),
+    // behind on wider ones (13824 x 10240 23.7 -> 27.2, 14336 x 16384 35.2 -> 37.7: 10 - 16 waves per workgroup x 864+ workgroups), which keep the ring.
+    if ((N >> 4) <= 768)
+      for (int d : {8, 9})
+        if (kbl % d == 0 && kbl / d >= 4 && kbl / d <= 16) return tile_form(1, d, true);
   }
-  // 4 < M: int4_mm_rb_kernel on slabs of 16 / 32 / 64 / 128 rows (MT m-tiles: only the rows that exist are staged, read and
-  // multiplied).  128-column tiles (8 waves) when that still gives ~a workgroup per CU; otherwise 64-column tiles (4 waves) cut
-  // along K into at most 8 parts of >= 8 k-blocks so that the grid fills the chip (Llama-3-8B projections at M = 128: o_proj
-  // 39.8 -> 14.6 us, down_proj 129 -> 29.6 us).  Modes 600 + 10 a + S (128-row slabs; wpb 8 / 4 waves, S parts, a = ablation /
-  // trace build) and 700 + 10 log2(MT) + S: tuning / profiling.
+  if (M == 1) return tile_form(1);
+  if (M <= 4) return tile_form(4);
+  // round 4: an 8-row build between the 4- and the 16-row one (half the x requests, LDS staging and slab of the 16-row build for batches
+  // of 5 .. 8; mode 88 = the 16-row build as before, for A/B)
+  return tile_form(M <= 8 && rows8 ? 8 : 16);
+}
+
+// Round 5: the 128 x 128 / 32 x 32 x 16 kernel with DMA-producer waves (int4_mm_w32_kernel) from 129 rows on, and on wide weights
+// (>= 64 column tiles) from 65 rows.  profiles/int4_w32_ab_r05.jsonl, cold, us (this dispatch before -> after): M = 256 qkv 32.8 -> 26.9,
+// o 21.6 -> 21.5, gate 49.2 -> 37.9, down 56.1 -> 44.2; M = 2048 gate 320 -> 281, down 301 -> 267; M = 128 gate 29.0 -> 28.2 (qkv, o, down
+// stay: 48 / 32 column tiles need 5 - 8 K parts of 64 KiB partial tiles to fill the chip, 20.4 / 15.0 / 31.7 vs 22.0 / 21.7 / 34.1).
+bool w32_band(int64_t M, int64_t N) { return M > 64 && (M > 128 || (N + 127) / 128 >= 64); }
+Int4Route w32_route(int64_t M, int64_t N, int64_t K, int G, bool tiles64 = true) {
+  // Round 6: 64-column wave tiles (128 x 256 workgroup tiles) where one K part of them fills whole rounds of the chip -- the tile is twice as
+  // large, so the last round has to be >= 7/8 full -- from 512 rows, group sizes >= 128 (int4_mm_w32_tiles64).  profiles/int4_w64_ab_r06.jsonl,
+  // cold, us: M = 512 gate 70.7 -> 64.1; M = 2048 o 79.7 -> 72.8, down 262 -> 238, gate 278 -> 266; qkv at M = 2048 (384 tiles = 1.5 rounds)
+  // 117 -> 121 and every shape below 200 tiles (K parts of a 128 KiB partial tile) 1.3 - 4 x slower: those keep the 128 x 128 tile.  Mode 912: never.
+  if (G >= 128 && tiles64 && int4_mm_w32_tiles64(M, N)) return w32_form(2, true, 1);
+  const int64_t base8 = std::max<int64_t>(1, ((N + 127) / 128) * ((M + 127) / 128));
+  const int64_t fit8 = (int64_t)kSplitMaxTiles / base8;
+  return w32_form(1, true, (int)std::max<int64_t>(1, std::min<int64_t>({256 / base8, fit8, 8, (K >> 7) / 4})));
+}
+
+// 4 < M: int4_mm_rb_kernel on slabs of 16 / 32 / 64 / 128 rows (MT m-tiles: only the rows that exist are staged, read and
+// multiplied).  128-column tiles (8 waves) when that still gives ~a workgroup per CU; otherwise 64-column tiles (4 waves) cut
+// along K into at most 8 parts of >= 8 k-blocks so that the grid fills the chip (Llama-3-8B projections at M = 128: o_proj
+// 39.8 -> 14.6 us, down_proj 129 -> 29.6 us).  waves / forced_split 0: by rule; prod: the producer form for one 128-row slab (mode 910: never).
+Int4Route rb_route(int64_t M, int64_t N, int64_t K, int mt, int waves = 0, int forced_split = 0, bool prod = true) {
   const int64_t kblocks = K >> 7;
-  int mt = (M <= 16) ? 1 : (M <= 32) ? 2 : (M <= 64) ? 4 : 8;
-  int forced_split = 0, waves = 0;
-  if (g_tune_mode >= 600 && g_tune_mode < 700) {
-    const int abl = (g_tune_mode - 600) / 10;
-    mt = 8;
-    waves = (g_tune_wpb == 4) ? 4 : 8;
-    forced_split = std::max(1, g_tune_mode % 10);
-    if constexpr (G == 128) {
-      const int64_t base = ((N + 127) / 128) * ((M + 127) / 128);
-      const int sp = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)forced_split, kblocks, kSplitMaxTiles / std::max<int64_t>(base, 1)}));
-#ifdef AO_LAB  // 1 - 4: parts of the k-block removed (wrong results): laboratory library only
-      if (abl == 1) return launch_mm_rb<G, 8, 1, 8, 1>(x, qdata, sz, y, M, N, K, sp, stream);
-      if (abl == 2) return launch_mm_rb<G, 8, 1, 8, 2>(x, qdata, sz, y, M, N, K, sp, stream);
-      if (abl == 3) return launch_mm_rb<G, 8, 1, 8, 3>(x, qdata, sz, y, M, N, K, sp, stream);
-      if (abl == 4) return launch_mm_rb<G, 8, 1, 8, 4>(x, qdata, sz, y, M, N, K, sp, stream);
-#endif
-      if (abl == 5) return launch_mm_rb<G, 8, 1, 8, 5>(x, qdata, sz, y, M, N, K, sp, stream);
-      if (abl == 6) return launch_mm_rb<G, 4, 2>(x, qdata, sz, y, M, N, K, sp, stream);
-    }
-  } else if (g_tune_mode >= 900 && g_tune_mode < 910 && M > 64) {
-    // profiling: the producer-wave form (4 consumers + 4 DMA producers, 128-row slabs), 90S = S K-parts (900: as the product picks)
-    const int64_t base9 = ((N + 63) / 64) * ((M + 127) / 128);
-    const int64_t fit9 = (int64_t)kSplitMaxTiles * 128 * 128 / (base9 * 64 * 128);
-    const int sp = (g_tune_mode == 900) ? (int)std::max<int64_t>(1, std::min<int64_t>({256 / base9, fit9, 8, kblocks / 8}))
-                                        : (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)(g_tune_mode - 900), kblocks, fit9}));
-    return launch_mm_rb<G, 4, 1, 8, 0, true>(x, qdata, sz, y, M, N, K, sp, stream);
-#ifdef AO_LAB
-  } else if (g_tune_mode == 910 && M > 64) {
-    // profiling: the same without the scale / zero DMAs (wrong numbers): what the dword LDS-DMAs cost
-    const int64_t base9 = ((N + 63) / 64) * ((M + 127) / 128);
-    const int64_t fit9 = (int64_t)kSplitMaxTiles * 128 * 128 / (base9 * 64 * 128);
-    return launch_mm_rb<G, 4, 1, 8, 6, true>(x, qdata, sz, y, M, N, K, (int)std::max<int64_t>(1, std::min<int64_t>({256 / base9, fit9, 8, kblocks / 8})), stream);
-#endif
-  } else if (g_tune_mode >= 800 && g_tune_mode < 840 && M > 16) {
-    // profiling (round 3): two n-tiles per wave -- every A fragment read from LDS feeds two MFMAs.  80S / 81S: 64-row slabs x 128
-    // columns (4 waves, fused / with DMA-producer waves), 82S / 83S: 128-row slabs x 128 columns; S = K parts (0: fill ~256 workgroups)
-    const int kind = (g_tune_mode - 800) / 10, s_req = g_tune_mode % 10;
-    const int rows = (kind < 2) ? 64 : 128;
-    const int64_t base8 = ((N + 127) / 128) * ((M + rows - 1) / rows);
-    const int64_t fit8 = (int64_t)kSplitMaxTiles * 128 * 128 / (base8 * 128 * rows);
-    const int sp = (int)std::max<int64_t>(1, s_req == 0 ? std::min<int64_t>({256 / base8, fit8, 8, kblocks / 8}) : std::min<int64_t>({(int64_t)s_req, kblocks, fit8}));
-    if (kind == 0) return launch_mm_rb<G, 4, 2, 4>(x, qdata, sz, y, M, N, K, sp, stream);
-    if (kind == 1) return launch_mm_rb<G, 4, 2, 4, 0, true>(x, qdata, sz, y, M, N, K, sp, stream);
-    if (kind == 2) return launch_mm_rb<G, 4, 2, 8>(x, qdata, sz, y, M, N, K, sp, stream);
-    return launch_mm_rb<G, 4, 2, 8, 0, true>(x, qdata, sz, y, M, N, K, sp, stream);
-  } else if (g_tune_mode >= 920 && g_tune_mode < 940 && M > 64) {
-    // round 5: the 128 x 128 / 32 x 32 x 16 kernel.  92S fused, 93S with DMA-producer waves; S = K parts (0: fill ~256 workgroups)
-    const int s_req = g_tune_mode % 10;
-    const int64_t base8 = ((N + 127) / 128) * ((M + 127) / 128);
-    const int64_t fit8 = (int64_t)kSplitMaxTiles / base8;
-    const int sp = (int)std::max<int64_t>(1, s_req == 0 ? std::min<int64_t>({256 / base8, fit8, 8, kblocks / 4}) : std::min<int64_t>({(int64_t)s_req, kblocks, fit8}));
-    if (g_tune_mode < 930) return launch_mm_w32<G, false>(x, qdata, sz, y, M, N, K, sp, stream);
-    return launch_mm_w32<G, true>(x, qdata, sz, y, M, N, K, sp, stream);
-  } else if (g_tune_mode >= 950 && g_tune_mode < 960 && M > 64 && G >= 128) {
-    // round 6: 64-column wave tiles (128 x 256 workgroup tiles, every A fragment feeds two MFMAs), producer form; 95S: S K parts (0: fill ~256 workgroups).
-    // (The form in which the consumers fetch for themselves -- 4 waves, 424 registers, no spills -- was 5 - 25 % behind this one in every cell of
-    // profiles/int4_w64_ab_r06.jsonl (modes 96S there) and left the tree.)
-    if constexpr (G >= 128) {
-      const int s_req = g_tune_mode % 10;
-      const int64_t base8 = ((N + 255) / 256) * ((M + 127) / 128);
-      const int64_t fit8 = (int64_t)kSplitMaxTiles / (2 * base8);
-      const int sp = (int)std::max<int64_t>(1, s_req == 0 ? std::min<int64_t>({256 / base8, fit8, 8, kblocks / 4}) : std::min<int64_t>({(int64_t)s_req, kblocks, fit8}));
-      return launch_mm_w32<G, true, 0, 2>(x, qdata, sz, y, M, N, K, sp, stream);
-    }
-  } else if (g_tune_mode >= 940 && g_tune_mode < 950 && M > 64) {
-    // profiling: 945 = the producer form with s_memtime stamps; 941 / 942 / 943 (laboratory library only: wrong results) = without the
-    // 32 x 32 x 16 MFMAs / the dequant / the A-fragment reads.  One K part.
-    if constexpr (G == 128) {
-#ifdef AO_LAB
-      if (g_tune_mode == 941) return launch_mm_w32<G, true, 1>(x, qdata, sz, y, M, N, K, 1, stream);
-      if (g_tune_mode == 942) return launch_mm_w32<G, true, 2>(x, qdata, sz, y, M, N, K, 1, stream);
-      if (g_tune_mode == 943) return launch_mm_w32<G, true, 3>(x, qdata, sz, y, M, N, K, 1, stream);
-#endif
-      if (g_tune_mode == 945) return launch_mm_w32<G, true, 5>(x, qdata, sz, y, M, N, K, 1, stream);
-    }
-    return launch_mm_w32<G, true>(x, qdata, sz, y, M, N, K, 1, stream);
-  } else if (g_tune_mode >= 700 && g_tune_mode < 800) {
-    mt = 1 << std::min(3, (g_tune_mode - 700) / 10);
-    waves = (g_tune_wpb == 8 && mt >= 2) ? 8 : 4;
-    forced_split = std::max(1, g_tune_mode % 10);
-  }
-  // Round 5: the 128 x 128 / 32 x 32 x 16 kernel with DMA-producer waves (int4_mm_w32_kernel) from 129 rows on, and on wide weights
-  // (>= 64 column tiles) from 65 rows.  profiles/int4_w32_ab_r05.jsonl, cold, us (this dispatch before -> after): M = 256 qkv 32.8 -> 26.9,
-  // o 21.6 -> 21.5, gate 49.2 -> 37.9, down 56.1 -> 44.2; M = 2048 gate 320 -> 281, down 301 -> 267; M = 128 gate 29.0 -> 28.2 (qkv, o, down
-  // stay: 48 / 32 column tiles need 5 - 8 K parts of 64 KiB partial tiles to fill the chip, 20.4 / 15.0 / 31.7 vs 22.0 / 21.7 / 34.1).
-  // Mode 911: never (the round-4 dispatch, for A/B).
-  if (g_tune_mode != 911 && (g_tune_mode < 600 || g_tune_mode == 912) && forced_split == 0 && waves == 0 && M > 64 && (M > 128 || (N + 127) / 128 >= 64)) {
-    // Round 6: 64-column wave tiles (128 x 256 workgroup tiles) where one K part of them fills whole rounds of the chip -- the tile is twice as
-    // large, so the last round has to be >= 7/8 full -- from 512 rows, group sizes >= 128 (int4_mm_w32_tiles64).  profiles/int4_w64_ab_r06.jsonl,
-    // cold, us: M = 512 gate 70.7 -> 64.1; M = 2048 o 79.7 -> 72.8, down 262 -> 238, gate 278 -> 266; qkv at M = 2048 (384 tiles = 1.5 rounds)
-    // 117 -> 121 and every shape below 200 tiles (K parts of a 128 KiB partial tile) 1.3 - 4 x slower: those keep the 128 x 128 tile.  Mode 912: never.
-    if constexpr (G >= 128) {
-      if (g_tune_mode != 912 && int4_mm_w32_tiles64(M, N)) return launch_mm_w32<G, true, 0, 2>(x, qdata, sz, y, M, N, K, 1, stream);
-    }
-    const int64_t base8 = ((N + 127) / 128) * ((M + 127) / 128);
-    const int64_t fit8 = (int64_t)kSplitMaxTiles / base8;
-    const int sp = (int)std::max<int64_t>(1, std::min<int64_t>({256 / base8, fit8, 8, kblocks / 4}));
-    return launch_mm_w32<G, true>(x, qdata, sz, y, M, N, K, sp, stream);
-  }
   const int64_t slabs = (M + 16 * mt - 1) / (16 * mt);
   // (32-row slabs: 4 waves x K parts beat the 8-wave tile that cuts nothing -- 28672 x 8192 at M = 24 / 32: 53 -> 43.5 us)
   if (waves == 0) waves = (mt >= 4 && ((N + 127) / 128) * slabs >= 190) ? 8 : 4;
   const int bn = waves * 16;
-  const int64_t base = ((N + bn - 1) / bn) * slabs;
+  const int64_t base = std::max<int64_t>(1, ((N + bn - 1) / bn) * slabs);
   const int64_t fit = (int64_t)kSplitMaxTiles * 128 * 128 / (base * bn * 16 * mt);
   int split = 1;
   if (forced_split > 0) split = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)forced_split, kblocks, fit}));
@@ -1362,21 +1283,207 @@ int dispatch_mm(const uint16_t* x, const int32_t* qdata, const uint16_t* sz, uin
     split = (int)std::max<int64_t>(1, std::min<int64_t>({std::max<int64_t>(base <= 512 ? 4 : 1, 1024 / base), fit, 8, kblocks / 4}));
   else if (waves == 4 && mt == 4) split = (int)std::max<int64_t>(1, std::min<int64_t>({512 / base, fit, 8, kblocks / 8}));
   else if (waves == 4) split = (int)std::max<int64_t>(1, std::min<int64_t>({256 / base, fit, 8, kblocks / 8}));
-  if (waves == 8) {
-    if (mt == 8) return launch_mm_rb<G, 8, 1, 8>(x, qdata, sz, y, M, N, K, split, stream);
-    if (mt == 4) return launch_mm_rb<G, 8, 1, 4>(x, qdata, sz, y, M, N, K, split, stream);
-    return launch_mm_rb<G, 8, 1, 2>(x, qdata, sz, y, M, N, K, split, stream);
+  // one 128-row slab (65 .. 128 rows: the "bs = 128" half of the BASELINE metric): the form with DMA-producer waves -- Llama-3-8B
+  // at bs = 128 32.3k -> 35.4k tok/s (gate_proj 28.2 -> 25.5 us, same bits); with two or more slabs the two forms measure the
+  // same (bs = 256) or the fused form wins (bs = 2048: 57k vs 50k tok/s)
+  return rb_form(waves, 1, waves == 8 && mt < 4 ? 2 : mt, split, 0, prod && waves == 4 && mt == 8 && slabs == 1);
+}
+
+// The forms the A/B modes of ao_int4_set_tuning force (every one but the laboratory ablations computes the product's result).
+// Modes 93-99 / 88: the per-tile builds (94 never / 93 always the batched kernel on wide weights at M <= 16, 97 the ring kernel at M = 1
+// whatever K, 98 the 4-row build at M = 1, 99 the 16-row build at any M, 88 no 8-row build).  600 + 10 a + S: 128-row slabs (wpb 8 / 4
+// waves, S parts, a = ablation / trace build); 700 + 10 log2(MT) + S: MT m-tiles, S parts; 80S - 83S, 90S, 910, 92S / 93S, 94x, 95S: the
+// other batched / 32 x 32 x 16 forms; 911 / 912: never the 32 x 32 x 16 kernel / its 128 x 256 tile.
+Int4Route int4_forced_route(int64_t M, int64_t N, int64_t K, int G, const Int4Force& f) {
+  const int mode = f.mode;
+  const bool wide = (N >> 4) >= 1024 && mode != 94, tall = M > 8 && (N >> 4) >= 288 && mode != 94;
+  if (M == 1 && mode == 98) return tile_form(4);
+  if (mode == 99) return tile_form(16);
+  if (M <= 16 && mode < 600 && !tall && !(wide && (M > 4 || mode == 93))) return tile_route(M, N, K, mode == 97, mode != 88);
+  const int64_t kblocks = K >> 7;
+  int mt = (M <= 16) ? 1 : (M <= 32) ? 2 : (M <= 64) ? 4 : 8;
+  int forced_split = 0, waves = 0;
+  if (mode >= 600 && mode < 700) {
+    const int abl = (mode - 600) / 10;
+    mt = 8;
+    waves = (f.wpb == 4) ? 4 : 8;
+    forced_split = std::max(1, mode % 10);
+    if (G == 128) {
+      const int64_t base = ((N + 127) / 128) * ((M + 127) / 128);
+      const int sp = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)forced_split, kblocks, kSplitMaxTiles / std::max<int64_t>(base, 1)}));
+#ifdef AO_LAB  // 1 - 4: parts of the k-block removed (wrong results): laboratory library only
+      if (abl >= 1 && abl <= 4) return rb_form(8, 1, 8, sp, abl);
+#endif
+      if (abl == 5) return rb_form(8, 1, 8, sp, 5);
+      if (abl == 6) return rb_form(4, 2, 8, sp);
+    }
+  } else if (mode >= 900 && mode < 910 && M > 64) {
+    // profiling: the producer-wave form (4 consumers + 4 DMA producers, 128-row slabs), 90S = S K-parts (900: as the product picks)
+    const int64_t base9 = std::max<int64_t>(1, ((N + 63) / 64) * ((M + 127) / 128));
+    const int64_t fit9 = (int64_t)kSplitMaxTiles * 128 * 128 / (base9 * 64 * 128);
+    const int sp = (mode == 900) ? (int)std::max<int64_t>(1, std::min<int64_t>({256 / base9, fit9, 8, kblocks / 8}))
+                                 : (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)(mode - 900), kblocks, fit9}));
+    return rb_form(4, 1, 8, sp, 0, true);
+#ifdef AO_LAB
+  } else if (mode == 910 && M > 64) {
+    // profiling: the same without the scale / zero DMAs (wrong numbers): what the dword LDS-DMAs cost
+    const int64_t base9 = std::max<int64_t>(1, ((N + 63) / 64) * ((M + 127) / 128));
+    const int64_t fit9 = (int64_t)kSplitMaxTiles * 128 * 128 / (base9 * 64 * 128);
+    return rb_form(4, 1, 8, (int)std::max<int64_t>(1, std::min<int64_t>({256 / base9, fit9, 8, kblocks / 8})), 6, true);
+#endif
+  } else if (mode >= 800 && mode < 840 && M > 16) {
+    // profiling (round 3): two n-tiles per wave -- every A fragment read from LDS feeds two MFMAs.  80S / 81S: 64-row slabs x 128
+    // columns (4 waves, fused / with DMA-producer waves), 82S / 83S: 128-row slabs x 128 columns; S = K parts (0: fill ~256 workgroups)
+    const int kind = (mode - 800) / 10, s_req = mode % 10;
+    const int rows = (kind < 2) ? 64 : 128;
+    const int64_t base8 = std::max<int64_t>(1, ((N + 127) / 128) * ((M + rows - 1) / rows));
+    const int64_t fit8 = (int64_t)kSplitMaxTiles * 128 * 128 / (base8 * 128 * rows);
+    const int sp = (int)std::max<int64_t>(1, s_req == 0 ? std::min<int64_t>({256 / base8, fit8, 8, kblocks / 8}) : std::min<int64_t>({(int64_t)s_req, kblocks, fit8}));
+    return rb_form(4, 2, rows / 16, sp, 0, kind % 2 == 1);
+  } else if (mode >= 920 && mode < 940 && M > 64) {
+    // round 5: the 128 x 128 / 32 x 32 x 16 kernel.  92S fused, 93S with DMA-producer waves; S = K parts (0: fill ~256 workgroups)
+    const int s_req = mode % 10;
+    const int64_t base8 = std::max<int64_t>(1, ((N + 127) / 128) * ((M + 127) / 128));
+    const int64_t fit8 = (int64_t)kSplitMaxTiles / base8;
+    const int sp = (int)std::max<int64_t>(1, s_req == 0 ? std::min<int64_t>({256 / base8, fit8, 8, kblocks / 4}) : std::min<int64_t>({(int64_t)s_req, kblocks, fit8}));
+    return w32_form(1, mode >= 930, sp);
+  } else if (mode >= 950 && mode < 960 && M > 64 && G >= 128) {
+    // round 6: 64-column wave tiles (128 x 256 workgroup tiles, every A fragment feeds two MFMAs), producer form; 95S: S K parts (0: fill ~256 workgroups).
+    // (The form in which the consumers fetch for themselves -- 4 waves, 424 registers, no spills -- was 5 - 25 % behind this one in every cell of
+    // profiles/int4_w64_ab_r06.jsonl (modes 96S there) and left the tree.)
+    const int s_req = mode % 10;
+    const int64_t base8 = std::max<int64_t>(1, ((N + 255) / 256) * ((M + 127) / 128));
+    const int64_t fit8 = (int64_t)kSplitMaxTiles / (2 * base8);
+    const int sp = (int)std::max<int64_t>(1, s_req == 0 ? std::min<int64_t>({256 / base8, fit8, 8, kblocks / 4}) : std::min<int64_t>({(int64_t)s_req, kblocks, fit8}));
+    return w32_form(2, true, sp);
+  } else if (mode >= 940 && mode < 950 && M > 64) {
+    // profiling: 945 = the producer form with s_memtime stamps; 941 / 942 / 943 (laboratory library only: wrong results) = without the
+    // 32 x 32 x 16 MFMAs / the dequant / the A-fragment reads.  One K part.
+    if (G == 128) {
+#ifdef AO_LAB
+      if (mode >= 941 && mode <= 943) return w32_form(1, true, 1, mode - 940);
+#endif
+      if (mode == 945) return w32_form(1, true, 1, 5);
+    }
+    return w32_form(1, true, 1);
+  } else if (mode >= 700 && mode < 800) {
+    mt = 1 << std::min(3, (mode - 700) / 10);
+    waves = (f.wpb == 8 && mt >= 2) ? 8 : 4;
+    forced_split = std::max(1, mode % 10);
   }
-  if (mt == 8) {
-    // one 128-row slab (65 .. 128 rows: the "bs = 128" half of the BASELINE metric): the form with DMA-producer waves -- Llama-3-8B
-    // at bs = 128 32.3k -> 35.4k tok/s (gate_proj 28.2 -> 25.5 us, same bits); with two or more slabs the two forms measure the
-    // same (bs = 256) or the fused form wins (bs = 2048: 57k vs 50k tok/s).  Mode 910: never.
-    if (slabs == 1 && g_tune_mode != 910) return launch_mm_rb<G, 4, 1, 8, 0, true>(x, qdata, sz, y, M, N, K, split, stream);
-    return launch_mm_rb<G, 4, 1, 8>(x, qdata, sz, y, M, N, K, split, stream);
+  if (mode != 911 && (mode < 600 || mode == 912) && forced_split == 0 && waves == 0 && w32_band(M, N)) return w32_route(M, N, K, G, mode != 912);
+  return rb_route(M, N, K, mt, waves, forced_split, mode != 910);
+}
+
+// The route of ao_int4_weight_int4pack_mm (group size G); with f = Int4Force{} the product dispatch, which ao_int4_mm_kernel_name reports.
+Int4Route int4_route(int64_t M, int64_t N, int64_t K, int G, const Int4Force& f) {
+  Int4Route r;
+  if (f.mode != 0) r = int4_forced_route(M, N, K, G, f);
+  // M <= 16: one workgroup per 16-wide n-tile, waves split K (int4_mm_kernel, built for 1, 4, 8 or 16 rows).  In the hipGraph
+  // bench the single-row build beat both purpose-built decode kernels this round tried (a persistent balanced streaming kernel
+  // with hand-counted LDS-DMA rings and a per-tile kernel with workgroup-shared x): 868 vs 732 tok/s.
+  // At 4 < M <= 16 the per-tile kernel re-reads x for every 16 output columns (4 KiB of x per 1 KiB of weights at 16 rows): fine
+  // for the narrow projections, 1.5x the M = 1 time on wide ones -- weights of >= 1024 n-tiles (merged gate_up_proj, lm_head) take
+  // the batched kernel below with 16-row slabs, where 4 n-tiles share one staged x tile (gate_up_proj at M = 16: 32 -> 21.8 us).
+  // (At M <= 4 the same switch measured 16.2 vs 17.4 us on one box and 19.7 vs 14.2 us on another: not taken.)
+  // Round 6 (profiles/int4_forms_r06.jsonl, int4_forms_parts_r06.jsonl: 16 shapes of four models x M = 5 .. 16 x 9 forms, cold): the 16-row per-tile
+  // build (9 .. 16 rows) is 1.3 - 1.6 x the 8-row build's time, and from 288 n-tiles on the batched kernel's 16-row slabs with K parts pass it --
+  // gate 14336 x 4096 at M = 12 / 16 19.0 / 19.4 -> 14.1 us, 15360 x 5120 25.1 / 26.5 -> 16.6 / 16.8, 5120 x 13824 25.7 -> 17.4, 10240 x 8192
+  // 24.0 / 25.3 -> 17.5 / 17.9, qkv 6144 x 4096 10.0 / 10.2 -> 9.5; at 224 - 256 n-tiles (o 4096^2: 6.2 against 8.5) and up to 8 rows the per-tile
+  // kernel stays ahead.
+  else if (M <= 16 && !(M > 8 && (N >> 4) >= 288) && !(M > 4 && (N >> 4) >= 1024)) r = tile_route(M, N, K);
+  else if (w32_band(M, N)) r = w32_route(M, N, K, G);
+  else r = rb_route(M, N, K, (M <= 16) ? 1 : (M <= 32) ? 2 : (M <= 64) ? 4 : 8);
+  r.wpb = f.wpb;  // (the per-tile kernel's waves per workgroup; ao_int4_set_tuning)
+  return r;
+}
+
+#define AO_MM_ARGS x, qdata, sz, y, M, N, K
+
+// the template instantiation of a route
+template <int G>
+int launch_route(const Int4Route& r, const uint16_t* x, const int32_t* qdata, const uint16_t* sz, uint16_t* y, int64_t M, int64_t N, int64_t K,
+                 hipStream_t stream) {
+  const int s = r.split;
+  switch (r.form) {
+    case Int4Route::Tile:
+      if (r.rows == 1 && r.straight) {
+        switch (r.depth) {
+          case 4: return launch_mm<G, 1, 4>(AO_MM_ARGS, stream, true, r.wpb);
+          case 7: return launch_mm<G, 1, 7>(AO_MM_ARGS, stream, true, r.wpb);
+          case 14: return launch_mm<G, 1, 14>(AO_MM_ARGS, stream, true, r.wpb);
+          case 2: return launch_mm<G, 1, 2>(AO_MM_ARGS, stream, true, r.wpb);
+          case 8: return launch_mm<G, 1, 8>(AO_MM_ARGS, stream, true, r.wpb);
+          case 9: return launch_mm<G, 1, 9>(AO_MM_ARGS, stream, true, r.wpb);
+        }
+        break;
+      }
+      switch (r.rows) {
+        case 1: return launch_mm<G, 1>(AO_MM_ARGS, stream, false, r.wpb);
+        case 4: return launch_mm<G, 4>(AO_MM_ARGS, stream, false, r.wpb);
+        case 8: return launch_mm<G, 8>(AO_MM_ARGS, stream, false, r.wpb);
+        case 16: return launch_mm<G, 16>(AO_MM_ARGS, stream, false, r.wpb);
+      }
+      break;
+    case Int4Route::Rb:
+      if (r.waves == 8 && r.abl != 0) {
+        if constexpr (G == 128) {
+#ifdef AO_LAB
+          if (r.abl == 1) return launch_mm_rb<G, 8, 1, 8, 1>(AO_MM_ARGS, s, stream);
+          if (r.abl == 2) return launch_mm_rb<G, 8, 1, 8, 2>(AO_MM_ARGS, s, stream);
+          if (r.abl == 3) return launch_mm_rb<G, 8, 1, 8, 3>(AO_MM_ARGS, s, stream);
+          if (r.abl == 4) return launch_mm_rb<G, 8, 1, 8, 4>(AO_MM_ARGS, s, stream);
+#endif
+          if (r.abl == 5) return launch_mm_rb<G, 8, 1, 8, 5>(AO_MM_ARGS, s, stream);
+        }
+        break;
+      }
+#ifdef AO_LAB
+      if (r.abl == 6) return launch_mm_rb<G, 4, 1, 8, 6, true>(AO_MM_ARGS, s, stream);
+#endif
+      if (r.abl != 0) break;
+      if (r.nt == 2) {
+        if (r.mt == 4) return r.prod ? launch_mm_rb<G, 4, 2, 4, 0, true>(AO_MM_ARGS, s, stream) : launch_mm_rb<G, 4, 2, 4>(AO_MM_ARGS, s, stream);
+        return r.prod ? launch_mm_rb<G, 4, 2, 8, 0, true>(AO_MM_ARGS, s, stream) : launch_mm_rb<G, 4, 2, 8>(AO_MM_ARGS, s, stream);
+      }
+      if (r.waves == 8) {
+        if (r.mt == 8) return launch_mm_rb<G, 8, 1, 8>(AO_MM_ARGS, s, stream);
+        if (r.mt == 4) return launch_mm_rb<G, 8, 1, 4>(AO_MM_ARGS, s, stream);
+        return launch_mm_rb<G, 8, 1, 2>(AO_MM_ARGS, s, stream);
+      }
+      if (r.mt == 8) return r.prod ? launch_mm_rb<G, 4, 1, 8, 0, true>(AO_MM_ARGS, s, stream) : launch_mm_rb<G, 4, 1, 8>(AO_MM_ARGS, s, stream);
+      if (r.mt == 4) return launch_mm_rb<G, 4, 1, 4>(AO_MM_ARGS, s, stream);
+      if (r.mt == 2) return launch_mm_rb<G, 4, 1, 2>(AO_MM_ARGS, s, stream);
+      return launch_mm_rb<G, 4, 1, 1>(AO_MM_ARGS, s, stream);
+    case Int4Route::W32:
+      if (!r.prod) return launch_mm_w32<G, false>(AO_MM_ARGS, s, stream);
+      if (r.cg == 2) {
+        if constexpr (G >= 128) return launch_mm_w32<G, true, 0, 2>(AO_MM_ARGS, s, stream);
+        break;
+      }
+      if (r.abl != 0) {
+        if constexpr (G == 128) {
+#ifdef AO_LAB
+          if (r.abl == 1) return launch_mm_w32<G, true, 1>(AO_MM_ARGS, s, stream);
+          if (r.abl == 2) return launch_mm_w32<G, true, 2>(AO_MM_ARGS, s, stream);
+          if (r.abl == 3) return launch_mm_w32<G, true, 3>(AO_MM_ARGS, s, stream);
+#endif
+          if (r.abl == 5) return launch_mm_w32<G, true, 5>(AO_MM_ARGS, s, stream);
+        }
+        break;
+      }
+      return launch_mm_w32<G, true>(AO_MM_ARGS, s, stream);
   }
-  if (mt == 4) return launch_mm_rb<G, 4, 1, 4>(x, qdata, sz, y, M, N, K, split, stream);
-  if (mt == 2) return launch_mm_rb<G, 4, 1, 2>(x, qdata, sz, y, M, N, K, split, stream);
-  return launch_mm_rb<G, 4, 1, 1>(x, qdata, sz, y, M, N, K, split, stream);
+  set_error("int4_mm: no instantiation for form %d (rows %d, depth %d, waves %d, mt %d, abl %d, cg %d)", (int)r.form, r.rows, r.depth, r.waves, r.mt,
+            r.abl, r.cg);
+  return AO_ERR_INVALID_ARGUMENT;
+}
+#undef AO_MM_ARGS
+
+template <int G>
+int dispatch_mm(const uint16_t* x, const int32_t* qdata, const uint16_t* sz, uint16_t* y, int64_t M,
+                int64_t N, int64_t K, hipStream_t stream) {
+  return launch_route<G>(int4_route(M, N, K, G, g_int4_force), x, qdata, sz, y, M, N, K, stream);
 }
 
 int check_int4_shape(const char* fn, int64_t N, int64_t K, int group_size) {
@@ -1397,12 +1504,11 @@ int check_int4_shape(const char* fn, int64_t N, int64_t K, int group_size) {
 
 using namespace ao;
 
+// the product route's kernel (int4_route with no override; host logic only)
 extern "C" const char* ao_int4_mm_kernel_name(int64_t M, int64_t N, int64_t K, int group_size) {
-  (void)K;
-  if (M > 64 && (M > 128 || (N + 127) / 128 >= 64))  // round 5: 128 x 128 tiles, 32 x 32 x 16 MFMAs; round 6: 128 x 256 where they fill whole rounds
-    return (group_size >= 128 && int4_mm_w32_tiles64(M, N)) ? "int4_mm_w32_kernel<128x256>" : "int4_mm_w32_kernel";
-  if (M > 16 || (M > 4 && (N >> 4) >= 1024) || (M > 8 && (N >> 4) >= 288)) return "int4_mm_rb_kernel";  // (round 6: 9 .. 16 rows from 288 n-tiles)
-  return "int4_mm_kernel";
+  const Int4Route r = int4_route(M, N, K, group_size, Int4Force{});
+  if (r.form == Int4Route::W32) return r.cg == 2 ? "int4_mm_w32_kernel<128x256>" : "int4_mm_w32_kernel";
+  return r.form == Int4Route::Rb ? "int4_mm_rb_kernel" : "int4_mm_kernel";
 }
 
 extern "C" int ao_int4_set_trace(unsigned long long* trace_dev) {
@@ -1411,12 +1517,15 @@ extern "C" int ao_int4_set_trace(unsigned long long* trace_dev) {
   return AO_OK;
 }
 
-namespace ao { void fp8_int4_set_mt(int mt, bool nt1); }  // fp8_int4_kernels.hip
+const Int4Force& ao::int4_force() { return g_int4_force; }
+
 extern "C" int ao_int4_set_tuning(int waves_per_block, int mode) {
-  g_tune_wpb = waves_per_block;
-  g_tune_mode = mode;
+  Int4Force& f = g_int4_force;
+  f.wpb = waves_per_block;
+  f.mode = mode;
   // fp8-act x int4: 961 / 962 / 964 m-tiles per workgroup forced; 970 / 972 / 974: one n-tile per workgroup (0 / 2 / 4 m-tiles: 0 = by M)
-  ao::fp8_int4_set_mt((mode == 961 || mode == 962 || mode == 964) ? mode - 960 : (mode == 972 || mode == 974) ? mode - 970 : 0, mode >= 970 && mode <= 974);
+  f.fp8_mt = (mode == 961 || mode == 962 || mode == 964) ? mode - 960 : (mode == 972 || mode == 974) ? mode - 970 : 0;
+  f.fp8_nt1 = mode >= 970 && mode <= 974;
   return AO_OK;
 }
 

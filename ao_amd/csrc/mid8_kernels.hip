@@ -21,6 +21,7 @@
 //     than cast + matmul (profiles/mid8_sweep_r04.txt) and its ticket / time-out paths were the round-4 advisor's two
 //     findings; round 5 removed it.
 #include "common.h"
+#include "gemm8_route.h"
 #include "quant_math.h"
 #include "splitk.h"
 
@@ -28,7 +29,6 @@
 #include <type_traits>
 
 namespace ao {
-thread_local int g_mid8_mode = 0;  // ao_gemm8_set_variant 300: never this kernel; 301: always (where the shape allows); 31S: force S K-parts
 namespace {
 
 typedef int i32x8 __attribute__((ext_vector_type(8)));
@@ -198,27 +198,26 @@ __global__ __launch_bounds__(512, 4) void mid8_kernel(Mid8Args p) {
 
 constexpr int kG = 4;  // ring depth of the k loop (G x 2 KiB per wave in flight; 16 waves per CU)
 
-struct Mid8Plan {
-  int mt, split;
-};
+}  // namespace
 
 // Rows: 32 / 64 / 128-row slabs.  K parts: ~one workgroup per CU, parts that divide the K steps evenly.
 // Product dispatch (cold weights, 70B / TP8 fp8 shards, profiles/mid8_sweep_r04.txt): the kernel beats the round-3 paths at
 // 17 .. 32 rows on long K (qkv 1280 x 8192 at M = 32: 11.1 us against 15.1; gate_up 7168 x 8192: 17.2 against 27.8) and loses
 // everywhere else (M = 128: qkv 21 us against rb8_kernel's 16, gate_up 28 against 26.5, down 27 against 19 -- its k loop waits on
 // activation / weight requests only 2 / 4 steps old and on every A-fragment read, at the 128 VGPRs of four waves per SIMD), so that
-// is all it takes by itself; 301 / 31S force it anywhere for A/B runs and the parity tests.
-bool mid8_plan(int64_t M, int64_t N, int64_t K, Mid8Plan* out) {
-  if (g_mid8_mode == 300) return false;
+// is all it takes by itself.  mode (ao_gemm8_set_variant): 300 never; 301 / 31S force it anywhere for A/B runs and the parity tests, 31S with S
+// K parts.
+bool mid8_plan(int64_t M, int64_t N, int64_t K, int mode, Mid8Plan* out) {
+  if (mode == 300) return false;
   if (M <= 16 || M > 256 || N % 16 != 0 || K % (128 * kG) != 0 || M * K >= (1ll << 31) || N * K >= (1ll << 31)) return false;
-  const bool forced = g_mid8_mode == 301 || (g_mid8_mode >= 310 && g_mid8_mode < 330);
+  const bool forced = mode == 301 || (mode >= 310 && mode < 330);
   if (!forced && !(M <= 32 && K >= 4096)) return false;
   const int mt = (M <= 32) ? 2 : (M <= 64) ? 4 : 8;
   const int64_t slabs = (M + 16 * mt - 1) / (16 * mt), cols = (N + 127) / 128, groups = K / (128 * kG);
   const int64_t base = cols * slabs;
   if (!forced && base >= 400) return false;  // enough tiles for the tiled GEMMs
   int64_t want = std::max<int64_t>(1, 256 / base);
-  if (g_mid8_mode >= 310 && g_mid8_mode < 330) want = g_mid8_mode - 310;
+  if (mode >= 310 && mode < 330) want = mode - 310;
   int split = 1;
   for (int64_t s = 1; s <= std::min<int64_t>(groups, 16); ++s)
     if (groups % s == 0 && s <= want) split = (int)s;
@@ -235,6 +234,8 @@ bool mid8_plan(int64_t M, int64_t N, int64_t K, Mid8Plan* out) {
   *out = Mid8Plan{mt, split};
   return true;
 }
+
+namespace {
 
 template <bool INT8, int MT>
 int launch_mid8(Mid8Args p, int split, hipStream_t stream) {
@@ -264,19 +265,8 @@ int run_mid8(const Mid8Args& p, const Mid8Plan& plan, hipStream_t stream) {
 
 }  // namespace
 
-bool mid8_takes(int64_t M, int64_t N, int64_t K) {
-  Mid8Plan plan;
-  return mid8_plan(M, N, K, &plan);
-}
-bool mid8_takes_fused(int64_t M, int64_t N, int64_t K) { return K <= 16384 && mid8_takes(M, N, K); }
-
 int mid8_scaled(bool int8, const void* a, const float* scale_a, const void* b, const float* scale_b, const uint16_t* bias, uint16_t* y, int64_t M,
-                int64_t N, int64_t K, hipStream_t stream) {
-  Mid8Plan plan;
-  if (!mid8_plan(M, N, K, &plan)) {
-    set_error("mid8_scaled: shape M=%lld N=%lld K=%lld not covered", (long long)M, (long long)N, (long long)K);
-    return AO_ERR_INVALID_ARGUMENT;
-  }
+                int64_t N, int64_t K, const Mid8Plan& plan, hipStream_t stream) {
   Mid8Args p{};
   p.a = static_cast<const uint8_t*>(a); p.b = static_cast<const uint8_t*>(b); p.scale_a = scale_a; p.scale_b = scale_b; p.bias = bias; p.y = y;
   p.M = (int)M; p.N = (int)N; p.K = (int)K;
@@ -286,12 +276,7 @@ int mid8_scaled(bool int8, const void* a, const float* scale_a, const void* b, c
 // ao_*_dynamic_linear at 16 < M <= 256: the per-row cast (the stand-alone kernel: same arithmetic, same bits) into a scratch area BEHIND
 // the parts of the meeting in the stream's split-K workspace, then the kernel above on it -- stream-ordered, two launches.
 int mid8_dynamic(bool int8, const uint16_t* x, const void* b, const float* scale_b, const uint16_t* bias, uint16_t* y, int64_t M, int64_t N, int64_t K,
-                 hipStream_t stream) {
-  Mid8Plan plan;
-  if (K > 16384 || !mid8_plan(M, N, K, &plan)) {
-    set_error("mid8_dynamic: shape M=%lld N=%lld K=%lld not covered", (long long)M, (long long)N, (long long)K);
-    return AO_ERR_INVALID_ARGUMENT;
-  }
+                 const Mid8Plan& plan, hipStream_t stream) {
   const size_t tiles = (size_t)((N + 127) / 128) * (size_t)((M + 16 * plan.mt - 1) / (16 * plan.mt));
   const size_t part_floats = (plan.split > 1) ? tiles * (plan.split + (plan.split + 3) / 4) * 128 * 16 * plan.mt : 0;
   const size_t code_floats = ((size_t)M * K + 15) / 16 * 4, scale_floats = (size_t)((M + 3) / 4 * 4);
@@ -301,7 +286,7 @@ int mid8_dynamic(bool int8, const uint16_t* x, const void* b, const float* scale
   uint8_t* xq = reinterpret_cast<uint8_t*>(ws + part_floats);
   float* xs = ws + part_floats + code_floats;
   if (int rc = int8 ? ao_int8_quantize_rowwise(x, reinterpret_cast<int8_t*>(xq), xs, M, K, stream) : ao_fp8_quantize_rowwise(x, xq, xs, M, K, stream)) return rc;
-  return mid8_scaled(int8, xq, xs, b, scale_b, bias, y, M, N, K, stream);
+  return mid8_scaled(int8, xq, xs, b, scale_b, bias, y, M, N, K, plan, stream);
 }
 
 }  // namespace ao

@@ -16,6 +16,7 @@
 // s_waitcnt vmcnt + one LDS-only barrier per step.  K is cut into parts when the grid is small; the
 // parts meet through the fence-free split-K workspace (splitk.h), the last arriver applies the scales.
 #include "common.h"
+#include "gemm8_route.h"
 #include "lds_dma.h"
 #include "quant_math.h"
 #include "splitk.h"
@@ -1132,10 +1133,12 @@ __global__ __launch_bounds__(64 * WAVES) void mx_stream_kernel(Rb8Args p) {
 }
 
 thread_local unsigned long long* g_fp8_rb_trace = nullptr;  // profiling only (ao_int4_set_trace shares the pointer)
-// A/B knobs of the rowwise weight-streaming kernel (ao_gemm8_set_tuning; 0 = product rule): column-tile width, K parts, same-XCD meeting
-thread_local int g_rb8_bn = 0, g_rb8_split = 0, g_rb8_ablate = 0;
-thread_local int g_rb8_bm = 0;  // A/B (ao_gemm8_set_tuning key 3): 64 / 128 = that slab height at any M (0: the cost model's pick)
-thread_local bool g_rb8_sm = true;  // rb8_kernel's 2 x 4 wave arrangement where it is built (ao_gemm8_set_variant 103: off)
+
+// slab rows of the grouped forms: 64 for decode-size groups, else 128 (ao_gemm8_set_tuning key 3 forces a height: A/B)
+int grouped_slab_rows(int64_t M_total, int64_t groups) {
+  const int forced = gemm8_force().rb8_bm;
+  return (forced == 64 || forced == 128) ? forced : (M_total <= 48 * groups) ? 64 : 128;
+}
 
 template <int WAVES, int KIND, int MT = 8, bool SLIM = false, int QS = 1>
 int launch_rb8(Rb8Args p, int split, hipStream_t stream) {
@@ -1164,11 +1167,11 @@ int launch_rb8(Rb8Args p, int split, hipStream_t stream) {
     if (int rc = splitk_workspace(stream, &p.ws, &p.tickets, (size_t)grid.x * grid.y * slots * BN * BM, split)) return rc;
   }
   p.trace = g_fp8_rb_trace;
-  p.ablate = g_rb8_ablate;
+  p.ablate = gemm8_force().rb8_ablate;
   auto kern = (p.trace != nullptr) ? rb8_kernel<WAVES, KIND, MT, true, SLIM, QS> : rb8_kernel<WAVES, KIND, MT, false, SLIM, QS>;
   if constexpr (WAVES == 8 && MT == 8 && (KIND == RB8_FP8 || KIND == RB8_INT8) && !SLIM && QS == 1) {
     // the 2 x 4 wave arrangement (fewer operand fragments per MFMA); ao_gemm8_set_variant(103): the 1 x 8 form, for A/B
-    if (g_rb8_sm) kern = (p.trace != nullptr) ? rb8_kernel<WAVES, KIND, MT, true, SLIM, QS, true> : rb8_kernel<WAVES, KIND, MT, false, SLIM, QS, true>;
+    if (!gemm8_force().rb8_1x8) kern = (p.trace != nullptr) ? rb8_kernel<WAVES, KIND, MT, true, SLIM, QS, true> : rb8_kernel<WAVES, KIND, MT, false, SLIM, QS, true>;
   }
   if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), smem, "hipFuncSetAttribute(rb8_kernel)")) return rc;
   ao::launch(kern, grid, block, smem, stream, p);
@@ -1176,7 +1179,6 @@ int launch_rb8(Rb8Args p, int split, hipStream_t stream) {
   return AO_OK;
 }
 
-thread_local int g_mx_proto = 0;  // A/B (ao_gemm8_set_tuning key 9): 1 head ticket after the loop, 2 no early read of the tail ticket (1 | 2: the round-3 meeting)
 // Launch of the stream-K form: one workgroup per resident slot of the chip.
 constexpr int kChipCUs = 256;  // MI355X
 template <int WAVES, int SW, int QS, int CAST = 0>
@@ -1189,7 +1191,7 @@ int launch_mx_stream(Rb8Args p, hipStream_t stream) {
   const unsigned Wg = (unsigned)(per_cu * kChipCUs);
   if (int rc = splitk_workspace(stream, &p.ws, &p.tickets, (size_t)2 * Wg * 64 * 16 * WAVES)) return rc;
   p.trace = g_fp8_rb_trace;
-  p.ablate = g_mx_proto;  // the meeting protocol's A/B bits
+  p.ablate = gemm8_force().mx_proto;  // the meeting protocol's A/B bits (ao_gemm8_set_tuning key 9)
   auto kern = (p.trace != nullptr) ? mx_stream_kernel<WAVES, SW, QS, true, CAST> : mx_stream_kernel<WAVES, SW, QS, false, CAST>;
   if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), smem, "hipFuncSetAttribute(mx_stream_kernel)")) return rc;
   ao::launch(kern, dim3(Wg), dim3(64 * WAVES), smem, stream, p);
@@ -1197,30 +1199,19 @@ int launch_mx_stream(Rb8Args p, hipStream_t stream) {
   return AO_OK;
 }
 
-thread_local bool g_mx_quad = true;  // (ao_gemm8_set_variant 129: off) block scales fetched per 4 k steps where K % 512 == 0
-thread_local int g_mx_stream = 1;  // (ao_gemm8_set_variant) 1 product: the stream-K kernel for decode-size groups; 0 never (113: one workgroup per tile, the form of larger groups)
-thread_local int g_fp8_rb_force = 0;  // profiling only: 0 product heuristic, 1 never, 2 always, 3 always + 64-column tiles, two workgroups per CU
-
 }  // namespace
 
-void fp8_rowwise_rb_set_mode(int mode) { g_fp8_rb_force = mode; }
-void rb8_set_wave_grid(bool two_by_four) { g_rb8_sm = two_by_four; }
-void rb8_set_tuning(int bn, int split, int ablate) { g_rb8_bn = bn; g_rb8_split = split; g_rb8_ablate = ablate; }
-void rb8_set_slab_rows(int rows) { g_rb8_bm = rows; }
-void mx_stream_set_tuning(int proto) { g_mx_proto = proto; }
-void mx_rb_set_stream(int mode, bool quad) { g_mx_stream = mode; g_mx_quad = quad; }
 void fp8_rowwise_rb_set_trace(unsigned long long* p) { g_fp8_rb_trace = p; }
-bool fp8_rowwise_rb_forced() { return g_fp8_rb_force >= 2; }
 
 // (Round 5 also built 256-row slabs: ahead of the tile kernels where 128-row slabs needed a second round of the chip, behind the 256 x 128
 // phase-interleaved GEMM built later that round, which takes exactly those shapes -- removed in round 6; profiles/midm_forms_r05.jsonl.)
-bool gemm8_p8h_band(int64_t M, int64_t N, int64_t K);  // gemm8_p8_kernels.hip
 
 // True when this kernel is the better choice: the 128 x 128 GEMM grid would leave most of the chip idle (same rule for int8).
-bool fp8_rowwise_rb_preferred(int64_t M, int64_t N, int64_t K) {
+// force (Gemm8Force::rb): 0 this rule, 1 never, 2 / 3 always.
+bool rb8_preferred(int64_t M, int64_t N, int64_t K, int force) {
   if (K % 128 != 0 || N % 16 != 0 || M * K >= (1ll << 32) || N * K >= (1ll << 32)) return false;
-  if (g_fp8_rb_force == 1) return false;
-  if (g_fp8_rb_force >= 2) return true;
+  if (force == 1) return false;
+  if (force >= 2) return true;
   // up to one 128 x 128 workgroup per CU (one round of the chip).  Round 4 (profiles/fp8_dispatch_sweep_r04.txt, cold 70B / TP8 shards): the bound
   // was 190, and the 224 - 256 tiles of M = 512 fell to the 4-wave two-stage tile kernel -- gate_up 73.6 us against 44.3 here (hipBLASLt
   // 47.5), down 39.8 / 23.6 (24.4), o 20.9 / 11.7 (11.5); from two rounds on (M = 1024: 448 - 512 tiles) the tiled kernels are level or ahead
@@ -1234,8 +1225,8 @@ bool fp8_rowwise_rb_preferred(int64_t M, int64_t N, int64_t K) {
 // M = 24 / 32 / 48 / 64: 52 / 58 / 74 / 90 us -> 37 / 38 / 38 / 40; down 5120 x 13824 at M = 8 .. 16: 31 - 34 -> 22 - 23; down 3584 x 18944 at
 // M = 24 / 32 (once mid8 refuses a K it cannot split): 34 -> 23; qkv 4608 x 3584 at 24 / 32: 12.7 / 13.8 -> 10.3; the 70B / TP8 down shard
 // 8192 x 3584 at 24 / 32: 13.7 / 14.2 -> 13.0 / 12.6 -- and level or behind on smaller ones (o 3584 x 3584: 8.8 against 9.6), which stay.
-bool rb8_small_m_preferred(int64_t M, int64_t N, int64_t K) {
-  if (g_fp8_rb_force == 1) return false;
+bool rb8_small_m_preferred(int64_t M, int64_t N, int64_t K, int force) {
+  if (force == 1) return false;
   if (K % 128 != 0 || N % 16 != 0 || M * K >= (1ll << 32) || N * K >= (1ll << 32)) return false;
   return M >= 8 && M <= 64 && N * K >= 16000000;
 }
@@ -1296,34 +1287,32 @@ inline Rb8Plan rb8_plan(int64_t M, int64_t N, int64_t K, int bm_forced = 0) {
 }
 
 }  // namespace
-// what rb8_run picks without tuning overrides (host logic only: ao_gemm8_plan, tests/test_host_dispatch.py)
-void rb8_plan_query(int64_t M, int64_t N, int64_t K, int* bm, int* bn, int* split) {
-  const Rb8Plan plan = rb8_plan(M, N, K);
-  const int64_t base = ((N + plan.bn - 1) / plan.bn) * ((M + plan.bm - 1) / plan.bm);
-  const int64_t fit = (int64_t)kSplitMaxTiles * 128 * 128 / (base * plan.bn * plan.bm) * 4 / 5;
-  *bm = plan.bm;
-  *bn = plan.bn;
-  *split = (int)std::max<int64_t>(1, std::min<int64_t>(plan.split, fit));
+
+// Slab height, tile width and K parts of a rowwise launch: the cost model's pick (64-row slabs for M <= 64 always), clamped to the split-K
+// workspace.  Overrides: tuning key 3 a height, key 1 a width (variant 102: 64 columns), key 2 the parts.
+void rb8_launch_plan(int64_t M, int64_t N, int64_t K, const Gemm8Force& f, int* bm_out, int* bn_out, int* split_out) {
+  Rb8Plan plan = rb8_plan(M, N, K, (f.rb8_bm == 64 || f.rb8_bm == 128) ? f.rb8_bm : 0);
+  const int bm = plan.bm;
+  const int64_t slabs = (M + bm - 1) / bm, ksteps = K >> 7;
+  if (f.rb == 3) plan.bn = 64;
+  const int bn = (f.rb8_bn == 32 || f.rb8_bn == 64 || f.rb8_bn == 128) ? f.rb8_bn : plan.bn;
+  const int64_t base = ((N + bn - 1) / bn) * slabs;
+  const int64_t fit = (int64_t)kSplitMaxTiles * 128 * 128 / (base * bn * bm) * 4 / 5;
+  int split = (bn == plan.bn) ? plan.split : (int)std::max<int64_t>(1, std::min<int64_t>({256 / base, fit, 16, ksteps / 4}));
+  if (f.rb8_split > 0) split = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)f.rb8_split, fit, 16, ksteps}));
+  *bm_out = bm;
+  *bn_out = bn;
+  *split_out = (int)std::max<int64_t>(1, std::min<int64_t>(split, fit));
 }
+
 namespace {
 
 template <int KIND>
 int rb8_run(const uint8_t* a, const uint8_t* b, const float* scale_a, const float* scale_b, const uint16_t* bias, uint16_t* y, int64_t M,
-            int64_t N, int64_t K, hipStream_t stream) {
+            int64_t N, int64_t K, int bm, int bn, int split, hipStream_t stream) {
   Rb8Args p{};
   p.a = a; p.b = b; p.scale_a = scale_a; p.scale_b = scale_b; p.bias = bias; p.y = y;
   p.M = (int)M; p.N = (int)N; p.K = (int)K;
-  // slab height, tile width, K parts: the cost model's pick (64-row slabs for M <= 64 always; tuning key 3 forces a height)
-  Rb8Plan plan = rb8_plan(M, N, K, (g_rb8_bm == 64 || g_rb8_bm == 128) ? g_rb8_bm : 0);
-  const int bm = plan.bm;
-  const int64_t slabs = (M + bm - 1) / bm, ksteps = K >> 7;
-  if (g_fp8_rb_force == 3) plan.bn = 64;
-  int bn = (g_rb8_bn == 32 || g_rb8_bn == 64 || g_rb8_bn == 128) ? g_rb8_bn : plan.bn;
-  const int64_t base = ((N + bn - 1) / bn) * slabs;
-  const int64_t fit = (int64_t)kSplitMaxTiles * 128 * 128 / (base * bn * bm) * 4 / 5;
-  int split = (bn == plan.bn) ? plan.split : (int)std::max<int64_t>(1, std::min<int64_t>({256 / base, fit, 16, ksteps / 4}));
-  if (g_rb8_split > 0) split = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)g_rb8_split, fit, 16, ksteps}));
-  split = (int)std::max<int64_t>(1, std::min<int64_t>(split, fit));
   if (bn == 32) return (bm == 64) ? launch_rb8<2, KIND, 4>(p, split, stream) : launch_rb8<2, KIND, 8>(p, split, stream);
   if (bm == 64) return bn == 64 ? launch_rb8<4, KIND, 4>(p, split, stream) : launch_rb8<8, KIND, 4>(p, split, stream);
   return bn == 64 ? launch_rb8<4, KIND, 8>(p, split, stream) : launch_rb8<8, KIND, 8>(p, split, stream);
@@ -1331,14 +1320,13 @@ int rb8_run(const uint8_t* a, const uint8_t* b, const float* scale_a, const floa
 
 }  // namespace
 
-int fp8_rowwise_rb(const uint8_t* a, const uint8_t* b, const float* scale_a, const float* scale_b, const uint16_t* bias, uint16_t* y,
-                   int64_t M, int64_t N, int64_t K, hipStream_t stream) {
-  return rb8_run<RB8_FP8>(a, b, scale_a, scale_b, bias, y, M, N, K, stream);
-}
-
-int int8_scaled_rb(const int8_t* a, const int8_t* b, const float* scale_a, const float* scale_b, const uint16_t* bias, uint16_t* y,
-                   int64_t M, int64_t N, int64_t K, hipStream_t stream) {
-  return rb8_run<RB8_INT8>(reinterpret_cast<const uint8_t*>(a), reinterpret_cast<const uint8_t*>(b), scale_a, scale_b, bias, y, M, N, K, stream);
+// the rowwise scaled GEMM (int8 or fp8 codes) with the launch shape of rb8_launch_plan
+int rb8_scaled(bool int8, const void* a, const void* b, const float* scale_a, const float* scale_b, const uint16_t* bias, uint16_t* y, int64_t M,
+               int64_t N, int64_t K, int bm, int bn, int split, hipStream_t stream) {
+  const uint8_t* a8 = static_cast<const uint8_t*>(a);
+  const uint8_t* b8 = static_cast<const uint8_t*>(b);
+  return int8 ? rb8_run<RB8_INT8>(a8, b8, scale_a, scale_b, bias, y, M, N, K, bm, bn, split, stream)
+              : rb8_run<RB8_FP8>(a8, b8, scale_a, scale_b, bias, y, M, N, K, bm, bn, split, stream);
 }
 
 // MXFP8 grouped GEMM (aten::_scaled_grouped_mm as called from mxfp8_grouped_mm.py:541, numerics of :959-1023): out rows of
@@ -1353,7 +1341,7 @@ int mxfp8_grouped_rb(const uint8_t* a, const uint8_t* a_scale, const uint8_t* b,
   // Slab capacity from the average group size (the sizes themselves live on the device): 64 rows for decode-size groups (two
   // workgroups per CU; a group's real m-tile count is found on the device), else 128.
   const int64_t groups = (offs != nullptr ? E : 1);
-  const int bm = (g_rb8_bm == 64 || g_rb8_bm == 128) ? g_rb8_bm : (M_total <= 48 * groups) ? 64 : 128;  // (tuning key 3 forces a height: A/B)
+  const int bm = grouped_slab_rows(M_total, groups);
   p.slabs = (int)std::max<int64_t>(1, (std::min(rows_hint, M_total) + bm - 1) / bm);
   // 64-column tiles when 128-column ones would not give every CU a workgroup even if every group had tokens
   // (cutting K into 2 - 4 parts that meet through the split-K workspace -- finer work items for the last round when few experts
@@ -1362,12 +1350,13 @@ int mxfp8_grouped_rb(const uint8_t* a, const uint8_t* a_scale, const uint8_t* b,
   // decode-size groups: the stream-K form when its bounds hold (group table in registers: E <= 64; 32-bit step counter; a
   // ticket per tile).  Mixtral's shapes, hipGraph, us (w1 / w2; profiles/mx_rb_trace_r03.txt session G): three experts hit 58.0 / 71.3
   // with one workgroup per tile -> 56.1 / 52.2; all eight 111 / 110 -> 101 / 91.
-  if (bm == 64 && g_mx_stream != 0 && groups <= 64) {
+  const Gemm8Force& f = gemm8_force();
+  if (bm == 64 && f.mx_stream && groups <= 64) {
     const int64_t tiles = ((M_total + 63) / 64 + groups) * ((N + 63) / 64);  // (64-column tiles: the bound of every form)
     if (tiles <= kSplitMaxTickets && tiles * (K >> 7) < (1ll << 31))
     {
       // scales fetched per 4 steps when K allows (16-byte pieces of 16-byte-aligned scale rows), else per step
-      const bool quad = g_mx_quad && K % 512 == 0 && ((uintptr_t)a_scale % 16 == 0) && ((uintptr_t)b_scale % 16 == 0);
+      const bool quad = f.mx_quad && K % 512 == 0 && ((uintptr_t)a_scale % 16 == 0) && ((uintptr_t)b_scale % 16 == 0);
       // round 6: ONE 16-wave workgroup per CU over 256-column tiles where the scales can be fetched per 4 steps; other K (and variant 129,
       // which tests that form on every shape) the 8-wave form of rounds 3 - 5 with the scales fetched per step, two workgroups per CU
       if (quad) return launch_mx_stream<16, 3, 4>(p, stream);
@@ -1375,7 +1364,7 @@ int mxfp8_grouped_rb(const uint8_t* a, const uint8_t* a_scale, const uint8_t* b,
     }
   }
   // larger groups (and more than 64 experts): one workgroup per (slab, tile); scales per 4 steps when K allows
-  const bool quad = g_mx_quad && K % 512 == 0 && ((uintptr_t)a_scale % 16 == 0) && ((uintptr_t)b_scale % 16 == 0);
+  const bool quad = f.mx_quad && K % 512 == 0 && ((uintptr_t)a_scale % 16 == 0) && ((uintptr_t)b_scale % 16 == 0);
   if (bm == 64) {
     return quad ? launch_rb8<4, RB8_MX, 4, false, 4>(p, 1, stream) : launch_rb8<4, RB8_MX, 4, true>(p, 1, stream);
   }
@@ -1414,7 +1403,7 @@ int fp8_rowwise_grouped_rb(const uint8_t* a, const uint8_t* b, const float* scal
   Rb8Args p{};
   p.a = a; p.b = b; p.scale_a = scale_a; p.scale_b = scale_b; p.y = out; p.offs = offs;
   p.M = (int)M_total; p.N = (int)N; p.K = (int)K; p.E = (int)E;
-  const int bm = (g_rb8_bm == 64 || g_rb8_bm == 128) ? g_rb8_bm : (M_total <= 48 * E) ? 64 : 128;
+  const int bm = grouped_slab_rows(M_total, E);
   p.slabs = (int)std::max<int64_t>(1, (M_total + bm - 1) / bm);
   if (bm == 64) return launch_rb8<4, RB8_FP8_GROUPED, 4>(p, 1, stream);
   return (((N + 127) / 128) * E * p.slabs < 400) ? launch_rb8<4, RB8_FP8_GROUPED, 8>(p, 1, stream) : launch_rb8<8, RB8_FP8_GROUPED, 8>(p, 1, stream);

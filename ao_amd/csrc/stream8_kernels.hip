@@ -12,6 +12,7 @@
 // operands (one byte per lane per 32-k block), so no cuBLAS-style scale swizzle
 // and no separate dequant pass exist.  One barrier for the split-K reduction.
 #include "common.h"
+#include "gemm8_route.h"
 
 #include <type_traits>
 
@@ -25,7 +26,6 @@ bool mxfp8_grouped_dyn_fits(int64_t M_total, int64_t N, int64_t K, int64_t E, bo
 int mxfp8_grouped_stream16(const void* a, const uint8_t* a_scale, const uint8_t* b, const uint8_t* b_scale, const uint8_t* b2, const uint8_t* b2_scale,
                            const int32_t* offs, uint16_t* out, uint16_t* out2, int64_t M_total, int64_t N, int64_t K, int64_t E, int scaling_mode,
                            hipStream_t stream);
-thread_local int g_mx_variant = 0;  // profiling / A-B tests (ao_gemm8_set_variant 110 / 111): 0 by shape, 1 always the LDS-staged kernel, 2 never
 namespace {
 
 typedef int i32x8 __attribute__((ext_vector_type(8)));
@@ -456,7 +456,7 @@ extern "C" int ao_mxfp8_grouped_mm(const uint8_t* a, const uint8_t* a_scale, con
   // M_total * K >= 4 GiB, or more than 65535 possible non-empty (expert, slab) pairs -- take the per-tile kernels below, which have neither limit)
   const int64_t rb_bm = (M_total <= 48 * (offs != nullptr ? E : 1)) ? 64 : 128;
   const bool rb_ok = M_total * K < (1ll << 32) && N * K < (1ll << 32) && (offs != nullptr ? E : 0) + (M_total + rb_bm - 1) / rb_bm <= 65535;
-  if (g_mx_variant != 2 && rb_ok) return mxfp8_grouped_rb(a, a_scale, b, b_scale, offs, out, M_total, N, K, E, M_total, (hipStream_t)stream);
+  if (gemm8_force().mx != 2 && rb_ok) return mxfp8_grouped_rb(a, a_scale, b, b_scale, offs, out, M_total, N, K, E, M_total, (hipStream_t)stream);
   if (offs != nullptr && K % 2048 == 0) {
     // Group sizes live on the device.  Size the m-tiling for twice the AVERAGE group: a larger group
     // takes another pass over its expert's weights (correct, slower), while sizing for the worst

@@ -146,17 +146,19 @@ int ao_gemm8_set_variant(int variant);
  *          (3 = the round-3 protocol)
  * An unknown key is an error.  DESIGN.md 4.5h. */
 int ao_gemm8_set_tuning(int key, int value);
-/* Name of the kernel ao_int4_weight_int4pack_mm launches for this problem (product dispatch, no
- * tuning override): what a profiler's kernel table should be matched against.  Static string. */
+/* Name of the kernel ao_int4_weight_int4pack_mm launches for this problem: the product route, whatever override
+ * ao_int4_set_tuning has set -- what a profiler's kernel table should be matched against.  Static string. */
 const char* ao_int4_mm_kernel_name(int64_t M, int64_t N, int64_t K, int group_size);
 /* Which kernel ao_fp8_scaled_mm (int8 = 0) / ao_int8_scaled_mm (int8 = 1) dispatches a shape to: "dec8_kernel" (M <= 16), "mid8_kernel",
- * "stream8_kernel", "rb8_kernel" (up to 256 tiles of 128 x 128), "gemm8_p8_kernel" / "gemm8_dma_kernel<...>" / "gemm8_kernel" (tiled), or
- * "invalid".  Host logic only (no launch): bench / tests label their measurements with it.  DESIGN.md 4.4-4.5g. */
+ * "stream8_kernel", "rb8_kernel" (up to 256 tiles of 128 x 128), "gemm8_p8h_kernel" / "gemm8_p8_kernel" / "gemm8_p8p_kernel" /
+ * "gemm8_dma_kernel<...>" / "gemm8_kernel" (tiled), or "invalid".  The route the launch takes for 16-byte-aligned scales and output, whatever
+ * override ao_gemm8_set_variant / ao_gemm8_set_tuning has set (the product dispatch).  Host logic only (no launch): bench / tests label their
+ * measurements with it.  DESIGN.md 4.4-4.5g. */
 const char* ao_gemm8_kernel_name(int int8, int64_t M, int64_t N, int64_t K);
-/* The launch shape behind that name: column-tile width and K parts of the product dispatch for the shape (rb8_kernel: the cost model's
- * pick; gemm8_p8h_kernel: 128 columns and 1 .. 4 parts; others: their tile width, one part).  Host logic only.  DESIGN.md 4.5h. */
+/* The launch shape of that same route: column-tile width and K parts (rb8_kernel: the cost model's pick; gemm8_p8h_kernel: 128 columns and
+ * 1 .. 4 parts; the per-tile streaming kernels: 16, one part; others: their tile width, one part).  Host logic only.  DESIGN.md 4.5h. */
 int ao_gemm8_plan(int int8, int64_t M, int64_t N, int64_t K, int* tile_cols, int* k_parts);
-/* The rows of that launch's tile: rb8_kernel's slab height (64 up to 64 rows; 64 or 128 beyond, by the cost model -- round 6: 64-row slabs
+/* The rows of that route's tile: rb8_kernel's slab height (64 up to 64 rows; 64 or 128 beyond, by the cost model -- round 6: 64-row slabs
  * cut M instead of K where the fixed costs of a launch outweigh its loop), 256 for the 256 x 128 / 256 x 256 GEMMs, 128 / 16 otherwise.
  * Host logic only.  DESIGN.md 4.5. */
 int ao_gemm8_plan_rows(int int8, int64_t M, int64_t N, int64_t K, int* tile_rows);

@@ -82,6 +82,20 @@ TABLE = [
     ((0, 64, 1024), "invalid"),
 ]
 
+# ao_gemm8_plan / ao_gemm8_plan_rows on the shapes of profiles/midm_final_r06.jsonl (test_8bit_launch_plans_on_the_sweep_shapes)
+PLAN_SHAPES = {"qkv70b": (1280, 8192), "o70b": (8192, 1024), "gate70b": (7168, 8192), "down70b": (8192, 3584),
+               "qkv8b": (6144, 4096), "o8b": (4096, 4096), "gate_up8b": (28672, 4096), "down8b": (4096, 14336)}
+PLANS = {  # M: (kernel, tile rows, tile columns, K parts)
+    "qkv70b": {96: ("rb8", 64, 64, 4), 128: ("rb8", 64, 64, 4), 256: ("rb8", 64, 64, 3), 512: ("rb8", 64, 128, 3), 768: ("rb8", 128, 128, 4), 1024: ("p8h", 256, 128, 4), 2048: ("p8h", 256, 128, 3)},
+    "o70b": {96: ("rb8", 64, 64, 1), 128: ("rb8", 64, 64, 1), 256: ("rb8", 64, 128, 1), 512: ("rb8", 128, 128, 1), 768: ("p8h", 256, 128, 1), 1024: ("p8h", 256, 128, 1), 2048: ("p8", 256, 256, 1)},
+    "gate70b": {96: ("rb8", 64, 128, 2), 128: ("rb8", 64, 128, 2), 256: ("rb8", 64, 128, 1), 512: ("p8h", 256, 128, 2), 768: ("p8h", 256, 128, 1), 1024: ("p8h", 256, 128, 1), 2048: ("p8", 256, 256, 1)},
+    "down70b": {96: ("rb8", 64, 64, 1), 128: ("rb8", 64, 64, 1), 256: ("rb8", 64, 128, 1), 512: ("rb8", 128, 128, 1), 768: ("p8h", 256, 128, 1), 1024: ("p8h", 256, 128, 1), 2048: ("p8", 256, 256, 1)},
+    "qkv8b": {96: ("rb8", 64, 128, 2), 128: ("rb8", 64, 128, 2), 256: ("rb8", 64, 128, 1), 512: ("rb8", 128, 128, 1), 768: ("p8h", 256, 128, 1), 1024: ("p8h", 256, 128, 1), 2048: ("p8", 256, 256, 1)},
+    "o8b": {96: ("rb8", 64, 64, 2), 128: ("rb8", 64, 64, 2), 256: ("rb8", 64, 128, 2), 512: ("rb8", 64, 128, 1), 768: ("rb8", 128, 128, 1), 1024: ("rb8", 128, 128, 1), 2048: ("p8h", 256, 128, 1)},
+    "gate_up8b": {96: ("rb8", 128, 128, 1), 128: ("rb8", 128, 128, 1), 256: ("p8h", 256, 128, 1), 512: ("p8", 256, 256, 1), 1024: ("p8", 256, 256, 1), 2048: ("p8", 256, 256, 1)},
+    "down8b": {96: ("rb8", 64, 128, 4), 128: ("rb8", 64, 128, 4), 256: ("rb8", 128, 128, 4), 512: ("p8h", 256, 128, 4), 768: ("p8h", 256, 128, 2), 1024: ("p8h", 256, 128, 2), 2048: ("p8h", 256, 128, 1)},
+}
+
 
 @pytest.mark.parametrize("int8", [0, 1])
 def test_8bit_dispatch_table(int8):
@@ -132,6 +146,16 @@ def test_fp8_int4_tile_forms():
     assert name(128, 4096, 4000) == "invalid" and name(0, 4096, 4096) == "invalid" and name(8, 4096, 4096, 48) == "invalid"
 
 
+def _plan(lib, int8, m, n, k):
+    import ctypes
+
+    short = {"rb8_kernel": "rb8", "gemm8_p8h_kernel": "p8h", "gemm8_p8_kernel": "p8", "gemm8_p8p_kernel": "p8"}
+    rows, cols, parts = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _lib.check(lib.ao_gemm8_plan(int8, m, n, k, ctypes.byref(cols), ctypes.byref(parts)))
+    _lib.check(lib.ao_gemm8_plan_rows(int8, m, n, k, ctypes.byref(rows)))
+    return (short[lib.ao_gemm8_kernel_name(int8, m, n, k).decode()], rows.value, cols.value, parts.value)
+
+
 def test_8bit_launch_plans_on_the_sweep_shapes():
     """ao_gemm8_plan / ao_gemm8_plan_rows: tile rows / width / K parts of the product dispatch on the shapes of profiles/midm_final_r06.jsonl
     (fp8 = int8).  The weight-streaming kernel's pick comes from a cost model fitted to the round-6 grid (rb8_plan;
@@ -140,26 +164,10 @@ def test_8bit_launch_plans_on_the_sweep_shapes():
     import ctypes
 
     lib = _lib.lib()
-    shapes = {"qkv70b": (1280, 8192), "o70b": (8192, 1024), "gate70b": (7168, 8192), "down70b": (8192, 3584),
-              "qkv8b": (6144, 4096), "o8b": (4096, 4096), "gate_up8b": (28672, 4096), "down8b": (4096, 14336)}
-    want = {  # M: (kernel, tile rows, tile columns, K parts)
-        "qkv70b": {96: ("rb8", 64, 64, 4), 128: ("rb8", 64, 64, 4), 256: ("rb8", 64, 64, 3), 512: ("rb8", 64, 128, 3), 768: ("rb8", 128, 128, 4), 1024: ("p8h", 256, 128, 4), 2048: ("p8h", 256, 128, 3)},
-        "o70b": {96: ("rb8", 64, 64, 1), 128: ("rb8", 64, 64, 1), 256: ("rb8", 64, 128, 1), 512: ("rb8", 128, 128, 1), 768: ("p8h", 256, 128, 1), 1024: ("p8h", 256, 128, 1), 2048: ("p8", 256, 256, 1)},
-        "gate70b": {96: ("rb8", 64, 128, 2), 128: ("rb8", 64, 128, 2), 256: ("rb8", 64, 128, 1), 512: ("p8h", 256, 128, 2), 768: ("p8h", 256, 128, 1), 1024: ("p8h", 256, 128, 1), 2048: ("p8", 256, 256, 1)},
-        "down70b": {96: ("rb8", 64, 64, 1), 128: ("rb8", 64, 64, 1), 256: ("rb8", 64, 128, 1), 512: ("rb8", 128, 128, 1), 768: ("p8h", 256, 128, 1), 1024: ("p8h", 256, 128, 1), 2048: ("p8", 256, 256, 1)},
-        "qkv8b": {96: ("rb8", 64, 128, 2), 128: ("rb8", 64, 128, 2), 256: ("rb8", 64, 128, 1), 512: ("rb8", 128, 128, 1), 768: ("p8h", 256, 128, 1), 1024: ("p8h", 256, 128, 1), 2048: ("p8", 256, 256, 1)},
-        "o8b": {96: ("rb8", 64, 64, 2), 128: ("rb8", 64, 64, 2), 256: ("rb8", 64, 128, 2), 512: ("rb8", 64, 128, 1), 768: ("rb8", 128, 128, 1), 1024: ("rb8", 128, 128, 1), 2048: ("p8h", 256, 128, 1)},
-        "gate_up8b": {96: ("rb8", 128, 128, 1), 128: ("rb8", 128, 128, 1), 256: ("p8h", 256, 128, 1), 512: ("p8", 256, 256, 1), 1024: ("p8", 256, 256, 1), 2048: ("p8", 256, 256, 1)},
-        "down8b": {96: ("rb8", 64, 128, 4), 128: ("rb8", 64, 128, 4), 256: ("rb8", 128, 128, 4), 512: ("p8h", 256, 128, 4), 768: ("p8h", 256, 128, 2), 1024: ("p8h", 256, 128, 2), 2048: ("p8h", 256, 128, 1)},
-    }
-    short = {"rb8_kernel": "rb8", "gemm8_p8h_kernel": "p8h", "gemm8_p8_kernel": "p8", "gemm8_p8p_kernel": "p8"}
-    for name, (n, k) in shapes.items():
-        for m, expect in want[name].items():
+    for name, (n, k) in PLAN_SHAPES.items():
+        for m, expect in PLANS[name].items():
             for int8 in (0, 1):
-                rows, cols, parts = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-                _lib.check(lib.ao_gemm8_plan(int8, m, n, k, ctypes.byref(cols), ctypes.byref(parts)))
-                _lib.check(lib.ao_gemm8_plan_rows(int8, m, n, k, ctypes.byref(rows)))
-                got = (short[lib.ao_gemm8_kernel_name(int8, m, n, k).decode()], rows.value, cols.value, parts.value)
+                got = _plan(lib, int8, m, n, k)
                 assert got == expect, (name, m, int8, got, expect)
     # the per-tile streaming kernels report their 16-wide n-tiles; a shape no kernel takes is an error
     cols, parts = ctypes.c_int(), ctypes.c_int()
@@ -167,3 +175,42 @@ def test_8bit_launch_plans_on_the_sweep_shapes():
     assert (cols.value, parts.value) == (16, 1)
     with pytest.raises(ValueError):
         _lib.check(lib.ao_gemm8_plan(0, 0, 64, 1024, ctypes.byref(cols), ctypes.byref(parts)))
+
+
+def test_dyn_linear_fits_refuses_empty_weights():
+    lib = _lib.lib()
+    assert lib.ao_dyn_linear_fits(32, 0, 4096) == 0 and lib.ao_dyn_linear_fits(4, 0, 4096) == 0 and lib.ao_dyn_linear_fits(4, 4096, 4096) == 1
+
+
+def test_queries_ignore_overrides():
+    """The queries report the product route whatever override the calling thread has set: what the tables above pin is what launches
+    without one (ao_gemm8_set_variant / ao_gemm8_set_tuning / ao_int4_set_tuning only steer the launches)."""
+    lib = _lib.lib()
+
+    def check_8bit(setting):
+        for int8 in (0, 1):
+            got = {shape: lib.ao_gemm8_kernel_name(int8, *shape).decode() for shape, _ in TABLE}
+            assert got == dict(TABLE), (setting, int8)
+            for name, (n, k) in PLAN_SHAPES.items():
+                for m, expect in PLANS[name].items():
+                    assert _plan(lib, int8, m, n, k) == expect, (setting, name, m, int8)
+
+    int4 = lambda: {(m, n, k, g): lib.ao_int4_mm_kernel_name(m, n, k, g).decode()  # noqa: E731
+                    for m in (1, 5, 9, 16, 17, 64, 65, 128, 129, 512, 2048) for n, k in PLAN_SHAPES.values() for g in (32, 128)}
+    int4_product = int4()
+    try:
+        for variant in (1, 8, 32, 100, 101, 103, 113, 201, 293, 299, 300, 301, 312):
+            lib.ao_gemm8_set_variant(variant)
+            check_8bit(("variant", variant))
+        lib.ao_gemm8_set_variant(0)
+        for key, value in ((1, 32), (3, 128), (6, 2), (7, 3)):
+            lib.ao_gemm8_set_tuning(key, value)
+            check_8bit(("tuning", key, value))
+        for wpb, mode in ((8, 99), (0, 911), (0, 650)):
+            lib.ao_int4_set_tuning(wpb, mode)
+            assert int4() == int4_product, (wpb, mode)
+    finally:
+        lib.ao_gemm8_set_variant(0)
+        for key in (1, 3, 6, 7):
+            lib.ao_gemm8_set_tuning(key, 0)
+        lib.ao_int4_set_tuning(0, 0)
