@@ -48,6 +48,10 @@ _SIGNATURES = {
     "ao_fp8_int4_kernel_name": [_I64, _I64, _I64, _INT],
     "ao_gemm8_plan": [_INT, _I64, _I64, _I64, _P, _P],
     "ao_gemm8_plan_rows": [_INT, _I64, _I64, _I64, _P],
+    "ao_gemm8_route": [_INT, _I64, _I64, _I64, _INT, _P, _INT],
+    "ao_gemm8_overridden": [],
+    "ao_int4_overridden": [],
+    "ao_int4_mm_route": [_I64, _I64, _I64, _INT, _P, _INT],
     "ao_int8_quantize_rowwise": [_P, _P, _P, _I64, _I64, _P],
     "ao_int8_scaled_mm": [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _P],
     "ao_int8_int_mm": [_P, _P, _P, _I64, _I64, _I64, _P],

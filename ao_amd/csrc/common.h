@@ -97,6 +97,13 @@ __device__ __forceinline__ float round_bf16(float f) {
   return (float)b;
 }
 
+// a * b rounded to fp32 on its own.  The int8 epilogue adds the bias to the rounded product (int8_tensor.py:315-359: two tensor ops),
+// so the multiply and that add must not be contracted into one v_fma_f32.
+__device__ __forceinline__ float mul_f32_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
 __device__ __forceinline__ uint16_t f32_to_bf16_bits(float f) {
   __bf16 b = (__bf16)f;
   return __builtin_bit_cast(uint16_t, b);

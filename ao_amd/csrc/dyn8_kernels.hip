@@ -124,7 +124,7 @@ __global__ __launch_bounds__(512) void dyn8_kernel(Dyn8Args p) {
       int isum = 0;
       for (int w = 0; w < nwaves; ++w) isum += __float_as_int(red[(size_t)w * 256 + idx]);
       // t = bf16(f32(c) * sx[m]);  y = bf16(f32(t) * sw[n] (+ bias))   (int8_tensor.py:315-359)
-      v = round_bf16((float)isum * rs[row]) * p.col_scale[gn];
+      v = mul_f32_rn(round_bf16((float)isum * rs[row]), p.col_scale[gn]);
     } else {
       float sum = 0.f;
       for (int w = 0; w < nwaves; ++w) sum += red[(size_t)w * 256 + idx];

@@ -188,7 +188,7 @@ __global__ __launch_bounds__(THREADS) void gemm8_kernel(Gemm8Args p) {
         } else if (EPI == EPI_INT8_SCALED) {
           // t = bf16(f32(c) * sx[m]);  y = bf16(f32(t) * sw[n] (+ bias))   (int8_tensor.py:315-359)
           const float t = round_bf16((float)acc[i][j][r] * p.row_scale[gm]);
-          float y = t * cs;
+          float y = mul_f32_rn(t, cs);
           if (p.bias != nullptr) y += bias;
           reinterpret_cast<uint16_t*>(p.out)[(size_t)gm * p.N + gn] = f32_to_bf16_bits(y);
         } else {
@@ -354,7 +354,7 @@ __global__ __launch_bounds__(128 * WN) void gemm8_dma_kernel(Gemm8Args p) {
           reinterpret_cast<float*>(p.out)[(size_t)gm * p.N + gn] = (float)acc[i][j][r];
         } else if (EPI == EPI_INT8_SCALED) {
           const float t = round_bf16((float)acc[i][j][r] * p.row_scale[gm]);
-          float y = t * cs;
+          float y = mul_f32_rn(t, cs);
           if (p.bias != nullptr) y += bias;
           reinterpret_cast<uint16_t*>(p.out)[(size_t)gm * p.N + gn] = f32_to_bf16_bits(y);
         } else {
@@ -541,6 +541,17 @@ extern "C" int ao_gemm8_set_variant(int variant) {
   return AO_OK;
 }
 
+// 1 when the calling thread has any ao_gemm8_set_variant / ao_gemm8_set_tuning override set (tests assert the product dispatch)
+extern "C" int ao_gemm8_overridden(void) {
+  const Gemm8Force& f = g_force;
+  const Gemm8Force d{};
+  return !(f.regstage == d.regstage && f.tiled_only == d.tiled_only && f.tile == d.tile && f.rb == d.rb && f.rb8_1x8 == d.rb8_1x8 &&
+           f.mx == d.mx && f.mx_stream == d.mx_stream && f.mx_quad == d.mx_quad && f.dec8 == d.dec8 && f.mid8 == d.mid8 &&
+           f.rb8_bn == d.rb8_bn && f.rb8_split == d.rb8_split && f.rb8_bm == d.rb8_bm && f.p8_group_rows == d.p8_group_rows &&
+           f.rb8_ablate == d.rb8_ablate && f.p8_persist == d.p8_persist && f.p8_split == d.p8_split && f.p8h_form == d.p8h_form &&
+           f.mx_proto == d.mx_proto);
+}
+
 extern "C" int ao_gemm8_set_tuning(int key, int value) {
   static int Gemm8Force::*const kKeys[] = {nullptr, &Gemm8Force::rb8_bn, &Gemm8Force::rb8_split, &Gemm8Force::rb8_bm, &Gemm8Force::p8_group_rows,
                                            &Gemm8Force::rb8_ablate, &Gemm8Force::p8_persist, &Gemm8Force::p8_split, &Gemm8Force::p8h_form,
@@ -618,6 +629,18 @@ extern "C" int ao_gemm8_plan_rows(int int8, int64_t M, int64_t N, int64_t K, int
   AO_REQUIRE_PTR(tile_rows);
   int cols = 0, parts = 0;
   return gemm8_plan3(int8, M, N, K, tile_rows, &cols, &parts);
+}
+
+// Every field of the product route of one entry point (host logic only): tests derive their case list from it.
+extern "C" int ao_gemm8_route(int entry, int64_t M, int64_t N, int64_t K, int aligned, int32_t* out, int cap) {
+  AO_REQUIRE_PTR(out);
+  AO_REQUIRE(entry >= 0 && entry <= (int)Gemm8Entry::Fp8Dyn, "ao_gemm8_route: unknown entry %d", entry);
+  AO_REQUIRE(cap >= 11, "ao_gemm8_route: out holds %d fields, the route has 11", cap);
+  const Gemm8Route r = gemm8_route((Gemm8Entry)entry, M, N, K, aligned != 0, Gemm8Force{});
+  const int32_t v[11] = {(int32_t)r.kernel, r.tile_rows, r.tile_cols, r.k_parts, r.dec.waves, r.dec.depth,
+                         r.dec.loop, r.dec.half, r.dec.rows8, r.mid.mt, r.mid.split};
+  for (int i = 0; i < 11; ++i) out[i] = v[i];
+  return AO_OK;
 }
 
 extern "C" int ao_int8_int_mm(const int8_t* a, const int8_t* b_t, int32_t* c, int64_t M, int64_t N, int64_t K,

@@ -254,7 +254,7 @@ __global__ __launch_bounds__(512) void gemm8_p8_kernel(P8Args p) {
           float v;
           if constexpr (EPI == P8_INT8_SCALED) {
             // t = bf16(f32(c) * sx[m]);  y = bf16(f32(t) * sw[n] (+ bias))   (int8_tensor.py:315-359)
-            v = round_bf16((float)__builtin_bit_cast(i32x4, acc[mt][nt])[r] * rs[r]) * cs[nt];
+            v = mul_f32_rn(round_bf16((float)__builtin_bit_cast(i32x4, acc[mt][nt])[r] * rs[r]), cs[nt]);
           } else {
             v = acc[mt][nt][r] * rs[r] * cs[nt];
           }
@@ -539,7 +539,7 @@ __global__ __launch_bounds__(512) void gemm8_p8p_kernel(P8Args p) {
                 for (int r = 0; r < 4; ++r) {
                   if constexpr (EPI == P8_INT8_SCALED) {
                     // t = bf16(f32(c) * sx[m]);  y = bf16(f32(t) * sw[n] (+ bias))   (int8_tensor.py:315-359)
-                    v[r] = round_bf16((float)__builtin_bit_cast(i32x4, acc[mt][nt])[r] * rs) * cs[n2][r];
+                    v[r] = mul_f32_rn(round_bf16((float)__builtin_bit_cast(i32x4, acc[mt][nt])[r] * rs), cs[n2][r]);
                   } else {
                     v[r] = acc[mt][nt][r] * rs * cs[n2][r];
                   }
@@ -826,7 +826,7 @@ __global__ __launch_bounds__(512) void gemm8_p8h_kernel(P8Args p) {
         for (int r = 0; r < 4; ++r) {
           float v;
           if constexpr (EPI == P8_INT8_SCALED) {
-            v = round_bf16((float)__builtin_bit_cast(i32x4, acc[mt][nt])[r] * rs[r]) * cs[nt];  // (int8_tensor.py:315-359)
+            v = mul_f32_rn(round_bf16((float)__builtin_bit_cast(i32x4, acc[mt][nt])[r] * rs[r]), cs[nt]);  // (int8_tensor.py:315-359)
           } else {
             v = acc[mt][nt][r] * rs[r] * cs[nt];
           }

@@ -1511,6 +1511,18 @@ extern "C" const char* ao_int4_mm_kernel_name(int64_t M, int64_t N, int64_t K, i
   return r.form == Int4Route::Rb ? "int4_mm_rb_kernel" : "int4_mm_kernel";
 }
 
+// every field of that route (host logic only): tests derive their case list from it
+extern "C" int ao_int4_mm_route(int64_t M, int64_t N, int64_t K, int group_size, int32_t* out, int cap) {
+  AO_REQUIRE_PTR(out);
+  AO_REQUIRE(cap >= 10, "ao_int4_mm_route: out holds %d fields, the route has 10", cap);
+  if (int rc = check_int4_shape(__func__, N, K, group_size)) return rc;
+  AO_REQUIRE(group_size != 0 && M > 0 && M < (1ll << 31), "ao_int4_mm_route: bad M=%lld or group size %d", (long long)M, group_size);
+  const Int4Route r = int4_route(M, N, K, group_size, Int4Force{});
+  const int32_t v[10] = {(int32_t)r.form, r.rows, r.depth, r.straight, r.waves, r.nt, r.mt, r.cg, r.split, r.prod};
+  for (int i = 0; i < 10; ++i) out[i] = v[i];
+  return AO_OK;
+}
+
 extern "C" int ao_int4_set_trace(unsigned long long* trace_dev) {
   g_mm_trace = trace_dev;
   fp8_rowwise_rb_set_trace(trace_dev);
@@ -1518,6 +1530,13 @@ extern "C" int ao_int4_set_trace(unsigned long long* trace_dev) {
 }
 
 const Int4Force& ao::int4_force() { return g_int4_force; }
+
+// 1 when the calling thread has an ao_int4_set_tuning override set
+extern "C" int ao_int4_overridden(void) {
+  const Int4Force& f = g_int4_force;
+  const Int4Force d{};
+  return !(f.wpb == d.wpb && f.mode == d.mode && f.fp8_mt == d.fp8_mt && f.fp8_nt1 == d.fp8_nt1);
+}
 
 extern "C" int ao_int4_set_tuning(int waves_per_block, int mode) {
   Int4Force& f = g_int4_force;

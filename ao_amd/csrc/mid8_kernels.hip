@@ -186,7 +186,7 @@ __global__ __launch_bounds__(512, 4) void mid8_kernel(Mid8Args p) {
         float v;
         if constexpr (INT8) {
           // t = bf16(f32(c) * sx[m]);  y = bf16(f32(t) * sw[n] (+ bias))   (int8_tensor.py:315-359)
-          v = round_bf16((float)__builtin_bit_cast(i32x4, acc[mt])[r] * sa[mt * 4 + r]) * sb;
+          v = mul_f32_rn(round_bf16((float)__builtin_bit_cast(i32x4, acc[mt])[r] * sa[mt * 4 + r]), sb);
         } else {
           v = acc[mt][r] * sa[mt * 4 + r] * sb;
         }

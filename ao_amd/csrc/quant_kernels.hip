@@ -158,7 +158,7 @@ __global__ __launch_bounds__(kThreads) void scale_epilogue_kernel(const void* __
     float v;
     if (INT8) {
       const float t = round_bf16((float)reinterpret_cast<const int32_t*>(acc)[row * N + n] * rs);
-      v = t * col_scale[n];
+      v = mul_f32_rn(t, col_scale[n]);
     } else {
       v = reinterpret_cast<const float*>(acc)[row * N + n] * rs * col_scale[n];
     }
@@ -269,7 +269,7 @@ __global__ __launch_bounds__(kThreads) void scale_epilogue_asym_kernel(const int
   for (int64_t n = (int64_t)blockIdx.x * kThreads + threadIdx.x; n < N; n += (int64_t)gridDim.x * kThreads) {
     float t = round_bf16((float)acc[row * N + n] * xs);
     t = round_bf16(t - round_bf16(zs * (float)w_sums[n]));
-    float v = t * w_scale[n];
+    float v = mul_f32_rn(t, w_scale[n]);
     if (bias != nullptr) v += bf16_lo_to_f32(bias[n]);
     y[row * N + n] = f32_to_bf16_bits(v);
   }

@@ -523,7 +523,7 @@ __global__ __launch_bounds__(64 * WAVES) void rb8_kernel(Rb8Args p) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float v;
-          if constexpr (INT8) v = round_bf16((float)__builtin_bit_cast(i32x4, c)[r] * sa4[r]) * sbv;
+          if constexpr (INT8) v = mul_f32_rn(round_bf16((float)__builtin_bit_cast(i32x4, c)[r] * sa4[r]), sbv);
           else v = c[r] * sa4[r] * sbv;
           if (p.bias != nullptr) v += bv;
           *reinterpret_cast<uint16_t*>(smem + (mt * 16 + kq * 4 + r) * RS + (ntl * 16 + nl) * 2) = f32_to_bf16_bits(v);
@@ -578,7 +578,7 @@ __global__ __launch_bounds__(64 * WAVES) void rb8_kernel(Rb8Args p) {
           const int m = m0 + (4 * wm + i) * 16 + kq * 4 + r;
           if (m < m_end && nj[j] >= 0) {
             float v;
-            if constexpr (INT8) v = round_bf16((float)__builtin_bit_cast(i32x4, acc[2 * i + j])[r] * sa[i * 4 + r]) * sbj[j];
+            if constexpr (INT8) v = mul_f32_rn(round_bf16((float)__builtin_bit_cast(i32x4, acc[2 * i + j])[r] * sa[i * 4 + r]), sbj[j]);
             else v = acc[2 * i + j][r] * sa[i * 4 + r] * sbj[j];
             if (p.bias != nullptr) v += biasj[j];
             y[(size_t)m * p.N + nj[j]] = f32_to_bf16_bits(v);
@@ -614,7 +614,7 @@ __global__ __launch_bounds__(64 * WAVES) void rb8_kernel(Rb8Args p) {
           float v;
           if constexpr (INT8) {
             // t = bf16(f32(c) * sx[m]);  y = bf16(f32(t) * sw[n] (+ bias))   (int8_tensor.py:315-359)
-            v = round_bf16((float)__builtin_bit_cast(i32x4, acc[mt])[r] * sa[mt * 4 + r]) * sb;
+            v = mul_f32_rn(round_bf16((float)__builtin_bit_cast(i32x4, acc[mt])[r] * sa[mt * 4 + r]), sb);
           } else {
             v = acc[mt][r] * sa[mt * 4 + r] * sb;
           }

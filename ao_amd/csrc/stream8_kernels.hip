@@ -143,7 +143,7 @@ __global__ __launch_bounds__(512) void stream8_kernel(Stream8Args p) {
         const int gm = row_begin + m_base + row, gn = ntile * 16 + col;
         if constexpr (INT8) {
           // t = bf16(f32(c) * sx[m]);  y = bf16(f32(t) * sw[n] (+ bias))   (int8_tensor.py:315-359)
-          sum = round_bf16((float)isum * p.row_scale[gm]) * p.col_scale[gn];
+          sum = mul_f32_rn(round_bf16((float)isum * p.row_scale[gm]), p.col_scale[gn]);
           if (p.bias != nullptr) sum += bf16_lo_to_f32(p.bias[gn]);
         } else if (!MX) {
           sum = sum * p.row_scale[gm] * p.col_scale[gn];

@@ -123,6 +123,8 @@ int ao_int4_quantize_tinygemm(const uint16_t* w, int32_t* qdata,
  * kernel -- and so return wrong numbers -- exist only in the laboratory build (`python -m ao_amd.build --lab` ->
  * tools/bin/_C_mi355_lab.so, compiled with -DAO_LAB; tools select it through AO_MI355_LIB).  Thread-local. */
 int ao_int4_set_tuning(int waves_per_block, int mode);
+/* 1 when the calling thread has an ao_int4_set_tuning override set, else 0 (tests assert the product dispatch).  Host only. */
+int ao_int4_overridden(void);
 /* Profiling only: 0 = product dispatch of the 8-bit GEMMs (LDS-DMA staged kernel when K % 128 == 0),
  * 1 = force the register-staged kernel, 2 / 4 / 8 = force the LDS-DMA kernel with 128x128, 256x128 (4 waves), 256x256 (8 waves) tiles,
  * 32 = the phase-interleaved 256x256 kernel, 33 = its 256x128 form (gemm8_p8h_kernel); 100 / 101 / 102 = the fp8 weight-streaming kernel never / always / always with 64-column tiles; 103 = its round-3 wave arrangement (1 x 8);
@@ -146,9 +148,15 @@ int ao_gemm8_set_variant(int variant);
  *          (3 = the round-3 protocol)
  * An unknown key is an error.  DESIGN.md 4.5h. */
 int ao_gemm8_set_tuning(int key, int value);
+/* 1 when the calling thread has any ao_gemm8_set_variant / ao_gemm8_set_tuning override set, else 0.  Host only. */
+int ao_gemm8_overridden(void);
 /* Name of the kernel ao_int4_weight_int4pack_mm launches for this problem: the product route, whatever override
  * ao_int4_set_tuning has set -- what a profiler's kernel table should be matched against.  Static string. */
 const char* ao_int4_mm_kernel_name(int64_t M, int64_t N, int64_t K, int group_size);
+/* Every field of that product route (host logic only): out[cap >= 10] = form (0 int4_mm_kernel, 1 int4_mm_rb_kernel, 2 int4_mm_w32_kernel),
+ * rows of the per-tile build, ring depth, straight-line, waves, n-tiles, m-tiles, column groups (w32: 2 = 128 x 256 tiles), K parts,
+ * producer form. */
+int ao_int4_mm_route(int64_t M, int64_t N, int64_t K, int group_size, int32_t* out, int cap);
 /* Which kernel ao_fp8_scaled_mm (int8 = 0) / ao_int8_scaled_mm (int8 = 1) dispatches a shape to: "dec8_kernel" (M <= 16), "mid8_kernel",
  * "stream8_kernel", "rb8_kernel" (up to 256 tiles of 128 x 128), "gemm8_p8h_kernel" / "gemm8_p8_kernel" / "gemm8_p8p_kernel" /
  * "gemm8_dma_kernel<...>" / "gemm8_kernel" (tiled), or "invalid".  The route the launch takes for 16-byte-aligned scales and output, whatever
@@ -162,6 +170,12 @@ int ao_gemm8_plan(int int8, int64_t M, int64_t N, int64_t K, int* tile_cols, int
  * cut M instead of K where the fixed costs of a launch outweigh its loop), 256 for the 256 x 128 / 256 x 256 GEMMs, 128 / 16 otherwise.
  * Host logic only.  DESIGN.md 4.5. */
 int ao_gemm8_plan_rows(int int8, int64_t M, int64_t N, int64_t K, int* tile_rows);
+/* Every field of the product route of one 8-bit entry point, for aligned (1) or unaligned (0) scales / bias (the route the launch takes
+ * with no override set; host logic only).  entry: 0 ao_int8_scaled_mm, 1 ao_fp8_scaled_mm, 2 ao_int8_int_mm, 3 ao_fp8_mm_f32,
+ * 4 ao_int8_dynamic_linear, 5 ao_fp8_dynamic_linear.  out[cap >= 11] = kernel (0 = invalid, then the ao_gemm8_kernel_name order: dec8,
+ * mid8, stream8, rb8, p8h, p8, p8p, dma 128x128, dma 256x256, dma 256x128, dma 256x256 4 waves, gemm8_kernel, dyn8), tile rows,
+ * tile columns, K parts, dec8 waves, depth, loop, half, rows8, mid8 m-tiles, mid8 K parts. */
+int ao_gemm8_route(int entry, int64_t M, int64_t N, int64_t K, int aligned, int32_t* out, int cap);
 /* Which form of fp8_int4_mm_kernel ao_fp8_int4_linear launches for a shape: "<m-tiles x n-tiles>" of 16 x 16 per workgroup -- "<1x1>" up to
  * 16 rows, "<2x1>" / "<2x2>" beyond (round 5: the weights stream once per 32 rows, the staged activations serve 32 columns), or "invalid".
  * Host logic only.  DESIGN.md 4.9. */

@@ -198,17 +198,30 @@ def test_queries_ignore_overrides():
     int4 = lambda: {(m, n, k, g): lib.ao_int4_mm_kernel_name(m, n, k, g).decode()  # noqa: E731
                     for m in (1, 5, 9, 16, 17, 64, 65, 128, 129, 512, 2048) for n, k in PLAN_SHAPES.values() for g in (32, 128)}
     int4_product = int4()
+
+    def routes():  # every field of ao_gemm8_route / ao_int4_mm_route
+        import route_cases as rc
+
+        shapes = [(m, n, k) for m in (1, 5, 16, 17, 64, 65, 128, 129, 512, 2048) for n, k in PLAN_SHAPES.values()]
+        r8 = {(e, a) + s: rc.route8(lib, e, *s, aligned=a) for e in rc.ENTRIES8 for a in (True, False) for s in shapes}
+        r4 = {s + (g,): rc.route4(lib, *s, g) for s in shapes for g in (32, 128)}
+        return r8, r4
+
+    routes_product = routes()
     try:
         for variant in (1, 8, 32, 100, 101, 103, 113, 201, 293, 299, 300, 301, 312):
             lib.ao_gemm8_set_variant(variant)
             check_8bit(("variant", variant))
+            assert routes() == routes_product, ("variant", variant)
         lib.ao_gemm8_set_variant(0)
         for key, value in ((1, 32), (3, 128), (6, 2), (7, 3)):
             lib.ao_gemm8_set_tuning(key, value)
             check_8bit(("tuning", key, value))
+            assert routes() == routes_product, ("tuning", key, value)
         for wpb, mode in ((8, 99), (0, 911), (0, 650)):
             lib.ao_int4_set_tuning(wpb, mode)
             assert int4() == int4_product, (wpb, mode)
+            assert routes() == routes_product, (wpb, mode)
     finally:
         lib.ao_gemm8_set_variant(0)
         for key in (1, 3, 6, 7):

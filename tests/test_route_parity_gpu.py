@@ -1,0 +1,287 @@
+"""Every GEMM route the product takes (tests/route_cases.py CASES) against a float64 reference, through the C ABI, on guarded and
+poisoned output buffers (tests/_parity.py).
+
+Operands are drawn directly, not quantised from normals: int8 codes uniform over [-128, 127], every finite e4m3fn code, random int4
+nibbles; row / column scales 2^U(-10, 4), int4 scales and zeros 2^U(-6, 2) per (group, column), bias randn x 2^U(-4, 4) per column,
+bf16 activations (int4, dynamic entries) with row magnitudes 2^U(-8, 8).  A scale, group or bias read from the wrong index is off by a
+large factor.  The reference is a float64 product in torch on the device; the int8 epilogue and the activation casts are the oracle's.
+Every case launches twice into differently poisoned buffers (split-K routes with another split-K launch in between) and must give the
+same bits; its route must still be the recorded one.
+"""
+import numpy as np
+import pytest
+import torch
+
+import _parity
+import route_cases as rc
+from ao_amd import _lib
+from oracle import fp8_ref, int4_ref, int8_ref
+
+# Outputs equal to the oracle's rounding, at least (tests/_parity.py; bf16 x int4: its default 0.97).  Measured on every route of
+# these families with the operands below: fp8 GEMMs 0.958 - 0.97, fp8 x int4 0.94 - 0.96, each element within the bound.
+EQUAL_FP8 = 0.95
+EQUAL_FP8_INT4 = 0.93
+
+_TILE_INDEX = None
+
+
+def _tile_index():
+    """Flat (n, k) index, inside one 16 x 128 tile, of every nibble slot of the tile's 64 x 4 words (oracle int4_ref._tile_coords)."""
+    global _TILE_INDEX
+    if _TILE_INDEX is None:
+        n_idx, k_idx = int4_ref._tile_coords(1, 1)
+        _TILE_INDEX = torch.from_numpy((n_idx[0, 0] * 128 + k_idx[0, 0]).astype(np.int64))
+    return _TILE_INDEX
+
+
+def pack_int4(q):
+    """oracle int4_ref.convert_weight_to_int4pack(nibble_pack(q)) in torch: q int [N, K] in 0..15 -> int32 [N/8, K/128, 32, 4]."""
+    N, K = q.shape
+    t = q.reshape(N // 16, 16, K // 128, 128).permute(0, 2, 1, 3).reshape(N // 16, K // 128, 2048)
+    vals = t[:, :, _tile_index().to(q.device).view(-1)].view(N // 16, K // 128, 64, 4, 8).to(torch.int64)
+    words = (vals << (4 * torch.arange(8, device=q.device))).sum(-1)
+    words = torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32)
+    return words.reshape(N // 8, K // 128, 32, 4)
+
+
+def dequant_tinygemm(q, sz, G):
+    """oracle int4_ref.dequantize_tinygemm in torch: bf16( bf16( bf16(q - 8) * s ) + z ), bf16 [N, K]."""
+    N, K = q.shape
+    s = sz[..., 0].float().T[:, :, None]
+    z = sz[..., 1].float().T[:, :, None]
+    w = ((q - 8).float().view(N, K // G, G) * s).bfloat16().float() + z
+    return w.bfloat16().view(N, K)
+
+
+# ---- operands ----
+
+class Draw:
+    def __init__(self, seed, dev):
+        self.g = torch.Generator(device=dev).manual_seed(seed)
+        self.dev = dev
+
+    def rand(self, *shape):
+        return torch.rand(*shape, generator=self.g, device=self.dev, dtype=torch.float64)
+
+    def pow2(self, lo, hi, *shape):
+        return torch.exp2(self.rand(*shape) * (hi - lo) + lo)
+
+    def int8(self, *shape):
+        return torch.randint(-128, 128, shape, generator=self.g, device=self.dev, dtype=torch.int8)
+
+    def fp8(self, *shape):
+        """Every finite e4m3fn code (0x7F / 0xFF are NaN), subnormals and +-448 included."""
+        i = torch.randint(0, 254, shape, generator=self.g, device=self.dev)
+        return (i + (i >= 0x7F).to(i.dtype)).to(torch.uint8)
+
+    def nibbles(self, *shape):
+        return torch.randint(0, 16, shape, generator=self.g, device=self.dev)
+
+    def scales(self, n):
+        return self.pow2(-10, 4, n).float()
+
+    def bias(self, n):
+        return (torch.randn(n, generator=self.g, device=self.dev, dtype=torch.float64) * self.pow2(-4, 4, n)).bfloat16()
+
+    def act(self, M, K):
+        """bf16 activations whose row magnitudes span 2^-8 .. 2^8."""
+        x = torch.randn(M, K, generator=self.g, device=self.dev, dtype=torch.float64) * self.pow2(-8, 8, M, 1)
+        return x.bfloat16()
+
+    def int4_sz(self, K, N, G, zeros=True):
+        s = self.pow2(-6, 2, K // G, N)
+        z = self.pow2(-6, 2, K // G, N) * (torch.randint(0, 2, (K // G, N), generator=self.g, device=self.dev) * 2 - 1) if zeros else 0 * s
+        return torch.stack([s, z], -1).bfloat16().contiguous()
+
+
+def _offset(t, aligned):
+    """t itself, or a copy of it at a one-element offset (4 bytes for fp32 scales, 2 for bf16 bias)."""
+    if aligned or t is None:
+        return t
+    buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=t.device)
+    buf[1:].copy_(t)
+    return buf[1:]
+
+
+def _e4m3(codes):
+    return torch.from_numpy(fp8_ref.E4M3.astype(np.float64)).to(codes.device)[codes.long()]
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+# ---- one case: operands, launch, reference ----
+
+class Run:
+    """Operands of a case, a launch into a guarded buffer, and the reference the output must meet."""
+
+    def __init__(self, case, seed, dev):
+        self.case, self.dev = case, dev
+        fam, entry, M, N, K, G, bias, aligned = case
+        d = Draw(seed, dev)
+        self.bias = d.bias(N) if bias else None
+        self.ref = {}
+        if fam == "gemm8":
+            self._gemm8(d, entry, M, N, K)
+        elif fam == "int4":
+            self._int4(d, M, N, K, G)
+        else:
+            self._fp8_int4(d, entry, M, N, K, G)
+        self.sa = _offset(getattr(self, "sa", None), aligned)
+        self.sb = _offset(getattr(self, "sb", None), aligned)
+        self.bias_arg = _offset(self.bias, aligned)
+
+    def _bias64(self):
+        return 0 if self.bias is None else self.bias.double()[None, :]
+
+    def _gemm8(self, d, entry, M, N, K):
+        self.out_dtype = torch.int32 if entry == "int_mm" else torch.float32 if entry == "fp8_mm_f32" else torch.bfloat16
+        if entry in ("int8_dyn", "fp8_dyn"):
+            self.x = d.act(M, K)
+            xs = self.x.float().cpu().numpy()
+            q, s = (int8_ref if entry == "int8_dyn" else fp8_ref).quantize_rowwise(xs)
+            self.a = torch.from_numpy(q.view(np.uint8) if entry == "fp8_dyn" else q).to(self.dev)
+            self.sa = torch.from_numpy(s).to(self.dev)
+        else:
+            self.a = d.int8(M, K) if entry in ("int8_scaled", "int_mm") else d.fp8(M, K)
+            self.sa = d.scales(M) if entry in rc.SCALED else None
+        int8 = entry in ("int8_scaled", "int_mm", "int8_dyn")
+        self.b = d.int8(N, K) if int8 else d.fp8(N, K)
+        self.sb = d.scales(N) if entry not in ("int_mm", "fp8_mm_f32") else None
+        A, B = (self.a.double(), self.b.double()) if int8 else (_e4m3(self.a), _e4m3(self.b))
+        acc = A @ B.T
+        if entry == "int_mm":
+            self.ref["ref_bits"] = acc.to(torch.int32)
+        elif int8:  # the oracle's epilogue on the exact accumulator (int8_ref.scaled_mm)
+            y = (acc.float() * self.sa[:, None]).bfloat16().float() * self.sb[None, :]
+            if self.bias is not None:
+                y = y + self.bias.float()[None, :]
+            self.ref["ref_bits"] = y.bfloat16()
+        else:
+            S = A.abs() @ B.abs().T
+            if entry != "fp8_mm_f32":
+                sc = self.sa.double()[:, None] * self.sb.double()[None, :]
+                acc, S = acc * sc + self._bias64(), S * sc + abs(self._bias64())
+            self.ref.update(ref64=acc, S=S, K=K, equal=EQUAL_FP8)
+
+    def _int4(self, d, M, N, K, G):
+        self.out_dtype = torch.bfloat16
+        self.x = d.act(M, K)
+        q = d.nibbles(N, K)
+        self.qdata = pack_int4(q)
+        self.sz = d.int4_sz(K, N, G)
+        w = dequant_tinygemm(q, self.sz, G).double()
+        X = self.x.double()
+        self.ref.update(ref64=X @ w.T, S=X.abs() @ w.abs().T, K=K)
+
+    def _fp8_int4(self, d, entry, M, N, K, G):
+        self.out_dtype = torch.bfloat16
+        if entry.startswith("dyn"):
+            self.x = d.act(M, K)
+            q8, s8 = fp8_ref.quantize_rowwise(self.x.float().cpu().numpy())
+            self.a, self.sa = torch.from_numpy(q8).to(self.dev), torch.from_numpy(s8).to(self.dev)
+        else:
+            self.a, self.sa = d.fp8(M, K), d.scales(M)
+        q = d.nibbles(N, K)
+        self.qdata = pack_int4(q)
+        self.sz = d.int4_sz(K, N, G, zeros=entry.endswith("asym"))
+        s = self.sz[..., 0].double().T.repeat_interleave(G, 1)
+        z = self.sz[..., 1].double().T.repeat_interleave(G, 1)
+        w, wabs = s * (q - 8).double() + z, (s * (q - 8).double()).abs() + z.abs()
+        X = _e4m3(self.a)
+        xs = self.sa.double()[:, None]
+        self.ref.update(ref64=xs * (X @ w.T) + self._bias64(), S=xs * (X.abs() @ wabs.T) + abs(self._bias64()), K=K, equal=EQUAL_FP8_INT4)
+
+    def launch(self, buf):
+        lib = _lib.lib()
+        fam, entry, M, N, K, G = self.case[:6]
+        s = torch.cuda.current_stream().cuda_stream
+        y = buf.out.data_ptr()
+        if fam == "gemm8":
+            call = {
+                "int8_scaled": lambda: lib.ao_int8_scaled_mm(_ptr(self.a), _ptr(self.sa), _ptr(self.b), _ptr(self.sb), _ptr(self.bias_arg), y, M, N, K, s),
+                "fp8_scaled": lambda: lib.ao_fp8_scaled_mm(_ptr(self.a), _ptr(self.b), _ptr(self.sa), _ptr(self.sb), _ptr(self.bias_arg), y, M, N, K, s),
+                "int_mm": lambda: lib.ao_int8_int_mm(_ptr(self.a), _ptr(self.b), y, M, N, K, s),
+                "fp8_mm_f32": lambda: lib.ao_fp8_mm_f32(_ptr(self.a), _ptr(self.b), y, M, N, K, s),
+                "int8_dyn": lambda: lib.ao_int8_dynamic_linear(_ptr(self.x), _ptr(self.b), _ptr(self.sb), _ptr(self.bias_arg), y, M, N, K, s),
+                "fp8_dyn": lambda: lib.ao_fp8_dynamic_linear(_ptr(self.x), _ptr(self.b), _ptr(self.sb), _ptr(self.bias_arg), y, M, N, K, s),
+            }[entry]
+            rc_ = call()
+        elif fam == "int4":
+            rc_ = lib.ao_int4_weight_int4pack_mm(_ptr(self.x), _ptr(self.qdata), _ptr(self.sz), y, M, N, K, G, s)
+        elif entry.startswith("dyn"):
+            rc_ = lib.ao_fp8_int4_dynamic_linear(_ptr(self.x), _ptr(self.qdata), _ptr(self.sz), _ptr(self.bias_arg), y, M, N, K, G, s)
+        else:
+            rc_ = lib.ao_fp8_int4_linear(_ptr(self.a), _ptr(self.sa), _ptr(self.qdata), _ptr(self.sz), _ptr(self.bias_arg), y, M, N, K, G, s)
+        _lib.check(rc_)
+        torch.cuda.synchronize()
+
+
+# the smallest split-K case of each family: launched between the two launches of a split-K case
+_SPLIT = {}
+for _c, _s in sorted(rc.CASES, key=lambda cs: rc.cost(cs[0])):
+    if _s.endswith("/kparts"):
+        _SPLIT.setdefault(_c.family, _c)
+
+
+@pytest.fixture(scope="module")
+def product_dispatch():
+    """The launches take the product dispatch: no override may be set when the module starts, and none is left when it ends."""
+    lib = _lib.lib()
+    assert not lib.ao_gemm8_overridden() and not lib.ao_int4_overridden(), "an earlier test left an ao_gemm8_* / ao_int4_set_tuning override set"
+    try:
+        yield lib
+    finally:
+        torch.cuda.synchronize()
+        assert not lib.ao_gemm8_overridden() and not lib.ao_int4_overridden()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("index", range(len(rc.CASES)), ids=["%s:%d,%d,%d%s%s" % (s, c.M, c.N, c.K, "+b" if c.bias else "", "" if c.aligned else ":unal")
+                                                              for c, s in rc.CASES])
+def test_route_parity(product_dispatch, index):
+    case, sig = rc.CASES[index]
+    lib = product_dispatch
+    route = rc.route_of(lib, case)
+    assert route is not None and route["sig"] == sig, (case, sig, route and route["sig"])
+    dev = torch.device("cuda", 0)
+    run = Run(case, 1000 + index, dev)
+    buf = _parity.Guarded(case.M, case.N, run.out_dtype, dev)
+    run.launch(buf)
+    _parity.check(buf, route=route, **run.ref)
+    first = buf.bits().clone()
+
+    if route["parts"] > 1:  # no ticket or workspace state may carry over from another split-K launch
+        other = _SPLIT[case.family] if _SPLIT[case.family] != case else None
+        if other is not None:
+            orun = Run(other, 7, dev)
+            orun.launch(_parity.Guarded(other.M, other.N, orun.out_dtype, dev))
+    buf.poison(_parity.SENTINEL2)
+    run.launch(buf)
+    assert not buf.guard_problems(), buf.guard_problems()
+    same = buf.bits() == first
+    if not bool(same.all()):
+        i, j = (int(v) for v in torch.nonzero(~same)[0])
+        raise AssertionError("second launch differs in %d elements, first at row %d, column %d%s"
+                             % (int((~same).sum()), i, j, _parity.locate(i, j, route)))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("entry", ("int8_dyn", "fp8_dyn"))
+@pytest.mark.parametrize("M", (1, 5, 16))
+@pytest.mark.parametrize("bias", (False, True))
+def test_dyn8_override_form(product_dispatch, entry, M, bias):
+    """dyn8_kernel, the fused decode form no product route takes (ao_gemm8_set_variant(299): never dec8_kernel), against the same
+    reference: its int8 epilogue adds the bias to the rounded product like the others."""
+    lib = product_dispatch
+    case = rc.Case("gemm8", entry, M, 208, 1152, 0, bias, True)
+    dev = torch.device("cuda", 0)
+    run = Run(case, 77 + M, dev)
+    buf = _parity.Guarded(case.M, case.N, run.out_dtype, dev)
+    lib.ao_gemm8_set_variant(299)
+    try:
+        run.launch(buf)
+    finally:
+        lib.ao_gemm8_set_variant(0)
+    _parity.check(buf, **run.ref)
