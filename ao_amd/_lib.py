@@ -49,6 +49,7 @@ _SIGNATURES = {
     "ao_gemm8_plan": [_INT, _I64, _I64, _I64, _P, _P],
     "ao_gemm8_plan_rows": [_INT, _I64, _I64, _I64, _P],
     "ao_gemm8_route": [_INT, _I64, _I64, _I64, _INT, _P, _INT],
+    "ao_grouped8_route": [_INT, _I64, _I64, _I64, _I64, _INT, _P, _INT],
     "ao_gemm8_overridden": [],
     "ao_int4_overridden": [],
     "ao_int4_mm_route": [_I64, _I64, _I64, _INT, _P, _INT],

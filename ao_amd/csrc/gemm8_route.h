@@ -1,6 +1,8 @@
 // Host only: which kernel an 8-bit GEMM entry point launches for a shape, and with what launch shape.
 // gemm8_route (gemm8_kernels.hip) is the one function that decides: the entry points launch what it returns, and the introspection
 // queries (ao_gemm8_kernel_name / ao_gemm8_plan / ao_gemm8_plan_rows) report what it returns for the product (Gemm8Force{}).
+// grouped8_route (rb8_kernels.hip) does the same for the grouped entry points (ao_fp8_grouped_mm, ao_mxfp8_grouped_mm and its fused-cast /
+// pair forms; ao_grouped8_route reports it).
 // The band rules it is built from are pure functions of the shape and the forced codes, defined next to their kernels.
 // The A/B knobs that change no route are read by the launchers from gemm8_force(): rb8_kernel's wave arrangement (variant 103) and probe
 // bits (tuning key 5), gemm8_p8(h)'s group rows (key 4), the laboratory loop forms of gemm8_p8h (key 8), the MX stream-K meeting (key 9).
@@ -45,7 +47,7 @@ struct Gemm8Force {
   int tile = 0;             // 2 / 4 / 8 / 16 / 32 / 33: that tiled GEMM form
   int rb = 0;               // the rowwise weight-streaming kernel: 1 never (100, explicit tile variants), 2 always (101), 3 always + 64 columns (102)
   bool rb8_1x8 = false;     // 103: its round-3 wave arrangement (1 x 8)
-  int mx = 0;               // MXFP8 grouped mm: 1 always the LDS-staged kernels (110), 2 never (111)
+  int mx = 0;               // MXFP8 grouped mm: 2 never the LDS-staged kernels (111); 1 (110) is the product route, kept so old scripts run
   bool mx_stream = true;    // 113 (false): decode-size groups take one workgroup per tile instead of the stream-K kernel
   bool mx_quad = true;      // 129 (false): the stream-K kernel's per-step-scales form on every K
   int dec8 = 0;             // 200 .. 299: dec8_kernel's forms (dec8_plan)
@@ -59,6 +61,25 @@ const Gemm8Force& gemm8_force();
 
 // aligned: row / column scales and output 16-byte aligned, bias 4-byte aligned (the persistent 256 x 256 form needs it)
 Gemm8Route gemm8_route(Gemm8Entry entry, int64_t M, int64_t N, int64_t K, bool aligned, const Gemm8Force& f);
+
+// ao_fp8_grouped_mm, ao_mxfp8_grouped_mm, ao_mxfp8_grouped_mm_dyn, ao_mxfp8_grouped_mm_dyn_pair, ao_mxfp8_grouped_mm_pair
+enum class Grouped8Entry { Fp8Rowwise, Mx, MxDyn, MxDynPair, MxPair };
+
+// rb8_kernel (RB8_FP8_GROUPED / RB8_MX), mx_stream_kernel (stream-K), mx_grouped_kernel, stream8_kernel<S8_MX>
+enum class Grouped8Kernel { Invalid, Rb8, MxStream, MxGrouped, Stream8 };
+
+// The template arguments and launch shape of a grouped launch -- rb8: <waves, mt, slim, qs> over slabs of slab_rows rows, `slabs` per group;
+// mx_stream: <waves, sw, qs, cast>; mx_grouped: <mt, tn>; stream8: <mt>
+struct Grouped8Route {
+  Grouped8Kernel kernel = Grouped8Kernel::Invalid;
+  int waves = 0, mt = 0, slim = 0, qs = 0, sw = 0, cast = 0, tn = 0, slab_rows = 0, slabs = 0;
+};
+
+// The one decision of the grouped entry points, and the only reader of the MX forcing codes (variants 110 / 111 / 113 / 129, tuning key 3).
+// aligned: every pointer the per-4-step-scale (QS = 4) and stream-K forms read is 16-byte aligned; scaling_mode: the fused cast's
+// (AO_MX_SCALE_FLOOR / _RCEIL).  Invalid: the entry refuses the shape.
+Grouped8Route grouped8_route(Grouped8Entry entry, int64_t M_total, int64_t N, int64_t K, int64_t E, bool have_offs, bool aligned, int scaling_mode,
+                             const Gemm8Force& f);
 
 // ---- band rules (pure) ----
 bool dec8_plan(int64_t M, int64_t N, int64_t K, int mode, Dec8Shape* shape);  // dec8_kernels.hip (mode: Gemm8Force::dec8)

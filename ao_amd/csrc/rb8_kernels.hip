@@ -1134,12 +1134,6 @@ __global__ __launch_bounds__(64 * WAVES) void mx_stream_kernel(Rb8Args p) {
 
 thread_local unsigned long long* g_fp8_rb_trace = nullptr;  // profiling only (ao_int4_set_trace shares the pointer)
 
-// slab rows of the grouped forms: 64 for decode-size groups, else 128 (ao_gemm8_set_tuning key 3 forces a height: A/B)
-int grouped_slab_rows(int64_t M_total, int64_t groups) {
-  const int forced = gemm8_force().rb8_bm;
-  return (forced == 64 || forced == 128) ? forced : (M_total <= 48 * groups) ? 64 : 128;
-}
-
 template <int WAVES, int KIND, int MT = 8, bool SLIM = false, int QS = 1>
 int launch_rb8(Rb8Args p, int split, hipStream_t stream) {
   constexpr int BN = WAVES * 16;
@@ -1329,84 +1323,120 @@ int rb8_scaled(bool int8, const void* a, const void* b, const float* scale_a, co
               : rb8_run<RB8_FP8>(a8, b8, scale_a, scale_b, bias, y, M, N, K, bm, bn, split, stream);
 }
 
-// MXFP8 grouped GEMM (aten::_scaled_grouped_mm as called from mxfp8_grouped_mm.py:541, numerics of :959-1023): out rows of
-// group e = dq(a rows) . dq(b[e])^T with the E8M0 block scales as MFMA operands.  Group sizes live on the device:
-// `rows_hint` = rows the largest group is expected to have; the grid provides ceil(rows_hint / 128) slabs per group
-// (callers pass M_total when they cannot bound it: empty slabs exit at once).
-int mxfp8_grouped_rb(const uint8_t* a, const uint8_t* a_scale, const uint8_t* b, const uint8_t* b_scale, const int32_t* offs, uint16_t* out,
-                     int64_t M_total, int64_t N, int64_t K, int64_t E, int64_t rows_hint, hipStream_t stream) {
-  Rb8Args p{};
-  p.a = a; p.b = b; p.y = out; p.a_mx = a_scale; p.b_mx = b_scale; p.offs = offs;
-  p.M = (int)M_total; p.N = (int)N; p.K = (int)K; p.E = (int)E;
-  // Slab capacity from the average group size (the sizes themselves live on the device): 64 rows for decode-size groups (two
-  // workgroups per CU; a group's real m-tile count is found on the device), else 128.
-  const int64_t groups = (offs != nullptr ? E : 1);
-  const int bm = grouped_slab_rows(M_total, groups);
-  p.slabs = (int)std::max<int64_t>(1, (std::min(rows_hint, M_total) + bm - 1) / bm);
+// ---- the grouped GEMMs: MXFP8 (aten::_scaled_grouped_mm as called from mxfp8_grouped_mm.py:541, numerics of :959-1023) and rowwise fp8
+// (Float8Tensor's _grouped_mm, float8_tensor.py:1085-1122).  Out rows of group e = a rows . b[e]^T; the group sizes live on the device. ----
+
+namespace {
+
+// the stream-K form's bounds: the group table in registers (<= 64 groups), a ticket per 64-column tile (the bound of every form), a 32-bit
+// step counter.  products: 2 for the pair forms.
+bool mx_stream_fits(int64_t M_total, int64_t N, int64_t K, int64_t groups, int products) {
+  const int64_t tiles = ((M_total + 63) / 64 + groups) * ((N + 63) / 64) * products;
+  return groups <= 64 && tiles <= kSplitMaxTickets && tiles * (K >> 7) < (1ll << 31);
+}
+
+}  // namespace
+
+Grouped8Route grouped8_route(Grouped8Entry entry, int64_t M_total, int64_t N, int64_t K, int64_t E, bool have_offs, bool aligned, int scaling_mode,
+                             const Gemm8Force& f) {
+  Grouped8Route r;
+  if (M_total < 0 || N <= 0 || K <= 0 || E <= 0 || K % 128 != 0 || N % 16 != 0) return r;
+  const int64_t groups = have_offs ? E : 1;
+  const bool decode = M_total <= 48 * groups;  // decode-size groups (on average)
+  if (entry == Grouped8Entry::MxDyn || entry == Grouped8Entry::MxDynPair || entry == Grouped8Entry::MxPair) {
+    // the fused-cast and pair forms: decode-size groups on the 16-wave stream-K kernel only -- callers cast + multiply otherwise
+    if (M_total == 0 || !decode || !aligned || K % 512 != 0 || M_total * K >= (1ll << 31) || N * K >= (1ll << 32) ||
+        !mx_stream_fits(M_total, N, K, groups, entry == Grouped8Entry::MxDyn ? 1 : 2))
+      return r;
+    r.kernel = Grouped8Kernel::MxStream;
+    r.waves = 16, r.sw = 3, r.qs = 4, r.cast = (entry == Grouped8Entry::MxPair) ? 0 : (scaling_mode == 1) ? 2 : 1;
+    return r;
+  }
+  // rb8_kernel's slab height from the average group size: 64 rows for decode-size groups (two workgroups per CU; a group's real m-tile count
+  // is found on the device), else 128 (tuning key 3 forces a height: A/B).  The grid provides ceil(M_total / rows) slabs per group (empty
+  // ones exit at once).  It addresses activation rows with 32-bit byte offsets and puts the non-empty (expert, slab) pairs -- at most
+  // ceil(M_total / rows) + E -- on grid.y: tensors beyond either bound take the per-tile kernels, which have neither limit.
+  r.slab_rows = (f.rb8_bm == 64 || f.rb8_bm == 128) ? f.rb8_bm : decode ? 64 : 128;
+  r.slabs = (int)std::max<int64_t>(1, (M_total + r.slab_rows - 1) / r.slab_rows);
+  const bool rb_fits = M_total * K < (1ll << 32) && N * K < (1ll << 32) && (have_offs ? E : 0) + (M_total + r.slab_rows - 1) / r.slab_rows <= 65535;
   // 64-column tiles when 128-column ones would not give every CU a workgroup even if every group had tokens
   // (cutting K into 2 - 4 parts that meet through the split-K workspace -- finer work items for the last round when few experts
   // have tokens -- was measured and dropped: w1 64.6 -> 76.7 us, w2 78 -> 79 us with three experts hit, 105 -> 113 us with all
   // eight: priming a part's rings costs what the shorter tail saves)
-  // decode-size groups: the stream-K form when its bounds hold (group table in registers: E <= 64; 32-bit step counter; a
-  // ticket per tile).  Mixtral's shapes, hipGraph, us (w1 / w2; profiles/mx_rb_trace_r03.txt session G): three experts hit 58.0 / 71.3
-  // with one workgroup per tile -> 56.1 / 52.2; all eight 111 / 110 -> 101 / 91.
-  const Gemm8Force& f = gemm8_force();
-  if (bm == 64 && f.mx_stream && groups <= 64) {
-    const int64_t tiles = ((M_total + 63) / 64 + groups) * ((N + 63) / 64);  // (64-column tiles: the bound of every form)
-    if (tiles <= kSplitMaxTickets && tiles * (K >> 7) < (1ll << 31))
-    {
-      // scales fetched per 4 steps when K allows (16-byte pieces of 16-byte-aligned scale rows), else per step
-      const bool quad = f.mx_quad && K % 512 == 0 && ((uintptr_t)a_scale % 16 == 0) && ((uintptr_t)b_scale % 16 == 0);
-      // round 6: ONE 16-wave workgroup per CU over 256-column tiles where the scales can be fetched per 4 steps; other K (and variant 129,
-      // which tests that form on every shape) the 8-wave form of rounds 3 - 5 with the scales fetched per step, two workgroups per CU
-      if (quad) return launch_mx_stream<16, 3, 4>(p, stream);
-      return launch_mx_stream<8, 3, 1>(p, stream);
+  const int waves = (r.slab_rows == 128 && ((N + 127) / 128) * groups * r.slabs >= 400) ? 8 : 4;
+  if (entry == Grouped8Entry::Fp8Rowwise) {
+    if (!rb_fits) return Grouped8Route{};
+    r.kernel = Grouped8Kernel::Rb8;
+    r.waves = waves, r.mt = r.slab_rows / 16, r.qs = 1;
+    return r;
+  }
+  // MXFP8: the LDS-staged kernels are the product path.  Mixtral-8x7B expert shapes, 8 experts (w1, w2; us): 16 rows per expert --
+  // A-stationary kernel 97 / 120, LDS-staged 89 / 110; 128 rows per expert -- 381 / 474 (the A-stationary kernel re-streams the weights
+  // per 64-row pass) vs 211 / 172.  Variant 111 keeps the older kernels reachable for A/B runs.
+  if (f.mx != 2 && rb_fits) {
+    // scales fetched per 4 steps when K allows (16-byte pieces of 16-byte-aligned scale rows), else per step (and under variant 129)
+    const bool quad = f.mx_quad && K % 512 == 0 && aligned;
+    // decode-size groups: the stream-K form when its bounds hold.  Mixtral's shapes, hipGraph, us (w1 / w2; profiles/mx_rb_trace_r03.txt
+    // session G): three experts hit 58.0 / 71.3 with one workgroup per tile -> 56.1 / 52.2; all eight 111 / 110 -> 101 / 91.
+    // Round 6: ONE 16-wave workgroup per CU over 256-column tiles with the scales per 4 steps; else the 8-wave form of rounds 3 - 5, two
+    // workgroups per CU.  Variant 113: one workgroup per tile instead.
+    if (r.slab_rows == 64 && f.mx_stream && mx_stream_fits(M_total, N, K, groups, 1)) {
+      r.kernel = Grouped8Kernel::MxStream;
+      r.waves = quad ? 16 : 8, r.sw = 3, r.qs = quad ? 4 : 1;
+      return r;
     }
+    // larger groups (and more than 64 experts): one workgroup per (slab, tile)
+    r.kernel = Grouped8Kernel::Rb8;
+    r.waves = waves, r.mt = r.slab_rows / 16, r.slim = (r.slab_rows == 64 && !quad), r.qs = quad ? 4 : 1;
+    return r;
   }
-  // larger groups (and more than 64 experts): one workgroup per (slab, tile); scales per 4 steps when K allows
-  const bool quad = f.mx_quad && K % 512 == 0 && ((uintptr_t)a_scale % 16 == 0) && ((uintptr_t)b_scale % 16 == 0);
-  if (bm == 64) {
-    return quad ? launch_rb8<4, RB8_MX, 4, false, 4>(p, 1, stream) : launch_rb8<4, RB8_MX, 4, true>(p, 1, stream);
+  r.slab_rows = r.slabs = 0;
+  if (have_offs && K % 2048 == 0) {
+    // the A-stationary kernel.  Size the m-tiling for twice the AVERAGE group: a larger group takes another pass over its expert's
+    // weights (correct, slower), while sizing for the worst case (one group of M_total rows) would carry 4 m-tiles of A and
+    // accumulators everywhere.  n-tiles per workgroup: as many as the accumulators allow (A is fetched once per workgroup) while the
+    // grid still has >= 1024 workgroups -- only experts that received tokens do any work.
+    const int64_t guess = (2 * M_total + E - 1) / E, ntiles = N >> 4;
+    auto enough = [&](int tn) { return ((ntiles + tn - 1) / tn) * E >= 1024; };
+    r.kernel = Grouped8Kernel::MxGrouped;
+    r.mt = guess <= 16 ? 1 : guess <= 32 ? 2 : 4;
+    r.tn = (r.mt == 1 && enough(8)) ? 8 : enough(4) ? 4 : 2;
+    return r;
   }
-  if (((N + 127) / 128) * groups * p.slabs < 400) return quad ? launch_rb8<4, RB8_MX, 8, false, 4>(p, 1, stream) : launch_rb8<4, RB8_MX, 8>(p, 1, stream);
-  return quad ? launch_rb8<8, RB8_MX, 8, false, 4>(p, 1, stream) : launch_rb8<8, RB8_MX, 8>(p, 1, stream);
+  // other K: the per-tile kernel, m-tiling for the worst case (a group cannot exceed M_total rows)
+  r.kernel = Grouped8Kernel::Stream8;
+  r.mt = M_total <= 16 ? 1 : M_total <= 32 ? 2 : 4;
+  return r;
 }
 
-// The same with the activations' 1 x 32 cast fused into the A-fill (reference call order mxfp8_grouped_mm.py:330-371: to_mx(A)
-// then the grouped mm): `a` is the BF16 [M_total, K] matrix.  Decode-size groups on the 16-wave stream-K kernel only: mx_dyn_fits says
-// whether a shape is taken (callers cast + multiply otherwise).
-// (products: 1, or 2 for the pair forms -- two weight tensors of one shape against the same activations in one launch)
-bool mxfp8_grouped_dyn_fits(int64_t M_total, int64_t N, int64_t K, int64_t E, bool have_offs, int products) {
-  const int64_t groups = have_offs ? E : 1;
-  if (M_total <= 0 || M_total > 48 * groups || groups > 64 || K % 512 != 0 || N % 16 != 0) return false;
-  if (M_total * K >= (1ll << 31) || N * K >= (1ll << 32)) return false;
-  const int64_t tiles = ((M_total + 63) / 64 + groups) * ((N + 63) / 64) * products;
-  return tiles <= kSplitMaxTickets && tiles * (K >> 7) < (1ll << 31);
-}
-// a: BF16 activations (scaling_mode 0 / 1: the cast fused into the A-fill) or, with a_scale != nullptr, their e4m3 codes.  b2 / b2_scale /
-// out2: the second product of the pair forms, or null.
-int mxfp8_grouped_stream16(const void* a, const uint8_t* a_scale, const uint8_t* b, const uint8_t* b_scale, const uint8_t* b2, const uint8_t* b2_scale,
-                           const int32_t* offs, uint16_t* out, uint16_t* out2, int64_t M_total, int64_t N, int64_t K, int64_t E, int scaling_mode,
-                           hipStream_t stream) {
+// The MXFP8 grouped GEMM on rb8_kernel or the stream-K form, in the shape of `r`.  a: e4m3 codes with a_scale, or BF16 activations
+// (a_scale null: the cast fused into the A-fill); b2 / b2_scale / out2: the second product of the pair forms, or null.
+int mxfp8_grouped_rb(const Grouped8Route& r, const void* a, const uint8_t* a_scale, const uint8_t* b, const uint8_t* b_scale, const uint8_t* b2,
+                     const uint8_t* b2_scale, const int32_t* offs, uint16_t* out, uint16_t* out2, int64_t M_total, int64_t N, int64_t K, int64_t E,
+                     hipStream_t stream) {
   Rb8Args p{};
   p.a = reinterpret_cast<const uint8_t*>(a); p.b = b; p.y = out; p.a_mx = a_scale; p.b_mx = b_scale; p.offs = offs;
   p.b2 = b2; p.b2_mx = b2_scale; p.y2 = out2;
-  p.M = (int)M_total; p.N = (int)N; p.K = (int)K; p.E = (int)E;
-  if (a_scale != nullptr) return launch_mx_stream<16, 3, 4>(p, stream);
-  return scaling_mode == 1 ? launch_mx_stream<16, 3, 4, 2>(p, stream) : launch_mx_stream<16, 3, 4, 1>(p, stream);
+  p.M = (int)M_total; p.N = (int)N; p.K = (int)K; p.E = (int)E; p.slabs = r.slabs;
+  if (r.kernel == Grouped8Kernel::MxStream) {
+    if (r.qs == 1) return launch_mx_stream<8, 3, 1>(p, stream);
+    if (r.cast == 0) return launch_mx_stream<16, 3, 4>(p, stream);
+    return r.cast == 2 ? launch_mx_stream<16, 3, 4, 2>(p, stream) : launch_mx_stream<16, 3, 4, 1>(p, stream);
+  }
+  if (r.mt == 4) return r.qs == 4 ? launch_rb8<4, RB8_MX, 4, false, 4>(p, 1, stream) : launch_rb8<4, RB8_MX, 4, true>(p, 1, stream);
+  if (r.waves == 4) return r.qs == 4 ? launch_rb8<4, RB8_MX, 8, false, 4>(p, 1, stream) : launch_rb8<4, RB8_MX, 8>(p, 1, stream);
+  return r.qs == 4 ? launch_rb8<8, RB8_MX, 8, false, 4>(p, 1, stream) : launch_rb8<8, RB8_MX, 8>(p, 1, stream);
 }
 
-// Float8Tensor's _grouped_mm, rowwise (float8_tensor.py:1085-1122 -> scaled_grouped_mm with RowWise scales):
-//   out[rows of group e] = bf16((a . b[e]^T) * scale_a[m] * scale_b[e][n]); the grouping of the MXFP8 form, the epilogue of fp8 rowwise
-int fp8_rowwise_grouped_rb(const uint8_t* a, const uint8_t* b, const float* scale_a, const float* scale_b, const int32_t* offs, uint16_t* out,
-                           int64_t M_total, int64_t N, int64_t K, int64_t E, hipStream_t stream) {
+// The rowwise fp8 grouped GEMM: out[rows of group e] = bf16((a . b[e]^T) * scale_a[m] * scale_b[e][n]) -- the grouping of the MXFP8
+// form, the epilogue of fp8 rowwise -- in the shape of `r`
+int fp8_rowwise_grouped_rb(const Grouped8Route& r, const uint8_t* a, const uint8_t* b, const float* scale_a, const float* scale_b, const int32_t* offs,
+                           uint16_t* out, int64_t M_total, int64_t N, int64_t K, int64_t E, hipStream_t stream) {
   Rb8Args p{};
   p.a = a; p.b = b; p.scale_a = scale_a; p.scale_b = scale_b; p.y = out; p.offs = offs;
-  p.M = (int)M_total; p.N = (int)N; p.K = (int)K; p.E = (int)E;
-  const int bm = grouped_slab_rows(M_total, E);
-  p.slabs = (int)std::max<int64_t>(1, (M_total + bm - 1) / bm);
-  if (bm == 64) return launch_rb8<4, RB8_FP8_GROUPED, 4>(p, 1, stream);
-  return (((N + 127) / 128) * E * p.slabs < 400) ? launch_rb8<4, RB8_FP8_GROUPED, 8>(p, 1, stream) : launch_rb8<8, RB8_FP8_GROUPED, 8>(p, 1, stream);
+  p.M = (int)M_total; p.N = (int)N; p.K = (int)K; p.E = (int)E; p.slabs = r.slabs;
+  if (r.mt == 4) return launch_rb8<4, RB8_FP8_GROUPED, 4>(p, 1, stream);
+  return r.waves == 4 ? launch_rb8<4, RB8_FP8_GROUPED, 8>(p, 1, stream) : launch_rb8<8, RB8_FP8_GROUPED, 8>(p, 1, stream);
 }
 
 }  // namespace ao

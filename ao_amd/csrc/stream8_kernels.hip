@@ -17,15 +17,12 @@
 #include <type_traits>
 
 namespace ao {
-// rb8_kernels.hip: LDS-staged weight-streaming form (full-line weight requests)
-int fp8_rowwise_grouped_rb(const uint8_t* a, const uint8_t* b, const float* scale_a, const float* scale_b, const int32_t* offs, uint16_t* out,
-                           int64_t M_total, int64_t N, int64_t K, int64_t E, hipStream_t stream);  // rb8_kernels.hip
-int mxfp8_grouped_rb(const uint8_t* a, const uint8_t* a_scale, const uint8_t* b, const uint8_t* b_scale, const int32_t* offs, uint16_t* out,
-                     int64_t M_total, int64_t N, int64_t K, int64_t E, int64_t rows_hint, hipStream_t stream);
-bool mxfp8_grouped_dyn_fits(int64_t M_total, int64_t N, int64_t K, int64_t E, bool have_offs, int products);
-int mxfp8_grouped_stream16(const void* a, const uint8_t* a_scale, const uint8_t* b, const uint8_t* b_scale, const uint8_t* b2, const uint8_t* b2_scale,
-                           const int32_t* offs, uint16_t* out, uint16_t* out2, int64_t M_total, int64_t N, int64_t K, int64_t E, int scaling_mode,
-                           hipStream_t stream);
+// rb8_kernels.hip: the LDS-staged weight-streaming and stream-K forms, launched in the shape grouped8_route picked
+int fp8_rowwise_grouped_rb(const Grouped8Route& r, const uint8_t* a, const uint8_t* b, const float* scale_a, const float* scale_b, const int32_t* offs,
+                           uint16_t* out, int64_t M_total, int64_t N, int64_t K, int64_t E, hipStream_t stream);
+int mxfp8_grouped_rb(const Grouped8Route& r, const void* a, const uint8_t* a_scale, const uint8_t* b, const uint8_t* b_scale, const uint8_t* b2,
+                     const uint8_t* b2_scale, const int32_t* offs, uint16_t* out, uint16_t* out2, int64_t M_total, int64_t N, int64_t K, int64_t E,
+                     hipStream_t stream);
 namespace {
 
 typedef int i32x8 __attribute__((ext_vector_type(8)));
@@ -358,15 +355,11 @@ int launch_mx_grouped_tn(const Stream8Args& p, hipStream_t stream) {
   return AO_OK;
 }
 
-// n-tiles per workgroup: as many as the accumulators allow (A is fetched once per workgroup) while
-// the grid still has >= 1024 workgroups -- only experts that received tokens do any work
-template <int MT>
-int launch_mx_grouped(const Stream8Args& p, hipStream_t stream) {
-  const int64_t ntiles = p.N >> 4;
-  auto enough = [&](int tn) { return ((ntiles + tn - 1) / tn) * p.E >= 1024; };
-  if (MT == 1 && enough(8)) return launch_mx_grouped_tn<1, 8>(p, stream);
-  if (enough(4)) return launch_mx_grouped_tn<MT, 4>(p, stream);
-  return launch_mx_grouped_tn<MT, 2>(p, stream);
+// mx_grouped_kernel<MT, TN> of the route
+int launch_mx_grouped(const Grouped8Route& r, const Stream8Args& p, hipStream_t stream) {
+  if (r.mt == 1) return r.tn == 8 ? launch_mx_grouped_tn<1, 8>(p, stream) : r.tn == 4 ? launch_mx_grouped_tn<1, 4>(p, stream) : launch_mx_grouped_tn<1, 2>(p, stream);
+  if (r.mt == 2) return r.tn == 4 ? launch_mx_grouped_tn<2, 4>(p, stream) : launch_mx_grouped_tn<2, 2>(p, stream);
+  return r.tn == 4 ? launch_mx_grouped_tn<4, 4>(p, stream) : launch_mx_grouped_tn<4, 2>(p, stream);
 }
 
 template <int KIND>
@@ -416,8 +409,8 @@ extern "C" int ao_fp8_grouped_mm(const uint8_t* a, const float* scale_a, const u
   AO_REQUIRE(M_total >= 0 && N > 0 && K > 0 && E > 0, "ao_fp8_grouped_mm: bad shape M_total=%lld N=%lld K=%lld E=%lld", (long long)M_total,
              (long long)N, (long long)K, (long long)E);
   AO_REQUIRE(K % 128 == 0 && N % 16 == 0, "ao_fp8_grouped_mm: K=%lld must be a multiple of 128 and N=%lld of 16", (long long)K, (long long)N);
-  const int64_t bm = (M_total <= 48 * E) ? 64 : 128;
-  AO_REQUIRE(M_total * K < (1ll << 32) && N * K < (1ll << 32) && E + (M_total + bm - 1) / bm <= 65535,
+  const Grouped8Route r = grouped8_route(Grouped8Entry::Fp8Rowwise, M_total, N, K, E, true, true, 0, gemm8_force());
+  AO_REQUIRE(r.kernel != Grouped8Kernel::Invalid,
              "ao_fp8_grouped_mm: tensor too large for one launch (M_total * K and N * K must stay below 4 Gi elements)");
   if (M_total == 0) return AO_OK;
   AO_REQUIRE_PTR(a);
@@ -426,7 +419,7 @@ extern "C" int ao_fp8_grouped_mm(const uint8_t* a, const float* scale_a, const u
   AO_REQUIRE_PTR(scale_b);
   AO_REQUIRE_PTR(offs);
   AO_REQUIRE_PTR(out);
-  return fp8_rowwise_grouped_rb(a, b, scale_a, scale_b, offs, out, M_total, N, K, E, (hipStream_t)stream);
+  return fp8_rowwise_grouped_rb(r, a, b, scale_a, scale_b, offs, out, M_total, N, K, E, (hipStream_t)stream);
 }
 
 extern "C" int ao_mxfp8_grouped_mm(const uint8_t* a, const uint8_t* a_scale, const uint8_t* b,
@@ -445,44 +438,46 @@ extern "C" int ao_mxfp8_grouped_mm(const uint8_t* a, const uint8_t* a_scale, con
   AO_REQUIRE_PTR(b_scale);
   AO_REQUIRE_PTR(out);
   AO_REQUIRE(offs != nullptr || E == 1, "ao_mxfp8_grouped_mm: offs is required when E > 1");
+  const bool aligned = (uintptr_t)a_scale % 16 == 0 && (uintptr_t)b_scale % 16 == 0;
+  const Grouped8Route r = grouped8_route(Grouped8Entry::Mx, M_total, N, K, E, offs != nullptr, aligned, 0, gemm8_force());
+  switch (r.kernel) {
+    case Grouped8Kernel::Rb8:
+    case Grouped8Kernel::MxStream:
+      return mxfp8_grouped_rb(r, a, a_scale, b, b_scale, nullptr, nullptr, offs, out, nullptr, M_total, N, K, E, (hipStream_t)stream);
+    default: break;
+  }
   Stream8Args p{};
   p.a = a; p.a_scale = a_scale; p.b = b; p.b_scale = b_scale; p.offs = offs; p.out = out;
   p.M_total = (int)M_total; p.N = (int)N; p.K = (int)K; p.E = (int)E;
-  // The LDS-staged weight-streaming kernel (rb8_kernels.hip) is the product path; its slab height follows the average group
-  // size.  Mixtral-8x7B expert shapes, 8 experts (w1, w2; us): 16 rows per expert -- A-stationary kernel below 97 / 120,
-  // LDS-staged 89 / 110; 128 rows per expert -- 381 / 474 (the A-stationary kernel re-streams the weights per 64-row pass) vs
-  // 211 / 172.  Variant 111 keeps the older kernels reachable for A/B runs.
-  // (it addresses activation rows with 32-bit byte offsets and puts experts x slabs on grid.y: tensors beyond either bound --
-  // M_total * K >= 4 GiB, or more than 65535 possible non-empty (expert, slab) pairs -- take the per-tile kernels below, which have neither limit)
-  const int64_t rb_bm = (M_total <= 48 * (offs != nullptr ? E : 1)) ? 64 : 128;
-  const bool rb_ok = M_total * K < (1ll << 32) && N * K < (1ll << 32) && (offs != nullptr ? E : 0) + (M_total + rb_bm - 1) / rb_bm <= 65535;
-  if (gemm8_force().mx != 2 && rb_ok) return mxfp8_grouped_rb(a, a_scale, b, b_scale, offs, out, M_total, N, K, E, M_total, (hipStream_t)stream);
-  if (offs != nullptr && K % 2048 == 0) {
-    // Group sizes live on the device.  Size the m-tiling for twice the AVERAGE group: a larger group
-    // takes another pass over its expert's weights (correct, slower), while sizing for the worst
-    // case (one group of M_total rows) would carry 4 m-tiles of A and accumulators everywhere.
-    const int64_t guess = (2 * M_total + E - 1) / E;
-    if (guess <= 16) return launch_mx_grouped<1>(p, (hipStream_t)stream);
-    if (guess <= 32) return launch_mx_grouped<2>(p, (hipStream_t)stream);
-    return launch_mx_grouped<4>(p, (hipStream_t)stream);
-  }
-  // other K: the per-tile kernel, m-tiling for the worst case (a group cannot exceed M_total rows)
-  return launch_stream8<S8_MX>(p, (int)M_total, (hipStream_t)stream);
+  if (r.kernel == Grouped8Kernel::MxGrouped) return launch_mx_grouped(r, p, (hipStream_t)stream);
+  return launch_stream8<S8_MX>(p, 16 * r.mt, (hipStream_t)stream);  // (the route's m-tiles)
 }
 
-// Host-only: whether ao_mxfp8_grouped_mm_dyn (products = 1) / the pair forms (products = 2) take the shape: decode-size groups
-// (M_total <= 48 per group, <= 64 groups), K % 512 == 0, N % 16 == 0.
+// Host-only: whether ao_mxfp8_grouped_mm_dyn / the pair forms take the shape with aligned operands (grouped8_route: decode-size groups,
+// M_total <= 48 per group, <= 64 groups, K % 512 == 0, N % 16 == 0).
 extern "C" int ao_mxfp8_grouped_mm_dyn_fits(int64_t M_total, int64_t N, int64_t K, int64_t E) {
-  return mxfp8_grouped_dyn_fits(M_total, N, K, E, true, 1) ? 1 : 0;
+  return grouped8_route(Grouped8Entry::MxDyn, M_total, N, K, E, true, true, 0, Gemm8Force{}).kernel != Grouped8Kernel::Invalid;
 }
 extern "C" int ao_mxfp8_grouped_mm_pair_fits(int64_t M_total, int64_t N, int64_t K, int64_t E) {
-  return mxfp8_grouped_dyn_fits(M_total, N, K, E, true, 2) ? 1 : 0;
+  return grouped8_route(Grouped8Entry::MxDynPair, M_total, N, K, E, true, true, 0, Gemm8Force{}).kernel != Grouped8Kernel::Invalid;
+}
+
+// Every field of the product route of one grouped entry point (host logic only; offs given, AO_MX_SCALE_RCEIL for the fused cast)
+extern "C" int ao_grouped8_route(int entry, int64_t M_total, int64_t N, int64_t K, int64_t E, int aligned, int32_t* out, int cap) {
+  AO_REQUIRE_PTR(out);
+  AO_REQUIRE(entry >= 0 && entry <= (int)Grouped8Entry::MxPair, "ao_grouped8_route: unknown entry %d", entry);
+  AO_REQUIRE(cap >= 10, "ao_grouped8_route: out holds %d fields, the route has 10", cap);
+  const Grouped8Route r = grouped8_route((Grouped8Entry)entry, M_total, N, K, E, true, aligned != 0, AO_MX_SCALE_RCEIL, Gemm8Force{});
+  const int32_t v[10] = {(int32_t)r.kernel, r.waves, r.mt, r.slim, r.qs, r.sw, r.cast, r.tn, r.slab_rows, r.slabs};
+  for (int i = 0; i < 10; ++i) out[i] = v[i];
+  return AO_OK;
 }
 
 namespace {
-int mx_stream16_entry(const char* fn, const void* a, const uint8_t* a_scale, const uint8_t* b, const uint8_t* b_scale, const uint8_t* b2,
-                      const uint8_t* b2_scale, const int32_t* offs, uint16_t* out, uint16_t* out2, int64_t M_total, int64_t N, int64_t K, int64_t E,
-                      int scaling_mode, bool pair, void* stream) {
+int mx_stream16_entry(const char* fn, Grouped8Entry entry, const void* a, const uint8_t* a_scale, const uint8_t* b, const uint8_t* b_scale,
+                      const uint8_t* b2, const uint8_t* b2_scale, const int32_t* offs, uint16_t* out, uint16_t* out2, int64_t M_total, int64_t N,
+                      int64_t K, int64_t E, int scaling_mode, void* stream) {
+  const bool pair = entry != Grouped8Entry::MxDyn;
   AO_REQUIRE(a_scale != nullptr || scaling_mode == 0 || scaling_mode == 1, "%s: scaling_mode must be AO_MX_SCALE_FLOOR or AO_MX_SCALE_RCEIL, got %d", fn, scaling_mode);
   AO_REQUIRE(M_total >= 0 && N > 0 && K > 0 && E > 0, "%s: bad shape M_total=%lld N=%lld K=%lld E=%lld", fn, (long long)M_total, (long long)N, (long long)K, (long long)E);
   if (M_total == 0) return AO_OK;
@@ -498,12 +493,13 @@ int mx_stream16_entry(const char* fn, const void* a, const uint8_t* a_scale, con
   }
   const bool aligned = ((uintptr_t)b_scale % 16 == 0) && ((uintptr_t)a % 16 == 0) && (a_scale == nullptr || (uintptr_t)a_scale % 16 == 0) &&
                        (!pair || (uintptr_t)b2_scale % 16 == 0);
-  AO_REQUIRE(mxfp8_grouped_dyn_fits(M_total, N, K, E, true, pair ? 2 : 1) && aligned,
+  const Grouped8Route r = grouped8_route(entry, M_total, N, K, E, true, aligned, scaling_mode, gemm8_force());
+  AO_REQUIRE(r.kernel != Grouped8Kernel::Invalid,
              "%s: shape M_total=%lld N=%lld K=%lld E=%lld is not a decode-size grouped product (ao_mxfp8_grouped_mm_dyn_fits / _pair_fits; scales and "
              "activations 16-byte aligned): cast with ao_mxfp8_quantize_rowwise and call ao_mxfp8_grouped_mm per weight", fn, (long long)M_total, (long long)N,
              (long long)K, (long long)E);
-  return mxfp8_grouped_stream16(a, a_scale, b, b_scale, pair ? b2 : nullptr, pair ? b2_scale : nullptr, offs, out, pair ? out2 : nullptr, M_total, N, K, E,
-                                scaling_mode, (hipStream_t)stream);
+  return mxfp8_grouped_rb(r, a, a_scale, b, b_scale, pair ? b2 : nullptr, pair ? b2_scale : nullptr, offs, out, pair ? out2 : nullptr, M_total, N, K, E,
+                          (hipStream_t)stream);
 }
 }  // namespace
 
@@ -511,19 +507,20 @@ int mx_stream16_entry(const char* fn, const void* a, const uint8_t* a_scale, con
 // grouped mm): a is the BF16 activation matrix, the cast happens in the kernel's A-fill with the stand-alone cast's arithmetic.
 extern "C" int ao_mxfp8_grouped_mm_dyn(const uint16_t* a, const uint8_t* b, const uint8_t* b_scale, const int32_t* offs, uint16_t* out,
                                        int64_t M_total, int64_t N, int64_t K, int64_t E, int scaling_mode, void* stream) {
-  return mx_stream16_entry(__func__, a, nullptr, b, b_scale, nullptr, nullptr, offs, out, nullptr, M_total, N, K, E, scaling_mode, false, stream);
+  return mx_stream16_entry(__func__, Grouped8Entry::MxDyn, a, nullptr, b, b_scale, nullptr, nullptr, offs, out, nullptr, M_total, N, K, E, scaling_mode, stream);
 }
 // Two expert-weight tensors of ONE shape against the same activations in one launch -- an MoE layer's w1 and w3 (x @ w1, x @ w3: the
-// reference calls _to_mxfp8_then_scaled_grouped_mm once per weight, casting x twice): out1 / out3 are bit-identical to two single calls.
+// reference calls _to_mxfp8_then_scaled_grouped_mm once per weight, casting x twice): out1 / out3 hold the same values as two single calls
+// (include/ao_mi355.h).
 extern "C" int ao_mxfp8_grouped_mm_dyn_pair(const uint16_t* a, const uint8_t* b1, const uint8_t* b1_scale, const uint8_t* b3, const uint8_t* b3_scale,
                                             const int32_t* offs, uint16_t* out1, uint16_t* out3, int64_t M_total, int64_t N, int64_t K, int64_t E,
                                             int scaling_mode, void* stream) {
-  return mx_stream16_entry(__func__, a, nullptr, b1, b1_scale, b3, b3_scale, offs, out1, out3, M_total, N, K, E, scaling_mode, true, stream);
+  return mx_stream16_entry(__func__, Grouped8Entry::MxDynPair, a, nullptr, b1, b1_scale, b3, b3_scale, offs, out1, out3, M_total, N, K, E, scaling_mode, stream);
 }
 // The same with activations the caller cast already (e4m3 codes + E8M0 scales: the output of the EP dispatch, or a cast shared with other consumers).
 extern "C" int ao_mxfp8_grouped_mm_pair(const uint8_t* a, const uint8_t* a_scale, const uint8_t* b1, const uint8_t* b1_scale, const uint8_t* b3,
                                         const uint8_t* b3_scale, const int32_t* offs, uint16_t* out1, uint16_t* out3, int64_t M_total, int64_t N,
                                         int64_t K, int64_t E, void* stream) {
   AO_REQUIRE_PTR(a_scale);
-  return mx_stream16_entry(__func__, a, a_scale, b1, b1_scale, b3, b3_scale, offs, out1, out3, M_total, N, K, E, 0, true, stream);
+  return mx_stream16_entry(__func__, Grouped8Entry::MxPair, a, a_scale, b1, b1_scale, b3, b3_scale, offs, out1, out3, M_total, N, K, E, 0, stream);
 }

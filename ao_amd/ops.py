@@ -5,6 +5,7 @@ borrowed) and error behaviour as the ops they replace; each docstring cites the
 reference call site.  Tensors must live on the GPU ("cuda" == HIP device on
 ROCm); there is no CPU fallback.
 """
+import ctypes
 from typing import Optional
 
 import torch
@@ -774,8 +775,18 @@ def _mx_mode(scaling_mode) -> int:
 
 
 def mxfp8_grouped_mm_dyn_fits(m, n, k, e) -> bool:
-    """Whether mxfp8_grouped_mm_dyn takes the shape (host logic: decode-size groups, K % 512 == 0)."""
+    """Whether mxfp8_grouped_mm_dyn takes the shape with aligned operands (host logic: decode-size groups, K % 512 == 0)."""
     return bool(_lib.lib().ao_mxfp8_grouped_mm_dyn_fits(int(m), int(n), int(k), int(e)))
+
+
+def mxfp8_grouped_mm_fuses(a, *b_scales) -> bool:
+    """Whether mxfp8_grouped_mm_dyn (one weight scale) / mxfp8_grouped_mm_pair (two) takes the BF16 activations `a` in ONE launch: the
+    route (ao_grouped8_route) for these tensors as they reach the C entry point, after .contiguous().  Else cast + mxfp8_grouped_mm."""
+    e, n, _ = b_scales[0].shape
+    aligned = all(t.contiguous().data_ptr() % 16 == 0 for t in (a, *b_scales))
+    out = (ctypes.c_int32 * 10)()
+    _lib.check(_lib.lib().ao_grouped8_route(2 if len(b_scales) == 1 else 3, a.shape[0], n, a.shape[1], e, int(aligned), out, 10))
+    return out[0] != 0
 
 
 def mxfp8_grouped_mm_dyn(a, b, b_scale, offs, scaling_mode="rceil"):

@@ -164,9 +164,8 @@ def _to_mxfp8_then_scaled_grouped_mm_pair(A: torch.Tensor, B1_t, B3_t, offs: tor
             ws.append(_cached_expert_weights(B_t, scale_calculation_mode) if cache_weights else MXFP8ExpertWeights.from_hp(B_t, scale_calculation_mode))
     w1, w3 = ws
     assert w1.data.shape == w3.data.shape and A.shape[-1] == w1.data.shape[-1], f"shapes {A.shape}, {w1.data.shape}, {w3.data.shape} are not compatible"
-    E, N, K = w1.data.shape
     offs = offs.to(torch.int32)
-    if FUSE_ACTIVATION_CAST and A.is_cuda and ops.mxfp8_grouped_mm_pair_fits(A.shape[0], N, K, E):
+    if FUSE_ACTIVATION_CAST and A.is_cuda and ops.mxfp8_grouped_mm_fuses(A, w1.scale, w3.scale):
         return ops.mxfp8_grouped_mm_pair(A, w1.data, w1.scale, w3.data, w3.scale, offs, scale_calculation_mode)
     return _cast_then_grouped_mm(A, w1, offs, scale_calculation_mode), _cast_then_grouped_mm(A, w3, offs, scale_calculation_mode)
 
@@ -174,9 +173,8 @@ def _to_mxfp8_then_scaled_grouped_mm_pair(A: torch.Tensor, B1_t, B3_t, offs: tor
 def _cast_then_grouped_mm(A, w, offs, scale_calculation_mode):
     """to_mx(A) then the grouped mm (mxfp8_grouped_mm.py:330-371).  Decode-size groups take ONE launch with the cast fused into the kernel's
     A-fill (round 6, SURVEY 8 f1: ops.mxfp8_grouped_mm_dyn, bit-identical); other shapes the cast kernel and the GEMM."""
-    E, N, K = w.data.shape
     offs = offs.to(torch.int32)
-    if FUSE_ACTIVATION_CAST and A.is_cuda and ops.mxfp8_grouped_mm_dyn_fits(A.shape[0], N, K, E):
+    if FUSE_ACTIVATION_CAST and A.is_cuda and ops.mxfp8_grouped_mm_fuses(A, w.scale):
         return ops.mxfp8_grouped_mm_dyn(A, w.data, w.scale, offs, scale_calculation_mode)
     a_q, a_s = ops.mxfp8_quantize(A.contiguous(), scale_calculation_mode)
     return ops.mxfp8_grouped_mm(a_q, a_s, w.data, w.scale, offs)

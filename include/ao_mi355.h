@@ -128,7 +128,7 @@ int ao_int4_overridden(void);
 /* Profiling only: 0 = product dispatch of the 8-bit GEMMs (LDS-DMA staged kernel when K % 128 == 0),
  * 1 = force the register-staged kernel, 2 / 4 / 8 = force the LDS-DMA kernel with 128x128, 256x128 (4 waves), 256x256 (8 waves) tiles,
  * 32 = the phase-interleaved 256x256 kernel, 33 = its 256x128 form (gemm8_p8h_kernel); 100 / 101 / 102 = the fp8 weight-streaming kernel never / always / always with 64-column tiles; 103 = its round-3 wave arrangement (1 x 8);
- * MXFP8 grouped mm: 110 always the LDS-staged kernels, 111 never (A-stationary / per-tile kernels); decode-size groups: 113 one workgroup
+ * MXFP8 grouped mm: 111 never the LDS-staged kernels (A-stationary / per-tile kernels), 110 the product route (kept so old scripts run); decode-size groups: 113 one workgroup
  * per tile instead of the stream-K kernel, 129 the stream-K kernel's per-step-scales form (what K % 512 != 0 takes) on every K
  * (ao_amd/csrc/rb8_kernels.hip); the decode kernel (dec8_kernel): 201 .. 208 its ring depth, 290 half-line loads, 291 / 292 never /
  * always 8-row tiles, 293 the round-4 bound of 64 KiB of activation codes (product since round 6: the CU's whole LDS), 299 never;
@@ -176,6 +176,12 @@ int ao_gemm8_plan_rows(int int8, int64_t M, int64_t N, int64_t K, int* tile_rows
  * mid8, stream8, rb8, p8h, p8, p8p, dma 128x128, dma 256x256, dma 256x128, dma 256x256 4 waves, gemm8_kernel, dyn8), tile rows,
  * tile columns, K parts, dec8 waves, depth, loop, half, rows8, mid8 m-tiles, mid8 K parts. */
 int ao_gemm8_route(int entry, int64_t M, int64_t N, int64_t K, int aligned, int32_t* out, int cap);
+/* Every field of the product route of one grouped entry point (host logic only; offs given; the fused cast as AO_MX_SCALE_RCEIL), for
+ * aligned (1) or unaligned (0) operands -- the scales, and the activations of the fused-cast and pair forms.  entry: 0 ao_fp8_grouped_mm,
+ * 1 ao_mxfp8_grouped_mm, 2 ao_mxfp8_grouped_mm_dyn, 3 ao_mxfp8_grouped_mm_dyn_pair, 4 ao_mxfp8_grouped_mm_pair.  out[cap >= 10] = kernel
+ * (0 = invalid: the entry refuses the shape, 1 rb8_kernel, 2 mx_stream_kernel, 3 mx_grouped_kernel, 4 stream8_kernel), waves, m-tiles,
+ * slim, scale fetches per 1 / 4 k steps, weight stages, cast (0 none, 1 floor, 2 rceil), n-tiles, slab rows, slabs per group. */
+int ao_grouped8_route(int entry, int64_t M_total, int64_t N, int64_t K, int64_t E, int aligned, int32_t* out, int cap);
 /* Which form of fp8_int4_mm_kernel ao_fp8_int4_linear launches for a shape: "<m-tiles x n-tiles>" of 16 x 16 per workgroup -- "<1x1>" up to
  * 16 rows, "<2x1>" / "<2x2>" beyond (round 5: the weights stream once per 32 rows, the staged activations serve 32 columns), or "invalid".
  * Host logic only.  DESIGN.md 4.9. */

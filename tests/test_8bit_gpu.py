@@ -656,6 +656,28 @@ def test_mxfp8_grouped_mm_fused_cast_refuses_other_shapes_and_the_mirror_falls_b
             assert torch.equal(got, want)
 
 
+def test_mxfp8_mirror_falls_back_for_unaligned_activations():
+    """The fused launches need 16-byte-aligned activations: a storage-offset view of A takes the cast + grouped mm (ops.mxfp8_grouped_mm_fuses
+    asks the route for the tensors as passed), with exactly the bits of the aligned input -- single product and pair."""
+    from ao_amd.prototype import mx as MXP
+
+    sizes, n, k = [16, 16, 16, 16], 256, 4096  # (the pair's shares cut the tiles where the single launches do: same bits)
+    m = sum(sizes)
+    a = _randn_bf16((m, k), 81 + n, 2.0).to(DEV)
+    a_off = torch.empty(m * k + 1, dtype=torch.bfloat16, device=DEV)[1:].view(m, k)  # 2 bytes past an aligned base
+    a_off.copy_(a)
+    assert a_off.is_contiguous() and a_off.data_ptr() % 16 != 0
+    w1 = _randn_bf16((len(sizes), n, k), 82 + k, 0.1).to(DEV).transpose(-2, -1)
+    w3 = _randn_bf16((len(sizes), n, k), 83 + k, 0.1).to(DEV).transpose(-2, -1)
+    offs = torch.tensor(np.cumsum(sizes), dtype=torch.int32, device=DEV)
+    w = MXP.MXFP8ExpertWeights.from_hp(w1)
+    assert ops.mxfp8_grouped_mm_fuses(a, w.scale) and not ops.mxfp8_grouped_mm_fuses(a_off, w.scale)
+    assert torch.equal(MXP._to_mxfp8_then_scaled_grouped_mm(a_off, w1, offs), MXP._to_mxfp8_then_scaled_grouped_mm(a, w1, offs))
+    want = MXP._to_mxfp8_then_scaled_grouped_mm_pair(a, w1, w3, offs)
+    got = MXP._to_mxfp8_then_scaled_grouped_mm_pair(a_off, w1, w3, offs)
+    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+
+
 @pytest.mark.parametrize("m,n,k,bias", [(128, 1024, 8192, False), (128, 7168, 8192, True), (200, 8192, 1024, True), (2048, 1024, 1024, False),
                                         (96, 48, 256, True), (65, 4096, 3584, False), (1000, 208, 384, True)])
 def test_fp8_weight_streaming_mid_m(m, n, k, bias):

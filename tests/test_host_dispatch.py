@@ -3,6 +3,8 @@
 DESIGN.md 4.4-4.5g describes which kernel serves which (M, N, K) band and why (each boundary was measured); these tests pin the table so
 that a change of a rule shows up as a diff here.  Shapes: Llama-3-70B TP = 8 shards and Llama-3-8B linears of BASELINE.json's configs.
 """
+import ctypes
+
 import pytest
 
 from ao_amd import _lib
@@ -182,6 +184,248 @@ def test_dyn_linear_fits_refuses_empty_weights():
     assert lib.ao_dyn_linear_fits(32, 0, 4096) == 0 and lib.ao_dyn_linear_fits(4, 0, 4096) == 0 and lib.ao_dyn_linear_fits(4, 4096, 4096) == 1
 
 
+# ao_grouped8_route's product route of every grouped entry point: both slab heights and both sides of each boundary (M_total = 48 E and
+# 48 E + 1; E = 64 / 65: the stream-K group table; K % 512 and K % 2048; N * K and the tickets).  "entry E M_total K:" then the route for
+# N = 208 / 4096 / 14336, each unaligned then aligned.  A route: kernel ("-" refused, rb8_kernel, mx_stream_kernel, mx_grouped_kernel,
+# stream8_kernel), then its nonzero fields -- w waves, m m-tiles, l slim, q scale fetches per 1 / 4 k steps, t weight stages, c cast
+# (1 floor, 2 rceil), n n-tiles, r slab rows, s slabs per group.
+GROUPED_TABLE = """
+fp8 1 48 384: rb8 w4 m4 q1 r64 s1 | rb8 w4 m4 q1 r64 s1 | rb8 w4 m4 q1 r64 s1 | rb8 w4 m4 q1 r64 s1 | rb8 w4 m4 q1 r64 s1 | rb8 w4 m4 q1 r64 s1
+fp8 1 48 512: rb8 w4 m4 q1 r64 s1 | rb8 w4 m4 q1 r64 s1 | rb8 w4 m4 q1 r64 s1 | rb8 w4 m4 q1 r64 s1 | rb8 w4 m4 q1 r64 s1 | rb8 w4 m4 q1 r64 s1
+fp8 1 48 2048: rb8 w4 m4 q1 r64 s1 | rb8 w4 m4 q1 r64 s1 | rb8 w4 m4 q1 r64 s1 | rb8 w4 m4 q1 r64 s1 | rb8 w4 m4 q1 r64 s1 | rb8 w4 m4 q1 r64 s1
+fp8 1 48 4096: rb8 w4 m4 q1 r64 s1 | rb8 w4 m4 q1 r64 s1 | rb8 w4 m4 q1 r64 s1 | rb8 w4 m4 q1 r64 s1 | rb8 w4 m4 q1 r64 s1 | rb8 w4 m4 q1 r64 s1
+fp8 1 48 14336: rb8 w4 m4 q1 r64 s1 | rb8 w4 m4 q1 r64 s1 | rb8 w4 m4 q1 r64 s1 | rb8 w4 m4 q1 r64 s1 | rb8 w4 m4 q1 r64 s1 | rb8 w4 m4 q1 r64 s1
+fp8 1 49 384: rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q1 r128 s1
+fp8 1 49 512: rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q1 r128 s1
+fp8 1 49 2048: rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q1 r128 s1
+fp8 1 49 4096: rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q1 r128 s1
+fp8 1 49 14336: rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q1 r128 s1
+fp8 8 384 384: rb8 w4 m4 q1 r64 s6 | rb8 w4 m4 q1 r64 s6 | rb8 w4 m4 q1 r64 s6 | rb8 w4 m4 q1 r64 s6 | rb8 w4 m4 q1 r64 s6 | rb8 w4 m4 q1 r64 s6
+fp8 8 384 512: rb8 w4 m4 q1 r64 s6 | rb8 w4 m4 q1 r64 s6 | rb8 w4 m4 q1 r64 s6 | rb8 w4 m4 q1 r64 s6 | rb8 w4 m4 q1 r64 s6 | rb8 w4 m4 q1 r64 s6
+fp8 8 384 2048: rb8 w4 m4 q1 r64 s6 | rb8 w4 m4 q1 r64 s6 | rb8 w4 m4 q1 r64 s6 | rb8 w4 m4 q1 r64 s6 | rb8 w4 m4 q1 r64 s6 | rb8 w4 m4 q1 r64 s6
+fp8 8 384 4096: rb8 w4 m4 q1 r64 s6 | rb8 w4 m4 q1 r64 s6 | rb8 w4 m4 q1 r64 s6 | rb8 w4 m4 q1 r64 s6 | rb8 w4 m4 q1 r64 s6 | rb8 w4 m4 q1 r64 s6
+fp8 8 384 14336: rb8 w4 m4 q1 r64 s6 | rb8 w4 m4 q1 r64 s6 | rb8 w4 m4 q1 r64 s6 | rb8 w4 m4 q1 r64 s6 | rb8 w4 m4 q1 r64 s6 | rb8 w4 m4 q1 r64 s6
+fp8 8 385 384: rb8 w4 m8 q1 r128 s4 | rb8 w4 m8 q1 r128 s4 | rb8 w8 m8 q1 r128 s4 | rb8 w8 m8 q1 r128 s4 | rb8 w8 m8 q1 r128 s4 | rb8 w8 m8 q1 r128 s4
+fp8 8 385 512: rb8 w4 m8 q1 r128 s4 | rb8 w4 m8 q1 r128 s4 | rb8 w8 m8 q1 r128 s4 | rb8 w8 m8 q1 r128 s4 | rb8 w8 m8 q1 r128 s4 | rb8 w8 m8 q1 r128 s4
+fp8 8 385 2048: rb8 w4 m8 q1 r128 s4 | rb8 w4 m8 q1 r128 s4 | rb8 w8 m8 q1 r128 s4 | rb8 w8 m8 q1 r128 s4 | rb8 w8 m8 q1 r128 s4 | rb8 w8 m8 q1 r128 s4
+fp8 8 385 4096: rb8 w4 m8 q1 r128 s4 | rb8 w4 m8 q1 r128 s4 | rb8 w8 m8 q1 r128 s4 | rb8 w8 m8 q1 r128 s4 | rb8 w8 m8 q1 r128 s4 | rb8 w8 m8 q1 r128 s4
+fp8 8 385 14336: rb8 w4 m8 q1 r128 s4 | rb8 w4 m8 q1 r128 s4 | rb8 w8 m8 q1 r128 s4 | rb8 w8 m8 q1 r128 s4 | rb8 w8 m8 q1 r128 s4 | rb8 w8 m8 q1 r128 s4
+fp8 64 3072 384: rb8 w4 m4 q1 r64 s48 | rb8 w4 m4 q1 r64 s48 | rb8 w4 m4 q1 r64 s48 | rb8 w4 m4 q1 r64 s48 | rb8 w4 m4 q1 r64 s48 | rb8 w4 m4 q1 r64 s48
+fp8 64 3072 512: rb8 w4 m4 q1 r64 s48 | rb8 w4 m4 q1 r64 s48 | rb8 w4 m4 q1 r64 s48 | rb8 w4 m4 q1 r64 s48 | rb8 w4 m4 q1 r64 s48 | rb8 w4 m4 q1 r64 s48
+fp8 64 3072 2048: rb8 w4 m4 q1 r64 s48 | rb8 w4 m4 q1 r64 s48 | rb8 w4 m4 q1 r64 s48 | rb8 w4 m4 q1 r64 s48 | rb8 w4 m4 q1 r64 s48 | rb8 w4 m4 q1 r64 s48
+fp8 64 3072 4096: rb8 w4 m4 q1 r64 s48 | rb8 w4 m4 q1 r64 s48 | rb8 w4 m4 q1 r64 s48 | rb8 w4 m4 q1 r64 s48 | rb8 w4 m4 q1 r64 s48 | rb8 w4 m4 q1 r64 s48
+fp8 64 3072 14336: rb8 w4 m4 q1 r64 s48 | rb8 w4 m4 q1 r64 s48 | rb8 w4 m4 q1 r64 s48 | rb8 w4 m4 q1 r64 s48 | rb8 w4 m4 q1 r64 s48 | rb8 w4 m4 q1 r64 s48
+fp8 64 3073 384: rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25
+fp8 64 3073 512: rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25
+fp8 64 3073 2048: rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25
+fp8 64 3073 4096: rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25
+fp8 64 3073 14336: rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25
+fp8 65 3120 384: rb8 w4 m4 q1 r64 s49 | rb8 w4 m4 q1 r64 s49 | rb8 w4 m4 q1 r64 s49 | rb8 w4 m4 q1 r64 s49 | rb8 w4 m4 q1 r64 s49 | rb8 w4 m4 q1 r64 s49
+fp8 65 3120 512: rb8 w4 m4 q1 r64 s49 | rb8 w4 m4 q1 r64 s49 | rb8 w4 m4 q1 r64 s49 | rb8 w4 m4 q1 r64 s49 | rb8 w4 m4 q1 r64 s49 | rb8 w4 m4 q1 r64 s49
+fp8 65 3120 2048: rb8 w4 m4 q1 r64 s49 | rb8 w4 m4 q1 r64 s49 | rb8 w4 m4 q1 r64 s49 | rb8 w4 m4 q1 r64 s49 | rb8 w4 m4 q1 r64 s49 | rb8 w4 m4 q1 r64 s49
+fp8 65 3120 4096: rb8 w4 m4 q1 r64 s49 | rb8 w4 m4 q1 r64 s49 | rb8 w4 m4 q1 r64 s49 | rb8 w4 m4 q1 r64 s49 | rb8 w4 m4 q1 r64 s49 | rb8 w4 m4 q1 r64 s49
+fp8 65 3120 14336: rb8 w4 m4 q1 r64 s49 | rb8 w4 m4 q1 r64 s49 | rb8 w4 m4 q1 r64 s49 | rb8 w4 m4 q1 r64 s49 | rb8 w4 m4 q1 r64 s49 | rb8 w4 m4 q1 r64 s49
+fp8 65 3121 384: rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25
+fp8 65 3121 512: rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25
+fp8 65 3121 2048: rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25
+fp8 65 3121 4096: rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25
+fp8 65 3121 14336: rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25
+mx 1 48 384: mxs w8 q1 t3 r64 s1 | mxs w8 q1 t3 r64 s1 | mxs w8 q1 t3 r64 s1 | mxs w8 q1 t3 r64 s1 | mxs w8 q1 t3 r64 s1 | mxs w8 q1 t3 r64 s1
+mx 1 48 512: mxs w8 q1 t3 r64 s1 | mxs w16 q4 t3 r64 s1 | mxs w8 q1 t3 r64 s1 | mxs w16 q4 t3 r64 s1 | mxs w8 q1 t3 r64 s1 | mxs w16 q4 t3 r64 s1
+mx 1 48 2048: mxs w8 q1 t3 r64 s1 | mxs w16 q4 t3 r64 s1 | mxs w8 q1 t3 r64 s1 | mxs w16 q4 t3 r64 s1 | mxs w8 q1 t3 r64 s1 | mxs w16 q4 t3 r64 s1
+mx 1 48 4096: mxs w8 q1 t3 r64 s1 | mxs w16 q4 t3 r64 s1 | mxs w8 q1 t3 r64 s1 | mxs w16 q4 t3 r64 s1 | mxs w8 q1 t3 r64 s1 | mxs w16 q4 t3 r64 s1
+mx 1 48 14336: mxs w8 q1 t3 r64 s1 | mxs w16 q4 t3 r64 s1 | mxs w8 q1 t3 r64 s1 | mxs w16 q4 t3 r64 s1 | mxs w8 q1 t3 r64 s1 | mxs w16 q4 t3 r64 s1
+mx 1 49 384: rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q1 r128 s1
+mx 1 49 512: rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q4 r128 s1 | rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q4 r128 s1 | rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q4 r128 s1
+mx 1 49 2048: rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q4 r128 s1 | rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q4 r128 s1 | rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q4 r128 s1
+mx 1 49 4096: rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q4 r128 s1 | rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q4 r128 s1 | rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q4 r128 s1
+mx 1 49 14336: rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q4 r128 s1 | rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q4 r128 s1 | rb8 w4 m8 q1 r128 s1 | rb8 w4 m8 q4 r128 s1
+mx 8 384 384: mxs w8 q1 t3 r64 s6 | mxs w8 q1 t3 r64 s6 | mxs w8 q1 t3 r64 s6 | mxs w8 q1 t3 r64 s6 | mxs w8 q1 t3 r64 s6 | mxs w8 q1 t3 r64 s6
+mx 8 384 512: mxs w8 q1 t3 r64 s6 | mxs w16 q4 t3 r64 s6 | mxs w8 q1 t3 r64 s6 | mxs w16 q4 t3 r64 s6 | mxs w8 q1 t3 r64 s6 | mxs w16 q4 t3 r64 s6
+mx 8 384 2048: mxs w8 q1 t3 r64 s6 | mxs w16 q4 t3 r64 s6 | mxs w8 q1 t3 r64 s6 | mxs w16 q4 t3 r64 s6 | mxs w8 q1 t3 r64 s6 | mxs w16 q4 t3 r64 s6
+mx 8 384 4096: mxs w8 q1 t3 r64 s6 | mxs w16 q4 t3 r64 s6 | mxs w8 q1 t3 r64 s6 | mxs w16 q4 t3 r64 s6 | mxs w8 q1 t3 r64 s6 | mxs w16 q4 t3 r64 s6
+mx 8 384 14336: mxs w8 q1 t3 r64 s6 | mxs w16 q4 t3 r64 s6 | mxs w8 q1 t3 r64 s6 | mxs w16 q4 t3 r64 s6 | mxs w8 q1 t3 r64 s6 | mxs w16 q4 t3 r64 s6
+mx 8 385 384: rb8 w4 m8 q1 r128 s4 | rb8 w4 m8 q1 r128 s4 | rb8 w8 m8 q1 r128 s4 | rb8 w8 m8 q1 r128 s4 | rb8 w8 m8 q1 r128 s4 | rb8 w8 m8 q1 r128 s4
+mx 8 385 512: rb8 w4 m8 q1 r128 s4 | rb8 w4 m8 q4 r128 s4 | rb8 w8 m8 q1 r128 s4 | rb8 w8 m8 q4 r128 s4 | rb8 w8 m8 q1 r128 s4 | rb8 w8 m8 q4 r128 s4
+mx 8 385 2048: rb8 w4 m8 q1 r128 s4 | rb8 w4 m8 q4 r128 s4 | rb8 w8 m8 q1 r128 s4 | rb8 w8 m8 q4 r128 s4 | rb8 w8 m8 q1 r128 s4 | rb8 w8 m8 q4 r128 s4
+mx 8 385 4096: rb8 w4 m8 q1 r128 s4 | rb8 w4 m8 q4 r128 s4 | rb8 w8 m8 q1 r128 s4 | rb8 w8 m8 q4 r128 s4 | rb8 w8 m8 q1 r128 s4 | rb8 w8 m8 q4 r128 s4
+mx 8 385 14336: rb8 w4 m8 q1 r128 s4 | rb8 w4 m8 q4 r128 s4 | rb8 w8 m8 q1 r128 s4 | rb8 w8 m8 q4 r128 s4 | rb8 w8 m8 q1 r128 s4 | rb8 w8 m8 q4 r128 s4
+mx 64 3072 384: mxs w8 q1 t3 r64 s48 | mxs w8 q1 t3 r64 s48 | mxs w8 q1 t3 r64 s48 | mxs w8 q1 t3 r64 s48 | rb8 w4 m4 l1 q1 r64 s48 | rb8 w4 m4 l1 q1 r64 s48
+mx 64 3072 512: mxs w8 q1 t3 r64 s48 | mxs w16 q4 t3 r64 s48 | mxs w8 q1 t3 r64 s48 | mxs w16 q4 t3 r64 s48 | rb8 w4 m4 l1 q1 r64 s48 | rb8 w4 m4 q4 r64 s48
+mx 64 3072 2048: mxs w8 q1 t3 r64 s48 | mxs w16 q4 t3 r64 s48 | mxs w8 q1 t3 r64 s48 | mxs w16 q4 t3 r64 s48 | rb8 w4 m4 l1 q1 r64 s48 | rb8 w4 m4 q4 r64 s48
+mx 64 3072 4096: mxs w8 q1 t3 r64 s48 | mxs w16 q4 t3 r64 s48 | mxs w8 q1 t3 r64 s48 | mxs w16 q4 t3 r64 s48 | rb8 w4 m4 l1 q1 r64 s48 | rb8 w4 m4 q4 r64 s48
+mx 64 3072 14336: mxs w8 q1 t3 r64 s48 | mxs w16 q4 t3 r64 s48 | mxs w8 q1 t3 r64 s48 | mxs w16 q4 t3 r64 s48 | rb8 w4 m4 l1 q1 r64 s48 | rb8 w4 m4 q4 r64 s48
+mx 64 3073 384: rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25
+mx 64 3073 512: rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q4 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q4 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q4 r128 s25
+mx 64 3073 2048: rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q4 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q4 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q4 r128 s25
+mx 64 3073 4096: rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q4 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q4 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q4 r128 s25
+mx 64 3073 14336: rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q4 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q4 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q4 r128 s25
+mx 65 3120 384: rb8 w4 m4 l1 q1 r64 s49 | rb8 w4 m4 l1 q1 r64 s49 | rb8 w4 m4 l1 q1 r64 s49 | rb8 w4 m4 l1 q1 r64 s49 | rb8 w4 m4 l1 q1 r64 s49 | rb8 w4 m4 l1 q1 r64 s49
+mx 65 3120 512: rb8 w4 m4 l1 q1 r64 s49 | rb8 w4 m4 q4 r64 s49 | rb8 w4 m4 l1 q1 r64 s49 | rb8 w4 m4 q4 r64 s49 | rb8 w4 m4 l1 q1 r64 s49 | rb8 w4 m4 q4 r64 s49
+mx 65 3120 2048: rb8 w4 m4 l1 q1 r64 s49 | rb8 w4 m4 q4 r64 s49 | rb8 w4 m4 l1 q1 r64 s49 | rb8 w4 m4 q4 r64 s49 | rb8 w4 m4 l1 q1 r64 s49 | rb8 w4 m4 q4 r64 s49
+mx 65 3120 4096: rb8 w4 m4 l1 q1 r64 s49 | rb8 w4 m4 q4 r64 s49 | rb8 w4 m4 l1 q1 r64 s49 | rb8 w4 m4 q4 r64 s49 | rb8 w4 m4 l1 q1 r64 s49 | rb8 w4 m4 q4 r64 s49
+mx 65 3120 14336: rb8 w4 m4 l1 q1 r64 s49 | rb8 w4 m4 q4 r64 s49 | rb8 w4 m4 l1 q1 r64 s49 | rb8 w4 m4 q4 r64 s49 | rb8 w4 m4 l1 q1 r64 s49 | rb8 w4 m4 q4 r64 s49
+mx 65 3121 384: rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q1 r128 s25
+mx 65 3121 512: rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q4 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q4 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q4 r128 s25
+mx 65 3121 2048: rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q4 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q4 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q4 r128 s25
+mx 65 3121 4096: rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q4 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q4 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q4 r128 s25
+mx 65 3121 14336: rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q4 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q4 r128 s25 | rb8 w8 m8 q1 r128 s25 | rb8 w8 m8 q4 r128 s25
+mx_dyn 1 48 384: - | - | - | - | - | -
+mx_dyn 1 48 512: - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2
+mx_dyn 1 48 2048: - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2
+mx_dyn 1 48 4096: - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2
+mx_dyn 1 48 14336: - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2
+mx_dyn 1 49 384: - | - | - | - | - | -
+mx_dyn 1 49 512: - | - | - | - | - | -
+mx_dyn 1 49 2048: - | - | - | - | - | -
+mx_dyn 1 49 4096: - | - | - | - | - | -
+mx_dyn 1 49 14336: - | - | - | - | - | -
+mx_dyn 8 384 384: - | - | - | - | - | -
+mx_dyn 8 384 512: - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2
+mx_dyn 8 384 2048: - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2
+mx_dyn 8 384 4096: - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2
+mx_dyn 8 384 14336: - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2
+mx_dyn 8 385 384: - | - | - | - | - | -
+mx_dyn 8 385 512: - | - | - | - | - | -
+mx_dyn 8 385 2048: - | - | - | - | - | -
+mx_dyn 8 385 4096: - | - | - | - | - | -
+mx_dyn 8 385 14336: - | - | - | - | - | -
+mx_dyn 64 3072 384: - | - | - | - | - | -
+mx_dyn 64 3072 512: - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2 | - | -
+mx_dyn 64 3072 2048: - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2 | - | -
+mx_dyn 64 3072 4096: - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2 | - | -
+mx_dyn 64 3072 14336: - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2 | - | -
+mx_dyn 64 3073 384: - | - | - | - | - | -
+mx_dyn 64 3073 512: - | - | - | - | - | -
+mx_dyn 64 3073 2048: - | - | - | - | - | -
+mx_dyn 64 3073 4096: - | - | - | - | - | -
+mx_dyn 64 3073 14336: - | - | - | - | - | -
+mx_dyn 65 3120 384: - | - | - | - | - | -
+mx_dyn 65 3120 512: - | - | - | - | - | -
+mx_dyn 65 3120 2048: - | - | - | - | - | -
+mx_dyn 65 3120 4096: - | - | - | - | - | -
+mx_dyn 65 3120 14336: - | - | - | - | - | -
+mx_dyn 65 3121 384: - | - | - | - | - | -
+mx_dyn 65 3121 512: - | - | - | - | - | -
+mx_dyn 65 3121 2048: - | - | - | - | - | -
+mx_dyn 65 3121 4096: - | - | - | - | - | -
+mx_dyn 65 3121 14336: - | - | - | - | - | -
+mx_dyn_pair 1 48 384: - | - | - | - | - | -
+mx_dyn_pair 1 48 512: - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2
+mx_dyn_pair 1 48 2048: - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2
+mx_dyn_pair 1 48 4096: - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2
+mx_dyn_pair 1 48 14336: - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2
+mx_dyn_pair 1 49 384: - | - | - | - | - | -
+mx_dyn_pair 1 49 512: - | - | - | - | - | -
+mx_dyn_pair 1 49 2048: - | - | - | - | - | -
+mx_dyn_pair 1 49 4096: - | - | - | - | - | -
+mx_dyn_pair 1 49 14336: - | - | - | - | - | -
+mx_dyn_pair 8 384 384: - | - | - | - | - | -
+mx_dyn_pair 8 384 512: - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2
+mx_dyn_pair 8 384 2048: - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2
+mx_dyn_pair 8 384 4096: - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2
+mx_dyn_pair 8 384 14336: - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2
+mx_dyn_pair 8 385 384: - | - | - | - | - | -
+mx_dyn_pair 8 385 512: - | - | - | - | - | -
+mx_dyn_pair 8 385 2048: - | - | - | - | - | -
+mx_dyn_pair 8 385 4096: - | - | - | - | - | -
+mx_dyn_pair 8 385 14336: - | - | - | - | - | -
+mx_dyn_pair 64 3072 384: - | - | - | - | - | -
+mx_dyn_pair 64 3072 512: - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2 | - | -
+mx_dyn_pair 64 3072 2048: - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2 | - | -
+mx_dyn_pair 64 3072 4096: - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2 | - | -
+mx_dyn_pair 64 3072 14336: - | mxs w16 q4 t3 c2 | - | mxs w16 q4 t3 c2 | - | -
+mx_dyn_pair 64 3073 384: - | - | - | - | - | -
+mx_dyn_pair 64 3073 512: - | - | - | - | - | -
+mx_dyn_pair 64 3073 2048: - | - | - | - | - | -
+mx_dyn_pair 64 3073 4096: - | - | - | - | - | -
+mx_dyn_pair 64 3073 14336: - | - | - | - | - | -
+mx_dyn_pair 65 3120 384: - | - | - | - | - | -
+mx_dyn_pair 65 3120 512: - | - | - | - | - | -
+mx_dyn_pair 65 3120 2048: - | - | - | - | - | -
+mx_dyn_pair 65 3120 4096: - | - | - | - | - | -
+mx_dyn_pair 65 3120 14336: - | - | - | - | - | -
+mx_dyn_pair 65 3121 384: - | - | - | - | - | -
+mx_dyn_pair 65 3121 512: - | - | - | - | - | -
+mx_dyn_pair 65 3121 2048: - | - | - | - | - | -
+mx_dyn_pair 65 3121 4096: - | - | - | - | - | -
+mx_dyn_pair 65 3121 14336: - | - | - | - | - | -
+mx_pair 1 48 384: - | - | - | - | - | -
+mx_pair 1 48 512: - | mxs w16 q4 t3 | - | mxs w16 q4 t3 | - | mxs w16 q4 t3
+mx_pair 1 48 2048: - | mxs w16 q4 t3 | - | mxs w16 q4 t3 | - | mxs w16 q4 t3
+mx_pair 1 48 4096: - | mxs w16 q4 t3 | - | mxs w16 q4 t3 | - | mxs w16 q4 t3
+mx_pair 1 48 14336: - | mxs w16 q4 t3 | - | mxs w16 q4 t3 | - | mxs w16 q4 t3
+mx_pair 1 49 384: - | - | - | - | - | -
+mx_pair 1 49 512: - | - | - | - | - | -
+mx_pair 1 49 2048: - | - | - | - | - | -
+mx_pair 1 49 4096: - | - | - | - | - | -
+mx_pair 1 49 14336: - | - | - | - | - | -
+mx_pair 8 384 384: - | - | - | - | - | -
+mx_pair 8 384 512: - | mxs w16 q4 t3 | - | mxs w16 q4 t3 | - | mxs w16 q4 t3
+mx_pair 8 384 2048: - | mxs w16 q4 t3 | - | mxs w16 q4 t3 | - | mxs w16 q4 t3
+mx_pair 8 384 4096: - | mxs w16 q4 t3 | - | mxs w16 q4 t3 | - | mxs w16 q4 t3
+mx_pair 8 384 14336: - | mxs w16 q4 t3 | - | mxs w16 q4 t3 | - | mxs w16 q4 t3
+mx_pair 8 385 384: - | - | - | - | - | -
+mx_pair 8 385 512: - | - | - | - | - | -
+mx_pair 8 385 2048: - | - | - | - | - | -
+mx_pair 8 385 4096: - | - | - | - | - | -
+mx_pair 8 385 14336: - | - | - | - | - | -
+mx_pair 64 3072 384: - | - | - | - | - | -
+mx_pair 64 3072 512: - | mxs w16 q4 t3 | - | mxs w16 q4 t3 | - | -
+mx_pair 64 3072 2048: - | mxs w16 q4 t3 | - | mxs w16 q4 t3 | - | -
+mx_pair 64 3072 4096: - | mxs w16 q4 t3 | - | mxs w16 q4 t3 | - | -
+mx_pair 64 3072 14336: - | mxs w16 q4 t3 | - | mxs w16 q4 t3 | - | -
+mx_pair 64 3073 384: - | - | - | - | - | -
+mx_pair 64 3073 512: - | - | - | - | - | -
+mx_pair 64 3073 2048: - | - | - | - | - | -
+mx_pair 64 3073 4096: - | - | - | - | - | -
+mx_pair 64 3073 14336: - | - | - | - | - | -
+mx_pair 65 3120 384: - | - | - | - | - | -
+mx_pair 65 3120 512: - | - | - | - | - | -
+mx_pair 65 3120 2048: - | - | - | - | - | -
+mx_pair 65 3120 4096: - | - | - | - | - | -
+mx_pair 65 3120 14336: - | - | - | - | - | -
+mx_pair 65 3121 384: - | - | - | - | - | -
+mx_pair 65 3121 512: - | - | - | - | - | -
+mx_pair 65 3121 2048: - | - | - | - | - | -
+mx_pair 65 3121 4096: - | - | - | - | - | -
+mx_pair 65 3121 14336: - | - | - | - | - | -
+"""
+GROUPED_ENTRIES = ("fp8", "mx", "mx_dyn", "mx_dyn_pair", "mx_pair")
+
+
+def _grouped_route(lib, entry, m, n, k, e, aligned):
+    out = (ctypes.c_int32 * 10)()
+    assert lib.ao_grouped8_route(GROUPED_ENTRIES.index(entry), m, n, k, e, int(aligned), out, 10) == 0
+    return " ".join([("-", "rb8", "mxs", "mxg", "s8")[out[0]]] + [f"{c}{v}" for c, v in zip("wmlqtcnrs", out[1:]) if v])
+
+
+def _grouped_table(lib):
+    got = []
+    for line in GROUPED_TABLE.strip().splitlines():
+        entry, e, m, k = line.split(":")[0].split()
+        got.append(f"{entry} {e} {m} {k}: " + " | ".join(_grouped_route(lib, entry, int(m), n, int(k), int(e), a) for n in (208, 4096, 14336)
+                                                          for a in (False, True)))
+    return got
+
+
+def test_grouped_dispatch_table():
+    assert _grouped_table(_lib.lib()) == GROUPED_TABLE.strip().splitlines()
+
+
+def test_grouped_fits_are_the_route():
+    """ao_mxfp8_grouped_mm_dyn_fits / _pair_fits answer "the route is not refused for aligned operands", through ops as bench.py calls them."""
+    from ao_amd import ops
+
+    lib = _lib.lib()
+    for e in (1, 8, 64, 65):
+        for m in (0, 1, 48 * e, 48 * e + 1):
+            for k in (384, 512, 2048, 4096, 14336, 1 << 20):
+                for n in (208, 4096, 14336):
+                    assert ops.mxfp8_grouped_mm_dyn_fits(m, n, k, e) == (_grouped_route(lib, "mx_dyn", m, n, k, e, True) != "-"), (m, n, k, e)
+                    assert ops.mxfp8_grouped_mm_pair_fits(m, n, k, e) == (_grouped_route(lib, "mx_dyn_pair", m, n, k, e, True) != "-"), (m, n, k, e)
+
+
 def test_queries_ignore_overrides():
     """The queries report the product route whatever override the calling thread has set: what the tables above pin is what launches
     without one (ao_gemm8_set_variant / ao_gemm8_set_tuning / ao_int4_set_tuning only steer the launches)."""
@@ -205,16 +449,16 @@ def test_queries_ignore_overrides():
         shapes = [(m, n, k) for m in (1, 5, 16, 17, 64, 65, 128, 129, 512, 2048) for n, k in PLAN_SHAPES.values()]
         r8 = {(e, a) + s: rc.route8(lib, e, *s, aligned=a) for e in rc.ENTRIES8 for a in (True, False) for s in shapes}
         r4 = {s + (g,): rc.route4(lib, *s, g) for s in shapes for g in (32, 128)}
-        return r8, r4
+        return r8, r4, _grouped_table(lib)
 
     routes_product = routes()
     try:
-        for variant in (1, 8, 32, 100, 101, 103, 113, 201, 293, 299, 300, 301, 312):
+        for variant in (1, 8, 32, 100, 101, 103, 110, 111, 113, 129, 201, 293, 299, 300, 301, 312):
             lib.ao_gemm8_set_variant(variant)
             check_8bit(("variant", variant))
             assert routes() == routes_product, ("variant", variant)
         lib.ao_gemm8_set_variant(0)
-        for key, value in ((1, 32), (3, 128), (6, 2), (7, 3)):
+        for key, value in ((1, 32), (3, 64), (3, 128), (6, 2), (7, 3)):
             lib.ao_gemm8_set_tuning(key, value)
             check_8bit(("tuning", key, value))
             assert routes() == routes_product, ("tuning", key, value)
