@@ -260,17 +260,16 @@ __global__ __launch_bounds__(1024) void dec8_kernel(Dec8Args p) {
     if (ROWS8 && col >= 8) continue;
     const int gn = ntile * TR + col;
     const float sx = DYN ? rs[row] : p.row_scale[row];
-    float v;
+    float c;
     if constexpr (INT8) {
       int isum = 0;
       for (int w = 0; w < nwaves; ++w) isum += __float_as_int(red[(size_t)w * 256 + idx]);
-      // t = bf16(f32(c) * sx[m]);  y = bf16(f32(t) * sw[n] (+ bias))   (int8_tensor.py:315-359)
-      v = mul_f32_rn(round_bf16((float)isum * sx), p.col_scale[gn]);
+      c = (float)isum;
     } else {
-      float sum = 0.f;
-      for (int w = 0; w < nwaves; ++w) sum += red[(size_t)w * 256 + idx];
-      v = sum * sx * p.col_scale[gn];
+      c = 0.f;
+      for (int w = 0; w < nwaves; ++w) c += red[(size_t)w * 256 + idx];
     }
+    float v = epilogue8<INT8>(c, sx, p.col_scale[gn]);
     if (p.bias != nullptr) v += bf16_lo_to_f32(p.bias[gn]);
     p.out[(size_t)row * p.N + gn] = f32_to_bf16_bits(v);
   }

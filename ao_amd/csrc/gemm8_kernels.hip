@@ -13,6 +13,7 @@
 // bf16 (or raw int32 for _int_mm).
 #include "common.h"
 #include "gemm8_route.h"
+#include "quant_math.h"
 
 namespace ao {
 // the launchers: each takes the launch shape gemm8_route picked (epi numbering of gemm8_p8 / gemm8_p8h = enum Epilogue)
@@ -185,15 +186,8 @@ __global__ __launch_bounds__(THREADS) void gemm8_kernel(Gemm8Args p) {
           reinterpret_cast<int32_t*>(p.out)[(size_t)gm * p.N + gn] = (int32_t)acc[i][j][r];
         } else if (EPI == EPI_FP8_RAW) {
           reinterpret_cast<float*>(p.out)[(size_t)gm * p.N + gn] = (float)acc[i][j][r];
-        } else if (EPI == EPI_INT8_SCALED) {
-          // t = bf16(f32(c) * sx[m]);  y = bf16(f32(t) * sw[n] (+ bias))   (int8_tensor.py:315-359)
-          const float t = round_bf16((float)acc[i][j][r] * p.row_scale[gm]);
-          float y = mul_f32_rn(t, cs);
-          if (p.bias != nullptr) y += bias;
-          reinterpret_cast<uint16_t*>(p.out)[(size_t)gm * p.N + gn] = f32_to_bf16_bits(y);
         } else {
-          float y = (float)acc[i][j][r] * p.row_scale[gm] * cs;
-          if (p.bias != nullptr) y += bias;
+          const float y = epilogue8<EPI == EPI_INT8_SCALED>((float)acc[i][j][r], p.row_scale[gm], cs, p.bias != nullptr, bias);
           reinterpret_cast<uint16_t*>(p.out)[(size_t)gm * p.N + gn] = f32_to_bf16_bits(y);
         }
       }
@@ -352,14 +346,8 @@ __global__ __launch_bounds__(128 * WN) void gemm8_dma_kernel(Gemm8Args p) {
           reinterpret_cast<int32_t*>(p.out)[(size_t)gm * p.N + gn] = (int32_t)acc[i][j][r];
         } else if (EPI == EPI_FP8_RAW) {
           reinterpret_cast<float*>(p.out)[(size_t)gm * p.N + gn] = (float)acc[i][j][r];
-        } else if (EPI == EPI_INT8_SCALED) {
-          const float t = round_bf16((float)acc[i][j][r] * p.row_scale[gm]);
-          float y = mul_f32_rn(t, cs);
-          if (p.bias != nullptr) y += bias;
-          reinterpret_cast<uint16_t*>(p.out)[(size_t)gm * p.N + gn] = f32_to_bf16_bits(y);
         } else {
-          float y = (float)acc[i][j][r] * p.row_scale[gm] * cs;
-          if (p.bias != nullptr) y += bias;
+          const float y = epilogue8<EPI == EPI_INT8_SCALED>((float)acc[i][j][r], p.row_scale[gm], cs, p.bias != nullptr, bias);
           reinterpret_cast<uint16_t*>(p.out)[(size_t)gm * p.N + gn] = f32_to_bf16_bits(y);
         }
       }

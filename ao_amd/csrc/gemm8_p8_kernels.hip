@@ -22,6 +22,7 @@
 #include "common.h"
 #include "gemm8_route.h"
 #include "lds_dma.h"
+#include "quant_math.h"
 #include "splitk.h"
 
 namespace ao {
@@ -251,14 +252,8 @@ __global__ __launch_bounds__(512) void gemm8_p8_kernel(P8Args p) {
       for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          float v;
-          if constexpr (EPI == P8_INT8_SCALED) {
-            // t = bf16(f32(c) * sx[m]);  y = bf16(f32(t) * sw[n] (+ bias))   (int8_tensor.py:315-359)
-            v = mul_f32_rn(round_bf16((float)__builtin_bit_cast(i32x4, acc[mt][nt])[r] * rs[r]), cs[nt]);
-          } else {
-            v = acc[mt][nt][r] * rs[r] * cs[nt];
-          }
-          if (p.bias != nullptr) v += bias[nt];
+          const float c = IS_INT ? (float)__builtin_bit_cast(i32x4, acc[mt][nt])[r] : acc[mt][nt][r];
+          const float v = epilogue8<IS_INT>(c, rs[r], cs[nt], p.bias != nullptr, bias[nt]);
           *reinterpret_cast<uint16_t*>(region + (mt * 16 + kq * 4 + r) * kEpiStride + (nt * 16 + nl) * 2) = f32_to_bf16_bits(v);
         }
     }
@@ -517,7 +512,7 @@ __global__ __launch_bounds__(512) void gemm8_p8p_kernel(P8Args p) {
           // column pair by column pair (two 16-column tiles = the 32 columns one store covers): 8 + 8 scale / bias registers live at a time
 #pragma unroll
           for (int pr = 0; pr < 2; ++pr) {
-            f32x4 cs[2], bs[2];
+            f32x4 cs[2], bs[2] = {};  // (bs goes to epilogue8 without BIAS too)
 #pragma unroll
             for (int n2 = 0; n2 < 2; ++n2) {
               const int nt = 2 * pr + n2;
@@ -537,13 +532,8 @@ __global__ __launch_bounds__(512) void gemm8_p8p_kernel(P8Args p) {
                 float v[4];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                  if constexpr (EPI == P8_INT8_SCALED) {
-                    // t = bf16(f32(c) * sx[m]);  y = bf16(f32(t) * sw[n] (+ bias))   (int8_tensor.py:315-359)
-                    v[r] = mul_f32_rn(round_bf16((float)__builtin_bit_cast(i32x4, acc[mt][nt])[r] * rs), cs[n2][r]);
-                  } else {
-                    v[r] = acc[mt][nt][r] * rs * cs[n2][r];
-                  }
-                  if constexpr (BIAS) v[r] += bs[n2][r];
+                  const float c = IS_INT ? (float)__builtin_bit_cast(i32x4, acc[mt][nt])[r] : acc[mt][nt][r];
+                  v[r] = epilogue8<IS_INT>(c, rs, cs[n2][r], BIAS, bs[n2][r]);
                 }
                 d[n2][0] = pack_bf16x2(v[0], v[1]);
                 d[n2][1] = pack_bf16x2(v[2], v[3]);
@@ -824,13 +814,8 @@ __global__ __launch_bounds__(512) void gemm8_p8h_kernel(P8Args p) {
       for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          float v;
-          if constexpr (EPI == P8_INT8_SCALED) {
-            v = mul_f32_rn(round_bf16((float)__builtin_bit_cast(i32x4, acc[mt][nt])[r] * rs[r]), cs[nt]);  // (int8_tensor.py:315-359)
-          } else {
-            v = acc[mt][nt][r] * rs[r] * cs[nt];
-          }
-          if (p.bias != nullptr) v += bias[nt];
+          const float c = IS_INT ? (float)__builtin_bit_cast(i32x4, acc[mt][nt])[r] : acc[mt][nt][r];
+          const float v = epilogue8<IS_INT>(c, rs[r], cs[nt], p.bias != nullptr, bias[nt]);
           *reinterpret_cast<uint16_t*>(region + (mt * 16 + kq * 4 + r) * kEpiStride + (nt * 16 + nl) * 2) = f32_to_bf16_bits(v);
         }
     }

@@ -26,7 +26,7 @@
 #include "splitk.h"
 
 namespace ao {
-void fp8_rowwise_rb_set_trace(unsigned long long* p);  // fp8_rb_kernels.hip
+void fp8_rowwise_rb_set_trace(unsigned long long* p);  // rb8_kernels.hip
 namespace {
 
 // ---------------------------------------------------------------------------

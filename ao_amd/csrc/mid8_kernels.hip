@@ -183,14 +183,8 @@ __global__ __launch_bounds__(512, 4) void mid8_kernel(Mid8Args p) {
     for (int r = 0; r < 4; ++r) {
       const int m = m0 + mt * 16 + kq * 4 + r;
       if (m < p.M) {
-        float v;
-        if constexpr (INT8) {
-          // t = bf16(f32(c) * sx[m]);  y = bf16(f32(t) * sw[n] (+ bias))   (int8_tensor.py:315-359)
-          v = mul_f32_rn(round_bf16((float)__builtin_bit_cast(i32x4, acc[mt])[r] * sa[mt * 4 + r]), sb);
-        } else {
-          v = acc[mt][r] * sa[mt * 4 + r] * sb;
-        }
-        if (p.bias != nullptr) v += bias;
+        const float c = INT8 ? (float)__builtin_bit_cast(i32x4, acc[mt])[r] : acc[mt][r];
+        const float v = epilogue8<INT8>(c, sa[mt * 4 + r], sb, p.bias != nullptr, bias);
         y[(size_t)m * p.N + n] = f32_to_bf16_bits(v);
       }
     }

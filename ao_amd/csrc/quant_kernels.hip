@@ -146,8 +146,6 @@ __global__ __launch_bounds__(kThreads) void rowwise_amax_kernel(const uint16_t* 
 }
 
 // ---- scale epilogues over all-reduced accumulators (row-parallel TP linears): the arithmetic of the fused GEMM epilogues ----
-// int8: t = bf16(f32(c) * sx[m]);  y = bf16(f32(t) * sw[n] (+ bias))        (int8_tensor.py:315-359)
-// fp8 : y = bf16(c * sa[m] * sb[n] (+ bias))                                (float8/inference.py:104-123)
 template <bool INT8>
 __global__ __launch_bounds__(kThreads) void scale_epilogue_kernel(const void* __restrict__ acc, const float* __restrict__ row_scale,
                                                                   const float* __restrict__ col_scale, const uint16_t* __restrict__ bias,
@@ -155,13 +153,8 @@ __global__ __launch_bounds__(kThreads) void scale_epilogue_kernel(const void* __
   const int64_t row = blockIdx.y;
   const float rs = row_scale[row];
   for (int64_t n = (int64_t)blockIdx.x * kThreads + threadIdx.x; n < N; n += (int64_t)gridDim.x * kThreads) {
-    float v;
-    if (INT8) {
-      const float t = round_bf16((float)reinterpret_cast<const int32_t*>(acc)[row * N + n] * rs);
-      v = mul_f32_rn(t, col_scale[n]);
-    } else {
-      v = reinterpret_cast<const float*>(acc)[row * N + n] * rs * col_scale[n];
-    }
+    const float c = INT8 ? (float)reinterpret_cast<const int32_t*>(acc)[row * N + n] : reinterpret_cast<const float*>(acc)[row * N + n];
+    float v = epilogue8<INT8>(c, rs, col_scale[n]);
     if (bias != nullptr) v += bf16_lo_to_f32(bias[n]);
     y[row * N + n] = f32_to_bf16_bits(v);
   }
@@ -200,18 +193,7 @@ __global__ __launch_bounds__(kThreads) void int8_quant_rowwise_asym_kernel(const
     zero_point[row] = (int8_t)(int)zp;
   }
   u32x2* qr = reinterpret_cast<u32x2*>(q + row * K);
-  for (int64_t i = threadIdx.x; i < nvec; i += kThreads) {
-    const u32x4 v = xr[i];
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-    uint32_t out[2] = {0u, 0u};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float a = fminf(fmaxf(rintf(bf16_lo_to_f32(w[j]) * inv) + zp, -128.f), 127.f);
-      const float b = fminf(fmaxf(rintf(bf16_hi_to_f32(w[j]) * inv) + zp, -128.f), 127.f);
-      out[j >> 1] |= (((uint32_t)(int)a & 0xffu) | (((uint32_t)(int)b & 0xffu) << 8)) << ((j & 1) * 16);
-    }
-    qr[i] = u32x2{out[0], out[1]};
-  }
+  for (int64_t i = threadIdx.x; i < nvec; i += kThreads) qr[i] = int8_quant8_zp(xr[i], inv, zp);
 }
 
 // static activation quantization (Int8StaticActivationInt8WeightConfig: Int8Tensor.from_hp(x, scale=..., zero_point=...), int8_tensor.py:
@@ -224,18 +206,7 @@ __global__ __launch_bounds__(kThreads) void int8_quant_static_kernel(const uint1
   const float inv = 1.0f / scale[row * stride];
   const float zp = zero_point != nullptr ? (float)zero_point[row * stride] : 0.0f;
   u32x2* qr = reinterpret_cast<u32x2*>(q + row * K);
-  for (int64_t i = threadIdx.x; i < (K >> 3); i += kThreads) {
-    const u32x4 v = xr[i];
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-    uint32_t out[2] = {0u, 0u};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float a = fminf(fmaxf(rintf(bf16_lo_to_f32(w[j]) * inv) + zp, -128.f), 127.f);
-      const float b = fminf(fmaxf(rintf(bf16_hi_to_f32(w[j]) * inv) + zp, -128.f), 127.f);
-      out[j >> 1] |= (((uint32_t)(int)a & 0xffu) | (((uint32_t)(int)b & 0xffu) << 8)) << ((j & 1) * 16);
-    }
-    qr[i] = u32x2{out[0], out[1]};
-  }
+  for (int64_t i = threadIdx.x; i < (K >> 3); i += kThreads) qr[i] = int8_quant8_zp(xr[i], inv, zp);
 }
 
 // row sums of an int8 [N][K] weight (the zero-point correction's rowsum(W), int8_tensor.py:326): one wave per row
@@ -269,7 +240,7 @@ __global__ __launch_bounds__(kThreads) void scale_epilogue_asym_kernel(const int
   for (int64_t n = (int64_t)blockIdx.x * kThreads + threadIdx.x; n < N; n += (int64_t)gridDim.x * kThreads) {
     float t = round_bf16((float)acc[row * N + n] * xs);
     t = round_bf16(t - round_bf16(zs * (float)w_sums[n]));
-    float v = mul_f32_rn(t, w_scale[n]);
+    float v = int8_out(t, w_scale[n]);
     if (bias != nullptr) v += bf16_lo_to_f32(bias[n]);
     y[row * N + n] = f32_to_bf16_bits(v);
   }

@@ -1,9 +1,10 @@
-// Per-row activation quantisation arithmetic shared by the stand-alone casts (quant_kernels.hip) and the fused
-// dynamic-quant linears (dyn8_kernels.hip): the reference's op sequence, element for element.
+// The 8-bit arithmetic at both ends of a linear, the reference's op sequence element for element.  Per-row activation quantisation,
+// shared by the stand-alone casts (quant_kernels.hip) and the fused dynamic-quant linears (dyn8_kernels.hip):
 //   int8 : scale = f32(max(bf16(amax / 127.5), bf16(f32_eps)));  q = clamp(rint(x * (1/scale)), -128, 127)
 //          (int8_tensor.py:191-230, quant_primitives.py:1534-1583, :463-485)
 //   fp8  : scale = f32(bf16(amax / 448));  q = e4m3_rne(clamp(f32(x) / scale, -448, 448))
 //          (float8_tensor.py:167-253, quant_primitives.py:2192-2212, 2271-2287)
+// and the rowwise output epilogue, shared by every int8 / fp8 GEMM kernel and the stand-alone scale epilogues (epilogue8 below).
 #pragma once
 #include "common.h"
 
@@ -34,6 +35,20 @@ __device__ __forceinline__ u32x2 int8_quant8(const u32x4& v, float inv) {
   for (int j = 0; j < 4; ++j) {
     const float a = fminf(fmaxf(rintf(bf16_lo_to_f32(w[j]) * inv), -128.f), 127.f);
     const float b = fminf(fmaxf(rintf(bf16_hi_to_f32(w[j]) * inv), -128.f), 127.f);
+    const uint32_t pa = (uint32_t)(int)a & 0xffu, pb = (uint32_t)(int)b & 0xffu;
+    out[j >> 1] |= (pa | (pb << 8)) << ((j & 1) * 16);
+  }
+  return u32x2{out[0], out[1]};
+}
+// the zero-point form (asymmetric / static activations, quant_primitives.py:463-485): q = clamp(rint(x * inv) + zp, -128, 127).  Not
+// int8_quant8 with zp = 0: + 0.0f turns a -0.0 into +0.0, so the symmetric form would gain an add.
+__device__ __forceinline__ u32x2 int8_quant8_zp(const u32x4& v, float inv, float zp) {
+  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+  uint32_t out[2] = {0u, 0u};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float a = fminf(fmaxf(rintf(bf16_lo_to_f32(w[j]) * inv) + zp, -128.f), 127.f);
+    const float b = fminf(fmaxf(rintf(bf16_hi_to_f32(w[j]) * inv) + zp, -128.f), 127.f);
     const uint32_t pa = (uint32_t)(int)a & 0xffu, pb = (uint32_t)(int)b & 0xffu;
     out[j >> 1] |= (pa | (pb << 8)) << ((j & 1) * 16);
   }
@@ -75,6 +90,26 @@ __device__ __forceinline__ u32x2 fp8_quant8(const u32x4& v, float s) {
   return u32x2{cvt4_e4m3(f[0], f[1], f[2], f[3]), cvt4_e4m3(f[4], f[5], f[6], f[7])};
 }
 
+// ---- rowwise output epilogue: the fp32 value the caller rounds to bf16 at its store -----------------------------------------------
+//   int8 : t = bf16(f32(c) * sx[m]);  y = bf16(f32(t) * sw[n] (+ bias))   (int8_tensor.py:315-359)
+//   fp8  : y = bf16(c * sa[m] * sb[n] (+ bias))                           (float8/inference.py:104-123)
+// The int8 product t * sw and the bias add are two tensor ops: mul_f32_rn keeps them from contracting into one v_fma_f32.
+// c is the accumulator already converted to fp32 by the caller ((float) of the int32 sum for int8): converting it in here
+// reorders the K loop of gemm8_dma_kernel<0, ...>.  Kernels that load the bias at the store, only where there is one, call without
+// it and add it after: the same fp32 add, and passing it in changed their branch layout.
+// int8's last step alone: the asymmetric epilogue (quant_kernels.hip) applies its zero-point correction to t first.
+__device__ __forceinline__ float int8_out(float t, float sc, bool has_bias = false, float bias = 0.f) {
+  float v = mul_f32_rn(t, sc);
+  if (has_bias) v += bias;
+  return v;
+}
+template <bool INT8>
+__device__ __forceinline__ float epilogue8(float c, float sr, float sc, bool has_bias = false, float bias = 0.f) {
+  if (INT8) return int8_out(round_bf16(c * sr), sc, has_bias, bias);
+  float v = c * sr * sc;
+  if (has_bias) v += bias;
+  return v;
+}
 
 // ---- MXFP8 (to_mx, prototype/mx_formats/mx_tensor.py:228-409) --------------------------------------------------------------------
 // E8M0 scale exponent of one 32-block from its amax (:255-330; RCEIL :111-129, :161-225) and the reciprocal 2^(127 - e) built from the

@@ -522,10 +522,7 @@ __global__ __launch_bounds__(64 * WAVES) void rb8_kernel(Rb8Args p) {
         const f32x4 sa4 = *reinterpret_cast<const f32x4*>(sa_lds + mt * 16 + kq * 4);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          float v;
-          if constexpr (INT8) v = mul_f32_rn(round_bf16((float)__builtin_bit_cast(i32x4, c)[r] * sa4[r]), sbv);
-          else v = c[r] * sa4[r] * sbv;
-          if (p.bias != nullptr) v += bv;
+          const float v = epilogue8<INT8>(INT8 ? (float)__builtin_bit_cast(i32x4, c)[r] : c[r], sa4[r], sbv, p.bias != nullptr, bv);
           *reinterpret_cast<uint16_t*>(smem + (mt * 16 + kq * 4 + r) * RS + (ntl * 16 + nl) * 2) = f32_to_bf16_bits(v);
         }
       };
@@ -577,10 +574,8 @@ __global__ __launch_bounds__(64 * WAVES) void rb8_kernel(Rb8Args p) {
         for (int r = 0; r < 4; ++r) {
           const int m = m0 + (4 * wm + i) * 16 + kq * 4 + r;
           if (m < m_end && nj[j] >= 0) {
-            float v;
-            if constexpr (INT8) v = mul_f32_rn(round_bf16((float)__builtin_bit_cast(i32x4, acc[2 * i + j])[r] * sa[i * 4 + r]), sbj[j]);
-            else v = acc[2 * i + j][r] * sa[i * 4 + r] * sbj[j];
-            if (p.bias != nullptr) v += biasj[j];
+            const float c = INT8 ? (float)__builtin_bit_cast(i32x4, acc[2 * i + j])[r] : acc[2 * i + j][r];
+            const float v = epilogue8<INT8>(c, sa[i * 4 + r], sbj[j], p.bias != nullptr, biasj[j]);
             y[(size_t)m * p.N + nj[j]] = f32_to_bf16_bits(v);
           }
         }
@@ -611,14 +606,8 @@ __global__ __launch_bounds__(64 * WAVES) void rb8_kernel(Rb8Args p) {
       for (int r = 0; r < 4; ++r) {
         const int m = m0 + mt * 16 + kq * 4 + r;
         if (m < m_end) {  // (= p.M for the ungrouped kinds)
-          float v;
-          if constexpr (INT8) {
-            // t = bf16(f32(c) * sx[m]);  y = bf16(f32(t) * sw[n] (+ bias))   (int8_tensor.py:315-359)
-            v = mul_f32_rn(round_bf16((float)__builtin_bit_cast(i32x4, acc[mt])[r] * sa[mt * 4 + r]), sb);
-          } else {
-            v = acc[mt][r] * sa[mt * 4 + r] * sb;
-          }
-          if (p.bias != nullptr) v += bias;
+          const float c = INT8 ? (float)__builtin_bit_cast(i32x4, acc[mt])[r] : acc[mt][r];
+          const float v = epilogue8<INT8>(c, sa[mt * 4 + r], sb, p.bias != nullptr, bias);
           y[(size_t)m * p.N + n] = f32_to_bf16_bits(v);
         }
       }

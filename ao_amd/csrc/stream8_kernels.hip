@@ -13,6 +13,7 @@
 // and no separate dequant pass exist.  One barrier for the split-K reduction.
 #include "common.h"
 #include "gemm8_route.h"
+#include "quant_math.h"
 
 #include <type_traits>
 
@@ -138,12 +139,8 @@ __global__ __launch_bounds__(512) void stream8_kernel(Stream8Args p) {
           else sum += red[((size_t)w * MT + t) * 256 + rc];
         }
         const int gm = row_begin + m_base + row, gn = ntile * 16 + col;
-        if constexpr (INT8) {
-          // t = bf16(f32(c) * sx[m]);  y = bf16(f32(t) * sw[n] (+ bias))   (int8_tensor.py:315-359)
-          sum = mul_f32_rn(round_bf16((float)isum * p.row_scale[gm]), p.col_scale[gn]);
-          if (p.bias != nullptr) sum += bf16_lo_to_f32(p.bias[gn]);
-        } else if (!MX) {
-          sum = sum * p.row_scale[gm] * p.col_scale[gn];
+        if constexpr (!MX) {
+          sum = epilogue8<INT8>(INT8 ? (float)isum : sum, p.row_scale[gm], p.col_scale[gn]);
           if (p.bias != nullptr) sum += bf16_lo_to_f32(p.bias[gn]);
         }
         p.out[(size_t)gm * p.N + gn] = f32_to_bf16_bits(sum);

@@ -146,3 +146,11 @@ def test_fp8_gemm_covers_the_mfma_to_epilogue_hazard_explicitly(tmp_path):
         assert not any(t.startswith("v_mfma") for t in ins[pairs[-1]:]) or len(pairs) >= 1
         checked += 1
     assert checked >= 6, "fp8 instantiations of gemm8_p8_kernel / gemm8_p8p_kernel / gemm8_p8h_kernel not found"
+
+
+def test_kernel_sources_leave_the_8bit_epilogue_to_quant_math():
+    """The int8 / fp8 rowwise output epilogue has one definition (quant_math.h: epilogue8, int8_out).  mul_f32_rn is its int8 product;
+    a kernel source that calls it is restating the formula instead of calling the helper."""
+    csrc = os.path.join(ROOT, "ao_amd", "csrc")
+    offenders = sorted(f for f in os.listdir(csrc) if f.endswith(".hip") and "mul_f32_rn(" in open(os.path.join(csrc, f)).read())
+    assert not offenders, f"call epilogue8 / int8_out (quant_math.h) instead of mul_f32_rn in: {', '.join(offenders)}"
