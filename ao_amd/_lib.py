@@ -108,6 +108,13 @@ _SIGNATURES = {
     "ao_moe_permute_indices": [_P, _P, _P, _P, _P, _I64, _I64, _I64, _INT, _P],
     "ao_moe_gather_rows": [_P, _P, _P, _I64, _I64, _I64, _P],
     "ao_moe_scatter_rows": [_P, _P, _P, _I64, _I64, _I64, _P],
+    "ao_mxfp4_quantize_rowwise": [_P, _P, _P, _I64, _I64, _INT, _P],
+    "ao_mx_linear": [_INT, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _P],
+    "ao_mx_dynamic_linear_fits": [_INT, _I64, _I64, _I64],
+    "ao_mx_dynamic_linear": [_INT, _P, _P, _P, _P, _P, _I64, _I64, _I64, _INT, _P],
+    "ao_mx_linear_route": [_INT, _I64, _I64, _I64, _P, _INT],
+    "ao_mx_linear_kernel_name": [_INT, _I64, _I64, _I64],
+    "ao_mx_linear_set_form": [_INT],
 }
 
 
@@ -149,6 +156,8 @@ def lib():
         l.ao_int4_mm_kernel_name.restype = ctypes.c_char_p
         if hasattr(l, "ao_gemm8_kernel_name"):
             l.ao_gemm8_kernel_name.restype = ctypes.c_char_p
+        if hasattr(l, "ao_mx_linear_kernel_name"):
+            l.ao_mx_linear_kernel_name.restype = ctypes.c_char_p
         if hasattr(l, "ao_fp8_int4_kernel_name"):
             l.ao_fp8_int4_kernel_name.restype = ctypes.c_char_p
         l.ao_moe_padded_rows.restype = _I64

@@ -137,6 +137,19 @@ __device__ __forceinline__ float mx_reciprocal(uint32_t e) {
   if (re == 255u) rbits = 0x7F800001u;  // NaN
   return bits_to_f32(rbits);
 }
+// 8 bf16 -> 8 e4m3 codes of a block whose E8M0 exponent is e (to_mx's data_hp * reciprocal, then the saturating cast)
+template <int MODE>
+__device__ __forceinline__ u32x2 mx_encode8(const u32x4& v, uint32_t e) {
+  const float r = mx_reciprocal(e);
+  float f[8] = {bf16_lo_to_f32(v.x), bf16_hi_to_f32(v.x), bf16_lo_to_f32(v.y), bf16_hi_to_f32(v.y),
+                bf16_lo_to_f32(v.z), bf16_hi_to_f32(v.z), bf16_lo_to_f32(v.w), bf16_hi_to_f32(v.w)};
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    f[j] *= r;
+    if (MODE == 0) f[j] = clamp448(f[j]);  // eager saturation (torch < 2.13), :361-373
+  }
+  return u32x2{cvt4_e4m3(f[0], f[1], f[2], f[3]), cvt4_e4m3(f[4], f[5], f[6], f[7])};
+}
 // The 1 x 32 cast of one block by FOUR ADJACENT LANES (lane & 3 = the block's quarter: 8 bf16 each): block amax across the four lanes,
 // the E8M0 exponent (returned in e, the same in all four), 8 e4m3 codes of this lane's quarter.  One definition for the stand-alone cast
 // (quant_kernels.hip: mxfp8_quant_kernel) and the cast fused into the grouped GEMM's A-fill (rb8_kernels.hip): the same bits by construction.
@@ -150,15 +163,70 @@ __device__ __forceinline__ u32x2 mx_cast8(const u32x4& v, uint32_t& e) {
   nanbits |= __shfl_xor(nanbits, 1);
   nanbits |= __shfl_xor(nanbits, 2);
   e = mx_block_exponent<MODE>(m, (nanbits == 0u) && (m < INFINITY));
-  const float r = mx_reciprocal(e);
-  float f[8] = {bf16_lo_to_f32(v.x), bf16_hi_to_f32(v.x), bf16_lo_to_f32(v.y), bf16_hi_to_f32(v.y),
-                bf16_lo_to_f32(v.z), bf16_hi_to_f32(v.z), bf16_lo_to_f32(v.w), bf16_hi_to_f32(v.w)};
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    f[j] *= r;
-    if (MODE == 0) f[j] = clamp448(f[j]);  // eager saturation (torch < 2.13), :361-373
+  return mx_encode8<MODE>(v, e);
+}
+
+// ---- MXFP4 (to_mx(x, float4_e2m1fn_x2, 32, mode)) ---------------------------------------------------------------------------------
+// Block exponent (F4_E2M1_MAX_POW2 = 2; RCEIL: descale = amax * f32(1/6) rounded up to a power of two, :161-225) and the e2m1 code of one
+// scaled value by the integer steps of custom_fp_utils._f32_to_floatx_unpacked(x, 2, 1): |x| >= 6 saturates to 7; |x| < 1 is rounded
+// by the fp32 add x + 2^22 (RNE at a step of 0.5); otherwise the mantissa is rounded to one bit by the magic-adder form (a NaN takes
+// this branch, like the reference's).  The sign bit is kept, -0 included.
+template <int MODE>
+__device__ __forceinline__ uint32_t mxfp4_block_exponent(float m, bool finite) {
+  uint32_t e;
+  if (MODE == 1) {
+    const uint32_t bits = f32_to_bits(m * (1.0f / 6.0f));
+    const uint32_t be = (bits >> 23) & 0xffu, mant = bits & 0x7fffffu;
+    const bool up = (be == 0) ? (mant > 0x400000u) : (mant != 0);
+    e = be + (up ? 1u : 0u);
+  } else {
+    const int ex = (int)((f32_to_bits(m) >> 23) & 0xffu) - 127 - 2;
+    e = (uint32_t)(min(max(ex, -127), 128) + 127);
   }
-  return u32x2{cvt4_e4m3(f[0], f[1], f[2], f[3]), cvt4_e4m3(f[4], f[5], f[6], f[7])};
+  return finite ? e : 255u;
+}
+__device__ __forceinline__ uint32_t e2m1_code(uint32_t bits) {
+#pragma clang fp contract(off)
+  const uint32_t sign = (bits >> 28) & 8u;
+  const uint32_t a = bits & 0x7fffffffu;
+  const float x = bits_to_f32(a);
+  uint32_t c;
+  if (x >= 6.0f) {
+    c = 7u;
+  } else if (x < 1.0f) {
+    c = (f32_to_bits(x + 0x1p22f) - (149u << 23)) & 0xffu;
+  } else {
+    c = ((a + (0xC1000000u + 0x1FFFFFu) + ((a >> 22) & 1u)) >> 22) & 0xffu;  // ((1 - 127) << 23) + magic adder, mod 2^32
+  }
+  return c | sign;
+}
+// The 1 x 32 cast of one block held by ONE lane (32 bf16 in four 16-byte pieces): E8M0 exponent in e, 32 codes packed two per byte (element
+// 2i in the low nibble, pack_uint4).  One definition for the stand-alone cast and the cast fused into the MX linear's A operand.
+// Non-finite blocks (e = 255) multiply by the NaN reciprocal 0x7F800001: the reference's products are that NaN quieted (0x7FC00001) for
+// every element, NaN elements included, so all 32 codes are e2m1_code(0x7FC00001) = 3 -- taken here from the bits, not from whichever
+// NaN operand the hardware multiply would propagate.
+template <int MODE>
+__device__ __forceinline__ u32x4 mx_cast4(const u32x4 (&v)[4], uint32_t& e) {
+  bool has_nan = false;
+  float m = 0.f;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) m = fmaxf(m, amax8(v[i], has_nan));
+  e = mxfp4_block_exponent<MODE>(m, !has_nan && m < INFINITY);
+  const float r = mx_reciprocal(e);
+  uint32_t out[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const uint32_t w[4] = {v[i].x, v[i].y, v[i].z, v[i].w};
+    uint32_t o = 0u;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const uint32_t xb = (j & 1) ? (w[j >> 1] & 0xffff0000u) : (w[j >> 1] << 16);
+      const uint32_t pb = (e == 255u) ? 0x7FC00001u : f32_to_bits(bits_to_f32(xb) * r);
+      o |= e2m1_code(pb) << (4 * j);
+    }
+    out[i] = o;
+  }
+  return u32x4{out[0], out[1], out[2], out[3]};
 }
 
 }  // namespace ao

@@ -1135,3 +1135,130 @@ def fp8_dynamic_linear(x, wq, w_scale, bias=None):
     """Float8Tensor F.linear with dynamic per-row e4m3 activation quantisation in ONE launch (float8_tensor.py:167-253,
     float8/inference.py:104-123): same bits as fp8_quantize_rowwise + fp8_scaled_mm at these sizes."""
     return _dynamic_linear("fp8_dynamic_linear", _lib.lib().ao_fp8_dynamic_linear, x, wq, w_scale, bias, torch.float8_e4m3fn)
+
+
+# ---- MX dense linears (MXFP4 / MXFP8; include/ao_mi355.h "MX dense linears", DESIGN.md 4.10) ------------------------------------
+MX_FMT_E4M3 = 0  # the scaled MFMA's format codes
+MX_FMT_E2M1 = 4
+_MX_FMTS = {MX_FMT_E4M3, MX_FMT_E2M1}
+
+
+def mx_fmt(elem_dtype) -> int:
+    """torch element dtype of an MXTensor -> the C ABI's fmt code (float8_e4m3fn 0, float4_e2m1fn_x2 4)."""
+    if elem_dtype == torch.float8_e4m3fn:
+        return MX_FMT_E4M3
+    if elem_dtype == torch.float4_e2m1fn_x2:
+        return MX_FMT_E2M1
+    raise NotImplementedError(f"MX linears on MI355X take float8_e4m3fn or float4_e2m1fn_x2 elements, got {elem_dtype}")
+
+
+def mxfp4_quantize(x: torch.Tensor, scaling_mode: str = "rceil"):
+    """Rowwise (1x32) MXFP4 cast: to_mx(x, float4_e2m1fn_x2, 32, mode) (prototype/mx_formats/mx_tensor.py:228-409).
+    x bf16 [..., C] -> (data uint8 [..., C/2] packed e2m1 codes, element 2i in the low nibble; scale float8_e8m0fnu [..., C/32])."""
+    dev = _require_gpu("mxfp4_quantize", x)
+    if x.dtype != torch.bfloat16:
+        raise RuntimeError(f"mxfp4_quantize: expected bfloat16, got {x.dtype}")
+    if not x.is_contiguous():
+        raise RuntimeError("mxfp4_quantize: expected a contiguous tensor")
+    mode = _mx_mode(scaling_mode)
+    c = x.shape[-1]
+    if c % 32 != 0 or c == 0:
+        raise RuntimeError(f"mxfp4_quantize: the last dimension of shape {tuple(x.shape)} must be divisible by 32")
+    r = x.numel() // c
+    q = torch.empty((*x.shape[:-1], c // 2), dtype=torch.uint8, device=dev)
+    s = torch.empty((*x.shape[:-1], c // 32), dtype=torch.uint8, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_mxfp4_quantize_rowwise(_ptr(x), _ptr(q), _ptr(s), r, c, mode, _stream()))
+    return q, s.view(torch.float8_e8m0fnu)
+
+
+def mx_quantize(x: torch.Tensor, fmt: int, scaling_mode="rceil"):
+    """(codes, scales) of the 1 x 32 cast of bf16 x for fmt (MX_FMT_E4M3 / MX_FMT_E2M1)."""
+    if fmt == MX_FMT_E2M1:
+        return mxfp4_quantize(x, scaling_mode)
+    return mxfp8_quantize(x, scaling_mode)
+
+
+MX_LINEAR_KERNELS = {0: "invalid", 1: "mx_linear_stream_kernel", 2: "mx_linear_tile_kernel"}
+
+
+def mx_linear_route(fmt: int, m: int, n: int, k: int) -> dict:
+    """The route mx_mm / mx_linear launch for a shape (host logic only, ao_mx_linear_route)."""
+    out = (ctypes.c_int32 * 7)()
+    _lib.check(_lib.lib().ao_mx_linear_route(int(fmt), int(m), int(n), int(k), out, 7))
+    kernel, waves, mt, tile_m, tile_n, gx, gy = list(out)
+    return {"kernel": MX_LINEAR_KERNELS.get(kernel, "invalid"), "waves": waves, "m_tiles": mt, "tile_m": tile_m, "tile_n": tile_n,
+            "grid": (gx, gy)}
+
+
+def mx_linear_kernel_name(fmt: int, m: int, n: int, k: int) -> str:
+    return _lib.lib().ao_mx_linear_kernel_name(int(fmt), int(m), int(n), int(k)).decode()
+
+
+def mx_linear_set_form(form: int) -> None:
+    """Measurement only: 0 the product route, 1 the streaming form, 2 the tiled form (calling thread)."""
+    _lib.check(_lib.lib().ao_mx_linear_set_form(int(form)))
+
+
+def _mx_operands(name, fmt, b, b_scale, bias, k_from_a):
+    if fmt not in _MX_FMTS:
+        raise RuntimeError(f"{name}: fmt must be {MX_FMT_E4M3} (e4m3) or {MX_FMT_E2M1} (e2m1), got {fmt}")
+    b = b.view(torch.uint8) if b.dtype in (torch.float8_e4m3fn, torch.float4_e2m1fn_x2) else b
+    if b.dtype != torch.uint8 or b.dim() != 2:
+        raise RuntimeError(f"{name}: the weight codes must be a 2-D uint8 / e4m3 tensor [N, K or K/2], got {b.dtype} {tuple(b.shape)}")
+    n = b.shape[0]
+    k = b.shape[1] * (2 if fmt == MX_FMT_E2M1 else 1)
+    if k != k_from_a:
+        raise RuntimeError(f"{name}: K of the activation ({k_from_a}) and of the weight ({k}) differ")
+    b_scale = b_scale.view(torch.uint8)
+    if tuple(b_scale.shape) != (n, k // 32):
+        raise RuntimeError(f"{name}: the weight scales must be [N, K/32] = {(n, k // 32)}, got {tuple(b_scale.shape)}")
+    if bias is not None and (bias.dtype != torch.bfloat16 or bias.numel() != n):
+        raise RuntimeError(f"{name}: bias must be bfloat16 [N], got {bias.dtype} {tuple(bias.shape)}")
+    return b.contiguous(), b_scale.contiguous(), (bias.contiguous() if bias is not None else None), n, k
+
+
+def mx_mm(a, a_scale, b, b_scale, bias=None, fmt: int = MX_FMT_E2M1):
+    """The MX GEMM on codes: a [M, K or K/2], a_scale [M, K/32], b [N, K or K/2] (the weight as stored), b_scale [N, K/32], bias bf16 [N]
+    -> bf16 [M, N] = bf16(sum_k dq(a) dq(b) + bias), fp32 accumulation (ao_mx_linear)."""
+    dev = _require_gpu("mx_mm", a, a_scale, b, b_scale, bias)
+    a = a.view(torch.uint8) if a.dtype in (torch.float8_e4m3fn, torch.float4_e2m1fn_x2) else a
+    if a.dtype != torch.uint8 or a.dim() != 2:
+        raise RuntimeError(f"mx_mm: the activation codes must be a 2-D uint8 / e4m3 tensor, got {a.dtype} {tuple(a.shape)}")
+    m = a.shape[0]
+    ka = a.shape[1] * (2 if fmt == MX_FMT_E2M1 else 1)
+    b, b_scale, bias, n, k = _mx_operands("mx_mm", fmt, b, b_scale, bias, ka)
+    a_scale = a_scale.view(torch.uint8).contiguous()
+    if tuple(a_scale.shape) != (m, k // 32):
+        raise RuntimeError(f"mx_mm: the activation scales must be [M, K/32] = {(m, k // 32)}, got {tuple(a_scale.shape)}")
+    out = torch.empty((m, n), dtype=torch.bfloat16, device=dev)
+    if m == 0:
+        return out
+    with _on(dev):
+        _lib.check(_lib.lib().ao_mx_linear(int(fmt), _ptr(a.contiguous()), _ptr(a_scale), _ptr(b), _ptr(b_scale), _ptr(bias), _ptr(out),
+                                           m, n, k, _stream()))
+    return out
+
+
+def mx_linear(x, b, b_scale, bias=None, fmt: int = MX_FMT_E2M1, scaling_mode="rceil", fuse: bool = True):
+    """MXTensor's linear with a dynamic activation: to_mx(x, elem, 32, scaling_mode) then the MX GEMM.  x bf16 [M, K]; b / b_scale the
+    weight as stored.  Shapes the streaming form takes run the cast inside the GEMM (ao_mx_dynamic_linear, bit-identical to the two
+    launches); others cast first.  fuse=False: always the two launches."""
+    dev = _require_gpu("mx_linear", x, b, b_scale, bias)
+    if x.dtype != torch.bfloat16 or x.dim() != 2:
+        raise RuntimeError(f"mx_linear: x must be a 2-D bfloat16 tensor, got {x.dtype} {tuple(x.shape)}")
+    x = x.contiguous()
+    m, kx = x.shape
+    b, b_scale, bias, n, k = _mx_operands("mx_linear", fmt, b, b_scale, bias, kx)
+    mode = _mx_mode(scaling_mode)
+    if fuse and _lib.lib().ao_mx_dynamic_linear_fits(int(fmt), m, n, k):
+        out = torch.empty((m, n), dtype=torch.bfloat16, device=dev)
+        if m > 0:
+            with _on(dev):
+                _lib.check(_lib.lib().ao_mx_dynamic_linear(int(fmt), _ptr(x), _ptr(b), _ptr(b_scale), _ptr(bias), _ptr(out), m, n, k, mode,
+                                                           _stream()))
+        return out
+    if m == 0:
+        return torch.empty((0, n), dtype=torch.bfloat16, device=dev)
+    aq, a_s = mx_quantize(x, fmt, scaling_mode)
+    return mx_mm(aq, a_s, b, b_scale, bias, fmt)

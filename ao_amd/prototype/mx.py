@@ -1,4 +1,5 @@
-"""MXFP8 (block 32, e4m3 elements, E8M0 scales): cast and MoE grouped GEMM forward, MI355X-native.
+"""MXFP8 (block 32, e4m3 elements, E8M0 scales): cast and MoE grouped GEMM forward, MI355X-native.  The MXFP4 cast and the dense MX
+linears (MXTensor, MXDynamicActivationMXWeightConfig) live in mx_tensor.py and are re-exported here.
 
 Host-side mirror of
   * torchao/prototype/mx_formats/mx_tensor.py:228-409  to_mx(x, float8_e4m3fn, 32, mode)
@@ -17,7 +18,7 @@ import torch
 
 from .. import ops
 
-__all__ = ["ScaleCalculationMode", "to_mx", "mx_dequantize", "_to_mxfp8_then_scaled_grouped_mm", "pad_token_groups", "unpad_token_groups",
+__all__ = ["ScaleCalculationMode", "to_mx", "MXTensor", "QuantizeTensorToMXKwargs", "MXDynamicActivationMXWeightConfig", "mx_dequantize", "_to_mxfp8_then_scaled_grouped_mm", "pad_token_groups", "unpad_token_groups",
            "to_blocked", "mx_block_rearrange_2d_M_groups_cuda", "compute_blocked_scale_offsets_for_M_groups"]
 
 BLOCK = 32
@@ -33,9 +34,10 @@ class ScaleCalculationMode(Enum):
 
 def to_mx(data_hp: torch.Tensor, elem_dtype: torch.dtype = torch.float8_e4m3fn, block_size: int = BLOCK,
           scaling_mode: ScaleCalculationMode = ScaleCalculationMode.FLOOR):
-    """(scale_e8m0 [..., C/32], data_e4m3 [..., C]) -- the reference's return order (mx_tensor.py:409)."""
-    if elem_dtype != torch.float8_e4m3fn:
-        raise NotImplementedError(f"to_mx on MI355X implements float8_e4m3fn elements only, got {elem_dtype}")
+    """(scale_e8m0 [..., C/32], data) -- the reference's return order (mx_tensor.py:409); data e4m3 [..., C], or for
+    float4_e2m1fn_x2 uint8 [..., C/2] packed codes (pack_uint4: element 2i in the low nibble)."""
+    if elem_dtype not in (torch.float8_e4m3fn, torch.float4_e2m1fn_x2):
+        raise NotImplementedError(f"to_mx on MI355X implements float8_e4m3fn and float4_e2m1fn_x2 elements, got {elem_dtype}")
     if block_size != BLOCK:
         raise NotImplementedError(f"to_mx on MI355X implements block_size 32 only, got {block_size}")
     assert data_hp.dtype in (torch.bfloat16,), f"{data_hp.dtype} is not supported yet (bfloat16 only on MI355X)"
@@ -43,7 +45,7 @@ def to_mx(data_hp: torch.Tensor, elem_dtype: torch.dtype = torch.float8_e4m3fn, 
         f"the last dimension of shape {data_hp.shape} must be divisible by block_size {block_size}"
     )
     assert data_hp.is_contiguous(), "unsupported"
-    q, s = ops.mxfp8_quantize(data_hp, scaling_mode)
+    q, s = ops.mx_quantize(data_hp, ops.mx_fmt(elem_dtype), scaling_mode)
     return s, q
 
 
@@ -212,3 +214,6 @@ def compute_blocked_scale_offsets_for_M_groups(offsets: torch.Tensor):
     group_sizes = torch.diff(offsets, prepend=zero)
     starts = torch.cumsum((group_sizes + 127) // 128 * 128, dim=0)
     return group_sizes, torch.cat([zero, starts.to(offsets.dtype)])
+
+
+from .mx_tensor import MXDynamicActivationMXWeightConfig, MXTensor, QuantizeTensorToMXKwargs  # noqa: E402,F401  (config_from_dict resolves names here)

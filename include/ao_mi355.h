@@ -560,6 +560,39 @@ int ao_int8_scale_epilogue(const int32_t* acc, const float* x_scale, const float
 int ao_fp8_scale_epilogue(const float* acc, const float* scale_a, const float* scale_b,
                           const uint16_t* bias, uint16_t* y, int64_t M, int64_t N, void* stream);
 
+/* ---- MX dense linears: MXFP4 (e2m1) / MXFP8 (e4m3) elements, E8M0 scales over 1 x 32 blocks along K -------------------------
+ * The GEMM of torchao's MXTensor linear (torchao/prototype/mx_formats/mx_tensor.py:760-880, _addmm_mx_dispatch; the weight of
+ * MXDynamicActivationMXWeightConfig, inference_workflow.py:80-171).  fmt is the scaled MFMA's format code: AO_MX_FMT_E4M3 (0) or
+ * AO_MX_FMT_E2M1 (4).  Codes are row-major and K-contiguous: e4m3 [rows][K], e2m1 packed [rows][K/2] (element 2i in the low nibble,
+ * pack_uint4, kernels.py:155-160); scales E8M0 bytes [rows][K/32] in plain row-major layout (to_mx(..., is_swizzled_scales=False); no
+ * 128 x 4 swizzle).  Shapes: M >= 0, N >= 1, K a positive multiple of 32, each operand < 2 GiB; ragged edges are masked.  DESIGN.md 4.10. */
+#define AO_MX_FMT_E4M3 0
+#define AO_MX_FMT_E2M1 4
+/* Replaces to_mx(x, torch.float4_e2m1fn_x2, 32, mode) (mx_tensor.py:228-409; RCEIL :161-224; e2m1 rounding
+ * custom_fp_utils._f32_to_floatx_unpacked): x bf16 [R][C], C % 32 == 0 -> q [R][C/2] packed codes, scale_e8m0 [R][C/32];
+ * byte for byte the reference's.  x and q 16-byte aligned. */
+int ao_mxfp4_quantize_rowwise(const uint16_t* x, uint8_t* q, uint8_t* scale_e8m0, int64_t R, int64_t C, int scaling_mode, void* stream);
+/* out bf16 [M][N] = bf16( sum_k dq(a)[m][k] dq(b)[n][k] + bias[n] ), dq = element * 2^(scale - 127), fp32 accumulation, one rounding
+ * (the numerics of the reference's EMULATED path, mx_tensor.py:828-841, without its bf16 rounding of the dequantised operands).  a / a_scale:
+ * the activation's codes; b / b_scale: the weight as stored [N][...]; bias bf16 [N] or NULL.  a and b 16-byte aligned. */
+int ao_mx_linear(int fmt, const uint8_t* a, const uint8_t* a_scale, const uint8_t* b, const uint8_t* b_scale, const uint16_t* bias,
+                 uint16_t* out, int64_t M, int64_t N, int64_t K, void* stream);
+/* to_mx(x, elem, 32, scaling_mode) followed by ao_mx_linear in ONE launch, for the shapes the streaming form takes
+ * (ao_mx_dynamic_linear_fits, host logic: 1 when the route is mx_linear_stream_kernel); bit-identical to the cast + ao_mx_linear.
+ * Other shapes return AO_ERR_INVALID_ARGUMENT.  x bf16 [M][K], 16-byte aligned. */
+int ao_mx_dynamic_linear_fits(int fmt, int64_t M, int64_t N, int64_t K);
+int ao_mx_dynamic_linear(int fmt, const uint16_t* x, const uint8_t* b, const uint8_t* b_scale, const uint16_t* bias, uint16_t* out,
+                         int64_t M, int64_t N, int64_t K, int scaling_mode, void* stream);
+/* The route both MX linear entries launch (host logic only): out[cap >= 7] = kernel (0 = invalid shape, 1 mx_linear_stream_kernel,
+ * 2 mx_linear_tile_kernel), waves per workgroup, m-tiles of 16 per workgroup, tile rows, tile columns, grid x, grid y.  The streaming
+ * form up to 64 rows (e4m3) / 32 rows (e2m1), the 128 x 128 LDS-tiled form beyond. */
+int ao_mx_linear_route(int fmt, int64_t M, int64_t N, int64_t K, int32_t* out, int cap);
+/* "mx_linear_stream_kernel", "mx_linear_tile_kernel" or "invalid": the kernel of that route. */
+const char* ao_mx_linear_kernel_name(int fmt, int64_t M, int64_t N, int64_t K);
+/* Measurement only: force the form of the calling thread's MX linears (0 the product route, 1 streaming, 2 tiled); the route queries
+ * report the forced form. */
+int ao_mx_linear_set_form(int form);
+
 #ifdef __cplusplus
 }
 #endif
