@@ -314,7 +314,7 @@ int ao_mxfp8_quantize_colwise_3d(const uint16_t* x, uint8_t* q_t, uint8_t* scale
  *   out[offs[e-1]:offs[e]] = dq(a_rows) @ dq(b[e])^T,  dq = fp8 * 2^(scale-127)
  *   a e4m3 [M_total][K]; a_scale e8m0 [M_total][K/32];
  *   b e4m3 [E][N][K] (each expert row-major [N][K]); b_scale e8m0 [E][N][K/32];
- *   offs int32 [E] cumulative group ends; out bf16 [M_total][N].
+ *   offs int32 [E] cumulative group ends; out bf16 [M_total][N].  Rows past offs[E-1] are not written.
  * Scale layout is plain row-major (CDNA4 scaled-MFMA takes scales in VGPRs; the
  * cuBLAS 128x4 "blocked" swizzle is not read by any GEMM here; ao_mx_block_rearrange_2d_m_groups writes it as a data format). */
 int ao_mxfp8_grouped_mm(const uint8_t* a, const uint8_t* a_scale,

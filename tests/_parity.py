@@ -5,11 +5,13 @@ the output starting 16-byte aligned, all filled with a NaN sentinel (bf16 0x7FA5
 accumulator of an 8-bit GEMM reaches).  `check` then asserts, in this order: the guards are untouched, no sentinel is left inside
 M x N, and every element matches the reference:
   * exact: the same bits as `ref_bits` (int8 scaled / dynamic outputs on the oracle's epilogue, int_mm's int32);
-  * otherwise |y - ref64| <= ulp(ref64) + 2 K 2^-24 S per element, S = |x| |w|^T with the scales applied (float64), ulp of bf16 or
-    fp32 as the output; and, for bf16 outputs of at least 1024 elements, a fraction `equal` of them equal to the oracle's rounding of
-    ref64 (fp32 -> bf16): 0.97 by default.  The fp8 MFMAs sum e4m3 products spanning 2^36 less exactly than a float64 sum rounded
-    once, and the fp8 x int4 kernel rounds once more per group: callers pass what those families reach within the bound above.
-A failure names the count of bad elements, the first bad (row, column) and its tile and K parts under the route.
+  * otherwise |y - ref64| <= ulp(ref64) + 2 max(K, k_floor) 2^-24 S per element, S = |x| |w|^T with the scales applied (float64),
+    ulp of bf16 or fp32 as the output, `k_floor` 0 by default; and, for bf16 outputs of at least 1024 elements, a fraction `equal` of
+    them equal to the oracle's rounding of ref64 (fp32 -> bf16): 0.97 by default.  The fp8 MFMAs sum e4m3 products spanning 2^36 less
+    exactly than a float64 sum rounded once -- by a share of S that one MFMA sets and a longer K does not grow, hence the floor on K
+    -- and the fp8 x int4 kernel rounds once more per group: callers pass what those families reach within the bound above.
+`written_rows` (the grouped GEMMs: offs[-1]) asks for rows [written_rows, M) to still hold the sentinel and compares only the rows
+above.  A failure names the count of bad elements, the first bad (row, column) and its tile and K parts under the route.
 """
 import torch
 
@@ -83,16 +85,37 @@ def locate(i, j, route):
     return " (tile %d, %d of %d x %d; %d K parts)" % (i // route["rows"], j // route["cols"], route["rows"], route["cols"], route["parts"])
 
 
-def problems(buf, *, ref64=None, S=None, K=None, ref_bits=None, route=None, equal=EQUAL_FRACTION):
+def bound(ref64, S, K, dtype, k_floor=0):
+    return ulp(ref64, dtype) + 2.0 * max(K, k_floor) * 2.0 ** -24 * S
+
+
+def k_needed(y, ref64, S, dtype):
+    """The smallest max(K, k_floor) under which every element of y meets the bound."""
+    over = ((y.to(torch.float64) - ref64).abs() - ulp(ref64, dtype)).clamp(min=0)
+    return (over / (2.0 * 2.0 ** -24 * S)).nan_to_num(0.0).max().item() if y.numel() else 0.0
+
+
+def problems(buf, *, ref64=None, S=None, K=None, ref_bits=None, route=None, equal=EQUAL_FRACTION, k_floor=0, written_rows=None):
     """Every way the guarded output misses the reference, as messages (empty: the output passes)."""
     msgs = buf.guard_problems()
     bits = buf.bits()
+    rows = buf.M if written_rows is None else written_rows
+    if rows < buf.M:
+        written = bits[rows:] != buf.sentinel
+        if bool(written.any()):
+            i, j = (int(v) for v in torch.nonzero(written)[0])
+            msgs.append("%d elements written in the rows past %d that must stay unwritten, first at row %d, column %d%s"
+                        % (int(written.sum()), rows, rows + i, j, locate(rows + i, j, route)))
+    bits = bits[:rows]
     unwritten = bits == buf.sentinel
     if bool(unwritten.any()):
         i, j = (int(v) for v in torch.nonzero(unwritten)[0])
         msgs.append("%d elements left unwritten (sentinel), first at row %d, column %d%s" % (int(unwritten.sum()), i, j, locate(i, j, route)))
-    y = buf.out
+    y = buf.out[:rows]
+    if ref64 is not None:
+        ref64, S = ref64[:rows], S[:rows]
     if ref_bits is not None:
+        ref_bits = ref_bits[:rows]
         want = ref_bits.view(_BITS[buf.dtype]) if ref_bits.dtype != _BITS[buf.dtype] else ref_bits
         bad = bits != want
         if bool(bad.any()):
@@ -101,12 +124,14 @@ def problems(buf, *, ref64=None, S=None, K=None, ref_bits=None, route=None, equa
                         % (int(bad.sum()), i, j, y[i, j].item(), ref_bits.view(buf.dtype)[i, j].item(), locate(i, j, route)))
         return msgs
     yd = y.to(torch.float64)
-    bound = ulp(ref64, buf.dtype) + 2.0 * K * 2.0 ** -24 * S
-    bad = ~((yd - ref64).abs() <= bound)  # NaN fails
+    b = bound(ref64, S, K, buf.dtype, k_floor)
+    bad = ~((yd - ref64).abs() <= b)  # NaN fails
     if bool(bad.any()):
         i, j = (int(v) for v in torch.nonzero(bad)[0])
-        msgs.append("%d elements outside |y - ref| <= ulp + 2 K 2^-24 S, first at row %d, column %d: %r vs %r (bound %.3g)%s"
-                    % (int(bad.sum()), i, j, y[i, j].item(), ref64[i, j].item(), bound[i, j].item(), locate(i, j, route)))
+        msgs.append("%d elements outside |y - ref| <= ulp + 2 max(K, %d) 2^-24 S, first at row %d, column %d: %r vs %r (bound %.3g; the "
+                    "worst element needs max(K, k_floor) >= %.0f)%s"
+                    % (int(bad.sum()), k_floor, i, j, y[i, j].item(), ref64[i, j].item(), b[i, j].item(), k_needed(y, ref64, S, buf.dtype),
+                       locate(i, j, route)))
     if buf.dtype == torch.bfloat16 and y.numel() >= EQUAL_MIN_ELEMENTS:
         eq = (y == oracle_round(ref64, buf.dtype)).double().mean().item()
         if eq < equal:

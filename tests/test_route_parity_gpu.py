@@ -5,8 +5,11 @@ Operands are drawn directly, not quantised from normals: int8 codes uniform over
 nibbles; row / column scales 2^U(-10, 4), int4 scales and zeros 2^U(-6, 2) per (group, column), bias randn x 2^U(-4, 4) per column,
 bf16 activations (int4, dynamic entries) with row magnitudes 2^U(-8, 8).  A scale, group or bias read from the wrong index is off by a
 large factor.  The reference is a float64 product in torch on the device; the int8 epilogue and the activation casts are the oracle's.
-Every case launches twice into differently poisoned buffers (split-K routes with another split-K launch in between) and must give the
-same bits; its route must still be the recorded one.
+MX dense linears: every finite e4m3 code or all 16 e2m1 nibbles, E8M0 scales 127 + U{-12..12} per (row, 32-block), so a scale read
+from the neighbouring block or the wrong half of the e4m3 lane map is off by up to 2^24; the fused cast's activations have magnitudes
+2^U(-8, 8) per (row, block) and one all-zero block, cast by the oracle (oracle/mx_ref.to_mx, tests/mx_linear_ref.to_mx4) under both
+scaling modes.  Every case launches twice into differently poisoned buffers (split-K routes with another split-K launch in between) and
+must give the same bits; its route must still be the recorded one.
 """
 import numpy as np
 import pytest
@@ -15,12 +18,23 @@ import torch
 import _parity
 import route_cases as rc
 from ao_amd import _lib
-from oracle import fp8_ref, int4_ref, int8_ref
+import mx_linear_ref
+from oracle import fp8_ref, int4_ref, int8_ref, mx_ref
 
 # Outputs equal to the oracle's rounding, at least (tests/_parity.py; bf16 x int4: its default 0.97).  Measured on every route of
 # these families with the operands below: fp8 GEMMs 0.958 - 0.97, fp8 x int4 0.94 - 0.96, each element within the bound.
 EQUAL_FP8 = 0.95
 EQUAL_FP8_INT4 = 0.93
+# MX dense (scaled MFMA): the floor on K of the bound (tests/_parity.py) and the equal fraction per format, measured on every MX case
+# with the operands below (E8M0 scales spread over 2^+-12 per block).  e2m1: every element within ulp + 0.13 x 2^-23 S, equal 0.9997
+# at least.  e4m3: one scaled MFMA sums e4m3 products spanning 2^36 less exactly than a float64 sum rounded once -- by a share of S
+# that does not grow with K: the worst element needs max(K, floor) >= 1110 on the route cases (607 at K = 32, 1110 at 1024, 904 at
+# 4160), 1153 on the forced stream form at K = 160 and 1286 on the grouped MX cases (K = 128) -- the same instruction, one floor:
+# 1408.  Equal 0.963 at least.
+K_FLOOR_E4M3_MX = 1408
+K_FLOOR_MX = {"e2m1": 0, "e4m3": K_FLOOR_E4M3_MX}
+EQUAL_MX = {"e2m1": 0.99, "e4m3": 0.96}
+MX_MODES = {"floor": mx_ref.FLOOR, "rceil": mx_ref.RCEIL}
 
 _TILE_INDEX = None
 
@@ -88,6 +102,22 @@ class Draw:
         x = torch.randn(M, K, generator=self.g, device=self.dev, dtype=torch.float64) * self.pow2(-8, 8, M, 1)
         return x.bfloat16()
 
+    def e8m0(self, *shape):
+        """E8M0 block scales 127 + U{-12..12}, independent per element."""
+        return (127 + torch.randint(-12, 13, shape, generator=self.g, device=self.dev)).to(torch.uint8)
+
+    def e2m1(self, *shape):
+        """Packed e2m1 codes [..., K / 2] of all 16 nibbles (element 2i in the low nibble of byte i)."""
+        q = self.nibbles(*shape)
+        return (q[..., 0::2] | (q[..., 1::2] << 4)).to(torch.uint8)
+
+    def mx_act(self, M, K):
+        """bf16 activations whose (row, 32-block) magnitudes span 2^-8 .. 2^8, one block all zero."""
+        x = torch.randn(M, K, generator=self.g, device=self.dev, dtype=torch.float64)
+        x = x * self.pow2(-8, 8, M, K // 32).repeat_interleave(32, 1)
+        x[M // 2, 32 * ((K // 32) // 2):32 * ((K // 32) // 2 + 1)] = 0
+        return x.bfloat16()
+
     def int4_sz(self, K, N, G, zeros=True):
         s = self.pow2(-6, 2, K // G, N)
         z = self.pow2(-6, 2, K // G, N) * (torch.randint(0, 2, (K // G, N), generator=self.g, device=self.dev) * 2 - 1) if zeros else 0 * s
@@ -95,12 +125,13 @@ class Draw:
 
 
 def _offset(t, aligned):
-    """t itself, or a copy of it at a one-element offset (4 bytes for fp32 scales, 2 for bf16 bias)."""
+    """t itself, or a copy of it at a one-element offset (4 bytes for fp32 scales, 2 for bf16 bias, 1 for E8M0 scales)."""
     if aligned or t is None:
         return t
     buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=t.device)
-    buf[1:].copy_(t)
-    return buf[1:]
+    out = buf[1:].view(t.shape)
+    out.copy_(t)
+    return out
 
 
 def _e4m3(codes):
@@ -111,13 +142,33 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
+def mx_dequant(codes, scale, fmt):
+    """float64 elements 2^(scale - 127) of e4m3 codes [..., K] or packed e2m1 [..., K / 2] (exact)."""
+    if fmt == "e2m1":
+        table = torch.from_numpy(mx_linear_ref.E2M1_VALUES.astype(np.float64)).to(codes.device)
+        q = torch.stack([codes & 15, codes >> 4], -1).flatten(-2)
+        v = table[q.long()]
+    else:
+        v = _e4m3(codes)
+    return v * torch.exp2(scale.double() - 127).repeat_interleave(32, -1)
+
+
+def mx_cast(x, fmt, mode):
+    """The oracle's 1 x 32 cast of bf16 x (to_mx / to_mx4) -> (codes, E8M0 scales) on x's device."""
+    if fmt == "e2m1":
+        q, s = mx_linear_ref.to_mx4(x.view(torch.int16).cpu().numpy().view(np.uint16), MX_MODES[mode])
+    else:
+        q, s = mx_ref.to_mx(x.float().cpu().numpy(), MX_MODES[mode])
+    return torch.from_numpy(np.ascontiguousarray(q)).to(x.device), torch.from_numpy(np.ascontiguousarray(s)).to(x.device)
+
+
 # ---- one case: operands, launch, reference ----
 
 class Run:
     """Operands of a case, a launch into a guarded buffer, and the reference the output must meet."""
 
-    def __init__(self, case, seed, dev):
-        self.case, self.dev = case, dev
+    def __init__(self, case, seed, dev, mode=None):
+        self.case, self.dev, self.mode = case, dev, mode
         fam, entry, M, N, K, G, bias, aligned = case
         d = Draw(seed, dev)
         self.bias = d.bias(N) if bias else None
@@ -126,6 +177,8 @@ class Run:
             self._gemm8(d, entry, M, N, K)
         elif fam == "int4":
             self._int4(d, M, N, K, G)
+        elif fam == "mx":
+            self._mx(d, entry, M, N, K)
         else:
             self._fp8_int4(d, entry, M, N, K, G)
         self.sa = _offset(getattr(self, "sa", None), aligned)
@@ -193,6 +246,21 @@ class Run:
         xs = self.sa.double()[:, None]
         self.ref.update(ref64=xs * (X @ w.T) + self._bias64(), S=xs * (X.abs() @ wabs.T) + abs(self._bias64()), K=K, equal=EQUAL_FP8_INT4)
 
+    def _mx(self, d, entry, M, N, K):
+        """Codes and scales drawn directly (codes entry) or the oracle's cast of drawn activations (fused entry, self.mode)."""
+        fmt, form = entry.split("_")
+        self.fmt, self.out_dtype = fmt, torch.bfloat16
+        codes = d.fp8 if fmt == "e4m3" else (lambda r, k: d.e2m1(r, k))
+        self.b, self.sb = codes(N, K), d.e8m0(N, K // 32)
+        if form == "codes":
+            self.a, self.sa = codes(M, K), d.e8m0(M, K // 32)
+        else:
+            self.x = d.mx_act(M, K)
+            self.a, self.sa = mx_cast(self.x, fmt, self.mode)
+        A, B = mx_dequant(self.a, self.sa, fmt), mx_dequant(self.b, self.sb, fmt)
+        self.ref.update(ref64=A @ B.T + self._bias64(), S=A.abs() @ B.abs().T + abs(self._bias64()), K=K, equal=EQUAL_MX[fmt],
+                        k_floor=K_FLOOR_MX[fmt])
+
     def launch(self, buf):
         lib = _lib.lib()
         fam, entry, M, N, K, G = self.case[:6]
@@ -208,6 +276,12 @@ class Run:
                 "fp8_dyn": lambda: lib.ao_fp8_dynamic_linear(_ptr(self.x), _ptr(self.b), _ptr(self.sb), _ptr(self.bias_arg), y, M, N, K, s),
             }[entry]
             rc_ = call()
+        elif fam == "mx":
+            fmt = rc.MX_FMT[self.fmt]
+            if entry.endswith("fused"):
+                rc_ = lib.ao_mx_dynamic_linear(fmt, _ptr(self.x), _ptr(self.b), _ptr(self.sb), _ptr(self.bias_arg), y, M, N, K, MX_MODES[self.mode], s)
+            else:
+                rc_ = lib.ao_mx_linear(fmt, _ptr(self.a), _ptr(self.sa), _ptr(self.b), _ptr(self.sb), _ptr(self.bias_arg), y, M, N, K, s)
         elif fam == "int4":
             rc_ = lib.ao_int4_weight_int4pack_mm(_ptr(self.x), _ptr(self.qdata), _ptr(self.sz), y, M, N, K, G, s)
         elif entry.startswith("dyn"):
@@ -246,25 +320,26 @@ def test_route_parity(product_dispatch, index):
     route = rc.route_of(lib, case)
     assert route is not None and route["sig"] == sig, (case, sig, route and route["sig"])
     dev = torch.device("cuda", 0)
-    run = Run(case, 1000 + index, dev)
-    buf = _parity.Guarded(case.M, case.N, run.out_dtype, dev)
-    run.launch(buf)
-    _parity.check(buf, route=route, **run.ref)
-    first = buf.bits().clone()
+    for mode in (MX_MODES if case.family == "mx" and case.entry.endswith("fused") else (None,)):
+        run = Run(case, 1000 + index, dev, mode)
+        buf = _parity.Guarded(case.M, case.N, run.out_dtype, dev)
+        run.launch(buf)
+        _parity.check(buf, route=route, **run.ref)
+        first = buf.bits().clone()
 
-    if route["parts"] > 1:  # no ticket or workspace state may carry over from another split-K launch
-        other = _SPLIT[case.family] if _SPLIT[case.family] != case else None
-        if other is not None:
-            orun = Run(other, 7, dev)
-            orun.launch(_parity.Guarded(other.M, other.N, orun.out_dtype, dev))
-    buf.poison(_parity.SENTINEL2)
-    run.launch(buf)
-    assert not buf.guard_problems(), buf.guard_problems()
-    same = buf.bits() == first
-    if not bool(same.all()):
-        i, j = (int(v) for v in torch.nonzero(~same)[0])
-        raise AssertionError("second launch differs in %d elements, first at row %d, column %d%s"
-                             % (int((~same).sum()), i, j, _parity.locate(i, j, route)))
+        if route["parts"] > 1:  # no ticket or workspace state may carry over from another split-K launch
+            other = _SPLIT[case.family] if _SPLIT[case.family] != case else None
+            if other is not None:
+                orun = Run(other, 7, dev)
+                orun.launch(_parity.Guarded(other.M, other.N, orun.out_dtype, dev))
+        buf.poison(_parity.SENTINEL2)
+        run.launch(buf)
+        assert not buf.guard_problems(), buf.guard_problems()
+        same = buf.bits() == first
+        if not bool(same.all()):
+            i, j = (int(v) for v in torch.nonzero(~same)[0])
+            raise AssertionError("second launch differs in %d elements, first at row %d, column %d%s"
+                                 % (int((~same).sum()), i, j, _parity.locate(i, j, route)))
 
 
 @pytest.mark.gpu
@@ -285,3 +360,31 @@ def test_dyn8_override_form(product_dispatch, entry, M, bias):
     finally:
         lib.ao_gemm8_set_variant(0)
     _parity.check(buf, **run.ref)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("entry,M,N,form", [
+    ("e4m3_codes", 100, 1000, 1), ("e4m3_fused", 100, 1000, 1), ("e2m1_codes", 100, 257, 1), ("e2m1_fused", 70, 257, 1),
+    ("e4m3_codes", 5, 1000, 2), ("e2m1_codes", 32, 257, 2),
+])
+def test_mx_linear_forced_forms(entry, M, N, form):
+    """ao_mx_linear_set_form: the stream form above the seam (4 m-tiles, more than one grid row), the tiled form at M <= seam; the
+    route query reads the same override, so the form that runs is asserted."""
+    lib = _lib.lib()
+    K = 160
+    case = rc.Case("mx", entry, M, N, K, 0, True, True)
+    dev = torch.device("cuda", 0)
+    for mode in (MX_MODES if entry.endswith("fused") else (None,)):
+        run = Run(case, 31 + M, dev, mode)
+        buf = _parity.Guarded(M, N, torch.bfloat16, dev)
+        lib.ao_mx_linear_set_form(form)
+        try:
+            r = rc.mx_route(lib, rc.MX_FMT[run.fmt], M, N, K)
+            run.launch(buf)
+        finally:
+            lib.ao_mx_linear_set_form(0)
+        product = rc.mx_route(lib, rc.MX_FMT[run.fmt], M, N, K)["kernel"]
+        assert r["kernel"] == rc.MX_KERNELS[form] != product, (r, product)
+        if form == 1:
+            assert r["mt"] == 4 and r["grid_y"] > 1, r
+        _parity.check(buf, **run.ref)
