@@ -53,6 +53,7 @@ _SIGNATURES = {
     "ao_gemm8_overridden": [],
     "ao_int4_overridden": [],
     "ao_int4_mm_route": [_I64, _I64, _I64, _INT, _P, _INT],
+    "ao_int4_balanced_halves": [_I64, _INT, _INT],
     "ao_int8_quantize_rowwise": [_P, _P, _P, _I64, _I64, _P],
     "ao_int8_scaled_mm": [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _P],
     "ao_int8_int_mm": [_P, _P, _P, _I64, _I64, _I64, _P],

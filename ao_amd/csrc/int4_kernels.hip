@@ -163,12 +163,24 @@ struct XRegs {
 // instruction orders of the dequant, several n-tiles per workgroup, and cross-workgroup K parts at M = 1.
 // STRAIGHT: every wave of the workgroup owns exactly DEPTH blocks (K = 128 DEPTH waves): prologue, one pass of the ring, done --
 //   no steady-state / drain loops, fewer live registers (64 VGPRs: four 8-wave workgroups per CU instead of three)
-template <int G, int MAXM, int DEPTH, bool STRAIGHT = false>
+// BAL (the 8-wave x 4-block straight-line form only): the balanced grid.  With T n-tiles the grid is T + r workgroups: the first
+//   2 r are the two HALVES of the last r tiles (the tiles left over after whole rounds of the CUs), the other T - r own a whole tile as before.
+//   Half p runs, on its waves 0 .. 3, exactly what waves 4 p .. 4 p + 3 of a whole-tile workgroup run (waves 4 .. 7 leave before any barrier),
+//   parks its four per-wave partial rows in the split-K workspace (sc1 stores, splitk.h) and takes the tile's ticket; the half that arrives
+//   last adds the eight per-wave partials in wave order 0 .. 7 -- the sum the whole-tile epilogue forms, bit for bit -- and stores the row.
+//   Nobody waits: the halves hold half a tile's work and meet while the whole tiles are still running.
+// STAMP (profiling, tuning modes 983 / 984): thread 0 of every workgroup writes 8 u64 behind the parked partials -- hardware id, the 100 MHz
+//   clock at entry and exit, the shader clock at entry / first weight block landed / wave 0 done with its blocks / exit.
+template <int G, int MAXM, int DEPTH, bool STRAIGHT = false, bool BAL = false, bool STAMP = false>
 __global__ __launch_bounds__((MAXM > 4) ? 512 : 1024) void int4_mm_kernel(
     const uint16_t* __restrict__ x, const u32x4* __restrict__ qdata,
-    const uint32_t* __restrict__ sz, uint16_t* __restrict__ y, int M, int N, int K, float* __restrict__ /* unused */, unsigned* __restrict__ /* unused */) {
-  // (the two trailing arguments carried the M = 1 split-K workspace of round 3; the form is gone, the kernarg layout stays: removing them
-  // re-allocates the prologue's scalar registers, and every measurement of this kernel since round 3 was taken on this layout)
+    const uint32_t* __restrict__ sz, uint16_t* __restrict__ y, int M, int N, int K, float* __restrict__ ws, unsigned* __restrict__ tickets) {
+  // (the two trailing arguments carried the M = 1 split-K workspace of round 3 and carry the balanced grid's now; the other builds leave them
+  // unused and the kernarg layout stays: removing them re-allocates the prologue's scalar registers, and every measurement of this kernel
+  // since round 3 was taken on this layout)
+  static_assert(!(BAL || STAMP) || (STRAIGHT && MAXM == 1 && DEPTH == 4), "the balanced grid and the stamps exist on the 8 x 4 straight-line form");
+  unsigned long long stamp[6] = {0, 0, 0, 0, 0, 0};
+  if constexpr (STAMP) { stamp[0] = __builtin_amdgcn_s_memrealtime(); stamp[2] = __builtin_amdgcn_s_memtime(); }
   constexpr int NG = (G >= 128) ? 1 : (128 / G);              // groups per 128-k block
   constexpr int ROWSTRIDE = (MAXM <= 4) ? 256 : 272;          // bytes, padded vs bank conflicts
   constexpr int SLAB = (MAXM + 1) * ROWSTRIDE;                // per-wave x staging: rows 0 .. MAXM - 1 + one zero row
@@ -177,13 +189,24 @@ __global__ __launch_bounds__((MAXM > 4) ? 512 : 1024) void int4_mm_kernel(
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int nwaves = blockDim.x >> 6;
-  const int ntile = blockIdx.x;
+  int ntile = blockIdx.x;
+  int kwave = wave;        // the wave of a whole-tile workgroup whose blocks this wave runs
+  int part = -1;           // BAL: 0 / 1 in a half-tile workgroup
+  const int halves = BAL ? 2 * ((int)gridDim.x - (N >> 4)) : 0;  // (the host launched T + r workgroups)
+  if constexpr (BAL) {
+    // (selects, not branches: what follows stays one basic block, as in the other builds)
+    const bool halved = (int)blockIdx.x < halves;
+    if (halved && wave >= 4) return;  // before any barrier: the workgroup's barriers count its four live waves
+    part = halved ? (int)(blockIdx.x & 1) : -1;
+    ntile = halved ? (N >> 4) - (halves >> 1) + ((int)blockIdx.x >> 1) : (int)blockIdx.x - halves;
+    kwave = wave + (halved ? 4 * part : 0);
+  }
   const int m0 = blockIdx.y * 16;
   const int rows = min(16, M - m0);
   const int kblocks = K >> 7;
   // straight-line form: every wave owns exactly DEPTH blocks (the host checked K = 128 DEPTH waves) -- no division by the runtime wave count
   constexpr bool kFixedRun = STRAIGHT;
-  const int kb0 = kFixedRun ? wave * DEPTH : (kblocks * wave) / nwaves;
+  const int kb0 = kFixedRun ? kwave * DEPTH : (kblocks * wave) / nwaves;
   const int kb1 = kFixedRun ? kb0 + DEPTH : (kblocks * (wave + 1)) / nwaves;
 
   char* slab = smem + wave * SLAB;
@@ -312,10 +335,19 @@ __global__ __launch_bounds__((MAXM > 4) ? 512 : 1024) void int4_mm_kernel(
   };
   if constexpr (STRAIGHT) {
     // the host guarantees kb1 - kb0 == DEPTH for every wave: one pass of the ring
+    if constexpr (STAMP) {
+      // block 0's weights have landed once only the requests issued behind them are still out (its scale words and x piece, the other blocks)
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NG + 1 + (DEPTH - 1) * (NG + 2)) : "memory");
+      stamp[3] = __builtin_amdgcn_s_memtime();
+    }
     for_slots([&](auto dc) {
       constexpr int d = decltype(dc)::value;
       consume(st[d]);
     });
+    if constexpr (STAMP) {
+      asm volatile("" ::"v"(acc));
+      stamp[4] = __builtin_amdgcn_s_memtime();
+    }
     float* r = red + wave * 256 + (kq * 4) * 16 + (lane & 15);
     r[0] = acc.x; r[16] = acc.y; r[32] = acc.z; r[48] = acc.w;
     acc = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -351,12 +383,58 @@ __global__ __launch_bounds__((MAXM > 4) ? 512 : 1024) void int4_mm_kernel(
   }
   __syncthreads();
   const int tid = threadIdx.x;
+  auto write_stamps = [&] {
+    if constexpr (STAMP) {
+      if (tid == 0) {
+        unsigned long long* s = reinterpret_cast<unsigned long long*>(ws + (size_t)halves * 64) + (size_t)blockIdx.x * 8;
+        s[0] = ((unsigned long long)__builtin_amdgcn_s_getreg(20 | (31 << 11)) << 32) | __builtin_amdgcn_s_getreg(4 | (31 << 11));  // XCC_ID | HW_ID
+        s[1] = stamp[0]; s[2] = __builtin_amdgcn_s_memrealtime();
+        s[3] = stamp[2]; s[4] = stamp[3]; s[5] = stamp[4]; s[6] = __builtin_amdgcn_s_memtime();
+        s[7] = ((unsigned long long)(unsigned)(part + 1) << 32) | (unsigned)ntile;
+      }
+    }
+  };
+  if constexpr (BAL) {
+    if (part >= 0) {
+      // the meeting of the two halves of tile `ntile`, on wave 0: lane (w, col) parks partial w of this half.  Workspace: [pair][half][wave][col]
+      if (wave == 0) {
+        constexpr int kSc1 = 16;  // as in split_k_meet: written through / read at agent scope, the halves sit on different XCDs
+        const int pair = blockIdx.x >> 1;
+        const __amdgpu_buffer_rsrc_t rws = __builtin_amdgcn_make_buffer_rsrc(ws + (size_t)pair * 128, 0, 512, 0x00020000);
+        float mine = red[(lane >> 4) * 256 + (lane & 15)];
+        asm volatile("" : "+v"(mine));
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, mine), rws, (part * 64 + lane) * 4, 0, kSc1);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // written through before the ticket is taken
+        asm volatile("" ::"v"(mine));
+        unsigned t = 0;
+        if (lane == 0) {
+          const unsigned inc = 1u;
+          t = __hip_atomic_fetch_add(&tickets[pair], inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          if (t == 1u) __hip_atomic_store(&tickets[pair], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch
+        }
+        t = __builtin_amdgcn_readfirstlane(t);
+        if (t == 1u && lane < 16) {
+          float other[4];
+#pragma unroll
+          for (int w = 0; w < 4; ++w)
+            other[w] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rws, ((1 - part) * 64 + w * 16 + lane) * 4, 0, kSc1));
+          float sum = 0.f;
+#pragma unroll
+          for (int w = 0; w < 8; ++w) sum += ((w >> 2) == part) ? red[(w & 3) * 256 + lane] : other[w & 3];  // wave order, as below
+          y[(size_t)ntile * 16 + lane] = f32_to_bf16_bits(sum);
+        }
+      }
+      write_stamps();
+      return;
+    }
+  }
   const int row = tid >> 4, col = tid & 15;
   if (tid < 256 && row < rows) {
     float sum = 0.f;
     for (int w = 0; w < nwaves; ++w) sum += red[w * 256 + tid];
     y[(size_t)(m0 + row) * N + ntile * 16 + col] = f32_to_bf16_bits(sum);
   }
+  write_stamps();
 }
 
 // ---------------------------------------------------------------------------
@@ -1191,6 +1269,37 @@ int launch_mm(const uint16_t* x, const int32_t* qdata, const uint16_t* sz, uint1
   return AO_OK;
 }
 
+// The balanced grid of the one-row 8-wave x 4-block straight-line form (int4_mm_kernel<.., BAL>): `halves` left-over tiles run as two
+// half-tile workgroups each, which meet through the split-K workspace.  STAMP: the profiling build (modes 983 / 984; g = 128), whose stamps
+// land behind the parked partials and are copied to the ao_int4_set_trace buffer ([workgroups][8] u64) by the launch.
+template <int G, bool BAL, bool STAMP>
+int launch_mm_row1(const uint16_t* x, const int32_t* qdata, const uint16_t* sz, uint16_t* y, int64_t M, int64_t N, int64_t K, hipStream_t stream,
+                   int halves) {
+  const int64_t ntiles = N >> 4;
+  AO_REQUIRE(M == 1 && (K >> 7) == 32, "int4_mm: the balanced grid is built for one row and K = 4096 (8 waves x 4 blocks), got M=%lld K=%lld",
+             (long long)M, (long long)K);
+  AO_REQUIRE(halves >= (BAL ? 1 : 0) && halves <= (BAL ? ntiles : 0) && halves <= kSplitMaxTickets,
+             "int4_mm: %d halved tiles of %lld", halves, (long long)ntiles);
+  const size_t smem = (size_t)8 * (512 + 1024);
+  dim3 grid((unsigned)(ntiles + halves)), block(512);
+  float* ws = nullptr;
+  unsigned* tickets = nullptr;
+  const size_t park_floats = (size_t)halves * 128, stamp_floats = STAMP ? (size_t)grid.x * 16 : 0;
+  if (int rc = splitk_workspace(stream, &ws, &tickets, park_floats + stamp_floats, 2)) return rc;
+  auto kern = int4_mm_kernel<G, 1, 4, true, BAL, STAMP>;
+  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), smem, "hipFuncSetAttribute(int4_mm_kernel)")) return rc;
+  ao::launch(kern, grid, block, smem, stream, x, reinterpret_cast<const u32x4*>(qdata), reinterpret_cast<const uint32_t*>(sz), y, (int)M, (int)N,
+             (int)K, ws, tickets);
+  AO_LAUNCH_CHECK("int4_mm_kernel launch");
+  if constexpr (STAMP) {
+    if (g_mm_trace != nullptr) {
+      hipError_t e = hipMemcpyAsync(g_mm_trace, ws + park_floats, stamp_floats * sizeof(float), hipMemcpyDeviceToDevice, stream);
+      if (e != hipSuccess) return hip_failed(e, "hipMemcpyAsync(int4_mm_kernel stamps)");
+    }
+  }
+  return AO_OK;
+}
+
 // The form of an int4 matmul launch.  Tile: int4_mm_kernel, `rows` the build (1, 4, 8 or 16 rows), its ring depth, straight-line or
 // not, waves per workgroup forced (0: by rule).  Rb: int4_mm_rb_kernel<WAVES, NT, MT, ABL, PROD> with `split` K parts.  W32:
 // int4_mm_w32_kernel<PROD, ABL, CG> (CG 1: 128 x 128 tiles, 2: 128 x 256) with `split` K parts.
@@ -1200,6 +1309,8 @@ struct Int4Route {
   bool straight = false;
   int waves = 4, nt = 1, mt = 1, abl = 0, cg = 1, split = 1;
   bool prod = false;
+  int halves = 0;       // Tile, one row, 8 x 4 straight-line: left-over n-tiles run as two half-tile workgroups each (0: today's grid)
+  bool stamp = false;   // the stamped profiling build of that form
 };
 
 Int4Route tile_form(int rows, int depth = 4, bool straight = false) {
@@ -1375,10 +1486,36 @@ Int4Route int4_forced_route(int64_t M, int64_t N, int64_t K, int G, const Int4Fo
   return rb_route(M, N, K, mt, waves, forced_split, mode != 910);
 }
 
+// Compute units of the current device (cached per device); 256, the MI355X, where there is no device to ask (the host-only queries).
+int device_cus() {
+  static std::mutex mu;
+  static int cached[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
+    (void)hipGetLastError();
+    return 256;
+  }
+  std::lock_guard<std::mutex> lock(mu);
+  if (cached[dev] == 0) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) {
+      (void)hipGetLastError();
+      n = 256;
+    }
+    cached[dev] = n;
+  }
+  return cached[dev];
+}
+
+// Modes 981 - 984 of ao_int4_set_tuning: the balanced grid never / wherever the form allows (any left-over count) / the stamped build on
+// today's grid / the stamped build on the balanced grid as 982 cuts it.  Every other choice stays the product's.
+constexpr int kBalOff = 981, kBalOn = 982, kStampGrid = 983, kStampBal = 984;
+
 // The route of ao_int4_weight_int4pack_mm (group size G); with f = Int4Force{} the product dispatch, which ao_int4_mm_kernel_name reports.
 Int4Route int4_route(int64_t M, int64_t N, int64_t K, int G, const Int4Force& f) {
   Int4Route r;
-  if (f.mode != 0) r = int4_forced_route(M, N, K, G, f);
+  const bool bal_mode = f.mode >= kBalOff && f.mode <= kStampBal;
+  if (f.mode != 0 && !bal_mode) r = int4_forced_route(M, N, K, G, f);
   // M <= 16: one workgroup per 16-wide n-tile, waves split K (int4_mm_kernel, built for 1, 4, 8 or 16 rows).  In the hipGraph
   // bench the single-row build beat both purpose-built decode kernels this round tried (a persistent balanced streaming kernel
   // with hand-counted LDS-DMA rings and a per-tile kernel with workgroup-shared x): 868 vs 732 tok/s.
@@ -1395,6 +1532,12 @@ Int4Route int4_route(int64_t M, int64_t N, int64_t K, int G, const Int4Force& f)
   else if (w32_band(M, N)) r = w32_route(M, N, K, G);
   else r = rb_route(M, N, K, (M <= 16) ? 1 : (M <= 32) ? 2 : (M <= 64) ? 4 : 8);
   r.wpb = f.wpb;  // (the per-tile kernel's waves per workgroup; ao_int4_set_tuning)
+  // The balanced grid, decided here and nowhere else: the one-row straight-line form of 8 waves x 4 blocks (K = 4096).
+  if ((f.mode == 0 || bal_mode) && r.form == Int4Route::Tile && r.rows == 1 && r.straight && r.depth == 4 && (K >> 7) == 32) {
+    const bool forced = f.mode == kBalOn || f.mode == kStampBal;
+    if (f.mode != kBalOff && f.mode != kStampGrid) r.halves = ao_int4_balanced_halves(N >> 4, device_cus(), forced);
+    r.stamp = (f.mode == kStampGrid || f.mode == kStampBal) && G == 128;
+  }
   return r;
 }
 
@@ -1407,6 +1550,12 @@ int launch_route(const Int4Route& r, const uint16_t* x, const int32_t* qdata, co
   const int s = r.split;
   switch (r.form) {
     case Int4Route::Tile:
+      if (r.stamp) {
+        if constexpr (G == 128)
+          return r.halves > 0 ? launch_mm_row1<G, true, true>(AO_MM_ARGS, stream, r.halves) : launch_mm_row1<G, false, true>(AO_MM_ARGS, stream, 0);
+        break;
+      }
+      if (r.halves > 0) return launch_mm_row1<G, true, false>(AO_MM_ARGS, stream, r.halves);
       if (r.rows == 1 && r.straight) {
         switch (r.depth) {
           case 4: return launch_mm<G, 1, 4>(AO_MM_ARGS, stream, true, r.wpb);
@@ -1504,6 +1653,17 @@ int check_int4_shape(const char* fn, int64_t N, int64_t K, int group_size) {
 
 using namespace ao;
 
+// The balanced grid's rule (host arithmetic only; int4_route is its one caller in the library).  T n-tiles on C compute units leave
+// r = T mod C tiles over after whole rounds.  The product cuts them in two when all tiles are resident at once (one round: C < T <= 4 C)
+// and the 2 r halves are one more per CU (2 r = C) -- what was measured; forced != 0 (modes 982 / 984) cuts any r > 0.
+extern "C" int ao_int4_balanced_halves(int64_t tiles, int cus, int forced) {
+  if (tiles <= 0 || cus <= 0) return 0;
+  const int64_t r = tiles % cus;
+  if (r > kSplitMaxTickets) return 0;
+  if (forced) return (int)r;
+  return (tiles > cus && tiles <= 4ll * cus && 2 * r == cus) ? (int)r : 0;
+}
+
 // the product route's kernel (int4_route with no override; host logic only)
 extern "C" const char* ao_int4_mm_kernel_name(int64_t M, int64_t N, int64_t K, int group_size) {
   const Int4Route r = int4_route(M, N, K, group_size, Int4Force{});
@@ -1520,6 +1680,7 @@ extern "C" int ao_int4_mm_route(int64_t M, int64_t N, int64_t K, int group_size,
   const Int4Route r = int4_route(M, N, K, group_size, Int4Force{});
   const int32_t v[10] = {(int32_t)r.form, r.rows, r.depth, r.straight, r.waves, r.nt, r.mt, r.cg, r.split, r.prod};
   for (int i = 0; i < 10; ++i) out[i] = v[i];
+  if (cap >= 11) out[10] = r.halves;  // n-tiles run as two half-tile workgroups (the balanced grid; `split` stays 1)
   return AO_OK;
 }
 

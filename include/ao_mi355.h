@@ -121,7 +121,10 @@ int ao_int4_quantize_tinygemm(const uint16_t* w, int32_t* qdata,
  * workgroup (0 = heuristic) and an A/B mode of the int4 mm (0 = product dispatch).  Every mode this library honours computes the
  * SAME result as the product (other ring depths, tile shapes, K splits, trace stamps); the ablation builds that drop parts of the
  * kernel -- and so return wrong numbers -- exist only in the laboratory build (`python -m ao_amd.build --lab` ->
- * tools/bin/_C_mi355_lab.so, compiled with -DAO_LAB; tools select it through AO_MI355_LIB).  Thread-local. */
+ * tools/bin/_C_mi355_lab.so, compiled with -DAO_LAB; tools select it through AO_MI355_LIB).  Thread-local.
+ * Modes 981 - 984 steer only the balanced grid of the one-row kernel and leave every other choice the product's: 981 never,
+ * 982 wherever the form allows (one row, K = 4096: any left-over tile count, for A/B and tests on small shapes), 983 / 984 the stamped
+ * profiling build (g = 128; [workgroups][8] u64 into the ao_int4_set_trace buffer) on today's grid / on the grid of 982. */
 int ao_int4_set_tuning(int waves_per_block, int mode);
 /* 1 when the calling thread has an ao_int4_set_tuning override set, else 0 (tests assert the product dispatch).  Host only. */
 int ao_int4_overridden(void);
@@ -155,8 +158,12 @@ int ao_gemm8_overridden(void);
 const char* ao_int4_mm_kernel_name(int64_t M, int64_t N, int64_t K, int group_size);
 /* Every field of that product route (host logic only): out[cap >= 10] = form (0 int4_mm_kernel, 1 int4_mm_rb_kernel, 2 int4_mm_w32_kernel),
  * rows of the per-tile build, ring depth, straight-line, waves, n-tiles, m-tiles, column groups (w32: 2 = 128 x 256 tiles), K parts,
- * producer form. */
+ * producer form.  With cap >= 11 also out[10] = the n-tiles the one-row kernel runs as two half-tile workgroups each (the balanced grid;
+ * 0 = one workgroup per tile; K parts stays 1). */
 int ao_int4_mm_route(int64_t M, int64_t N, int64_t K, int group_size, int32_t* out, int cap);
+/* The balanced grid's rule, host arithmetic only: of `tiles` n-tiles on `cus` compute units, how many the one-row kernel cuts in two
+ * (r = tiles mod cus when cus < tiles <= 4 cus and 2 r = cus, else 0; forced != 0, the rule of tuning mode 982: r whatever it is). */
+int ao_int4_balanced_halves(int64_t tiles, int cus, int forced);
 /* Which kernel ao_fp8_scaled_mm (int8 = 0) / ao_int8_scaled_mm (int8 = 1) dispatches a shape to: "dec8_kernel" (M <= 16), "mid8_kernel",
  * "stream8_kernel", "rb8_kernel" (up to 256 tiles of 128 x 128), "gemm8_p8h_kernel" / "gemm8_p8_kernel" / "gemm8_p8p_kernel" /
  * "gemm8_dma_kernel<...>" / "gemm8_kernel" (tiled), or "invalid".  The route the launch takes for 16-byte-aligned scales and output, whatever
@@ -187,7 +194,8 @@ int ao_grouped8_route(int entry, int64_t M_total, int64_t N, int64_t K, int64_t 
  * Host logic only.  DESIGN.md 4.9. */
 const char* ao_fp8_int4_kernel_name(int64_t M, int64_t N, int64_t K, int group_size);
 /* Profiling only: device buffer [workgroups][16] of s_memtime stamps written by the trace builds of the batched
- * kernels (int4: tuning mode 65S; fp8 rowwise mid-M kernel: whenever the pointer is set); NULL disables. */
+ * kernels (int4: tuning mode 65S; fp8 rowwise mid-M kernel: whenever the pointer is set); NULL disables.  The stamped one-row int4
+ * build (tuning modes 983 / 984) writes [workgroups][8] instead. */
 int ao_int4_set_trace(unsigned long long* trace_dev);
 
 /* ------------------------------------------------------------------------- *
