@@ -116,6 +116,9 @@ _SIGNATURES = {
     "ao_mx_linear_route": [_INT, _I64, _I64, _I64, _P, _INT],
     "ao_mx_linear_kernel_name": [_INT, _I64, _I64, _I64],
     "ao_mx_linear_set_form": [_INT],
+    "ao_wo8_linear": [_INT, _P, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _P],
+    "ao_wo8_linear_route": [_INT, _I64, _I64, _I64, _P, _INT],
+    "ao_wo8_linear_set_form": [_INT],
 }
 
 

@@ -111,6 +111,41 @@ __device__ __forceinline__ float epilogue8(float c, float sr, float sc, bool has
   return v;
 }
 
+// ---- weight-only linears (wo8_kernels.hip): bf16 activation x 8-bit weight ----------------------------------------------------------
+// 16 codes -> 16 bf16 weights (w0: codes 0..7, w1: 8..15), the operand the bf16 MFMA multiplies.
+//   int8 : bf16(q), exact (int8_tensor.py:347-351: qdata.t().to(bf16))
+//   e4m3 : bf16(f32(q) * s), the fp32 product rounded to fp32 and then to bf16 (float8_tensor.py:255-275 dequantize, :466)
+template <bool INT8>
+__device__ __forceinline__ void wo8_weight16(const u32x4& q, float s, u32x4& w0, u32x4& w1) {
+  const uint32_t c[4] = {q.x, q.y, q.z, q.w};
+  uint32_t o[8];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    if (INT8) {
+      const int v = (int)c[i];
+      o[2 * i] = pack_bf16x2((float)((v << 24) >> 24), (float)((v << 16) >> 24));
+      o[2 * i + 1] = pack_bf16x2((float)((v << 8) >> 24), (float)(v >> 24));
+    } else {
+      const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)c[i], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)c[i], true);
+      o[2 * i] = pack_bf16x2(lo.x * s, lo.y * s);
+      o[2 * i + 1] = pack_bf16x2(hi.x * s, hi.y * s);
+    }
+  }
+  w0 = u32x4{o[0], o[1], o[2], o[3]};
+  w1 = u32x4{o[4], o[5], o[6], o[7]};
+}
+// The output epilogue: the fp32 value the caller rounds to bf16 at its store (c: the fp32 sum).
+//   int8 : t = bf16(c);  u = bf16(f32(t) * f32(bf16(s)));  y = bf16(f32(u) + bias)   (int8_tensor.py:352-359: scale.to(m.dtype), y += bias)
+//   e4m3 : t = bf16(c);  y = bf16(f32(t) + bias)                                      (float8_tensor.py:466-468; s went into the weights)
+// Three roundings for int8, not epilogue8's one: every step is a bf16 tensor op in the reference.
+template <bool INT8>
+__device__ __forceinline__ float wo8_out(float c, float s, bool has_bias = false, float bias = 0.f) {
+  float v = round_bf16(c);
+  if (INT8) v = round_bf16(mul_f32_rn(v, round_bf16(s)));
+  if (has_bias) v += bias;
+  return v;
+}
+
 // ---- MXFP8 (to_mx, prototype/mx_formats/mx_tensor.py:228-409) --------------------------------------------------------------------
 // E8M0 scale exponent of one 32-block from its amax (:255-330; RCEIL :111-129, :161-225) and the reciprocal 2^(127 - e) built from the
 // E8M0 byte 254 - e (:132-158).  MODE: AO_MX_SCALE_FLOOR (0) / AO_MX_SCALE_RCEIL (1).

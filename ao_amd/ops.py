@@ -1262,3 +1262,70 @@ def mx_linear(x, b, b_scale, bias=None, fmt: int = MX_FMT_E2M1, scaling_mode="rc
         return torch.empty((0, n), dtype=torch.bfloat16, device=dev)
     aq, a_s = mx_quantize(x, fmt, scaling_mode)
     return mx_mm(aq, a_s, b, b_scale, bias, fmt)
+
+
+# ---- int8 / float8 weight-only linears (include/ao_mi355.h "WEIGHT-ONLY linears") ---------------------------------
+WO8_FMT_INT8 = 0
+WO8_FMT_E4M3 = 1
+WO8_KERNELS = {0: "invalid", 1: "wo8_stream_kernel", 2: "wo8_tile_kernel"}
+
+
+def wo8_route(fmt: int, m: int, n: int, k: int) -> dict:
+    """The route int8_wo_linear / fp8_wo_linear launch for a shape (host logic only, ao_wo8_linear_route); kernel "invalid" for shapes
+    nothing takes."""
+    out = (ctypes.c_int32 * 7)()
+    _lib.check(_lib.lib().ao_wo8_linear_route(int(fmt), int(m), int(n), int(k), out, 7))
+    kernel, waves, mt, tile_m, tile_n, gx, gy = list(out)
+    return {"kernel": WO8_KERNELS.get(kernel, "invalid"), "waves": waves, "m_tiles": mt, "tile_m": tile_m, "tile_n": tile_n,
+            "grid": (gx, gy)}
+
+
+def wo8_set_form(form: int) -> None:
+    """Measurement only: 0 the product route, 1 the streaming form, 2 the tiled form (calling thread)."""
+    _lib.check(_lib.lib().ao_wo8_linear_set_form(int(form)))
+
+
+def _wo_linear(name, fmt, x, wq, w_scale, bias, wdtype, out=None):
+    dev = _require_gpu(name, x, wq, w_scale, bias)
+    if x.dim() != 2 or x.dtype != torch.bfloat16:
+        raise RuntimeError(f"{name}: x must be a 2-D bfloat16 tensor, got {tuple(x.shape)} {x.dtype}")
+    if wq.dim() != 2 or wq.dtype != wdtype:
+        raise RuntimeError(f"{name}: weight must be a 2-D {wdtype} tensor [N, K]")
+    x = x.contiguous()
+    wq = wq.contiguous()
+    m, k = x.shape
+    n, k2 = wq.shape
+    if k != k2:
+        raise RuntimeError(f"{name}: K mismatch {k} vs {k2}")
+    w_scale = w_scale.reshape(-1).to(torch.float32).contiguous()
+    if w_scale.numel() not in (n, 1):
+        raise RuntimeError(f"{name}: weight scale must be per-row ([N]) or per-tensor (one element)")
+    if bias is not None:
+        bias = bias.to(torch.bfloat16).contiguous()
+        if bias.numel() != n:
+            raise RuntimeError(f"{name}: bias must have N elements")
+    if out is None:
+        y = torch.empty((m, n), dtype=torch.bfloat16, device=dev)
+    else:
+        y = out
+        if y.dtype != torch.bfloat16 or tuple(y.shape) != (m, n) or not y.is_contiguous() or y.device != dev:
+            raise RuntimeError(f"{name}: out must be a contiguous bfloat16 [{m}, {n}] tensor on {dev}")
+    with _on(dev):
+        _lib.check(_lib.lib().ao_wo8_linear(fmt, _ptr(x), _ptr(wq.view(torch.uint8) if wdtype != torch.int8 else wq), _ptr(w_scale),
+                                            w_scale.numel(), _ptr(bias), _ptr(y), m, n, k, _stream()))
+    return y
+
+
+def int8_wo_linear(x2, wq, w_scale, bias=None, out=None):
+    """Int8Tensor WEIGHT-ONLY F.linear on a 2-D bf16 activation (int8_tensor.py:346-359): bf16(bf16(bf16(x . q^T) * bf16(s)) + bias),
+    one launch, no activation cast.  w_scale: one per row or one element; out: an optional bf16 [M, N] tensor to write."""
+    return _wo_linear("int8_wo_linear", WO8_FMT_INT8, x2, wq, w_scale, bias, torch.int8, out)
+
+
+def fp8_wo_linear(x2, wq, w_scale, bias=None, out=None):
+    """Float8Tensor WEIGHT-ONLY F.linear on a 2-D bf16 activation (float8_tensor.py:460-469): bf16(bf16(x . dequantize(w)^T) + bias)
+    with the per-element bf16 rounding of dequantize (:255-275), one launch."""
+    return _wo_linear("fp8_wo_linear", WO8_FMT_E4M3, x2, wq, w_scale, bias, torch.float8_e4m3fn, out)
+
+
+__all__ += ["int8_wo_linear", "fp8_wo_linear", "wo8_route", "wo8_set_form"]

@@ -7,12 +7,14 @@ from .config import (  # noqa: F401
     config_to_dict,
     Float8DynamicActivationFloat8WeightConfig,
     Float8DynamicActivationInt4WeightConfig,
+    Float8WeightOnlyConfig,
     FqnToConfig,
     Int4ChooseQParamsAlgorithm,
     Int4PackingFormat,
     Int4WeightOnlyConfig,
     Int8DynamicActivationInt8WeightConfig,
     Int8StaticActivationInt8WeightConfig,
+    Int8WeightOnlyConfig,
     ModuleFqnToConfig,
 )
 from .granularity import PerGroup, PerRow, PerTensor  # noqa: F401

@@ -4,7 +4,7 @@ import enum
 from dataclasses import dataclass, field
 from typing import List, Optional, Union
 
-from .granularity import Granularity, PerRow, PerTensor
+from .granularity import Granularity, PerGroup, PerRow, PerTensor
 from .quant_primitives import MappingType
 
 
@@ -115,6 +115,50 @@ class Int8StaticActivationInt8WeightConfig(AOBaseConfig):
     def get_act_quant_kwargs(self):
         from .int8_tensor import QuantizeTensorToInt8Kwargs
         return QuantizeTensorToInt8Kwargs(granularity=self.granularity[0], mapping_type=self.act_mapping_type, reduce_range=self.reduce_range)
+
+
+@dataclass
+class Int8WeightOnlyConfig(AOBaseConfig):
+    """int8 weight-only, bf16 activations (reference quant_api.py:702-740; same fields in the same order).  granularity PerRow (default)
+    or PerTensor; PerGroup parses, so that a config upstream serialised decodes, and quantize_ refuses it.
+    `group_size` is version 1's field: it must stay None.  `set_inductor_config` (upstream default True) is accepted and does nothing:
+    no inductor setting bears on the HIP kernel."""
+
+    group_size: Optional[int] = None
+    granularity: Optional[Granularity] = field(default_factory=PerRow)
+    set_inductor_config: bool = True
+    version: int = 2
+
+    def __post_init__(self):
+        if self.version == 1:
+            raise ValueError("version 1 of Int8WeightOnlyConfig has been removed, please use version 2")
+        assert self.group_size is None, (
+            f"Only support version 2 with group_size=None, got {self.group_size}. Use granularity=PerGroup({self.group_size}) instead.")
+        assert isinstance(self.granularity, (PerTensor, PerRow, PerGroup)), (
+            f"granularity must be PerTensor, PerRow, or PerGroup, but got {self.granularity}")
+
+
+@dataclass
+class Float8WeightOnlyConfig(AOBaseConfig):
+    """float8 e4m3 weight-only, bf16 activations (reference quant_api.py:1031-1062; same fields in the same order).  granularity None =
+    PerRow (the reference's default), PerTensor; PerGroup parses and quantize_ refuses it.  `set_inductor_config` (upstream default True)
+    is accepted and does nothing."""
+
+    weight_dtype: object = None  # torch.float8_e4m3fn (None: that); gfx950 implements OCP e4m3fn only
+    set_inductor_config: bool = True
+    version: int = 2
+    granularity: Optional[Granularity] = None
+
+    def __post_init__(self):
+        import torch
+
+        if self.granularity is None:
+            self.granularity = PerRow()
+        assert isinstance(self.granularity, (PerTensor, PerRow, PerGroup)), (
+            f"granularity must be PerTensor, PerRow, or PerGroup, got {type(self.granularity)}")
+        self.weight_dtype = torch.float8_e4m3fn if self.weight_dtype is None else self.weight_dtype
+        if self.weight_dtype != torch.float8_e4m3fn:
+            raise NotImplementedError(f"Float8WeightOnlyConfig on MI355X implements float8_e4m3fn weights, got {self.weight_dtype}")
 
 
 class KernelPreference(str, enum.Enum):

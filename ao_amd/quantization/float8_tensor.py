@@ -1,4 +1,5 @@
-"""Float8Tensor: float8 e4m3 weight (PerRow or PerTensor scales) with dynamic activations of the same granularity, MI355X-native.
+"""Float8Tensor: float8 e4m3 weight (PerRow or PerTensor scales) with dynamic activations of the same granularity, or weight-only
+under bf16 activations (act_quant_kwargs=None: ao_wo8_linear), MI355X-native.
 
 Host-side mirror of torchao/quantization/quantize_/workflows/float8/float8_tensor.py for the branch
 SURVEY.md 8(a9, a10) scopes -- PerRow, KernelPreference TORCH/AUTO on AMD, i.e. what
@@ -259,6 +260,31 @@ def _(func, types, args, kwargs):
     return [_like(self, q, sc) for q, sc in zip(qs, scales)]
 
 
+def _weight_only_linear(x, w, bias, out_dtype):
+    """reference :460-469: torch.matmul(x, weight.dequantize()) + bias on the bf16 activation itself -- the weight rounded to bf16 element
+    by element (dequantize, :255-275) inside the one HIP launch (ops.fp8_wo_linear)."""
+    assert w.qdata.dim() == 2, "F.linear takes a 2-D weight: select an expert of a 3-D weight first (weight[e])"
+    if w.qdata.dtype != torch.float8_e4m3fn:
+        raise NotImplementedError(f"Float8Tensor on MI355X implements float8_e4m3fn only, got {w.qdata.dtype}")
+    if w.scale.numel() not in (1, w.qdata.shape[0]):
+        raise NotImplementedError("Float8Tensor weight-only linear on MI355X implements PerRow / PerTensor weight scales, got scale "
+                                  f"{tuple(w.scale.shape)} for weight {tuple(w.qdata.shape)}")
+    _require_bf16_activation(x, "Float8Tensor weight-only linear")
+    x2 = x.reshape(-1, x.shape[-1]).contiguous()
+    n = w.qdata.shape[0]
+    if x2.shape[0] == 0:
+        y = x2.new_zeros((0, n))
+    else:
+        from ..torch_ops import kernels
+
+        y = kernels(x2).fp8_wo_linear(x2, w.qdata, w.scale.reshape(-1), bias)
+        bias = None
+    y = y.reshape(*x.shape[:-1], n)
+    if bias is not None:
+        y = y + bias.to(y.dtype)
+    return y.to(out_dtype)
+
+
 def _float8_linear(x, w, bias):
     """reference :278-469 -> preprocess_data / preprocess_scale -> _scaled_mm(A row-major,
     B = W.t() column-major, scale_a [M,1], scale_b [1,N], bias, out_dtype, use_fast_accum)."""
@@ -267,10 +293,7 @@ def _float8_linear(x, w, bias):
     if w.act_pre_scale is not None:
         x = x * w.act_pre_scale
     if w.act_quant_kwargs is None:
-        raise NotImplementedError(
-            "Float8Tensor weight-only linear is not on the MI355X hot path (SURVEY.md section 8): "
-            "use Float8DynamicActivationFloat8WeightConfig"
-        )
+        return _weight_only_linear(x, w, bias, out_dtype)
     _check(w.act_quant_kwargs.granularity, w.act_quant_kwargs.float8_dtype)
     x2 = x.reshape(-1, x.shape[-1]).contiguous()
     n = w.qdata.shape[0]

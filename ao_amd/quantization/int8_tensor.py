@@ -1,4 +1,4 @@
-"""Int8Tensor: int8 weight with dynamic int8 activations, MI355X-native.
+"""Int8Tensor: int8 weight with dynamic int8 activations, or weight-only under bf16 activations, MI355X-native.
 
 Host-side mirror of torchao/quantization/quantize_/workflows/int8/int8_tensor.py (same attribute names, from_hp / linear /
 slice semantics for the path SURVEY.md 8(a7, a8) scopes): PerRow (default) or PerTensor symmetric weights; dynamic
@@ -176,6 +176,31 @@ implements = Int8Tensor.implements
 implements_torch_function = Int8Tensor.implements_torch_function
 
 
+def _weight_only_linear(x, w, bias, out_dtype):
+    """reference :336-359, the per-row / per-tensor weight-only branch: bf16(bf16(x . q^T) * bf16(scale)) + bias on the bf16 activation
+    itself, one HIP launch (ops.int8_wo_linear)."""
+    if w.qdata.dim() == 2 and w.scale.numel() not in (1, w.qdata.shape[0]):
+        raise NotImplementedError("Int8Tensor weight-only linear on MI355X implements PerRow / PerTensor weight scales, got scale "
+                                  f"{tuple(w.scale.shape)} for weight {tuple(w.qdata.shape)} (per-group int8 is outside the SURVEY.md section 8 path)")
+    if w.zero_point is not None:
+        raise NotImplementedError("Int8Tensor linear on MI355X takes symmetric weights (asymmetric is an ACTIVATION option in the reference)")
+    assert w.qdata.dim() == 2, "F.linear takes a 2-D weight: select an expert of a 3-D weight first (weight[e])"
+    _require_bf16_activation(x, "Int8Tensor weight-only linear")
+    x2 = x.reshape(-1, x.shape[-1]).contiguous()
+    n = w.qdata.shape[0]
+    if x2.shape[0] == 0:
+        y = x2.new_zeros((0, n))
+    else:
+        from ..torch_ops import kernels
+
+        y = kernels(x2).int8_wo_linear(x2, w.qdata, w.scale.reshape(-1), bias)
+        bias = None
+    y = y.reshape(*x.shape[:-1], n)
+    if bias is not None:
+        y = y + bias.to(y.dtype)
+    return y.to(out_dtype)
+
+
 @implements(aten.linear.default)
 @implements_torch_function(F.linear)
 def _(func, types, args, kwargs):
@@ -188,10 +213,7 @@ def _(func, types, args, kwargs):
     if w.act_pre_scale is not None:
         x = x * w.act_pre_scale
     if w.act_quant_kwargs is None:
-        raise NotImplementedError(
-            "Int8Tensor weight-only linear is not on the MI355X hot path (SURVEY.md section 8): "
-            "use Int8DynamicActivationInt8WeightConfig"
-        )
+        return _weight_only_linear(x, w, bias, out_dtype)
     act = w.act_quant_kwargs
     _check_granularity(act.granularity, "activation")
     if w.zero_point is not None:

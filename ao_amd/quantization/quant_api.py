@@ -14,12 +14,14 @@ from .config import (
     AOBaseConfig,
     Float8DynamicActivationFloat8WeightConfig,
     Float8DynamicActivationInt4WeightConfig,
+    Float8WeightOnlyConfig,
     Int4ChooseQParamsAlgorithm,
     Int4PackingFormat,
     Int4WeightOnlyConfig,
     Int8DynamicActivationInt8WeightConfig,
     FqnToConfig,
     Int8StaticActivationInt8WeightConfig,
+    Int8WeightOnlyConfig,
 )
 
 logger = logging.getLogger(__name__)
@@ -304,3 +306,53 @@ def _float8_dynamic_activation_float8_weight_transform(module, config, *, parame
     )
     setattr(module, parameter_name, nn.Parameter(new_weight, requires_grad=False))
     return module
+
+
+def _refuse_per_group(config):
+    from .granularity import PerGroup
+
+    if isinstance(config.granularity, PerGroup):
+        raise NotImplementedError(
+            f"{type(config).__name__}(granularity={config.granularity}): per-group 8-bit weights are not implemented on MI355X (DESIGN.md "
+            "section 7): the weight-only kernels apply one scale per output row or per tensor; use PerRow() or PerTensor()")
+
+
+def _set_weight_only(module, parameter_name, new_weight):
+    """The quantized parameter, and an extra_repr that names it (the reference's handlers do the same through _module_extra_repr)."""
+    import types
+
+    setattr(module, parameter_name, nn.Parameter(new_weight, requires_grad=False))
+    original = type(module).extra_repr
+
+    def extra_repr(self):
+        w = getattr(self, parameter_name)
+        return f"{original(self)}, {parameter_name}={type(w).__name__}({w._quantization_type()})"
+
+    module.extra_repr = types.MethodType(extra_repr, module)
+    return module
+
+
+@register_quantize_module_handler(Int8WeightOnlyConfig)
+def _int8_weight_only_transform(module, config, *, parameter_name="weight"):
+    """reference quant_api.py:743-770: Int8Tensor.from_hp(weight, granularity) with no activation quantization; F.linear then runs the
+    weight-only kernel on the bf16 activation."""
+    from .int8_tensor import Int8Tensor
+
+    assert hasattr(module, parameter_name), (
+        f"applying int8 weight only quant requires module to have {parameter_name} attribute but {module} does not have one")
+    assert config.version == 2, f"Unexpected version: {config.version}"
+    _refuse_per_group(config)
+    return _set_weight_only(module, parameter_name, Int8Tensor.from_hp(getattr(module, parameter_name), granularity=config.granularity))
+
+
+@register_quantize_module_handler(Float8WeightOnlyConfig)
+def _float8_weight_only_transform(module, config, *, parameter_name="weight"):
+    """reference quant_api.py:1065-1100: Float8Tensor.from_hp(weight, float8_dtype, granularity) with no activation quantization."""
+    from .float8_tensor import Float8Tensor
+
+    assert hasattr(module, parameter_name), (
+        f"applying float8 weight only quant requires module to have {parameter_name} attribute but {module} does not have one")
+    assert config.version == 2, f"Unexpected version: {config.version}"
+    _refuse_per_group(config)
+    new_weight = Float8Tensor.from_hp(getattr(module, parameter_name), float8_dtype=config.weight_dtype, granularity=config.granularity)
+    return _set_weight_only(module, parameter_name, new_weight)

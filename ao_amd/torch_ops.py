@@ -73,6 +73,8 @@ _lib_def.define("mxfp8_grouped_mm(Tensor a, Tensor a_scale, Tensor b, Tensor b_s
 _lib_def.define("mxfp4_quantize(Tensor x, str scaling_mode) -> (Tensor, Tensor)")
 _lib_def.define("mx_mm(Tensor a, Tensor a_scale, Tensor b, Tensor b_scale, Tensor? bias, int fmt) -> Tensor")
 _lib_def.define("mx_linear(Tensor x, Tensor b, Tensor b_scale, Tensor? bias, int fmt, str scaling_mode) -> Tensor")
+_lib_def.define("int8_wo_linear(Tensor x, Tensor wq, Tensor w_scale, Tensor? bias) -> Tensor")
+_lib_def.define("fp8_wo_linear(Tensor x, Tensor wq, Tensor w_scale, Tensor? bias) -> Tensor")
 # same schemas as torchao::fused_pad_token_groups / fused_unpad_token_groups (kernels/mxfp8/quant.py:1244-1246, 1319-1321)
 _lib_def.define("fused_pad_token_groups(Tensor inputs, Tensor offsets, int alignment_size) -> (Tensor, Tensor, Tensor)")
 _lib_def.define(
@@ -102,6 +104,8 @@ _lib_impl.impl("mxfp8_grouped_mm", ops.mxfp8_grouped_mm)
 _lib_impl.impl("mxfp4_quantize", lambda x, mode: ops.mxfp4_quantize(x, mode))
 _lib_impl.impl("mx_mm", ops.mx_mm)
 _lib_impl.impl("mx_linear", lambda x, b, b_scale, bias, fmt, mode: ops.mx_linear(x, b, b_scale, bias, fmt, mode))
+_lib_impl.impl("int8_wo_linear", lambda x, wq, w_scale, bias: ops.int8_wo_linear(x, wq, w_scale, bias))
+_lib_impl.impl("fp8_wo_linear", lambda x, wq, w_scale, bias: ops.fp8_wo_linear(x, wq, w_scale, bias))
 _lib_impl.impl("fused_pad_token_groups", ops.fused_pad_token_groups)
 _lib_impl.impl("fused_unpad_token_groups", ops.fused_unpad_token_groups)
 
@@ -219,6 +223,16 @@ def _(x, b, b_scale, bias, fmt, scaling_mode):
     return x.new_empty((x.shape[0], b.shape[0]), dtype=torch.bfloat16)
 
 
+@torch.library.register_fake("ao_mi355::int8_wo_linear")
+def _(x, wq, w_scale, bias):
+    return x.new_empty((x.shape[0], wq.shape[0]), dtype=torch.bfloat16)
+
+
+@torch.library.register_fake("ao_mi355::fp8_wo_linear")
+def _(x, wq, w_scale, bias):
+    return x.new_empty((x.shape[0], wq.shape[0]), dtype=torch.bfloat16)
+
+
 @torch.library.register_fake("ao_mi355::fused_pad_token_groups")
 def _(inputs, offsets, alignment_size):
     rows = inputs.shape[0] + offsets.shape[0] * alignment_size
@@ -241,7 +255,7 @@ _lib_autograd = torch.library.Library("ao_mi355", "IMPL", "Autograd")
 for _name in ("weight_int4pack_mm", "convert_weight_to_int4pack", "int8_scaled_mm", "fp8_scaled_mm", "int8_dynamic_linear", "fp8_dynamic_linear",
               "int8_linear", "fp8_linear", "int8_linear_asym", "int8_linear_tensorwise", "fp8_linear_tensorwise", "fp8_linear_clamped",
               "int8_linear_static", "fp8_int4_linear", "fp8_int4_act_linear", "int8_quantize_rowwise", "fp8_quantize_rowwise", "mxfp8_quantize", "mxfp8_grouped_mm",
-              "fused_pad_token_groups", "fused_unpad_token_groups", "mxfp4_quantize", "mx_mm", "mx_linear"):
+              "fused_pad_token_groups", "fused_unpad_token_groups", "mxfp4_quantize", "mx_mm", "mx_linear", "int8_wo_linear", "fp8_wo_linear"):
     _lib_autograd.impl(_name, torch.library.fallthrough_kernel)
 
 

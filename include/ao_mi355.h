@@ -601,6 +601,28 @@ const char* ao_mx_linear_kernel_name(int fmt, int64_t M, int64_t N, int64_t K);
  * report the forced form. */
 int ao_mx_linear_set_form(int form);
 
+/* ---- int8 / float8 WEIGHT-ONLY linears: bf16 activation x 8-bit weight (wo8_kernels.hip) ----------------------------------------------
+ * Replaces the weight-only branch of Int8Tensor's F.linear (quantize_/workflows/int8/int8_tensor.py:346-359, what Int8WeightOnlyConfig,
+ * quant_api.py:702-770, produces) and of Float8Tensor's (quantize_/workflows/float8/float8_tensor.py:460-469 with dequantize :255-275,
+ * Float8WeightOnlyConfig, quant_api.py:1031-1100).  x bf16 [M, K]; wq int8 or float8_e4m3fn [N, K], K-contiguous; w_scale fp32, one per
+ * row (scale_count = N) or one for the tensor (scale_count = 1); bias bf16 [N] or null; out bf16 [M, N].  fp32 accumulation, every
+ * bf16(.) round-to-nearest-even:
+ *   int8: t = bf16(sum_k x q);  u = bf16(f32(t) f32(bf16(s[n])));  y = bf16(f32(u) + bias[n])
+ *   e4m3: w = bf16(f32(q) s[n]) per element;  t = bf16(sum_k x w);  y = bf16(f32(t) + bias[n])
+ * M >= 0 (M = 0: OK, nothing launched), N >= 1, K a positive multiple of 16 up to 2^31 - 1024, M K and N K below 2^31.  x and wq 16-byte aligned; w_scale
+ * 4-byte, bias and out 2-byte aligned. */
+#define AO_WO8_FMT_INT8 0
+#define AO_WO8_FMT_E4M3 1
+int ao_wo8_linear(int fmt, const uint16_t* x, const void* wq, const float* w_scale, int64_t scale_count, const uint16_t* bias,
+                  uint16_t* out, int64_t M, int64_t N, int64_t K, void* stream);
+/* The route ao_wo8_linear launches (host logic only; the dispatch of int8_tensor.py:336-359 / float8_tensor.py:460-469 has one path, this
+ * library two forms): out[cap >= 7] = kernel (0 = no kernel takes the shape, 1 wo8_stream_kernel, 2 wo8_tile_kernel), waves per
+ * workgroup, m-tiles of 16 per workgroup, tile rows, tile columns, grid x, grid y. */
+int ao_wo8_linear_route(int fmt, int64_t M, int64_t N, int64_t K, int32_t* out, int cap);
+/* Measurement only (no reference counterpart: int8_tensor.py:346-359 / float8_tensor.py:460-469 have one path): force the form of the
+ * calling thread's weight-only linears (0 the product route, 1 streaming, 2 tiled); the route query reports the forced form. */
+int ao_wo8_linear_set_form(int form);
+
 #ifdef __cplusplus
 }
 #endif
