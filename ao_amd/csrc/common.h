@@ -69,6 +69,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x8 __attribute__((ext_vector_type(8)));
 typedef int i32x16 __attribute__((ext_vector_type(16)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -76,6 +77,10 @@ typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int kWave = 64;  // gfx950 wavefront
+
+// workgroup barrier that orders LDS traffic only: __syncthreads() carries a workgroup-scope release fence, which on gfx9 means
+// s_waitcnt vmcnt(0) -- it would drain the weight loads a streaming kernel keeps in flight across its barriers
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 __device__ __forceinline__ float bits_to_f32(uint32_t u) { return __uint_as_float(u); }
 __device__ __forceinline__ uint32_t f32_to_bits(float f) { return __float_as_uint(f); }

@@ -25,14 +25,13 @@
 #include "common.h"
 #include "gemm8_route.h"
 #include "quant_math.h"
+#include "stream_blocks.h"
 
 #include <algorithm>
 #include <type_traits>
 
 namespace ao {
 namespace {
-
-typedef int i32x8 __attribute__((ext_vector_type(8)));
 
 struct Dec8Args {
   const void* x;           // DYN: bf16 [M][K];  else codes [M][K]
@@ -43,10 +42,6 @@ struct Dec8Args {
   uint16_t* out;           // [M][N] bf16
   int M, N, K;
 };
-
-// workgroup barrier that orders LDS traffic only: __syncthreads() carries a workgroup-scope release fence, which on gfx9 means
-// s_waitcnt vmcnt(0) -- it would drain the weight ring that is in flight across every barrier of this kernel
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 constexpr int kSlabStride = 144;            // bytes between the 16 rows of a wave's transposition slab
 constexpr int kSlab = 16 * kSlabStride;     // 2304 B
@@ -136,33 +131,8 @@ __global__ __launch_bounds__(1024) void dec8_kernel(Dec8Args p) {
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (wave-private codes: no barrier)
   } else if constexpr (DYN) {
-    // dyn8_kernel's two passes over the L2-resident activation, then the ring
-    const int nvec = p.K >> 3;
-    const uint16_t* x = reinterpret_cast<const uint16_t*>(p.x);
-    for (int r = 0; r < p.M; ++r) {
-      const u32x4* xr = reinterpret_cast<const u32x4*>(x + (size_t)r * p.K);
-      float m = 0.f;
-      bool has_nan = false;
-      for (int i = tid; i < nvec; i += nthreads) m = fmaxf(m, amax8(xr[i], has_nan));
-      if (has_nan) m = INFINITY;
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
-      if (lane == 0) wmax[wave * 16 + r] = m;
-    }
-    lds_barrier();
-    if (tid < p.M) {
-      float m = 0.f;
-      for (int w = 0; w < nwaves; ++w) m = fmaxf(m, wmax[w * 16 + tid]);
-      rs[tid] = INT8 ? int8_row_scale(m) : fp8_row_scale(m);
-    }
-    lds_barrier();
-    for (int r = 0; r < p.M; ++r) {
-      const u32x4* xr = reinterpret_cast<const u32x4*>(x + (size_t)r * p.K);
-      const float s = rs[r];
-      const float inv = 1.0f / s;
-      for (int i = tid; i < nvec; i += nthreads)
-        *reinterpret_cast<u32x2*>(xq + r * stride + i * 8) = INT8 ? int8_quant8(xr[i], inv) : fp8_quant8(xr[i], s);
-    }
+    // the workgroup-wide two-pass cast (dyn8_kernel's), then the ring
+    cast_rows_to_lds<INT8, true>(reinterpret_cast<const uint16_t*>(p.x), p.M, p.K, xq, stride, wmax, rs);
     issue_ring();
   } else if constexpr (XFAST) {
     // codes [M][K]: a wave copies the part of every row that ITS k-run multiplies (M x DEPTH x 8 vectors of 16 bytes, at most kXV
@@ -212,16 +182,7 @@ __global__ __launch_bounds__(1024) void dec8_kernel(Dec8Args p) {
     }
     const u32x4 a0 = *reinterpret_cast<const u32x4*>(arow + rel * 128);
     const u32x4 a1 = *reinterpret_cast<const u32x4*>(arow + rel * 128 + 64);
-    if constexpr (INT8) {
-      i32x4 c = __builtin_bit_cast(i32x4, acc);
-      c = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, a0), __builtin_bit_cast(i32x4, b0), c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, a1), __builtin_bit_cast(i32x4, b1), c, 0, 0, 0);
-      acc = __builtin_bit_cast(f32x4, c);
-    } else {
-      const i32x8 af = {(int)a0.x, (int)a0.y, (int)a0.z, (int)a0.w, (int)a1.x, (int)a1.y, (int)a1.z, (int)a1.w};
-      const i32x8 bf = {(int)b0.x, (int)b0.y, (int)b0.z, (int)b0.w, (int)b1.x, (int)b1.y, (int)b1.z, (int)b1.w};
-      acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af, bf, acc, 0, 0, 0, 127, 0, 127);
-    }
+    acc = mfma8_k128<INT8>(a0, a1, b0, b1, acc);
   };
   if constexpr (!LOOP) {
 #pragma unroll
@@ -250,10 +211,7 @@ __global__ __launch_bounds__(1024) void dec8_kernel(Dec8Args p) {
   }
 
   // ---- 3. split-K reduction across waves (wave order: reproducible), scales, store
-  {
-    float* r = red + (size_t)wave * 256 + (kq * 4) * 16 + nl;  // [row 16][col 16]
-    r[0] = acc.x; r[16] = acc.y; r[32] = acc.z; r[48] = acc.w;
-  }
+  park_tile(red + (size_t)wave * 256, kq, nl, acc);
   lds_barrier();
   for (int idx = tid; idx < p.M * 16; idx += nthreads) {  // (workgroups of 1 .. 3 waves have fewer threads than outputs)
     const int row = idx >> 4, col = idx & 15;

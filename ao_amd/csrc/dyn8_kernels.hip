@@ -14,6 +14,7 @@
 #include "common.h"
 #include "gemm8_route.h"
 #include "quant_math.h"
+#include "stream_blocks.h"
 
 #include <algorithm>
 
@@ -25,8 +26,6 @@ int dec8_dynamic(bool int8, const uint16_t* x, const void* wq, const float* w_sc
 int mid8_dynamic(bool int8, const uint16_t* x, const void* b, const float* scale_b, const uint16_t* bias, uint16_t* y, int64_t M, int64_t N, int64_t K,
                  const Mid8Plan& plan, hipStream_t stream);
 namespace {
-
-typedef int i32x8 __attribute__((ext_vector_type(8)));
 
 struct Dyn8Args {
   const uint16_t* x;       // [M][K] bf16
@@ -51,33 +50,8 @@ __global__ __launch_bounds__(512) void dyn8_kernel(Dyn8Args p) {
   float* rs = wmax + nwaves * kMaxRows;                              // [16] row scales
   float* red = rs + kMaxRows;                                        // [nwaves][256] split-K partials
 
-  // ---- 1. per-row amax -> scale (every workgroup, redundantly: the activation is L2-resident and tiny)
-  const int nvec = p.K >> 3;  // 8 bf16 per 16 B
-  for (int r = 0; r < p.M; ++r) {
-    const u32x4* xr = reinterpret_cast<const u32x4*>(p.x + (size_t)r * p.K);
-    float m = 0.f;
-    bool has_nan = false;
-    for (int i = threadIdx.x; i < nvec; i += blockDim.x) m = fmaxf(m, amax8(xr[i], has_nan));
-    if (has_nan) m = INFINITY;  // (NaN rows are outside the contract, as in the stand-alone cast)
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
-    if (lane == 0) wmax[wave * kMaxRows + r] = m;
-  }
-  __syncthreads();
-  if (threadIdx.x < p.M) {
-    float m = 0.f;
-    for (int w = 0; w < nwaves; ++w) m = fmaxf(m, wmax[w * kMaxRows + threadIdx.x]);
-    rs[threadIdx.x] = INT8 ? int8_row_scale(m) : fp8_row_scale(m);
-  }
-  __syncthreads();
-  // ---- 2. cast into LDS
-  for (int r = 0; r < p.M; ++r) {
-    const u32x4* xr = reinterpret_cast<const u32x4*>(p.x + (size_t)r * p.K);
-    const float s = rs[r];
-    const float inv = 1.0f / s;
-    for (int i = threadIdx.x; i < nvec; i += blockDim.x)
-      *reinterpret_cast<u32x2*>(xq + r * stride + i * 8) = INT8 ? int8_quant8(xr[i], inv) : fp8_quant8(xr[i], s);
-  }
+  // ---- 1. + 2. per-row amax -> scale, then the cast into LDS (every workgroup, redundantly: the activation is L2-resident and tiny)
+  cast_rows_to_lds<INT8, false>(p.x, p.M, p.K, xq, stride, wmax, rs);
   __syncthreads();
 
   // ---- 3. stream this n-tile's weights past the codes
@@ -97,23 +71,11 @@ __global__ __launch_bounds__(512) void dyn8_kernel(Dyn8Args p) {
     u32x4 a0 = *reinterpret_cast<const u32x4*>(arow + ks * 128);
     u32x4 a1 = *reinterpret_cast<const u32x4*>(arow + ks * 128 + 64);
     if (!valid) { a0 = u32x4{0, 0, 0, 0}; a1 = u32x4{0, 0, 0, 0}; }
-    if constexpr (INT8) {
-      i32x4 c = __builtin_bit_cast(i32x4, acc);
-      c = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, a0), __builtin_bit_cast(i32x4, b0), c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, a1), __builtin_bit_cast(i32x4, b1), c, 0, 0, 0);
-      acc = __builtin_bit_cast(f32x4, c);
-    } else {
-      const i32x8 af = {(int)a0.x, (int)a0.y, (int)a0.z, (int)a0.w, (int)a1.x, (int)a1.y, (int)a1.z, (int)a1.w};
-      const i32x8 bf = {(int)b0.x, (int)b0.y, (int)b0.z, (int)b0.w, (int)b1.x, (int)b1.y, (int)b1.z, (int)b1.w};
-      acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af, bf, acc, 0, 0, 0, 127, 0, 127);
-    }
+    acc = mfma8_k128<INT8>(a0, a1, b0, b1, acc);
   }
 
   // ---- 4. split-K reduction across waves (wave order: reproducible), scales, store
-  {
-    float* r = red + (size_t)wave * 256 + (kq * 4) * 16 + (lane & 15);  // [row 16][col 16]
-    r[0] = acc.x; r[16] = acc.y; r[32] = acc.z; r[48] = acc.w;
-  }
+  park_tile(red + (size_t)wave * 256, kq, lane & 15, acc);
   __syncthreads();
   for (int idx = threadIdx.x; idx < 256; idx += blockDim.x) {
     const int row = idx >> 4, col = idx & 15;

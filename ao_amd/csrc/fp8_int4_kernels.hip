@@ -21,6 +21,7 @@
 
 #include "common.h"
 #include "quant_math.h"
+#include "stream_blocks.h"
 
 namespace ao {
 namespace {
@@ -186,7 +187,6 @@ __global__ __launch_bounds__(512) void fp8_int4_mm_kernel(const uint8_t* __restr
     for (int d = 0; d < DEPTH; ++d) issue(st[d], min(kb0 + d, kb_last));
     __builtin_amdgcn_sched_barrier(0);  // nothing that waits for an earlier load may move above the ring's requests
   };
-  auto lds_barrier = [] { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };  // LDS-only: must not drain the ring
   if constexpr (FUSE == 1) {
     // M == 1: this wave's k-run is blocks [kb0, kb1): (kb1 - kb0) x 16 vectors of 8 bf16, at most XW per lane (host: <= 16 blocks per wave)
     constexpr int XW = 4;
@@ -272,10 +272,7 @@ __global__ __launch_bounds__(512) void fp8_int4_mm_kernel(const uint8_t* __restr
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-      float* r = red + ((wave * MT + mt) * NT + nt) * 256 + (kq * 4) * 16 + (lane & 15);
-      r[0] = acc[mt][nt].x; r[16] = acc[mt][nt].y; r[32] = acc[mt][nt].z; r[48] = acc[mt][nt].w;
-    }
+    for (int nt = 0; nt < NT; ++nt) park_tile(red + ((wave * MT + mt) * NT + nt) * 256, kq, lane & 15, acc[mt][nt]);
   __syncthreads();
   const int tid = threadIdx.x;
   for (int e = tid; e < MT * NT * 256; e += blockDim.x) {

@@ -34,7 +34,6 @@ int fp8_rowwise_stream(const uint8_t* a, const uint8_t* b, const float* scale_a,
 
 namespace {
 
-typedef int i32x8 __attribute__((ext_vector_type(8)));
 
 constexpr int BM = 128, BN = 128, BK = 128;  // BK in bytes == elements
 constexpr int LDS_STRIDE = BK + 16;          // 144 B

@@ -28,7 +28,6 @@
 namespace ao {
 namespace {
 
-typedef int i32x8 __attribute__((ext_vector_type(8)));
 
 enum P8Epi { P8_INT8_SCALED = 0, P8_INT32 = 1, P8_FP8_ROWWISE = 2, P8_FP8_RAW = 3 };
 

@@ -24,14 +24,13 @@
 #include "gemm8_route.h"
 #include "quant_math.h"
 #include "splitk.h"
+#include "stream_blocks.h"
 
 #include <algorithm>
 #include <type_traits>
 
 namespace ao {
 namespace {
-
-typedef int i32x8 __attribute__((ext_vector_type(8)));
 
 struct Mid8Args {
   const uint8_t* a;        // [M][K] codes
@@ -44,8 +43,6 @@ struct Mid8Args {
   float* ws;               // split-K parts
   unsigned* tickets;
 };
-
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 constexpr int kRow = 144;          // LDS bytes per 128-byte row (weights slab and activation tile): 16 rows hit 64 distinct banks
 constexpr int kSlab = 16 * kRow;   // 2304 B per wave
@@ -143,16 +140,7 @@ __global__ __launch_bounds__(512, 4) void mid8_kernel(Mid8Args p) {
       for (int mt = 0; mt < MT; ++mt) {
         const u32x4 a0 = *reinterpret_cast<const u32x4*>(A + mt * 16 * kRow);
         const u32x4 a1 = *reinterpret_cast<const u32x4*>(A + mt * 16 * kRow + 64);
-        if constexpr (INT8) {  // acc holds int32 bit patterns
-          i32x4 c = __builtin_bit_cast(i32x4, acc[mt]);
-          c = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, a0), __builtin_bit_cast(i32x4, b0), c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, a1), __builtin_bit_cast(i32x4, b1), c, 0, 0, 0);
-          acc[mt] = __builtin_bit_cast(f32x4, c);
-        } else {
-          const i32x8 af = {(int)a0.x, (int)a0.y, (int)a0.z, (int)a0.w, (int)a1.x, (int)a1.y, (int)a1.z, (int)a1.w};
-          const i32x8 bf = {(int)b0.x, (int)b0.y, (int)b0.z, (int)b0.w, (int)b1.x, (int)b1.y, (int)b1.z, (int)b1.w};
-          acc[mt] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af, bf, acc[mt], 0, 0, 0, 127, 0, 127);
-        }
+        acc[mt] = mfma8_k128<INT8>(a0, a1, b0, b1, acc[mt]);  // (INT8: acc holds int32 bit patterns)
       }
       // (the fence keeps a step's MFMAs inside the step: left alone the scheduler carries accumulators across the barrier in renamed
       // registers, and the fused MT = 8 forms spilled their weight ring at the 128-VGPR budget of four waves per SIMD)

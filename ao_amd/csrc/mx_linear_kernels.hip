@@ -12,7 +12,8 @@
 //   e2m1: lane group kq holds k = 32 kq .. +31 (four VGPRs, element 2i in the low nibble of byte i -- the packed layout of to_mx), so one
 //         lane owns one whole block; tests/test_mx_linear_gpu.py pins this map with one-hot operands.
 //
-// Two forms, one route (mx_route) read by the launch and by ao_mx_linear_route / ao_mx_linear_kernel_name:
+// Two forms, one route (mx_route: this family's shape check, seams and forced form over the plans of two_form_route.h)
+// read by the launch and by ao_mx_linear_route / ao_mx_linear_kernel_name:
 //   mx_linear_stream_kernel: the weight is streamed once; a workgroup owns 16 columns and splits K over its waves, the partial tiles
 //     meet in LDS in wave order.  The bf16 activation may be cast inside (CAST): the lanes that feed the A operand cast their blocks with
 //     the stand-alone casts' functions (quant_math.h: mx_cast4, mx_encode8), so the codes and scales are those of the cast kernels and
@@ -22,11 +23,11 @@
 //     lane), two stages; rows / columns past the matrix and k past K read as zero through the buffer's range check.
 #include "common.h"
 #include "quant_math.h"
+#include "stream_blocks.h"
+#include "two_form_route.h"
 
 namespace ao {
 namespace {
-
-typedef int i32x8 __attribute__((ext_vector_type(8)));
 
 constexpr int kFmtE4M3 = AO_MX_FMT_E4M3;  // MFMA format codes (cbsz / blgp)
 constexpr int kFmtE2M1 = AO_MX_FMT_E2M1;
@@ -39,14 +40,6 @@ constexpr int kFmtE2M1 = AO_MX_FMT_E2M1;
 constexpr int kStreamMaxRowsE4M3 = 64;
 constexpr int kStreamMaxRowsE2M1 = 32;
 
-struct MxRoute {
-  int kernel = 0;  // 0 invalid, 1 mx_linear_stream_kernel, 2 mx_linear_tile_kernel
-  int waves = 0;   // waves per workgroup
-  int mt = 0;      // m-tiles of 16 per workgroup (stream form)
-  int tile_m = 0, tile_n = 0;
-  int grid_x = 0, grid_y = 0;
-};
-
 thread_local int g_form = 0;  // ao_mx_linear_set_form: 0 the product route, 1 stream, 2 tile
 
 bool mx_shape_ok(int fmt, int64_t M, int64_t N, int64_t K) {
@@ -57,36 +50,11 @@ bool mx_shape_ok(int fmt, int64_t M, int64_t N, int64_t K) {
   return M * kb < (1ll << 31) && N * kb < (1ll << 31) && M * N < (1ll << 40);
 }
 
-MxRoute mx_route(int fmt, int64_t M, int64_t N, int64_t K) {
-  MxRoute r;
-  if (!mx_shape_ok(fmt, M, N, K)) return r;
+// kernel 1: mx_linear_stream_kernel, 2: mx_linear_tile_kernel (128 x 128 tiles)
+TwoFormRoute mx_route(int fmt, int64_t M, int64_t N, int64_t K) {
+  if (!mx_shape_ok(fmt, M, N, K)) return TwoFormRoute{};
   const int seam = fmt == kFmtE2M1 ? kStreamMaxRowsE2M1 : kStreamMaxRowsE4M3;
-  const int form = g_form != 0 ? g_form : (M <= seam ? 1 : 2);
-  if (form == 1) {
-    const int64_t ntiles = (N + 15) / 16;
-    const int64_t ksteps = (K + 127) / 128;
-    r.kernel = 1;
-    r.mt = M <= 16 ? 1 : (M <= 32 ? 2 : 4);
-    // enough waves in flight to cover HBM latency on 256 CUs: fewer column tiles, more K parts per tile; no wave without a k step
-    int w = ntiles >= 1024 ? 4 : (ntiles >= 256 ? 8 : 16);
-    if (r.mt == 4 && w > 8) w = 8;  // the meeting buffer: waves x m-tiles x 1 KiB of static LDS
-    while (w > 1 && w > ksteps) w >>= 1;
-    r.waves = w;
-    r.tile_m = 16 * r.mt;
-    r.tile_n = 16;
-    r.grid_x = (int)ntiles;
-    r.grid_y = (int)std::max<int64_t>(1, (M + r.tile_m - 1) / r.tile_m);
-  } else {
-    r.kernel = 2;
-    r.waves = 4;
-    r.mt = 4;
-    r.tile_m = 128;
-    r.tile_n = 128;
-    r.grid_x = (int)((N + 127) / 128);
-    r.grid_y = (int)((M + 127) / 128);
-  }
-  if (r.grid_y > 65535) r.kernel = 0;
-  return r;
+  return two_form_route(g_form != 0 ? g_form : (M <= seam ? 1 : 2), M, N, K, 128);
 }
 
 struct MxArgs {
@@ -105,9 +73,7 @@ __device__ __forceinline__ u32x4 ld16(const uint16_t* p) { return *reinterpret_c
 
 template <int FMT>
 __device__ __forceinline__ f32x4 mx_mfma(const u32x4& a0, const u32x4& a1, const u32x4& b0, const u32x4& b1, f32x4 c, int sa, int sb) {
-  const i32x8 af = {(int)a0.x, (int)a0.y, (int)a0.z, (int)a0.w, (int)a1.x, (int)a1.y, (int)a1.z, (int)a1.w};
-  const i32x8 bf = {(int)b0.x, (int)b0.y, (int)b0.z, (int)b0.w, (int)b1.x, (int)b1.y, (int)b1.z, (int)b1.w};
-  return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af, bf, c, FMT, FMT, 0, sa, 0, sb);
+  return mfma8_k128<false, FMT>(a0, a1, b0, b1, c, sa, sb);
 }
 
 // One lane's operand of k step `step` for row `row` of a codes matrix (rows past `rows` and blocks past K read as zero, scale 127).
@@ -365,29 +331,19 @@ __global__ __launch_bounds__(256) void mxfp4_quant_kernel(const uint16_t* __rest
 }
 
 // ---- launches -------------------------------------------------------------------------------------------------------------------
-template <int FMT, int CAST, int MT>
-int launch_stream_mt(const MxRoute& r, const MxArgs& a, hipStream_t st) {
-  const dim3 grid(r.grid_x, r.grid_y);
-  switch (r.waves) {
-    case 1: ao::launch(mx_linear_stream_kernel<FMT, CAST, MT, 1>, grid, dim3(64), 0, st, a); break;
-    case 2: ao::launch(mx_linear_stream_kernel<FMT, CAST, MT, 2>, grid, dim3(128), 0, st, a); break;
-    case 4: ao::launch(mx_linear_stream_kernel<FMT, CAST, MT, 4>, grid, dim3(256), 0, st, a); break;
-    case 8: ao::launch(mx_linear_stream_kernel<FMT, CAST, MT, 8>, grid, dim3(512), 0, st, a); break;
-    default: ao::launch(mx_linear_stream_kernel<FMT, CAST, MT, 16>, grid, dim3(1024), 0, st, a); break;
-  }
+template <int FMT, int CAST>
+int launch_stream(const TwoFormRoute& r, const MxArgs& a, hipStream_t st) {
+  if (int rc = with_stream_form<true>("mx_linear_stream_kernel", r, [&](auto mt, auto waves) {
+        constexpr int MT = decltype(mt)::value, WAVES = decltype(waves)::value;
+        ao::launch(mx_linear_stream_kernel<FMT, CAST, MT, WAVES>, dim3(r.grid_x, r.grid_y), dim3(64 * WAVES), 0, st, a);
+      }))
+    return rc;
   AO_LAUNCH_CHECK("mx_linear_stream_kernel launch");
   return AO_OK;
 }
 
-template <int FMT, int CAST>
-int launch_stream(const MxRoute& r, const MxArgs& a, hipStream_t st) {
-  if (r.mt == 1) return launch_stream_mt<FMT, CAST, 1>(r, a, st);
-  if (r.mt == 2) return launch_stream_mt<FMT, CAST, 2>(r, a, st);
-  return launch_stream_mt<FMT, CAST, 4>(r, a, st);
-}
-
 template <int FMT>
-int launch_tile(const MxRoute& r, const MxArgs& a, hipStream_t st) {
+int launch_tile(const TwoFormRoute& r, const MxArgs& a, hipStream_t st) {
   constexpr size_t smem = 2 * TileCfg<FMT>::STAGE;
   auto kern = mx_linear_tile_kernel<FMT>;
   if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), smem, "hipFuncSetAttribute(mx_linear_tile_kernel)")) return rc;
@@ -436,9 +392,8 @@ extern "C" int ao_mxfp4_quantize_rowwise(const uint16_t* x, uint8_t* q, uint8_t*
 extern "C" int ao_mx_linear_route(int fmt, int64_t M, int64_t N, int64_t K, int32_t* out, int cap) {
   AO_REQUIRE_PTR(out);
   AO_REQUIRE(cap >= 7, "ao_mx_linear_route: cap must be >= 7, got %d", cap);
-  const MxRoute r = mx_route(fmt, M, N, K);
-  const int32_t v[7] = {r.kernel, r.waves, r.mt, r.tile_m, r.tile_n, r.grid_x, r.grid_y};
-  for (int i = 0; i < 7; ++i) out[i] = v[i];
+  const TwoFormRoute r = mx_route(fmt, M, N, K);
+  write_route(r, out);
   return AO_OK;
 }
 
@@ -466,7 +421,7 @@ extern "C" int ao_mx_linear(int fmt, const uint8_t* a, const uint8_t* a_scale, c
   AO_REQUIRE_PTR(a_scale);
   AO_REQUIRE_PTR(out);
   AO_REQUIRE(aligned16(a) && aligned16(b), "%s: the codes must be 16-byte aligned", __func__);
-  const MxRoute r = mx_route(fmt, M, N, K);
+  const TwoFormRoute r = mx_route(fmt, M, N, K);
   AO_REQUIRE(r.kernel != 0, "%s: no route for M=%lld N=%lld K=%lld", __func__, (long long)M, (long long)N, (long long)K);
   const MxArgs args{a, a_scale, nullptr, b, b_scale, bias, out, (int)M, (int)N, (int)K};
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -483,7 +438,7 @@ extern "C" int ao_mx_dynamic_linear(int fmt, const uint16_t* x, const uint8_t* b
              "%s: scaling_mode must be AO_MX_SCALE_FLOOR or AO_MX_SCALE_RCEIL, got %d", __func__, scaling_mode);
   AO_REQUIRE_PTR(b);
   AO_REQUIRE_PTR(b_scale);
-  const MxRoute r = mx_route(fmt, M, N, K);
+  const TwoFormRoute r = mx_route(fmt, M, N, K);
   AO_REQUIRE(r.kernel == 1, "%s: M=%lld N=%lld K=%lld takes the tiled form: cast (ao_mx*_quantize_rowwise) and call ao_mx_linear", __func__,
              (long long)M, (long long)N, (long long)K);
   if (M == 0) return AO_OK;

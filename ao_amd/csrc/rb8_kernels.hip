@@ -20,14 +20,13 @@
 #include "lds_dma.h"
 #include "quant_math.h"
 #include "splitk.h"
+#include "stream_blocks.h"
 
 #include <algorithm>
 #include <type_traits>
 
 namespace ao {
 namespace {
-
-typedef int i32x8 __attribute__((ext_vector_type(8)));
 
 constexpr int kStages = 3;   // activation ring (shared), filled 2 steps ahead
 // weight ring (per wave), filled kWStages - 1 steps ahead: the HBM stream needs the bytes in flight.  6 stages; 5 for the
@@ -338,28 +337,16 @@ __global__ __launch_bounds__(64 * WAVES) void rb8_kernel(Rb8Args p) {
       ++ksync;
       __builtin_amdgcn_sched_barrier(0);  // the reads are ISSUED here, ahead of the MFMAs of the step before
     };
-    auto one = [&](f32x4& c, const u32x4& a0, const u32x4& a1, const u32x4& b0, const u32x4& b1) {
-      if constexpr (INT8) {  // acc holds int32 bit patterns
-        i32x4 ci = __builtin_bit_cast(i32x4, c);
-        ci = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, a0), __builtin_bit_cast(i32x4, b0), ci, 0, 0, 0);
-        ci = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, a1), __builtin_bit_cast(i32x4, b1), ci, 0, 0, 0);
-        c = __builtin_bit_cast(f32x4, ci);
-      } else {
-        const i32x8 af = {(int)a0.x, (int)a0.y, (int)a0.z, (int)a0.w, (int)a1.x, (int)a1.y, (int)a1.z, (int)a1.w};
-        const i32x8 bf = {(int)b0.x, (int)b0.y, (int)b0.z, (int)b0.w, (int)b1.x, (int)b1.y, (int)b1.z, (int)b1.w};
-        c = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af, bf, c, 0, 0, 0, 127, 0, 127);
-      }
-    };
     auto mma = [&](const Frags& f) {
       if (TRACE && (p.ablate & 3)) {
       } else if constexpr (SM) {
 #pragma unroll
         for (int i = 0; i < MH; ++i)
 #pragma unroll
-          for (int j = 0; j < 2; ++j) one(acc[2 * i + j], f.a0[i], f.a1[i], f.b0[j], f.b1[j]);
+          for (int j = 0; j < 2; ++j) acc[2 * i + j] = mfma8_k128<INT8>(f.a0[i], f.a1[i], f.b0[j], f.b1[j], acc[2 * i + j]);
       } else {
 #pragma unroll
-        for (int mt = 0; mt < MTC; ++mt) one(acc[mt], f.a0[mt], f.a1[mt], f.b0[0], f.b1[0]);
+        for (int mt = 0; mt < MTC; ++mt) acc[mt] = mfma8_k128<INT8>(f.a0[mt], f.a1[mt], f.b0[0], f.b1[0], acc[mt]);
       }
       __builtin_amdgcn_sched_barrier(0);
     };
@@ -406,18 +393,7 @@ __global__ __launch_bounds__(64 * WAVES) void rb8_kernel(Rb8Args p) {
         const u32x4 a0 = *reinterpret_cast<const u32x4*>(A + (4 * wm + i) * 2048 + pa);
         const u32x4 a1 = *reinterpret_cast<const u32x4*>(A + (4 * wm + i) * 2048 + (pa ^ 64));
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          if constexpr (INT8) {
-            i32x4 c = __builtin_bit_cast(i32x4, acc[2 * i + j]);
-            c = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, a0), __builtin_bit_cast(i32x4, b0[j]), c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, a1), __builtin_bit_cast(i32x4, b1[j]), c, 0, 0, 0);
-            acc[2 * i + j] = __builtin_bit_cast(f32x4, c);
-          } else {
-            const i32x8 af = {(int)a0.x, (int)a0.y, (int)a0.z, (int)a0.w, (int)a1.x, (int)a1.y, (int)a1.z, (int)a1.w};
-            const i32x8 bfj = {(int)b0[j].x, (int)b0[j].y, (int)b0[j].z, (int)b0[j].w, (int)b1[j].x, (int)b1[j].y, (int)b1[j].z, (int)b1[j].w};
-            acc[2 * i + j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af, bfj, acc[2 * i + j], 0, 0, 0, 127, 0, 127);
-          }
-        }
+        for (int j = 0; j < 2; ++j) acc[2 * i + j] = mfma8_k128<INT8>(a0, a1, b0[j], b1[j], acc[2 * i + j]);
       }
       stage = (stage == KA - 1) ? 0 : stage + 1;
       wstage = (wstage == kWStages - 1) ? 0 : wstage + 1;
@@ -426,7 +402,6 @@ __global__ __launch_bounds__(64 * WAVES) void rb8_kernel(Rb8Args p) {
     const char* W = smem + KA * kABuf + (wave * kWStages + wstage) * 2048;
     const u32x4 b0 = *reinterpret_cast<const u32x4*>(W + pa);  // the n-tile's 16 rows are laid out like an m-tile
     const u32x4 b1 = *reinterpret_cast<const u32x4*>(W + (pa ^ 64));
-    const i32x8 bf = {(int)b0.x, (int)b0.y, (int)b0.z, (int)b0.w, (int)b1.x, (int)b1.y, (int)b1.z, (int)b1.w};
     // MX: the scale byte of lane group kq is that of 32-k block kq of the step (operand layout probed on gfx950, stream8_kernels.hip)
     [[maybe_unused]] const char* AS = smem + KA * kABuf + WAVES * (kWStages * 2048) +
                                       ((QS == 1) ? stage * WAVES * SCL : ((k >> 2) & 1) * WAVES * ASB + (k & 3) * 4);
@@ -441,20 +416,12 @@ __global__ __launch_bounds__(64 * WAVES) void rb8_kernel(Rb8Args p) {
     for (int mt = 0; mt < MTC; ++mt) {
       const u32x4 a0 = *reinterpret_cast<const u32x4*>(A + mt * 2048 + pa);
       const u32x4 a1 = *reinterpret_cast<const u32x4*>(A + mt * 2048 + (pa ^ 64));
-      if constexpr (INT8) {  // acc holds int32 bit patterns
-        i32x4 c = __builtin_bit_cast(i32x4, acc[mt]);
-        c = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, a0), __builtin_bit_cast(i32x4, b0), c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, a1), __builtin_bit_cast(i32x4, b1), c, 0, 0, 0);
-        acc[mt] = __builtin_bit_cast(f32x4, c);
-      } else {
-        const i32x8 af = {(int)a0.x, (int)a0.y, (int)a0.z, (int)a0.w, (int)a1.x, (int)a1.y, (int)a1.z, (int)a1.w};
-        int sa = 127;
-        if constexpr (MX) {  // row mt * 16 + nl sits in the region of wave row / RPW, slot row % RPW
-          const int row = mt * 16 + nl;
-          sa = (int)(*reinterpret_cast<const uint32_t*>(AS + (row / RPW) * ((QS == 1) ? SCL : ASB) + (row % RPW) * ((QS == 1) ? 4 : 16)) >> (8 * kq)) & 0xff;
-        }
-        acc[mt] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af, bf, acc[mt], 0, 0, 0, sa, 0, sb);
+      int sa = 127;
+      if constexpr (MX) {  // row mt * 16 + nl sits in the region of wave row / RPW, slot row % RPW
+        const int row = mt * 16 + nl;
+        sa = (int)(*reinterpret_cast<const uint32_t*>(AS + (row / RPW) * ((QS == 1) ? SCL : ASB) + (row % RPW) * ((QS == 1) ? 4 : 16)) >> (8 * kq)) & 0xff;
       }
+      acc[mt] = mfma8_k128<INT8>(a0, a1, b0, b1, acc[mt], sa, sb);  // (INT8: acc holds int32 bit patterns)
     }
     stage = (stage == KA - 1) ? 0 : stage + 1;
     wstage = (wstage == kWStages - 1) ? 0 : wstage + 1;
@@ -991,7 +958,7 @@ __global__ __launch_bounds__(64 * WAVES) void mx_stream_kernel(Rb8Args p) {
     const char* Wt = smem + kWOff + (wave * SW + wstage) * 2048;
     const u32x4 b0 = *reinterpret_cast<const u32x4*>(Wt + pa);  // the n-tile's 16 rows are laid out like an m-tile
     const u32x4 b1 = *reinterpret_cast<const u32x4*>(Wt + (pa ^ 64));
-    const i32x8 bf = {(int)b0.x, (int)b0.y, (int)b0.z, (int)b0.w, (int)b1.x, (int)b1.y, (int)b1.z, (int)b1.w};
+    const i32x8 bf = pack_k128(b0, b1);
     // the scale byte of lane group kq is that of 32-k block kq of the step (operand layout probed on gfx950, stream8_kernels.hip)
     const int blk = ((g - gv) >> 2) & 1, ph = (g - gv) & 3;  // QS == 4: slot and position of this step's scale dword
     const char* AS = smem + kWOff + WAVES * (SW * 2048) + (kCast ? stage * 256 : ((QS == 1) ? stage : blk) * WAVES * ASB + ((QS == 1) ? 0 : ph * 4));
@@ -1002,10 +969,10 @@ __global__ __launch_bounds__(64 * WAVES) void mx_stream_kernel(Rb8Args p) {
       if (mt < mt_have) {  // uniform: a 32-row group reads and multiplies two m-tiles
         const u32x4 a0 = *reinterpret_cast<const u32x4*>(A + mt * 2048 + pa);
         const u32x4 a1 = *reinterpret_cast<const u32x4*>(A + mt * 2048 + (pa ^ 64));
-        const i32x8 af = {(int)a0.x, (int)a0.y, (int)a0.z, (int)a0.w, (int)a1.x, (int)a1.y, (int)a1.z, (int)a1.w};
+        const i32x8 af = pack_k128(a0, a1);
         const int row = mt * 16 + nl;  // its scales sit in the slot of wave row / RPW (CAST: [row][4 B])
         const int sa = (int)(*reinterpret_cast<const uint32_t*>(AS + (kCast ? row * 4 : (row / RPW) * ASB + (row % RPW) * ((QS == 1) ? 4 : 16))) >> (8 * kq)) & 0xff;
-        acc[mt] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af, bf, acc[mt], 0, 0, 0, sa, 0, sb);
+        acc[mt] = mfma8_k128_packed(af, bf, acc[mt], sa, sb);
       }
     }
     stage = (stage == KA - 1) ? 0 : stage + 1;

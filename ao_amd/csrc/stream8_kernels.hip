@@ -14,6 +14,7 @@
 #include "common.h"
 #include "gemm8_route.h"
 #include "quant_math.h"
+#include "stream_blocks.h"
 
 #include <type_traits>
 
@@ -25,8 +26,6 @@ int mxfp8_grouped_rb(const Grouped8Route& r, const void* a, const uint8_t* a_sca
                      const uint8_t* b2_scale, const int32_t* offs, uint16_t* out, uint16_t* out2, int64_t M_total, int64_t N, int64_t K, int64_t E,
                      hipStream_t stream);
 namespace {
-
-typedef int i32x8 __attribute__((ext_vector_type(8)));
 
 struct Stream8Args {
   const uint8_t* a;        // [M_total][K] e4m3
@@ -99,7 +98,6 @@ __global__ __launch_bounds__(512) void stream8_kernel(Stream8Args p) {
       const u32x4 b1 = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(brow + (size_t)ks * 128 + 64));
       int sb = 127;
       if (MX) sb = (int)((*reinterpret_cast<const uint32_t*>(bsrow + ks * 4)) >> (8 * kq)) & 0xff;
-      const i32x8 bf = {(int)b0.x, (int)b0.y, (int)b0.z, (int)b0.w, (int)b1.x, (int)b1.y, (int)b1.z, (int)b1.w};
 #pragma unroll
       for (int t = 0; t < MT; ++t) {
         if (t * 16 < rows) {  // uniform
@@ -108,22 +106,14 @@ __global__ __launch_bounds__(512) void stream8_kernel(Stream8Args p) {
           int sa = 127;
           if (MX) sa = (int)((*reinterpret_cast<const uint32_t*>(asrow[t] + ks * 4)) >> (8 * kq)) & 0xff;
           if (!valid[t]) { a0 = u32x4{0, 0, 0, 0}; a1 = u32x4{0, 0, 0, 0}; sa = 127; }
-          if constexpr (INT8) {  // acc holds int32 bit patterns
-            i32x4 c = __builtin_bit_cast(i32x4, acc[t]);
-            c = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, a0), __builtin_bit_cast(i32x4, b0), c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, a1), __builtin_bit_cast(i32x4, b1), c, 0, 0, 0);
-            acc[t] = __builtin_bit_cast(f32x4, c);
-          } else {
-            const i32x8 af = {(int)a0.x, (int)a0.y, (int)a0.z, (int)a0.w, (int)a1.x, (int)a1.y, (int)a1.z, (int)a1.w};
-            acc[t] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af, bf, acc[t], 0, 0, 0, sa, 0, sb);
-          }
+          acc[t] = mfma8_k128<INT8>(a0, a1, b0, b1, acc[t], sa, sb);  // (INT8: acc holds int32 bit patterns)
         }
       }
     }
 
     // split-K reduction across waves: red[wave][t][row 16][col 16]
 #pragma unroll
-    for (int t = 0; t < MT; ++t) {
+    for (int t = 0; t < MT; ++t) {  // (park_tile, written out: through the function the MX kind's register allocation changed)
       float* r = red + ((size_t)wave * MT + t) * 256 + (kq * 4) * 16 + (lane & 15);
       r[0] = acc[t].x; r[16] = acc[t].y; r[32] = acc[t].z; r[48] = acc[t].w;
     }
@@ -283,7 +273,7 @@ __global__ __launch_bounds__(256) void mx_grouped_kernel(Stream8Args p) {
           u32x4 a0 = cur.a[s][t][0], a1 = cur.a[s][t][1];
           int sc = (int)(cur.sa[s][t] >> (8 * kq)) & 0xff;
           if (!valid[t]) { a0 = u32x4{0, 0, 0, 0}; a1 = u32x4{0, 0, 0, 0}; sc = 127; }  // v_cndmask, not a branch
-          af[s][t] = i32x8{(int)a0.x, (int)a0.y, (int)a0.z, (int)a0.w, (int)a1.x, (int)a1.y, (int)a1.z, (int)a1.w};
+          af[s][t] = pack_k128(a0, a1);
           sa[s][t] = sc;
         }
       if (!LAST) {
@@ -296,11 +286,9 @@ __global__ __launch_bounds__(256) void mx_grouped_kernel(Stream8Args p) {
 #pragma unroll
         for (int s = 0; s < S; ++s) {
           const int sb = (int)(sg.sb[s] >> (8 * kq)) & 0xff;
-          const i32x8 bf = {(int)sg.b[s][0].x, (int)sg.b[s][0].y, (int)sg.b[s][0].z, (int)sg.b[s][0].w,
-                            (int)sg.b[s][1].x, (int)sg.b[s][1].y, (int)sg.b[s][1].z, (int)sg.b[s][1].w};
+          const i32x8 bf = pack_k128(sg.b[s][0], sg.b[s][1]);
 #pragma unroll
-          for (int t = 0; t < MT; ++t)
-            acc[j][t] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(af[s][t], bf, acc[j][t], 0, 0, 0, sa[s][t], 0, sb);
+          for (int t = 0; t < MT; ++t) acc[j][t] = mfma8_k128_packed(af[s][t], bf, acc[j][t], sa[s][t], sb);
         }
         if (!LAST) issue(st[j % D], (j + D) % TN, c + (j + D) / TN);
         else if (j + D < TN) issue(st[j % D], j + D, c);
@@ -316,10 +304,7 @@ __global__ __launch_bounds__(256) void mx_grouped_kernel(Stream8Args p) {
 #pragma unroll
       for (int r = 0; r < R; ++r)
 #pragma unroll
-        for (int t = 0; t < MT; ++t) {
-          float* q = red + (((size_t)wave * R + r) * MT + t) * 256 + (kq * 4) * 16 + nl;
-          q[0] = acc[j0 + r][t].x; q[16] = acc[j0 + r][t].y; q[32] = acc[j0 + r][t].z; q[48] = acc[j0 + r][t].w;
-        }
+        for (int t = 0; t < MT; ++t) park_tile(red + (((size_t)wave * R + r) * MT + t) * 256, kq, nl, acc[j0 + r][t]);
       __syncthreads();
       for (int idx = threadIdx.x; idx < R * MT * 256; idx += W * 64) {
         const int r = idx / (MT * 256), t = (idx / 256) % MT, rc = idx & 255;

@@ -9,7 +9,8 @@
 // per-element rounding for e4m3.  The MFMA sums over k in whatever order its lanes hold it, so lane l takes 16 consecutive k of row
 // l & 15 -- one 16-byte weight load, two 16-byte activation loads -- and feeds two MFMAs (k 0..7 and 8..15 of its piece).
 //
-// Two forms, one route (wo8_route) read by the launch and by ao_wo8_linear_route:
+// Two forms, one route (wo8_route: this family's shape check, seams and forced form over the plans of two_form_route.h)
+// read by the launch and by ao_wo8_linear_route:
 //   wo8_stream_kernel: the weight is streamed once, 1 byte per weight.  A workgroup owns 16 columns and splits K over its waves in runs of
 //     128-k steps; a step's two loads of a lane (pieces kq and 4 + kq) complete 128-byte lines, nontemporal; a wave requests a chunk of
 //     four steps ahead of the chunk it multiplies.  The activation is read from global memory inside the multiply, behind those requests
@@ -22,6 +23,7 @@
 //     ragged N and K; not tuned.
 #include "common.h"
 #include "quant_math.h"
+#include "two_form_route.h"
 
 #include <algorithm>
 
@@ -41,14 +43,6 @@ constexpr int kFmtE4M3 = AO_WO8_FMT_E4M3;
 constexpr int kStreamMaxRowsInt8 = 64;
 constexpr int kStreamMaxRowsE4M3 = 64;
 
-struct Wo8Route {
-  int kernel = 0;  // 0 invalid, 1 wo8_stream_kernel, 2 wo8_tile_kernel
-  int waves = 0;   // waves per workgroup
-  int mt = 0;      // m-tiles of 16 per workgroup
-  int tile_m = 0, tile_n = 0;
-  int grid_x = 0, grid_y = 0;
-};
-
 thread_local int g_form = 0;  // ao_wo8_linear_set_form: 0 the product route, 1 stream, 2 tile
 
 bool wo8_shape_ok(int fmt, int64_t M, int64_t N, int64_t K) {
@@ -59,35 +53,12 @@ bool wo8_shape_ok(int fmt, int64_t M, int64_t N, int64_t K) {
   return M * K < (1ll << 31) && N * K < (1ll << 31) && M * N < (1ll << 40);
 }
 
-Wo8Route wo8_route(int fmt, int64_t M, int64_t N, int64_t K) {
-  Wo8Route r;
-  if (!wo8_shape_ok(fmt, M, N, K)) return r;
+// kernel 1: wo8_stream_kernel, 2: wo8_tile_kernel (64 x 64 tiles)
+TwoFormRoute wo8_route(int fmt, int64_t M, int64_t N, int64_t K) {
+  if (!wo8_shape_ok(fmt, M, N, K)) return TwoFormRoute{};
   const int seam = fmt == kFmtInt8 ? kStreamMaxRowsInt8 : kStreamMaxRowsE4M3;
-  const int form = g_form != 0 ? g_form : (M <= seam ? 1 : 2);
-  if (form == 1) {
-    const int64_t ntiles = (N + 15) / 16;
-    const int64_t ksteps = (K + 127) / 128;
-    r.kernel = 1;
-    r.mt = M <= 16 ? 1 : (M <= 32 ? 2 : 4);
-    // enough waves in flight to cover HBM latency on 256 CUs: fewer column tiles, more K parts per tile; no wave without a k step
-    int w = ntiles >= 1024 ? 4 : (ntiles >= 256 ? 8 : 16);
-    if (r.mt == 4 && w > 8) w = 8;  // the meeting buffer: waves x m-tiles x 1 KiB of static LDS
-    while (w > 1 && w > ksteps) w >>= 1;
-    r.waves = w;
-    r.tile_m = 16 * r.mt;
-    r.tile_n = 16;
-    r.grid_x = (int)ntiles;
-    r.grid_y = (int)std::max<int64_t>(1, (M + r.tile_m - 1) / r.tile_m);
-  } else {
-    r.kernel = 2;
-    r.waves = 4;
-    r.mt = 4;
-    r.tile_m = 64;
-    r.tile_n = 64;
-    r.grid_x = (int)((N + 63) / 64);
-    r.grid_y = (int)std::max<int64_t>(1, (M + 63) / 64);
-  }
-  if (r.grid_y > 65535) r.kernel = 0;
+  TwoFormRoute r = two_form_route(g_form != 0 ? g_form : (M <= seam ? 1 : 2), M, N, K, 64);
+  r.grid_y = std::max(r.grid_y, 1);  // (this family's tiled form reports one grid row at M = 0 -- a forced form only; never launched)
   return r;
 }
 
@@ -100,8 +71,6 @@ struct Wo8Args {
   int M, N, K;
   int per_tensor;        // one scale for every row
 };
-
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 __device__ __forceinline__ f32x4 mfma_bf16(const u32x4& a, const u32x4& b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
@@ -276,37 +245,20 @@ __global__ __launch_bounds__(256) void wo8_tile_kernel(Wo8Args p) {
 }
 
 // ---- launches -------------------------------------------------------------------------------------------------------------------
-template <int FMT, int MT>
-int launch_stream_mt(const Wo8Route& r, const Wo8Args& a, hipStream_t st) {
-  const dim3 grid(r.grid_x, r.grid_y);
-  switch (r.waves) {
-    case 1: ao::launch(wo8_stream_kernel<FMT, MT, 1>, grid, dim3(64), 0, st, a); break;
-    case 2: ao::launch(wo8_stream_kernel<FMT, MT, 2>, grid, dim3(128), 0, st, a); break;
-    case 4: ao::launch(wo8_stream_kernel<FMT, MT, 4>, grid, dim3(256), 0, st, a); break;
-    case 8: ao::launch(wo8_stream_kernel<FMT, MT, 8>, grid, dim3(512), 0, st, a); break;
-    case 16:
-      if constexpr (MT <= 2) {  // (4 m-tiles x 16 waves: the meeting buffer would pass the static LDS; wo8_route caps them at 8)
-        ao::launch(wo8_stream_kernel<FMT, MT, 16>, grid, dim3(1024), 0, st, a);
-        break;
-      }
-      [[fallthrough]];
-    default:
-      set_error("wo8_stream_kernel: no instantiation for %d m-tiles x %d waves", MT, r.waves);
-      return AO_ERR_INVALID_ARGUMENT;
-  }
+// (4 m-tiles x 16 waves: the meeting buffer would pass the static LDS; the stream-form plan caps 4 m-tiles at 8 waves)
+template <int FMT>
+int launch_stream(const TwoFormRoute& r, const Wo8Args& a, hipStream_t st) {
+  if (int rc = with_stream_form<false>("wo8_stream_kernel", r, [&](auto mt, auto waves) {
+        constexpr int MT = decltype(mt)::value, WAVES = decltype(waves)::value;
+        ao::launch(wo8_stream_kernel<FMT, MT, WAVES>, dim3(r.grid_x, r.grid_y), dim3(64 * WAVES), 0, st, a);
+      }))
+    return rc;
   AO_LAUNCH_CHECK("wo8_stream_kernel launch");
   return AO_OK;
 }
 
 template <int FMT>
-int launch_stream(const Wo8Route& r, const Wo8Args& a, hipStream_t st) {
-  if (r.mt == 1) return launch_stream_mt<FMT, 1>(r, a, st);
-  if (r.mt == 2) return launch_stream_mt<FMT, 2>(r, a, st);
-  return launch_stream_mt<FMT, 4>(r, a, st);
-}
-
-template <int FMT>
-int launch_tile(const Wo8Route& r, const Wo8Args& a, hipStream_t st) {
+int launch_tile(const TwoFormRoute& r, const Wo8Args& a, hipStream_t st) {
   ao::launch(wo8_tile_kernel<FMT>, dim3(r.grid_x, r.grid_y), dim3(256), 0, st, a);
   AO_LAUNCH_CHECK("wo8_tile_kernel launch");
   return AO_OK;
@@ -322,9 +274,8 @@ using namespace ao;
 extern "C" int ao_wo8_linear_route(int fmt, int64_t M, int64_t N, int64_t K, int32_t* out, int cap) {
   AO_REQUIRE_PTR(out);
   AO_REQUIRE(cap >= 7, "ao_wo8_linear_route: cap must be >= 7, got %d", cap);
-  const Wo8Route r = wo8_route(fmt, M, N, K);
-  const int32_t v[7] = {r.kernel, r.waves, r.mt, r.tile_m, r.tile_n, r.grid_x, r.grid_y};
-  for (int i = 0; i < 7; ++i) out[i] = v[i];
+  const TwoFormRoute r = wo8_route(fmt, M, N, K);
+  write_route(r, out);
   return AO_OK;
 }
 
@@ -348,7 +299,7 @@ extern "C" int ao_wo8_linear(int fmt, const uint16_t* x, const void* wq, const f
   AO_REQUIRE_PTR(out);
   AO_REQUIRE(aligned_to(x, 16) && aligned_to(wq, 16), "%s: x and the codes must be 16-byte aligned", __func__);
   AO_REQUIRE(aligned_to(w_scale, 4) && aligned_to(bias, 2) && aligned_to(out, 2), "%s: w_scale must be 4-byte, bias and out 2-byte aligned", __func__);
-  const Wo8Route r = wo8_route(fmt, M, N, K);
+  const TwoFormRoute r = wo8_route(fmt, M, N, K);
   AO_REQUIRE(r.kernel != 0, "%s: no route for M=%lld N=%lld K=%lld", __func__, (long long)M, (long long)N, (long long)K);
   const Wo8Args args{x, static_cast<const uint8_t*>(wq), w_scale, bias, out, (int)M, (int)N, (int)K, scale_count == 1 ? 1 : 0};
   hipStream_t st = static_cast<hipStream_t>(stream);

@@ -471,3 +471,32 @@ def test_queries_ignore_overrides():
         for key in (1, 3, 6, 7):
             lib.ao_gemm8_set_tuning(key, 0)
         lib.ao_int4_set_tuning(0, 0)
+
+
+def test_two_form_routes_match_the_recording():
+    """The seven route fields of the MX dense and the weight-only linears -- every format under every ao_*_linear_set_form value, the
+    shapes a family refuses and the grid-row cap included -- are those recorded in tests/golden/two_form_routes.json
+    (tests/golden/make_two_form_routes.py); and one family's forced form does not move the other family's routes."""
+    import importlib.util
+    import os
+
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "make_two_form_routes.py")
+    spec = importlib.util.spec_from_file_location("make_two_form_routes", path)
+    rec = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(rec)
+
+    lib = _lib.lib()
+    want = rec.load()
+    assert len(want) == 12 and all(len(cells) == len(rec.M_GRID) * len(rec.N_GRID) * len(rec.K_GRID) for cells in want.values())
+    got = rec.record(lib)
+    for key in want:
+        assert got[key] == want[key], key
+
+    for forced, other in (("mx", "wo8"), ("wo8", "mx")):
+        try:
+            for form in (1, 2):
+                assert getattr(lib, rec.FAMILIES[forced][1])(form) == 0
+                for key, cells in rec.record_form(lib, other, None).items():
+                    assert cells == want[key], (forced, form, key)
+        finally:
+            getattr(lib, rec.FAMILIES[forced][1])(0)
