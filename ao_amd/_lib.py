@@ -119,6 +119,14 @@ _SIGNATURES = {
     "ao_wo8_linear": [_INT, _P, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _P],
     "ao_wo8_linear_route": [_INT, _I64, _I64, _I64, _P, _INT],
     "ao_wo8_linear_set_form": [_INT],
+    "ao_fp8_quantize_block_1x128": [_P, _P, _P, _I64, _I64, _P],
+    "ao_fp8_quantize_block_128x128": [_P, _P, _P, _I64, _I64, _P],
+    "ao_fp8_block_linear": [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _P],
+    "ao_fp8_block_dynamic_linear_fits": [_I64, _I64, _I64],
+    "ao_fp8_block_dynamic_linear": [_P, _P, _P, _P, _P, _I64, _I64, _I64, _P],
+    "ao_fp8_block_linear_route": [_I64, _I64, _I64, _P, _INT],
+    "ao_fp8_block_linear_kernel_name": [_I64, _I64, _I64],
+    "ao_fp8_block_linear_set_form": [_INT],
 }
 
 
@@ -162,6 +170,8 @@ def lib():
             l.ao_gemm8_kernel_name.restype = ctypes.c_char_p
         if hasattr(l, "ao_mx_linear_kernel_name"):
             l.ao_mx_linear_kernel_name.restype = ctypes.c_char_p
+        if hasattr(l, "ao_fp8_block_linear_kernel_name"):
+            l.ao_fp8_block_linear_kernel_name.restype = ctypes.c_char_p
         if hasattr(l, "ao_fp8_int4_kernel_name"):
             l.ao_fp8_int4_kernel_name.restype = ctypes.c_char_p
         l.ao_moe_padded_rows.restype = _I64

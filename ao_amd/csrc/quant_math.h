@@ -146,6 +146,24 @@ __device__ __forceinline__ float wo8_out(float c, float s, bool has_bias = false
   return v;
 }
 
+// ---- blockwise float8 linears (fp8_block_kernels.hip): 1 x 128 activation blocks, 128 x 128 weight blocks ----------------------------
+// One K block onto the accumulator of a lane's four rows (kernels.py:85-97: accumulator += tl.dot(a, b) * a_s[:, None] * b_s[None, :]):
+//   acc[r] += (p[r] * a_s[r]) * b_s, two products and a sum in fp32, each rounded on its own -- the chain tests/fp8_block_ref.py restates
+// in plain fp32, so none of them may contract into a v_fma_f32.  p: the block's 128-k MFMA onto a zero accumulator.
+__device__ __forceinline__ f32x4 fp8_block_acc(f32x4 acc, f32x4 p, f32x4 a_s, float b_s) {
+#pragma clang fp contract(off)
+  const f32x4 t = p * a_s;
+  const f32x4 u = t * b_s;
+  return acc + u;
+}
+// The output: t = bf16(acc);  y = bf16(f32(t) + bias[n]) -- rounded to bf16 BEFORE the bias (float8_tensor.py:445-447: the GEMM returns
+// bf16, the bias is added to that tensor).  The fp32 value the caller rounds to bf16 at its store.
+__device__ __forceinline__ float fp8_block_out(float acc, bool has_bias = false, float bias = 0.f) {
+  float v = round_bf16(acc);
+  if (has_bias) v += bias;
+  return v;
+}
+
 // ---- MXFP8 (to_mx, prototype/mx_formats/mx_tensor.py:228-409) --------------------------------------------------------------------
 // E8M0 scale exponent of one 32-block from its amax (:255-330; RCEIL :111-129, :161-225) and the reciprocal 2^(127 - e) built from the
 // E8M0 byte 254 - e (:132-158).  MODE: AO_MX_SCALE_FLOOR (0) / AO_MX_SCALE_RCEIL (1).

@@ -1329,3 +1329,139 @@ def fp8_wo_linear(x2, wq, w_scale, bias=None, out=None):
 
 
 __all__ += ["int8_wo_linear", "fp8_wo_linear", "wo8_route", "wo8_set_form"]
+
+
+# ---- blockwise float8 linears: 1 x 128 activation blocks, 128 x 128 weight blocks (include/ao_mi355.h) ---------------
+FP8_BLOCK_KERNELS = {0: "invalid", 1: "fp8_block_stream_kernel", 2: "fp8_block_tile_kernel"}
+# The host rule for "the cast fused into the GEMM, or two launches": fused up to this many rows.  0: never by itself -- every one of
+# the fused form's ceil(N / 16) workgroups casts the whole activation again, and at every M = 1 .. 15 on every one of the five Llama-3-8B
+# shapes but o the one launch took longer than the two (tools/bench_fp8_block_linear.py --fused, profiles/fp8_block_linear.jsonl,
+# DESIGN.md 4.12).  fuse=True still reaches it.
+FP8_BLOCK_FUSED_MAX_ROWS = 0
+
+
+def fp8_quantize_block_1x128(x: torch.Tensor):
+    """Float8Tensor.from_hp(x, float8_e4m3fn, PerBlock([1, 128])) (float8_tensor.py:233-242, quant_primitives.py:2173-2212, :2271-2287).
+    x bf16 [..., K], K % 128 == 0 -> (qdata float8_e4m3fn [..., K], scale fp32 [..., K/128]); no row-wide amax."""
+    dev = _require_gpu("fp8_quantize_block_1x128", x)
+    if x.dtype != torch.bfloat16 or x.dim() < 1 or x.shape[-1] % 128 != 0 or x.shape[-1] == 0:
+        raise RuntimeError(f"fp8_quantize_block_1x128: x must be bfloat16 [..., K] with K a positive multiple of 128, got {x.dtype} {tuple(x.shape)}")
+    k = x.shape[-1]
+    rows = x.contiguous().reshape(-1, k)
+    m = rows.shape[0]
+    q = torch.empty((m, k), dtype=torch.uint8, device=dev)
+    s = torch.empty((m, k // 128), dtype=torch.float32, device=dev)
+    if m > 0:
+        with _on(dev):
+            _lib.check(_lib.lib().ao_fp8_quantize_block_1x128(_ptr(rows), _ptr(q), _ptr(s), m, k, _stream()))
+    return q.view(torch.float8_e4m3fn).reshape(x.shape), s.reshape(*x.shape[:-1], k // 128)
+
+
+def fp8_quantize_block_128x128(w: torch.Tensor):
+    """Float8Tensor.from_hp(w, float8_e4m3fn, PerBlock([128, 128])) (same lines).  w bf16 [N, K], both multiples of 128 ->
+    (qdata float8_e4m3fn [N, K], scale fp32 [N/128, K/128])."""
+    dev = _require_gpu("fp8_quantize_block_128x128", w)
+    if w.dtype != torch.bfloat16 or w.dim() != 2:
+        raise RuntimeError(f"fp8_quantize_block_128x128: w must be a 2-D bfloat16 tensor, got {w.dtype} {tuple(w.shape)}")
+    n, k = w.shape
+    if n % 128 != 0 or k % 128 != 0 or k == 0:
+        raise RuntimeError(f"fp8_quantize_block_128x128: shape {(n, k)} is not divisible by the block (128, 128)")
+    w = w.contiguous()
+    q = torch.empty((n, k), dtype=torch.uint8, device=dev)
+    s = torch.empty((n // 128, k // 128), dtype=torch.float32, device=dev)
+    if n > 0:
+        with _on(dev):
+            _lib.check(_lib.lib().ao_fp8_quantize_block_128x128(_ptr(w), _ptr(q), _ptr(s), n, k, _stream()))
+    return q.view(torch.float8_e4m3fn), s
+
+
+def fp8_block_linear_route(m: int, n: int, k: int) -> dict:
+    """The route fp8_block_linear / fp8_block_mm launch for a shape (host logic only, ao_fp8_block_linear_route); kernel "invalid" for
+    shapes nothing takes."""
+    out = (ctypes.c_int32 * 7)()
+    _lib.check(_lib.lib().ao_fp8_block_linear_route(int(m), int(n), int(k), out, 7))
+    kernel, waves, mt, tile_m, tile_n, gx, gy = list(out)
+    return {"kernel": FP8_BLOCK_KERNELS.get(kernel, "invalid"), "waves": waves, "m_tiles": mt, "tile_m": tile_m, "tile_n": tile_n,
+            "grid": (gx, gy)}
+
+
+def fp8_block_linear_kernel_name(m: int, n: int, k: int) -> str:
+    return _lib.lib().ao_fp8_block_linear_kernel_name(int(m), int(n), int(k)).decode()
+
+
+def fp8_block_linear_set_form(form: int) -> None:
+    """Measurement only: 0 the product route, 1 the streaming form, 2 the tiled form (calling thread)."""
+    _lib.check(_lib.lib().ao_fp8_block_linear_set_form(int(form)))
+
+
+def _fp8_block_weight(name, wq, w_scale, bias, k_from_a):
+    wq = _fp8_bytes(name, wq)
+    if wq.dim() != 2:
+        raise RuntimeError(f"{name}: the weight codes must be 2-D [N, K], got {tuple(wq.shape)}")
+    n, k = wq.shape
+    if k != k_from_a:
+        raise RuntimeError(f"{name}: K of the activation ({k_from_a}) and of the weight ({k}) differ")
+    if k == 0 or k % 128 != 0:
+        raise RuntimeError(f"{name}: K must be a positive multiple of 128, got {k}")
+    if w_scale.dtype != torch.float32 or tuple(w_scale.shape) != ((n + 127) // 128, k // 128):
+        raise RuntimeError(f"{name}: the weight scales must be float32 [ceil(N/128), K/128] = {((n + 127) // 128, k // 128)}, got "
+                           f"{w_scale.dtype} {tuple(w_scale.shape)}")
+    if bias is not None:
+        if bias.numel() != n:
+            raise RuntimeError(f"{name}: bias must have N elements")
+        bias = bias.to(torch.bfloat16).contiguous()
+    return wq.contiguous(), w_scale.contiguous(), bias, n, k
+
+
+def _bf16_out(name, out, m, n, dev):
+    if out is None:
+        return torch.empty((m, n), dtype=torch.bfloat16, device=dev)
+    if out.dtype != torch.bfloat16 or tuple(out.shape) != (m, n) or not out.is_contiguous() or out.device != dev:
+        raise RuntimeError(f"{name}: out must be a contiguous bfloat16 [{m}, {n}] tensor on {dev}")
+    return out
+
+
+def fp8_block_mm(aq, a_scale, wq, w_scale, bias=None, out=None):
+    """The blockwise GEMM on codes (kernels.py:56-128, float8_tensor.py:433-447): aq e4m3 [M, K], a_scale fp32 [M, K/128], wq e4m3 [N, K]
+    (the weight as stored), w_scale fp32 [ceil(N/128), K/128], bias [N] -> bf16 [M, N] (ao_fp8_block_linear)."""
+    dev = _require_gpu("fp8_block_mm", aq, a_scale, wq, w_scale, bias)
+    aq = _fp8_bytes("fp8_block_mm", aq)
+    if aq.dim() != 2:
+        raise RuntimeError(f"fp8_block_mm: the activation codes must be 2-D [M, K], got {tuple(aq.shape)}")
+    m = aq.shape[0]
+    wq, w_scale, bias, n, k = _fp8_block_weight("fp8_block_mm", wq, w_scale, bias, aq.shape[1])
+    if a_scale.dtype != torch.float32 or tuple(a_scale.shape) != (m, k // 128):
+        raise RuntimeError(f"fp8_block_mm: the activation scales must be float32 [M, K/128] = {(m, k // 128)}, got {a_scale.dtype} {tuple(a_scale.shape)}")
+    y = _bf16_out("fp8_block_mm", out, m, n, dev)
+    if m > 0:
+        with _on(dev):
+            _lib.check(_lib.lib().ao_fp8_block_linear(_ptr(aq.contiguous()), _ptr(a_scale.contiguous()), _ptr(wq), _ptr(w_scale), _ptr(bias),
+                                                      _ptr(y), m, n, k, _stream()))
+    return y
+
+
+def fp8_block_linear(x2, wq, w_scale, bias=None, fuse=None, out=None):
+    """Float8Tensor's linear with 1 x 128 dynamic activation blocks on a 128 x 128 block-scaled weight (float8_tensor.py:433-447): the
+    1 x 128 cast, then the blockwise GEMM.  x2 bf16 [M, K].  fuse None: the host rule (the cast inside the GEMM, one launch, up to
+    FP8_BLOCK_FUSED_MAX_ROWS rows where the route is the streaming form; two launches otherwise); True: fused wherever the streaming
+    form takes the shape; False: always two launches.  The same bits either way."""
+    dev = _require_gpu("fp8_block_linear", x2, wq, w_scale, bias)
+    if x2.dim() != 2 or x2.dtype != torch.bfloat16:
+        raise RuntimeError(f"fp8_block_linear: x must be a 2-D bfloat16 tensor, got {tuple(x2.shape)} {x2.dtype}")
+    x2 = x2.contiguous()
+    m = x2.shape[0]
+    wq, w_scale, bias, n, k = _fp8_block_weight("fp8_block_linear", wq, w_scale, bias, x2.shape[1])
+    fused = (m <= FP8_BLOCK_FUSED_MAX_ROWS) if fuse is None else bool(fuse)
+    if fused and m > 0 and _lib.lib().ao_fp8_block_dynamic_linear_fits(m, n, k):
+        y = _bf16_out("fp8_block_linear", out, m, n, dev)
+        with _on(dev):
+            _lib.check(_lib.lib().ao_fp8_block_dynamic_linear(_ptr(x2), _ptr(wq), _ptr(w_scale), _ptr(bias), _ptr(y), m, n, k, _stream()))
+        return y
+    if m == 0:
+        return _bf16_out("fp8_block_linear", out, m, n, dev)
+    aq, a_s = fp8_quantize_block_1x128(x2)
+    return fp8_block_mm(aq, a_s, wq, w_scale, bias, out)
+
+
+__all__ += ["fp8_quantize_block_1x128", "fp8_quantize_block_128x128", "fp8_block_linear", "fp8_block_mm", "fp8_block_linear_kernel_name",
+            "fp8_block_linear_route", "fp8_block_linear_set_form"]

@@ -17,7 +17,7 @@ from .config import (  # noqa: F401
     Int8WeightOnlyConfig,
     ModuleFqnToConfig,
 )
-from .granularity import PerGroup, PerRow, PerTensor  # noqa: F401
+from .granularity import PerBlock, PerGroup, PerRow, PerTensor  # noqa: F401
 from .quant_primitives import MappingType  # noqa: F401
 from .float8_tensor import Float8Tensor, QuantizeTensorToFloat8Kwargs  # noqa: F401
 from .int4_plain_tensor import Int4Tensor  # noqa: F401

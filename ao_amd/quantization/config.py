@@ -4,7 +4,7 @@ import enum
 from dataclasses import dataclass, field
 from typing import List, Optional, Union
 
-from .granularity import Granularity, PerGroup, PerRow, PerTensor
+from .granularity import Granularity, PerBlock, PerGroup, PerRow, PerTensor
 from .quant_primitives import MappingType
 
 
@@ -49,11 +49,21 @@ class Int4WeightOnlyConfig(AOBaseConfig):
         self.int4_choose_qparams_algorithm = Int4ChooseQParamsAlgorithm(self.int4_choose_qparams_algorithm)
 
 
-def _normalize_granularity(granularity, default, what):
+_BLOCK_PAIR = (PerBlock((1, 128)), PerBlock((128, 128)))  # 1 x 128 activation blocks, 128 x 128 weight blocks
+
+
+def _normalize_granularity(granularity, default, what, block_pair=False):
     """(activation, weight) granularities from None / one Granularity / a list of two (reference Int8Tensor._normalize_granularity
-    int8_tensor.py:140-174; quantization/utils.py _normalize_granularity for float8)."""
+    int8_tensor.py:140-174; float8/inference.py:231-268 for float8).  block_pair: the float8 dynamic config also takes exactly
+    [PerBlock([1, 128]), PerBlock([128, 128])] (:257, _granularity_is_a_1_128_w_128_128); every other use of PerBlock is refused in
+    the reference's words (:260)."""
     if granularity is None:
         return default(), default()
+    uses_block = isinstance(granularity, PerBlock) or (isinstance(granularity, (list, tuple)) and any(isinstance(g, PerBlock) for g in granularity))
+    if uses_block:
+        if block_pair and isinstance(granularity, (list, tuple)) and tuple(granularity) == _BLOCK_PAIR:
+            return _BLOCK_PAIR
+        raise ValueError(f"Unsupported granularity types: {granularity}.")
     if isinstance(granularity, Granularity):
         pair = (granularity, granularity)
     elif isinstance(granularity, (list, tuple)):
@@ -193,7 +203,8 @@ class Float8MMConfig:
 class Float8DynamicActivationFloat8WeightConfig(AOBaseConfig):
     """float8 e4m3 dynamic activation x float8 weight (reference quant_api.py:1112-1297; same fields in the same order, so that a
     config the reference serialised decodes here).  granularity: None = PerTensor for both (the reference's default), PerRow() (the
-    BASELINE configuration), or [activation, weight] of the same type."""
+    BASELINE configuration), [activation, weight] of the same type, or exactly [PerBlock([1, 128]), PerBlock([128, 128])]: 1 x 128
+    activation blocks and 128 x 128 weight blocks (its default mm_config has use_fast_accum False, :1159-1172)."""
 
     activation_dtype: object = None  # torch.float8_e4m3fn (None: that); gfx950 implements OCP e4m3fn only
     weight_dtype: object = None
@@ -212,7 +223,8 @@ class Float8DynamicActivationFloat8WeightConfig(AOBaseConfig):
     def __post_init__(self):
         import torch
 
-        act, weight = _normalize_granularity(self.granularity, PerTensor, "Float8DynamicActivationFloat8WeightConfig")
+        act, weight = _normalize_granularity(self.granularity, PerTensor, "Float8DynamicActivationFloat8WeightConfig", block_pair=True)
+        blockwise = isinstance(act, PerBlock)
         if type(act) is not type(weight):
             raise ValueError(f"Different granularities for activation and weight are not supported: {act}, {weight}")
         self.granularity = [act, weight]
@@ -227,8 +239,13 @@ class Float8DynamicActivationFloat8WeightConfig(AOBaseConfig):
         self.kernel_preference = KernelPreference(self.kernel_preference)
         if self.kernel_preference not in (KernelPreference.AUTO, KernelPreference.TORCH):
             raise NotImplementedError(f"kernel_preference {self.kernel_preference.value} names a library that is not this backend; use AUTO")
+        if blockwise:  # reference quant_api.py:1159-1172
+            if self.version < 2:
+                raise ValueError("blockwise float8 (PerBlock([1, 128]) x PerBlock([128, 128])) requires version >= 2")
+            if self.activation_value_lb is not None or self.activation_value_ub is not None:
+                raise ValueError("activation_value_lb / activation_value_ub are not supported with blockwise float8 granularity")
         if self.mm_config is None:
-            self.mm_config = Float8MMConfig(use_fast_accum=True)
+            self.mm_config = Float8MMConfig(use_fast_accum=not blockwise)
 
 
 @dataclass
@@ -291,6 +308,8 @@ def _encode(value):
 
     import torch
 
+    if isinstance(value, PerBlock):  # upstream's JSON only carries a list here (granularity.py:138-141)
+        return {"_type": "PerBlock", "_version": 1, "_data": {"block_size": list(value.block_size)}}
     if isinstance(value, AOBaseConfig) or (dataclasses.is_dataclass(value) and not isinstance(value, type)):
         if dataclasses.is_dataclass(value):
             items = [(f.name, getattr(value, f.name)) for f in dataclasses.fields(value)]

@@ -1,5 +1,6 @@
 """Float8Tensor: float8 e4m3 weight (PerRow or PerTensor scales) with dynamic activations of the same granularity, or weight-only
-under bf16 activations (act_quant_kwargs=None: ao_wo8_linear), MI355X-native.
+under bf16 activations (act_quant_kwargs=None: ao_wo8_linear), or 128 x 128 block scales with 1 x 128 dynamic activation blocks
+(PerBlock: ao_fp8_block_linear), MI355X-native.
 
 Host-side mirror of torchao/quantization/quantize_/workflows/float8/float8_tensor.py for the branch
 SURVEY.md 8(a9, a10) scopes -- PerRow, KernelPreference TORCH/AUTO on AMD, i.e. what
@@ -15,7 +16,7 @@ import torch.nn.functional as F
 
 from .. import ops
 from .base_tensor import LowBitTensorBase, aten
-from .granularity import Granularity, PerRow, PerTensor
+from .granularity import Granularity, PerBlock, PerRow, PerTensor, get_block_size
 
 __all__ = ["Float8Tensor", "QuantizeTensorToFloat8Kwargs"]
 
@@ -64,13 +65,39 @@ class QuantizeTensorToFloat8Kwargs:
     hp_value_ub: Optional[float] = None
 
 
-def _check(granularity, float8_dtype):
-    if not isinstance(granularity, (PerRow, PerTensor)):
-        raise NotImplementedError(f"Float8Tensor on MI355X implements PerRow / PerTensor, got {granularity} (blockwise scaling is outside SURVEY.md section 8)")
+_ACT_BLOCK = PerBlock((1, 128))     # 1 x 128 activation blocks
+_WEIGHT_BLOCK = PerBlock((128, 128))  # 128 x 128 weight blocks
+
+
+def _check(granularity, float8_dtype, role=None):
+    """role: "activation" admits PerBlock((1, 128)), "weight" PerBlock((128, 128)), None (a cast on its own) either."""
+    if isinstance(granularity, PerBlock):
+        allowed = {"activation": (_ACT_BLOCK,), "weight": (_WEIGHT_BLOCK,), None: (_ACT_BLOCK, _WEIGHT_BLOCK)}[role]
+        if granularity not in allowed:
+            raise NotImplementedError(f"Float8Tensor on MI355X implements blockwise scales as PerBlock([1, 128]) activations x "
+                                      f"PerBlock([128, 128]) weights only, got {granularity} for the {role or 'tensor'}")
+    elif not isinstance(granularity, (PerRow, PerTensor)):
+        raise NotImplementedError(f"Float8Tensor on MI355X implements PerRow / PerTensor / PerBlock([1, 128]) x PerBlock([128, 128]), got {granularity}")
     if isinstance(granularity, PerRow) and granularity.dim != -1:
         raise NotImplementedError(f"Float8Tensor on MI355X implements PerRow(dim=-1) only, got {granularity}")
     if float8_dtype != torch.float8_e4m3fn:
         raise NotImplementedError(f"Float8Tensor on MI355X implements float8_e4m3fn only, got {float8_dtype}")
+
+
+def _blockwise(t):
+    """A tensor with 128 x 128 block scales, or one whose activations are cast in 1 x 128 blocks.  (A [128, 128] tensor with ONE scale
+    has block_size [128, 128] under PerTensor as well; the two are the same tensor, and it stays on the tensorwise path.)"""
+    act = t.act_quant_kwargs
+    if act is not None and isinstance(act.granularity, PerBlock):
+        return True
+    bs = list(t.block_size)
+    return len(bs) >= 2 and bs[-2:] == [128, 128] and tuple(t.shape[-2:]) != (128, 128)
+
+
+def _refuse_blockwise(t, what):
+    if _blockwise(t):
+        raise NotImplementedError(f"{what} is not implemented for Float8Tensor with blockwise scales (block_size {list(t.block_size)}) on "
+                                  "MI355X: the blockwise path takes a 2-D weight in F.linear / mm, t / transpose and slices at multiples of 128")
 
 
 class Float8Tensor(LowBitTensorBase):
@@ -113,6 +140,17 @@ class Float8Tensor(LowBitTensorBase):
             # reference quant_api.py:1211-1216: PerRow quantization only works for bfloat16 precision; the MI355X kernels take
             # bfloat16 for PerTensor too
             raise AssertionError("PerRow quantization only works for bfloat16 precision input weight")
+        if isinstance(granularity, PerBlock):
+            # reference :233-242 with get_block_size (utils.py:603-621): a shape the block does not divide raises and names the shape
+            block_size = list(get_block_size(tuple(hp_tensor.shape), granularity))
+            if granularity == _ACT_BLOCK:  # one scale per 128 columns of every row: [..., K] -> scale [..., K / 128]
+                qdata, scale = ops.fp8_quantize_block_1x128(hp_tensor)
+            elif hp_tensor.dim() != 2:
+                raise NotImplementedError(f"Float8Tensor.from_hp with blockwise scales (PerBlock([128, 128])) takes 2-D weights on MI355X, got "
+                                          f"{tuple(hp_tensor.shape)}: 3-D expert weights are not implemented")
+            else:
+                qdata, scale = ops.fp8_quantize_block_128x128(hp_tensor)
+            return cls(qdata, scale, block_size, hp_tensor.dtype, act_quant_kwargs=act_quant_kwargs)
         if hp_tensor.dim() not in (2, 3):
             raise NotImplementedError("Float8Tensor.from_hp on MI355X takes 2-D weights or 3-D [E, N, K] expert weights")
         k = hp_tensor.shape[-1]
@@ -126,8 +164,13 @@ class Float8Tensor(LowBitTensorBase):
         return cls(qdata, scale, [1] * (hp_tensor.dim() - 1) + [k], hp_tensor.dtype, act_quant_kwargs=act_quant_kwargs)
 
     def dequantize(self, output_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
-        """reference :255-275: fp8 -> fp32 * scale, then cast"""
-        return (self.qdata.to(torch.float32) * self.scale.to(torch.float32)).to(output_dtype or self.dtype)
+        """reference :255-275: fp8 -> fp32 * scale, then cast; block scales are expanded block by block first
+        (_maybe_expand_scale_to_tensor_shape; a ragged last block of a checkpoint weight keeps its leading part)"""
+        scale = self.scale.to(torch.float32)
+        for i in range(self.qdata.dim() if scale.dim() == self.qdata.dim() else 0):  # (a scale of lower rank broadcasts as it is)
+            if scale.shape[i] not in (1, self.qdata.shape[i]):
+                scale = scale.repeat_interleave(self.block_size[i], dim=i).narrow(i, 0, self.qdata.shape[i])
+        return (self.qdata.to(torch.float32) * scale).to(output_dtype or self.dtype)
 
 
 implements = Float8Tensor.implements
@@ -188,6 +231,8 @@ def _(func, types, args, kwargs):
     tensors = args[0]
     dim = (args[1] if len(args) > 1 else kwargs.get("dim", 0)) % tensors[0].dim()
     t0 = tensors[0]
+    for t in tensors:
+        _refuse_blockwise(t, "aten.cat")
     for t in tensors[1:]:
         assert t0.qdata.dim() == t.qdata.dim() and t0.scale.dim() == t.scale.dim()
         assert list(t0.block_size) == list(t.block_size) and t0.act_quant_kwargs == t.act_quant_kwargs
@@ -248,6 +293,7 @@ def _(func, types, args, kwargs):
     the scales are split too, along a blocked dimension every chunk keeps the scale (its block is the chunk)."""
     self, size = args[0], args[1]
     dim = args[2] if len(args) > 2 else kwargs.get("dim", 0)
+    _refuse_blockwise(self, "aten.split")
     assert isinstance(size, int), "unimplemented"
     dim = dim % self.dim()
     qs = torch.split(self.qdata, size, dim)
@@ -285,6 +331,38 @@ def _weight_only_linear(x, w, bias, out_dtype):
     return y.to(out_dtype)
 
 
+def _blockwise_linear(x, w, bias, out_dtype):
+    """reference :433-447: the activation cast in 1 x 128 blocks, blockwise_fp8_gemm on the 128 x 128 block-scaled weight (bf16 out), the
+    bias added to that bf16 tensor -- the cast and the GEMM in one or two HIP launches (ops.fp8_block_linear), the bias inside."""
+    act = w.act_quant_kwargs
+    if act is None:
+        raise NotImplementedError("weight-only linear is not implemented for Float8Tensor with blockwise scales (block_size "
+                                  f"{list(w.block_size)}) on MI355X: give it act_quant_kwargs with granularity PerBlock([1, 128])")
+    _check(act.granularity, act.float8_dtype, "activation")
+    if act.granularity != _ACT_BLOCK or list(w.block_size) != [128, 128] or w.qdata.dim() != 2:
+        raise NotImplementedError("Float8Tensor linear with blockwise scales on MI355X takes PerBlock([1, 128]) activations and a 2-D weight "
+                                  f"with block_size [128, 128], got activations {act.granularity}, weight {tuple(w.shape)} with block_size "
+                                  f"{list(w.block_size)}")
+    if act.hp_value_lb is not None or act.hp_value_ub is not None:
+        raise NotImplementedError("hp_value_lb / hp_value_ub are not implemented for blockwise activation scales")
+    if w.qdata.dtype != torch.float8_e4m3fn:
+        raise NotImplementedError(f"Float8Tensor on MI355X implements float8_e4m3fn only, got {w.qdata.dtype}")
+    _require_bf16_activation(x, "Float8Tensor linear with blockwise scales (1 x 128 activation blocks)")
+    x2 = x.reshape(-1, x.shape[-1]).contiguous()
+    n = w.qdata.shape[0]
+    if x2.shape[0] == 0:
+        y = x2.new_zeros((0, n))
+    else:
+        from ..torch_ops import kernels
+
+        y = kernels(x2).fp8_block_linear(x2, w.qdata, w.scale.to(torch.float32), bias)
+        bias = None
+    y = y.reshape(*x.shape[:-1], n)
+    if bias is not None:
+        y = y + bias.to(y.dtype)
+    return y.to(out_dtype)
+
+
 def _float8_linear(x, w, bias):
     """reference :278-469 -> preprocess_data / preprocess_scale -> _scaled_mm(A row-major,
     B = W.t() column-major, scale_a [M,1], scale_b [1,N], bias, out_dtype, use_fast_accum)."""
@@ -292,6 +370,8 @@ def _float8_linear(x, w, bias):
     out_dtype = x.dtype
     if w.act_pre_scale is not None:
         x = x * w.act_pre_scale
+    if _blockwise(w):
+        return _blockwise_linear(x, w, bias, out_dtype)
     if w.act_quant_kwargs is None:
         return _weight_only_linear(x, w, bias, out_dtype)
     _check(w.act_quant_kwargs.granularity, w.act_quant_kwargs.float8_dtype)
@@ -338,6 +418,24 @@ def _(func, types, args, kwargs):
     assert step == 1 and dim in (0, 1)
     end = min(end, self.shape[dim])
     pre = self.act_pre_scale
+    if _blockwise(self) or self.block_size[-1] not in (1, self.shape[-1]):
+        # _slice_scale_for_dimension (float8/inference.py:126-174): along a blocked dimension the scales of the blocks the slice covers,
+        # [start // block, ceil(end / block)).  A boundary inside a block would leave a scale that covers elements outside the slice.
+        assert self.qdata.dim() == 2, "slicing a Float8Tensor with blockwise scales takes a 2-D tensor"
+        start = start + self.shape[dim] if start < 0 else start
+        end = end + self.shape[dim] if end < 0 else end
+        bs = self.block_size[dim]
+        if bs == 1:
+            s = self.scale.narrow(dim, start, max(end - start, 0))
+        else:
+            if start % bs != 0 or (end % bs != 0 and end != self.shape[dim]):
+                raise NotImplementedError(f"slicing a Float8Tensor with blockwise scales along dimension {dim} takes boundaries at multiples of "
+                                          f"{bs}, got [{start}:{end}]")
+            s = self.scale.narrow(dim, start // bs, max((end + bs - 1) // bs - start // bs, 0))
+        q = self.qdata.narrow(dim, start, max(end - start, 0)).contiguous()
+        if dim == 1 and pre is not None and pre.numel() == self.shape[1]:
+            pre = pre.reshape(-1)[start:end]
+        return Float8Tensor(q, s.contiguous(), list(self.block_size), self.dtype_, self.act_quant_kwargs, pre)
     per_tensor = self.scale.numel() == 1
     if dim == 0:
         q = self.qdata[start:end].contiguous()
@@ -365,6 +463,7 @@ def _(func, types, args, kwargs):
     mat_a, mat_b = args[0], args[1]
     offs = args[2] if len(args) > 2 else kwargs.get("offs", None)
     assert isinstance(mat_b, Float8Tensor)
+    _refuse_blockwise(mat_b, "aten._grouped_mm")
     assert offs is not None, "offs is required for _grouped_mm"
     is_b_transposed = mat_b.qdata.stride(-2) < mat_b.qdata.stride(-1)
     assert is_b_transposed and mat_b.qdata.dim() == 3 and mat_a.dim() == 2, "unsupported"

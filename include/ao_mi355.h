@@ -623,6 +623,45 @@ int ao_wo8_linear_route(int fmt, int64_t M, int64_t N, int64_t K, int32_t* out, 
  * calling thread's weight-only linears (0 the product route, 1 streaming, 2 tiled); the route query reports the forced form. */
 int ao_wo8_linear_set_form(int form);
 
+/* ---- blockwise float8 linears: 1 x 128 activation blocks, 128 x 128 weight blocks, fp32 scales (fp8_block_kernels.hip) ----------------
+ * Float8DynamicActivationFloat8WeightConfig with granularity [PerBlock([1, 128]), PerBlock([128, 128])] (quant_api.py:1112-1297), the layout
+ * of the DeepSeek-V3 / Qwen3 FP8 checkpoints (weight_scale_inv = the [N/128][K/128] scale).  Upstream runs it on SM 8.9 / XPU only
+ * (torchao/float8/inference.py:306-310) through a Triton GEMM (quantize_/workflows/float8/kernels.py:56-128).  Codes are e4m3fn bytes,
+ * row-major and K-contiguous.  Shapes of the linears: M >= 0 (M = 0: OK, nothing launched), N >= 1 (ragged N and M are masked; b_scale has
+ * ceil(N / 128) rows), K a positive multiple of 128, each operand below 2 GiB.  x / q / a / b 16-byte aligned, scales 4-byte, bias and out
+ * 2-byte.  Null pointers and bad shapes are rejected on the host before any launch.  DESIGN.md 4.12. */
+/* The stream form runs up to this many rows, the 128 x 128 LDS-tiled form beyond: the hand-over with the least time summed over the
+ * Llama-3-8B five shapes and M = 16 .. 256 with each form forced (profiles/fp8_block_linear.jsonl). */
+#define AO_FP8_BLOCK_STREAM_MAX_ROWS 192
+/* Replaces Float8Tensor.from_hp(x, e4m3fn, PerBlock([1, 128])), kernel_choice "torch" (float8_tensor.py:233-242, quant_primitives.py:2173-2212,
+ * :2271-2287): x bf16 [M][K] -> q [M][K], scale fp32 [M][K/128] = f32(bf16(amax_block / 448)), q = e4m3_sat(f32(x) / scale); byte for byte
+ * the reference's (a block of zeros: scale 0, NaN codes).  No row-wide amax pass. */
+int ao_fp8_quantize_block_1x128(const uint16_t* x, uint8_t* q, float* scale, int64_t M, int64_t K, void* stream);
+/* The same cast with PerBlock([128, 128]) (same lines): w bf16 [N][K], N and K multiples of 128 -> q [N][K], scale fp32 [N/128][K/128]. */
+int ao_fp8_quantize_block_128x128(const uint16_t* w, uint8_t* q, float* scale, int64_t N, int64_t K, void* stream);
+/* Replaces blockwise_fp8_gemm (kernels.py:56-128, :85-97 the loop; float8_tensor.py:433-447 the call and the bias).  Per output element, fp32:
+ *   acc = 0;  for kb ascending: p = sum of the block's 128 products a[m][k] b[n][k];  acc += (p * a_scale[m][kb]) * b_scale[n / 128][kb]
+ *   t = bf16(acc);  out = bias ? bf16(f32(t) + f32(bias[n])) : t      (bf16 before the bias; bf16 out whatever the bias)
+ * K parts are cut at multiples of 128 and added in part order: a launch is reproducible.  a [M][K], a_scale [M][K/128], b [N][K],
+ * b_scale [ceil(N/128)][K/128], bias bf16 [N] or NULL, out bf16 [M][N]. */
+int ao_fp8_block_linear(const uint8_t* a, const float* a_scale, const uint8_t* b, const float* b_scale, const uint16_t* bias, uint16_t* out,
+                        int64_t M, int64_t N, int64_t K, void* stream);
+/* ao_fp8_quantize_block_1x128 followed by ao_fp8_block_linear in ONE launch (float8_tensor.py:433-447 does the two steps), for the shapes the
+ * streaming form takes (ao_fp8_block_dynamic_linear_fits, host logic: 1 when the route is fp8_block_stream_kernel); bit-identical to the
+ * two launches.  Other shapes return AO_ERR_INVALID_ARGUMENT.  x bf16 [M][K], 16-byte aligned. */
+int ao_fp8_block_dynamic_linear_fits(int64_t M, int64_t N, int64_t K);
+int ao_fp8_block_dynamic_linear(const uint16_t* x, const uint8_t* b, const float* b_scale, const uint16_t* bias, uint16_t* out, int64_t M,
+                                int64_t N, int64_t K, void* stream);
+/* The route both blockwise linear entries launch (host logic only; kernels.py:56-128 has one kernel, this library two forms):
+ * out[cap >= 7] = kernel (0 = invalid shape or more than 65535 grid rows, 1 fp8_block_stream_kernel, 2 fp8_block_tile_kernel), waves per
+ * workgroup, m-tiles of 16 per workgroup, tile rows, tile columns, grid x, grid y. */
+int ao_fp8_block_linear_route(int64_t M, int64_t N, int64_t K, int32_t* out, int cap);
+/* "fp8_block_stream_kernel", "fp8_block_tile_kernel" or "invalid": the kernel of that route (kernels.py:56-128). */
+const char* ao_fp8_block_linear_kernel_name(int64_t M, int64_t N, int64_t K);
+/* Measurement only (no reference counterpart: kernels.py:56-128 has one path): force the form of the calling thread's blockwise linears
+ * (0 the product route, 1 streaming, 2 tiled); the route queries report the forced form. */
+int ao_fp8_block_linear_set_form(int form);
+
 #ifdef __cplusplus
 }
 #endif
