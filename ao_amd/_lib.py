@@ -127,6 +127,10 @@ _SIGNATURES = {
     "ao_fp8_block_linear_route": [_I64, _I64, _I64, _P, _INT],
     "ao_fp8_block_linear_kernel_name": [_I64, _I64, _I64],
     "ao_fp8_block_linear_set_form": [_INT],
+    "ao_fp8_block_grouped_mm": [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P],
+    "ao_fp8_block_grouped_mm_route": [_I64, _I64, _I64, _I64, _P, _INT],
+    "ao_fp8_block_grouped_mm_kernel_name": [_I64, _I64, _I64, _I64],
+    "ao_fp8_block_grouped_mm_set_form": [_INT],
 }
 
 
@@ -172,6 +176,8 @@ def lib():
             l.ao_mx_linear_kernel_name.restype = ctypes.c_char_p
         if hasattr(l, "ao_fp8_block_linear_kernel_name"):
             l.ao_fp8_block_linear_kernel_name.restype = ctypes.c_char_p
+        if hasattr(l, "ao_fp8_block_grouped_mm_kernel_name"):
+            l.ao_fp8_block_grouped_mm_kernel_name.restype = ctypes.c_char_p
         if hasattr(l, "ao_fp8_int4_kernel_name"):
             l.ao_fp8_int4_kernel_name.restype = ctypes.c_char_p
         l.ao_moe_padded_rows.restype = _I64

@@ -17,6 +17,12 @@
 //   K parts (the waves of the stream form's workgroup) are cut at multiples of 128 and added in part order: a launch is reproducible.
 //   Any N >= 1: b_s has ceil(N / 128) rows; ragged N and M are masked (kernels.py's offs_n // BLOCK_SIZE_K).  K a positive multiple of 128.
 //
+// The grouped GEMM for MoE experts (ao_fp8_block_grouped_mm; the reference has it as a training prototype only,
+// prototype/moe_training/blockwise_fp8/grouped_mm.py over DeepGEMM or the bf16 emulation of blockwise_fp8_training/grouped_kernels.py:78-93)
+// applies the same chain, without a bias, per token group [offs[e-1], offs[e]) against expert e: fp8_block_grouped_stream_kernel (grid
+// (ceil(N / 16), E), the group's rows 16 MT at a time) and the GROUPED instantiation of fp8_block_tile_kernel, routed on the mean group
+// size (grouped_route).
+//
 // Two forms, one route (block_route: this family's shape check, seam and forced form over the plans of two_form_route.h)
 // read by the launches and by ao_fp8_block_linear_route / ao_fp8_block_linear_kernel_name:
 //   fp8_block_stream_kernel: the weight is streamed once; a workgroup owns 16 columns and 16 / 32 / 64 rows and splits K over its waves
@@ -203,6 +209,26 @@ __global__ __launch_bounds__(64 * WAVES) void fp8_block_stream_kernel(BlockArgs 
   }
 }
 
+// ---- grouped (MoE experts) ------------------------------------------------------------------------------------------------------
+// Token group e = rows [offs[e-1], offs[e]) of a (offs[-1] = 0) against expert e's weight b[e] and scales b_scale[e]; the dense chain
+// per element, no bias.  The kernels only read offs: a group's bounds are clamped to [0, M_total] (a bad offs cannot address outside a
+// or out) and a non-increasing pair is an empty group.
+struct GroupedArgs {
+  const uint8_t* a;       // codes [M_total][K]
+  const float* a_scale;   // [M_total][K/128]
+  const uint8_t* b;       // codes [E][N][K]
+  const float* b_scale;   // [E][ceil(N/128)][K/128]
+  const int32_t* offs;    // [E] cumulative group ends
+  uint16_t* out;          // bf16 [M_total][N]
+  int M_total, N, K, E;
+};
+
+__device__ __forceinline__ int clamp_row(int r, int M_total) { return r < 0 ? 0 : (r > M_total ? M_total : r); }
+__device__ __forceinline__ void group_bounds(const GroupedArgs& p, int e, int& row_begin, int& row_end) {
+  row_begin = clamp_row(e > 0 ? p.offs[e - 1] : 0, p.M_total);
+  row_end = clamp_row(p.offs[e], p.M_total);
+}
+
 // ---- LDS-tiled form -------------------------------------------------------------------------------------------------------------
 // Stage layout: A then B, 128 rows of 128 bytes each, the eight 16-byte pieces of a row swizzled by row so that the 16 lanes of a
 // fragment read hit different banks: piece c of row r sits at slot r * 8 + (c ^ (r % 8)).
@@ -234,10 +260,37 @@ __device__ __forceinline__ void tile_frag(const char* op, int r, int kq, u32x4& 
   v1 = *reinterpret_cast<const u32x4*>(op + (r * 8 + ((kq + 4) ^ (r & 7))) * 16);
 }
 
-__global__ __launch_bounds__(256) void fp8_block_tile_kernel(BlockArgs p) {
+// 128 x 128 output tiles by workgroups of four waves: ONE body, two instantiations.
+//   GROUPED false, "fp8_block_tile_kernel": the dense linear; q is the problem, the tile row is blockIdx.y.
+//   GROUPED true, "fp8_block_grouped_tile_kernel": grid y is the host's upper bound ceil(M_total / 128) + E on the 128-row tiles of all
+//     groups (a group adds at most one partial tile); a workgroup finds its (group, tile) by walking offs and leaves when it has none;
+//     p is then the group's row window [row_begin, row_end) against its expert, expressed by offset base pointers (so the buffer
+//     ranges end at the window).
+// A template and not a device function called by two kernels: as an always-inline function the same body compiled to 256 + 36
+// registers in the dense kernel (one wave a SIMD) where this form keeps the 224 + 4 (two waves a SIMD) it had before the grouped GEMM.
+template <bool GROUPED>
+__global__ __launch_bounds__(256) void fp8_block_tile_kernel(std::conditional_t<GROUPED, GroupedArgs, BlockArgs> q) {
+  unsigned tile_y = blockIdx.y;
+  BlockArgs p;
+  if constexpr (GROUPED) {
+    int t = blockIdx.y, e = 0, row_begin = 0, row_end = 0;
+    for (; e < q.E; ++e) {
+      group_bounds(q, e, row_begin, row_end);
+      const int tiles = row_end > row_begin ? (row_end - row_begin + 127) >> 7 : 0;
+      if (t < tiles) break;
+      t -= tiles;
+    }
+    if (e == q.E) return;
+    const int kb = q.K >> 7;
+    p = BlockArgs{q.a + (size_t)row_begin * q.K, q.a_scale + (size_t)row_begin * kb, nullptr, q.b + (size_t)e * q.N * q.K,
+                  q.b_scale + (size_t)e * ((q.N + 127) >> 7) * kb, nullptr, q.out + (size_t)row_begin * q.N, row_end - row_begin, q.N, q.K};
+    tile_y = t;
+  } else {
+    p = q;
+  }
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, kq = lane >> 4;
-  const int m0 = blockIdx.y * 128, n0 = blockIdx.x * 128;
+  const int m0 = tile_y * 128, n0 = blockIdx.x * 128;
   const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
   const int kblocks = p.K >> 7;
   const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void*)p.a, 0, p.M * p.K, 0x00020000);
@@ -305,6 +358,66 @@ __global__ __launch_bounds__(256) void fp8_block_tile_kernel(BlockArgs p) {
   }
 }
 
+// ---- grouped streaming form -----------------------------------------------------------------------------------------------------
+// Grid (ceil(N / 16), E): a workgroup owns 16 columns of one expert and walks its group's rows 16 MT at a time; per pass the step of
+// fp8_block_stream_kernel (the weight block comes from L2 from the second pass on), the meeting in wave order, and a barrier before
+// the next pass reuses the meeting buffer.
+template <int MT, int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void fp8_block_grouped_stream_kernel(GroupedArgs p) {
+  __shared__ float red[WAVES][MT][256];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), kq = lane >> 4, nl = lane & 15;
+  const int e = blockIdx.y;
+  int row_begin, row_end;
+  group_bounds(p, e, row_begin, row_end);
+  if (row_end <= row_begin) return;  // an empty group: the whole workgroup leaves
+  const int n = blockIdx.x * 16 + nl;
+  const int kblocks = p.K >> 7;
+  const int ks0 = (kblocks * wave) / WAVES, ks1 = (kblocks * (wave + 1)) / WAVES;
+  const bool nv = n < p.N;
+  // the expert's base in 64 bits: the whole b may pass 2 GiB
+  const uint8_t* brow = p.b + (size_t)e * p.N * p.K + (size_t)(nv ? n : 0) * p.K + 16 * kq;
+  const float* bs_row = p.b_scale + ((size_t)e * ((p.N + 127) >> 7) + (blockIdx.x >> 3)) * kblocks;
+  const u32x4 z = {0u, 0u, 0u, 0u};
+  for (int m0 = row_begin; m0 < row_end; m0 += 16 * MT) {
+    f32x4 acc[MT];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) acc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 2
+    for (int step = ks0; step < ks1; ++step) {
+      const u32x4 b0 = nv ? ld16(brow + step * 128) : z, b1 = nv ? ld16(brow + step * 128 + 64) : z;
+      const float bs = bs_row[step];
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) {
+        u32x4 a0, a1;
+        f32x4 as;
+        load_block_codes(p.a, m0 + mt * 16 + nl, row_end, step, kq, p.K, a0, a1);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = m0 + mt * 16 + 4 * kq + r;
+          as[r] = row < row_end ? p.a_scale[(size_t)row * kblocks + step] : 0.f;
+        }
+        const f32x4 prod = mfma8_k128<false>(a0, a1, b0, b1, f32x4{0.f, 0.f, 0.f, 0.f});
+        acc[mt] = fp8_block_acc(acc[mt], prod, as, bs);
+      }
+    }
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) park_tile(&red[wave][mt][0], kq, nl, acc[mt]);
+    __syncthreads();
+    // the partial tiles are added in wave order
+    for (int idx = threadIdx.x; idx < MT * 256; idx += 64 * WAVES) {
+      const int mt = idx >> 8, rc = idx & 255;
+      const int row = m0 + mt * 16 + (rc >> 4), col = blockIdx.x * 16 + (rc & 15);
+      if (row < row_end && col < p.N) {
+        float sum = red[0][mt][rc];
+#pragma unroll
+        for (int w = 1; w < WAVES; ++w) sum += red[w][mt][rc];
+        p.out[(size_t)row * p.N + col] = f32_to_bf16_bits(fp8_block_out(sum));
+      }
+    }
+    __syncthreads();  // the next pass parks into the same buffer
+  }
+}
+
 // ---- launches -------------------------------------------------------------------------------------------------------------------
 // (4 m-tiles x 16 waves: the meeting buffer would pass the static LDS; the stream-form plan caps 4 m-tiles at 8 waves)
 template <bool CAST>
@@ -320,7 +433,7 @@ int launch_stream(const TwoFormRoute& r, const BlockArgs& a, hipStream_t st) {
 
 int launch_tile(const TwoFormRoute& r, const BlockArgs& a, hipStream_t st) {
   constexpr size_t smem = 2 * kStageBytes;
-  auto kern = fp8_block_tile_kernel;
+  auto kern = fp8_block_tile_kernel<false>;
   if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), smem, "hipFuncSetAttribute(fp8_block_tile_kernel)")) return rc;
   ao::launch(kern, dim3(r.grid_x, r.grid_y), dim3(256), smem, st, a);
   AO_LAUNCH_CHECK("fp8_block_tile_kernel launch");
@@ -334,6 +447,50 @@ int check_linear(const char* fn, int64_t M, int64_t N, int64_t K) {
 }
 
 bool aligned_to(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+// ---- the grouped route ------------------------------------------------------------------------------------------------------------
+// Without a sync the host knows only M_total and E: the route keys on the mean group size ceil(M_total / E).
+constexpr int kGroupedStreamMaxRows = AO_FP8_BLOCK_GROUPED_STREAM_MAX_ROWS;
+
+thread_local int g_grouped_form = 0;  // ao_fp8_block_grouped_mm_set_form: 0 the product route, 1 stream, 2 tile
+
+bool grouped_shape_ok(int64_t M_total, int64_t N, int64_t K, int64_t E) {
+  if (E < 1 || E > 65535) return false;
+  return block_shape_ok(M_total, N, K);  // M_total K and the per-expert N K below 2 GiB; the expert base is 64-bit
+}
+
+// kernel 1: fp8_block_grouped_stream_kernel, grid (ceil(N / 16), E), m-tiles and waves of the stream plan at the mean group size;
+// 2: fp8_block_grouped_tile_kernel = fp8_block_tile_kernel<true>, grid (ceil(N / 128), ceil(M_total / 128) + E)
+TwoFormRoute grouped_route(int64_t M_total, int64_t N, int64_t K, int64_t E) {
+  if (!grouped_shape_ok(M_total, N, K, E)) return TwoFormRoute{};
+  const int64_t mean = (M_total + E - 1) / E;
+  const int form = g_grouped_form != 0 ? g_grouped_form : (mean <= kGroupedStreamMaxRows ? 1 : 2);
+  TwoFormRoute r = two_form_route(form, form == 1 ? mean : M_total, N, K, 128);
+  if (r.kernel == 0) return TwoFormRoute{};
+  const int64_t gy = form == 1 ? E : (int64_t)r.grid_y + E;
+  if (gy > 65535) return TwoFormRoute{};
+  r.grid_y = (int)gy;
+  return r;
+}
+
+int launch_grouped_stream(const TwoFormRoute& r, const GroupedArgs& a, hipStream_t st) {
+  if (int rc = with_stream_form<false>("fp8_block_grouped_stream_kernel", r, [&](auto mt, auto waves) {
+        constexpr int MT = decltype(mt)::value, WAVES = decltype(waves)::value;
+        ao::launch(fp8_block_grouped_stream_kernel<MT, WAVES>, dim3(r.grid_x, r.grid_y), dim3(64 * WAVES), 0, st, a);
+      }))
+    return rc;
+  AO_LAUNCH_CHECK("fp8_block_grouped_stream_kernel launch");
+  return AO_OK;
+}
+
+int launch_grouped_tile(const TwoFormRoute& r, const GroupedArgs& a, hipStream_t st) {
+  constexpr size_t smem = 2 * kStageBytes;
+  auto kern = fp8_block_tile_kernel<true>;
+  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), smem, "hipFuncSetAttribute(fp8_block_tile_kernel<GROUPED>)")) return rc;
+  ao::launch(kern, dim3(r.grid_x, r.grid_y), dim3(256), smem, st, a);
+  AO_LAUNCH_CHECK("fp8_block_grouped_tile_kernel (fp8_block_tile_kernel<GROUPED>) launch");
+  return AO_OK;
+}
 
 }  // namespace
 }  // namespace ao
@@ -431,4 +588,49 @@ extern "C" int ao_fp8_block_dynamic_linear(const uint16_t* x, const uint8_t* b, 
              __func__);
   const BlockArgs args{nullptr, nullptr, x, b, b_scale, bias, out, (int)M, (int)N, (int)K};
   return launch_stream<true>(r, args, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int ao_fp8_block_grouped_mm_route(int64_t M_total, int64_t N, int64_t K, int64_t E, int32_t* out, int cap) {
+  AO_REQUIRE_PTR(out);
+  AO_REQUIRE(cap >= 7, "ao_fp8_block_grouped_mm_route: cap must be >= 7, got %d", cap);
+  write_route(grouped_route(M_total, N, K, E), out);
+  return AO_OK;
+}
+
+extern "C" const char* ao_fp8_block_grouped_mm_kernel_name(int64_t M_total, int64_t N, int64_t K, int64_t E) {
+  switch (grouped_route(M_total, N, K, E).kernel) {
+    case 1: return "fp8_block_grouped_stream_kernel";
+    case 2: return "fp8_block_grouped_tile_kernel";
+    default: return "invalid";
+  }
+}
+
+extern "C" int ao_fp8_block_grouped_mm_set_form(int form) {
+  AO_REQUIRE(form >= 0 && form <= 2, "ao_fp8_block_grouped_mm_set_form: form must be 0 (route), 1 (stream) or 2 (tile), got %d", form);
+  g_grouped_form = form;
+  return AO_OK;
+}
+
+extern "C" int ao_fp8_block_grouped_mm(const uint8_t* a, const float* a_scale, const uint8_t* b, const float* b_scale, const int32_t* offs,
+                                       uint16_t* out, int64_t M_total, int64_t N, int64_t K, int64_t E, void* stream) {
+  AO_REQUIRE(grouped_shape_ok(M_total, N, K, E),
+             "%s: bad shape M_total=%lld N=%lld K=%lld E=%lld (M_total >= 0, N >= 1, K a positive multiple of 128, 1 <= E <= 65535, "
+             "M_total K and the per-expert N K < 2 GiB)",
+             __func__, (long long)M_total, (long long)N, (long long)K, (long long)E);
+  AO_REQUIRE_PTR(b);
+  AO_REQUIRE_PTR(b_scale);
+  AO_REQUIRE_PTR(offs);
+  if (M_total == 0) return AO_OK;
+  AO_REQUIRE_PTR(a);
+  AO_REQUIRE_PTR(a_scale);
+  AO_REQUIRE_PTR(out);
+  AO_REQUIRE(aligned_to(a, 16) && aligned_to(b, 16), "%s: the codes must be 16-byte aligned", __func__);
+  AO_REQUIRE(aligned_to(a_scale, 4) && aligned_to(b_scale, 4) && aligned_to(offs, 4) && aligned_to(out, 2),
+             "%s: the scales and offs must be 4-byte, out 2-byte aligned", __func__);
+  const TwoFormRoute r = grouped_route(M_total, N, K, E);
+  AO_REQUIRE(r.kernel != 0, "%s: no route for M_total=%lld N=%lld K=%lld E=%lld (more than 65535 grid rows)", __func__, (long long)M_total,
+             (long long)N, (long long)K, (long long)E);
+  const GroupedArgs args{a, a_scale, b, b_scale, offs, out, (int)M_total, (int)N, (int)K, (int)E};
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  return r.kernel == 1 ? launch_grouped_stream(r, args, st) : launch_grouped_tile(r, args, st);
 }

@@ -1465,3 +1465,69 @@ def fp8_block_linear(x2, wq, w_scale, bias=None, fuse=None, out=None):
 
 __all__ += ["fp8_quantize_block_1x128", "fp8_quantize_block_128x128", "fp8_block_linear", "fp8_block_mm", "fp8_block_linear_kernel_name",
             "fp8_block_linear_route", "fp8_block_linear_set_form"]
+
+
+# ---- blockwise float8 grouped GEMM for MoE experts (include/ao_mi355.h) ------------------------------------------------
+FP8_BLOCK_GROUPED_KERNELS = {0: "invalid", 1: "fp8_block_grouped_stream_kernel", 2: "fp8_block_grouped_tile_kernel"}
+
+
+def fp8_block_grouped_mm_route(m_total: int, n: int, k: int, e: int) -> dict:
+    """The route fp8_block_grouped_mm launches for a shape (host logic only, ao_fp8_block_grouped_mm_route: it keys on the mean group
+    size ceil(M_total / E)); kernel "invalid" for shapes nothing takes."""
+    out = (ctypes.c_int32 * 7)()
+    _lib.check(_lib.lib().ao_fp8_block_grouped_mm_route(int(m_total), int(n), int(k), int(e), out, 7))
+    kernel, waves, mt, tile_m, tile_n, gx, gy = list(out)
+    return {"kernel": FP8_BLOCK_GROUPED_KERNELS.get(kernel, "invalid"), "waves": waves, "m_tiles": mt, "tile_m": tile_m, "tile_n": tile_n,
+            "grid": (gx, gy)}
+
+
+def fp8_block_grouped_mm_kernel_name(m_total: int, n: int, k: int, e: int) -> str:
+    return _lib.lib().ao_fp8_block_grouped_mm_kernel_name(int(m_total), int(n), int(k), int(e)).decode()
+
+
+def fp8_block_grouped_mm_set_form(form: int) -> None:
+    """Measurement only: 0 the product route, 1 the streaming form, 2 the tiled form (calling thread)."""
+    _lib.check(_lib.lib().ao_fp8_block_grouped_mm_set_form(int(form)))
+
+
+def fp8_block_grouped_mm(aq, a_scale, wq, w_scale, offs, out=None):
+    """The blockwise GEMM of fp8_block_mm per token group against that group's expert (ao_fp8_block_grouped_mm): aq e4m3 [M_total, K],
+    a_scale fp32 [M_total, K/128], wq e4m3 [E, N, K] (the experts as stored), w_scale fp32 [E, ceil(N/128), K/128], offs int32 [E]
+    cumulative group ends (read on the device) -> bf16 [M_total, N].  Rows past offs[-1] are not written: a fresh output is zero-filled,
+    an `out=` tensor keeps what it held there."""
+    name = "fp8_block_grouped_mm"
+    dev = _require_gpu(name, aq, a_scale, wq, w_scale, offs, out)
+    aq = _fp8_bytes(name, aq)
+    wq = _fp8_bytes(name, wq)
+    if aq.dim() != 2:
+        raise RuntimeError(f"{name}: the activation codes must be 2-D [M_total, K], got {tuple(aq.shape)}")
+    if wq.dim() != 3:
+        raise RuntimeError(f"{name}: the weight codes must be 3-D [E, N, K], got {tuple(wq.shape)}")
+    m, k = aq.shape
+    e, n, kw = wq.shape
+    if k != kw:
+        raise RuntimeError(f"{name}: K of the activation ({k}) and of the weight ({kw}) differ")
+    if k == 0 or k % 128 != 0:
+        raise RuntimeError(f"{name}: K must be a positive multiple of 128, got {k}")
+    if e < 1 or n < 1:
+        raise RuntimeError(f"{name}: the weight codes must hold at least one expert and one row, got {tuple(wq.shape)}")
+    if a_scale.dtype != torch.float32 or tuple(a_scale.shape) != (m, k // 128):
+        raise RuntimeError(f"{name}: the activation scales must be float32 [M_total, K/128] = {(m, k // 128)}, got {a_scale.dtype} "
+                           f"{tuple(a_scale.shape)}")
+    if w_scale.dtype != torch.float32 or tuple(w_scale.shape) != (e, (n + 127) // 128, k // 128):
+        raise RuntimeError(f"{name}: the weight scales must be float32 [E, ceil(N/128), K/128] = {(e, (n + 127) // 128, k // 128)}, got "
+                           f"{w_scale.dtype} {tuple(w_scale.shape)}")
+    if offs.dtype != torch.int32 or offs.dim() != 1 or offs.numel() != e:
+        raise RuntimeError(f"{name}: offs must be int32 [E] = [{e}], got {offs.dtype} {tuple(offs.shape)}")
+    if out is None:
+        y = torch.zeros((m, n), dtype=torch.bfloat16, device=dev)
+    else:
+        y = _bf16_out(name, out, m, n, dev)
+    if m > 0:
+        with _on(dev):
+            _lib.check(_lib.lib().ao_fp8_block_grouped_mm(_ptr(aq.contiguous()), _ptr(a_scale.contiguous()), _ptr(wq.contiguous()),
+                                                          _ptr(w_scale.contiguous()), _ptr(offs.contiguous()), _ptr(y), m, n, k, e, _stream()))
+    return y
+
+
+__all__ += ["fp8_block_grouped_mm", "fp8_block_grouped_mm_route", "fp8_block_grouped_mm_kernel_name", "fp8_block_grouped_mm_set_form"]

@@ -662,6 +662,42 @@ const char* ao_fp8_block_linear_kernel_name(int64_t M, int64_t N, int64_t K);
  * (0 the product route, 1 streaming, 2 tiled); the route queries report the forced form. */
 int ao_fp8_block_linear_set_form(int form);
 
+/* ---- blockwise float8 grouped GEMM for MoE experts (fp8_block_kernels.hip) -----------------------------------------------
+ * The routed experts of the DeepSeek-V3 / Qwen3 FP8 checkpoints: token group e = rows [offs[e-1], offs[e]) of a (offs[-1] = 0) against
+ * expert e, the chain of ao_fp8_block_linear per output element, in fp32, no bias:
+ *   acc = 0;  for kb ascending: p = sum of the block's 128 products a[m][k] b[e][n][k];  acc += (p * a_scale[m][kb]) * b_scale[e][n / 128][kb]
+ *   out[m][n] = bf16(acc)
+ * Upstream has the operation as a training prototype only (torchao/prototype/moe_training/blockwise_fp8/grouped_mm.py with
+ * grouped_mm_backend.py: DeepGEMM, or an emulation that dequantizes both operands to bf16, blockwise_fp8_training/grouped_kernels.py:78-93);
+ * Float8Tensor's aten._grouped_mm refuses block scales (float8_tensor.py:1085-1122).
+ * a e4m3fn [M_total][K]; a_scale fp32 [M_total][K/128]; b e4m3fn [E][N][K], every expert row-major and K-contiguous as the checkpoint
+ * stores it; b_scale fp32 [E][ceil(N/128)][K/128] (weight_scale_inv, stacked); offs int32 [E], cumulative group ends, read on the device
+ * (no host sync); out bf16 [M_total][N].  Rows past offs[E-1] are not written.  Empty groups are legal anywhere; group sizes need no
+ * alignment.  A group's row range is clamped to [0, M_total] and a non-increasing pair of offs is an empty group, so a bad offs cannot
+ * address outside a or out.  K parts are cut at multiples of 128 and added in part order: a launch is reproducible.
+ * M_total >= 0 (0: OK, nothing launched), N >= 1 (ragged N masked), K a positive multiple of 128, 1 <= E <= 65535; M_total K and the
+ * per-expert N K below 2^31 (the expert base is 64-bit: the whole b may pass 2 GiB).  a and b 16-byte aligned, the scales and offs 4-byte,
+ * out 2-byte.  Null pointers and bad shapes are rejected on the host before any launch. */
+/* The route keys on the mean group size ceil(M_total / E), all the host knows without a sync: fp8_block_grouped_stream_kernel up to this
+ * many rows, fp8_block_grouped_tile_kernel beyond.  It started at the dense family's 192; the sweep of tools/bench_fp8_block_grouped.py
+ * --sweep (each form forced over uniform groups of 16 .. 512 rows on one EP-8 rank's DeepSeek-V3 and Qwen3-235B experts,
+ * profiles/fp8_block_grouped.jsonl) moved it: summed over the four shapes and eleven group sizes the hand-over at 16 rows costs
+ * 10126 us, at 0 rows 10173, at 32 rows 10275, at 192 rows 19270.  A group of up to 128 rows is ONE tile of the tiled form whatever its
+ * size, while the stream form walks it 16 rows at a time. */
+#define AO_FP8_BLOCK_GROUPED_STREAM_MAX_ROWS 16
+int ao_fp8_block_grouped_mm(const uint8_t* a, const float* a_scale, const uint8_t* b, const float* b_scale, const int32_t* offs, uint16_t* out,
+                            int64_t M_total, int64_t N, int64_t K, int64_t E, void* stream);
+/* The route of that launch (host logic only; grouped_kernels.py:78-93 has one path, this library two forms): out[cap >= 7] = kernel (0 =
+ * invalid shape or more than 65535 grid rows, 1 fp8_block_grouped_stream_kernel, 2 fp8_block_grouped_tile_kernel), waves per workgroup,
+ * m-tiles of 16 per pass or workgroup, tile rows, tile columns, grid x, grid y (stream: E; tile: ceil(M_total / 128) + E, the host's upper
+ * bound on the tile count). */
+int ao_fp8_block_grouped_mm_route(int64_t M_total, int64_t N, int64_t K, int64_t E, int32_t* out, int cap);
+/* "fp8_block_grouped_stream_kernel", "fp8_block_grouped_tile_kernel" or "invalid": the kernel of that route. */
+const char* ao_fp8_block_grouped_mm_kernel_name(int64_t M_total, int64_t N, int64_t K, int64_t E);
+/* Measurement only (no reference counterpart): force the form of the calling thread's blockwise grouped GEMMs (0 the product route,
+ * 1 streaming, 2 tiled); the route queries report the forced form. */
+int ao_fp8_block_grouped_mm_set_form(int form);
+
 #ifdef __cplusplus
 }
 #endif
