@@ -282,4 +282,96 @@ __device__ __forceinline__ u32x4 mx_cast4(const u32x4 (&v)[4], uint32_t& e) {
   return u32x4{out[0], out[1], out[2], out[3]};
 }
 
+// ---- NVFP4 (nvfp4_kernels.hip): e2m1 codes, one e4m3 scale per 1 x 16 block, an optional fp32 per-tensor scale p -----------------------
+// The contracts of prototype/mx_formats/nvfp4_tensor.py, each stated once:
+//   cast (nvfp4_quantize, :772-854), per block, in fp32:  block_scale = amax / 6;
+//     no p: s8 = e4m3(clamp(block_scale, 2^-6, 448));      r = 1.0 / f32(s8)
+//     p   : s8 = e4m3(clamp(block_scale / p, 2^-6, 448));  r = (1.0 / p) / f32(s8)
+//     code = f32_to_f4_unpacked(clamp(x r, -6, 6)) (e2m1_code above), element 2i in the low nibble of byte i (pack_uint4)
+//   per_tensor_amax_to_scale (:756-769): amax / 2688
+//   dequantize (:199-257): s32 = p f32(s8) (f32(s8) without p);  v = f32(code) s32;  round v to the output dtype -- with a p that is
+//     not a power of two both fp32 products round, and both roundings are kept
+//   weight-only linear (nvfp4_linear, :593-596): w = bf16(dequantize);  y = bf16(sum_k x w + bias), fp32 accumulation, ONE rounding
+//   dynamic linear (_addmm_nvfp4_dispatch, :487-578): acc = sum_k (a_code a_s8)(b_code b_s8) in fp32 -- code x block scale is exact in
+//     bf16 (2 + 4 significand bits), so the bf16 MFMA multiplies the products a native FP4 unit would.  No per-tensor scale:
+//     y = bf16(acc + bias).  Otherwise t = bf16(acc);  u = bf16(f32(t) f32(bf16(P)));  y = bf16(f32(u) + f32(bias)), P = pa pb (fp32
+//     product) or the one scale that is present.
+constexpr float kE4M3Eps = 0.015625f;  // torch.finfo(float8_e4m3fn).tiny
+
+// f32 of one e4m3 scale byte
+__device__ __forceinline__ float e4m3_byte_to_f32(uint32_t b) {
+  const f32x2 v = __builtin_amdgcn_cvt_pk_f32_fp8((int)b, false);
+  return v.x;
+}
+// dequantize's scale: p f32(s8), the fp32 product rounded on its own
+__device__ __forceinline__ float nvfp4_scale32(uint32_t s8, bool has_p, float p) {
+  const float s = e4m3_byte_to_f32(s8);
+  return has_p ? mul_f32_rn(p, s) : s;
+}
+// 16 codes of one block (8 bytes) -> 16 bf16 (w0: elements 0..7, w1: 8..15) = bf16(f32(code) s32).  An e2m1 nibble seee placed in an e4m3
+// byte as s00ee.m00 reads as the e2m1 value / 64, subnormals included, so the hardware e4m3 convert and an exact x 64 give f32(code).
+__device__ __forceinline__ void nvfp4_block16(u32x2 q, float s32, u32x4& w0, u32x4& w1) {
+#pragma clang fp contract(off)
+  const uint32_t c[2] = {q.x, q.y};
+  uint32_t o[8];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const uint32_t ev = ((c[i] & 0x08080808u) << 4) | ((c[i] & 0x07070707u) << 2);          // elements 0, 2, 4, 6 of the dword
+    const uint32_t od = (c[i] & 0x80808080u) | (((c[i] >> 4) & 0x07070707u) << 2);           // elements 1, 3, 5, 7
+    const f32x2 e01 = __builtin_amdgcn_cvt_pk_f32_fp8((int)ev, false), e23 = __builtin_amdgcn_cvt_pk_f32_fp8((int)ev, true);
+    const f32x2 o01 = __builtin_amdgcn_cvt_pk_f32_fp8((int)od, false), o23 = __builtin_amdgcn_cvt_pk_f32_fp8((int)od, true);
+    o[4 * i + 0] = pack_bf16x2((e01.x * 64.0f) * s32, (o01.x * 64.0f) * s32);
+    o[4 * i + 1] = pack_bf16x2((e01.y * 64.0f) * s32, (o01.y * 64.0f) * s32);
+    o[4 * i + 2] = pack_bf16x2((e23.x * 64.0f) * s32, (o23.x * 64.0f) * s32);
+    o[4 * i + 3] = pack_bf16x2((e23.y * 64.0f) * s32, (o23.y * 64.0f) * s32);
+  }
+  w0 = u32x4{o[0], o[1], o[2], o[3]};
+  w1 = u32x4{o[4], o[5], o[6], o[7]};
+}
+__device__ __forceinline__ float clamp6(float v) { return (v != v) ? v : fminf(fmaxf(v, -6.f), 6.f); }  // torch.clamp keeps NaN
+// The 1 x 16 cast of one block held by ONE lane (16 bf16 in two 16-byte pieces): the e4m3 scale byte in s8, 16 codes packed two a byte.
+// A block that holds a NaN, or any block under a NaN p (the dynamic amax of an activation that holds one), has the scale byte 0x7F and
+// every product NaN.  The reference's codes then come from that NaN's mantissa bits: f32(e4m3 NaN) is 0x7FF00000 on its CPU run and so is
+// every product, code 4; under a NaN p the reciprocal is 1 / p = 0x7FC00000, code 3.  Taken here from the case, not from whichever NaN the
+// hardware multiply would propagate.  (A zero or infinite p is outside the contract.)
+__device__ __forceinline__ u32x2 nvfp4_cast16(const u32x4 (&v)[2], bool has_p, float p, uint32_t& s8) {
+#pragma clang fp contract(off)
+  bool has_nan = false;
+  float m = fmaxf(amax8(v[0], has_nan), amax8(v[1], has_nan));
+  if (has_nan) m = bits_to_f32(0x7FC00000u);
+  float bs = m / 6.0f;
+  if (has_p) bs = bs / p;
+  const float cl = (bs != bs) ? bs : fminf(fmaxf(bs, kE4M3Eps), 448.0f);
+  s8 = (cl != cl) ? 0x7Fu : (cvt4_e4m3(cl, 0.f, 0.f, 0.f) & 0xffu);
+  if (s8 == 0x7Fu) return (has_p && p != p) ? u32x2{0x33333333u, 0x33333333u} : u32x2{0x44444444u, 0x44444444u};
+  const float sf = e4m3_byte_to_f32(s8);
+  const float r = has_p ? (1.0f / p) / sf : 1.0f / sf;
+  uint32_t out[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const uint32_t w[4] = {v[i].x, v[i].y, v[i].z, v[i].w};
+    uint32_t o = 0u;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const uint32_t xb = (j & 1) ? (w[j >> 1] & 0xffff0000u) : (w[j >> 1] << 16);
+      o |= e2m1_code(f32_to_bits(clamp6(bits_to_f32(xb) * r))) << (4 * j);
+    }
+    out[i] = o;
+  }
+  return u32x2{out[0], out[1]};
+}
+// The outputs: the fp32 value the caller rounds to bf16 at its store (c: the fp32 sum).
+__device__ __forceinline__ float nvfp4_wo_out(float c, bool has_bias, float bias) { return has_bias ? c + bias : c; }
+// P of the dynamic linear from the two device pointers (null: none); has_P false when neither is present
+__device__ __forceinline__ float nvfp4_P(const float* pa, const float* pb, bool& has_P) {
+  has_P = pa != nullptr || pb != nullptr;
+  if (pa != nullptr && pb != nullptr) return mul_f32_rn(*pa, *pb);
+  return pa != nullptr ? *pa : (pb != nullptr ? *pb : 1.0f);
+}
+__device__ __forceinline__ float nvfp4_mm_out(float c, bool has_P, float P, bool has_bias, float bias) {
+  if (!has_P) return has_bias ? c + bias : c;
+  const float u = round_bf16(mul_f32_rn(round_bf16(c), round_bf16(P)));
+  return has_bias ? u + bias : u;
+}
+
 }  // namespace ao

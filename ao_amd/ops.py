@@ -1531,3 +1531,146 @@ def fp8_block_grouped_mm(aq, a_scale, wq, w_scale, offs, out=None):
 
 
 __all__ += ["fp8_block_grouped_mm", "fp8_block_grouped_mm_route", "fp8_block_grouped_mm_kernel_name", "fp8_block_grouped_mm_set_form"]
+
+
+# ---- NVFP4 linears: e2m1 codes, 1 x 16 e4m3 block scales, fp32 per-tensor scales (include/ao_mi355.h "NVFP4 linears") ----
+NVFP4_KIND_WEIGHT_ONLY = 0
+NVFP4_KIND_DYNAMIC = 1
+NVFP4_KERNELS = {0: "invalid", 1: "nvfp4_stream_kernel", 2: "nvfp4_tile_kernel"}
+
+
+def nvfp4_linear_route(kind: int, m: int, n: int, k: int) -> dict:
+    """The route nvfp4_wo_linear (kind 0) / nvfp4_mm (kind 1) launch for a shape (host logic only, ao_nvfp4_linear_route); kernel
+    "invalid" for shapes nothing takes."""
+    out = (ctypes.c_int32 * 7)()
+    _lib.check(_lib.lib().ao_nvfp4_linear_route(int(kind), int(m), int(n), int(k), out, 7))
+    kernel, waves, mt, tile_m, tile_n, gx, gy = list(out)
+    return {"kernel": NVFP4_KERNELS.get(kernel, "invalid"), "waves": waves, "m_tiles": mt, "tile_m": tile_m, "tile_n": tile_n,
+            "grid": (gx, gy)}
+
+
+def nvfp4_linear_kernel_name(kind: int, m: int, n: int, k: int) -> str:
+    return _lib.lib().ao_nvfp4_linear_kernel_name(int(kind), int(m), int(n), int(k)).decode()
+
+
+def nvfp4_set_form(form: int) -> None:
+    """Measurement only: 0 the product route, 1 the streaming form, 2 the tiled form (calling thread)."""
+    _lib.check(_lib.lib().ao_nvfp4_linear_set_form(int(form)))
+
+
+def _nvfp4_rows(name, x):
+    if x.dtype != torch.bfloat16:
+        raise RuntimeError(f"{name}: expected bfloat16, got {x.dtype}")
+    if x.dim() < 1 or not x.is_contiguous():
+        raise RuntimeError(f"{name}: expected a contiguous tensor")
+    c = x.shape[-1]
+    if c % 16 != 0 or c == 0:
+        raise RuntimeError(f"{name}: the last dimension of shape {tuple(x.shape)} must be divisible by 16")
+    return x.numel() // c, c
+
+
+def _nvfp4_scalar(name, what, p, dev):
+    """A per-tensor scale as one fp32 on the device (None stays None): read by the kernels through its pointer, never on the host."""
+    if p is None:
+        return None
+    if not isinstance(p, torch.Tensor) or p.numel() != 1:
+        raise RuntimeError(f"{name}: {what} must be a tensor of one element")
+    if p.device != dev:
+        raise RuntimeError(f"{name}: {what} is on {p.device}, the operands on {dev}")
+    return p.reshape(()).to(torch.float32).contiguous()
+
+
+def nvfp4_amax_scale(x: torch.Tensor) -> torch.Tensor:
+    """per_tensor_amax_to_scale(torch.max(torch.abs(x))) (nvfp4_tensor.py:605-607, :756-769) on the device: bf16 [..., C] -> fp32
+    0-dim max|x| / 2688, NaN if x holds one.  No host read (capturable)."""
+    dev = _require_gpu("nvfp4_amax_scale", x)
+    r, c = _nvfp4_rows("nvfp4_amax_scale", x)
+    out = torch.empty((), dtype=torch.float32, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_nvfp4_amax_scale(_ptr(x), _ptr(out), r, c, _stream()))
+    return out
+
+
+def nvfp4_quantize(x: torch.Tensor, per_tensor_scale: Optional[torch.Tensor] = None):
+    """nvfp4_quantize (nvfp4_tensor.py:772-854), the reference's bytes.  x bf16 [..., C] -> (codes uint8 [..., C/2], element 2i in the low
+    nibble; block scales float8_e4m3fn [..., C/16], row-major).  per_tensor_scale: a one-element tensor on the device, or None."""
+    dev = _require_gpu("nvfp4_quantize", x, per_tensor_scale)
+    r, c = _nvfp4_rows("nvfp4_quantize", x)
+    p = _nvfp4_scalar("nvfp4_quantize", "per_tensor_scale", per_tensor_scale, dev)
+    q = torch.empty((*x.shape[:-1], c // 2), dtype=torch.uint8, device=dev)
+    s = torch.empty((*x.shape[:-1], c // 16), dtype=torch.uint8, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_nvfp4_quantize(_ptr(x), _ptr(p), _ptr(q), _ptr(s), r, c, _stream()))
+    return q, s.view(torch.float8_e4m3fn)
+
+
+def _nvfp4_codes(name, what, q, s):
+    q = q.view(torch.uint8) if q.dtype == torch.float4_e2m1fn_x2 else q
+    if q.dtype != torch.uint8 or q.dim() != 2:
+        raise RuntimeError(f"{name}: the {what} codes must be a 2-D uint8 tensor [rows, K/2], got {q.dtype} {tuple(q.shape)}")
+    rows, k = q.shape[0], q.shape[1] * 2
+    if s.dtype not in (torch.float8_e4m3fn, torch.uint8):
+        raise RuntimeError(f"{name}: the {what} block scales must be float8_e4m3fn, got {s.dtype}")
+    s = s.view(torch.uint8)
+    if k % 16 != 0 or tuple(s.shape) != (rows, k // 16):
+        raise RuntimeError(f"{name}: the {what} block scales must be row-major [rows, K/16] = {(rows, k // 16)}, got {tuple(s.shape)}")
+    return q.contiguous(), s.contiguous(), rows, k
+
+
+def _nvfp4_bias(name, bias, n):
+    if bias is None:
+        return None
+    if bias.dtype != torch.bfloat16 or bias.numel() != n:
+        raise RuntimeError(f"{name}: bias must be bfloat16 [N], got {bias.dtype} {tuple(bias.shape)}")
+    return bias.contiguous()
+
+
+def nvfp4_wo_linear(x2, wq, w_scale, per_tensor_scale=None, bias=None, out=None):
+    """NVFP4Tensor's WEIGHT-ONLY F.linear on a 2-D bf16 activation (nvfp4_tensor.py:593-596): bf16(x . bf16(dequantize(w))^T + bias), fp32
+    accumulation, one rounding; one launch that reads 0.5625 bytes a weight.  wq [N, K/2], w_scale e4m3 [N, K/16], per_tensor_scale one
+    fp32 on the device or None; out: an optional bf16 [M, N] tensor to write."""
+    dev = _require_gpu("nvfp4_wo_linear", x2, wq, w_scale, per_tensor_scale, bias)
+    if x2.dim() != 2 or x2.dtype != torch.bfloat16:
+        raise RuntimeError(f"nvfp4_wo_linear: x must be a 2-D bfloat16 tensor, got {tuple(x2.shape)} {x2.dtype}")
+    x2 = x2.contiguous()
+    wq, w_scale, n, k = _nvfp4_codes("nvfp4_wo_linear", "weight", wq, w_scale)
+    m, kx = x2.shape
+    if kx != k:
+        raise RuntimeError(f"nvfp4_wo_linear: K mismatch {kx} vs {k}")
+    p = _nvfp4_scalar("nvfp4_wo_linear", "per_tensor_scale", per_tensor_scale, dev)
+    bias = _nvfp4_bias("nvfp4_wo_linear", bias, n)
+    y = _bf16_out("nvfp4_wo_linear", out, m, n, dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_nvfp4_wo_linear(_ptr(x2), _ptr(wq), _ptr(w_scale), _ptr(p), _ptr(bias), _ptr(y), m, n, k, _stream()))
+    return y
+
+
+def nvfp4_mm(a, a_scale, b, b_scale, a_per_tensor_scale=None, b_per_tensor_scale=None, bias=None, out=None):
+    """The NVFP4 x NVFP4 GEMM on codes (_addmm_nvfp4_dispatch, nvfp4_tensor.py:487-578): a [M, K/2], a_scale [M, K/16], b [N, K/2] (the
+    weight as stored), b_scale [N, K/16] -> bf16 [M, N].  acc = sum_k dq(a) dq(b) in fp32; without per-tensor scales bf16(acc + bias),
+    otherwise bf16(bf16(bf16(acc) bf16(P)) + bias) with P = pa pb."""
+    dev = _require_gpu("nvfp4_mm", a, a_scale, b, b_scale, a_per_tensor_scale, b_per_tensor_scale, bias)
+    a, a_scale, m, ka = _nvfp4_codes("nvfp4_mm", "activation", a, a_scale)
+    b, b_scale, n, k = _nvfp4_codes("nvfp4_mm", "weight", b, b_scale)
+    if ka != k:
+        raise RuntimeError(f"nvfp4_mm: K of the activation ({ka}) and of the weight ({k}) differ")
+    pa = _nvfp4_scalar("nvfp4_mm", "a_per_tensor_scale", a_per_tensor_scale, dev)
+    pb = _nvfp4_scalar("nvfp4_mm", "b_per_tensor_scale", b_per_tensor_scale, dev)
+    bias = _nvfp4_bias("nvfp4_mm", bias, n)
+    y = _bf16_out("nvfp4_mm", out, m, n, dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_nvfp4_linear(_ptr(a), _ptr(a_scale), _ptr(pa), _ptr(b), _ptr(b_scale), _ptr(pb), _ptr(bias), _ptr(y), m, n, k,
+                                              _stream()))
+    return y
+
+
+def nvfp4_linear(x2, wq, w_scale, w_per_tensor_scale=None, act_per_tensor_scale=None, dynamic_per_tensor_scale=False, bias=None):
+    """NVFP4Tensor's F.linear with a dynamic activation (nvfp4_tensor.py:598-619): the activation's per-tensor scale (the device amax when
+    dynamic_per_tensor_scale, else act_per_tensor_scale, else none), its 1 x 16 cast, then the codes x codes GEMM."""
+    pa = nvfp4_amax_scale(x2) if dynamic_per_tensor_scale else act_per_tensor_scale
+    aq, a_s = nvfp4_quantize(x2.contiguous(), pa)
+    return nvfp4_mm(aq, a_s, wq, w_scale, pa, w_per_tensor_scale, bias)
+
+
+__all__ += ["nvfp4_amax_scale", "nvfp4_quantize", "nvfp4_wo_linear", "nvfp4_mm", "nvfp4_linear", "nvfp4_linear_route",
+            "nvfp4_linear_kernel_name", "nvfp4_set_form"]

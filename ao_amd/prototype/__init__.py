@@ -1,4 +1,12 @@
 """Prototype-namespace mirrors (torchao/prototype/*) that sit on the SURVEY.md section 8 path."""
 from .blockwise_fp8 import Float8BlockwiseExpertWeights, fp8_blockwise_grouped_mm  # noqa: F401
+from .nvfp4_tensor import (  # noqa: F401
+    NVFP4DynamicActivationNVFP4WeightConfig,
+    NVFP4Tensor,
+    NVFP4WeightOnlyConfig,
+    QuantizeTensorToNVFP4Kwargs,
+    per_tensor_amax_to_scale,
+)
 
-__all__ = ["Float8BlockwiseExpertWeights", "fp8_blockwise_grouped_mm"]
+__all__ = ["Float8BlockwiseExpertWeights", "fp8_blockwise_grouped_mm", "NVFP4Tensor", "NVFP4WeightOnlyConfig",
+           "NVFP4DynamicActivationNVFP4WeightConfig", "QuantizeTensorToNVFP4Kwargs", "per_tensor_amax_to_scale"]

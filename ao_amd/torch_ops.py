@@ -79,6 +79,11 @@ _lib_def.define("fp8_quantize_block_1x128(Tensor x) -> (Tensor, Tensor)")
 _lib_def.define("fp8_quantize_block_128x128(Tensor w) -> (Tensor, Tensor)")
 _lib_def.define("fp8_block_linear(Tensor x, Tensor wq, Tensor w_scale, Tensor? bias) -> Tensor")
 _lib_def.define("fp8_block_grouped_mm(Tensor a, Tensor a_scale, Tensor b, Tensor b_scale, Tensor offs) -> Tensor")
+_lib_def.define("nvfp4_amax_scale(Tensor x) -> Tensor")
+_lib_def.define("nvfp4_quantize(Tensor x, Tensor? per_tensor_scale) -> (Tensor, Tensor)")
+_lib_def.define("nvfp4_wo_linear(Tensor x, Tensor wq, Tensor w_scale, Tensor? per_tensor_scale, Tensor? bias) -> Tensor")
+_lib_def.define("nvfp4_mm(Tensor a, Tensor a_scale, Tensor b, Tensor b_scale, Tensor? a_per_tensor_scale, Tensor? b_per_tensor_scale, Tensor? bias) -> Tensor")
+_lib_def.define("nvfp4_linear(Tensor x, Tensor wq, Tensor w_scale, Tensor? w_per_tensor_scale, Tensor? act_per_tensor_scale, bool dynamic_per_tensor_scale, Tensor? bias) -> Tensor")
 # same schemas as torchao::fused_pad_token_groups / fused_unpad_token_groups (kernels/mxfp8/quant.py:1244-1246, 1319-1321)
 _lib_def.define("fused_pad_token_groups(Tensor inputs, Tensor offsets, int alignment_size) -> (Tensor, Tensor, Tensor)")
 _lib_def.define(
@@ -114,6 +119,11 @@ _lib_impl.impl("fp8_quantize_block_1x128", ops.fp8_quantize_block_1x128)
 _lib_impl.impl("fp8_quantize_block_128x128", ops.fp8_quantize_block_128x128)
 _lib_impl.impl("fp8_block_linear", lambda x, wq, w_scale, bias: ops.fp8_block_linear(x, wq, w_scale, bias))
 _lib_impl.impl("fp8_block_grouped_mm", lambda a, a_scale, b, b_scale, offs: ops.fp8_block_grouped_mm(a, a_scale, b, b_scale, offs))
+_lib_impl.impl("nvfp4_amax_scale", ops.nvfp4_amax_scale)
+_lib_impl.impl("nvfp4_quantize", ops.nvfp4_quantize)
+_lib_impl.impl("nvfp4_wo_linear", lambda x, wq, w_scale, p, bias: ops.nvfp4_wo_linear(x, wq, w_scale, p, bias))
+_lib_impl.impl("nvfp4_mm", lambda a, a_scale, b, b_scale, pa, pb, bias: ops.nvfp4_mm(a, a_scale, b, b_scale, pa, pb, bias))
+_lib_impl.impl("nvfp4_linear", ops.nvfp4_linear)
 _lib_impl.impl("fused_pad_token_groups", ops.fused_pad_token_groups)
 _lib_impl.impl("fused_unpad_token_groups", ops.fused_unpad_token_groups)
 
@@ -261,6 +271,32 @@ def _(a, a_scale, b, b_scale, offs):
     return a.new_empty((a.shape[0], b.shape[1]), dtype=torch.bfloat16)
 
 
+@torch.library.register_fake("ao_mi355::nvfp4_amax_scale")
+def _(x):
+    return x.new_empty((), dtype=torch.float32)
+
+
+@torch.library.register_fake("ao_mi355::nvfp4_quantize")
+def _(x, per_tensor_scale):
+    return (x.new_empty((*x.shape[:-1], x.shape[-1] // 2), dtype=torch.uint8),
+            x.new_empty((*x.shape[:-1], x.shape[-1] // 16), dtype=torch.float8_e4m3fn))
+
+
+@torch.library.register_fake("ao_mi355::nvfp4_wo_linear")
+def _(x, wq, w_scale, per_tensor_scale, bias):
+    return x.new_empty((x.shape[0], wq.shape[0]), dtype=torch.bfloat16)
+
+
+@torch.library.register_fake("ao_mi355::nvfp4_mm")
+def _(a, a_scale, b, b_scale, a_per_tensor_scale, b_per_tensor_scale, bias):
+    return a.new_empty((a.shape[0], b.shape[0]), dtype=torch.bfloat16)
+
+
+@torch.library.register_fake("ao_mi355::nvfp4_linear")
+def _(x, wq, w_scale, w_per_tensor_scale, act_per_tensor_scale, dynamic_per_tensor_scale, bias):
+    return x.new_empty((x.shape[0], wq.shape[0]), dtype=torch.bfloat16)
+
+
 @torch.library.register_fake("ao_mi355::fused_pad_token_groups")
 def _(inputs, offsets, alignment_size):
     rows = inputs.shape[0] + offsets.shape[0] * alignment_size
@@ -284,7 +320,8 @@ for _name in ("weight_int4pack_mm", "convert_weight_to_int4pack", "int8_scaled_m
               "int8_linear", "fp8_linear", "int8_linear_asym", "int8_linear_tensorwise", "fp8_linear_tensorwise", "fp8_linear_clamped",
               "int8_linear_static", "fp8_int4_linear", "fp8_int4_act_linear", "int8_quantize_rowwise", "fp8_quantize_rowwise", "mxfp8_quantize", "mxfp8_grouped_mm",
               "fused_pad_token_groups", "fused_unpad_token_groups", "mxfp4_quantize", "mx_mm", "mx_linear", "int8_wo_linear", "fp8_wo_linear",
-              "fp8_quantize_block_1x128", "fp8_quantize_block_128x128", "fp8_block_linear", "fp8_block_grouped_mm"):
+              "fp8_quantize_block_1x128", "fp8_quantize_block_128x128", "fp8_block_linear", "fp8_block_grouped_mm",
+              "nvfp4_amax_scale", "nvfp4_quantize", "nvfp4_wo_linear", "nvfp4_mm", "nvfp4_linear"):
     _lib_autograd.impl(_name, torch.library.fallthrough_kernel)
 
 

@@ -698,6 +698,41 @@ const char* ao_fp8_block_grouped_mm_kernel_name(int64_t M_total, int64_t N, int6
  * 1 streaming, 2 tiled); the route queries report the forced form. */
 int ao_fp8_block_grouped_mm_set_form(int form);
 
+/* ---- NVFP4 linears: e2m1 codes, one e4m3 scale per 1 x 16 block, an optional fp32 per-tensor scale (nvfp4_kernels.hip) -----------------
+ * NVFP4Tensor of prototype/mx_formats/nvfp4_tensor.py and the two configs of inference_workflow.py:173-400.  Codes are packed two a byte
+ * along K, element 2i in the low nibble of byte i; block scales are float8_e4m3fn bytes, ROW-MAJOR [rows][K/16] (no 128 x 4 swizzle);
+ * per-tensor scales are read through device pointers, NULL meaning none.  The arithmetic contracts are those of csrc/quant_math.h
+ * ("NVFP4"); DESIGN.md 4.14.  Null pointers and bad shapes are rejected on the host before any launch. */
+#define AO_NVFP4_KIND_WEIGHT_ONLY 0
+#define AO_NVFP4_KIND_DYNAMIC 1
+/* Replaces per_tensor_amax_to_scale(torch.max(torch.abs(x))) (nvfp4_tensor.py:605-607, :756-769): x bf16 [R][C], C a multiple of 16 ->
+ * out[0] = max|x| / 2688 in fp32, NaN if x holds one.  Three launches on the stream, no host read; x 16-byte, out 4-byte aligned. */
+int ao_nvfp4_amax_scale(const uint16_t* x, float* out, int64_t R, int64_t C, void* stream);
+/* Replaces nvfp4_quantize (nvfp4_tensor.py:772-854), the reference's bytes: x bf16 [R][C] contiguous, C a multiple of 16 -> q [R][C/2],
+ * scale_e4m3 [R][C/16]; per_tensor_scale a device pointer to one fp32 or NULL.  x 16-byte, q 8-byte aligned. */
+int ao_nvfp4_quantize(const uint16_t* x, const float* per_tensor_scale, uint8_t* q, uint8_t* scale_e4m3, int64_t R, int64_t C, void* stream);
+/* Replaces the weight-only branch of nvfp4_linear (nvfp4_tensor.py:593-596: F.linear(x, weight.dequantize(bf16), bias), dequantize
+ * :199-257): w = bf16(f32(code) (p f32(s8))) per element; out = bf16(sum_k x w + bias), fp32 accumulation, one rounding.  x bf16 [M][K],
+ * wq [N][K/2], w_scale [N][K/16], bias bf16 [N] or NULL, out bf16 [M][N].  M >= 0 (M = 0: OK, nothing launched), N >= 1, K a positive
+ * multiple of 16 up to 2^31 - 1024, M K and N K below 2^31.  x 16-byte aligned; the codes 16-byte and the block scales 2-byte aligned
+ * (8-byte and 1-byte where K is not a multiple of 32); the per-tensor scale 4-byte, bias and out 2-byte. */
+int ao_nvfp4_wo_linear(const uint16_t* x, const uint8_t* wq, const uint8_t* w_scale, const float* w_per_tensor_scale, const uint16_t* bias,
+                       uint16_t* out, int64_t M, int64_t N, int64_t K, void* stream);
+/* Replaces _addmm_nvfp4_dispatch (nvfp4_tensor.py:487-578: torch._scaled_mm on sm100, then the per-tensor scales and the bias):
+ * acc = sum_k (a_code a_s8)(b_code b_s8) in fp32.  Neither per-tensor scale: out = bf16(acc + bias).  Otherwise t = bf16(acc);
+ * u = bf16(f32(t) f32(bf16(P))), P = pa pb (fp32) or the one present;  out = bias ? bf16(f32(u) + f32(bias)) : u.  a [M][K/2],
+ * a_scale [M][K/16], b [N][K/2] (the weight as stored), b_scale [N][K/16].  Shapes and alignment as ao_nvfp4_wo_linear. */
+int ao_nvfp4_linear(const uint8_t* a, const uint8_t* a_scale, const float* a_per_tensor_scale, const uint8_t* b, const uint8_t* b_scale,
+                    const float* b_per_tensor_scale, const uint16_t* bias, uint16_t* out, int64_t M, int64_t N, int64_t K, void* stream);
+/* The route ao_nvfp4_wo_linear (kind 0) / ao_nvfp4_linear (kind 1) launch (host logic only; nvfp4_tensor.py:581-619 has one path per
+ * kind, this library two forms): out[cap >= 7] = kernel (0 = no kernel takes the shape, 1 nvfp4_stream_kernel, 2 nvfp4_tile_kernel),
+ * waves per workgroup, m-tiles of 16 per workgroup, tile rows, tile columns, grid x, grid y. */
+int ao_nvfp4_linear_route(int kind, int64_t M, int64_t N, int64_t K, int32_t* out, int cap);
+const char* ao_nvfp4_linear_kernel_name(int kind, int64_t M, int64_t N, int64_t K);
+/* Measurement only (no reference counterpart: nvfp4_tensor.py:581-619 has one path): force the form of the calling thread's NVFP4
+ * linears (0 the product route, 1 streaming, 2 tiled); the route query reports the forced form. */
+int ao_nvfp4_linear_set_form(int form);
+
 #ifdef __cplusplus
 }
 #endif
