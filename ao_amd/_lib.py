@@ -138,6 +138,12 @@ _SIGNATURES = {
     "ao_nvfp4_linear_route": [_INT, _I64, _I64, _I64, _P, _INT],
     "ao_nvfp4_linear_kernel_name": [_INT, _I64, _I64, _I64],
     "ao_nvfp4_linear_set_form": [_INT],
+    "ao_nvfp4_grouped_mm": [_INT, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P],
+    "ao_nvfp4_group_amax_scale": [_P, _P, _P, _I64, _I64, _I64, _P],
+    "ao_nvfp4_quantize_grouped": [_P, _P, _P, _P, _P, _I64, _I64, _I64, _P],
+    "ao_nvfp4_grouped_mm_route": [_INT, _I64, _I64, _I64, _I64, _P, _INT],
+    "ao_nvfp4_grouped_mm_kernel_name": [_INT, _I64, _I64, _I64, _I64],
+    "ao_nvfp4_grouped_mm_set_form": [_INT],
 }
 
 
@@ -187,6 +193,8 @@ def lib():
             l.ao_fp8_block_grouped_mm_kernel_name.restype = ctypes.c_char_p
         if hasattr(l, "ao_nvfp4_linear_kernel_name"):
             l.ao_nvfp4_linear_kernel_name.restype = ctypes.c_char_p
+        if hasattr(l, "ao_nvfp4_grouped_mm_kernel_name"):
+            l.ao_nvfp4_grouped_mm_kernel_name.restype = ctypes.c_char_p
         if hasattr(l, "ao_fp8_int4_kernel_name"):
             l.ao_fp8_int4_kernel_name.restype = ctypes.c_char_p
         l.ao_moe_padded_rows.restype = _I64

@@ -20,6 +20,11 @@
 //   nvfp4_tile_kernel: 64 x 64 output tiles, four waves of 32 x 32, both operands staged in LDS as bf16 -- a block decoded ONCE, by the
 //     thread that stages it -- with the next k step's global loads in flight under the MFMAs.  A first cut: correct for every M, ragged
 //     N and K; not tuned.
+//
+// The grouped GEMM for MoE experts (ao_nvfp4_grouped_mm; the reference: NVFP4Tensor's aten._grouped_mm :709-753 over mslk /
+// sm100, or the bf16 emulation of prototype/moe_training/nvfp4_grouped_mm.py:62-116) applies the same chains, without a bias, per token
+// group [offs[e-1], offs[e]) against expert e: the GROUPED instantiations of the two kernels above -- the same bodies -- routed on the mean
+// group size (nvfp4_grouped_route), with the per-group amax and cast next to the dense ones.
 #include "common.h"
 #include "quant_math.h"
 #include "two_form_route.h"
@@ -72,7 +77,18 @@ struct Nvfp4Args {
   const uint16_t* bias;    // bf16 [N] or null
   uint16_t* out;           // bf16 [M][N]
   int M, N, K;
+  // grouped (MoE experts) only: M is M_total, b / b_scale hold E experts, pa / pb one scale an expert, no bias
+  const int32_t* offs;     // [E] cumulative group ends, or null (dense)
+  int E;
 };
+
+// Token group e = rows [offs[e-1], offs[e]) (offs[-1] = 0).  The kernels only read offs: a group's bounds are clamped to [0, M_total] (a
+// bad offs cannot address outside the activation or out) and a non-increasing pair is an empty group.
+__device__ __forceinline__ int clamp_row(int r, int M_total) { return r < 0 ? 0 : (r > M_total ? M_total : r); }
+__device__ __forceinline__ void group_bounds(const int32_t* offs, int e, int M_total, int& row_begin, int& row_end) {
+  row_begin = clamp_row(e > 0 ? offs[e - 1] : 0, M_total);
+  row_end = clamp_row(offs[e], M_total);
+}
 
 __device__ __forceinline__ f32x4 mfma_bf16(const u32x4& a, const u32x4& b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
@@ -108,12 +124,26 @@ __device__ __forceinline__ void decode_blocks(const u32x4& q, uint32_t s, bool h
 // ---- streaming form -------------------------------------------------------------------------------------------------------------
 constexpr int kChunk = 4;  // 128-k steps a wave requests at once
 
-template <int KIND, int MT, int WAVES>
+// ONE body, two instantiations per (KIND, MT, WAVES):
+//   GROUPED false, "nvfp4_stream_kernel": the dense linear; blockIdx.y is the workgroup's block of 16 MT rows.
+//   GROUPED true, "nvfp4_grouped_stream_kernel": grid (ceil(N / 16), E); blockIdx.y is the expert, and the workgroup walks its group's rows
+//     16 MT at a time: a pass is the dense body (the weight comes from L2 from the second pass on), with a barrier before the next pass
+//     reuses the meeting buffer.  pb[e] is folded into the decode (weight-only); P_e = pa[e] pb[e] is applied in the epilogue.
+template <int KIND, int MT, int WAVES, bool GROUPED>
 __global__ __launch_bounds__(64 * WAVES) void nvfp4_stream_kernel(Nvfp4Args p) {
   __shared__ f32x4 red[WAVES][MT][64];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), kq = lane >> 4;
   const int n = blockIdx.x * 16 + (lane & 15);
-  const int m0 = blockIdx.y * 16 * MT;
+  int m0 = blockIdx.y * 16 * MT, row_end = p.M;
+  if constexpr (GROUPED) {
+    group_bounds(p.offs, blockIdx.y, p.M, m0, row_end);
+    if (row_end <= m0) return;  // an empty group: the whole workgroup leaves, before any barrier
+    // the expert's base in 64 bits: the whole b may pass 2^31 elements
+    p.b += (size_t)blockIdx.y * p.N * (p.K >> 1);
+    p.b_scale += (size_t)blockIdx.y * p.N * (p.K >> 4);
+    if (p.pa != nullptr) p.pa += blockIdx.y;
+    if (p.pb != nullptr) p.pb += blockIdx.y;
+  }
   const int ksteps = (p.K + 127) >> 7;
   const int ks0 = (ksteps * wave) / WAVES, ks1 = (ksteps * (wave + 1)) / WAVES;
   const int kb = p.K >> 4;
@@ -121,90 +151,98 @@ __global__ __launch_bounds__(64 * WAVES) void nvfp4_stream_kernel(Nvfp4Args p) {
   // columns past N read the last row (never stored)
   const uint8_t* wrow = p.b + (size_t)min(n, p.N - 1) * (p.K >> 1);
   const uint8_t* wsrow = p.b_scale + (size_t)min(n, p.N - 1) * kb;
+  int kq32 = 32 * kq;
   // the weight-only linear folds the weight's per-tensor scale into the weights (dequantize); codes x codes applies P after the sum
   const bool has_pw = KIND == kKindWo && p.pb != nullptr;
   const float pw = has_pw ? *p.pb : 1.f;
-  // rows past M alias the tile's first row: they only reach outputs that are never stored
-  size_t arow[MT];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) {
-    const int row = m0 + mt * 16 + (lane & 15);
-    arow[mt] = (size_t)(row < p.M ? row : m0);
-  }
   struct Stage {
     u32x4 q;
     uint32_t s;
   };
   auto issue = [&](Stage (&st)[kChunk], int step) {
 #pragma unroll
-    for (int d = 0; d < kChunk; ++d) load_blocks<true>(wrow, wsrow, (step + d) * 128 + 32 * kq, p.K, k32, st[d].q, st[d].s);
+    for (int d = 0; d < kChunk; ++d) load_blocks<true>(wrow, wsrow, (step + d) * 128 + kq32, p.K, k32, st[d].q, st[d].s);
     __builtin_amdgcn_sched_barrier(0);  // every request of the chunk is out before anything waits
   };
-  f32x4 acc[MT];
+  for (;; m0 += 16 * MT) {  // (dense: one pass)
+    // (grouped: a pass recomputes its addresses -- hoisted out of the pass loop they cost 40 registers and, at 16 waves, scratch)
+    if constexpr (GROUPED) asm volatile("" : "+v"(wrow), "+v"(wsrow), "+v"(kq32));
+    // rows past the end (M, or the group's) alias the pass's first row: they only reach outputs that are never stored
+    size_t arow[MT];
 #pragma unroll
-  for (int mt = 0; mt < MT; ++mt) acc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  Stage cur[kChunk], nxt[kChunk];
-  issue(cur, ks0);
-  for (int step = ks0; step < ks1; step += kChunk) {
-    const bool more = step + kChunk < ks1;  // wave-uniform
-    if (more) issue(nxt, step + kChunk);
+    for (int mt = 0; mt < MT; ++mt) {
+      const int row = m0 + mt * 16 + (lane & 15);
+      arow[mt] = (size_t)(row < row_end ? row : m0);
+    }
+    f32x4 acc[MT];
 #pragma unroll
-    for (int d = 0; d < kChunk; ++d) {
-      if (step + d < ks1) {
-        const int k0 = (step + d) * 128 + 32 * kq;
-        // (16 | K: a block lies inside K or outside; outside, both operands are zero)
-        const bool v0 = k0 < p.K, v1 = k0 + 16 < p.K;
-        u32x4 w[4];
-        decode_blocks(cur[d].q, cur[d].s, has_pw, pw, v0, v1, w);
+    for (int mt = 0; mt < MT; ++mt) acc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    Stage cur[kChunk], nxt[kChunk];
+    issue(cur, ks0);
+    for (int step = ks0; step < ks1; step += kChunk) {
+      const bool more = step + kChunk < ks1;  // wave-uniform
+      if (more) issue(nxt, step + kChunk);
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-          u32x4 a[4];
-          if constexpr (KIND == kKindWo) {
-            const u32x4 z = {0u, 0u, 0u, 0u};
-            const uint16_t* xp = p.x + arow[mt] * p.K + (v0 ? k0 : 0);
-            const uint16_t* xq = p.x + arow[mt] * p.K + (v1 ? k0 + 16 : 0);
-            a[0] = *reinterpret_cast<const u32x4*>(xp);
-            a[1] = *reinterpret_cast<const u32x4*>(xp + 8);
-            a[2] = *reinterpret_cast<const u32x4*>(xq);
-            a[3] = *reinterpret_cast<const u32x4*>(xq + 8);
-            if (!v0) a[0] = a[1] = z;
-            if (!v1) a[2] = a[3] = z;
-          } else {
-            u32x4 aq;
-            uint32_t as;
-            load_blocks<false>(p.a + arow[mt] * (p.K >> 1), p.a_scale + arow[mt] * kb, k0, p.K, k32, aq, as);
-            decode_blocks(aq, as, false, 1.f, v0, v1, a);
+      for (int d = 0; d < kChunk; ++d) {
+        if (step + d < ks1) {
+          const int k0 = (step + d) * 128 + kq32;
+          // (16 | K: a block lies inside K or outside; outside, both operands are zero)
+          const bool v0 = k0 < p.K, v1 = k0 + 16 < p.K;
+          u32x4 w[4];
+          decode_blocks(cur[d].q, cur[d].s, has_pw, pw, v0, v1, w);
+#pragma unroll
+          for (int mt = 0; mt < MT; ++mt) {
+            u32x4 a[4];
+            if constexpr (KIND == kKindWo) {
+              const u32x4 z = {0u, 0u, 0u, 0u};
+              const uint16_t* xp = p.x + arow[mt] * p.K + (v0 ? k0 : 0);
+              const uint16_t* xq = p.x + arow[mt] * p.K + (v1 ? k0 + 16 : 0);
+              a[0] = *reinterpret_cast<const u32x4*>(xp);
+              a[1] = *reinterpret_cast<const u32x4*>(xp + 8);
+              a[2] = *reinterpret_cast<const u32x4*>(xq);
+              a[3] = *reinterpret_cast<const u32x4*>(xq + 8);
+              if (!v0) a[0] = a[1] = z;
+              if (!v1) a[2] = a[3] = z;
+            } else {
+              u32x4 aq;
+              uint32_t as;
+              load_blocks<false>(p.a + arow[mt] * (p.K >> 1), p.a_scale + arow[mt] * kb, k0, p.K, k32, aq, as);
+              decode_blocks(aq, as, false, 1.f, v0, v1, a);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[mt] = mfma_bf16(a[i], w[i], acc[mt]);
           }
+        }
+      }
+      if (more) {
 #pragma unroll
-          for (int i = 0; i < 4; ++i) acc[mt] = mfma_bf16(a[i], w[i], acc[mt]);
+        for (int d = 0; d < kChunk; ++d) cur[d] = nxt[d];
+      }
+    }
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) red[wave][mt][lane] = acc[mt];
+    lds_barrier();
+    // wave w stores m-tiles w, w + WAVES, ...: the partial tiles are added in wave order
+    const bool has_bias = p.bias != nullptr;
+    const float bias = (has_bias && n < p.N) ? bf16_lo_to_f32(p.bias[n]) : 0.f;
+    bool has_P = false;
+    const float P = KIND == kKindDyn ? nvfp4_P(p.pa, p.pb, has_P) : 1.f;
+    for (int mt = wave; mt < MT; mt += WAVES) {
+      f32x4 c = red[0][mt][lane];
+#pragma unroll
+      for (int w = 1; w < WAVES; ++w) c += red[w][mt][lane];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = m0 + mt * 16 + 4 * kq + r;
+        if (row < row_end && n < p.N) {
+          const float v = KIND == kKindWo ? nvfp4_wo_out(c[r], has_bias, bias) : nvfp4_mm_out(c[r], has_P, P, has_bias, bias);
+          p.out[(size_t)row * p.N + n] = f32_to_bf16_bits(v);
         }
       }
     }
-    if (more) {
-#pragma unroll
-      for (int d = 0; d < kChunk; ++d) cur[d] = nxt[d];
-    }
-  }
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) red[wave][mt][lane] = acc[mt];
-  lds_barrier();
-  // wave w stores m-tiles w, w + WAVES, ...: the partial tiles are added in wave order
-  const bool has_bias = p.bias != nullptr;
-  const float bias = (has_bias && n < p.N) ? bf16_lo_to_f32(p.bias[n]) : 0.f;
-  bool has_P = false;
-  const float P = KIND == kKindDyn ? nvfp4_P(p.pa, p.pb, has_P) : 1.f;
-  for (int mt = wave; mt < MT; mt += WAVES) {
-    f32x4 c = red[0][mt][lane];
-#pragma unroll
-    for (int w = 1; w < WAVES; ++w) c += red[w][mt][lane];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = m0 + mt * 16 + 4 * kq + r;
-      if (row < p.M && n < p.N) {
-        const float v = KIND == kKindWo ? nvfp4_wo_out(c[r], has_bias, bias) : nvfp4_mm_out(c[r], has_P, P, has_bias, bias);
-        p.out[(size_t)row * p.N + n] = f32_to_bf16_bits(v);
-      }
-    }
+    if constexpr (!GROUPED) break;
+    if (m0 + 16 * MT >= row_end) break;  // workgroup-uniform
+    lds_barrier();                       // the next pass parks into the same buffer
   }
 }
 
@@ -215,11 +253,43 @@ __global__ __launch_bounds__(64 * WAVES) void nvfp4_stream_kernel(Nvfp4Args p) {
 constexpr int kTileRow = 144;
 constexpr int kTileOp = 64 * kTileRow;
 
-template <int KIND>
+// ONE body, two instantiations per KIND:
+//   GROUPED false, "nvfp4_tile_kernel": the dense linear; the tile row is blockIdx.y.
+//   GROUPED true, "nvfp4_grouped_tile_kernel": grid y is the host's upper bound ceil(M_total / 64) + E on the 64-row tiles of all groups (a
+//     group adds at most one partial tile); a workgroup finds its (group, tile) by walking offs and leaves when it has none; p then becomes
+//     the group's row window [row_begin, row_end) against its expert, expressed by offset base pointers, so rows outside the window are
+//     staged as zeros and never stored.
+template <int KIND, bool GROUPED>
 __global__ __launch_bounds__(256) void nvfp4_tile_kernel(Nvfp4Args p) {
+  unsigned tile_y = blockIdx.y;
+  if constexpr (GROUPED) {
+    int t = blockIdx.y, e = 0, row_begin = 0, row_end = 0;
+    for (; e < p.E; ++e) {
+      group_bounds(p.offs, e, p.M, row_begin, row_end);
+      const int tiles = row_end > row_begin ? (row_end - row_begin + 63) >> 6 : 0;
+      if (t < tiles) break;
+      t -= tiles;
+    }
+    if (e == p.E) return;
+    const int kb = p.K >> 4;
+    if constexpr (KIND == kKindWo) {
+      p.x += (size_t)row_begin * p.K;
+    } else {
+      p.a += (size_t)row_begin * (p.K >> 1);
+      p.a_scale += (size_t)row_begin * kb;
+    }
+    // the expert's base in 64 bits: the whole b may pass 2^31 elements
+    p.b += (size_t)e * p.N * (p.K >> 1);
+    p.b_scale += (size_t)e * p.N * kb;
+    if (p.pa != nullptr) p.pa += e;
+    if (p.pb != nullptr) p.pb += e;
+    p.out += (size_t)row_begin * p.N;
+    p.M = row_end - row_begin;
+    tile_y = t;
+  }
   __shared__ __attribute__((aligned(16))) char smem[2 * kTileOp];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kq = lane >> 4;
-  const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
+  const int m0 = tile_y * 64, n0 = blockIdx.x * 64;
   const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
   const int sr = tid >> 2, sp = tid & 3;  // staging row and block
   const int kb = p.K >> 4;
@@ -339,13 +409,68 @@ __global__ void nvfp4_amax_scale_kernel(uint32_t* out) {
   if (threadIdx.x == 0) *reinterpret_cast<float*>(out) = bits_to_f32(*out) / 2688.0f;
 }
 
+// ---- the grouped cast: row r under its group's p[e].  The group is the first e with offs[e] > r (a binary search: offs is cumulative);
+// rows past offs[E-1] are not written.  Without p only that end is needed. --------------------------------------------------------------
+__global__ __launch_bounds__(256) void nvfp4_quant_grouped_kernel(const uint16_t* __restrict__ x, const float* __restrict__ p,
+                                                                  const int32_t* __restrict__ offs, uint8_t* __restrict__ q,
+                                                                  uint8_t* __restrict__ s, int64_t blocks, int kb, int E) {
+  const int64_t blk = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (blk >= blocks) return;
+  const int row = (int)(blk / kb);
+  const bool has_p = p != nullptr;
+  float ps = 1.f;
+  if (has_p) {
+    int lo = 0, hi = E;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (offs[mid] > row) hi = mid; else lo = mid + 1;
+    }
+    if (lo == E) return;
+    ps = p[lo];
+  } else if (row >= offs[E - 1]) {
+    return;
+  }
+  const u32x4* px = reinterpret_cast<const u32x4*>(x + blk * 16);
+  const u32x4 v[2] = {px[0], px[1]};
+  uint32_t s8;
+  *reinterpret_cast<u32x2*>(q + blk * 8) = nvfp4_cast16(v, has_p, ps, s8);
+  s[blk] = (uint8_t)s8;
+}
+
+// ---- per-group amax -> scale: as the per-tensor one, out[e] over group e's rows; grid (parts, E).  An empty group stays 0. -------------
+__global__ void nvfp4_group_amax_clear_kernel(uint32_t* out, int E) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e < E) out[e] = 0u;
+}
+
+__global__ __launch_bounds__(256) void nvfp4_group_amax_kernel(const uint16_t* __restrict__ x, const int32_t* __restrict__ offs, int M_total,
+                                                               int K, uint32_t* out) {
+  int row_begin, row_end;
+  group_bounds(offs, blockIdx.y, M_total, row_begin, row_end);
+  if (row_end <= row_begin) return;
+  const u32x4* px = reinterpret_cast<const u32x4*>(x + (size_t)row_begin * K);
+  const int64_t pieces = (int64_t)(row_end - row_begin) * (K >> 3);
+  float m = 0.f;
+  bool has_nan = false;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < pieces; i += (int64_t)gridDim.x * 256) m = fmaxf(m, amax8(px[i], has_nan));
+  m = wave_max(m);
+  const bool any_nan = __ballot(has_nan) != 0ull;
+  // (out[e] was cleared to 0: a wave that met nothing above 0 has nothing to add, and E addresses serialize what does arrive)
+  if ((threadIdx.x & 63) == 0 && (any_nan || m > 0.f)) atomicMax(out + blockIdx.y, any_nan ? 0x7FC00000u : f32_to_bits(m));
+}
+
+__global__ void nvfp4_group_amax_scale_kernel(uint32_t* out, int E) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e < E) reinterpret_cast<float*>(out)[e] = bits_to_f32(out[e]) / 2688.0f;
+}
+
 // ---- launches -------------------------------------------------------------------------------------------------------------------
 // (4 m-tiles x 16 waves: the meeting buffer would pass the static LDS; the stream-form plan caps 4 m-tiles at 8 waves)
 template <int KIND>
 int launch_stream(const TwoFormRoute& r, const Nvfp4Args& a, hipStream_t st) {
   if (int rc = with_stream_form<false>("nvfp4_stream_kernel", r, [&](auto mt, auto waves) {
         constexpr int MT = decltype(mt)::value, WAVES = decltype(waves)::value;
-        ao::launch(nvfp4_stream_kernel<KIND, MT, WAVES>, dim3(r.grid_x, r.grid_y), dim3(64 * WAVES), 0, st, a);
+        ao::launch(nvfp4_stream_kernel<KIND, MT, WAVES, false>, dim3(r.grid_x, r.grid_y), dim3(64 * WAVES), 0, st, a);
       }))
     return rc;
   AO_LAUNCH_CHECK("nvfp4_stream_kernel launch");
@@ -354,9 +479,52 @@ int launch_stream(const TwoFormRoute& r, const Nvfp4Args& a, hipStream_t st) {
 
 template <int KIND>
 int launch_tile(const TwoFormRoute& r, const Nvfp4Args& a, hipStream_t st) {
-  ao::launch(nvfp4_tile_kernel<KIND>, dim3(r.grid_x, r.grid_y), dim3(256), 0, st, a);
+  ao::launch(nvfp4_tile_kernel<KIND, false>, dim3(r.grid_x, r.grid_y), dim3(256), 0, st, a);
   AO_LAUNCH_CHECK("nvfp4_tile_kernel launch");
   return AO_OK;
+}
+
+template <int KIND>
+int launch_grouped_stream(const TwoFormRoute& r, const Nvfp4Args& a, hipStream_t st) {
+  if (int rc = with_stream_form<false>("nvfp4_grouped_stream_kernel", r, [&](auto mt, auto waves) {
+        constexpr int MT = decltype(mt)::value, WAVES = decltype(waves)::value;
+        ao::launch(nvfp4_stream_kernel<KIND, MT, WAVES, true>, dim3(r.grid_x, r.grid_y), dim3(64 * WAVES), 0, st, a);
+      }))
+    return rc;
+  AO_LAUNCH_CHECK("nvfp4_grouped_stream_kernel (nvfp4_stream_kernel<GROUPED>) launch");
+  return AO_OK;
+}
+
+template <int KIND>
+int launch_grouped_tile(const TwoFormRoute& r, const Nvfp4Args& a, hipStream_t st) {
+  ao::launch(nvfp4_tile_kernel<KIND, true>, dim3(r.grid_x, r.grid_y), dim3(256), 0, st, a);
+  AO_LAUNCH_CHECK("nvfp4_grouped_tile_kernel (nvfp4_tile_kernel<GROUPED>) launch");
+  return AO_OK;
+}
+
+// ---- the grouped route ------------------------------------------------------------------------------------------------------------
+// Without a sync the host knows only M_total and E: the route keys on the mean group size ceil(M_total / E).
+constexpr int kGroupedStreamMaxRows = AO_NVFP4_GROUPED_STREAM_MAX_ROWS;
+
+thread_local int g_grouped_form = 0;  // ao_nvfp4_grouped_mm_set_form: 0 the product route, 1 stream, 2 tile
+
+bool nvfp4_grouped_shape_ok(int kind, int64_t M_total, int64_t N, int64_t K, int64_t E) {
+  if (E < 1 || E > 65535) return false;
+  return nvfp4_shape_ok(kind, M_total, N, K);  // M_total K and the per-expert N K below 2^31; the expert base is 64-bit
+}
+
+// kernel 1: nvfp4_grouped_stream_kernel, grid (ceil(N / 16), E), m-tiles and waves of the stream plan at the mean group size;
+// 2: nvfp4_grouped_tile_kernel, grid (ceil(N / 64), ceil(M_total / 64) + E)
+TwoFormRoute nvfp4_grouped_route(int kind, int64_t M_total, int64_t N, int64_t K, int64_t E) {
+  if (!nvfp4_grouped_shape_ok(kind, M_total, N, K, E)) return TwoFormRoute{};
+  const int64_t mean = (M_total + E - 1) / E;
+  const int form = g_grouped_form != 0 ? g_grouped_form : (mean <= kGroupedStreamMaxRows ? 1 : 2);
+  TwoFormRoute r = two_form_route(form, form == 1 ? mean : M_total, N, K, 64);
+  if (r.kernel == 0) return TwoFormRoute{};
+  const int64_t gy = form == 1 ? E : (int64_t)r.grid_y + E;
+  if (gy > 65535) return TwoFormRoute{};
+  r.grid_y = (int)gy;
+  return r;
 }
 
 bool aligned_to(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
@@ -471,4 +639,114 @@ extern "C" int ao_nvfp4_linear(const uint8_t* a, const uint8_t* a_scale, const f
              "%s: the per-tensor scales must be 4-byte, bias and out 2-byte aligned", __func__);
   const Nvfp4Args args{nullptr, a, a_scale, b, b_scale, a_per_tensor_scale, b_per_tensor_scale, bias, out, (int)M, (int)N, (int)K};
   return run<kKindDyn>(__func__, args, M, N, K, static_cast<hipStream_t>(stream));
+}
+
+// ---- grouped (MoE experts) ----------------------------------------------------------------------------------------------------------
+extern "C" int ao_nvfp4_grouped_mm_route(int kind, int64_t M_total, int64_t N, int64_t K, int64_t E, int32_t* out, int cap) {
+  AO_REQUIRE_PTR(out);
+  AO_REQUIRE(cap >= 7, "ao_nvfp4_grouped_mm_route: cap must be >= 7, got %d", cap);
+  write_route(nvfp4_grouped_route(kind, M_total, N, K, E), out);
+  return AO_OK;
+}
+
+extern "C" const char* ao_nvfp4_grouped_mm_kernel_name(int kind, int64_t M_total, int64_t N, int64_t K, int64_t E) {
+  switch (nvfp4_grouped_route(kind, M_total, N, K, E).kernel) {
+    case 1: return "nvfp4_grouped_stream_kernel";
+    case 2: return "nvfp4_grouped_tile_kernel";
+    default: return "invalid";
+  }
+}
+
+extern "C" int ao_nvfp4_grouped_mm_set_form(int form) {
+  AO_REQUIRE(form >= 0 && form <= 2, "ao_nvfp4_grouped_mm_set_form: form must be 0 (route), 1 (stream) or 2 (tile), got %d", form);
+  g_grouped_form = form;
+  return AO_OK;
+}
+
+extern "C" int ao_nvfp4_grouped_mm(int kind, const uint16_t* x, const uint8_t* a, const uint8_t* a_scale, const uint8_t* b, const uint8_t* b_scale,
+                                   const float* pa, const float* pb, const int32_t* offs, uint16_t* out, int64_t M_total, int64_t N, int64_t K,
+                                   int64_t E, void* stream) {
+  AO_REQUIRE(nvfp4_grouped_shape_ok(kind, M_total, N, K, E),
+             "%s: bad kind or shape kind=%d M_total=%lld N=%lld K=%lld E=%lld (kind 0 or 1, M_total >= 0, N >= 1, K a positive multiple of 16, "
+             "1 <= E <= 65535, M_total K and the per-expert N K < 2^31)",
+             __func__, kind, (long long)M_total, (long long)N, (long long)K, (long long)E);
+  AO_REQUIRE_PTR(b);
+  AO_REQUIRE_PTR(b_scale);
+  AO_REQUIRE_PTR(offs);
+  AO_REQUIRE(kind == kKindDyn || pa == nullptr, "%s: the weight-only kind takes no activation scale pa", __func__);
+  if (M_total == 0) return AO_OK;
+  if (kind == kKindWo) {
+    AO_REQUIRE_PTR(x);
+    AO_REQUIRE(aligned_to(x, 16), "%s: x must be 16-byte aligned", __func__);
+  } else {
+    AO_REQUIRE_PTR(a);
+    AO_REQUIRE_PTR(a_scale);
+    AO_REQUIRE(aligned_to(a, K % 32 ? 8 : 16) && aligned_to(a_scale, K % 32 ? 1 : 2),
+               "%s: the activation codes must be 16-byte and their block scales 2-byte aligned (K %% 32 != 0: 8-byte and 1-byte)", __func__);
+  }
+  AO_REQUIRE_PTR(out);
+  AO_REQUIRE(aligned_to(b, K % 32 ? 8 : 16) && aligned_to(b_scale, K % 32 ? 1 : 2),
+             "%s: the weight codes must be 16-byte and their block scales 2-byte aligned (K %% 32 != 0: 8-byte and 1-byte)", __func__);
+  AO_REQUIRE(aligned_to(pa, 4) && aligned_to(pb, 4) && aligned_to(offs, 4) && aligned_to(out, 2),
+             "%s: the per-expert scales and offs must be 4-byte, out 2-byte aligned", __func__);
+  const TwoFormRoute r = nvfp4_grouped_route(kind, M_total, N, K, E);
+  AO_REQUIRE(r.kernel != 0, "%s: no route for M_total=%lld N=%lld K=%lld E=%lld (more than 65535 grid rows)", __func__, (long long)M_total,
+             (long long)N, (long long)K, (long long)E);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (kind == kKindWo) {
+    const Nvfp4Args args{x, nullptr, nullptr, b, b_scale, nullptr, pb, nullptr, out, (int)M_total, (int)N, (int)K, offs, (int)E};
+    return r.kernel == 1 ? launch_grouped_stream<kKindWo>(r, args, st) : launch_grouped_tile<kKindWo>(r, args, st);
+  }
+  const Nvfp4Args args{nullptr, a, a_scale, b, b_scale, pa, pb, nullptr, out, (int)M_total, (int)N, (int)K, offs, (int)E};
+  return r.kernel == 1 ? launch_grouped_stream<kKindDyn>(r, args, st) : launch_grouped_tile<kKindDyn>(r, args, st);
+}
+
+namespace {
+int check_grouped_rows(const char* fn, int64_t M_total, int64_t K, int64_t E) {
+  AO_REQUIRE(M_total >= 0 && K > 0 && K % 16 == 0 && E >= 1 && E <= 65535 && M_total < (1ll << 31) && K < (1ll << 31) && M_total * K < (1ll << 40),
+             "%s: bad shape M_total=%lld K=%lld E=%lld (M_total >= 0, K a positive multiple of 16, 1 <= E <= 65535)", fn, (long long)M_total,
+             (long long)K, (long long)E);
+  return AO_OK;
+}
+}  // namespace
+
+extern "C" int ao_nvfp4_group_amax_scale(const uint16_t* x, const int32_t* offs, float* out, int64_t M_total, int64_t K, int64_t E, void* stream) {
+  if (int rc = check_grouped_rows(__func__, M_total, K, E)) return rc;
+  AO_REQUIRE_PTR(offs);
+  AO_REQUIRE_PTR(out);
+  AO_REQUIRE(aligned_to(out, 4) && aligned_to(offs, 4), "%s: out and offs must be 4-byte aligned", __func__);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  uint32_t* bits = reinterpret_cast<uint32_t*>(out);
+  const unsigned eg = (unsigned)((E + 255) / 256);
+  ao::launch(nvfp4_group_amax_clear_kernel, dim3(eg), dim3(256), 0, s, bits, (int)E);
+  if (M_total > 0) {
+    AO_REQUIRE_PTR(x);
+    AO_REQUIRE(aligned_to(x, 16), "%s: x must be 16-byte aligned", __func__);
+    // parts per group: one pass of 256 lanes over a group of the mean size (a larger group takes more passes of its grid-stride loop)
+    const int64_t pieces = M_total * K / 8;
+    const int64_t parts = std::max<int64_t>(1, std::min<int64_t>({(pieces / E + 255) / 256, 1024, (16384 + E - 1) / E}));
+    ao::launch(nvfp4_group_amax_kernel, dim3((unsigned)parts, (unsigned)E), dim3(256), 0, s, x, offs, (int)M_total, (int)K, bits);
+  }
+  ao::launch(nvfp4_group_amax_scale_kernel, dim3(eg), dim3(256), 0, s, bits, (int)E);
+  AO_LAUNCH_CHECK("nvfp4_group_amax kernels launch");
+  return AO_OK;
+}
+
+extern "C" int ao_nvfp4_quantize_grouped(const uint16_t* x, const float* p, const int32_t* offs, uint8_t* q, uint8_t* scale_e4m3, int64_t M_total,
+                                         int64_t K, int64_t E, void* stream) {
+  if (int rc = check_grouped_rows(__func__, M_total, K, E)) return rc;
+  AO_REQUIRE_PTR(offs);
+  if (M_total == 0) return AO_OK;
+  AO_REQUIRE_PTR(x);
+  AO_REQUIRE_PTR(q);
+  AO_REQUIRE_PTR(scale_e4m3);
+  AO_REQUIRE(aligned_to(x, 16) && aligned_to(q, 8) && aligned_to(p, 4) && aligned_to(offs, 4),
+             "%s: x must be 16-byte, q 8-byte, p and offs 4-byte aligned", __func__);
+  const int64_t blocks = M_total * (K / 16);
+  const int64_t grid = (blocks + 255) / 256;
+  AO_REQUIRE(grid < (1ll << 31), "%s: tensor too large for one launch", __func__);
+  ao::launch(nvfp4_quant_grouped_kernel, dim3((unsigned)grid), dim3(256), 0, static_cast<hipStream_t>(stream), x, p, offs, q, scale_e4m3, blocks,
+             (int)(K / 16), (int)E);
+  AO_LAUNCH_CHECK("nvfp4_quant_grouped_kernel launch");
+  return AO_OK;
 }

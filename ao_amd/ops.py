@@ -1674,3 +1674,138 @@ def nvfp4_linear(x2, wq, w_scale, w_per_tensor_scale=None, act_per_tensor_scale=
 
 __all__ += ["nvfp4_amax_scale", "nvfp4_quantize", "nvfp4_wo_linear", "nvfp4_mm", "nvfp4_linear", "nvfp4_linear_route",
             "nvfp4_linear_kernel_name", "nvfp4_set_form"]
+
+
+# ---- NVFP4 grouped GEMM for MoE experts (include/ao_mi355.h "NVFP4 grouped GEMM") -----------------------------------------
+NVFP4_GROUPED_KERNELS = {0: "invalid", 1: "nvfp4_grouped_stream_kernel", 2: "nvfp4_grouped_tile_kernel"}
+
+
+def nvfp4_grouped_mm_route(kind: int, m_total: int, n: int, k: int, e: int) -> dict:
+    """The route nvfp4_grouped_mm launches for a kind and shape (host logic only, ao_nvfp4_grouped_mm_route: it keys on the mean group
+    size ceil(M_total / E)); kernel "invalid" for shapes nothing takes."""
+    out = (ctypes.c_int32 * 7)()
+    _lib.check(_lib.lib().ao_nvfp4_grouped_mm_route(int(kind), int(m_total), int(n), int(k), int(e), out, 7))
+    kernel, waves, mt, tile_m, tile_n, gx, gy = list(out)
+    return {"kernel": NVFP4_GROUPED_KERNELS.get(kernel, "invalid"), "waves": waves, "m_tiles": mt, "tile_m": tile_m, "tile_n": tile_n,
+            "grid": (gx, gy)}
+
+
+def nvfp4_grouped_mm_kernel_name(kind: int, m_total: int, n: int, k: int, e: int) -> str:
+    return _lib.lib().ao_nvfp4_grouped_mm_kernel_name(int(kind), int(m_total), int(n), int(k), int(e)).decode()
+
+
+def nvfp4_grouped_mm_set_form(form: int) -> None:
+    """Measurement only: 0 the product route, 1 the streaming form, 2 the tiled form (calling thread)."""
+    _lib.check(_lib.lib().ao_nvfp4_grouped_mm_set_form(int(form)))
+
+
+def _nvfp4_offs(name, offs, e):
+    if offs.dtype != torch.int32 or offs.dim() != 1 or offs.numel() != e:
+        raise RuntimeError(f"{name}: offs must be int32 [E] = [{e}], got {offs.dtype} {tuple(offs.shape)}")
+    return offs.contiguous()
+
+
+def _nvfp4_expert_scales(name, what, p, e, dev):
+    """Per-expert (per-group) scales as fp32 [E] on the device (None stays None): read by the kernels, never on the host."""
+    if p is None:
+        return None
+    if not isinstance(p, torch.Tensor) or p.numel() != e:
+        raise RuntimeError(f"{name}: {what} must be a tensor of E = {e} elements, one an expert, got "
+                           f"{tuple(p.shape) if isinstance(p, torch.Tensor) else type(p).__name__}")
+    if p.device != dev:
+        raise RuntimeError(f"{name}: {what} is on {p.device}, the operands on {dev}")
+    return p.reshape(e).to(torch.float32).contiguous()
+
+
+def _nvfp4_expert_codes(name, q, s):
+    q = q.view(torch.uint8) if q.dtype == torch.float4_e2m1fn_x2 else q
+    if q.dtype != torch.uint8 or q.dim() != 3:
+        raise RuntimeError(f"{name}: the weight codes must be a 3-D uint8 tensor [E, N, K/2], got {q.dtype} {tuple(q.shape)}")
+    e, n, k = q.shape[0], q.shape[1], q.shape[2] * 2
+    if e < 1 or n < 1:
+        raise RuntimeError(f"{name}: the weight codes must hold at least one expert and one row, got {tuple(q.shape)}")
+    if s.dtype not in (torch.float8_e4m3fn, torch.uint8):
+        raise RuntimeError(f"{name}: the weight block scales must be float8_e4m3fn, got {s.dtype}")
+    s = s.view(torch.uint8)
+    if k == 0 or k % 16 != 0 or tuple(s.shape) != (e, n, k // 16):
+        raise RuntimeError(f"{name}: the weight block scales must be row-major [E, N, K/16] = {(e, n, k // 16)}, got {tuple(s.shape)}")
+    return q.contiguous(), s.contiguous(), e, n, k
+
+
+def nvfp4_group_amax_scale(x: torch.Tensor, offs: torch.Tensor) -> torch.Tensor:
+    """nvfp4_amax_scale per token group (ao_nvfp4_group_amax_scale): x bf16 [M_total, K], offs int32 [E] cumulative group ends -> fp32 [E],
+    max|x[group e]| / 2688 (NaN if the group holds one, 0 for an empty group).  No host read (capturable)."""
+    name = "nvfp4_group_amax_scale"
+    dev = _require_gpu(name, x, offs)
+    if x.dim() != 2:
+        raise RuntimeError(f"{name}: x must be 2-D [M_total, K], got {tuple(x.shape)}")
+    r, c = _nvfp4_rows(name, x)
+    offs = _nvfp4_offs(name, offs, offs.numel() if offs.dim() == 1 else -1)
+    e = offs.numel()
+    out = torch.empty((e,), dtype=torch.float32, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_nvfp4_group_amax_scale(_ptr(x), _ptr(offs), _ptr(out), r, c, e, _stream()))
+    return out
+
+
+def nvfp4_quantize_grouped(x: torch.Tensor, per_group_scale: Optional[torch.Tensor], offs: torch.Tensor):
+    """nvfp4_quantize with row r cast under per_group_scale[e] of the group that holds it (ao_nvfp4_quantize_grouped): x bf16 [M_total, K],
+    per_group_scale fp32 [E] on the device or None, offs int32 [E] -> (codes uint8 [M_total, K/2], block scales float8_e4m3fn
+    [M_total, K/16]).  Rows past offs[-1] are not cast: they are zero in the fresh outputs."""
+    name = "nvfp4_quantize_grouped"
+    dev = _require_gpu(name, x, per_group_scale, offs)
+    if x.dim() != 2:
+        raise RuntimeError(f"{name}: x must be 2-D [M_total, K], got {tuple(x.shape)}")
+    r, c = _nvfp4_rows(name, x)
+    offs = _nvfp4_offs(name, offs, offs.numel() if offs.dim() == 1 else -1)
+    e = offs.numel()
+    p = _nvfp4_expert_scales(name, "per_group_scale", per_group_scale, e, dev)
+    q = torch.zeros((r, c // 2), dtype=torch.uint8, device=dev)
+    s = torch.zeros((r, c // 16), dtype=torch.uint8, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_nvfp4_quantize_grouped(_ptr(x), _ptr(p), _ptr(offs), _ptr(q), _ptr(s), r, c, e, _stream()))
+    return q, s.view(torch.float8_e4m3fn)
+
+
+def nvfp4_grouped_mm(kind, a, a_scale, wq, w_scale, offs, a_per_group_scale=None, w_per_expert_scale=None, out=None):
+    """The NVFP4 chains per token group against that group's expert (ao_nvfp4_grouped_mm), no bias.
+    kind NVFP4_KIND_WEIGHT_ONLY: a bf16 [M_total, K], a_scale None; nvfp4_wo_linear per group.
+    kind NVFP4_KIND_DYNAMIC: a codes [M_total, K/2], a_scale e4m3 [M_total, K/16]; nvfp4_mm per group.
+    wq codes [E, N, K/2] (the experts as stored), w_scale e4m3 [E, N, K/16], offs int32 [E] cumulative group ends (read on the device),
+    a_per_group_scale / w_per_expert_scale fp32 [E] on the device or None -> bf16 [M_total, N].  Rows past offs[-1] are not written: a fresh
+    output is zero-filled, an `out=` tensor keeps what it held there."""
+    name = "nvfp4_grouped_mm"
+    dev = _require_gpu(name, a, a_scale, wq, w_scale, offs, a_per_group_scale, w_per_expert_scale, out)
+    wq, w_scale, e, n, k = _nvfp4_expert_codes(name, wq, w_scale)
+    if kind == NVFP4_KIND_WEIGHT_ONLY:
+        if a.dim() != 2 or a.dtype != torch.bfloat16:
+            raise RuntimeError(f"{name}: the weight-only activation must be a 2-D bfloat16 tensor, got {tuple(a.shape)} {a.dtype}")
+        if a_scale is not None or a_per_group_scale is not None:
+            raise RuntimeError(f"{name}: the weight-only kind takes no activation scales")
+        x, aq, a_s = a.contiguous(), None, None
+        m, ka = x.shape
+    elif kind == NVFP4_KIND_DYNAMIC:
+        if a_scale is None:
+            raise RuntimeError(f"{name}: the codes x codes kind needs the activation block scales")
+        aq, a_s, m, ka = _nvfp4_codes(name, "activation", a, a_scale)
+        x = None
+    else:
+        raise RuntimeError(f"{name}: kind must be NVFP4_KIND_WEIGHT_ONLY (0) or NVFP4_KIND_DYNAMIC (1), got {kind}")
+    if ka != k:
+        raise RuntimeError(f"{name}: K of the activation ({ka}) and of the weight ({k}) differ")
+    offs = _nvfp4_offs(name, offs, e)
+    pa = _nvfp4_expert_scales(name, "a_per_group_scale", a_per_group_scale, e, dev)
+    pb = _nvfp4_expert_scales(name, "w_per_expert_scale", w_per_expert_scale, e, dev)
+    if out is None:
+        y = torch.zeros((m, n), dtype=torch.bfloat16, device=dev)
+    else:
+        y = _bf16_out(name, out, m, n, dev)
+    if m > 0:
+        with _on(dev):
+            _lib.check(_lib.lib().ao_nvfp4_grouped_mm(int(kind), _ptr(x), _ptr(aq), _ptr(a_s), _ptr(wq), _ptr(w_scale), _ptr(pa), _ptr(pb),
+                                                      _ptr(offs), _ptr(y), m, n, k, e, _stream()))
+    return y
+
+
+__all__ += ["nvfp4_grouped_mm", "nvfp4_group_amax_scale", "nvfp4_quantize_grouped", "nvfp4_grouped_mm_route",
+            "nvfp4_grouped_mm_kernel_name", "nvfp4_grouped_mm_set_form"]

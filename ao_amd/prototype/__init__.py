@@ -1,5 +1,6 @@
 """Prototype-namespace mirrors (torchao/prototype/*) that sit on the SURVEY.md section 8 path."""
 from .blockwise_fp8 import Float8BlockwiseExpertWeights, fp8_blockwise_grouped_mm  # noqa: F401
+from .nvfp4_grouped import NVFP4ExpertWeights, nvfp4_grouped_mm  # noqa: F401
 from .nvfp4_tensor import (  # noqa: F401
     NVFP4DynamicActivationNVFP4WeightConfig,
     NVFP4Tensor,
@@ -9,4 +10,5 @@ from .nvfp4_tensor import (  # noqa: F401
 )
 
 __all__ = ["Float8BlockwiseExpertWeights", "fp8_blockwise_grouped_mm", "NVFP4Tensor", "NVFP4WeightOnlyConfig",
-           "NVFP4DynamicActivationNVFP4WeightConfig", "QuantizeTensorToNVFP4Kwargs", "per_tensor_amax_to_scale"]
+           "NVFP4DynamicActivationNVFP4WeightConfig", "QuantizeTensorToNVFP4Kwargs", "per_tensor_amax_to_scale", "NVFP4ExpertWeights",
+           "nvfp4_grouped_mm"]

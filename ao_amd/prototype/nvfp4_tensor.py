@@ -15,7 +15,8 @@ Scales are stored ROW-MAJOR [rows, K/16] and `is_swizzled_scales` is always Fals
 scale bytes as per-lane register operands, so the 128 x 4 blocked layout the reference stores for cuBLAS has no use here.  A scale tensor a
 reference run or a checkpoint holds in that layout is un-swizzled once, on load, by NVFP4Tensor.from_reference_layout.  `use_triton_kernel`
 is accepted and ignored.  Not implemented (NotImplementedError): float32 weights or activations, 3-D / per-expert weights and
-_grouped_mm, and the observer flow step="prepare" / "convert".
+_grouped_mm ON THIS CLASS -- the experts of an MoE layer are an NVFP4ExpertWeights and their GEMM nvfp4_grouped_mm (nvfp4_grouped.py) --
+and the observer flow step="prepare" / "convert".
 """
 import enum
 from dataclasses import dataclass
@@ -105,8 +106,8 @@ class NVFP4Tensor(LowBitTensorBase):
         assert not is_swizzled_scales, ("NVFP4Tensor on MI355X stores row-major scales (is_swizzled_scales=False); load a swizzled scale "
                                         "tensor with NVFP4Tensor.from_reference_layout")
         if per_tensor_scale is not None and per_tensor_scale.dim() != 0:
-            raise NotImplementedError(f"NVFP4Tensor on MI355X takes a 0-dim per_tensor_scale (per-expert scales are not implemented), got "
-                                      f"shape {tuple(per_tensor_scale.shape)}")
+            raise NotImplementedError(f"NVFP4Tensor on MI355X takes a 0-dim per_tensor_scale (per-expert scales belong to "
+                                      f"NVFP4ExpertWeights), got shape {tuple(per_tensor_scale.shape)}")
         self.qdata = qdata
         self.scale = scale
         self.block_size = block_size
@@ -145,8 +146,8 @@ class NVFP4Tensor(LowBitTensorBase):
         """reference :131-194.  The cast runs on the MI355X kernel (ops.nvfp4_quantize: the bytes of the reference's nvfp4_quantize).
         is_swizzled_scales and use_triton_kernel are accepted and ignored: the scales are stored row-major."""
         if data_hp.dim() != 2:
-            raise NotImplementedError(f"NVFP4Tensor on MI355X quantizes 2-D tensors (3-D / per-expert weights are not implemented), got "
-                                      f"shape {tuple(data_hp.shape)}")
+            raise NotImplementedError(f"NVFP4Tensor on MI355X quantizes 2-D tensors (3-D / per-expert weights: "
+                                      f"NVFP4ExpertWeights.from_hp), got shape {tuple(data_hp.shape)}")
         _require_bf16("tensors", data_hp.dtype)
         assert block_size == BLOCK, "NVFP4 requires block_size=16"
         assert data_hp.shape[-1] % block_size == 0, "K dim must be divisible by block_size"
@@ -267,7 +268,8 @@ def _(func, types, args, kwargs):
 
 @implements(aten._grouped_mm.default)
 def _(func, types, args, kwargs):
-    raise NotImplementedError("NVFP4Tensor _grouped_mm (3-D / per-expert weights) is not implemented on MI355X")
+    raise NotImplementedError("NVFP4Tensor _grouped_mm (3-D / per-expert weights) is not implemented on MI355X: use "
+                              "ao_amd.prototype.nvfp4_grouped_mm on an NVFP4ExpertWeights")
 
 
 @implements(aten.t.default)

@@ -84,6 +84,9 @@ _lib_def.define("nvfp4_quantize(Tensor x, Tensor? per_tensor_scale) -> (Tensor, 
 _lib_def.define("nvfp4_wo_linear(Tensor x, Tensor wq, Tensor w_scale, Tensor? per_tensor_scale, Tensor? bias) -> Tensor")
 _lib_def.define("nvfp4_mm(Tensor a, Tensor a_scale, Tensor b, Tensor b_scale, Tensor? a_per_tensor_scale, Tensor? b_per_tensor_scale, Tensor? bias) -> Tensor")
 _lib_def.define("nvfp4_linear(Tensor x, Tensor wq, Tensor w_scale, Tensor? w_per_tensor_scale, Tensor? act_per_tensor_scale, bool dynamic_per_tensor_scale, Tensor? bias) -> Tensor")
+_lib_def.define("nvfp4_group_amax_scale(Tensor x, Tensor offs) -> Tensor")
+_lib_def.define("nvfp4_quantize_grouped(Tensor x, Tensor? per_group_scale, Tensor offs) -> (Tensor, Tensor)")
+_lib_def.define("nvfp4_grouped_mm(int kind, Tensor a, Tensor? a_scale, Tensor wq, Tensor w_scale, Tensor offs, Tensor? a_per_group_scale, Tensor? w_per_expert_scale) -> Tensor")
 # same schemas as torchao::fused_pad_token_groups / fused_unpad_token_groups (kernels/mxfp8/quant.py:1244-1246, 1319-1321)
 _lib_def.define("fused_pad_token_groups(Tensor inputs, Tensor offsets, int alignment_size) -> (Tensor, Tensor, Tensor)")
 _lib_def.define(
@@ -124,6 +127,9 @@ _lib_impl.impl("nvfp4_quantize", ops.nvfp4_quantize)
 _lib_impl.impl("nvfp4_wo_linear", lambda x, wq, w_scale, p, bias: ops.nvfp4_wo_linear(x, wq, w_scale, p, bias))
 _lib_impl.impl("nvfp4_mm", lambda a, a_scale, b, b_scale, pa, pb, bias: ops.nvfp4_mm(a, a_scale, b, b_scale, pa, pb, bias))
 _lib_impl.impl("nvfp4_linear", ops.nvfp4_linear)
+_lib_impl.impl("nvfp4_group_amax_scale", ops.nvfp4_group_amax_scale)
+_lib_impl.impl("nvfp4_quantize_grouped", ops.nvfp4_quantize_grouped)
+_lib_impl.impl("nvfp4_grouped_mm", lambda kind, a, a_scale, wq, w_scale, offs, pa, pb: ops.nvfp4_grouped_mm(kind, a, a_scale, wq, w_scale, offs, pa, pb))
 _lib_impl.impl("fused_pad_token_groups", ops.fused_pad_token_groups)
 _lib_impl.impl("fused_unpad_token_groups", ops.fused_unpad_token_groups)
 
@@ -297,6 +303,22 @@ def _(x, wq, w_scale, w_per_tensor_scale, act_per_tensor_scale, dynamic_per_tens
     return x.new_empty((x.shape[0], wq.shape[0]), dtype=torch.bfloat16)
 
 
+@torch.library.register_fake("ao_mi355::nvfp4_group_amax_scale")
+def _(x, offs):
+    return x.new_empty((offs.shape[0],), dtype=torch.float32)
+
+
+@torch.library.register_fake("ao_mi355::nvfp4_quantize_grouped")
+def _(x, per_group_scale, offs):
+    return (x.new_empty((x.shape[0], x.shape[1] // 2), dtype=torch.uint8),
+            x.new_empty((x.shape[0], x.shape[1] // 16), dtype=torch.float8_e4m3fn))
+
+
+@torch.library.register_fake("ao_mi355::nvfp4_grouped_mm")
+def _(kind, a, a_scale, wq, w_scale, offs, a_per_group_scale, w_per_expert_scale):
+    return a.new_empty((a.shape[0], wq.shape[1]), dtype=torch.bfloat16)
+
+
 @torch.library.register_fake("ao_mi355::fused_pad_token_groups")
 def _(inputs, offsets, alignment_size):
     rows = inputs.shape[0] + offsets.shape[0] * alignment_size
@@ -321,7 +343,8 @@ for _name in ("weight_int4pack_mm", "convert_weight_to_int4pack", "int8_scaled_m
               "int8_linear_static", "fp8_int4_linear", "fp8_int4_act_linear", "int8_quantize_rowwise", "fp8_quantize_rowwise", "mxfp8_quantize", "mxfp8_grouped_mm",
               "fused_pad_token_groups", "fused_unpad_token_groups", "mxfp4_quantize", "mx_mm", "mx_linear", "int8_wo_linear", "fp8_wo_linear",
               "fp8_quantize_block_1x128", "fp8_quantize_block_128x128", "fp8_block_linear", "fp8_block_grouped_mm",
-              "nvfp4_amax_scale", "nvfp4_quantize", "nvfp4_wo_linear", "nvfp4_mm", "nvfp4_linear"):
+              "nvfp4_amax_scale", "nvfp4_quantize", "nvfp4_wo_linear", "nvfp4_mm", "nvfp4_linear",
+              "nvfp4_group_amax_scale", "nvfp4_quantize_grouped", "nvfp4_grouped_mm"):
     _lib_autograd.impl(_name, torch.library.fallthrough_kernel)
 
 

@@ -733,6 +733,61 @@ const char* ao_nvfp4_linear_kernel_name(int kind, int64_t M, int64_t N, int64_t 
  * linears (0 the product route, 1 streaming, 2 tiled); the route query reports the forced form. */
 int ao_nvfp4_linear_set_form(int form);
 
+/* ---- NVFP4 grouped GEMM for MoE experts (nvfp4_kernels.hip) -------------------------------------------------------------
+ * Replaces NVFP4Tensor's aten._grouped_mm (nvfp4_tensor.py:709-753) on 3-D weights with a per-expert [E, 1, 1] scale
+ * (inference_workflow.py:309-319, nvfp4_tensor.py:830-834), which runs only through mslk or scaled_grouped_mm on sm100, and its portable
+ * form _emulated_nvfp4_scaled_grouped_mm_2d_3d (prototype/moe_training/nvfp4_grouped_mm.py:62-116: both operands dequantized to bf16, then
+ * torch._grouped_mm, 2 bytes a weight).  Token group e = rows [offs[e-1], offs[e]) (offs[-1] = 0) against expert e, the dense chain of
+ * ao_nvfp4_wo_linear / ao_nvfp4_linear per output element, no bias (_grouped_mm has none):
+ *   kind 0 (weight-only): w = bf16(f32(code) (pb[e] f32(s8)));  out = bf16(sum_k x w), fp32 sum, one rounding -- the reference's
+ *     torch._grouped_mm(x, dequantize(bf16)^T, offs).
+ *   kind 1 (codes x codes): acc = sum_k (a_code a_s8)(b_code b_s8) in fp32.  Neither pa nor pb: out = bf16(acc), the reference's emulated
+ *     2d-3d function.  Otherwise t = bf16(acc);  out = bf16(f32(t) f32(bf16(P_e))), P_e = pa[e] pb[e] (fp32) or the one present: the
+ *     dense entry's chain per group.  How sm100 applies the tensor-wise scales cannot be observed on this hardware, so this is the
+ *     library's stated contract, as for ao_nvfp4_linear.
+ * x bf16 [M_total][K] (kind 0; a and a_scale ignored) or a codes [M_total][K/2] with a_scale e4m3 [M_total][K/16] (kind 1; x ignored);
+ * b codes [E][N][K/2]; b_scale e4m3 [E][N][K/16], row-major; pb fp32 [E] or NULL (per-expert weight scale); pa fp32 [E] or NULL
+ * (per-group activation scale, kind 1 only: kind 0 refuses one); offs int32 [E], cumulative group ends, read on the device (no host sync);
+ * out bf16 [M_total][N].  Rows past offs[E-1] are not written.  Empty groups are legal anywhere; group sizes need no alignment.  A group's
+ * row range is clamped to [0, M_total] and a non-increasing pair of offs is an empty group, so a bad offs cannot address outside the
+ * activation or out.  K parts are cut at multiples of 128 and added in part order: a launch is reproducible.
+ * M_total >= 0 (0: OK, nothing launched), N >= 1 (ragged N masked), K a positive multiple of 16, 1 <= E <= 65535; M_total K and the
+ * per-expert N K below 2^31 (the expert base is 64-bit pointer arithmetic: the whole b may pass 2^31 elements).  Alignment as the dense
+ * entries (a per-expert stride cannot break the 16-byte row alignment for 16 | K); pa, pb and offs 4-byte.  Null pointers and bad shapes
+ * are rejected on the host before any launch. */
+/* The route keys on the mean group size ceil(M_total / E), all the host knows without a sync: nvfp4_grouped_stream_kernel up to this many
+ * rows, nvfp4_grouped_tile_kernel beyond (one seam for both kinds).  It started at the 16 rows the blockwise float8 grouped GEMM fitted for
+ * the same two-form structure; the sweep of tools/bench_nvfp4_grouped.py --sweep (each form forced over uniform groups of 2 .. 512 rows
+ * on one EP-8 rank's DeepSeek-V3 and Qwen3-235B experts, both kinds, profiles/nvfp4_grouped.jsonl) moved it to 0: these tiles have 64
+ * rows, not 128, and the tiled form was the faster one at EVERY swept group size, 2 rows included -- summed over the four shapes, both
+ * kinds and fourteen group sizes the hand-over at 0 rows costs 37179 us, at 2 rows 37427, at 16 rows 38342, at 64 rows 43566.  So the
+ * product route takes the tiled form for every M_total >= 1 and the streaming form is reached by the forced form only. */
+#define AO_NVFP4_GROUPED_STREAM_MAX_ROWS 0
+int ao_nvfp4_grouped_mm(int kind, const uint16_t* x, const uint8_t* a, const uint8_t* a_scale, const uint8_t* b, const uint8_t* b_scale,
+                        const float* pa, const float* pb, const int32_t* offs, uint16_t* out, int64_t M_total, int64_t N, int64_t K, int64_t E,
+                        void* stream);
+/* Replaces per_tensor_amax_to_scale(amax(dim=(1, 2))) of the per-expert weight scale (inference_workflow.py:309-319) and the per-group
+ * dynamic activation scale: x bf16 [M_total][K] -> out[e] = max|x[group e]| / 2688, the bits of ao_nvfp4_amax_scale on that group's rows
+ * (NaN if the group holds one; an empty group gives 0).  No host read (capturable).  x 16-byte, out and offs 4-byte aligned. */
+int ao_nvfp4_group_amax_scale(const uint16_t* x, const int32_t* offs, float* out, int64_t M_total, int64_t K, int64_t E, void* stream);
+/* Replaces nvfp4_quantize (nvfp4_tensor.py:772-854) under a per-group scale: ao_nvfp4_quantize's bytes with row r cast under p[e] of the
+ * group e that holds it (the first e with offs[e] > r).  Rows past offs[E-1] are not written.  p = NULL: ao_nvfp4_quantize on the rows
+ * below offs[E-1].  The same two entries serve the weights: view [E][N][K] as [E N][K] with offs[e] = N (e + 1), which gives the reference's
+ * bytes for to_nvfp4(w3d, per_tensor_scale=[E, 1, 1]) (nvfp4_quantize reshapes to [E, -1, 16] and broadcasts the scale, :830-834).  A zero
+ * (or infinite) p[e] is outside the contract, as for ao_nvfp4_quantize: so is the dynamic per-group scale of an all-zero group. */
+int ao_nvfp4_quantize_grouped(const uint16_t* x, const float* p, const int32_t* offs, uint8_t* q, uint8_t* scale_e4m3, int64_t M_total, int64_t K,
+                              int64_t E, void* stream);
+/* The route of ao_nvfp4_grouped_mm (host logic only; nvfp4_tensor.py:709-753 has one path, this library two forms): out[cap >= 7] = kernel
+ * (0 = invalid kind or shape, or more than 65535 grid rows, 1 nvfp4_grouped_stream_kernel, 2 nvfp4_grouped_tile_kernel), waves per
+ * workgroup, m-tiles of 16 per pass or workgroup, tile rows, tile columns, grid x, grid y (stream: E; tile: ceil(M_total / 64) + E, the
+ * host's upper bound on the tile count). */
+int ao_nvfp4_grouped_mm_route(int kind, int64_t M_total, int64_t N, int64_t K, int64_t E, int32_t* out, int cap);
+/* "nvfp4_grouped_stream_kernel", "nvfp4_grouped_tile_kernel" or "invalid": the kernel of that route. */
+const char* ao_nvfp4_grouped_mm_kernel_name(int kind, int64_t M_total, int64_t N, int64_t K, int64_t E);
+/* Measurement only (no reference counterpart): force the form of the calling thread's NVFP4 grouped GEMMs (0 the product route,
+ * 1 streaming, 2 tiled); the route queries report the forced form. */
+int ao_nvfp4_grouped_mm_set_form(int form);
+
 #ifdef __cplusplus
 }
 #endif
