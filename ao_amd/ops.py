@@ -27,6 +27,7 @@ __all__ = [
     "fp8_scaled_mm",
     "mxfp8_quantize",
     "mxfp8_grouped_mm",
+    "mxfp8_grouped_mm_wgrad",
     "dynamic_linear_fits",
     "dynamic_linear_preferred",
     "int8_dynamic_linear",
@@ -764,6 +765,46 @@ def mxfp8_grouped_mm(a, a_scale, b, b_scale, offs):
                 _ptr(a), _ptr(a_scale), _ptr(b), _ptr(b_scale), _ptr(offs.contiguous()), _ptr(out), m, n, k, e, _stream()
             )
         )
+    return out
+
+
+def _colwise_rows(name, what, t, rows, cols):
+    """The contiguous uint8 [rows, cols] tensor behind a colwise cast's output: either that tensor itself or the {cols, rows} view with
+    strides {1, cols} that mxfp8_quantize_colwise returns."""
+    if t.dim() == 2 and tuple(t.shape) == (cols, rows) and t.t().is_contiguous():
+        return t.t()
+    if t.dim() == 2 and tuple(t.shape) == (rows, cols) and t.is_contiguous():
+        return t
+    raise RuntimeError(f"{name}: {what} must be the contiguous [{rows}, {cols}] tensor or its transposed view (what mxfp8_quantize_colwise "
+                       f"returns), got shape {tuple(t.shape)} strides {tuple(t.stride())}")
+
+
+def mxfp8_grouped_mm_wgrad(g_t, g_scale, x_t, x_scale, offs, N: int, K: int):
+    """The weight gradient of the MXFP8 grouped mm (mxfp8_grouped_mm.py:712-796, numerics of the emulated 2d-2d path :1026-1057), on the
+    colwise (32 x 1) casts of grad_out [M, N] and x [M, K]: g_t e4m3 [N, M], g_scale e8m0 [M/32, N], x_t e4m3 [K, M], x_scale e8m0
+    [M/32, K] -- or the strided views of these that mxfp8_quantize_colwise returns ({M, N} / {N, M/32} / {M, K} / {K, M/32}); offs int32
+    [E] -> bf16 [E, N, K] with out[e] = dq(g)[rows of e]^T @ dq(x)[rows of e]; an empty group gives zeros.  Any offsets."""
+    name = "mxfp8_grouped_mm_wgrad"
+    dev = _require_gpu(name, g_t, g_scale, x_t, x_scale, offs)
+    n, k = int(N), int(K)
+    if n <= 0 or k <= 0 or g_t.numel() % n != 0:
+        raise RuntimeError(f"{name}: g_t with {g_t.numel()} elements does not hold [N={n}, M] codes")
+    m = g_t.numel() // n
+    if m % 32 != 0:
+        raise RuntimeError(f"{name}: M_total={m} must be a multiple of 32 (one scale per 32 tokens)")
+    if g_scale.dtype not in (torch.uint8, torch.float8_e8m0fnu) or x_scale.dtype not in (torch.uint8, torch.float8_e8m0fnu):
+        raise RuntimeError(f"{name}: expected float8_e8m0fnu scales, got {g_scale.dtype} and {x_scale.dtype}")
+    g = _colwise_rows(name, "g_t", _fp8_bytes(name, g_t), n, m)
+    x = _colwise_rows(name, "x_t", _fp8_bytes(name, x_t), k, m)
+    gs = _colwise_rows(name, "g_scale", g_scale.view(torch.uint8), m // 32, n)
+    xs = _colwise_rows(name, "x_scale", x_scale.view(torch.uint8), m // 32, k)
+    if offs.dtype != torch.int32 or offs.dim() != 1 or offs.numel() < 1:
+        raise RuntimeError(f"{name}: offs must be int32 [E]")
+    e = offs.numel()
+    out = torch.empty((e, n, k), dtype=torch.bfloat16, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_mxfp8_grouped_mm_wgrad(_ptr(g), _ptr(gs), _ptr(x), _ptr(xs), _ptr(offs.contiguous()), _ptr(out), m, n, k, e,
+                                                        _stream()))
     return out
 
 

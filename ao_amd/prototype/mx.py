@@ -1,11 +1,13 @@
-"""MXFP8 (block 32, e4m3 elements, E8M0 scales): cast and MoE grouped GEMM forward, MI355X-native.  The MXFP4 cast and the dense MX
-linears (MXTensor, MXDynamicActivationMXWeightConfig) live in mx_tensor.py and are re-exported here.
+"""MXFP8 (block 32, e4m3 elements, E8M0 scales): cast and MoE grouped GEMM, forward and backward, MI355X-native.  The MXFP4 cast and the
+dense MX linears (MXTensor, MXDynamicActivationMXWeightConfig) live in mx_tensor.py and are re-exported here.
 
 Host-side mirror of
   * torchao/prototype/mx_formats/mx_tensor.py:228-409  to_mx(x, float8_e4m3fn, 32, mode)
-  * torchao/prototype/moe_training/mxfp8_grouped_mm.py:56-239,330-371
-    _to_mxfp8_then_scaled_grouped_mm -- FORWARD only, numerics of the reference's
-    emulated path (:959-1023): both operands dequantised per 32-block, fp32 accumulate, bf16 out.
+  * torchao/prototype/moe_training/mxfp8_grouped_mm.py:56-371, 597-796
+    _to_mxfp8_then_scaled_grouped_mm and its autograd Function _MXFP8GroupedMM: forward, dgrad (the forward GEMM on grad_out and the
+    weights cast along N) and wgrad (ops.mxfp8_grouped_mm_wgrad on the 32 x 1 casts of grad_out and A), numerics of the reference's
+    emulated paths (:959-1057): both operands dequantised per 32-block, fp32 accumulate, bf16 out.  Without bias, MXTensor grad_output
+    or torch.compile of the Function.
 CDNA4's scaled MFMA takes the E8M0 bytes as register operands, so scales stay in plain [rows, K/32]
 layout: no 128x4 "blocked" swizzle and no per-group row padding are needed on this path
 (torchao::mx_block_rearrange_2d_M_groups / fused_pad_token_groups have no work to do on this path; both exist as ops for callers that hold
@@ -116,8 +118,10 @@ def _to_mxfp8_then_scaled_grouped_mm(
     out_dtype: Optional[torch.dtype] = torch.bfloat16,
     scale_calculation_mode: ScaleCalculationMode = ScaleCalculationMode.RCEIL,
     cache_weights: bool = False,
+    wgrad_with_hp: bool = False,
+    pad_token_groups_for_grouped_mm: bool = False,
 ) -> torch.Tensor:
-    """Forward of the reference's MXFP8 MoE grouped GEMM.
+    """The reference's MXFP8 MoE grouped GEMM; differentiable in a bf16 A and B_t (_MXFP8GroupedMM).
 
     A     bf16 [M_total, K]   tokens, grouped by expert
     B_t   bf16 [E, K, N]      expert weights, "transposed" view of [E, N, K] (strides (N*K, 1, N))
@@ -125,6 +129,10 @@ def _to_mxfp8_then_scaled_grouped_mm(
     ->    bf16 [M_total, N]
     B_t may also be an MXFP8ExpertWeights (cast once, MXFP8ExpertWeights.from_hp(B_t)); `cache_weights=True` memoises that
     cast per weight tensor (keyed on its storage and version counter: an in-place update re-casts) -- inference only.
+    When grad is enabled and A or B_t requires it, the call goes through _MXFP8GroupedMM: `wgrad_with_hp` computes the weight gradient by
+    torch._grouped_mm on bf16 instead of MXFP8, `pad_token_groups_for_grouped_mm` pads every group to a multiple of 32 tokens around the
+    GEMMs (the reference's names and defaults, :121-131) and lifts M_total % 32 == 0.  Calls without grad ignore both keywords and take
+    the path they always took.  MXFP8Tokens inputs are not differentiable.
     Raises like the reference for unsupported arguments (:167-200)."""
     from .ep import MXFP8Tokens
     if isinstance(A, MXFP8Tokens):
@@ -134,6 +142,11 @@ def _to_mxfp8_then_scaled_grouped_mm(
             _cached_expert_weights(B_t, scale_calculation_mode) if cache_weights else MXFP8ExpertWeights.from_hp(B_t, scale_calculation_mode))
         return ops.mxfp8_grouped_mm(A.data, A.scale, w.data, w.scale, offs.to(torch.int32))
     assert A.ndim == 2, "A must be 2D"
+    trains = torch.is_grad_enabled() and (A.requires_grad or (isinstance(B_t, torch.Tensor) and B_t.requires_grad))
+    if trains:
+        # a frozen cast has its blocks along K only: the dgrad needs the weights cast along N
+        assert not isinstance(B_t, MXFP8ExpertWeights), "MXFP8ExpertWeights is a frozen cast (no blocks along N): pass the bf16 B_t to train"
+        assert not cache_weights, "cache_weights=True memoises a frozen cast (no blocks along N): pass cache_weights=False to train"
     if isinstance(B_t, MXFP8ExpertWeights):
         assert block_size == BLOCK, "Only block_size=32 is supported"
         assert offs is not None, "offs must be provided for 2d-2d and 2d-3d grouped mm"
@@ -145,6 +158,12 @@ def _to_mxfp8_then_scaled_grouped_mm(
     assert out_dtype == torch.bfloat16, "Only bfloat16 out_dtype is supported"
     assert A.dtype == torch.bfloat16 and B_t.dtype == torch.bfloat16, "A and B_t must be bfloat16"
     assert A.shape[-1] == B_t.shape[-2], f"shape {A.shape} and {B_t.shape} are not compatible for _scaled_grouped_mm"
+    if trains:
+        k, n = B_t.shape[-2:]
+        assert n % 128 == 0 and k % 128 == 0, f"training needs N and K to be multiples of 128 (each is a contraction dimension once), got N={n} K={k}"
+        assert pad_token_groups_for_grouped_mm or A.shape[0] % BLOCK == 0, (
+            f"M_total={A.shape[0]} must be a multiple of 32 (the wgrad's scales cover 32 tokens): pass pad_token_groups_for_grouped_mm=True")
+        return _MXFP8GroupedMM.apply(A, B_t, offs, wgrad_with_hp, scale_calculation_mode, pad_token_groups_for_grouped_mm)
     # weights: 1x32 blocks along K of the [E, N, K] tensor (the reference quantises B_t.transpose(-2, -1))
     w = _cached_expert_weights(B_t, scale_calculation_mode) if cache_weights else MXFP8ExpertWeights.from_hp(B_t, scale_calculation_mode)
     return _cast_then_grouped_mm(A, w, offs, scale_calculation_mode)
@@ -180,6 +199,60 @@ def _cast_then_grouped_mm(A, w, offs, scale_calculation_mode):
         return ops.mxfp8_grouped_mm_dyn(A, w.data, w.scale, offs, scale_calculation_mode)
     a_q, a_s = ops.mxfp8_quantize(A.contiguous(), scale_calculation_mode)
     return ops.mxfp8_grouped_mm(a_q, a_s, w.data, w.scale, offs)
+
+
+class _MXFP8GroupedMM(torch.autograd.Function):
+    """Mirror of the reference's _MXFP8GroupedMM (mxfp8_grouped_mm.py:113-316): the forward of _to_mxfp8_then_scaled_grouped_mm, and
+      grad_A   [M, K]    = grad_out [M, N] x W [E, N, K]: the forward GEMM contracting over N (:597-709)
+      grad_B_t [E, K, N] = the (E, K, N) view of grad_W[e] = grad_out[rows of e]^T x A[rows of e] (:712-861)
+    with every operand cast to MXFP8 along the dimension its GEMM contracts."""
+
+    @staticmethod
+    def forward(ctx, A, B_t, offs, wgrad_with_hp, scale_calculation_mode, pad_token_groups_for_grouped_mm):
+        offs = offs.to(torch.int32)
+        num_tokens = A.shape[0]
+        if pad_token_groups_for_grouped_mm:
+            A_pad, pad_starts, pad_ends = pad_token_groups(A, offs, BLOCK)
+        else:
+            A_pad, pad_starts, pad_ends = A, None, offs
+        out = _cast_then_grouped_mm(A_pad, MXFP8ExpertWeights.from_hp(B_t, scale_calculation_mode), pad_ends, scale_calculation_mode)
+        if pad_token_groups_for_grouped_mm:
+            out = unpad_token_groups(out, offs, pad_starts, num_tokens, BLOCK)
+        ctx.save_for_backward(A_pad, B_t, offs, pad_starts, pad_ends)
+        ctx.wgrad_with_hp = wgrad_with_hp
+        ctx.scale_calculation_mode = scale_calculation_mode
+        ctx.pad = pad_token_groups_for_grouped_mm
+        ctx.num_tokens = num_tokens
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        A, B_t, offs, pad_starts, pad_ends = ctx.saved_tensors
+        mode = ctx.scale_calculation_mode
+        assert grad_out.dtype == torch.bfloat16, f"grad_output must be bfloat16, got {grad_out.dtype}"
+        grad_out = grad_out.contiguous()
+        if ctx.pad:
+            grad_out, _, _ = pad_token_groups(grad_out, offs, BLOCK)
+        grad_A = grad_B_t = None
+        if ctx.needs_input_grad[0]:
+            g_q, g_s = ops.mxfp8_quantize(grad_out, mode)
+            if B_t.is_contiguous():  # [E][K][N] as stored: its rows already run along N
+                w_q, w_s = ops.mxfp8_quantize(B_t, mode)
+            else:  # the usual view of an [E, N, K] weight: 32 x 1 blocks along N, codes written transposed
+                w_q, w_s = ops.mxfp8_quantize_3d(B_t.transpose(-2, -1).contiguous(), scaling_mode=mode)
+                w_q = w_q.transpose(-2, -1)  # the contiguous [E][K][N] codes behind the reference's column-major view
+            grad_A = ops.mxfp8_grouped_mm(g_q, g_s, w_q, w_s, pad_ends)  # rows past offs[-1] are zero
+            if ctx.pad:
+                grad_A = unpad_token_groups(grad_A, offs, pad_starts, ctx.num_tokens, BLOCK)
+        if ctx.needs_input_grad[1]:
+            if ctx.wgrad_with_hp:
+                grad_W = torch._grouped_mm(grad_out.transpose(-2, -1), A, offs=pad_ends, out_dtype=torch.bfloat16)
+            else:
+                g_t, g_ts = ops.mxfp8_quantize_colwise(grad_out, mode)
+                x_t, x_ts = ops.mxfp8_quantize_colwise(A.contiguous(), mode)
+                grad_W = ops.mxfp8_grouped_mm_wgrad(g_t, g_ts, x_t, x_ts, pad_ends, grad_out.shape[1], A.shape[1])
+            grad_B_t = grad_W.transpose(-2, -1)
+        return grad_A, grad_B_t, None, None, None, None
 
 
 def pad_token_groups(input_act: torch.Tensor, group_end_offsets: torch.Tensor, alignment_size: int = 32):

@@ -355,6 +355,18 @@ int ao_mxfp8_grouped_mm_pair(const uint8_t* a, const uint8_t* a_scale, const uin
                              const uint8_t* b3_scale, const int32_t* offs, uint16_t* out1, uint16_t* out3, int64_t M_total, int64_t N,
                              int64_t K, int64_t E, void* stream);
 
+/* The weight gradient of _to_mxfp8_then_scaled_grouped_mm: replaces the 2d-2d aten::_scaled_grouped_mm of _compute_wgrad
+ * (torchao/prototype/moe_training/mxfp8_grouped_mm.py:712-796), with the numerics of _emulated_mxfp8_scaled_grouped_mm_2d_2d (:1026-1057):
+ *   out[e][n][k] = bf16( sum_{m in [offs[e-1], offs[e])} dq(g)[m][n] dq(x)[m][k] ),  fp32 accumulation, one rounding.
+ * The operands are byte for byte what ao_mxfp8_quantize_colwise writes for grad_out [M_total][N] and x [M_total][K] (no relayout, no 128 x 4
+ * swizzle); the 32-token blocks lie on the global grid.  Any offsets: a block that straddles a group boundary lends its scale to both groups
+ * and each sums its own tokens.  An empty group's [N][K] slab is zero, tokens past offs[E-1] contribute to nothing, M_total == 0 zeroes out.
+ * M_total % 32 == 0, N % 16 == 0, K % 16 == 0, E < 65536, N M_total and K M_total below 2^31; the codes 16-byte aligned. */
+int ao_mxfp8_grouped_mm_wgrad(const uint8_t* g_t, const uint8_t* g_scale,   /* e4m3 [N][M_total], e8m0 [M_total/32][N] */
+                              const uint8_t* x_t, const uint8_t* x_scale,   /* e4m3 [K][M_total], e8m0 [M_total/32][K] */
+                              const int32_t* offs, uint16_t* out,           /* int32 [E] cumulative ends; bf16 [E][N][K] */
+                              int64_t M_total, int64_t N, int64_t K, int64_t E, void* stream);
+
 /* Float8Tensor's aten::_grouped_mm with rowwise scales (float8_tensor.py:1085-1122 -> scaled_grouped_mm, RowWise recipes):
  *   out[offs[e-1]:offs[e]] = bf16( (a_rows @ b[e]^T)_f32 * scale_a[m] * scale_b[e][n] )
  *   a e4m3 [M_total][K]; scale_a fp32 [M_total]; b e4m3 [E][N][K]; scale_b fp32 [E][N]; offs int32 [E]; out bf16 [M_total][N].
