@@ -114,8 +114,8 @@ __device__ __forceinline__ uint16_t f32_to_bf16_bits(float f) {
   return __builtin_bit_cast(uint16_t, b);
 }
 
-// max over the 64 lanes without LDS traffic: DPP within rows of 16, then the four row results through SGPRs
-__device__ __forceinline__ float wave_max(float m) {
+// max over the 16 lanes of a DPP row, in every one of them
+__device__ __forceinline__ float row16_max(float m) {
   auto dpp = [](float v, auto ctrl) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), decltype(ctrl)::value, 0xF, 0xF, true));
   };
@@ -123,6 +123,12 @@ __device__ __forceinline__ float wave_max(float m) {
   m = fmaxf(m, dpp(m, std::integral_constant<int, 0x4E>{}));   // quad_perm [2,3,0,1]
   m = fmaxf(m, dpp(m, std::integral_constant<int, 0x141>{}));  // row_half_mirror
   m = fmaxf(m, dpp(m, std::integral_constant<int, 0x140>{}));  // row_mirror
+  return m;
+}
+
+// max over the 64 lanes without LDS traffic: DPP within rows of 16, then the four row results through SGPRs
+__device__ __forceinline__ float wave_max(float m) {
+  m = row16_max(m);
   const float a = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, m), 0));
   const float b = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, m), 16));
   const float c = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, m), 32));

@@ -27,7 +27,7 @@ struct WgradArgs {
   const uint8_t* g_scale;  // e8m0 [M/32][N]
   const uint8_t* x;        // e4m3 [K][M]
   const uint8_t* x_scale;  // e8m0 [M/32][K]
-  const int32_t* offs;     // [E] cumulative ends
+  const int32_t* offs;     // [E] cumulative ends; null: one group [0, M)
   uint16_t* out;           // bf16 [E][N][K]
   int M, N, K;
 };
@@ -86,8 +86,9 @@ __global__ __launch_bounds__(256) void mx_wgrad_kernel(WgradArgs p) {
   const int wn = (wave >> 1) * 64, wk = (wave & 1) * 64;
   const int mb = p.M >> 5;
   // the group's tokens, clamped to the matrix; a range that runs backwards is an empty group
-  const int start = min(max(e > 0 ? p.offs[e - 1] : 0, 0), p.M);
-  const int end = min(max(p.offs[e], 0), p.M);
+  // (no offs: one group of every token, the dense linear's weight gradient)
+  const int start = p.offs != nullptr ? min(max(e > 0 ? p.offs[e - 1] : 0, 0), p.M) : 0;
+  const int end = p.offs != nullptr ? min(max(p.offs[e], 0), p.M) : p.M;
   const int s0 = start >> 7, s1 = end > start ? (end + 127) >> 7 : s0;
   // rows past the matrix fall outside the buffer's range and read as zero
   const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc((void*)p.g, 0, p.N * p.M, 0x00020000);
@@ -170,34 +171,57 @@ bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 using namespace ao;
 
-extern "C" int ao_mxfp8_grouped_mm_wgrad(const uint8_t* g_t, const uint8_t* g_scale, const uint8_t* x_t, const uint8_t* x_scale,
-                                         const int32_t* offs, uint16_t* out, int64_t M_total, int64_t N, int64_t K, int64_t E, void* stream) {
-  AO_REQUIRE(M_total >= 0 && N > 0 && K > 0 && E > 0, "%s: bad shape M_total=%lld N=%lld K=%lld E=%lld", __func__, (long long)M_total,
+namespace {
+// (AO_REQUIRE_PTR names the enclosing function: here the entry's name is `fn`)
+#define WGRAD_REQUIRE_PTR(p)                                    \
+  do {                                                          \
+    if ((p) == nullptr) {                                       \
+      ::ao::set_error("%s: null pointer argument '%s'", fn, #p); \
+      return AO_ERR_NULL_POINTER;                               \
+    }                                                           \
+  } while (0)
+
+// dense: one group [0, M_total) and no offs tensor (E == 1)
+int wgrad(const char* fn, const uint8_t* g_t, const uint8_t* g_scale, const uint8_t* x_t, const uint8_t* x_scale, const int32_t* offs, uint16_t* out,
+          int64_t M_total, int64_t N, int64_t K, int64_t E, bool dense, void* stream) {
+  AO_REQUIRE(M_total >= 0 && N > 0 && K > 0 && E > 0, "%s: bad shape M_total=%lld N=%lld K=%lld E=%lld", fn, (long long)M_total,
              (long long)N, (long long)K, (long long)E);
-  AO_REQUIRE(M_total % 32 == 0, "%s: M_total=%lld must be a multiple of 32 (one scale per 32 tokens)", __func__, (long long)M_total);
-  AO_REQUIRE(N % 16 == 0, "%s: N=%lld must be a multiple of 16", __func__, (long long)N);
-  AO_REQUIRE(K % 16 == 0, "%s: K=%lld must be a multiple of 16", __func__, (long long)K);
-  AO_REQUIRE(E < 65536, "%s: E=%lld must be below 65536 (the grid's z extent)", __func__, (long long)E);
+  AO_REQUIRE(M_total % 32 == 0, "%s: M_total=%lld must be a multiple of 32 (one scale per 32 tokens)", fn, (long long)M_total);
+  AO_REQUIRE(N % 16 == 0, "%s: N=%lld must be a multiple of 16", fn, (long long)N);
+  AO_REQUIRE(K % 16 == 0, "%s: K=%lld must be a multiple of 16", fn, (long long)K);
+  AO_REQUIRE(E < 65536, "%s: E=%lld must be below 65536 (the grid's z extent)", fn, (long long)E);
   AO_REQUIRE(M_total < (1ll << 31) && N < (1ll << 31) && K < (1ll << 31) && N * M_total < (1ll << 31) && K * M_total < (1ll << 31),
-             "%s: M_total=%lld N=%lld K=%lld: the sizes and both operands' byte counts must be below 2^31", __func__, (long long)M_total,
+             "%s: M_total=%lld N=%lld K=%lld: the sizes and both operands' byte counts must be below 2^31", fn, (long long)M_total,
              (long long)N, (long long)K);
-  AO_REQUIRE_PTR(out);
+  WGRAD_REQUIRE_PTR(out);
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (M_total == 0) {
     const hipError_t rc = hipMemsetAsync(out, 0, (size_t)E * N * K * sizeof(uint16_t), st);
-    if (rc != hipSuccess) return hip_failed(rc, "hipMemsetAsync(ao_mxfp8_grouped_mm_wgrad)");
+    if (rc != hipSuccess) return hip_failed(rc, "hipMemsetAsync(mx_wgrad)");
     return AO_OK;
   }
-  AO_REQUIRE_PTR(g_t);
-  AO_REQUIRE_PTR(g_scale);
-  AO_REQUIRE_PTR(x_t);
-  AO_REQUIRE_PTR(x_scale);
-  AO_REQUIRE_PTR(offs);
-  AO_REQUIRE(aligned16(g_t) && aligned16(x_t), "%s: the codes must be 16-byte aligned", __func__);
+  WGRAD_REQUIRE_PTR(g_t);
+  WGRAD_REQUIRE_PTR(g_scale);
+  WGRAD_REQUIRE_PTR(x_t);
+  WGRAD_REQUIRE_PTR(x_scale);
+  if (!dense) WGRAD_REQUIRE_PTR(offs);
+  AO_REQUIRE(aligned16(g_t) && aligned16(x_t), "%s: the codes must be 16-byte aligned", fn);
   constexpr size_t smem = 2 * kStage;
   if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(mx_wgrad_kernel), smem, "hipFuncSetAttribute(mx_wgrad_kernel)")) return rc;
-  const WgradArgs args{g_t, g_scale, x_t, x_scale, offs, out, (int)M_total, (int)N, (int)K};
+  const WgradArgs args{g_t, g_scale, x_t, x_scale, dense ? nullptr : offs, out, (int)M_total, (int)N, (int)K};
   ao::launch(mx_wgrad_kernel, dim3((unsigned)((K + 127) / 128), (unsigned)((N + 127) / 128), (unsigned)E), dim3(256), smem, st, args);
   AO_LAUNCH_CHECK("mx_wgrad_kernel launch");
   return AO_OK;
+}
+#undef WGRAD_REQUIRE_PTR
+}  // namespace
+
+extern "C" int ao_mxfp8_grouped_mm_wgrad(const uint8_t* g_t, const uint8_t* g_scale, const uint8_t* x_t, const uint8_t* x_scale,
+                                         const int32_t* offs, uint16_t* out, int64_t M_total, int64_t N, int64_t K, int64_t E, void* stream) {
+  return wgrad(__func__, g_t, g_scale, x_t, x_scale, offs, out, M_total, N, K, E, false, stream);
+}
+
+extern "C" int ao_mxfp8_mm_wgrad(const uint8_t* g_t, const uint8_t* g_scale, const uint8_t* x_t, const uint8_t* x_scale, uint16_t* out, int64_t M,
+                                 int64_t N, int64_t K, void* stream) {
+  return wgrad(__func__, g_t, g_scale, x_t, x_scale, nullptr, out, M, N, K, 1, true, stream);
 }

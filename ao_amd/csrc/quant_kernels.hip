@@ -269,10 +269,17 @@ __global__ __launch_bounds__(kThreads) void mxfp8_quant_kernel(const uint16_t* _
 // (column stride 132 B: 2-way conflicts) so that every column leaves as one 128-byte run of the transposed output.
 constexpr int kColTile = 128;
 constexpr int kColLdsStride = 132;
-template <int MODE>
+// ROWS: the rowwise (1 x 32) cast of the same tile from the same registers, so that x is read once for both directions
+// (mxfp8_quantize.cuh:460-820 with rowwise and colwise both set).  A 1 x 32 block of a row is the two columns of the 16 lanes of one DPP
+// row: mx_cast2 (quant_math.h) reduces the amax across them without LDS.  The row codes (two bytes a lane) and the row scales go through
+// LDS as well, rows of 128 bytes, and leave as 16-byte pieces of q_row and as the tile's 4 scale bytes of a row.
+template <int MODE, bool ROWS>
 __global__ __launch_bounds__(kThreads) void mxfp8_quant_colwise_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ qt,
-                                                                       uint8_t* __restrict__ scale, int64_t R, int64_t C) {
+                                                                       uint8_t* __restrict__ scale, uint8_t* __restrict__ q_row,
+                                                                       uint8_t* __restrict__ s_row, int64_t R, int64_t C) {
   __shared__ __attribute__((aligned(16))) uint8_t tile[kColTile * kColLdsStride];
+  __shared__ __attribute__((aligned(16))) uint8_t rtile[ROWS ? kColTile * kColTile : 16];
+  __shared__ __attribute__((aligned(16))) uint8_t rscale[ROWS ? kColTile * 4 : 16];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   // blockIdx.z: the matrix of a batch (expert) -- each [R][C] matrix is cast on its own, outputs laid out per matrix
   x += (int64_t)blockIdx.z * R * C;
@@ -309,6 +316,16 @@ __global__ __launch_bounds__(kThreads) void mxfp8_quant_colwise_kernel(const uin
       t1[i] = cvt4_e4m3(b[0], b[1], b[2], b[3]);
     }
     *reinterpret_cast<uint16_t*>(scale + (rb >> 5) * C + c) = (uint16_t)(e0 | (e1 << 8));
+    if (ROWS) {
+      // C % 32 == 0: the 16 lanes of a DPP row are inside the matrix together
+#pragma unroll
+      for (int r = 0; r < 32; ++r) {
+        uint32_t e;
+        const uint32_t codes = mx_cast2<MODE>(v[r], e);
+        *reinterpret_cast<uint16_t*>(rtile + (wave * 32 + r) * kColTile + 2 * lane) = (uint16_t)codes;
+        if ((lane & 15) == 0) rscale[(wave * 32 + r) * 4 + (lane >> 4)] = (uint8_t)e;
+      }
+    }
   }
   __syncthreads();
   // 128 columns x 8 pieces of 16 bytes (= 16 rows each)
@@ -318,6 +335,24 @@ __global__ __launch_bounds__(kThreads) void mxfp8_quant_colwise_kernel(const uin
     if (gc < C && gr < R) {
       const uint32_t* src = reinterpret_cast<const uint32_t*>(tile + col * kColLdsStride + part * 16);
       *reinterpret_cast<u32x4*>(qt + gc * R + gr) = u32x4{src[0], src[1], src[2], src[3]};
+    }
+  }
+  if (ROWS) {
+    // 128 rows x 8 pieces of 16 bytes (= 16 columns each); R % 32 == 0 and C % 32 == 0: a piece inside the matrix was written whole
+    for (int p = threadIdx.x; p < kColTile * 8; p += kThreads) {
+      const int row = p >> 3, part = p & 7;
+      const int64_t gr = r0 + row, gc = c0 + part * 16;
+      if (gr < R && gc < C) *reinterpret_cast<u32x4*>(q_row + gr * C + gc) = *reinterpret_cast<const u32x4*>(rtile + row * kColTile + part * 16);
+    }
+    // the tile's scale bytes of a row: one dword where every tile is whole along C (then it is aligned), single bytes otherwise
+    if (threadIdx.x < kColTile && r0 + threadIdx.x < R) {
+      uint8_t* dst = s_row + (r0 + threadIdx.x) * (C >> 5) + (c0 >> 5);
+      if ((C & (kColTile - 1)) == 0) {
+        *reinterpret_cast<uint32_t*>(dst) = *reinterpret_cast<const uint32_t*>(rscale + threadIdx.x * 4);
+      } else {
+        const int nb = (int)((C - c0 < kColTile ? C - c0 : (int64_t)kColTile) >> 5);
+        for (int j = 0; j < nb; ++j) dst[j] = rscale[threadIdx.x * 4 + j];
+      }
     }
   }
 }
@@ -361,8 +396,9 @@ extern "C" int ao_fp8_quantize_rowwise(const uint16_t* x, uint8_t* q, float* sca
 }
 
 namespace {
+// q_row / s_row: the rowwise outputs of the one-pass cast (ao_mxfp8_quantize_rowcol), null for the colwise casts
 int mxfp8_colwise(const char* fn, const uint16_t* x, uint8_t* q_t, uint8_t* scale_e8m0, int64_t E, int64_t R, int64_t C, int scaling_mode,
-                  void* stream) {
+                  void* stream, bool rows = false, uint8_t* q_row = nullptr, uint8_t* s_row = nullptr) {
   if (int rc = check_rows(fn, R, C, 32)) return rc;
   AO_REQUIRE(R % 32 == 0, "%s: R=%lld must be a multiple of 32", fn, (long long)R);
   AO_REQUIRE(E >= 0 && E <= 65535, "%s: E=%lld must be in [0, 65535]", fn, (long long)E);
@@ -372,18 +408,33 @@ int mxfp8_colwise(const char* fn, const uint16_t* x, uint8_t* q_t, uint8_t* scal
   AO_REQUIRE_PTR(x);
   AO_REQUIRE_PTR(q_t);
   AO_REQUIRE_PTR(scale_e8m0);
+  if (rows) {
+    AO_REQUIRE_PTR(q_row);
+    AO_REQUIRE_PTR(s_row);
+  }
   const int64_t gx = (C + kColTile - 1) / kColTile, gy = (R + kColTile - 1) / kColTile;
   AO_REQUIRE(gy <= 65535, "%s: R=%lld too large for one launch", fn, (long long)R);
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)gx, (unsigned)gy, (unsigned)E);
-  if (scaling_mode == AO_MX_SCALE_RCEIL)
-    ao::launch(mxfp8_quant_colwise_kernel<AO_MX_SCALE_RCEIL>, grid, dim3(kThreads), 0, s, x, q_t, scale_e8m0, R, C);
-  else
-    ao::launch(mxfp8_quant_colwise_kernel<AO_MX_SCALE_FLOOR>, grid, dim3(kThreads), 0, s, x, q_t, scale_e8m0, R, C);
+  if (rows) {
+    if (scaling_mode == AO_MX_SCALE_RCEIL)
+      ao::launch(mxfp8_quant_colwise_kernel<AO_MX_SCALE_RCEIL, true>, grid, dim3(kThreads), 0, s, x, q_t, scale_e8m0, q_row, s_row, R, C);
+    else
+      ao::launch(mxfp8_quant_colwise_kernel<AO_MX_SCALE_FLOOR, true>, grid, dim3(kThreads), 0, s, x, q_t, scale_e8m0, q_row, s_row, R, C);
+  } else if (scaling_mode == AO_MX_SCALE_RCEIL) {
+    ao::launch(mxfp8_quant_colwise_kernel<AO_MX_SCALE_RCEIL, false>, grid, dim3(kThreads), 0, s, x, q_t, scale_e8m0, q_row, s_row, R, C);
+  } else {
+    ao::launch(mxfp8_quant_colwise_kernel<AO_MX_SCALE_FLOOR, false>, grid, dim3(kThreads), 0, s, x, q_t, scale_e8m0, q_row, s_row, R, C);
+  }
   AO_LAUNCH_CHECK("mxfp8_quant_colwise_kernel launch");
   return AO_OK;
 }
 }  // namespace
+
+extern "C" int ao_mxfp8_quantize_rowcol(const uint16_t* x, uint8_t* q_row, uint8_t* s_row, uint8_t* q_col_t, uint8_t* s_col, int64_t R, int64_t C,
+                                        int scaling_mode, void* stream) {
+  return mxfp8_colwise(__func__, x, q_col_t, s_col, 1, R, C, scaling_mode, stream, true, q_row, s_row);
+}
 
 extern "C" int ao_mxfp8_quantize_colwise(const uint16_t* x, uint8_t* q_t, uint8_t* scale_e8m0, int64_t R, int64_t C, int scaling_mode,
                                          void* stream) {

@@ -62,6 +62,8 @@ __device__ __forceinline__ uint32_t cvt4_e4m3(float a, float b, float c, float d
   r = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, r, true);
   return r;
 }
+// two values: the codes in the low 16 bits
+__device__ __forceinline__ uint32_t cvt2_e4m3(float a, float b) { return __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0u, false) & 0xffffu; }
 __device__ __forceinline__ float clamp448(float v) {
   // torch.clamp propagates NaN; fminf/fmaxf would not
   return (v != v) ? v : fminf(fmaxf(v, -448.f), 448.f);
@@ -217,6 +219,23 @@ __device__ __forceinline__ u32x2 mx_cast8(const u32x4& v, uint32_t& e) {
   nanbits |= __shfl_xor(nanbits, 2);
   e = mx_block_exponent<MODE>(m, (nanbits == 0u) && (m < INFINITY));
   return mx_encode8<MODE>(v, e);
+}
+// The same cast of one block by the SIXTEEN LANES OF A DPP ROW, two adjacent bf16 each (the register layout of the colwise kernel, whose
+// lanes hold two columns): the block amax across the row (common.h: row16_max), the exponent (in e, the same in all sixteen), this lane's two
+// codes in the low 16 bits.  A NaN rides the reduction as +inf: either makes the block non-finite, the only thing mx_cast8 asks of them.
+template <int MODE>
+__device__ __forceinline__ uint32_t mx_cast2(uint32_t v, uint32_t& e) {
+  const float lo = bf16_lo_to_f32(v), hi = bf16_hi_to_f32(v);
+  const float a = fabsf(lo), b = fabsf(hi);
+  const float m = row16_max(((a != a) | (b != b)) ? INFINITY : fmaxf(a, b));
+  e = mx_block_exponent<MODE>(m, m < INFINITY);
+  const float r = mx_reciprocal(e);
+  float f0 = lo * r, f1 = hi * r;
+  if (MODE == 0) {  // eager saturation, as in mx_encode8
+    f0 = clamp448(f0);
+    f1 = clamp448(f1);
+  }
+  return cvt2_e4m3(f0, f1);
 }
 
 // ---- MXFP4 (to_mx(x, float4_e2m1fn_x2, 32, mode)) ---------------------------------------------------------------------------------

@@ -94,16 +94,20 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> mxfp8_quantize(const Tensor& input, b
   if (rowwise) {
     out_r = empty_strided_like(input, {rows, cols}, {cols, 1}, f8);
     sc_r = empty_strided_like(input, {rows, cols / 32}, {cols / 32, 1}, e8);
-    AO_RC(ao_mxfp8_quantize_rowwise(x, reinterpret_cast<uint8_t*>(out_r.data_ptr()), reinterpret_cast<uint8_t*>(sc_r.data_ptr()), rows, cols, mode,
-                                    current_stream(input)), op);
   }
   if (colwise) {
     // column-major data {rows, cols} with strides {1, rows}; scales {cols, rows / 32} with strides {1, cols} (mxfp8_extension.cpp:147-158):
     // the kernel writes [cols][rows] and [rows / 32][cols] row-major, which is that memory
     out_c = empty_strided_like(input, {rows, cols}, {1, rows}, f8);
     sc_c = empty_strided_like(input, {cols, rows / 32}, {1, cols}, e8);
-    AO_RC(ao_mxfp8_quantize_colwise(x, reinterpret_cast<uint8_t*>(out_c.data_ptr()), reinterpret_cast<uint8_t*>(sc_c.data_ptr()), rows, cols, mode,
-                                    current_stream(input)), op);
+  }
+  auto bytes = [](Tensor& t) { return reinterpret_cast<uint8_t*>(t.data_ptr()); };
+  if (rowwise && colwise) {  // one launch, x read once: the bytes of the two below
+    AO_RC(ao_mxfp8_quantize_rowcol(x, bytes(out_r), bytes(sc_r), bytes(out_c), bytes(sc_c), rows, cols, mode, current_stream(input)), op);
+  } else if (rowwise) {
+    AO_RC(ao_mxfp8_quantize_rowwise(x, bytes(out_r), bytes(sc_r), rows, cols, mode, current_stream(input)), op);
+  } else {
+    AO_RC(ao_mxfp8_quantize_colwise(x, bytes(out_c), bytes(sc_c), rows, cols, mode, current_stream(input)), op);
   }
   return std::make_tuple(out_r, out_c, sc_r, sc_c);
 }

@@ -28,6 +28,7 @@ __all__ = [
     "mxfp8_quantize",
     "mxfp8_grouped_mm",
     "mxfp8_grouped_mm_wgrad",
+    "mxfp8_mm_wgrad",
     "dynamic_linear_fits",
     "dynamic_linear_preferred",
     "int8_dynamic_linear",
@@ -39,6 +40,7 @@ __all__ = [
     "int8_linear",
     "fp8_linear",
     "mxfp8_quantize_colwise",
+    "mxfp8_quantize_rowcol",
     "fp8_grouped_mm",
     "rowwise_amax",
     "int8_quantize_rowwise_amax",
@@ -718,6 +720,28 @@ def mxfp8_quantize_colwise(x: torch.Tensor, scaling_mode: str = "rceil"):
     return qt.view(torch.float8_e4m3fn).t(), st.view(torch.float8_e8m0fnu).t()
 
 
+def mxfp8_quantize_rowcol(x: torch.Tensor, scaling_mode: str = "rceil"):
+    """Both casts of torchao::mxfp8_quantize(rowwise=True, colwise=True) in ONE launch that reads x once: x bf16 [R, C] ->
+    (q, s, q_t_view, s_t_view) with (q, s) the bytes of mxfp8_quantize(x) and (q_t_view, s_t_view) the bytes and the strided views of
+    mxfp8_quantize_colwise(x) ({R, C} strides {1, R}; {C, R/32} strides {1, C})."""
+    dev = _require_gpu("mxfp8_quantize_rowcol", x)
+    if x.dtype != torch.bfloat16 or x.dim() != 2 or not x.is_contiguous():
+        raise RuntimeError("mxfp8_quantize_rowcol: expected a contiguous 2-D bfloat16 tensor")
+    mode = MX_SCALE_MODES.get(str(getattr(scaling_mode, "value", scaling_mode)).lower())
+    if mode is None:
+        raise RuntimeError(f"mxfp8_quantize_rowcol: unsupported scaling mode {scaling_mode!r} (floor | rceil)")
+    r, c = x.shape
+    if r % 32 != 0 or c % 32 != 0 or c == 0:
+        raise RuntimeError(f"mxfp8_quantize_rowcol: shape {tuple(x.shape)} must be multiples of 32 in both dimensions")
+    q = torch.empty((r, c), dtype=torch.uint8, device=dev)
+    s = torch.empty((r, c // 32), dtype=torch.uint8, device=dev)
+    qt = torch.empty((c, r), dtype=torch.uint8, device=dev)
+    st = torch.empty((r // 32, c), dtype=torch.uint8, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_mxfp8_quantize_rowcol(_ptr(x), _ptr(q), _ptr(s), _ptr(qt), _ptr(st), r, c, mode, _stream()))
+    return (q.view(torch.float8_e4m3fn), s.view(torch.float8_e8m0fnu), qt.view(torch.float8_e4m3fn).t(), st.view(torch.float8_e8m0fnu).t())
+
+
 def mxfp8_quantize_3d(x: torch.Tensor, block_size: int = 32, scale_block_dim1: int = 32, scale_block_dim2: int = 1,
                       scaling_mode: str = "rceil"):
     """mxfp8_quantize_cuda_3d with logical (un-blocked) scales (prototype/moe_training/kernels/mxfp8/quant.py:1413-1440): x bf16
@@ -805,6 +829,30 @@ def mxfp8_grouped_mm_wgrad(g_t, g_scale, x_t, x_scale, offs, N: int, K: int):
     with _on(dev):
         _lib.check(_lib.lib().ao_mxfp8_grouped_mm_wgrad(_ptr(g), _ptr(gs), _ptr(x), _ptr(xs), _ptr(offs.contiguous()), _ptr(out), m, n, k, e,
                                                         _stream()))
+    return out
+
+
+def mxfp8_mm_wgrad(g_t, g_scale, x_t, x_scale, N: int, K: int):
+    """The weight gradient of a dense MXFP8 linear (mxfp8_linear.py:208-255) on the colwise (32 x 1) casts of grad_out [M, N] and x [M, K],
+    in the layouts mxfp8_grouped_mm_wgrad takes -> bf16 [N, K] = dq(g)^T @ dq(x): the grouped kernel over one group of every token, no offs
+    tensor.  The bits of mxfp8_grouped_mm_wgrad(..., offs=[M])[0]; M = 0 gives zeros."""
+    name = "mxfp8_mm_wgrad"
+    dev = _require_gpu(name, g_t, g_scale, x_t, x_scale)
+    n, k = int(N), int(K)
+    if n <= 0 or k <= 0 or g_t.numel() % n != 0:
+        raise RuntimeError(f"{name}: g_t with {g_t.numel()} elements does not hold [N={n}, M] codes")
+    m = g_t.numel() // n
+    if m % 32 != 0:
+        raise RuntimeError(f"{name}: M={m} must be a multiple of 32 (one scale per 32 tokens)")
+    if g_scale.dtype not in (torch.uint8, torch.float8_e8m0fnu) or x_scale.dtype not in (torch.uint8, torch.float8_e8m0fnu):
+        raise RuntimeError(f"{name}: expected float8_e8m0fnu scales, got {g_scale.dtype} and {x_scale.dtype}")
+    g = _colwise_rows(name, "g_t", _fp8_bytes(name, g_t), n, m)
+    x = _colwise_rows(name, "x_t", _fp8_bytes(name, x_t), k, m)
+    gs = _colwise_rows(name, "g_scale", g_scale.view(torch.uint8), m // 32, n)
+    xs = _colwise_rows(name, "x_scale", x_scale.view(torch.uint8), m // 32, k)
+    out = torch.empty((n, k), dtype=torch.bfloat16, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_mxfp8_mm_wgrad(_ptr(g), _ptr(gs), _ptr(x), _ptr(xs), _ptr(out), m, n, k, _stream()))
     return out
 
 

@@ -7,7 +7,7 @@ Host-side mirror of
     _to_mxfp8_then_scaled_grouped_mm and its autograd Function _MXFP8GroupedMM: forward, dgrad (the forward GEMM on grad_out and the
     weights cast along N) and wgrad (ops.mxfp8_grouped_mm_wgrad on the 32 x 1 casts of grad_out and A), numerics of the reference's
     emulated paths (:959-1057): both operands dequantised per 32-block, fp32 accumulate, bf16 out.  Without bias, MXTensor grad_output
-    or torch.compile of the Function.
+    or torch.compile of the Function.  The dense linear's training path and quantize_ are in mx_training.py.
 CDNA4's scaled MFMA takes the E8M0 bytes as register operands, so scales stay in plain [rows, K/32]
 layout: no 128x4 "blocked" swizzle and no per-group row padding are needed on this path
 (torchao::mx_block_rearrange_2d_M_groups / fused_pad_token_groups have no work to do on this path; both exist as ops for callers that hold
@@ -201,6 +201,22 @@ def _cast_then_grouped_mm(A, w, offs, scale_calculation_mode):
     return ops.mxfp8_grouped_mm(a_q, a_s, w.data, w.scale, offs)
 
 
+ONE_PASS_CAST = None  # None: by size (below); True / False force the one-pass kernel / the two launches (A/B and tests)
+ONE_PASS_CAST_MIN_ELEMENTS = 1 << 26  # 128 MiB of bf16, half the last-level cache
+
+
+def mxfp8_cast_both(x: torch.Tensor, scale_calculation_mode):
+    """(q, s, q_t, s_t): the rowwise and the colwise MXFP8 cast of a contiguous bf16 [R, C] x, what ops.mxfp8_quantize and
+    ops.mxfp8_quantize_colwise return -- by the one-pass kernel (ops.mxfp8_quantize_rowcol: x is read once) or by those two launches.
+    The same bytes either way; which is taken is a matter of speed alone.  Measured: a tensor of up to 96 MiB stays in
+    the 256 MiB last-level cache between the two launches, so their second read costs little and they are level to 6 % ahead; at 192 MiB
+    and beyond the one-pass kernel is 1.17-1.28 x faster.  The seam sits at 128 MiB, unmeasured in between."""
+    one_pass = x.numel() >= ONE_PASS_CAST_MIN_ELEMENTS if ONE_PASS_CAST is None else ONE_PASS_CAST
+    if one_pass:
+        return ops.mxfp8_quantize_rowcol(x, scale_calculation_mode)
+    return (*ops.mxfp8_quantize(x, scale_calculation_mode), *ops.mxfp8_quantize_colwise(x, scale_calculation_mode))
+
+
 class _MXFP8GroupedMM(torch.autograd.Function):
     """Mirror of the reference's _MXFP8GroupedMM (mxfp8_grouped_mm.py:113-316): the forward of _to_mxfp8_then_scaled_grouped_mm, and
       grad_A   [M, K]    = grad_out [M, N] x W [E, N, K]: the forward GEMM contracting over N (:597-709)
@@ -234,8 +250,14 @@ class _MXFP8GroupedMM(torch.autograd.Function):
         if ctx.pad:
             grad_out, _, _ = pad_token_groups(grad_out, offs, BLOCK)
         grad_A = grad_B_t = None
-        if ctx.needs_input_grad[0]:
+        mx_wgrad = ctx.needs_input_grad[1] and not ctx.wgrad_with_hp
+        if ctx.needs_input_grad[0] and mx_wgrad:  # both directions of grad_out: one read of it (the same bytes as the two casts)
+            g_q, g_s, g_t, g_ts = mxfp8_cast_both(grad_out, mode)
+        elif ctx.needs_input_grad[0]:
             g_q, g_s = ops.mxfp8_quantize(grad_out, mode)
+        elif mx_wgrad:
+            g_t, g_ts = ops.mxfp8_quantize_colwise(grad_out, mode)
+        if ctx.needs_input_grad[0]:
             if B_t.is_contiguous():  # [E][K][N] as stored: its rows already run along N
                 w_q, w_s = ops.mxfp8_quantize(B_t, mode)
             else:  # the usual view of an [E, N, K] weight: 32 x 1 blocks along N, codes written transposed
@@ -248,7 +270,6 @@ class _MXFP8GroupedMM(torch.autograd.Function):
             if ctx.wgrad_with_hp:
                 grad_W = torch._grouped_mm(grad_out.transpose(-2, -1), A, offs=pad_ends, out_dtype=torch.bfloat16)
             else:
-                g_t, g_ts = ops.mxfp8_quantize_colwise(grad_out, mode)
                 x_t, x_ts = ops.mxfp8_quantize_colwise(A.contiguous(), mode)
                 grad_W = ops.mxfp8_grouped_mm_wgrad(g_t, g_ts, x_t, x_ts, pad_ends, grad_out.shape[1], A.shape[1])
             grad_B_t = grad_W.transpose(-2, -1)

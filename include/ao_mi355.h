@@ -309,6 +309,13 @@ int ao_mxfp8_quantize_rowwise(const uint16_t* x, uint8_t* q, uint8_t* scale_e8m0
 int ao_mxfp8_quantize_colwise(const uint16_t* x, uint8_t* q_t, uint8_t* scale_e8m0,
                               int64_t R, int64_t C, int scaling_mode, void* stream);
 
+/* torchao::mxfp8_quantize with rowwise AND colwise set, in one launch that reads x once (the reference's CUDA kernel does the same,
+ * mxfp8_quantize.cuh:460-820): q_row / s_row hold exactly the bytes of ao_mxfp8_quantize_rowwise, q_col_t / s_col exactly those of
+ * ao_mxfp8_quantize_colwise.  x bf16 [R][C], R % 32 == 0, C % 32 == 0; R == 0 launches nothing. */
+int ao_mxfp8_quantize_rowcol(const uint16_t* x, uint8_t* q_row, uint8_t* s_row,   /* e4m3 [R][C], e8m0 [R][C/32] */
+                             uint8_t* q_col_t, uint8_t* s_col,                    /* e4m3 [C][R], e8m0 [R/32][C] */
+                             int64_t R, int64_t C, int scaling_mode, void* stream);
+
 /* The 3-D (per-expert) form: mxfp8_quantize_cuda_3d with (scale_block_dim1, scale_block_dim2) = (32, 1), logical scales
  * (torchao/prototype/moe_training/kernels/mxfp8/quant.py:1413-1440; csrc/cuda/mx_kernels/mxfp8_quantize.cuh:822-1290) --
  * every [R][C] matrix of the batch cast on its own, "column-major-per-expert" data.
@@ -366,6 +373,13 @@ int ao_mxfp8_grouped_mm_wgrad(const uint8_t* g_t, const uint8_t* g_scale,   /* e
                               const uint8_t* x_t, const uint8_t* x_scale,   /* e4m3 [K][M_total], e8m0 [M_total/32][K] */
                               const int32_t* offs, uint16_t* out,           /* int32 [E] cumulative ends; bf16 [E][N][K] */
                               int64_t M_total, int64_t N, int64_t K, int64_t E, void* stream);
+
+/* The weight gradient of a dense MXFP8 linear (mx_mm.backward, torchao/prototype/moe_training/mxfp8_linear.py:208-255): the kernel above over
+ * ONE group that holds every token, without an offs tensor -- out[n][k] = bf16( sum_m dq(g)[m][n] dq(x)[m][k] ), the bits of
+ * ao_mxfp8_grouped_mm_wgrad with E = 1 and offs = [M].  The same operand layouts and checks; M == 0 zeroes out. */
+int ao_mxfp8_mm_wgrad(const uint8_t* g_t, const uint8_t* g_scale,   /* e4m3 [N][M], e8m0 [M/32][N] */
+                      const uint8_t* x_t, const uint8_t* x_scale,   /* e4m3 [K][M], e8m0 [M/32][K] */
+                      uint16_t* out, int64_t M, int64_t N, int64_t K, void* stream);   /* bf16 [N][K] */
 
 /* Float8Tensor's aten::_grouped_mm with rowwise scales (float8_tensor.py:1085-1122 -> scaled_grouped_mm, RowWise recipes):
  *   out[offs[e-1]:offs[e]] = bf16( (a_rows @ b[e]^T)_f32 * scale_a[m] * scale_b[e][n] )
