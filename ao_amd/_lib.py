@@ -59,6 +59,9 @@ _SIGNATURES = {
     "ao_int8_int_mm": [_P, _P, _P, _I64, _I64, _I64, _P],
     "ao_fp8_quantize_rowwise": [_P, _P, _P, _I64, _I64, _P],
     "ao_fp8_scaled_mm": [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _P],
+    "ao_fp8_train_amax": [_P, _P, _P, _I64, _I64, _P],
+    "ao_fp8_train_cast": [_P, _P, _I64, _P, _I64, _INT, _P, _P, _P, _P, _P, _P, _I64, _I64, _P],
+    "ao_fp8_train_quantize_rowwise": [_P, _P, _P, _P, _INT, _I64, _I64, _P],
     "ao_mxfp8_quantize_rowwise": [_P, _P, _P, _I64, _I64, _INT, _P],
     "ao_mxfp8_quantize_colwise": [_P, _P, _P, _I64, _I64, _INT, _P],
     "ao_mxfp8_quantize_rowcol": [_P, _P, _P, _P, _P, _I64, _I64, _INT, _P],

@@ -92,6 +92,26 @@ __device__ __forceinline__ u32x2 fp8_quant8(const u32x4& v, float s) {
   return u32x2{cvt4_e4m3(f[0], f[1], f[2], f[3]), cvt4_e4m3(f[4], f[5], f[6], f[7])};
 }
 
+// ---- float8 TRAINING cast (fp8_train_kernels.hip): torchao/float8, not the inference cast above -------------------------------------
+//   scale = f32(448 / max(f64(amax), 1e-12)): divided in float64 and rounded once to fp32 (float8_utils.py:31-53); with
+//   round_scales_to_power_of_2, exp2(floor(log2(scale))) (:244-246) -- the mantissa bits cleared: every scale this formula gives from a
+//   bf16 amax is a normal fp32 (448 / 3.4e38 = 1.3e-36 .. 448 / 1e-12 = 4.5e14).
+//   q = e4m3_rne(clamp(f32(x) * scale, -448, 448))  (float8_training_tensor.py:153-154, float8_utils.py:118-139).  The clamp is live:
+//   without the power-of-two rounding amax * scale can round above 448.
+//   The GEMM multiplies by 1 / scale, an IEEE fp32 division (float8_ops.py:44-45).
+__device__ __forceinline__ float fp8_train_scale(float amax, bool pow2) {
+  const float s = (float)(448.0 / fmax((double)amax, 1e-12));
+  return pow2 ? bits_to_f32(f32_to_bits(s) & 0xff800000u) : s;
+}
+__device__ __forceinline__ float fp8_train_q(float x, float s) { return clamp448(x * s); }
+// 8 bf16 of one row -> 8 e4m3 codes (two dwords) under the row's scale
+__device__ __forceinline__ u32x2 fp8_train_quant8(const u32x4& v, float s) {
+  return u32x2{cvt4_e4m3(fp8_train_q(bf16_lo_to_f32(v.x), s), fp8_train_q(bf16_hi_to_f32(v.x), s), fp8_train_q(bf16_lo_to_f32(v.y), s),
+                         fp8_train_q(bf16_hi_to_f32(v.y), s)),
+               cvt4_e4m3(fp8_train_q(bf16_lo_to_f32(v.z), s), fp8_train_q(bf16_hi_to_f32(v.z), s), fp8_train_q(bf16_lo_to_f32(v.w), s),
+                         fp8_train_q(bf16_hi_to_f32(v.w), s))};
+}
+
 // ---- rowwise output epilogue: the fp32 value the caller rounds to bf16 at its store -----------------------------------------------
 //   int8 : t = bf16(f32(c) * sx[m]);  y = bf16(f32(t) * sw[n] (+ bias))   (int8_tensor.py:315-359)
 //   fp8  : y = bf16(c * sa[m] * sb[n] (+ bias))                           (float8/inference.py:104-123)

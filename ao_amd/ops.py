@@ -48,6 +48,11 @@ __all__ = [
     "fp8_mm_f32",
     "int8_scale_epilogue",
     "fp8_scale_epilogue",
+    "fp8_train_amax",
+    "fp8_train_cast",
+    "fp8_train_quantize_rowwise",
+    "fp8_train_quantize_colwise_t",
+    "fp8_train_quantize_both",
 ]
 
 
@@ -521,6 +526,105 @@ def fp8_quantize_tensorwise(x: torch.Tensor):
     (qdata e4m3fn [M, K], scale fp32 [1, 1])."""
     q, s = fp8_quantize_rowwise_amax(x, _tensor_amax_rows(x))
     return q, s[:1].reshape(1, 1)
+
+
+# ---------------------------------------------------------------------------
+# float8 TRAINING casts (torchao.float8): scale = f32(448 / max(f64(amax), 1e-12)), q = e4m3(clamp(f32(x) * scale)), and the
+# reciprocal the GEMM takes.  Codes come back as float8_e4m3fn, scales as fp32 column vectors; the GEMM is fp8_scaled_mm.
+# ---------------------------------------------------------------------------
+def _fp8_train_rows(name, x, transposed=False):
+    x = _as_rows(name, x, torch.bfloat16)
+    r, c = x.shape
+    if c % 16 != 0:
+        raise ValueError(f"{name}: C={c} must be a multiple of 16")
+    if transposed and r % 16 != 0:
+        raise ValueError(f"{name}: R={r} must be a multiple of 16 for the transposed output (its rows are the GEMM's K)")
+    return x, r, c
+
+
+def _fp8_train_amax_arg(name, what, amax, n, dev):
+    """An amax for the cast: one per row / column (n entries, stride 1) or one for the tensor (a single entry, stride 0)."""
+    if amax.device != dev or amax.dtype != torch.float32:
+        raise RuntimeError(f"{name}: {what} must be a float32 tensor on {dev}, got {amax.dtype} on {amax.device}")
+    amax = amax.reshape(-1).contiguous()
+    if amax.numel() == 1:
+        return amax, 0
+    if amax.numel() != n:
+        raise RuntimeError(f"{name}: {what} must have {n} entries or one, got {amax.numel()}")
+    return amax, 1
+
+
+def fp8_train_amax(x: torch.Tensor, rows: bool = True, cols: bool = False):
+    """tensor_to_amax (torchao/float8/float8_utils.py:56-82) along either or both axes in one read of x: bf16 [R, C] ->
+    (row_amax fp32 [R] = max |x| over dim -1, or None; col_amax fp32 [C] = max |x| over dim 0, or None).  The whole tensor's amax is
+    `row_amax.amax()`."""
+    dev = _require_gpu("fp8_train_amax", x)
+    x, r, c = _fp8_train_rows("fp8_train_amax", x)
+    if not (rows or cols):
+        raise ValueError("fp8_train_amax: neither rows nor cols asked for")
+    alloc = torch.zeros if r == 0 or c == 0 else torch.empty  # (an empty matrix launches nothing: its maxima are 0)
+    ra = alloc((r,), dtype=torch.float32, device=dev) if rows else None
+    ca = alloc((c,), dtype=torch.float32, device=dev) if cols else None
+    with _on(dev):
+        _lib.check(_lib.lib().ao_fp8_train_amax(_ptr(x), _ptr(ra), _ptr(ca), r, c, _stream()))
+    return ra, ca
+
+
+def fp8_train_cast(x: torch.Tensor, row_amax: Optional[torch.Tensor] = None, col_amax: Optional[torch.Tensor] = None, pow2: bool = False):
+    """hp_tensor_and_scale_to_float8 on the scale of amax_to_scale (float8_training_tensor.py:130-188, float8_utils.py:31-53) for either
+    or both directions in one read of x.  x bf16 [R, C] -> (rows, cols):
+      rows = (q e4m3fn [R, C], scale fp32 [R, 1], inv_scale fp32 [R, 1]) from row_amax, None without it;
+      cols = (q_t e4m3fn [C, R], scale fp32 [C, 1], inv_scale fp32 [C, 1]) from col_amax, None without it: the cast along dim 0, stored
+             transposed.
+    An amax with ONE entry is the whole tensor's (TENSORWISE): the scale vectors are then filled with the one scale, which is the vector
+    fp8_scaled_mm takes (float8_ops.py:356-359).  pow2: round_scales_to_power_of_2."""
+    name = "fp8_train_cast"
+    dev = _require_gpu(name, x, row_amax, col_amax)
+    if row_amax is None and col_amax is None:
+        raise ValueError(f"{name}: neither row_amax nor col_amax given")
+    x, r, c = _fp8_train_rows(name, x, transposed=col_amax is not None)
+    f32 = dict(dtype=torch.float32, device=dev)
+    ra = rs = q = s = inv = ca = cs = qt = st = invt = None
+    if row_amax is not None:
+        ra, rs = _fp8_train_amax_arg(name, "row_amax", row_amax, r, dev)
+        q, s, inv = torch.empty((r, c), dtype=torch.uint8, device=dev), torch.empty((r, 1), **f32), torch.empty((r, 1), **f32)
+    if col_amax is not None:
+        ca, cs = _fp8_train_amax_arg(name, "col_amax", col_amax, c, dev)
+        qt, st, invt = torch.empty((c, r), dtype=torch.uint8, device=dev), torch.empty((c, 1), **f32), torch.empty((c, 1), **f32)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_fp8_train_cast(_ptr(x), _ptr(ra), rs or 0, _ptr(ca), cs or 0, int(bool(pow2)), _ptr(q), _ptr(s), _ptr(inv),
+                                                _ptr(qt), _ptr(st), _ptr(invt), r, c, _stream()))
+    return ((q.view(torch.float8_e4m3fn), s, inv) if q is not None else None,
+            (qt.view(torch.float8_e4m3fn), st, invt) if qt is not None else None)
+
+
+def fp8_train_quantize_rowwise(x: torch.Tensor, pow2: bool = False):
+    """hp_tensor_to_float8_dynamic(x, e4m3, AXISWISE, axiswise_dim=-1) (float8_scaling_utils.py:29-72) as ONE launch: bf16 [R, C] ->
+    (q e4m3fn [R, C], scale fp32 [R, 1], inv_scale fp32 [R, 1]); the bytes of fp8_train_amax + fp8_train_cast."""
+    dev = _require_gpu("fp8_train_quantize_rowwise", x)
+    x, r, c = _fp8_train_rows("fp8_train_quantize_rowwise", x)
+    q = torch.empty((r, c), dtype=torch.uint8, device=dev)
+    s = torch.empty((r, 1), dtype=torch.float32, device=dev)
+    inv = torch.empty((r, 1), dtype=torch.float32, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_fp8_train_quantize_rowwise(_ptr(x), _ptr(q), _ptr(s), _ptr(inv), int(bool(pow2)), r, c, _stream()))
+    return q.view(torch.float8_e4m3fn), s, inv
+
+
+def fp8_train_quantize_colwise_t(x: torch.Tensor, pow2: bool = False, amax: Optional[torch.Tensor] = None):
+    """hp_tensor_to_float8_dynamic(x, e4m3, AXISWISE, axiswise_dim=0), stored transposed: bf16 [R, C] -> (q_t e4m3fn [C, R], scale fp32
+    [C, 1], inv_scale fp32 [C, 1]) -- the K-contiguous operand of a GEMM that contracts x's dim 0.  Two launches: amax, then cast.
+    `amax` (one entry): the whole tensor's, for a TENSORWISE cast in this layout; the amax launch is then skipped."""
+    if amax is None:
+        amax = fp8_train_amax(x, rows=False, cols=True)[1]
+    return fp8_train_cast(x, None, amax, pow2)[1]
+
+
+def fp8_train_quantize_both(x: torch.Tensor, pow2: bool = False):
+    """Both axiswise casts of x in two passes over it (one amax launch, one cast launch): bf16 [R, C] ->
+    ((q, scale, inv_scale) of fp8_train_quantize_rowwise, (q_t, scale, inv_scale) of fp8_train_quantize_colwise_t), the same bytes."""
+    ra, ca = fp8_train_amax(x, rows=True, cols=True)
+    return fp8_train_cast(x, ra, ca, pow2)
 
 
 def int8_quantize_rowwise_asym(x: torch.Tensor):

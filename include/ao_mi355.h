@@ -268,6 +268,35 @@ int ao_fp8_scaled_mm(const uint8_t* a, const uint8_t* b, const float* scale_a,
                      const float* scale_b, const uint16_t* bias, uint16_t* y,
                      int64_t M, int64_t N, int64_t K, void* stream);
 
+/* ---- float8 TRAINING casts (torchao.float8: hp_tensor_to_float8_dynamic, float8_scaling_utils.py:29-72) --------------------------
+ * Not the arithmetic of ao_fp8_quantize_rowwise:
+ *   scale = f32(448 / max(f64(amax), 1e-12))                                  (float8_utils.py:31-53: a float64 division)
+ *   pow2 != 0: scale = exp2(floor(log2(scale))), the mantissa bits cleared     (float8_utils.py:244-246)
+ *   q = e4m3fn_rne(clamp(f32(x) * scale, -448, 448))                           (float8_training_tensor.py:153-154, float8_utils.py:118-139)
+ *   inv_scale = 1.0f / scale, what ao_fp8_scaled_mm multiplies by              (float8_ops.py:44-45)
+ * x bf16 [R][C], finite.  C % 16 == 0; R % 16 == 0 where a transposed output is asked for; R == 0 or C == 0 launches nothing.  No
+ * allocation, no synchronisation: capturable in a graph. */
+
+/* tensor_to_amax (float8_utils.py:56-82) along either or both axes in ONE read of x: row_amax fp32 [R] = max |x| over each row
+ * (axiswise_dim = -1), col_amax fp32 [C] = over each column (axiswise_dim = 0); either may be NULL.  The tiles' partial maxima merge by an
+ * atomic max into the outputs, which the call zeroes on `stream` first: the result does not depend on scheduling. */
+int ao_fp8_train_amax(const uint16_t* x, float* row_amax, float* col_amax, int64_t R, int64_t C, void* stream);
+
+/* hp_tensor_and_scale_to_float8 (float8_training_tensor.py:130-188) for either or both directions in ONE read of x:
+ *   q_row e4m3fn [R][C], s_row / inv_s_row fp32 [R]       from row_amax  (the cast with axiswise_dim = -1)
+ *   q_col_t e4m3fn [C][R], s_col / inv_s_col fp32 [C]     from col_amax  (the cast with axiswise_dim = 0, stored transposed: the
+ *                                                          K-contiguous operand ao_fp8_scaled_mm takes for dgrad and wgrad)
+ * q_row == NULL or q_col_t == NULL skips that direction.  An amax stride is 1, or 0 for ONE amax of the whole tensor (TENSORWISE
+ * granularity; the scale vectors are then filled with the one scale, float8_ops.py:356-359). */
+int ao_fp8_train_cast(const uint16_t* x, const float* row_amax, int64_t row_amax_stride, const float* col_amax,
+                      int64_t col_amax_stride, int pow2, uint8_t* q_row, float* s_row, float* inv_s_row,
+                      uint8_t* q_col_t, float* s_col, float* inv_s_col, int64_t R, int64_t C, void* stream);
+
+/* The row direction alone (tensor_to_scale + hp_tensor_and_scale_to_float8 with axiswise_dim = -1, float8_scaling_utils.py:56-72) as ONE
+ * launch: the bytes of ao_fp8_train_amax + ao_fp8_train_cast. */
+int ao_fp8_train_quantize_rowwise(const uint16_t* x, uint8_t* q, float* s, float* inv_s, int pow2, int64_t R, int64_t C,
+                                  void* stream);
+
 /* HQQ qparams + codes for the tinygemm format: Int4TilePackedTo4dTensor.from_hp(..., HQQ)
  * (int4_tile_packed_to_4d_tensor.py:149-168 -> quant_primitives.py:1891-1997, optimizer :1797-1866 in float16 as on a GPU).
  *   w bf16 [N][K] -> nibble_bytes uint8 [N][K/2] (even k in the HIGH nibble: the input of
