@@ -62,6 +62,9 @@ _SIGNATURES = {
     "ao_fp8_train_amax": [_P, _P, _P, _I64, _I64, _P],
     "ao_fp8_train_cast": [_P, _P, _I64, _P, _I64, _INT, _P, _P, _P, _P, _P, _P, _I64, _I64, _P],
     "ao_fp8_train_quantize_rowwise": [_P, _P, _P, _P, _INT, _I64, _I64, _P],
+    "ao_fp8_train_quantize_group_colwise_t": [_P, _P, _P, _P, _P, _INT, _I64, _I64, _I64, _P],
+    "ao_fp8_train_quantize_colwise_t_3d": [_P, _P, _P, _P, _INT, _I64, _I64, _I64, _P],
+    "ao_fp8_grouped_mm_wgrad": [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P],
     "ao_mxfp8_quantize_rowwise": [_P, _P, _P, _I64, _I64, _INT, _P],
     "ao_mxfp8_quantize_colwise": [_P, _P, _P, _I64, _I64, _INT, _P],
     "ao_mxfp8_quantize_rowcol": [_P, _P, _P, _P, _P, _I64, _I64, _INT, _P],

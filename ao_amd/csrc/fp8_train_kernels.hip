@@ -19,21 +19,12 @@
 // R % 16 == 0 (its 16-byte pieces, and the K of the GEMM that reads it).
 #include "common.h"
 #include "quant_math.h"
+#include "fp8_train_tile.h"
 
 namespace ao {
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kTile = 128;
-constexpr int kTileLds = 132;  // bytes between two columns of the staged transposed tile
-
-// local row of (step, wave, DPP row, k) and the lane's first column
-__device__ __forceinline__ int tile_row(int step, int wave, int g) { return step * 64 + wave * 16 + g * 4; }
-
-__device__ __forceinline__ void unpack8(const u32x4& v, float (&f)[8]) {
-  f[0] = bf16_lo_to_f32(v.x); f[1] = bf16_hi_to_f32(v.x); f[2] = bf16_lo_to_f32(v.y); f[3] = bf16_hi_to_f32(v.y);
-  f[4] = bf16_lo_to_f32(v.z); f[5] = bf16_hi_to_f32(v.z); f[6] = bf16_lo_to_f32(v.w); f[7] = bf16_hi_to_f32(v.w);
-}
+using namespace fp8_train_tile;  // kThreads, kTile, kTileLds, tile_row, unpack8
 
 // ---- amax: one read of x; partial maxima of a tile merge into the zeroed outputs by an unsigned atomic max (non-negative fp32 order
 // like their bit patterns), so the result does not depend on the order the tiles arrive in ------------------------------------------------

@@ -53,6 +53,9 @@ __all__ = [
     "fp8_train_quantize_rowwise",
     "fp8_train_quantize_colwise_t",
     "fp8_train_quantize_both",
+    "fp8_train_quantize_group_colwise_t",
+    "fp8_train_quantize_colwise_t_3d",
+    "fp8_grouped_mm_wgrad",
 ]
 
 
@@ -625,6 +628,85 @@ def fp8_train_quantize_both(x: torch.Tensor, pow2: bool = False):
     ((q, scale, inv_scale) of fp8_train_quantize_rowwise, (q_t, scale, inv_scale) of fp8_train_quantize_colwise_t), the same bytes."""
     ra, ca = fp8_train_amax(x, rows=True, cols=True)
     return fp8_train_cast(x, ra, ca, pow2)
+
+
+def _offs_arg(name, offs, dev):
+    if offs.dtype != torch.int32 or offs.dim() != 1 or offs.numel() < 1:
+        raise RuntimeError(f"{name}: offs must be int32 [E], got {offs.dtype} {tuple(offs.shape)}")
+    return offs.contiguous()
+
+
+def fp8_train_quantize_group_colwise_t(x: torch.Tensor, offs: torch.Tensor, pow2: bool = True):
+    """torch_to_float8_per_group_colwise (torchao/prototype/moe_training/utils.py:20-86; kernels/jagged_float8_scales.py:221-252), stored
+    transposed: x bf16 [R, C], offs int32 [E] (cumulative group ends along R, multiples of 16, non-decreasing, within [0, R]; not validated)
+    -> (q_t e4m3fn [C, R], scale fp32 [E, C], inv_scale fp32 [E, C]): one scale per column and token group, the amax over the group's rows.
+    An empty group gets the scale of a zero amax; rows at or past offs[-1] belong to no group and get code 0."""
+    name = "fp8_train_quantize_group_colwise_t"
+    dev = _require_gpu(name, x, offs)
+    x, r, c = _fp8_train_rows(name, x, transposed=True)
+    offs = _offs_arg(name, offs, dev)
+    e = offs.numel()
+    qt = torch.empty((c, r), dtype=torch.uint8, device=dev)
+    if r == 0 or c == 0:  # nothing is launched: every group is empty
+        s = torch.full((e, c), 448.0 / 1e-12, dtype=torch.float32, device=dev)
+        if pow2:
+            s = (s.view(torch.int32) & -0x800000).view(torch.float32)
+        return qt.view(torch.float8_e4m3fn), s, s.reciprocal()
+    s = torch.empty((e, c), dtype=torch.float32, device=dev)
+    inv = torch.empty((e, c), dtype=torch.float32, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_fp8_train_quantize_group_colwise_t(_ptr(x), _ptr(offs), _ptr(qt), _ptr(s), _ptr(inv), int(bool(pow2)), r, c, e,
+                                                                    _stream()))
+    return qt.view(torch.float8_e4m3fn), s, inv
+
+
+def fp8_train_quantize_colwise_t_3d(w: torch.Tensor, pow2: bool = True):
+    """torch_to_3d_rowwise_float8_transpose_rhs (torchao/prototype/moe_training/utils.py:156-189) of w.transpose(-2, -1): w bf16 [E, R, C]
+    -> (q_t e4m3fn [E, C, R], scale fp32 [E, C], inv_scale fp32 [E, C]), the amax along R per expert; expert e's output is the bytes of
+    fp8_train_quantize_colwise_t(w[e], pow2)."""
+    name = "fp8_train_quantize_colwise_t_3d"
+    dev = _require_gpu(name, w)
+    if w.dtype != torch.bfloat16 or w.dim() != 3:
+        raise RuntimeError(f"{name}: expected a 3-D bfloat16 tensor, got {w.dtype} {tuple(w.shape)}")
+    w = w.contiguous()
+    e, r, c = w.shape
+    if c % 16 != 0 or r % 16 != 0:
+        raise ValueError(f"{name}: R={r} and C={c} must be multiples of 16")
+    qt = torch.empty((e, c, r), dtype=torch.uint8, device=dev)
+    s = torch.empty((e, c), dtype=torch.float32, device=dev)
+    inv = torch.empty((e, c), dtype=torch.float32, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_fp8_train_quantize_colwise_t_3d(_ptr(w), _ptr(qt), _ptr(s), _ptr(inv), int(bool(pow2)), e, r, c, _stream()))
+    return qt.view(torch.float8_e4m3fn), s, inv
+
+
+def fp8_grouped_mm_wgrad(g_t, g_inv, x_t, x_inv, offs, N: int, K: int):
+    """The weight gradient of the float8 rowwise grouped mm (torchao/prototype/moe_training/fp8_grouped_mm.py:282-319) on the jagged casts
+    of grad_out [M, N] and x [M, K] (fp8_train_quantize_group_colwise_t): g_t e4m3 [N, M], g_inv fp32 [E, N], x_t e4m3 [K, M], x_inv fp32
+    [E, K], offs int32 [E] or None (one group of every token) -> bf16 [E, N, K] with
+    out[e] = bf16((g_t[:, rows of e] @ x_t[:, rows of e]^T) * g_inv[e][:, None] * x_inv[e][None, :]); fp32 accumulation.  Any offsets; an
+    empty group gives zeros."""
+    name = "fp8_grouped_mm_wgrad"
+    dev = _require_gpu(name, g_t, g_inv, x_t, x_inv, offs)
+    n, k = int(N), int(K)
+    g, x = _fp8_bytes(name, g_t), _fp8_bytes(name, x_t)
+    if n <= 0 or k <= 0 or g.dim() != 2 or x.dim() != 2 or g.shape[0] != n or x.shape[0] != k or g.shape[1] != x.shape[1]:
+        raise RuntimeError(f"{name}: g_t must be [N={n}, M] and x_t [K={k}, M], got {tuple(g_t.shape)} and {tuple(x_t.shape)}")
+    m = g.shape[1]
+    if m % 16 != 0 or n % 16 != 0 or k % 16 != 0:
+        raise ValueError(f"{name}: M={m}, N={n} and K={k} must be multiples of 16")
+    e = 1
+    if offs is not None:
+        offs = _offs_arg(name, offs, dev)
+        e = offs.numel()
+    if g_inv.dtype != torch.float32 or x_inv.dtype != torch.float32 or g_inv.numel() != e * n or x_inv.numel() != e * k:
+        raise RuntimeError(f"{name}: g_inv and x_inv must be float32 [E={e}, N] and [E={e}, K], got {g_inv.dtype} {tuple(g_inv.shape)} and "
+                           f"{x_inv.dtype} {tuple(x_inv.shape)}")
+    g, x, g_inv, x_inv = g.contiguous(), x.contiguous(), g_inv.contiguous(), x_inv.contiguous()
+    out = torch.empty((e, n, k), dtype=torch.bfloat16, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_fp8_grouped_mm_wgrad(_ptr(g), _ptr(g_inv), _ptr(x), _ptr(x_inv), _ptr(offs), _ptr(out), m, n, k, e, _stream()))
+    return out
 
 
 def int8_quantize_rowwise_asym(x: torch.Tensor):

@@ -3,7 +3,8 @@
 Host-side mirror of torchao/prototype/moe_training:
   * mxfp8_linear.py:27-306      _to_mxfp8_then_scaled_mm, the autograd Function mx_mm, MXFP8Linear
   * config.py:29-36, 138-252    MXFP8TrainingRecipe, MXFP8TrainingOpConfig and its quantize_ handler
-  * tensor.py:34-154, 274-337   MXFP8TrainingWeightWrapperTensor (linear / mm / matmul / addmm and _grouped_mm overrides)
+  * tensor.py:34-154, 274-337   TrainingWeightWrapperBaseTensor, MXFP8TrainingWeightWrapperTensor (linear / mm / matmul / addmm and
+                                _grouped_mm overrides)
   * conversion_utils.py:50-125  _swap_params
 The three GEMMs of a linear (mxfp8_linear.py:85-91), every operand cast to MXFP8 along the dimension its GEMM contracts:
   out         [M, N] = x [M, K]        x W [N, K]^T    ops.mx_linear on W cast rowwise (1 x 32 along K)
@@ -27,7 +28,7 @@ from ..quantization.quant_api import register_quantize_module_handler
 from .mx import BLOCK, ScaleCalculationMode, _to_mxfp8_then_scaled_grouped_mm, mxfp8_cast_both
 
 __all__ = ["mx_mm", "_to_mxfp8_then_scaled_mm", "MXFP8Linear", "MXFP8TrainingRecipe", "MXFP8TrainingOpConfig",
-           "MXFP8TrainingWeightWrapperTensor", "_swap_params", "unwrap_weight"]
+           "TrainingWeightWrapperBaseTensor", "MXFP8TrainingWeightWrapperTensor", "_swap_params", "unwrap_weight"]
 
 
 def _to_mxfp8_then_scaled_mm(
@@ -224,23 +225,68 @@ def unwrap_weight(wrapper_tensor):
     return _UnwrapWeight.apply(wrapper_tensor)
 
 
-class MXFP8TrainingWeightWrapperTensor(torch.Tensor):
-    """A wrapper of a high-precision parameter that overrides linear / mm / matmul / addmm and _grouped_mm to cast both operands to MXFP8
-    dynamically and run the MXFP8 GEMMs, forward and backward, as its config says (tensor.py:52-154, 274-337)."""
+class TrainingWeightWrapperBaseTensor(torch.Tensor):
+    """A wrapper of a high-precision parameter that behaves like a plain tensor for every op but the GEMMs its subclass overrides in
+    __torch_function__ (tensor.py:52-154).  A subclass names its config type in `config_cls`: that registers it for _swap_params."""
 
-    config: MXFP8TrainingOpConfig = None
+    config = None
+    config_cls = None
+    _by_config = {}  # config type -> wrapper class
+
+    def __init_subclass__(cls, **kwargs):
+        super().__init_subclass__(**kwargs)
+        if cls.config_cls is not None:
+            TrainingWeightWrapperBaseTensor._by_config[cls.config_cls] = cls
 
     @staticmethod
-    def __new__(cls, tensor: torch.Tensor, config: MXFP8TrainingOpConfig):
+    def __new__(cls, tensor: torch.Tensor, config):
         self = torch.Tensor._make_wrapper_subclass(
             cls, tensor.size(), strides=tensor.stride(), storage_offset=tensor.storage_offset(), dtype=tensor.dtype, layout=tensor.layout,
             device=tensor.device, requires_grad=tensor.requires_grad)
         self.config = config
         return self
 
-    def __init__(self, tensor: torch.Tensor, config: MXFP8TrainingOpConfig):
+    def __init__(self, tensor: torch.Tensor, config):
         self._data = tensor
         self.config = config
+
+    @classmethod
+    def __torch_dispatch__(cls, func, types, args, kwargs=None):
+        config = None
+
+        def unwrap(t):
+            nonlocal config
+            if config is None:
+                config = t.config
+            else:
+                assert t.config == config, f"All {cls.__name__} instances must have the same config"
+            return t._data
+
+        args_unwrapped, kwargs_unwrapped = pytree.tree_map_only(cls, unwrap, (args, kwargs or {}))
+        assert config is not None, f"__torch_dispatch__ called on {func} without any {cls.__name__} arguments"
+        if func == torch.ops.aten.detach.default:  # detach is a special case
+            return cls(args_unwrapped[0], config)
+        out = func(*args_unwrapped, **kwargs_unwrapped)
+        if func not in _ops_to_preserve_subclass:
+            return out
+        return pytree.tree_map_only(torch.Tensor, lambda x: cls(x, config), out)
+
+    def __repr__(self):
+        return f"{type(self).__name__}(data={self._data}, config={self.config})"
+
+    def __tensor_flatten__(self):
+        return ["_data"], {"config": self.config}
+
+    @classmethod
+    def __tensor_unflatten__(cls, inner_tensors, flatten_spec, outer_size, outer_stride):
+        return cls(inner_tensors["_data"], flatten_spec["config"])
+
+
+class MXFP8TrainingWeightWrapperTensor(TrainingWeightWrapperBaseTensor):
+    """A wrapper of a high-precision parameter that overrides linear / mm / matmul / addmm and _grouped_mm to cast both operands to MXFP8
+    dynamically and run the MXFP8 GEMMs, forward and backward, as its config says (tensor.py:274-337)."""
+
+    config_cls = MXFP8TrainingOpConfig
 
     @classmethod
     def __torch_function__(cls, func, types, args=(), kwargs=None):
@@ -280,45 +326,14 @@ class MXFP8TrainingWeightWrapperTensor(torch.Tensor):
         with torch._C.DisableTorchFunctionSubclass():
             return func(*args, **kwargs)
 
-    @classmethod
-    def __torch_dispatch__(cls, func, types, args, kwargs=None):
-        config = None
 
-        def unwrap(t):
-            nonlocal config
-            if config is None:
-                config = t.config
-            else:
-                assert t.config == config, f"All {cls.__name__} instances must have the same config"
-            return t._data
-
-        args_unwrapped, kwargs_unwrapped = pytree.tree_map_only(MXFP8TrainingWeightWrapperTensor, unwrap, (args, kwargs or {}))
-        assert config is not None, f"__torch_dispatch__ called on {func} without any {cls.__name__} arguments"
-        if func == torch.ops.aten.detach.default:  # detach is a special case
-            return cls(args_unwrapped[0], config)
-        out = func(*args_unwrapped, **kwargs_unwrapped)
-        if func not in _ops_to_preserve_subclass:
-            return out
-        return pytree.tree_map_only(torch.Tensor, lambda x: cls(x, config), out)
-
-    def __repr__(self):
-        return f"MXFP8TrainingWeightWrapperTensor(data={self._data}, config={self.config})"
-
-    def __tensor_flatten__(self):
-        return ["_data"], {"config": self.config}
-
-    @classmethod
-    def __tensor_unflatten__(cls, inner_tensors, flatten_spec, outer_size, outer_stride):
-        return cls(inner_tensors["_data"], flatten_spec["config"])
-
-
-def _swap_params(module: nn.Module, *, module_filter_fn=None, config: Optional[MXFP8TrainingOpConfig] = None,
-                 target_parameter_name: Optional[str] = None) -> nn.Module:
+def _swap_params(module: nn.Module, *, module_filter_fn=None, config=None, target_parameter_name: Optional[str] = None) -> nn.Module:
     """Swap the data of every nn.Parameter of `module` and its children (of those that pass module_filter_fn(module, fqn), and of the
-    parameter named target_parameter_name alone, when given) for an MXFP8TrainingWeightWrapperTensor; a wrapped parameter is left as it
-    is, requires_grad is kept (conversion_utils.py:50-125)."""
-    assert isinstance(config, MXFP8TrainingOpConfig), f"Unsupported config type: {type(config)}"
-    tensor_cls = MXFP8TrainingWeightWrapperTensor
+    parameter named target_parameter_name alone, when given) for the weight wrapper tensor of `config`'s type
+    (MXFP8TrainingOpConfig: MXFP8TrainingWeightWrapperTensor); a wrapped parameter is left as it is, requires_grad is kept
+    (conversion_utils.py:32-125)."""
+    tensor_cls = TrainingWeightWrapperBaseTensor._by_config.get(type(config))
+    assert tensor_cls is not None, f"Unsupported config type: {type(config)}"
     if isinstance(module, nn.Parameter) and (module_filter_fn is None or module_filter_fn(module, "")):
         if not isinstance(module.data, tensor_cls):
             return nn.Parameter(tensor_cls(module.data, config), requires_grad=module.requires_grad)

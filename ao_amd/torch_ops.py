@@ -73,6 +73,9 @@ _lib_def.define("mxfp8_grouped_mm(Tensor a, Tensor a_scale, Tensor b, Tensor b_s
 _lib_def.define("mxfp8_grouped_mm_wgrad(Tensor g_t, Tensor g_scale, Tensor x_t, Tensor x_scale, Tensor offs, int N, int K) -> Tensor")
 _lib_def.define("mxfp8_mm_wgrad(Tensor g_t, Tensor g_scale, Tensor x_t, Tensor x_scale, int N, int K) -> Tensor")
 _lib_def.define("mxfp8_quantize_rowcol(Tensor x, str scaling_mode) -> (Tensor, Tensor, Tensor, Tensor)")
+_lib_def.define("fp8_train_quantize_group_colwise_t(Tensor x, Tensor offs, bool pow2) -> (Tensor, Tensor, Tensor)")
+_lib_def.define("fp8_train_quantize_colwise_t_3d(Tensor w, bool pow2) -> (Tensor, Tensor, Tensor)")
+_lib_def.define("fp8_grouped_mm_wgrad(Tensor g_t, Tensor g_inv, Tensor x_t, Tensor x_inv, Tensor? offs, int N, int K) -> Tensor")
 _lib_def.define("mxfp4_quantize(Tensor x, str scaling_mode) -> (Tensor, Tensor)")
 _lib_def.define("mx_mm(Tensor a, Tensor a_scale, Tensor b, Tensor b_scale, Tensor? bias, int fmt) -> Tensor")
 _lib_def.define("mx_linear(Tensor x, Tensor b, Tensor b_scale, Tensor? bias, int fmt, str scaling_mode) -> Tensor")
@@ -119,6 +122,9 @@ _lib_impl.impl("mxfp8_grouped_mm", ops.mxfp8_grouped_mm)
 _lib_impl.impl("mxfp8_grouped_mm_wgrad", ops.mxfp8_grouped_mm_wgrad)
 _lib_impl.impl("mxfp8_mm_wgrad", ops.mxfp8_mm_wgrad)
 _lib_impl.impl("mxfp8_quantize_rowcol", lambda x, mode: ops.mxfp8_quantize_rowcol(x, mode))
+_lib_impl.impl("fp8_train_quantize_group_colwise_t", ops.fp8_train_quantize_group_colwise_t)
+_lib_impl.impl("fp8_train_quantize_colwise_t_3d", ops.fp8_train_quantize_colwise_t_3d)
+_lib_impl.impl("fp8_grouped_mm_wgrad", ops.fp8_grouped_mm_wgrad)
 _lib_impl.impl("mxfp4_quantize", lambda x, mode: ops.mxfp4_quantize(x, mode))
 _lib_impl.impl("mx_mm", ops.mx_mm)
 _lib_impl.impl("mx_linear", lambda x, b, b_scale, bias, fmt, mode: ops.mx_linear(x, b, b_scale, bias, fmt, mode))
@@ -247,6 +253,24 @@ def _(g_t, g_scale, x_t, x_scale, N, K):
     return g_t.new_empty((N, K), dtype=torch.bfloat16)
 
 
+@torch.library.register_fake("ao_mi355::fp8_train_quantize_group_colwise_t")
+def _(x, offs, pow2):
+    r, c = x.shape
+    e = offs.shape[0]
+    return (x.new_empty((c, r), dtype=torch.float8_e4m3fn), x.new_empty((e, c), dtype=torch.float32), x.new_empty((e, c), dtype=torch.float32))
+
+
+@torch.library.register_fake("ao_mi355::fp8_train_quantize_colwise_t_3d")
+def _(w, pow2):
+    e, r, c = w.shape
+    return (w.new_empty((e, c, r), dtype=torch.float8_e4m3fn), w.new_empty((e, c), dtype=torch.float32), w.new_empty((e, c), dtype=torch.float32))
+
+
+@torch.library.register_fake("ao_mi355::fp8_grouped_mm_wgrad")
+def _(g_t, g_inv, x_t, x_inv, offs, N, K):
+    return g_t.new_empty((1 if offs is None else offs.shape[0], N, K), dtype=torch.bfloat16)
+
+
 @torch.library.register_fake("ao_mi355::mxfp8_quantize_rowcol")
 def _(x, scaling_mode):
     r, c = x.shape
@@ -365,6 +389,7 @@ for _name in ("weight_int4pack_mm", "convert_weight_to_int4pack", "int8_scaled_m
               "int8_linear", "fp8_linear", "int8_linear_asym", "int8_linear_tensorwise", "fp8_linear_tensorwise", "fp8_linear_clamped",
               "int8_linear_static", "fp8_int4_linear", "fp8_int4_act_linear", "int8_quantize_rowwise", "fp8_quantize_rowwise", "mxfp8_quantize", "mxfp8_grouped_mm",
               "mxfp8_grouped_mm_wgrad", "mxfp8_mm_wgrad", "mxfp8_quantize_rowcol",
+              "fp8_train_quantize_group_colwise_t", "fp8_train_quantize_colwise_t_3d", "fp8_grouped_mm_wgrad",
               "fused_pad_token_groups", "fused_unpad_token_groups", "mxfp4_quantize", "mx_mm", "mx_linear", "int8_wo_linear", "fp8_wo_linear",
               "fp8_quantize_block_1x128", "fp8_quantize_block_128x128", "fp8_block_linear", "fp8_block_grouped_mm",
               "nvfp4_amax_scale", "nvfp4_quantize", "nvfp4_wo_linear", "nvfp4_mm", "nvfp4_linear",

@@ -297,6 +297,39 @@ int ao_fp8_train_cast(const uint16_t* x, const float* row_amax, int64_t row_amax
 int ao_fp8_train_quantize_rowwise(const uint16_t* x, uint8_t* q, float* s, float* inv_s, int pow2, int64_t R, int64_t C,
                                   void* stream);
 
+/* ---- float8 rowwise training of the MoE grouped GEMM (torchao/prototype/moe_training/fp8_grouped_mm.py:24-319) -----------------------
+ * The casts use the arithmetic above (scale, pow2, q, inv_scale).  No allocation, no synchronisation: capturable in a graph. */
+
+/* The jagged column cast (kernels/jagged_float8_scales.py:221-252, utils.py:20-86 torch_to_float8_per_group_colwise): one scale per column
+ * and token group.  x bf16 [R][C]; offs int32 [E] on the device, cumulative group ends along R ->
+ *   q_t e4m3fn [C][R] (tokens innermost, as ao_fp8_train_cast's q_col_t), s / inv_s fp32 [E][C] (group-major: the reference's [E C] vector)
+ * The amax of column c in group e runs over rows [offs[e-1], offs[e]).  An empty group gets the scale of a zero amax (448 / 1e-12) and its
+ * reciprocal; rows at or past offs[E-1] belong to no group and get code 0.
+ * offs is not validated.  Its contract: non-decreasing, within [0, R], every end a multiple of 16.  For any other int32 contents the
+ * kernels stay inside their buffers and the values are unspecified.
+ * R % 16 == 0, C % 16 == 0, 1 <= E <= 65535, R <= 65535 * 128; R == 0 or C == 0 launches nothing.  x, q_t, s 16-byte aligned.
+ * Launches: a memset of s, the maxima (atomic max into s), the scales in place, the codes. */
+int ao_fp8_train_quantize_group_colwise_t(const uint16_t* x, const int32_t* offs, uint8_t* q_t, float* s, float* inv_s, int pow2,
+                                          int64_t R, int64_t C, int64_t E, void* stream);
+
+/* The batched transposing cast of a 3-D weight (kernels/float8_rowwise.py, utils.py:156-189 torch_to_3d_rowwise_float8_transpose_rhs):
+ * w bf16 [E][R][C] -> q_t e4m3fn [E][C][R], s / inv_s fp32 [E][C]; the amax along R, per expert.  Expert e's output is byte for byte that
+ * of ao_fp8_train_amax(cols) + ao_fp8_train_cast(q_col_t) on w[e].  R % 16 == 0, C % 16 == 0, E <= 65535 and E * R <= 65535 * 128 (the
+ * walk is over the [E R][C] view, 128 rows a tile; every index is 64-bit); E, R or C == 0 launches nothing. */
+int ao_fp8_train_quantize_colwise_t_3d(const uint16_t* w, uint8_t* q_t, float* s, float* inv_s, int pow2, int64_t E, int64_t R,
+                                       int64_t C, void* stream);
+
+/* The weight gradient of the float8 rowwise grouped GEMM (fp8_grouped_mm.py:282-319: torch._scaled_grouped_mm, 2-D x 2-D with offsets) on
+ * the two jagged casts:
+ *   out[e][n][k] = bf16( (sum_{m in [offs[e-1], offs[e])} g_t[n][m] * x_t[k][m]) * g_inv[e][n] * x_inv[e][k] )
+ * fp32 accumulation, one rounding.  offs == NULL (E == 1): one group of every token.  Any offsets (clamped to [0, M_total]); an empty group
+ * stores zeros; tokens past offs[E-1] contribute to nothing.  M_total, N, K multiples of 16; E <= 65535; N * M_total and K * M_total below
+ * 2^31 (32-bit buffer offsets); the codes 16-byte aligned.  M_total == 0 zeroes out. */
+int ao_fp8_grouped_mm_wgrad(const uint8_t* g_t, const float* g_inv,   /* e4m3 [N][M_total], fp32 [E][N] */
+                            const uint8_t* x_t, const float* x_inv,   /* e4m3 [K][M_total], fp32 [E][K] */
+                            const int32_t* offs, uint16_t* out,       /* int32 [E], bf16 [E][N][K] */
+                            int64_t M_total, int64_t N, int64_t K, int64_t E, void* stream);
+
 /* HQQ qparams + codes for the tinygemm format: Int4TilePackedTo4dTensor.from_hp(..., HQQ)
  * (int4_tile_packed_to_4d_tensor.py:149-168 -> quant_primitives.py:1891-1997, optimizer :1797-1866 in float16 as on a GPU).
  *   w bf16 [N][K] -> nibble_bytes uint8 [N][K/2] (even k in the HIGH nibble: the input of
