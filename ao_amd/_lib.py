@@ -140,6 +140,9 @@ _SIGNATURES = {
     "ao_fp8_block_grouped_mm_route": [_I64, _I64, _I64, _I64, _P, _INT],
     "ao_fp8_block_grouped_mm_kernel_name": [_I64, _I64, _I64, _I64],
     "ao_fp8_block_grouped_mm_set_form": [_INT],
+    "ao_fp8_block_train_cast": [_P, _P, _P, _P, _P, _I64, _I64, _P],
+    "ao_fp8_block_train_cast_weight": [_P, _P, _P, _P, _P, _I64, _I64, _P],
+    "ao_fp8_block_mm_wgrad": [_P, _P, _P, _P, _P, _I64, _I64, _I64, _P],
     "ao_nvfp4_amax_scale": [_P, _P, _I64, _I64, _P],
     "ao_nvfp4_quantize": [_P, _P, _P, _P, _I64, _I64, _P],
     "ao_nvfp4_wo_linear": [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _P],

@@ -1808,6 +1808,102 @@ def fp8_block_grouped_mm(aq, a_scale, wq, w_scale, offs, out=None):
 __all__ += ["fp8_block_grouped_mm", "fp8_block_grouped_mm_route", "fp8_block_grouped_mm_kernel_name", "fp8_block_grouped_mm_set_form"]
 
 
+# ---- blockwise float8 TRAINING: block-local casts and the weight-gradient GEMM (include/ao_mi355.h) --------------------
+# The casts return e4m3fn codes and the fp32 RECIPROCAL scales fp8_block_mm / fp8_block_mm_wgrad multiply by.  Shapes and dtypes are
+# checked first (ValueError naming the argument), then the device.
+def _fp8_block_train_matrix(name, what, t, whole_rows):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.bfloat16:
+        raise ValueError(f"{name}: {what} must be a bfloat16 tensor, got {getattr(t, 'dtype', type(t))}")
+    if t.dim() != 2:
+        raise ValueError(f"{name}: {what} must be 2-D, got {t.dim()}-D {tuple(t.shape)}")
+    r, c = t.shape
+    if c % 128 != 0:
+        raise ValueError(f"{name}: {what} has {c} columns, which must be a multiple of 128")
+    if whole_rows and r % 128 != 0:
+        raise ValueError(f"{name}: {what} has {r} rows, which must be a multiple of 128 for 128-row blocks")
+    return r, c
+
+
+def fp8_block_train_cast(x: torch.Tensor, rows: bool = True, cols: bool = False):
+    """The blockwise training casts of an activation or a gradient (torchao/prototype/blockwise_fp8_training/kernels.py:1031-1118) in ONE
+    read of x.  x bf16 [R, C], C % 128 == 0 -> (row, col):
+      row = (q e4m3fn [R, C], inv fp32 [R, C/128]): 1 x 128 blocks (torch_blockwise_scale_act_quant_lhs), None without `rows`; any R;
+      col = (q_t e4m3fn [C, R], inv fp32 [R/128, C]): 128 x 1 blocks stored transposed (torch_blockwise_scale_act_quant_rhs; the bytes of
+            act_quant_transposed_lhs), None without `cols`; R % 128 == 0."""
+    name = "fp8_block_train_cast"
+    if not (rows or cols):
+        raise ValueError(f"{name}: neither rows nor cols asked for")
+    r, c = _fp8_block_train_matrix(name, "x", x, bool(cols))
+    dev = _require_gpu(name, x)
+    x = x.contiguous()
+    f32 = dict(dtype=torch.float32, device=dev)
+    q = inv = qt = invt = None
+    if rows:
+        q, inv = torch.empty((r, c), dtype=torch.uint8, device=dev), torch.empty((r, c // 128), **f32)
+    if cols:
+        qt, invt = torch.empty((c, r), dtype=torch.uint8, device=dev), torch.empty((r // 128, c), **f32)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_fp8_block_train_cast(_ptr(x), _ptr(q), _ptr(inv), _ptr(qt), _ptr(invt), r, c, _stream()))
+    return ((q.view(torch.float8_e4m3fn), inv) if rows else None, (qt.view(torch.float8_e4m3fn), invt) if cols else None)
+
+
+def fp8_block_train_cast_weight(w: torch.Tensor, transposed: Optional[bool] = False):
+    """The 128 x 128 training cast of a weight (kernels.py:1121-1156, torch_blockwise_scale_weight_quant).  w bf16 [N, K], both multiples
+    of 128 -> transposed False: (q e4m3fn [N, K], inv fp32 [N/128, K/128]); True: (q_t [K, N], inv_t [K/128, N/128]), the transposes (the
+    operand of grad_input); None: both pairs from one read, (plain, transposed)."""
+    name = "fp8_block_train_cast_weight"
+    n, k = _fp8_block_train_matrix(name, "w", w, True)
+    dev = _require_gpu(name, w)
+    w = w.contiguous()
+    f32 = dict(dtype=torch.float32, device=dev)
+    q = inv = qt = invt = None
+    if transposed is None or not transposed:
+        q, inv = torch.empty((n, k), dtype=torch.uint8, device=dev), torch.empty((n // 128, k // 128), **f32)
+    if transposed is None or transposed:
+        qt, invt = torch.empty((k, n), dtype=torch.uint8, device=dev), torch.empty((k // 128, n // 128), **f32)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_fp8_block_train_cast_weight(_ptr(w), _ptr(q), _ptr(inv), _ptr(qt), _ptr(invt), n, k, _stream()))
+    plain = (q.view(torch.float8_e4m3fn), inv) if q is not None else None
+    trans = (qt.view(torch.float8_e4m3fn), invt) if qt is not None else None
+    return (plain, trans) if transposed is None else (trans if transposed else plain)
+
+
+def fp8_block_mm_wgrad(g_t, g_inv, x_t, x_inv):
+    """The blockwise weight gradient grad_output^T @ x (kernels.py:320-379) on the column casts of fp8_block_train_cast: g_t e4m3 [N, M],
+    g_inv fp32 [M/128, N], x_t e4m3 [K, M], x_inv fp32 [M/128, K] -> bf16 [N, K];
+    out[n][k] = bf16(sum over token blocks mb, ascending, of (p * g_inv[mb][n]) * x_inv[mb][k]), p the block's 128 products in fp32.
+    M, N and K multiples of 128; M == 0 gives zeros."""
+    name = "fp8_block_mm_wgrad"
+    for what, t in (("g_t", g_t), ("x_t", x_t)):
+        if not isinstance(t, torch.Tensor) or t.dtype not in (torch.float8_e4m3fn, torch.uint8):
+            raise ValueError(f"{name}: {what} must hold float8_e4m3fn codes (or their bytes as uint8), got {getattr(t, 'dtype', type(t))}")
+        if t.dim() != 2:
+            raise ValueError(f"{name}: {what} must be 2-D, got {t.dim()}-D {tuple(t.shape)}")
+    n, m = g_t.shape
+    k = x_t.shape[0]
+    if x_t.shape[1] != m:
+        raise ValueError(f"{name}: x_t must be [K, M={m}] like g_t [N, M], got {tuple(x_t.shape)}")
+    for what, v in (("M (the columns of g_t)", m), ("N (the rows of g_t)", n), ("K (the rows of x_t)", k)):
+        if v % 128 != 0:
+            raise ValueError(f"{name}: {what} = {v} must be a multiple of 128")
+    if n == 0 or k == 0:
+        raise ValueError(f"{name}: g_t and x_t must have rows, got N={n} K={k}")
+    for what, t, cols in (("g_inv", g_inv, n), ("x_inv", x_inv, k)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (m // 128, cols):
+            raise ValueError(f"{name}: {what} must be float32 [M/128, {cols}] = {(m // 128, cols)}, got {getattr(t, 'dtype', type(t))} "
+                             f"{tuple(getattr(t, 'shape', ()))}")
+    dev = _require_gpu(name, g_t, g_inv, x_t, x_inv)
+    g, x = _fp8_bytes(name, g_t).contiguous(), _fp8_bytes(name, x_t).contiguous()
+    out = torch.empty((n, k), dtype=torch.bfloat16, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_fp8_block_mm_wgrad(_ptr(g), _ptr(g_inv.contiguous()), _ptr(x), _ptr(x_inv.contiguous()), _ptr(out), m, n, k,
+                                                    _stream()))
+    return out
+
+
+__all__ += ["fp8_block_train_cast", "fp8_block_train_cast_weight", "fp8_block_mm_wgrad"]
+
+
 # ---- NVFP4 linears: e2m1 codes, 1 x 16 e4m3 block scales, fp32 per-tensor scales (include/ao_mi355.h "NVFP4 linears", DESIGN.md 4.14) ----
 NVFP4_KIND_WEIGHT_ONLY = 0
 NVFP4_KIND_DYNAMIC = 1

@@ -9,7 +9,8 @@ name:
   * the casts are Float8Tensor's, scale = f32(bf16(amax / 448)) (float8_tensor.py:233-242, quant_primitives.py:2173-2212, :2271-2287)
     -- what the checkpoints hold and what this library's dense blockwise layers of the same model use.  The training op re-quantizes
     the weights in every forward with another arithmetic, a reciprocal scale from an fp64 division with EPS = 1e-12
-    (blockwise_fp8_training/kernels.py:1031-1058); that cast is out of scope here;
+    (blockwise_fp8_training/kernels.py:1031-1058); that cast is out of scope here (the DENSE linear trains with it:
+    prototype/blockwise_fp8_training.py, DESIGN.md 4.20);
   * forward only: no autograd, no backward GEMMs;
   * the GEMM is the fp32 chain of the dense blockwise linear per token group (one scaled MFMA per 128-k block onto a zero accumulator,
     acc += (p * a_s) * b_s), not a bf16 dequantize followed by a bf16 grouped mm.

@@ -85,6 +85,10 @@ _lib_def.define("fp8_quantize_block_1x128(Tensor x) -> (Tensor, Tensor)")
 _lib_def.define("fp8_quantize_block_128x128(Tensor w) -> (Tensor, Tensor)")
 _lib_def.define("fp8_block_linear(Tensor x, Tensor wq, Tensor w_scale, Tensor? bias) -> Tensor")
 _lib_def.define("fp8_block_grouped_mm(Tensor a, Tensor a_scale, Tensor b, Tensor b_scale, Tensor offs) -> Tensor")
+# (a direction that is not asked for comes back as two empty tensors: an op returns Tensors)
+_lib_def.define("fp8_block_train_cast(Tensor x, bool rows, bool cols) -> (Tensor, Tensor, Tensor, Tensor)")
+_lib_def.define("fp8_block_train_cast_weight(Tensor w, bool transposed) -> (Tensor, Tensor)")
+_lib_def.define("fp8_block_mm_wgrad(Tensor g_t, Tensor g_inv, Tensor x_t, Tensor x_inv) -> Tensor")
 _lib_def.define("nvfp4_amax_scale(Tensor x) -> Tensor")
 _lib_def.define("nvfp4_quantize(Tensor x, Tensor? per_tensor_scale) -> (Tensor, Tensor)")
 _lib_def.define("nvfp4_wo_linear(Tensor x, Tensor wq, Tensor w_scale, Tensor? per_tensor_scale, Tensor? bias) -> Tensor")
@@ -132,6 +136,17 @@ _lib_impl.impl("int8_wo_linear", lambda x, wq, w_scale, bias: ops.int8_wo_linear
 _lib_impl.impl("fp8_wo_linear", lambda x, wq, w_scale, bias: ops.fp8_wo_linear(x, wq, w_scale, bias))
 _lib_impl.impl("fp8_quantize_block_1x128", ops.fp8_quantize_block_1x128)
 _lib_impl.impl("fp8_quantize_block_128x128", ops.fp8_quantize_block_128x128)
+
+
+def _fp8_block_train_cast(x, rows, cols):
+    row, col = ops.fp8_block_train_cast(x, rows, cols)
+    none = lambda: (x.new_empty((0,), dtype=torch.float8_e4m3fn), x.new_empty((0,), dtype=torch.float32))  # noqa: E731
+    return (*(row or none()), *(col or none()))
+
+
+_lib_impl.impl("fp8_block_train_cast", _fp8_block_train_cast)
+_lib_impl.impl("fp8_block_train_cast_weight", lambda w, transposed: ops.fp8_block_train_cast_weight(w, bool(transposed)))
+_lib_impl.impl("fp8_block_mm_wgrad", ops.fp8_block_mm_wgrad)
 _lib_impl.impl("fp8_block_linear", lambda x, wq, w_scale, bias: ops.fp8_block_linear(x, wq, w_scale, bias))
 _lib_impl.impl("fp8_block_grouped_mm", lambda a, a_scale, b, b_scale, offs: ops.fp8_block_grouped_mm(a, a_scale, b, b_scale, offs))
 _lib_impl.impl("nvfp4_amax_scale", ops.nvfp4_amax_scale)
@@ -271,6 +286,25 @@ def _(g_t, g_inv, x_t, x_inv, offs, N, K):
     return g_t.new_empty((1 if offs is None else offs.shape[0], N, K), dtype=torch.bfloat16)
 
 
+@torch.library.register_fake("ao_mi355::fp8_block_train_cast")
+def _(x, rows, cols):
+    r, c = x.shape
+    e = lambda on, shape, dt: x.new_empty(shape if on else (0,), dtype=dt)  # noqa: E731
+    return (e(rows, (r, c), torch.float8_e4m3fn), e(rows, (r, c // 128), torch.float32),
+            e(cols, (c, r), torch.float8_e4m3fn), e(cols, (r // 128, c), torch.float32))
+
+
+@torch.library.register_fake("ao_mi355::fp8_block_train_cast_weight")
+def _(w, transposed):
+    n, k = (w.shape[1], w.shape[0]) if transposed else w.shape
+    return w.new_empty((n, k), dtype=torch.float8_e4m3fn), w.new_empty((n // 128, k // 128), dtype=torch.float32)
+
+
+@torch.library.register_fake("ao_mi355::fp8_block_mm_wgrad")
+def _(g_t, g_inv, x_t, x_inv):
+    return g_t.new_empty((g_t.shape[0], x_t.shape[0]), dtype=torch.bfloat16)
+
+
 @torch.library.register_fake("ao_mi355::mxfp8_quantize_rowcol")
 def _(x, scaling_mode):
     r, c = x.shape
@@ -392,6 +426,7 @@ for _name in ("weight_int4pack_mm", "convert_weight_to_int4pack", "int8_scaled_m
               "fp8_train_quantize_group_colwise_t", "fp8_train_quantize_colwise_t_3d", "fp8_grouped_mm_wgrad",
               "fused_pad_token_groups", "fused_unpad_token_groups", "mxfp4_quantize", "mx_mm", "mx_linear", "int8_wo_linear", "fp8_wo_linear",
               "fp8_quantize_block_1x128", "fp8_quantize_block_128x128", "fp8_block_linear", "fp8_block_grouped_mm",
+              "fp8_block_train_cast", "fp8_block_train_cast_weight", "fp8_block_mm_wgrad",
               "nvfp4_amax_scale", "nvfp4_quantize", "nvfp4_wo_linear", "nvfp4_mm", "nvfp4_linear",
               "nvfp4_group_amax_scale", "nvfp4_quantize_grouped", "nvfp4_grouped_mm"):
     _lib_autograd.impl(_name, torch.library.fallthrough_kernel)

@@ -786,6 +786,36 @@ const char* ao_fp8_block_grouped_mm_kernel_name(int64_t M_total, int64_t N, int6
  * 1 streaming, 2 tiled); the route queries report the forced form. */
 int ao_fp8_block_grouped_mm_set_form(int form);
 
+/* ---- blockwise float8 TRAINING: the block-local casts and the weight-gradient GEMM (fp8_block_train_kernels.hip) --------
+ * fp8_blockwise_mm of torchao/prototype/blockwise_fp8_training/linear.py:98-211.  The contract of the casts is the reference's torch
+ * functions (kernels.py:1031-1156: torch_blockwise_scale_act_quant_lhs, _act_quant_rhs, _weight_quant):
+ *   scale = f32(448 / max(f64(amax_block), 1e-12));  q = e4m3fn(clamp(f32(x) * scale, -448, 448));  the outputs hold inv = 1 / scale,
+ * the RECIPROCAL scales the GEMMs multiply by.  This is the float8 training cast's arithmetic (ao_fp8_train_cast), not that of the
+ * inference block casts above (ao_fp8_quantize_block_1x128: scale = bf16(amax / 448), q = x / scale): a block of zeros gives scale
+ * f32(448 / 1e-12) and codes 0 here, scale 0 and NaN codes there.  The 128 x 1 direction clamps the amax at bf16(1e-12) = 1.00186e-12
+ * before it widens it, as kernels.py:1096 does (only the reciprocal of a block with a smaller amax shows it; its codes are 0 either way).
+ * One launch each, one read of the input, no amax pre-pass, no allocation, no synchronisation, no atomics.
+ *
+ * ao_fp8_block_train_cast: x bf16 [R][C], either or both directions; a null (codes, scales) pair skips that direction:
+ *   rows   : 1 x 128 blocks along the last dimension, q_row [R][C], inv_row [R][C/128] row-major (ao_fp8_block_linear's a_scale); R >= 1
+ *   columns: 128 x 1 blocks along dim 0, stored transposed, q_col_t [C][R], inv_col [R/128][C] -- the bytes of both
+ *            act_quant_transposed_lhs (grad_output) and act_quant_rhs (x); R % 128 == 0
+ * C % 128 == 0.  An empty matrix returns OK without a launch; other shapes are refused before any launch.
+ * ao_fp8_block_train_cast_weight: w bf16 [N][K], 128 x 128 blocks, N and K multiples of 128; either or both layouts:
+ *   q [N][K] with inv [N/128][K/128];  q_t [K][N] with inv_t [K/128][N/128] (the transposes: a block's codes do not depend on the layout).
+ * x / w and the codes 16-byte aligned, the scales 4-byte. */
+int ao_fp8_block_train_cast(const uint16_t* x, uint8_t* q_row, float* inv_row, uint8_t* q_col_t, float* inv_col, int64_t R, int64_t C,
+                            void* stream);
+int ao_fp8_block_train_cast_weight(const uint16_t* w, uint8_t* q, float* inv, uint8_t* q_t, float* inv_t, int64_t N, int64_t K, void* stream);
+/* The weight gradient grad_output^T @ x on the column casts (kernels.py:320-379, triton_fp8_gemm_1x128_128x1).  Per output element, fp32:
+ *   acc = 0;  for token block mb ascending: p = sum over the block's 128 tokens of g_t[n][m] x_t[k][m] (one scaled MFMA onto a zero
+ *   accumulator);  acc += (p * g_inv[mb][n]) * x_inv[mb][k];  out[n][k] = bf16(acc).
+ * No split along the tokens: a launch is reproducible.  M, N and K multiples of 128 (N, K > 0), each operand below 2^31 bytes; M == 0
+ * writes zeros.  The codes and g_inv 16-byte aligned, x_inv 4-byte, out 2-byte.  Violations are refused on the host before any launch. */
+int ao_fp8_block_mm_wgrad(const uint8_t* g_t, const float* g_inv,   /* e4m3 [N][M], fp32 [M/128][N] */
+                          const uint8_t* x_t, const float* x_inv,   /* e4m3 [K][M], fp32 [M/128][K] */
+                          uint16_t* out, int64_t M, int64_t N, int64_t K, void* stream);  /* bf16 [N][K] */
+
 /* ---- NVFP4 linears: e2m1 codes, one e4m3 scale per 1 x 16 block, an optional fp32 per-tensor scale (nvfp4_kernels.hip) -----------------
  * NVFP4Tensor of prototype/mx_formats/nvfp4_tensor.py and the two configs of inference_workflow.py:173-400.  Codes are packed two a byte
  * along K, element 2i in the low nibble of byte i; block scales are float8_e4m3fn bytes, ROW-MAJOR [rows][K/16] (no 128 x 4 swizzle);
