@@ -143,6 +143,8 @@ _SIGNATURES = {
     "ao_fp8_block_train_cast": [_P, _P, _P, _P, _P, _I64, _I64, _P],
     "ao_fp8_block_train_cast_weight": [_P, _P, _P, _P, _P, _I64, _I64, _P],
     "ao_fp8_block_mm_wgrad": [_P, _P, _P, _P, _P, _I64, _I64, _I64, _P],
+    "ao_fp8_block_train_cast_weight_3d": [_P, _P, _P, _P, _P, _I64, _I64, _I64, _P],
+    "ao_fp8_block_grouped_mm_wgrad": [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P],
     "ao_nvfp4_amax_scale": [_P, _P, _I64, _I64, _P],
     "ao_nvfp4_quantize": [_P, _P, _P, _P, _I64, _I64, _P],
     "ao_nvfp4_wo_linear": [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _P],

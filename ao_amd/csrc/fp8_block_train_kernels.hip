@@ -24,6 +24,10 @@
 // vectors of step mb + 1 (128 contiguous floats each per tile) are loaded into registers while step mb multiplies.  A lane's rows
 // 4 kq + r take g_inv as fp8_block_acc's a_s; its column is fixed per j, so x_inv is fp8_block_acc's b_s, one value per lane.  No split
 // along the tokens: a launch is reproducible.
+//
+// The routed experts (torchao/prototype/moe_training/blockwise_fp8/grouped_mm.py:98-265): the weight cast over a stack of
+// experts is the same cast kernel with the expert in blockIdx.z (ao_fp8_block_train_cast_weight_3d), and fp8_block_grouped_wgrad_kernel
+// (ao_fp8_block_grouped_mm_wgrad) is the weight gradient per token group on the same column casts of all tokens.
 #include "common.h"
 #include "quant_math.h"
 #include "stream_blocks.h"
@@ -44,7 +48,9 @@ constexpr uint32_t kEpsBf16Bits = 0x2B8D0000u;
 // WEIGHT true : one 128 x 128 block a tile; ROWS = the plain layout (q_row [R][C], inv_row [R/128][C/128]), COLS = the transposed one
 //               (q_col_t [C][R], inv_col [C/128][R/128]).
 // C % 128 == 0 always; rows past R (ROWS only, not WEIGHT) are read as zeros and never stored.
-template <bool ROWS, bool COLS, bool WEIGHT>
+// BATCHED (WEIGHT only): a 3-D weight [E][R][C], expert blockIdx.z.  Every layout of an expert is the 2-D one at the expert's offset (R and C
+//               are multiples of 128, so a block never holds two experts): the walk is the 2-D walk on pointers moved to the expert.
+template <bool ROWS, bool COLS, bool WEIGHT, bool BATCHED = false>
 __global__ __launch_bounds__(kThreads) void fp8_block_train_cast_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ q_row,
                                                                         float* __restrict__ inv_row, uint8_t* __restrict__ q_col_t,
                                                                         float* __restrict__ inv_col, int64_t R, int64_t C) {
@@ -54,6 +60,19 @@ __global__ __launch_bounds__(kThreads) void fp8_block_train_cast_kernel(const ui
   __shared__ float cred[kColMax ? 4 : 1][kTile];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ci = lane & 15, g = lane >> 4;
   const int64_t r0 = (int64_t)blockIdx.y * kTile, c0 = (int64_t)blockIdx.x * kTile, c = c0 + 8 * ci;
+  if (BATCHED) {
+    static_assert(WEIGHT || !BATCHED, "the batched walk is the weight cast's");
+    const int64_t e = blockIdx.z, blocks = (R / kTile) * (C / kTile);
+    x += e * R * C;
+    if (ROWS) {
+      q_row += e * R * C;
+      inv_row += e * blocks;
+    }
+    if (COLS) {
+      q_col_t += e * R * C;
+      inv_col += e * blocks;
+    }
+  }
   u32x4 v[2][4];
 #pragma unroll
   for (int step = 0; step < 2; ++step)
@@ -239,6 +258,105 @@ __global__ __launch_bounds__(256) void fp8_block_wgrad_kernel(BlockWgradArgs p) 
   }
 }
 
+// ---- the grouped weight gradient (ao_fp8_block_grouped_mm_wgrad) --------------------------------------------------------------------------
+//   out[e][n][k] = bf16(sum over the token blocks mb that meet group e = [offs[e-1], offs[e]), ascending, of (p * g_inv[mb][n]) * x_inv[mb][k]),
+//   p = the block's tokens INSIDE the group as one scaled MFMA onto a zero accumulator.
+// The grid (tiles of K, tiles of N, E), the clamp of offs to [0, M] and the register masks of a step's foreign tokens are fp8_wgrad_kernel's
+// (fp8_grouped_train_kernels.hip); the stages, the chain and the scale prefetch are fp8_block_wgrad_kernel's.  The block scales sit on the
+// GLOBAL 128-token grid (the casts know no groups), so a block that two groups share is multiplied twice, each time with the other group's
+// codes zeroed.  An empty group runs no step and stores zeros; no split along the tokens.
+struct BlockGroupedWgradArgs {
+  const uint8_t* g;     // e4m3 [N][M]
+  const float* g_inv;   // [M/128][N]
+  const uint8_t* x;     // e4m3 [K][M]
+  const float* x_inv;   // [M/128][K]
+  const int32_t* offs;  // [E] cumulative ends; null: one group [0, M)
+  uint16_t* out;        // bf16 [E][N][K]
+  int M, N, K;
+};
+
+__global__ __launch_bounds__(256, 2) void fp8_block_grouped_wgrad_kernel(BlockGroupedWgradArgs p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, kq = lane >> 4;
+  const int e = blockIdx.z;
+  const int n0 = blockIdx.y * 128, k0 = blockIdx.x * 128;
+  const int wn = (wave >> 1) * 64, wk = (wave & 1) * 64;
+  // the group's tokens, clamped to the matrix; a range that runs backwards is an empty group
+  const int start = p.offs != nullptr ? min(max(e > 0 ? p.offs[e - 1] : 0, 0), p.M) : 0;
+  const int end = p.offs != nullptr ? min(max(p.offs[e], 0), p.M) : p.M;
+  const int s0 = start >> 7, s1 = end > start ? (end + 127) >> 7 : s0;  // end <= M and M % 128 == 0: s1 <= M / 128
+  const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc((void*)p.g, 0, p.N * p.M, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.K * p.M, 0x00020000);
+  // M, N and K are multiples of 128: every row, token and scale index of a tile lies inside
+  const float* g_row = p.g_inv + n0 + wn + 4 * kq;
+  const float* x_col = p.x_inv + k0 + wk + (lane & 15);
+  f32x4 acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  f32x4 gs[4];
+  float xs[4];
+  if (s0 < s1) {
+    wgrad_scales(g_row, x_col, s0, p.N, p.K, gs, xs);
+    wgrad_issue(rg, rx, smem + (s0 & 1) * kStage, n0, k0, s0, p.M, p.N, p.K, wave, lane);
+  }
+  for (int step = s0; step < s1; ++step) {
+    char* cur = smem + (step & 1) * kStage;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();  // stage `step` has landed for every wave; every wave is done with the other stage
+    f32x4 ngs[4];
+    float nxs[4];
+    if (step + 1 < s1) {
+      wgrad_issue(rg, rx, smem + ((step + 1) & 1) * kStage, n0, k0, step + 1, p.M, p.N, p.K, wave, lane);
+      wgrad_scales(g_row, x_col, step + 1, p.N, p.K, ngs, nxs);
+    }
+    // a step that reaches outside the group: the lane's two 16-token pieces keep the group's own tokens only
+    const bool edge = step * 128 < start || step * 128 + 128 > end;  // wave-uniform
+    u32x4 mk0, mk1;
+    if (edge) {
+      mk0 = token_mask(step * 128 + 16 * kq, start, end);
+      mk1 = token_mask(step * 128 + 64 + 16 * kq, start, end);
+    }
+    u32x4 xf0[4], xf1[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) wgrad_frag(cur + kOpBytes, wk + 16 * j + (lane & 15), kq, xf0[j], xf1[j]);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      u32x4 g0, g1;
+      wgrad_frag(cur, wn + 16 * i + (lane & 15), kq, g0, g1);
+      if (edge) {
+        g0 &= mk0;
+        g1 &= mk1;
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const f32x4 prod = mfma8_k128<false>(g0, g1, xf0[j], xf1[j], f32x4{0.f, 0.f, 0.f, 0.f});
+        acc[i][j] = fp8_block_acc(acc[i][j], prod, gs[i], xs[j]);
+      }
+    }
+    if (step + 1 < s1) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        gs[i] = ngs[i];
+        xs[i] = nxs[i];
+      }
+    }
+  }
+  uint16_t* out = p.out + (size_t)e * p.N * p.K;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int k = k0 + wk + 16 * j + (lane & 15);
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int n = n0 + wn + 16 * i + 4 * kq + r;
+        out[(size_t)n * p.K + k] = f32_to_bf16_bits(fp8_block_out(acc[i][j][r]));
+      }
+  }
+}
+
 bool aligned_to(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 // the shape of a cast: both extents multiples of 128 where the direction needs it, and a grid that one launch holds
@@ -304,6 +422,71 @@ extern "C" int ao_fp8_block_train_cast_weight(const uint16_t* w, uint8_t* q, flo
   else if (plain) ao::launch(fp8_block_train_cast_kernel<true, false, true>, grid, block, 0, s, w, q, inv, q_t, inv_t, N, K);
   else ao::launch(fp8_block_train_cast_kernel<false, true, true>, grid, block, 0, s, w, q, inv, q_t, inv_t, N, K);
   AO_LAUNCH_CHECK("fp8_block_train_cast_kernel (weight) launch");
+  return AO_OK;
+}
+
+extern "C" int ao_fp8_block_train_cast_weight_3d(const uint16_t* w, uint8_t* q, float* inv, uint8_t* q_t, float* inv_t, int64_t E, int64_t N,
+                                                 int64_t K, void* stream) {
+  const bool plain = q != nullptr || inv != nullptr, trans = q_t != nullptr || inv_t != nullptr;
+  AO_REQUIRE(E >= 0 && N >= 0 && K >= 0, "%s: bad shape E=%lld N=%lld K=%lld", __func__, (long long)E, (long long)N, (long long)K);
+  AO_REQUIRE(N % 128 == 0 && K % 128 == 0, "%s: N=%lld and K=%lld must be multiples of 128 (a 128 x 128 block lies in one expert)", __func__,
+             (long long)N, (long long)K);
+  if (E == 0 || N == 0 || K == 0) return AO_OK;
+  AO_REQUIRE(E <= 65535, "%s: E=%lld must be at most 65535", __func__, (long long)E);
+  AO_REQUIRE(E * (N / kTile) <= 65535 && K / kTile < (1ll << 31), "%s: E=%lld N=%lld K=%lld too large for one launch (at most 65535 tiles of 128 rows)",
+             __func__, (long long)E, (long long)N, (long long)K);
+  AO_REQUIRE(plain || trans, "%s: neither (q, inv) nor (q_t, inv_t) given", __func__);
+  AO_REQUIRE_PTR(w);
+  if (plain) {
+    AO_REQUIRE_PTR(q);
+    AO_REQUIRE_PTR(inv);
+  }
+  if (trans) {
+    AO_REQUIRE_PTR(q_t);
+    AO_REQUIRE_PTR(inv_t);
+  }
+  AO_REQUIRE(aligned_to(w, 16) && aligned_to(q, 16) && aligned_to(q_t, 16) && aligned_to(inv, 4) && aligned_to(inv_t, 4),
+             "%s: w and the codes must be 16-byte, the scales 4-byte aligned", __func__);
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)(K / kTile), (unsigned)(N / kTile), (unsigned)E), block(kThreads);
+  if (plain && trans) ao::launch(fp8_block_train_cast_kernel<true, true, true, true>, grid, block, 0, s, w, q, inv, q_t, inv_t, N, K);
+  else if (plain) ao::launch(fp8_block_train_cast_kernel<true, false, true, true>, grid, block, 0, s, w, q, inv, q_t, inv_t, N, K);
+  else ao::launch(fp8_block_train_cast_kernel<false, true, true, true>, grid, block, 0, s, w, q, inv, q_t, inv_t, N, K);
+  AO_LAUNCH_CHECK("fp8_block_train_cast_kernel (3-D weight) launch");
+  return AO_OK;
+}
+
+extern "C" int ao_fp8_block_grouped_mm_wgrad(const uint8_t* g_t, const float* g_inv, const uint8_t* x_t, const float* x_inv, const int32_t* offs,
+                                             uint16_t* out, int64_t M, int64_t N, int64_t K, int64_t E, void* stream) {
+  AO_REQUIRE(M >= 0 && N > 0 && K > 0, "%s: bad shape M=%lld N=%lld K=%lld", __func__, (long long)M, (long long)N, (long long)K);
+  AO_REQUIRE(M % 128 == 0 && N % 128 == 0 && K % 128 == 0, "%s: M=%lld, N=%lld and K=%lld must be multiples of 128", __func__, (long long)M,
+             (long long)N, (long long)K);
+  AO_REQUIRE(E >= 1 && E <= 65535, "%s: E=%lld must be in 1..65535 (the grid's z extent)", __func__, (long long)E);
+  AO_REQUIRE(offs != nullptr || E == 1, "%s: without offs there is one group of every token, got E=%lld", __func__, (long long)E);
+  AO_REQUIRE(M < (1ll << 31) && N < (1ll << 31) && K < (1ll << 31) && N * M < (1ll << 31) && K * M < (1ll << 31) && N / 128 <= 65535,
+             "%s: M=%lld N=%lld K=%lld: the sizes and both operands' byte counts must be below 2^31", __func__, (long long)M, (long long)N,
+             (long long)K);
+  AO_REQUIRE_PTR(out);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (M == 0) {
+    const hipError_t rc = hipMemsetAsync(out, 0, (size_t)E * N * K * sizeof(uint16_t), st);
+    if (rc != hipSuccess) return hip_failed(rc, "hipMemsetAsync(fp8_block_grouped_mm_wgrad)");
+    return AO_OK;
+  }
+  AO_REQUIRE_PTR(g_t);
+  AO_REQUIRE_PTR(g_inv);
+  AO_REQUIRE_PTR(x_t);
+  AO_REQUIRE_PTR(x_inv);
+  AO_REQUIRE(aligned_to(g_t, 16) && aligned_to(x_t, 16) && aligned_to(g_inv, 16) && aligned_to(x_inv, 4) && aligned_to(out, 2) &&
+                 aligned_to(offs, 4),
+             "%s: the codes and g_inv must be 16-byte, x_inv and offs 4-byte and out 2-byte aligned", __func__);
+  constexpr size_t smem = 2 * kStage;
+  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(fp8_block_grouped_wgrad_kernel), smem,
+                                  "hipFuncSetAttribute(fp8_block_grouped_wgrad_kernel)"))
+    return rc;
+  const BlockGroupedWgradArgs args{g_t, g_inv, x_t, x_inv, offs, out, (int)M, (int)N, (int)K};
+  ao::launch(fp8_block_grouped_wgrad_kernel, dim3((unsigned)(K / 128), (unsigned)(N / 128), (unsigned)E), dim3(256), smem, st, args);
+  AO_LAUNCH_CHECK("fp8_block_grouped_wgrad_kernel launch");
   return AO_OK;
 }
 

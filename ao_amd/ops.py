@@ -1868,12 +1868,8 @@ def fp8_block_train_cast_weight(w: torch.Tensor, transposed: Optional[bool] = Fa
     return (plain, trans) if transposed is None else (trans if transposed else plain)
 
 
-def fp8_block_mm_wgrad(g_t, g_inv, x_t, x_inv):
-    """The blockwise weight gradient grad_output^T @ x (kernels.py:320-379) on the column casts of fp8_block_train_cast: g_t e4m3 [N, M],
-    g_inv fp32 [M/128, N], x_t e4m3 [K, M], x_inv fp32 [M/128, K] -> bf16 [N, K];
-    out[n][k] = bf16(sum over token blocks mb, ascending, of (p * g_inv[mb][n]) * x_inv[mb][k]), p the block's 128 products in fp32.
-    M, N and K multiples of 128; M == 0 gives zeros."""
-    name = "fp8_block_mm_wgrad"
+def _fp8_block_wgrad_operands(name, g_t, g_inv, x_t, x_inv):
+    """The shapes and dtypes of the column casts a blockwise weight gradient takes -> (M, N, K)."""
     for what, t in (("g_t", g_t), ("x_t", x_t)):
         if not isinstance(t, torch.Tensor) or t.dtype not in (torch.float8_e4m3fn, torch.uint8):
             raise ValueError(f"{name}: {what} must hold float8_e4m3fn codes (or their bytes as uint8), got {getattr(t, 'dtype', type(t))}")
@@ -1892,6 +1888,16 @@ def fp8_block_mm_wgrad(g_t, g_inv, x_t, x_inv):
         if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (m // 128, cols):
             raise ValueError(f"{name}: {what} must be float32 [M/128, {cols}] = {(m // 128, cols)}, got {getattr(t, 'dtype', type(t))} "
                              f"{tuple(getattr(t, 'shape', ()))}")
+    return m, n, k
+
+
+def fp8_block_mm_wgrad(g_t, g_inv, x_t, x_inv):
+    """The blockwise weight gradient grad_output^T @ x (kernels.py:320-379) on the column casts of fp8_block_train_cast: g_t e4m3 [N, M],
+    g_inv fp32 [M/128, N], x_t e4m3 [K, M], x_inv fp32 [M/128, K] -> bf16 [N, K];
+    out[n][k] = bf16(sum over token blocks mb, ascending, of (p * g_inv[mb][n]) * x_inv[mb][k]), p the block's 128 products in fp32.
+    M, N and K multiples of 128; M == 0 gives zeros."""
+    name = "fp8_block_mm_wgrad"
+    m, n, k = _fp8_block_wgrad_operands(name, g_t, g_inv, x_t, x_inv)
     dev = _require_gpu(name, g_t, g_inv, x_t, x_inv)
     g, x = _fp8_bytes(name, g_t).contiguous(), _fp8_bytes(name, x_t).contiguous()
     out = torch.empty((n, k), dtype=torch.bfloat16, device=dev)
@@ -1902,6 +1908,66 @@ def fp8_block_mm_wgrad(g_t, g_inv, x_t, x_inv):
 
 
 __all__ += ["fp8_block_train_cast", "fp8_block_train_cast_weight", "fp8_block_mm_wgrad"]
+
+
+# ---- blockwise float8 TRAINING of the MoE grouped GEMM: the 3-D weight cast and the grouped weight gradient -----------
+def fp8_block_train_cast_weight_3d(w: torch.Tensor, transposed: Optional[bool] = False):
+    """fp8_block_train_cast_weight over a stack of experts in one launch (ao_fp8_block_train_cast_weight_3d).  w bf16 [E, N, K], N and K
+    multiples of 128 -> transposed False: (q e4m3fn [E, N, K], inv fp32 [E, N/128, K/128]); True: (q_t [E, K, N], inv_t [E, K/128, N/128]);
+    None: both pairs from one read, (plain, transposed).  Expert e's outputs are the bytes of the 2-D op on w[e]."""
+    name = "fp8_block_train_cast_weight_3d"
+    if not isinstance(w, torch.Tensor) or w.dtype != torch.bfloat16:
+        raise ValueError(f"{name}: w must be a bfloat16 tensor, got {getattr(w, 'dtype', type(w))}")
+    if w.dim() != 3:
+        raise ValueError(f"{name}: w must be 3-D [E, N, K], got {w.dim()}-D {tuple(w.shape)}")
+    e, n, k = w.shape
+    if n % 128 != 0:
+        raise ValueError(f"{name}: w has {n} rows an expert, which must be a multiple of 128")
+    if k % 128 != 0:
+        raise ValueError(f"{name}: w has {k} columns, which must be a multiple of 128")
+    if e > 65535 or e * (n // 128) > 65535:
+        raise ValueError(f"{name}: w holds E={e} experts of {n // 128} row tiles; at most 65535 experts and 65535 row tiles fit one launch")
+    dev = _require_gpu(name, w)
+    w = w.contiguous()
+    f32 = dict(dtype=torch.float32, device=dev)
+    q = inv = qt = invt = None
+    if transposed is None or not transposed:
+        q, inv = torch.empty((e, n, k), dtype=torch.uint8, device=dev), torch.empty((e, n // 128, k // 128), **f32)
+    if transposed is None or transposed:
+        qt, invt = torch.empty((e, k, n), dtype=torch.uint8, device=dev), torch.empty((e, k // 128, n // 128), **f32)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_fp8_block_train_cast_weight_3d(_ptr(w), _ptr(q), _ptr(inv), _ptr(qt), _ptr(invt), e, n, k, _stream()))
+    plain = (q.view(torch.float8_e4m3fn), inv) if q is not None else None
+    trans = (qt.view(torch.float8_e4m3fn), invt) if qt is not None else None
+    return (plain, trans) if transposed is None else (trans if transposed else plain)
+
+
+def fp8_block_grouped_mm_wgrad(g_t, g_inv, x_t, x_inv, offs):
+    """The blockwise weight gradient per token group (ao_fp8_block_grouped_mm_wgrad) on the column casts of fp8_block_train_cast over ALL
+    tokens: g_t e4m3 [N, M], g_inv fp32 [M/128, N], x_t e4m3 [K, M], x_inv fp32 [M/128, K], offs int32 [E] cumulative group ends (read on
+    the device; None: one group of every token) -> bf16 [E, N, K];
+    out[e][n][k] = bf16(sum over the token blocks mb that meet group e, ascending, of (p * g_inv[mb][n]) * x_inv[mb][k]), p the products of
+    the block's tokens inside the group.  M, N and K multiples of 128; group ends need no alignment; an empty group gives zeros."""
+    name = "fp8_block_grouped_mm_wgrad"
+    m, n, k = _fp8_block_wgrad_operands(name, g_t, g_inv, x_t, x_inv)
+    if offs is not None and (not isinstance(offs, torch.Tensor) or offs.dtype != torch.int32 or offs.dim() != 1 or offs.numel() == 0):
+        raise ValueError(f"{name}: offs must be a non-empty int32 [E] tensor or None, got {getattr(offs, 'dtype', type(offs))} "
+                         f"{tuple(getattr(offs, 'shape', ()))}")
+    e = 1 if offs is None else offs.numel()
+    if e > 65535:
+        raise ValueError(f"{name}: offs holds {e} groups; at most 65535 fit one launch")
+    if n * m >= 2 ** 31 or k * m >= 2 ** 31:
+        raise ValueError(f"{name}: g_t and x_t must each be below 2^31 bytes, got N M = {n * m} and K M = {k * m}")
+    dev = _require_gpu(name, g_t, g_inv, x_t, x_inv, offs)
+    g, x = _fp8_bytes(name, g_t).contiguous(), _fp8_bytes(name, x_t).contiguous()
+    out = torch.empty((e, n, k), dtype=torch.bfloat16, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_fp8_block_grouped_mm_wgrad(_ptr(g), _ptr(g_inv.contiguous()), _ptr(x), _ptr(x_inv.contiguous()),
+                                                            _ptr(None if offs is None else offs.contiguous()), _ptr(out), m, n, k, e, _stream()))
+    return out
+
+
+__all__ += ["fp8_block_train_cast_weight_3d", "fp8_block_grouped_mm_wgrad"]
 
 
 # ---- NVFP4 linears: e2m1 codes, 1 x 16 e4m3 block scales, fp32 per-tensor scales (include/ao_mi355.h "NVFP4 linears", DESIGN.md 4.14) ----

@@ -1,5 +1,10 @@
 """Prototype-namespace mirrors (torchao/prototype/*) that sit on the SURVEY.md section 8 path."""
 from .blockwise_fp8 import Float8BlockwiseExpertWeights, fp8_blockwise_grouped_mm  # noqa: F401
+from .blockwise_fp8_grouped_training import (  # noqa: F401
+    _Float8BlockwiseGroupedMM,
+    _to_fp8_blockwise_then_emulated_scaled_grouped_mm,
+    _to_fp8_blockwise_then_scaled_grouped_mm,
+)
 from .blockwise_fp8_training import Float8BlockwiseLinear, Float8BlockwiseLinearConfig, fp8_blockwise_mm  # noqa: F401
 from .fp8_grouped_training import (  # noqa: F401
     Float8TrainingOpConfig,
@@ -30,4 +35,5 @@ __all__ = ["Float8BlockwiseExpertWeights", "fp8_blockwise_grouped_mm", "NVFP4Ten
            "nvfp4_grouped_mm", "MXFP8Linear", "MXFP8TrainingOpConfig", "MXFP8TrainingRecipe", "MXFP8TrainingWeightWrapperTensor",
            "_to_mxfp8_then_scaled_mm", "mx_mm", "Float8TrainingOpConfig", "Float8TrainingRecipe", "Float8TrainingWeightWrapperTensor",
            "_Float8GroupedMM", "_to_fp8_rowwise_then_scaled_grouped_mm", "fp8_blockwise_mm", "Float8BlockwiseLinear",
-           "Float8BlockwiseLinearConfig"]
+           "Float8BlockwiseLinearConfig", "_Float8BlockwiseGroupedMM", "_to_fp8_blockwise_then_scaled_grouped_mm",
+           "_to_fp8_blockwise_then_emulated_scaled_grouped_mm"]

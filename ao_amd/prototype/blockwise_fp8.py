@@ -11,7 +11,8 @@ name:
     the weights in every forward with another arithmetic, a reciprocal scale from an fp64 division with EPS = 1e-12
     (blockwise_fp8_training/kernels.py:1031-1058); that cast is out of scope here (the DENSE linear trains with it:
     prototype/blockwise_fp8_training.py, DESIGN.md 4.20);
-  * forward only: no autograd, no backward GEMMs;
+  * forward only: no autograd, no backward GEMMs (the mirror of the training op, with its names, its casts and all three GEMMs, is
+    prototype/blockwise_fp8_grouped_training.py, DESIGN.md 4.21, which calls this module's GEMM kernel on the training casts);
   * the GEMM is the fp32 chain of the dense blockwise linear per token group (one scaled MFMA per 128-k block onto a zero accumulator,
     acc += (p * a_s) * b_s), not a bf16 dequantize followed by a bf16 grouped mm.
 Float8Tensor's aten._grouped_mm keeps refusing block scales, as upstream does.

@@ -12,8 +12,8 @@ The three GEMMs, every operand cast each call from the high-precision tensor (th
   grad_weight [N, K] = grad_out^T      x x             ops.fp8_block_mm_wgrad on the 128 x 1 casts of grad_out and x (stored transposed)
 grad_out is cast in both directions by one read of it (ops.fp8_block_train_cast(go, rows=True, cols=True)).  The casts hold RECIPROCAL
 scales, which is what the GEMMs multiply by.  DESIGN.md 4.20.
-Left out: the grouped blockwise training op (moe_training/blockwise_fp8), the DTensor / FSDP sharding rules of the reference's kernels,
-torch.compile of the Function, e5m2 / fnuz elements, fp32 operands.
+The routed experts train through blockwise_fp8_grouped_training.py.
+Left out: the DTensor / FSDP sharding rules of the reference's kernels, torch.compile of the Function, e5m2 / fnuz elements, fp32 operands.
 """
 import torch
 from torch import nn

@@ -89,6 +89,8 @@ _lib_def.define("fp8_block_grouped_mm(Tensor a, Tensor a_scale, Tensor b, Tensor
 _lib_def.define("fp8_block_train_cast(Tensor x, bool rows, bool cols) -> (Tensor, Tensor, Tensor, Tensor)")
 _lib_def.define("fp8_block_train_cast_weight(Tensor w, bool transposed) -> (Tensor, Tensor)")
 _lib_def.define("fp8_block_mm_wgrad(Tensor g_t, Tensor g_inv, Tensor x_t, Tensor x_inv) -> Tensor")
+_lib_def.define("fp8_block_train_cast_weight_3d(Tensor w, bool transposed) -> (Tensor, Tensor)")
+_lib_def.define("fp8_block_grouped_mm_wgrad(Tensor g_t, Tensor g_inv, Tensor x_t, Tensor x_inv, Tensor? offs) -> Tensor")
 _lib_def.define("nvfp4_amax_scale(Tensor x) -> Tensor")
 _lib_def.define("nvfp4_quantize(Tensor x, Tensor? per_tensor_scale) -> (Tensor, Tensor)")
 _lib_def.define("nvfp4_wo_linear(Tensor x, Tensor wq, Tensor w_scale, Tensor? per_tensor_scale, Tensor? bias) -> Tensor")
@@ -147,6 +149,8 @@ def _fp8_block_train_cast(x, rows, cols):
 _lib_impl.impl("fp8_block_train_cast", _fp8_block_train_cast)
 _lib_impl.impl("fp8_block_train_cast_weight", lambda w, transposed: ops.fp8_block_train_cast_weight(w, bool(transposed)))
 _lib_impl.impl("fp8_block_mm_wgrad", ops.fp8_block_mm_wgrad)
+_lib_impl.impl("fp8_block_train_cast_weight_3d", lambda w, transposed: ops.fp8_block_train_cast_weight_3d(w, bool(transposed)))
+_lib_impl.impl("fp8_block_grouped_mm_wgrad", ops.fp8_block_grouped_mm_wgrad)
 _lib_impl.impl("fp8_block_linear", lambda x, wq, w_scale, bias: ops.fp8_block_linear(x, wq, w_scale, bias))
 _lib_impl.impl("fp8_block_grouped_mm", lambda a, a_scale, b, b_scale, offs: ops.fp8_block_grouped_mm(a, a_scale, b, b_scale, offs))
 _lib_impl.impl("nvfp4_amax_scale", ops.nvfp4_amax_scale)
@@ -305,6 +309,17 @@ def _(g_t, g_inv, x_t, x_inv):
     return g_t.new_empty((g_t.shape[0], x_t.shape[0]), dtype=torch.bfloat16)
 
 
+@torch.library.register_fake("ao_mi355::fp8_block_train_cast_weight_3d")
+def _(w, transposed):
+    e, n, k = (w.shape[0], w.shape[2], w.shape[1]) if transposed else w.shape
+    return w.new_empty((e, n, k), dtype=torch.float8_e4m3fn), w.new_empty((e, n // 128, k // 128), dtype=torch.float32)
+
+
+@torch.library.register_fake("ao_mi355::fp8_block_grouped_mm_wgrad")
+def _(g_t, g_inv, x_t, x_inv, offs):
+    return g_t.new_empty((1 if offs is None else offs.shape[0], g_t.shape[0], x_t.shape[0]), dtype=torch.bfloat16)
+
+
 @torch.library.register_fake("ao_mi355::mxfp8_quantize_rowcol")
 def _(x, scaling_mode):
     r, c = x.shape
@@ -427,6 +442,7 @@ for _name in ("weight_int4pack_mm", "convert_weight_to_int4pack", "int8_scaled_m
               "fused_pad_token_groups", "fused_unpad_token_groups", "mxfp4_quantize", "mx_mm", "mx_linear", "int8_wo_linear", "fp8_wo_linear",
               "fp8_quantize_block_1x128", "fp8_quantize_block_128x128", "fp8_block_linear", "fp8_block_grouped_mm",
               "fp8_block_train_cast", "fp8_block_train_cast_weight", "fp8_block_mm_wgrad",
+              "fp8_block_train_cast_weight_3d", "fp8_block_grouped_mm_wgrad",
               "nvfp4_amax_scale", "nvfp4_quantize", "nvfp4_wo_linear", "nvfp4_mm", "nvfp4_linear",
               "nvfp4_group_amax_scale", "nvfp4_quantize_grouped", "nvfp4_grouped_mm"):
     _lib_autograd.impl(_name, torch.library.fallthrough_kernel)

@@ -756,7 +756,8 @@ int ao_fp8_block_linear_set_form(int form);
  *   acc = 0;  for kb ascending: p = sum of the block's 128 products a[m][k] b[e][n][k];  acc += (p * a_scale[m][kb]) * b_scale[e][n / 128][kb]
  *   out[m][n] = bf16(acc)
  * Upstream has the operation as a training prototype only (torchao/prototype/moe_training/blockwise_fp8/grouped_mm.py with
- * grouped_mm_backend.py: DeepGEMM, or an emulation that dequantizes both operands to bf16, blockwise_fp8_training/grouped_kernels.py:78-93);
+ * grouped_mm_backend.py: DeepGEMM, or an emulation that dequantizes both operands to bf16, blockwise_fp8_training/grouped_kernels.py:78-93;
+ * its training side here: "blockwise float8 TRAINING of the MoE grouped GEMM" below);
  * Float8Tensor's aten._grouped_mm refuses block scales (float8_tensor.py:1085-1122).
  * a e4m3fn [M_total][K]; a_scale fp32 [M_total][K/128]; b e4m3fn [E][N][K], every expert row-major and K-contiguous as the checkpoint
  * stores it; b_scale fp32 [E][ceil(N/128)][K/128] (weight_scale_inv, stacked); offs int32 [E], cumulative group ends, read on the device
@@ -815,6 +816,36 @@ int ao_fp8_block_train_cast_weight(const uint16_t* w, uint8_t* q, float* inv, ui
 int ao_fp8_block_mm_wgrad(const uint8_t* g_t, const float* g_inv,   /* e4m3 [N][M], fp32 [M/128][N] */
                           const uint8_t* x_t, const float* x_inv,   /* e4m3 [K][M], fp32 [M/128][K] */
                           uint16_t* out, int64_t M, int64_t N, int64_t K, void* stream);  /* bf16 [N][K] */
+
+/* ---- blockwise float8 TRAINING of the MoE grouped GEMM (fp8_block_train_kernels.hip) ------------------------------------
+ * _Float8BlockwiseGroupedMM of torchao/prototype/moe_training/blockwise_fp8/grouped_mm.py:98-265.  The forward and grad_A are
+ * ao_fp8_block_grouped_mm on the casts above (rows of A / grad_output, the 3-D weight cast below); the two entries here are what was
+ * missing.
+ *
+ * ao_fp8_block_train_cast_weight_3d: ao_fp8_block_train_cast_weight over a stack of experts, w bf16 [E][N][K], in one launch and one
+ * read of w: expert e's outputs are byte for byte those of the 2-D entry on w[e], at e N K (codes) and e (N/128)(K/128) (scales) of
+ *   q [E][N][K] with inv [E][N/128][K/128]  (the forward's B of ao_fp8_block_grouped_mm);
+ *   q_t [E][K][N] with inv_t [E][K/128][N/128]  (grad_A's B).  A null pair skips that layout.
+ * N and K multiples of 128, 1 <= E <= 65535, at most 65535 row tiles (E N / 128); an empty tensor returns OK without a launch.  No
+ * allocation, no synchronisation, no atomics; every index is 64-bit.  w and the codes 16-byte aligned, the scales 4-byte. */
+int ao_fp8_block_train_cast_weight_3d(const uint16_t* w, uint8_t* q, float* inv, uint8_t* q_t, float* inv_t, int64_t E, int64_t N, int64_t K,
+                                      void* stream);
+/* The grouped weight gradient: ao_fp8_block_mm_wgrad per token group, on the column casts of the WHOLE token matrix (their 128-token blocks
+ * sit on the global grid, whatever offs is -- what the reference's emulated wgrad feeds torch._grouped_mm, grouped_mm_backend.py:158-194).
+ * Group e = tokens [lo, hi) = offs[e-1], offs[e] clamped to [0, M] (offs[-1] = 0); a non-increasing pair is an empty group.  Per output
+ * element (e, n, k), fp32:
+ *   acc = 0;  for every token block mb that meets [lo, hi), ascending: p = sum over the block's tokens INSIDE [lo, hi) of
+ *   g_t[n][m] x_t[k][m] (one scaled MFMA with unit scales onto a zero accumulator, the foreign tokens' codes zeroed in registers);
+ *   acc += (p * g_inv[mb][n]) * x_inv[mb][k];  out[e][n][k] = bf16(acc).
+ * An empty group stores zeros; tokens at or past offs[E-1] contribute to nothing; group ends need no alignment.  No split along the
+ * tokens: a launch is reproducible.  offs is read on the device; NULL means one group of every token (E must be 1).
+ * M, N and K multiples of 128 (N, K > 0), 1 <= E <= 65535, N M and K M below 2^31; M == 0 writes zeros.  The codes and g_inv 16-byte
+ * aligned, x_inv and offs 4-byte, out 2-byte.  Null pointers other than offs and bad shapes are refused on the host before any launch. */
+int ao_fp8_block_grouped_mm_wgrad(const uint8_t* g_t, const float* g_inv,   /* e4m3 [N][M], fp32 [M/128][N] */
+                                  const uint8_t* x_t, const float* x_inv,   /* e4m3 [K][M], fp32 [M/128][K] */
+                                  const int32_t* offs,                      /* int32 [E] cumulative ends, device; NULL = one group of every token */
+                                  uint16_t* out,                            /* bf16 [E][N][K] */
+                                  int64_t M, int64_t N, int64_t K, int64_t E, void* stream);
 
 /* ---- NVFP4 linears: e2m1 codes, one e4m3 scale per 1 x 16 block, an optional fp32 per-tensor scale (nvfp4_kernels.hip) -----------------
  * NVFP4Tensor of prototype/mx_formats/nvfp4_tensor.py and the two configs of inference_workflow.py:173-400.  Codes are packed two a byte
