@@ -34,13 +34,15 @@ int ensure_dynamic_lds(const void* kernel, size_t bytes, const char* what);
     }                                        \
   } while (0)
 
-#define AO_REQUIRE_PTR(p)                                        \
+// (fn: the entry's name, where a helper shared by several entries makes the check)
+#define AO_REQUIRE_PTR_FN(fn, p)                                 \
   do {                                                           \
     if ((p) == nullptr) {                                        \
-      ::ao::set_error("%s: null pointer argument '%s'", __func__, #p); \
+      ::ao::set_error("%s: null pointer argument '%s'", fn, #p); \
       return AO_ERR_NULL_POINTER;                                \
     }                                                            \
   } while (0)
+#define AO_REQUIRE_PTR(p) AO_REQUIRE_PTR_FN(__func__, p)
 
 #define AO_LAUNCH_CHECK(what)                          \
   do {                                                 \

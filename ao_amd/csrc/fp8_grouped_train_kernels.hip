@@ -1,6 +1,6 @@
 // float8 rowwise training of the MoE grouped GEMM for gfx950: the casts that follow token groups, the transposing cast of a 3-D weight and
 // the 2-D x 2-D grouped GEMM of the weight gradient.  The arithmetic of the casts is that of fp8_train_kernels.hip, stated once in
-// quant_math.h (fp8_train_scale, fp8_train_q); the GEMM's stage layout is that of mx_wgrad_kernels.hip (wgrad_stage.h).
+// quant_math.h (fp8_train_scale, fp8_train_q), their tile walk in fp8_train_tile.h; the GEMM is the weight-gradient frame (wgrad_frame.h).
 //
 // Reference (torchao 0.19.0 snapshot, prototype/moe_training):
 //   jagged cast : kernels/jagged_float8_scales.py:221-252, utils.py:20-86 (torch_to_float8_per_group_colwise): one scale per column and
@@ -20,13 +20,13 @@
 #include "quant_math.h"
 #include "fp8_train_tile.h"
 #include "stream_blocks.h"
-#include "wgrad_stage.h"
+#include "wgrad_frame.h"
 
 namespace ao {
 namespace {
 
 using namespace fp8_train_tile;
-using namespace wgrad_stage;
+using namespace wgrad_frame;
 
 constexpr int kSlabs = kTile / 16;
 
@@ -55,13 +55,7 @@ __global__ __launch_bounds__(kThreads) void fp8_group_amax_cols_kernel(const uin
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ci = lane & 15, g = lane >> 4;
   const int64_t r0 = (int64_t)blockIdx.y * kTile, c = (int64_t)blockIdx.x * kTile + 8 * ci;
   u32x4 v[2][4];
-#pragma unroll
-  for (int step = 0; step < 2; ++step)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int64_t r = r0 + tile_row(step, wave, g) + k;
-      v[step][k] = (r < rows && c < C) ? *reinterpret_cast<const u32x4*>(x + r * C + c) : u32x4{0u, 0u, 0u, 0u};
-    }
+  load_tile<true>(x, r0, c, rows, C, wave, g, v);
 #pragma unroll
   for (int step = 0; step < 2; ++step) {
     const int slab = step * 4 + wave;
@@ -73,15 +67,7 @@ __global__ __launch_bounds__(kThreads) void fp8_group_amax_cols_kernel(const uin
 #pragma unroll
       for (int j = 0; j < 8; ++j) cm[j] = fmaxf(cm[j], fabsf(f[j]));
     }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      cm[j] = fmaxf(cm[j], __shfl_xor(cm[j], 16));
-      cm[j] = fmaxf(cm[j], __shfl_xor(cm[j], 32));
-    }
-    if (g == 0) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) cred[slab][8 * ci + j] = cm[j];
-    }
+    reduce_cols(cm, cred[slab], ci, g);
     if (lane == 0) sgrp[slab] = slab_group<BATCHED>(offs, E, r0 + 16 * slab, rows, rows_per);
   }
   __syncthreads();
@@ -122,17 +108,11 @@ template <bool BATCHED>
 __global__ __launch_bounds__(kThreads) void fp8_group_cast_cols_t_kernel(const uint16_t* __restrict__ x, const int32_t* __restrict__ offs,
                                                                          const float* __restrict__ s, uint8_t* __restrict__ q_t,
                                                                          int64_t rows, int64_t C, int64_t rows_per, int E) {
-  __shared__ __attribute__((aligned(16))) uint8_t tile[kTile * kTileLds];
+  __shared__ __attribute__((aligned(16))) uint8_t tile[kTileLdsBytes];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ci = lane & 15, g = lane >> 4;
   const int64_t r0 = (int64_t)blockIdx.y * kTile, c0 = (int64_t)blockIdx.x * kTile, c = c0 + 8 * ci;
   u32x4 v[2][4];
-#pragma unroll
-  for (int step = 0; step < 2; ++step)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int64_t r = r0 + tile_row(step, wave, g) + k;
-      v[step][k] = (r < rows && c < C) ? *reinterpret_cast<const u32x4*>(x + r * C + c) : u32x4{0u, 0u, 0u, 0u};
-    }
+  load_tile<true>(x, r0, c, rows, C, wave, g, v);
 #pragma unroll
   for (int step = 0; step < 2; ++step) {
     const int lr = tile_row(step, wave, g);
@@ -144,27 +124,13 @@ __global__ __launch_bounds__(kThreads) void fp8_group_cast_cols_t_kernel(const u
       sc[0] = s0.x; sc[1] = s0.y; sc[2] = s0.z; sc[3] = s0.w;
       sc[4] = s1.x; sc[5] = s1.y; sc[6] = s1.z; sc[7] = s1.w;
     }
-    float f[4][8];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) unpack8(v[step][k], f[k]);
-#pragma unroll
-    for (int j = 0; j < 8; ++j)  // rows lr .. lr + 3 of column 8 ci + j: one dword (lr % 4 == 0, 132 % 4 == 0)
-      *reinterpret_cast<uint32_t*>(tile + (8 * ci + j) * kTileLds + lr) =
-          live ? cvt4_e4m3(fp8_train_q(f[0][j], sc[j]), fp8_train_q(f[1][j], sc[j]), fp8_train_q(f[2][j], sc[j]), fp8_train_q(f[3][j], sc[j]))
-               : 0u;
+    stage_cols_t(tile, v[step], sc, ci, lr, live);
   }
   __syncthreads();
-  // 128 columns x 8 pieces of 16 bytes (= one slab each); rows % 16 == 0: a piece that starts inside the matrix lies inside, and
-  // (batched, rows_per % 16 == 0) inside one expert
-  for (int p = threadIdx.x; p < kTile * kSlabs; p += kThreads) {
-    const int col = p >> 3, part = p & 7;
-    const int64_t gc = c0 + col, gr = r0 + part * 16;
-    if (gc < C && gr < rows) {
-      const uint32_t* src = reinterpret_cast<const uint32_t*>(tile + col * kTileLds + part * 16);
-      uint8_t* dst = BATCHED ? q_t + (gr / rows_per) * C * rows_per + gc * rows_per + gr % rows_per : q_t + gc * rows + gr;
-      *reinterpret_cast<u32x4*>(dst) = u32x4{src[0], src[1], src[2], src[3]};
-    }
-  }
+  // a piece is one slab: (batched, rows_per % 16 == 0) it lies inside one expert
+  flush_cols_t<true>(tile, c0, r0, C, rows, [&](int64_t gc, int64_t gr) {
+    return BATCHED ? q_t + (gr / rows_per) * C * rows_per + gc * rows_per + gr % rows_per : q_t + gc * rows + gr;
+  });
 }
 
 // rows = the rows walked (R, or E R batched); the grid's y extent carries 65535 tiles of 128 rows
@@ -185,9 +151,8 @@ int group_cast(const uint16_t* x, const int32_t* offs, uint8_t* q_t, float* s, f
 
 // ---- the grouped weight gradient -----------------------------------------------------------------------------------------------------------
 //   out[e][n][k] = bf16( (sum_{m in [offs[e-1], offs[e])} g_t[n][m] x_t[k][m]) * g_inv[e][n] * x_inv[e][k] )
-// mx_wgrad_kernel (mx_wgrad_kernels.hip) without block scales: the same grid (tiles of K, tiles of N, E), tiles, stages, k steps on the
-// global 128-token grid and register masking of a step's foreign tokens; the MFMA's scales are 2^0 and the two rowwise reciprocal scales
-// meet the fp32 sum in the epilogue (epilogue8<false>, quant_math.h).  Any offsets; an empty group runs no step and stores zeros.
+// The weight-gradient frame (wgrad_frame.h) with nothing per k step: the MFMA's scales are 2^0 and the two rowwise reciprocal scales of
+// the expert meet the fp32 sum in the epilogue (epilogue8<false>, quant_math.h).  Any offsets.
 struct Fp8WgradArgs {
   const uint8_t* g;    // e4m3 [N][M]
   const float* g_inv;  // [E][N]
@@ -198,80 +163,36 @@ struct Fp8WgradArgs {
   int M, N, K;
 };
 
-__global__ __launch_bounds__(256) void fp8_wgrad_kernel(Fp8WgradArgs p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, kq = lane >> 4;
-  const int e = blockIdx.z;
-  const int n0 = blockIdx.y * 128, k0 = blockIdx.x * 128;
-  const int wn = (wave >> 1) * 64, wk = (wave & 1) * 64;
-  // the group's tokens, clamped to the matrix; a range that runs backwards is an empty group
-  const int start = p.offs != nullptr ? min(max(e > 0 ? p.offs[e - 1] : 0, 0), p.M) : 0;
-  const int end = p.offs != nullptr ? min(max(p.offs[e], 0), p.M) : p.M;
-  const int s0 = start >> 7, s1 = end > start ? (end + 127) >> 7 : s0;
-  // rows past the matrix fall outside the buffer's range and read as zero
-  const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc((void*)p.g, 0, p.N * p.M, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.K * p.M, 0x00020000);
-  f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  if (s0 < s1) wgrad_issue(rg, rx, smem + (s0 & 1) * kStage, n0, k0, s0, p.M, p.N, p.K, wave, lane);
-  for (int step = s0; step < s1; ++step) {
-    char* cur = smem + (step & 1) * kStage;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();  // stage `step` has landed for every wave; every wave is done with the other stage
-    if (step + 1 < s1) wgrad_issue(rg, rx, smem + ((step + 1) & 1) * kStage, n0, k0, step + 1, p.M, p.N, p.K, wave, lane);
-    // a step that reaches outside the group: the lane's two 16-token pieces keep the group's own tokens only
-    const bool edge = step * 128 < start || step * 128 + 128 > end;  // wave-uniform
-    u32x4 mk0, mk1;
-    if (edge) {
-      mk0 = token_mask(step * 128 + 16 * kq, start, end);
-      mk1 = token_mask(step * 128 + 64 + 16 * kq, start, end);
-    }
-    u32x4 xf0[4], xf1[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) wgrad_frag(cur + kOpBytes, wk + 16 * j + (lane & 15), kq, xf0[j], xf1[j]);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      u32x4 g0, g1;
-      wgrad_frag(cur, wn + 16 * i + (lane & 15), kq, g0, g1);
-      if (edge) {
-        g0 &= mk0;
-        g1 &= mk1;
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = mfma8_k128<false, AO_MX_FMT_E4M3>(g0, g1, xf0[j], xf1[j], acc[i][j]);
-    }
+struct RowwisePolicy {
+  struct Scales {};
+  const Fp8WgradArgs& p;
+  const float *gi, *xi;  // the expert's reciprocals
+  __device__ __forceinline__ RowwisePolicy(const Fp8WgradArgs& p, const Lane&, int e)
+      : p(p), gi(p.g_inv + (size_t)e * p.N), xi(p.x_inv + (size_t)e * p.K) {}
+  __device__ __forceinline__ void load(int, Scales&) const {}
+  __device__ __forceinline__ f32x4 mac(f32x4 acc, u32x4 g0, u32x4 g1, u32x4 x0, u32x4 x1, const Scales&, int, int) const {
+    return mfma8_k128<false, AO_MX_FMT_E4M3>(g0, g1, x0, x1, acc);
   }
-  uint16_t* out = p.out + (size_t)e * p.N * p.K;
-  const float* gi = p.g_inv + (size_t)e * p.N;
-  const float* xi = p.x_inv + (size_t)e * p.K;
-  // the lane's 16 row scales first: a store to out may alias g_inv for all the compiler knows, and would have it load them again
-  float sg[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int n = n0 + wn + 16 * i + 4 * kq + r;
-      sg[i][r] = n < p.N ? gi[n] : 0.f;
-    }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int k = k0 + wk + 16 * j + (lane & 15);
-    if (k >= p.K) continue;
-    const float sx = xi[k];
+  __device__ __forceinline__ void store(uint16_t* out, const f32x4 (&acc)[4][4], const Lane& t) const {
+    // the lane's 16 row scales first: a store to out may alias g_inv for all the compiler knows, and would have it load them again
+    float sg[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int n = n0 + wn + 16 * i + 4 * kq + r;
-        if (n < p.N) out[(size_t)n * p.K + k] = f32_to_bf16_bits(epilogue8<false>(acc[i][j][r], sg[i][r], sx));
+        const int n = t.nrow() + 16 * i + r;
+        sg[i][r] = n < p.N ? gi[n] : 0.f;
       }
+    float sx[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) sx[j] = t.kcol() + 16 * j < p.K ? xi[t.kcol() + 16 * j] : 0.f;
+    wgrad_store<true>(out, t, p.N, p.K, [&](int i, int j, int r, int, int) { return epilogue8<false>(acc[i][j][r], sg[i][r], sx[j]); });
   }
-}
+};
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+__global__ __launch_bounds__(256) void fp8_wgrad_kernel(Fp8WgradArgs p) {
+  wgrad_tile<RowwisePolicy>(p);
+}
 
 constexpr int64_t kMaxGroups = 65535;  // the wgrad grid's z extent; the casts' binary search has no limit of its own
 
@@ -319,32 +240,12 @@ extern "C" int ao_fp8_train_quantize_colwise_t_3d(const uint16_t* w, uint8_t* q_
 
 extern "C" int ao_fp8_grouped_mm_wgrad(const uint8_t* g_t, const float* g_inv, const uint8_t* x_t, const float* x_inv, const int32_t* offs,
                                        uint16_t* out, int64_t M_total, int64_t N, int64_t K, int64_t E, void* stream) {
-  AO_REQUIRE(M_total >= 0 && N > 0 && K > 0 && E > 0, "%s: bad shape M_total=%lld N=%lld K=%lld E=%lld", __func__, (long long)M_total,
-             (long long)N, (long long)K, (long long)E);
-  AO_REQUIRE(M_total % 16 == 0, "%s: M_total=%lld must be a multiple of 16", __func__, (long long)M_total);
-  AO_REQUIRE(N % 16 == 0, "%s: N=%lld must be a multiple of 16", __func__, (long long)N);
-  AO_REQUIRE(K % 16 == 0, "%s: K=%lld must be a multiple of 16", __func__, (long long)K);
-  AO_REQUIRE(E <= kMaxGroups, "%s: E=%lld must be at most %lld (the grid's z extent)", __func__, (long long)E, (long long)kMaxGroups);
-  AO_REQUIRE(offs != nullptr || E == 1, "%s: without offs there is one group of every token, got E=%lld", __func__, (long long)E);
-  AO_REQUIRE(M_total < (1ll << 31) && N < (1ll << 31) && K < (1ll << 31) && N * M_total < (1ll << 31) && K * M_total < (1ll << 31),
-             "%s: M_total=%lld N=%lld K=%lld: the sizes and both operands' byte counts must be below 2^31", __func__, (long long)M_total,
-             (long long)N, (long long)K);
-  AO_REQUIRE_PTR(out);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (M_total == 0) {
-    const hipError_t rc = hipMemsetAsync(out, 0, (size_t)E * N * K * sizeof(uint16_t), st);
-    if (rc != hipSuccess) return hip_failed(rc, "hipMemsetAsync(fp8_wgrad)");
-    return AO_OK;
-  }
-  AO_REQUIRE_PTR(g_t);
+  bool launch;
+  if (int rc = check_entry(Entry{__func__, "M_total", 16, 16, true}, g_t, x_t, offs, out, M_total, N, K, E, st, &launch)) return rc;
+  if (!launch) return AO_OK;
   AO_REQUIRE_PTR(g_inv);
-  AO_REQUIRE_PTR(x_t);
   AO_REQUIRE_PTR(x_inv);
-  AO_REQUIRE(aligned16(g_t) && aligned16(x_t), "%s: the codes must be 16-byte aligned", __func__);
-  constexpr size_t smem = 2 * kStage;
-  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(fp8_wgrad_kernel), smem, "hipFuncSetAttribute(fp8_wgrad_kernel)")) return rc;
   const Fp8WgradArgs args{g_t, g_inv, x_t, x_inv, offs, out, (int)M_total, (int)N, (int)K};
-  ao::launch(fp8_wgrad_kernel, dim3((unsigned)((K + 127) / 128), (unsigned)((N + 127) / 128), (unsigned)E), dim3(256), smem, st, args);
-  AO_LAUNCH_CHECK("fp8_wgrad_kernel launch");
-  return AO_OK;
+  return launch_frame(fp8_wgrad_kernel, "fp8_wgrad_kernel", args, N, K, E, st);
 }

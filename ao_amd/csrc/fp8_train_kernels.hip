@@ -8,13 +8,8 @@
 //   1/s   : float8/float8_ops.py:44-45 (the GEMM takes scale.reciprocal())
 //
 // Two passes over x serve any set of directions: ao_fp8_train_amax reads x once for the row and / or column maxima, ao_fp8_train_cast
-// reads it once more and writes the row-major codes and / or the transposed ones.  Both walk 128 x 128 tiles with the same register
-// layout: a lane holds 4 consecutive rows x 8 adjacent columns (four 16-byte loads), the 16 lanes of a DPP row span the tile's 128
-// columns, the four DPP rows of a wave and the four waves stack 16-row slabs, two steps cover the 128 rows.  So
-//   * a row's 8 codes leave as one 8-byte store, 128 contiguous bytes per DPP row;
-//   * a column's 4 codes of a lane are one cvt4_e4m3 dword, staged in LDS (column stride 132 B: 2-way bank conflicts on the write,
-//     like mxfp8_quant_colwise_kernel) and read back so that every column leaves as one 128-byte run of the transposed output;
-//   * the row amax is a DPP reduction over 16 lanes, the column amax two shuffles and one LDS step across the waves.
+// reads it once more and writes the row-major codes and / or the transposed ones.  Both walk 128 x 128 tiles with the register layout
+// and the helpers of fp8_train_tile.h.
 // Tile edges: C % 8 == 0 keeps a lane's 8 columns inside together; rows are checked one by one; the transposed output needs
 // R % 16 == 0 (its 16-byte pieces, and the K of the GEMM that reads it).
 #include "common.h"
@@ -24,7 +19,7 @@
 namespace ao {
 namespace {
 
-using namespace fp8_train_tile;  // kThreads, kTile, kTileLds, tile_row, unpack8
+using namespace fp8_train_tile;  // the constants and the helpers of the tile walk
 
 // ---- amax: one read of x; partial maxima of a tile merge into the zeroed outputs by an unsigned atomic max (non-negative fp32 order
 // like their bit patterns), so the result does not depend on the order the tiles arrive in ------------------------------------------------
@@ -35,13 +30,7 @@ __global__ __launch_bounds__(kThreads) void fp8_train_amax_kernel(const uint16_t
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ci = lane & 15, g = lane >> 4;
   const int64_t r0 = (int64_t)blockIdx.y * kTile, c = (int64_t)blockIdx.x * kTile + 8 * ci;
   u32x4 v[2][4];
-#pragma unroll
-  for (int step = 0; step < 2; ++step)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int64_t r = r0 + tile_row(step, wave, g) + k;
-      v[step][k] = (r < R && c < C) ? *reinterpret_cast<const u32x4*>(x + r * C + c) : u32x4{0u, 0u, 0u, 0u};
-    }
+  load_tile<true>(x, r0, c, R, C, wave, g, v);
   float cm[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int step = 0; step < 2; ++step)
@@ -63,15 +52,7 @@ __global__ __launch_bounds__(kThreads) void fp8_train_amax_kernel(const uint16_t
       }
     }
   if (COLS) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      cm[j] = fmaxf(cm[j], __shfl_xor(cm[j], 16));
-      cm[j] = fmaxf(cm[j], __shfl_xor(cm[j], 32));
-    }
-    if (g == 0) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) cred[wave][8 * ci + j] = cm[j];
-    }
+    reduce_cols(cm, cred[wave], ci, g);
     __syncthreads();
     const int64_t gc = (int64_t)blockIdx.x * kTile + threadIdx.x;
     if (threadIdx.x < kTile && gc < C) {
@@ -92,18 +73,12 @@ __global__ __launch_bounds__(kThreads) void fp8_train_cast_kernel(const uint16_t
                                                                   float* __restrict__ s_row, float* __restrict__ inv_s_row,
                                                                   uint8_t* __restrict__ q_col_t, float* __restrict__ s_col,
                                                                   float* __restrict__ inv_s_col, int64_t R, int64_t C) {
-  __shared__ __attribute__((aligned(16))) uint8_t tile[COLS ? kTile * kTileLds : 16];
+  __shared__ __attribute__((aligned(16))) uint8_t tile[COLS ? kTileLdsBytes : 16];
   __shared__ float rs[kTile], cs[kTile];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ci = lane & 15, g = lane >> 4;
   const int64_t r0 = (int64_t)blockIdx.y * kTile, c0 = (int64_t)blockIdx.x * kTile, c = c0 + 8 * ci;
   u32x4 v[2][4];
-#pragma unroll
-  for (int step = 0; step < 2; ++step)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int64_t r = r0 + tile_row(step, wave, g) + k;
-      v[step][k] = (r < R && c < C) ? *reinterpret_cast<const u32x4*>(x + r * C + c) : u32x4{0u, 0u, 0u, 0u};
-    }
+  load_tile<true>(x, r0, c, R, C, wave, g, v);
   if (threadIdx.x < kTile) {
     if (COLS) {
       const int64_t gc = c0 + threadIdx.x;
@@ -146,27 +121,11 @@ __global__ __launch_bounds__(kThreads) void fp8_train_cast_kernel(const uint16_t
         if (r < R && c < C) *reinterpret_cast<u32x2*>(q_row + r * C + c) = fp8_train_quant8(v[step][k], rs[lr + k]);
       }
     }
-    if (COLS) {
-      float f[4][8];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) unpack8(v[step][k], f[k]);
-#pragma unroll
-      for (int j = 0; j < 8; ++j)  // rows lr .. lr + 3 of column 8 ci + j: one dword (lr % 4 == 0, 132 % 4 == 0)
-        *reinterpret_cast<uint32_t*>(tile + (8 * ci + j) * kTileLds + lr) =
-            cvt4_e4m3(fp8_train_q(f[0][j], sc[j]), fp8_train_q(f[1][j], sc[j]), fp8_train_q(f[2][j], sc[j]), fp8_train_q(f[3][j], sc[j]));
-    }
+    if (COLS) stage_cols_t(tile, v[step], sc, ci, lr);
   }
   if (COLS) {
     __syncthreads();
-    // 128 columns x 8 pieces of 16 bytes (= 16 rows each); R % 16 == 0: a piece that starts inside the matrix lies inside
-    for (int p = threadIdx.x; p < kTile * 8; p += kThreads) {
-      const int col = p >> 3, part = p & 7;
-      const int64_t gc = c0 + col, gr = r0 + part * 16;
-      if (gc < C && gr < R) {
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(tile + col * kTileLds + part * 16);
-        *reinterpret_cast<u32x4*>(q_col_t + gc * R + gr) = u32x4{src[0], src[1], src[2], src[3]};
-      }
-    }
+    flush_cols_t<true>(tile, c0, r0, C, R, [&](int64_t gc, int64_t gr) { return q_col_t + gc * R + gr; });
   }
 }
 

@@ -154,3 +154,18 @@ def test_kernel_sources_leave_the_8bit_epilogue_to_quant_math():
     csrc = os.path.join(ROOT, "ao_amd", "csrc")
     offenders = sorted(f for f in os.listdir(csrc) if f.endswith(".hip") and "mul_f32_rn(" in open(os.path.join(csrc, f)).read())
     assert not offenders, f"call epilogue8 / int8_out (quant_math.h) instead of mul_f32_rn in: {', '.join(offenders)}"
+
+
+def test_kernel_sources_leave_the_wgrad_frame_and_the_cast_tile_walk_to_their_headers():
+    """The weight-gradient GEMM's stages, loop and masks have one definition (wgrad_frame.h: wgrad_tile), and so has the transposed staging
+    of the casts' 128 x 128 tile (fp8_train_tile.h: stage_cols_t, flush_cols_t).  A kernel source that issues a stage, builds a token
+    mask or indexes the 132-byte-stride tile itself is restating them: a new recipe is a policy of the frame, a new cast calls the helpers."""
+    csrc = os.path.join(ROOT, "ao_amd", "csrc")
+    sources = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith(".hip")}
+    assert "wgrad_issue(" in open(os.path.join(csrc, "wgrad_frame.h")).read()  # (the names this test looks for are the headers')
+    assert "* kTileLds" in open(os.path.join(csrc, "fp8_train_tile.h")).read()
+    for needle, instead in (("wgrad_issue(", "wgrad_tile (wgrad_frame.h)"), ("token_mask(", "wgrad_tile (wgrad_frame.h)")):
+        offenders = [f for f, text in sources.items() if needle in text]
+        assert not offenders, f"call {instead} instead of {needle}...) in: {', '.join(offenders)}"
+    offenders = [f for f, text in sources.items() if re.search(r"\bkTileLds\b", text)]
+    assert not offenders, f"call stage_cols_t / flush_cols_t (fp8_train_tile.h) instead of indexing the staged tile in: {', '.join(offenders)}"
