@@ -78,6 +78,10 @@ int ensure_dynamic_lds(const void* kernel, size_t bytes, const char* what) {
 // and all, changes owner).  Allocation, growth and eviction cannot happen inside stream capture (hipMalloc / synchronise are
 // illegal there): run the op once on the stream, outside capture, with the largest shape first.  A graph captured on a stream
 // whose slot is later evicted must be re-captured (its launches would share the buffer with the new owner).
+// The mutex covers the table, not the caller's launch: with more than kSplitSlots split-K streams driven from SEVERAL host
+// threads an eviction on one thread can hand over a slot whose owner, on another thread, holds the pointers and has not
+// launched yet (INTEGRATION.md section 3 says what such a process must do; one thread, or up to kSplitSlots streams, cannot
+// meet it).
 namespace {
 struct SplitWs {
   hipStream_t stream = nullptr;
@@ -164,6 +168,30 @@ extern "C" int ao_splitk_reserve(void* stream, int64_t bytes) {
   float* part = nullptr;
   unsigned* tickets = nullptr;
   return splitk_workspace((hipStream_t)stream, &part, &tickets, floats, 1);
+}
+
+// What the table holds for `stream` on the current device, read under the table's mutex: allocates nothing, launches nothing,
+// and does not count as a use (the slot's place in the eviction order stays).  out[0] 1 if the stream holds a slot, [1] the
+// capacity of its parts area in bytes, [2] the slot's base address, [3] the retired buffers of the process.
+extern "C" int ao_splitk_query(void* stream, int64_t out[4]) {
+  using namespace ao;
+  AO_REQUIRE_PTR(out);
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return hip_failed(e, "hipGetDevice");
+  AO_REQUIRE(dev >= 0 && dev < 64, "device index %d out of range", dev);
+  std::lock_guard<std::mutex> lock(g_split_mu);
+  out[0] = out[1] = out[2] = 0;
+  for (int i = 0; i < kSplitSlots; ++i) {
+    const SplitWs& w = g_split_ws[dev][i];
+    if (!w.used || w.stream != (hipStream_t)stream) continue;
+    out[0] = 1;
+    out[1] = (int64_t)(w.floats * sizeof(float));
+    out[2] = (int64_t)reinterpret_cast<uintptr_t>(w.base);
+    break;
+  }
+  out[3] = (int64_t)g_split_retired.size();
+  return AO_OK;
 }
 
 namespace ao {

@@ -7,9 +7,9 @@ namespace ao {
 // Workspace: one per (device, stream); at most kSplitSlots streams per device hold one at a time (a further stream evicts the least
 // recently used slot after a device synchronise); sized on demand (8 MiB steps of two) up to kSplitSlotFloats fp32 of parked partial tiles
 // (kSplitMaxTiles tiles of 128 x 128; smaller tiles pack more of them) + kSplitMaxTickets tickets, one per output tile -- the
-// smallest tile a kernel parks is 64 x 16, two parts at least, so 4096 tickets cover every launch the float budget admits only
-// if the budget stays <= 4096 * 2 * 1024 floats; launchers check both.  Allocated on the first split-K launch on a stream
-// (outside stream capture); runtime.hip.
+// smallest tile a kernel parks is 64 x 16, two parts at least, so the 16384 tickets cover every launch the float budget admits
+// only if the budget stays <= 16384 * 2 * 1024 floats (kSplitSlotFloats is exactly that); launchers check both.  Allocated on the
+// first split-K launch on a stream (outside stream capture); runtime.hip.
 constexpr int kSplitSlots = 8;
 constexpr int kSplitMaxTiles = 2048;
 constexpr int kSplitMaxTickets = 16384;

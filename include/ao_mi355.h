@@ -56,6 +56,11 @@ const char* ao_last_error(void);
  * cuBLAS, which pre-allocate theirs per handle the same way (ATen's cublas workspace, CUDABlas / CublasHandlePool). */
 int ao_splitk_reserve(void* stream, int64_t bytes);
 
+/* Read-only view of the scratch buffer `stream` holds on the current device: allocates nothing, launches nothing and does not count as a use
+ * of the buffer.  out_host[0] = 1 if the stream holds one (else 0), [1] = the capacity of its partial-tile area in bytes, [2] = its base
+ * address (both 0 if none), [3] = the number of outgrown buffers the process keeps alive for graphs captured before a growth. */
+int ao_splitk_query(void* stream, int64_t out_host[4]);
+
 /* Per-launch kernel timing for benchmarks: after ao_prof_enable(n) the next n
  * kernel launches of this library are bracketed with HIP extension events that
  * timestamp the dispatch itself (begin/end of the kernel, no launch gaps).

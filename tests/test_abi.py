@@ -52,6 +52,25 @@ def test_empty_m_is_ok_without_gpu():
     assert lib.ao_int4_weight_int4pack_mm(None, one, one, None, 0, 16, 128, 128, None) == _lib.AO_OK
 
 
+def test_splitk_query_reports_instead_of_crashing():
+    """ao_splitk_query validates on the host: a null `out` is the null-pointer code; without a GPU the failed device lookup is the
+    library's AO_ERR_HIP with the HIP call named, and on a GPU a stream that never ran a split-K shape holds nothing."""
+    import torch
+
+    lib = _lib.lib()
+    assert lib.ao_splitk_query(None, None) == _lib.AO_ERR_NULL_POINTER
+    assert "null pointer" in _lib.last_error()
+    out = (ctypes.c_int64 * 4)(-1, -1, -1, -1)
+    rc = lib.ao_splitk_query(ctypes.c_void_p(16), out)  # the stream is only compared, never dereferenced
+    if not torch.cuda.is_available():
+        assert rc == _lib.AO_ERR_HIP
+        assert "hipGetDevice" in _lib.last_error()
+        with pytest.raises(RuntimeError):
+            _lib.check(rc)
+    else:
+        assert rc == _lib.AO_OK and list(out)[:3] == [0, 0, 0] and out[3] >= 0
+
+
 def test_ops_library_loads_and_registers_without_a_gpu():
     """ao_amd/_C_mi355_ops.so (C++ TORCH_LIBRARY_IMPL registrations, csrc_torch/binding.cpp) loads through
     torch.ops.load_library on a machine without a GPU and registers CUDA-key kernels under the reference's op names;

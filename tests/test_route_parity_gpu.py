@@ -261,7 +261,7 @@ class Run:
         self.ref.update(ref64=A @ B.T + self._bias64(), S=A.abs() @ B.abs().T + abs(self._bias64()), K=K, equal=EQUAL_MX[fmt],
                         k_floor=K_FLOOR_MX[fmt])
 
-    def launch(self, buf):
+    def launch(self, buf, sync=True):
         lib = _lib.lib()
         fam, entry, M, N, K, G = self.case[:6]
         s = torch.cuda.current_stream().cuda_stream
@@ -289,7 +289,8 @@ class Run:
         else:
             rc_ = lib.ao_fp8_int4_linear(_ptr(self.a), _ptr(self.sa), _ptr(self.qdata), _ptr(self.sz), _ptr(self.bias_arg), y, M, N, K, G, s)
         _lib.check(rc_)
-        torch.cuda.synchronize()
+        if sync:
+            torch.cuda.synchronize()
 
 
 # the smallest split-K case of each family: launched between the two launches of a split-K case

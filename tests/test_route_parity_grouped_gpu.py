@@ -95,7 +95,7 @@ class GRun:
     def buffers(self):
         return [_parity.Guarded(self.case.M, self.case.N, torch.bfloat16, self.dev) for _ in self.refs]
 
-    def launch(self, bufs):
+    def launch(self, bufs, sync=True):
         lib = _lib.lib()
         _, entry, M, N, K, E, _, _, mode = self.case
         s = torch.cuda.current_stream().cuda_stream
@@ -112,7 +112,8 @@ class GRun:
         else:
             rc_ = lib.ao_mxfp8_grouped_mm_pair(_ptr(self.a), _ptr(self.sa_arg), b[0], sb[0], b[1], sb[1], offs, y[0], y[1], M, N, K, E, s)
         _lib.check(rc_)
-        torch.cuda.synchronize()
+        if sync:
+            torch.cuda.synchronize()
 
     def check(self, bufs, route=None):
         for i, (buf, kw) in enumerate(zip(bufs, self.refs)):
