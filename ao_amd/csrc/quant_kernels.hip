@@ -551,10 +551,10 @@ extern "C" int ao_int8_quantize_static(const uint16_t* x, const float* scale, co
 
 extern "C" int ao_int8_row_sums(const int8_t* q, int32_t* sums, int64_t N, int64_t K, void* stream) {
   if (int rc = check_rows(__func__, N, K, 16)) return rc;
+  AO_REQUIRE(K <= (1ll << 24), "%s: K=%lld too large for an int32 row sum", __func__, (long long)K);
   if (N == 0) return AO_OK;
   AO_REQUIRE_PTR(q);
   AO_REQUIRE_PTR(sums);
-  AO_REQUIRE(K <= (1ll << 24), "%s: K=%lld too large for an int32 row sum", __func__, (long long)K);
   ao::launch(int8_row_sums_kernel, dim3((unsigned)((N + 3) / 4)), dim3(kThreads), 0, (hipStream_t)stream, q, sums, N, K);
   AO_LAUNCH_CHECK("int8_row_sums_kernel launch");
   return AO_OK;

@@ -418,9 +418,11 @@ def _strided_rows(name, x):
     if x.shape[1] % 8 != 0:
         raise ValueError(f"{name}: K={x.shape[1]} must be a multiple of 8")
     ok = x.stride(1) == 1 and x.stride(0) >= x.shape[1] and x.stride(0) % 8 == 0 and x.data_ptr() % 16 == 0
-    if not ok and x.shape[0] > 0:
+    if not ok:
         x = x.contiguous()
-    return x, (x.stride(0) if x.shape[0] > 1 else max(x.shape[1], x.stride(0)))
+        if x.data_ptr() % 16 != 0:  # a single row is "contiguous" wherever it starts
+            x = x.clone()
+    return x, (x.stride(0) if x.shape[0] > 1 else x.shape[1])  # (the stride of at most one row is never used)
 
 
 def rowwise_amax(x: torch.Tensor) -> torch.Tensor:
@@ -1291,13 +1293,16 @@ def _rows_u8(t):
 
 
 def gather_rows(x, indices, num_out=None):
-    """out[i] = x[indices[i]] for 0 <= indices[i] < rows(x), zeros otherwise (`vstack(x, 0)[indices]`, ep/permute.py:86-96)."""
-    dev = _require_gpu("gather_rows", x, indices)
+    """out[i] = x[indices[i]] for 0 <= indices[i] < rows(x), zeros otherwise (`vstack(x, 0)[indices]`, ep/permute.py:86-96).
+    `num_out` (at most the number of indices): only the first num_out output rows."""
     if x.dim() != 2 or indices.dim() != 1 or indices.dtype != torch.int32:
         raise ValueError("gather_rows: expected a 2-D tensor and int32 1-D indices")
+    n_out = indices.numel() if num_out is None else int(num_out)
+    if n_out < 0 or n_out > indices.numel():  # the kernel reads one index per output row
+        raise ValueError(f"gather_rows: num_out={n_out} must be in [0, {indices.numel()}], the number of indices")
+    dev = _require_gpu("gather_rows", x, indices)
     x, rows, row_bytes = _rows_u8(x)
     indices = indices.contiguous()
-    n_out = indices.numel() if num_out is None else num_out
     out = torch.empty((n_out, x.shape[1]), dtype=x.dtype, device=dev)
     with _on(dev):
         _lib.check(_lib.lib().ao_moe_gather_rows(_ptr(x), _ptr(indices), _ptr(out), rows, n_out, row_bytes, _stream()))

@@ -47,8 +47,9 @@ def int_mm(a, b_t):
     return a.astype(np.int32) @ b_t.astype(np.int32).T
 
 
-def scaled_mm(xq, x_scale, wq, w_scale, bias=None):
-    """The Int8Tensor linear epilogue on the GPU path.
+def scale_epilogue(c_int32, x_scale, w_scale, bias=None):
+    """The Int8Tensor linear's arithmetic after int_mm, from a given int32 accumulator [M,N] (what a K-sharded linear applies to the
+    summed accumulators of its ranks).
 
     int8_tensor.py:305-359 + int8/kernels.py:143-144, activation dtype bf16:
         t = bf16( f32(c_int32) * x_scale[m] )      (_int_scaled_matmul(...).to(bf16))
@@ -56,12 +57,17 @@ def scaled_mm(xq, x_scale, wq, w_scale, bias=None):
         y = y + bias                               (fp32 += bf16)
         return bf16(y)
     """
-    c = int_mm(xq, wq).astype(np.float32)  # int32 -> fp32 (RNE above 2^24, like torch)
+    c = np.asarray(c_int32, dtype=np.int32).astype(np.float32)  # int32 -> fp32 (RNE above 2^24, like torch)
     t = bf16.bf16_round(c * np.asarray(x_scale, np.float32)[:, None])
     y = t * np.asarray(w_scale, np.float32)[None, :]
     if bias is not None:
         y = y + np.asarray(bias, np.float32)[None, :]
     return bf16.bf16_round(y.astype(np.float32))
+
+
+def scaled_mm(xq, x_scale, wq, w_scale, bias=None):
+    """The Int8Tensor linear epilogue on the GPU path: scale_epilogue of int_mm(xq, wq)."""
+    return scale_epilogue(int_mm(xq, wq), x_scale, w_scale, bias)
 
 
 def linear(x, w, bias=None):
@@ -105,22 +111,28 @@ def quantize_rowwise_asym(x):
     return q, scale, zp.astype(np.int8)
 
 
-def scaled_mm_asym(xq, x_scale, x_zp, wq, w_scale, bias=None):
-    """The Int8Tensor linear with an asymmetric activation (int8_tensor.py:305-346):
+def scale_epilogue_asym(c_int32, x_scale, x_zp, w_row_sums, w_scale, bias=None):
+    """The Int8Tensor linear with an asymmetric activation after int_mm (int8_tensor.py:305-346), from a given int32 accumulator [M,N]
+    and the weight's row sums [N]:
         t    = bf16( f32(c_int32) * x_scale[m] )
         corr = bf16( (f32(zp[m]) * x_scale[m]) * f32(rowsum(wq)[n]) )
         t    = bf16( t - corr )
         y    = bf16( f32(t) * w_scale[n] (+ bias) )"""
-    c = int_mm(xq, wq).astype(np.float32)
+    c = np.asarray(c_int32, dtype=np.int32).astype(np.float32)
     xs = np.asarray(x_scale, np.float32)[:, None]
     t = bf16.bf16_round(c * xs)
-    wsum = wq.astype(np.int64).sum(axis=1).astype(np.float32)[None, :]
+    wsum = np.asarray(w_row_sums).astype(np.float32)[None, :]
     corr = bf16.bf16_round((np.asarray(x_zp, np.float32)[:, None] * xs).astype(np.float32) * wsum)
     t = bf16.bf16_round(t - corr)
     y = t * np.asarray(w_scale, np.float32)[None, :]
     if bias is not None:
         y = y + np.asarray(bias, np.float32)[None, :]
     return bf16.bf16_round(y.astype(np.float32))
+
+
+def scaled_mm_asym(xq, x_scale, x_zp, wq, w_scale, bias=None):
+    """scale_epilogue_asym of int_mm(xq, wq) and the int64 row sums of wq."""
+    return scale_epilogue_asym(int_mm(xq, wq), x_scale, x_zp, wq.astype(np.int64).sum(axis=1), w_scale, bias)
 
 
 def linear_asym(x, w, bias=None):

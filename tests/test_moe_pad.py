@@ -193,6 +193,108 @@ def test_permute_kernels_match_oracle_and_fixtures():
         assert np.array_equal(back, x_np)
 
 
+# ---- the row copies through the C ABI: every vector width, the seam of the four-in-flight loop, misaligned bases --------------------------
+ROWS_T, ROWS_L = 37, 53
+GUARD = 0xA5
+
+
+class _Bytes:
+    """`n` bytes on the device inside a larger allocation: 256 bytes before and 4352 after (a vector of the widest row past its end
+    included), the first byte `shift` bytes past a 16-byte boundary.  Filled with `data` (numpy uint8) or, an output, with the guard byte."""
+
+    def __init__(self, n, shift=0, data=None):
+        self.n = n
+        raw = torch.full((256 + 16 + n + 4352,), GUARD, dtype=torch.uint8, device="cuda")
+        self.lead = 256 + (-(raw.data_ptr() + 256) % 16) + shift
+        self.raw = raw
+        self.view = raw[self.lead:self.lead + n]
+        assert self.view.data_ptr() % 16 == shift
+        if data is not None:
+            self.view.copy_(torch.from_numpy(np.ascontiguousarray(data).reshape(-1)).cuda())
+        self.ptr = self.view.data_ptr()
+
+    def get(self):
+        raw = self.raw.cpu().numpy()
+        assert (raw[:self.lead] == GUARD).all(), "write before the output"
+        after = raw[self.lead + self.n:]
+        assert (after == GUARD).all(), "write %d bytes past the end of the output" % int(np.nonzero(after != GUARD)[0][0])
+        return raw[self.lead:self.lead + self.n].copy()
+
+
+def _row_indices(rng):
+    """53 indices over 37 rows: every row, 13 duplicates, and -1, T, T + 5 (the dummy row and past it), shuffled"""
+    idx = np.concatenate([np.arange(ROWS_T), rng.integers(0, ROWS_T, size=ROWS_L - ROWS_T - 3), [-1, ROWS_T, ROWS_T + 5]]).astype(np.int32)
+    rng.shuffle(idx)
+    assert idx.size == ROWS_L
+    return idx
+
+
+def _check_row_copies(width, in_shift=0, out_shift=0):
+    from ao_amd import _lib
+
+    lib, st = _lib.lib(), torch.cuda.current_stream().cuda_stream
+    T, L = ROWS_T, ROWS_L
+    rng = np.random.default_rng(width * 10 + in_shift + 2 * out_shift)
+    idx = _row_indices(rng)
+    real = (idx >= 0) & (idx < T)
+    idx_d = torch.from_numpy(idx).cuda()
+    table = rng.integers(0, 256, size=(T, width), dtype=np.uint8)
+    # gather: out[i] = table[idx[i]], a zero row for -1, T and T + 5
+    src, out = _Bytes(T * width, in_shift, table), _Bytes(L * width, out_shift)
+    _lib.check(lib.ao_moe_gather_rows(src.ptr, idx_d.data_ptr(), out.ptr, T, L, width, st))
+    torch.cuda.synchronize()
+    want = M.gather_rows(table, np.where(real, idx, -1))
+    assert not want[~real].any()
+    got = out.get().reshape(L, width)
+    assert np.array_equal(got, want), ("gather", width, np.argwhere(got != want)[:4])
+    # scatter: out[idx[i]] = payload[i]; duplicates carry the same payload, so the last write is any of them; rows 5 and 20 are named by
+    # nobody in the second run and keep the guard byte, as the indices -1, T and T + 5 write nothing anywhere
+    for dropped in ((), (5, 20)):
+        idx2 = np.where(np.isin(idx, dropped), -1, idx).astype(np.int32)
+        real2 = (idx2 >= 0) & (idx2 < T)
+        payload = rng.integers(0, 256, size=(L, width), dtype=np.uint8)
+        payload[real2] = table[idx2[real2]]
+        src, out = _Bytes(L * width, in_shift, payload), _Bytes(T * width, out_shift)
+        _lib.check(lib.ao_moe_scatter_rows(src.ptr, torch.from_numpy(idx2).cuda().data_ptr(), out.ptr, L, T, width, st))
+        torch.cuda.synchronize()
+        want = table.copy()
+        want[np.array(dropped, dtype=np.int64)] = GUARD
+        got = out.get().reshape(T, width)
+        assert np.array_equal(got, want), ("scatter", width, dropped, np.argwhere(got != want)[:4])
+
+
+# 1-byte lanes: 1; 2-byte: 2, 6; 4-byte: 12, 36; 16-byte: 48 and, around the hand-over of the four-in-flight loop (lane + 192 < nvec) to its
+# tail, 255, 256, 257 and 511 vectors
+@pytest.mark.gpu
+@pytest.mark.parametrize("width", [1, 2, 6, 12, 36, 48, 16 * 255, 16 * 256, 16 * 257, 16 * 511])
+def test_row_copies_at_every_vector_width_and_the_loop_seam(width):
+    _check_row_copies(width)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("in_shift,out_shift", [(4, 0), (0, 4)])
+def test_row_copies_from_and_to_a_base_that_is_not_16_byte_aligned(in_shift, out_shift):
+    """48-byte rows would go 16 bytes a lane; a base 4 bytes past a 16-byte boundary has to take them 4 bytes a lane, same bytes."""
+    _check_row_copies(48, in_shift, out_shift)
+
+
+@pytest.mark.gpu
+def test_gather_rows_returns_the_first_num_out_rows():
+    from ao_amd import ops
+
+    rng = np.random.default_rng(3)
+    idx = _row_indices(rng)
+    table = rng.integers(0, 256, size=(ROWS_T, 36), dtype=np.uint8)
+    want = M.gather_rows(table, np.where((idx >= 0) & (idx < ROWS_T), idx, -1))
+    x, idx_d = torch.from_numpy(table).cuda(), torch.from_numpy(idx).cuda()
+    for num_out in (None, ROWS_L, 20, 1, 0):
+        got = ops.gather_rows(x, idx_d, num_out)
+        n = ROWS_L if num_out is None else num_out
+        assert tuple(got.shape) == (n, 36) and np.array_equal(got.cpu().numpy(), want[:n])
+    with pytest.raises(ValueError, match=r"num_out=54 must be in \[0, 53\]"):
+        ops.gather_rows(x, idx_d, ROWS_L + 1)
+
+
 # ---- the 128 x 4 blocked layout of the E8M0 scales (torchao::mx_block_rearrange_2d_M_groups / to_blocked) --------------------------------
 TB_CASES = ["one_block", "ragged", "wide", "tiny", "k4096"]
 MG_CASES = ["groups", "single", "aligned", "k224"]
