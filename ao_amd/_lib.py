@@ -35,6 +35,9 @@ _SIGNATURES = {
     "ao_int4_convert_weight_to_int4pack": [_P, _P, _I64, _I64, _INT, _P],
     "ao_int4_unpack_int4pack": [_P, _P, _I64, _I64, _INT, _P],
     "ao_int4_weight_int4pack_mm": [_P, _P, _P, _P, _I64, _I64, _I64, _INT, _P],
+    "ao_int4_weight_int4pack_mm_pair": [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _INT, _P],
+    "ao_int4_pair_independent": [_P, _P, _P, _P, _I64, _I64, _I64],
+    "ao_int4_pair_fusions": [],
     "ao_int4_dequantize": [_P, _P, _P, _I64, _I64, _INT, _P],
     "ao_int4_quantize_tinygemm": [_P, _P, _P, _I64, _I64, _INT, _P],
     "ao_int4_hqq_workspace_bytes": [_I64, _I64, _INT],

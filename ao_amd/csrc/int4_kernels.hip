@@ -171,13 +171,13 @@ struct XRegs {
 //   Nobody waits: the halves hold half a tile's work and meet while the whole tiles are still running.
 // STAMP (profiling, tuning modes 983 / 984): thread 0 of every workgroup writes 8 u64 behind the parked partials -- hardware id, the 100 MHz
 //   clock at entry and exit, the shader clock at entry / first weight block landed / wave 0 done with its blocks / exit.
-template <int G, int MAXM, int DEPTH, bool STRAIGHT = false, bool BAL = false, bool STAMP = false>
-__global__ __launch_bounds__((MAXM > 4) ? 512 : 1024) void int4_mm_kernel(
+// The body is a function of the workgroup's place in its problem's grid (bx of nbx along x), not of blockIdx.x: int4_mm_kernel runs it on
+// its one problem, int4_mm_pair_kernel on one of two (below).
+template <int G, int MAXM, int DEPTH, bool STRAIGHT, bool BAL, bool STAMP>
+__device__ __forceinline__ void int4_mm_body(
     const uint16_t* __restrict__ x, const u32x4* __restrict__ qdata,
-    const uint32_t* __restrict__ sz, uint16_t* __restrict__ y, int M, int N, int K, float* __restrict__ ws, unsigned* __restrict__ tickets) {
-  // (the two trailing arguments carried the M = 1 split-K workspace of round 3 and carry the balanced grid's now; the other builds leave them
-  // unused and the kernarg layout stays: removing them re-allocates the prologue's scalar registers, and every measurement of this kernel
-  // since round 3 was taken on this layout)
+    const uint32_t* __restrict__ sz, uint16_t* __restrict__ y, int M, int N, int K, float* __restrict__ ws, unsigned* __restrict__ tickets,
+    const unsigned bx, const unsigned nbx) {
   static_assert(!(BAL || STAMP) || (STRAIGHT && MAXM == 1 && DEPTH == 4), "the balanced grid and the stamps exist on the 8 x 4 straight-line form");
   unsigned long long stamp[6] = {0, 0, 0, 0, 0, 0};
   if constexpr (STAMP) { stamp[0] = __builtin_amdgcn_s_memrealtime(); stamp[2] = __builtin_amdgcn_s_memtime(); }
@@ -189,16 +189,16 @@ __global__ __launch_bounds__((MAXM > 4) ? 512 : 1024) void int4_mm_kernel(
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int nwaves = blockDim.x >> 6;
-  int ntile = blockIdx.x;
+  int ntile = (int)bx;
   int kwave = wave;        // the wave of a whole-tile workgroup whose blocks this wave runs
   int part = -1;           // BAL: 0 / 1 in a half-tile workgroup
-  const int halves = BAL ? 2 * ((int)gridDim.x - (N >> 4)) : 0;  // (the host launched T + r workgroups)
+  const int halves = BAL ? 2 * ((int)nbx - (N >> 4)) : 0;  // (the host launched T + r workgroups)
   if constexpr (BAL) {
     // (selects, not branches: what follows stays one basic block, as in the other builds)
-    const bool halved = (int)blockIdx.x < halves;
+    const bool halved = (int)bx < halves;
     if (halved && wave >= 4) return;  // before any barrier: the workgroup's barriers count its four live waves
-    part = halved ? (int)(blockIdx.x & 1) : -1;
-    ntile = halved ? (N >> 4) - (halves >> 1) + ((int)blockIdx.x >> 1) : (int)blockIdx.x - halves;
+    part = halved ? (int)(bx & 1) : -1;
+    ntile = halved ? (N >> 4) - (halves >> 1) + ((int)bx >> 1) : (int)bx - halves;
     kwave = wave + (halved ? 4 * part : 0);
   }
   const int m0 = blockIdx.y * 16;
@@ -386,7 +386,7 @@ __global__ __launch_bounds__((MAXM > 4) ? 512 : 1024) void int4_mm_kernel(
   auto write_stamps = [&] {
     if constexpr (STAMP) {
       if (tid == 0) {
-        unsigned long long* s = reinterpret_cast<unsigned long long*>(ws + (size_t)halves * 64) + (size_t)blockIdx.x * 8;
+        unsigned long long* s = reinterpret_cast<unsigned long long*>(ws + (size_t)halves * 64) + (size_t)bx * 8;
         s[0] = ((unsigned long long)__builtin_amdgcn_s_getreg(20 | (31 << 11)) << 32) | __builtin_amdgcn_s_getreg(4 | (31 << 11));  // XCC_ID | HW_ID
         s[1] = stamp[0]; s[2] = __builtin_amdgcn_s_memrealtime();
         s[3] = stamp[2]; s[4] = stamp[3]; s[5] = stamp[4]; s[6] = __builtin_amdgcn_s_memtime();
@@ -399,7 +399,7 @@ __global__ __launch_bounds__((MAXM > 4) ? 512 : 1024) void int4_mm_kernel(
       // the meeting of the two halves of tile `ntile`, on wave 0: lane (w, col) parks partial w of this half.  Workspace: [pair][half][wave][col]
       if (wave == 0) {
         constexpr int kSc1 = 16;  // as in split_k_meet: written through / read at agent scope, the halves sit on different XCDs
-        const int pair = blockIdx.x >> 1;
+        const int pair = (int)(bx >> 1);
         const __amdgpu_buffer_rsrc_t rws = __builtin_amdgcn_make_buffer_rsrc(ws + (size_t)pair * 128, 0, 512, 0x00020000);
         float mine = red[(lane >> 4) * 256 + (lane & 15)];
         asm volatile("" : "+v"(mine));
@@ -435,6 +435,36 @@ __global__ __launch_bounds__((MAXM > 4) ? 512 : 1024) void int4_mm_kernel(
     y[(size_t)(m0 + row) * N + ntile * 16 + col] = f32_to_bf16_bits(sum);
   }
   write_stamps();
+}
+
+template <int G, int MAXM, int DEPTH, bool STRAIGHT = false, bool BAL = false, bool STAMP = false>
+__global__ __launch_bounds__((MAXM > 4) ? 512 : 1024) void int4_mm_kernel(
+    const uint16_t* __restrict__ x, const u32x4* __restrict__ qdata,
+    const uint32_t* __restrict__ sz, uint16_t* __restrict__ y, int M, int N, int K, float* __restrict__ ws, unsigned* __restrict__ tickets) {
+  // (the two trailing arguments carried the M = 1 split-K workspace of round 3 and carry the balanced grid's now; the other builds leave them
+  // unused and the kernarg layout stays: removing them re-allocates the prologue's scalar registers, and every measurement of this kernel
+  // since round 3 was taken on this layout)
+  int4_mm_body<G, MAXM, DEPTH, STRAIGHT, BAL, STAMP>(x, qdata, sz, y, M, N, K, ws, tickets, blockIdx.x, gridDim.x);
+}
+
+// Two one-row straight-line problems of one N, K and G in one launch ("twin linears"): grid.z = 2, and workgroup (bx, z) runs
+// on problem z exactly what workgroup bx of a single launch runs -- the same blocks, the same order, the same sums: the same bits.  The two
+// problems share nothing but the launch; BAL (tuning mode 986 only): each has its own park area and tickets ([z][halves] of both).
+struct Int4PairArgs {
+  const uint16_t* x0; const uint16_t* x1;
+  const u32x4* q0; const u32x4* q1;
+  const uint32_t* sz0; const uint32_t* sz1;
+  uint16_t* y0; uint16_t* y1;
+  int N, K;
+  float* ws;
+  unsigned* tickets;
+};
+template <int G, int DEPTH, bool BAL>
+__global__ __launch_bounds__(1024) void int4_mm_pair_kernel(const Int4PairArgs a) {
+  const bool second = blockIdx.z != 0;  // (wave-uniform: scalar selects)
+  const int halves = BAL ? (int)gridDim.x - (a.N >> 4) : 0;
+  int4_mm_body<G, 1, DEPTH, true, BAL, false>(second ? a.x1 : a.x0, second ? a.q1 : a.q0, second ? a.sz1 : a.sz0, second ? a.y1 : a.y0, 1, a.N, a.K,
+                                              a.ws + (second ? (size_t)halves * 128 : 0), a.tickets + (second ? halves : 0), blockIdx.x, gridDim.x);
 }
 
 // ---------------------------------------------------------------------------
@@ -1510,11 +1540,14 @@ int device_cus() {
 // Modes 981 - 984 of ao_int4_set_tuning: the balanced grid never / wherever the form allows (any left-over count) / the stamped build on
 // today's grid / the stamped build on the balanced grid as 982 cuts it.  Every other choice stays the product's.
 constexpr int kBalOff = 981, kBalOn = 982, kStampGrid = 983, kStampBal = 984;
+// Modes 985 / 986: twin linears (below) never fused under capture / the pair grid with each problem's balanced halves (A/B: the product pair
+// runs one workgroup per tile).  The route stays the product's.
+constexpr int kPairOff = 985, kPairHalves = 986;
 
 // The route of ao_int4_weight_int4pack_mm (group size G); with f = Int4Force{} the product dispatch, which ao_int4_mm_kernel_name reports.
 Int4Route int4_route(int64_t M, int64_t N, int64_t K, int G, const Int4Force& f) {
   Int4Route r;
-  const bool bal_mode = f.mode >= kBalOff && f.mode <= kStampBal;
+  const bool bal_mode = (f.mode >= kBalOff && f.mode <= kStampBal) || f.mode == kPairOff || f.mode == kPairHalves;
   if (f.mode != 0 && !bal_mode) r = int4_forced_route(M, N, K, G, f);
   // M <= 16: one workgroup per 16-wide n-tile, waves split K (int4_mm_kernel, built for 1, 4, 8 or 16 rows).  In the hipGraph
   // bench the single-row build beat both purpose-built decode kernels this round tried (a persistent balanced streaming kernel
@@ -1648,6 +1681,184 @@ int check_int4_shape(const char* fn, int64_t N, int64_t K, int group_size) {
   return AO_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Twin linears: two one-row straight-line problems of one N, K, G and route in one launch of int4_mm_pair_kernel.
+// ---------------------------------------------------------------------------
+struct Int4Problem {
+  const uint16_t* x; const int32_t* q; const uint16_t* sz; uint16_t* y;
+};
+
+// The pair launch of route r (what launch_mm / launch_mm_row1 launch for it, with grid.z = 2); false where r is not a one-row straight-line form.
+struct PairGeom {
+  dim3 grid, block;
+  size_t smem = 0;
+  int depth = 4, halves = 0;
+};
+bool pair_geometry(const Int4Route& r, int64_t M, int64_t N, int64_t K, bool keep_halves, PairGeom* g) {
+  if (!(r.form == Int4Route::Tile && M == 1 && r.rows == 1 && r.straight && !r.stamp)) return false;
+  const int d = r.depth;
+  if (!(d == 4 || d == 7 || d == 14 || d == 2 || d == 8 || d == 9)) return false;
+  const int64_t kblocks = K >> 7;
+  if (kblocks % d != 0 || kblocks / d < 4 || kblocks / d > 16) return false;
+  const int wpb = (int)(kblocks / d);
+  // keep_halves (mode 986, A/B): each problem with the balanced halves of its route; the product pair runs one workgroup per tile, the grid of
+  // the merged layout (profiles/int4_pair_ab.jsonl: never behind, and it needs no workspace)
+  g->halves = keep_halves ? r.halves : 0;
+  if (g->halves > 0 && !(d == 4 && wpb == 8 && 2 * g->halves <= kSplitMaxTickets)) return false;
+  g->depth = d;
+  g->grid = dim3((unsigned)((N >> 4) + g->halves), 1, 2);
+  g->block = dim3(wpb * 64);
+  g->smem = (size_t)wpb * (512 + 1024);
+  return true;
+}
+
+template <int G, typename F>
+int with_pair_kernel_g(int depth, bool bal, F&& f) {
+  switch (depth) {
+    case 4: return bal ? f(int4_mm_pair_kernel<G, 4, true>) : f(int4_mm_pair_kernel<G, 4, false>);
+    case 7: return f(int4_mm_pair_kernel<G, 7, false>);
+    case 14: return f(int4_mm_pair_kernel<G, 14, false>);
+    case 2: return f(int4_mm_pair_kernel<G, 2, false>);
+    case 8: return f(int4_mm_pair_kernel<G, 8, false>);
+    case 9: return f(int4_mm_pair_kernel<G, 9, false>);
+  }
+  set_error("int4_mm_pair: no %d-deep pair kernel", depth);
+  return AO_ERR_INVALID_ARGUMENT;
+}
+template <typename F>
+int with_pair_kernel(int group_size, int depth, bool bal, F&& f) {
+  switch (group_size) {
+    case 32: return with_pair_kernel_g<32>(depth, bal, f);
+    case 64: return with_pair_kernel_g<64>(depth, bal, f);
+    case 128: return with_pair_kernel_g<128>(depth, bal, f);
+    default: return with_pair_kernel_g<256>(depth, bal, f);
+  }
+}
+
+Int4PairArgs pair_args(const Int4Problem& a, const Int4Problem& b, int64_t N, int64_t K, float* ws, unsigned* tickets) {
+  Int4PairArgs p;
+  p.x0 = a.x; p.x1 = b.x;
+  p.q0 = reinterpret_cast<const u32x4*>(a.q); p.q1 = reinterpret_cast<const u32x4*>(b.q);
+  p.sz0 = reinterpret_cast<const uint32_t*>(a.sz); p.sz1 = reinterpret_cast<const uint32_t*>(b.sz);
+  p.y0 = a.y; p.y1 = b.y;
+  p.N = (int)N; p.K = (int)K;
+  p.ws = ws; p.tickets = tickets;
+  return p;
+}
+
+int launch_pair(int group_size, const PairGeom& g, const Int4Problem& a, const Int4Problem& b, int64_t N, int64_t K, hipStream_t stream) {
+  float* ws = nullptr;
+  unsigned* tickets = nullptr;
+  if (g.halves > 0)  // [problem][halved tile]: 128 parked floats and one ticket each
+    if (int rc = splitk_workspace(stream, &ws, &tickets, (size_t)2 * g.halves * 128, 2)) return rc;
+  const Int4PairArgs args = pair_args(a, b, N, K, ws, tickets);
+  return with_pair_kernel(group_size, g.depth, g.halves > 0, [&](auto kern) {
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), g.smem, "hipFuncSetAttribute(int4_mm_pair_kernel)")) return rc;
+    ao::launch(kern, g.grid, g.block, g.smem, stream, args);
+    AO_LAUNCH_CHECK("int4_mm_pair_kernel launch");
+    return (int)AO_OK;
+  });
+}
+
+// ---- fusion under stream capture ----
+// What a capturing stream is about to depend on.  (A query that fails -- the legacy stream beside another thread's capture -- reads as "not capturing".)
+struct Capture {
+  bool active = false;
+  unsigned long long id = 0;
+  const hipGraphNode_t* deps = nullptr;
+  size_t ndeps = 0;
+};
+Capture capture_of(hipStream_t s) {
+  Capture c;
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  hipGraph_t graph = nullptr;
+  if (hipStreamGetCaptureInfo_v2(s, &st, &c.id, &graph, &c.deps, &c.ndeps) != hipSuccess) {
+    (void)hipGetLastError();
+    return Capture{};
+  }
+  c.active = st == hipStreamCaptureStatusActive;
+  return c;
+}
+
+// The last one-row straight-line launch a capture recorded: one record for the process, replaced by the next such launch and void once the
+// capture id changes (ids are never re-used, so a record never outlives its graph's capture).
+struct PairRecord {
+  bool live = false, paired = false;
+  unsigned long long id = 0;
+  hipStream_t stream = nullptr;
+  hipGraphNode_t node = nullptr;
+  int group_size = 0, depth = 0, halves = 0;
+  int64_t N = 0, K = 0;
+  Int4Problem p{};
+};
+std::mutex g_pair_mu;
+PairRecord g_pair;
+long long g_pair_fusions = 0;
+
+// Rewrites the recorded node into the pair launch of (recorded problem, b) where the rule of DESIGN 4.1 allows; false: launch b as usual.
+bool try_fuse_pair(const Capture& cap, hipStream_t stream, const Int4Route& r, int group_size, int64_t N, int64_t K, const Int4Problem& b, bool keep_halves) {
+  std::lock_guard<std::mutex> lock(g_pair_mu);
+  PairRecord& rec = g_pair;
+  if (!rec.live) return false;
+  if (rec.id != cap.id) {
+    rec = PairRecord{};
+    return false;
+  }
+  if (rec.paired || rec.stream != stream || cap.ndeps != 1 || cap.deps == nullptr || cap.deps[0] != rec.node) return false;
+  if (rec.group_size != group_size || rec.N != N || rec.K != K || rec.depth != r.depth || rec.halves != r.halves) return false;
+  if (!ao_int4_pair_independent(rec.p.x, rec.p.y, b.x, b.y, 1, N, K)) return false;
+  PairGeom g;
+  if (!pair_geometry(r, 1, N, K, keep_halves, &g)) return false;
+  float* ws = nullptr;
+  unsigned* tickets = nullptr;
+  if (g.halves > 0 && !splitk_workspace_held(stream, &ws, &tickets, (size_t)2 * g.halves * 128)) return false;
+  Int4PairArgs args = pair_args(rec.p, b, N, K, ws, tickets);  // (copied by the node; <= 24 KiB of LDS: no opt-in to make under capture)
+  const hipGraphNode_t node = rec.node;
+  const int rc = with_pair_kernel(group_size, g.depth, g.halves > 0, [&](auto kern) {
+    void* params[1] = {&args};
+    hipKernelNodeParams np{};
+    np.func = reinterpret_cast<void*>(kern);
+    np.gridDim = g.grid;
+    np.blockDim = g.block;
+    np.sharedMemBytes = (unsigned)g.smem;
+    np.kernelParams = params;
+    np.extra = nullptr;
+    const hipError_t e = hipGraphKernelNodeSetParams(node, &np);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      set_error("int4 pair fusion: hipGraphKernelNodeSetParams refused the pair kernel: %s (%s); launched on its own", hipGetErrorString(e), hipGetErrorName(e));
+      return (int)AO_ERR_HIP;
+    }
+    return (int)AO_OK;
+  });
+  if (rc != AO_OK) {
+    rec = PairRecord{};
+    return false;
+  }
+  rec.paired = true;
+  ++g_pair_fusions;
+  return true;
+}
+
+// After a one-row straight-line launch under capture: the node it became is the capture's one dependency now.
+void record_pair_candidate(const Capture& before, hipStream_t stream, const Int4Route& r, int group_size, int64_t N, int64_t K, const Int4Problem& p) {
+  const Capture now = capture_of(stream);
+  hipGraphNodeType type = hipGraphNodeTypeCount;
+  const bool ok = now.active && now.id == before.id && now.ndeps == 1 && now.deps != nullptr &&
+                  hipGraphNodeGetType(now.deps[0], &type) == hipSuccess && type == hipGraphNodeTypeKernel;
+  if (!ok) (void)hipGetLastError();
+  std::lock_guard<std::mutex> lock(g_pair_mu);
+  g_pair = PairRecord{};
+  if (!ok) return;
+  g_pair.live = true;
+  g_pair.id = now.id;
+  g_pair.stream = stream;
+  g_pair.node = now.deps[0];
+  g_pair.group_size = group_size; g_pair.depth = r.depth; g_pair.halves = r.halves;
+  g_pair.N = N; g_pair.K = K;
+  g_pair.p = p;
+}
+
 }  // namespace
 }  // namespace ao
 
@@ -1748,6 +1959,19 @@ extern "C" int ao_int4_weight_int4pack_mm(const uint16_t* x, const int32_t* qdat
   AO_REQUIRE_PTR(x);
   AO_REQUIRE_PTR(y);
   hipStream_t s = (hipStream_t)stream;
+  // Twin linears: a one-row straight-line launch under stream capture is recorded, and the next call fuses into its node
+  // when the capture has seen nothing in between and the two problems are independent.  Eager launches pay one capture query.
+  Capture cap;
+  Int4Route twin;
+  bool candidate = false;
+  const Int4Problem prob{x, qdata, scale_and_zero, y};
+  if (M == 1 && (cap = capture_of(s)).active) {
+    PairGeom g;
+    twin = int4_route(M, N, K, group_size, g_int4_force);
+    candidate = pair_geometry(twin, M, N, K, true, &g);
+    if (candidate && g_int4_force.mode != kPairOff && try_fuse_pair(cap, s, twin, group_size, N, K, prob, g_int4_force.mode == kPairHalves))
+      return AO_OK;
+  }
   // The batched kernel addresses x rows with 32-bit byte offsets and grid.y is 16-bit: very tall activations go in row
   // chunks (a multiple of 128 rows, < 4 GiB of x and <= 65535 slabs each), one launch per chunk.
   const int64_t by_bytes = ((1ll << 32) - 1) / (2 * K) / 128 * 128;
@@ -1765,7 +1989,50 @@ extern "C" int ao_int4_weight_int4pack_mm(const uint16_t* x, const int32_t* qdat
     }
     if (rc != AO_OK) return rc;
   }
+  if (candidate) record_pair_candidate(cap, s, twin, group_size, N, K, prob);
   return AO_OK;
+}
+
+// The overlap rule of the pair fusion (host arithmetic on addresses; nothing is dereferenced).  The second call may join the first's launch
+// when its output [y1, y1 + M N) overlaps neither the first's input [x0, x0 + M K) nor its output [y0, y0 + M N), and its input
+// [x1, x1 + M K) does not overlap the first's output.  x0 == x1 is the expected case: both only read it.
+extern "C" int ao_int4_pair_independent(const uint16_t* x0, const uint16_t* y0, const uint16_t* x1, const uint16_t* y1, int64_t M, int64_t N,
+                                        int64_t K) {
+  if (M <= 0 || N <= 0 || K <= 0) return 0;
+  const auto overlap = [](const uint16_t* a, int64_t na, const uint16_t* b, int64_t nb) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + 2 * (uintptr_t)nb && b0 < a0 + 2 * (uintptr_t)na;
+  };
+  return !overlap(y1, M * N, x0, M * K) && !overlap(y1, M * N, y0, M * N) && !overlap(x1, M * K, y0, M * N);
+}
+
+extern "C" int ao_int4_pair_fusions(void) {
+  std::lock_guard<std::mutex> lock(g_pair_mu);
+  return (int)std::min<long long>(g_pair_fusions, 0x7fffffff);
+}
+
+extern "C" int ao_int4_weight_int4pack_mm_pair(const uint16_t* x0, const int32_t* q0, const uint16_t* sz0, uint16_t* y0, const uint16_t* x1,
+                                               const int32_t* q1, const uint16_t* sz1, uint16_t* y1, int64_t M, int64_t N, int64_t K,
+                                               int group_size, void* stream) {
+  AO_REQUIRE_PTR(q0);
+  AO_REQUIRE_PTR(sz0);
+  AO_REQUIRE_PTR(q1);
+  AO_REQUIRE_PTR(sz1);
+  if (int rc = check_int4_shape(__func__, N, K, group_size)) return rc;
+  AO_REQUIRE(M >= 0 && M < (1ll << 31), "ao_int4_weight_int4pack_mm_pair: bad M=%lld", (long long)M);
+  if (M == 0) return AO_OK;
+  AO_REQUIRE_PTR(x0);
+  AO_REQUIRE_PTR(y0);
+  AO_REQUIRE_PTR(x1);
+  AO_REQUIRE_PTR(y1);
+  PairGeom g;
+  const Int4Force& f = g_int4_force;
+  if (M == 1 && ao_int4_pair_independent(x0, y0, x1, y1, M, N, K) &&
+      pair_geometry(int4_route(M, N, K, group_size, f), M, N, K, f.mode == kPairHalves, &g))
+    return launch_pair(group_size, g, Int4Problem{x0, q0, sz0, y0}, Int4Problem{x1, q1, sz1, y1}, N, K, (hipStream_t)stream);
+  // every other route, and a second problem that depends on the first: the two single launches, in order
+  if (int rc = ao_int4_weight_int4pack_mm(x0, q0, sz0, y0, M, N, K, group_size, stream)) return rc;
+  return ao_int4_weight_int4pack_mm(x1, q1, sz1, y1, M, N, K, group_size, stream);
 }
 
 extern "C" int ao_int4_dequantize(const int32_t* qdata, const uint16_t* scale_and_zero,

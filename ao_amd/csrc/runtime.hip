@@ -158,6 +158,24 @@ int splitk_workspace(hipStream_t stream, float** part, unsigned** tickets, size_
   return AO_OK;
 }
 
+bool splitk_workspace_held(hipStream_t stream, float** part, unsigned** tickets, size_t need_floats) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
+    (void)hipGetLastError();
+    return false;
+  }
+  std::lock_guard<std::mutex> lock(g_split_mu);
+  for (int i = 0; i < kSplitSlots; ++i) {
+    SplitWs& w = g_split_ws[dev][i];
+    if (!w.used || w.stream != stream || w.base == nullptr || w.floats < need_floats) continue;
+    w.last_use = ++g_split_clock;
+    *part = reinterpret_cast<float*>(w.base);
+    *tickets = reinterpret_cast<unsigned*>(w.base + w.floats * sizeof(float));
+    return true;
+  }
+  return false;
+}
+
 }  // namespace ao
 
 // Pre-size the calling stream's split-K workspace (outside stream capture), so that every later launch on that stream -- whatever its

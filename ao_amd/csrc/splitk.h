@@ -19,6 +19,9 @@ constexpr size_t kSplitSlotFloats = (size_t)kSplitMaxTiles * 128 * 128;  // 128 
 // kSplitMaxParts -- a ticket that can never read "last" would skip the epilogue silently.
 constexpr int kSplitMaxParts = 16;
 int splitk_workspace(hipStream_t stream, float** part, unsigned** tickets, size_t need_floats, int parts = 1);
+// The workspace `stream` already holds on the current device, if its parts area takes need_floats: no allocation, no growth, no
+// synchronise -- safe inside stream capture, where a caller re-plans a launch this stream has made before (the int4 pair fusion).
+bool splitk_workspace_held(hipStream_t stream, float** part, unsigned** tickets, size_t need_floats);
 // ---------------------------------------------------------------------------
 // Split-K meeting: every part parks its fp32 tile in the workspace
 // ([tile][part][reg][thread], 16 B per thread and register: coalesced), takes a ticket, and the last one

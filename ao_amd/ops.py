@@ -199,6 +199,35 @@ def weight_int4pack_mm(
     return y
 
 
+def int4_mm_pair(x0, qdata0, scale_and_zero0, x1, qdata1, scale_and_zero1, group_size: int):
+    """Two weight_int4pack_mm calls of one shape in one launch (ao_int4_weight_int4pack_mm_pair): twin linears such as
+    gate_proj / up_proj on the same activation (x0 may be x1).  Returns (y0, y1), the bits of the two single calls."""
+    dev = _require_gpu("int4_mm_pair", x0, qdata0, scale_and_zero0, x1, qdata1, scale_and_zero1)
+    n, k = _int4_dims("int4_mm_pair", qdata0, scale_and_zero0, group_size)
+    if _int4_dims("int4_mm_pair", qdata1, scale_and_zero1, group_size) != (n, k):
+        raise RuntimeError("int4_mm_pair: the two weights must have one N and K")
+    for x in (x0, x1):
+        if x.dim() != 2 or x.dtype != torch.bfloat16 or x.shape[1] != k:
+            raise RuntimeError(f"int4_mm_pair: activations must be bfloat16 [M, {k}], got {x.dtype} {tuple(x.shape)}")
+    if x0.shape[0] != x1.shape[0]:
+        raise RuntimeError("int4_mm_pair: the two activations must have one M")
+    x0 = x0 if x0.is_contiguous() else x0.contiguous()
+    x1 = x1 if x1.is_contiguous() else x1.contiguous()
+    m = x0.shape[0]
+    y0 = torch.empty((m, n), dtype=torch.bfloat16, device=dev)
+    y1 = torch.empty((m, n), dtype=torch.bfloat16, device=dev)
+    if m == 0:
+        return y0, y1
+    with _on(dev):
+        _lib.check(
+            _lib.lib().ao_int4_weight_int4pack_mm_pair(
+                _ptr(x0), _ptr(qdata0), _ptr(scale_and_zero0), _ptr(y0), _ptr(x1), _ptr(qdata1), _ptr(scale_and_zero1), _ptr(y1),
+                m, n, k, group_size, _stream()
+            )
+        )
+    return y0, y1
+
+
 def int4_dequantize(qdata: torch.Tensor, scale_and_zero: torch.Tensor, group_size: int) -> torch.Tensor:
     """Packed int4 -> bf16 [N, K] with the reference's rounding sequence
     (torchao/quantization/utils.py:445-455, quant_primitives.py:999-1007)."""

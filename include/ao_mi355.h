@@ -106,6 +106,24 @@ int ao_int4_weight_int4pack_mm(const uint16_t* x, const int32_t* qdata,
                                int64_t M, int64_t N, int64_t K, int group_size,
                                void* stream);
 
+/* Two aten::_weight_int4pack_mm calls of one M, N, K and group size in one launch (call site: int4_tile_packed_to_4d_tensor.py:287,
+ * reached twice in a row by modules that keep twin linears apart -- gate_proj / up_proj, k_proj / v_proj -- on the same activation).
+ * Arguments and requirements per problem as for ao_int4_weight_int4pack_mm; x0 == x1 is allowed, the weights are only read.
+ * Returns AO_OK with y0, y1 holding, bit for bit, what the two single calls store.  Where the problem's route is a one-row (M = 1)
+ * straight-line form of int4_mm_kernel and ao_int4_pair_independent holds, that is ONE launch of int4_mm_pair_kernel (grid.z = 2);
+ * on every other route, or when the second problem depends on the first, the entry makes the two single launches in order
+ * (problem 0 first) -- it never fails because the pair form does not apply. */
+int ao_int4_weight_int4pack_mm_pair(const uint16_t* x0, const int32_t* qdata0, const uint16_t* scale_and_zero0, uint16_t* y0,
+                                    const uint16_t* x1, const int32_t* qdata1, const uint16_t* scale_and_zero1, uint16_t* y1,
+                                    int64_t M, int64_t N, int64_t K, int group_size, void* stream);
+/* The pair's independence rule, host arithmetic on addresses only: 1 when [y1, y1 + M N) overlaps neither [x0, x0 + M K) nor
+ * [y0, y0 + M N) and [x1, x1 + M K) does not overlap [y0, y0 + M N) (elements of 2 bytes), else 0. */
+int ao_int4_pair_independent(const uint16_t* x0, const uint16_t* y0, const uint16_t* x1, const uint16_t* y1, int64_t M, int64_t N,
+                             int64_t K);
+/* How many times ao_int4_weight_int4pack_mm, called under stream capture, folded its launch into the kernel node of the call before it
+ * ("twin linears"): a running count of the process (saturates at INT_MAX).  Host only. */
+int ao_int4_pair_fusions(void);
+
 /* Dequantize the packed weight to bf16 [N][K] with the oracle's rounding
  * sequence.  Replaces groupwise_affine_dequantize_tensor
  * (torchao/quantization/utils.py:445-455) for the packed format. */
@@ -129,7 +147,9 @@ int ao_int4_quantize_tinygemm(const uint16_t* w, int32_t* qdata,
  * tools/bin/_C_mi355_lab.so, compiled with -DAO_LAB; tools select it through AO_MI355_LIB).  Thread-local.
  * Modes 981 - 984 steer only the balanced grid of the one-row kernel and leave every other choice the product's: 981 never,
  * 982 wherever the form allows (one row, K = 4096: any left-over tile count, for A/B and tests on small shapes), 983 / 984 the stamped
- * profiling build (g = 128; [workgroups][8] u64 into the ao_int4_set_trace buffer) on today's grid / on the grid of 982. */
+ * profiling build (g = 128; [workgroups][8] u64 into the ao_int4_set_trace buffer) on today's grid / on the grid of 982.
+ * Modes 985 / 986 steer only the twin-linear pair: 985 never fuse two captured calls into one node, 986 the pair grid
+ * with each problem's balanced halves (the product pair runs one workgroup per tile; A/B). */
 int ao_int4_set_tuning(int waves_per_block, int mode);
 /* 1 when the calling thread has an ao_int4_set_tuning override set, else 0 (tests assert the product dispatch).  Host only. */
 int ao_int4_overridden(void);
