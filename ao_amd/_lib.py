@@ -162,6 +162,10 @@ _SIGNATURES = {
     "ao_nvfp4_grouped_mm_route": [_INT, _I64, _I64, _I64, _I64, _P, _INT],
     "ao_nvfp4_grouped_mm_kernel_name": [_INT, _I64, _I64, _I64, _I64],
     "ao_nvfp4_grouped_mm_set_form": [_INT],
+    "ao_nvfp4_train_amax": [_P, _P, _I64, _I64, ctypes.c_uint32, _INT, _P],
+    "ao_nvfp4_train_quantize_row_col": [_P, _P, ctypes.c_uint32, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P],
+    "ao_nvfp4_train_quantize_weight_2d": [_P, _P, _P, _P, _P, _P, _I64, _I64, _P],
+    "ao_nvfp4_scaled_mm": [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _P],
 }
 
 

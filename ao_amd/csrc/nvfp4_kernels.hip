@@ -80,6 +80,8 @@ struct Nvfp4Args {
   // grouped (MoE experts) only: M is M_total, b / b_scale hold E experts, pa / pb one scale an expert, no bias
   const int32_t* offs;     // [E] cumulative group ends, or null (dense)
   int E;
+  // codes x codes only: the epilogue of ao_nvfp4_scaled_mm, out = bf16(acc (pa pb)) rounded once (nvfp4_scaled_mm_out), not nvfp4_mm_out's chain
+  int scaled_mm;
 };
 
 // Token group e = rows [offs[e-1], offs[e]) (offs[-1] = 0).  The kernels only read offs: a group's bounds are clamped to [0, M_total] (a
@@ -235,7 +237,9 @@ __global__ __launch_bounds__(64 * WAVES) void nvfp4_stream_kernel(Nvfp4Args p) {
       for (int r = 0; r < 4; ++r) {
         const int row = m0 + mt * 16 + 4 * kq + r;
         if (row < row_end && n < p.N) {
-          const float v = KIND == kKindWo ? nvfp4_wo_out(c[r], has_bias, bias) : nvfp4_mm_out(c[r], has_P, P, has_bias, bias);
+          const float v = KIND == kKindWo  ? nvfp4_wo_out(c[r], has_bias, bias)
+                          : p.scaled_mm    ? nvfp4_scaled_mm_out(c[r], P)
+                                           : nvfp4_mm_out(c[r], has_P, P, has_bias, bias);
           p.out[(size_t)row * p.N + n] = f32_to_bf16_bits(v);
         }
       }
@@ -368,7 +372,9 @@ __global__ __launch_bounds__(256) void nvfp4_tile_kernel(Nvfp4Args p) {
         const int row = m0 + wm + 16 * i + 4 * kq + r;
         if (row < p.M) {
           const float c = acc[i][j][r];
-          const float v = KIND == kKindWo ? nvfp4_wo_out(c, has_bias, bias) : nvfp4_mm_out(c, has_P, P, has_bias, bias);
+          const float v = KIND == kKindWo  ? nvfp4_wo_out(c, has_bias, bias)
+                          : p.scaled_mm    ? nvfp4_scaled_mm_out(c, P)
+                                           : nvfp4_mm_out(c, has_P, P, has_bias, bias);
           p.out[(size_t)row * p.N + n] = f32_to_bf16_bits(v);
         }
       }
@@ -638,6 +644,26 @@ extern "C" int ao_nvfp4_linear(const uint8_t* a, const uint8_t* a_scale, const f
   AO_REQUIRE(aligned_to(a_per_tensor_scale, 4) && aligned_to(b_per_tensor_scale, 4) && aligned_to(bias, 2) && aligned_to(out, 2),
              "%s: the per-tensor scales must be 4-byte, bias and out 2-byte aligned", __func__);
   const Nvfp4Args args{nullptr, a, a_scale, b, b_scale, a_per_tensor_scale, b_per_tensor_scale, bias, out, (int)M, (int)N, (int)K};
+  return run<kKindDyn>(__func__, args, M, N, K, static_cast<hipStream_t>(stream));
+}
+
+// The training GEMMs (prototype/moe_training/nvfp4_training/nvfp4_linear.py:213-223, :278-306: torch.nn.functional.scaled_mm on e2m1
+// codes with BlockWise1x16 + TensorWise scales): the codes x codes route and bodies above under the scaled_mm epilogue.
+extern "C" int ao_nvfp4_scaled_mm(const uint8_t* a, const uint8_t* a_scale, const float* pa, const uint8_t* b, const uint8_t* b_scale, const float* pb,
+                                  uint16_t* out, int64_t M, int64_t N, int64_t K, void* stream) {
+  if (int rc = check_shape(__func__, kKindDyn, M, N, K)) return rc;
+  AO_REQUIRE_PTR(b);
+  AO_REQUIRE_PTR(b_scale);
+  AO_REQUIRE_PTR(pa);
+  AO_REQUIRE_PTR(pb);
+  if (M == 0) return AO_OK;
+  AO_REQUIRE_PTR(a);
+  AO_REQUIRE_PTR(a_scale);
+  AO_REQUIRE_PTR(out);
+  AO_REQUIRE(aligned_to(a, K % 32 ? 8 : 16) && aligned_to(b, K % 32 ? 8 : 16) && aligned_to(a_scale, K % 32 ? 1 : 2) && aligned_to(b_scale, K % 32 ? 1 : 2),
+             "%s: the codes must be 16-byte and the block scales 2-byte aligned (K %% 32 != 0: 8-byte and 1-byte)", __func__);
+  AO_REQUIRE(aligned_to(pa, 4) && aligned_to(pb, 4) && aligned_to(out, 2), "%s: the per-tensor scales must be 4-byte, out 2-byte aligned", __func__);
+  const Nvfp4Args args{nullptr, a, a_scale, b, b_scale, pa, pb, nullptr, out, (int)M, (int)N, (int)K, nullptr, 0, 1};
   return run<kKindDyn>(__func__, args, M, N, K, static_cast<hipStream_t>(stream));
 }
 

@@ -413,4 +413,135 @@ __device__ __forceinline__ float nvfp4_mm_out(float c, bool has_P, float P, bool
   return has_bias ? u + bias : u;
 }
 
+// ---- NVFP4 training (nvfp4_train_kernels.hip): the casts of prototype/moe_training/nvfp4_training ---------------------------------------
+// TransformerEngine's scale chain as test/prototype/moe_training/nvfp4_training/nvfp4_reference.py states it and
+// hadamard_utils._nvfp4_quantize implements it -- not nvfp4_quantize's above: the scale is rounded ONCE, the block scale has no lower
+// clamp, and the per-tensor scale is folded into an encode scale.  Every step one fp32 operation, the divisions correctly rounded:
+//   global   S_enc = min(2688 / amax, FLT_MAX);  S_enc = 1 if amax == 0 or the quotient is 0;  S_dec_global = 1 / S_enc
+//   block    s8 = e4m3(min(block_amax (S_enc (1/6)), 448)): the inner product rounded once, NO lower clamp (a zero block, or one that
+//            underflows e4m3, has the scale byte 0)
+//   encode   enc = min(1 / (f32(s8) S_dec_global), FLT_MAX);  scaled = clamp(x enc, -6, 6)
+//   RTNE     e2m1_code above, element 2i in the low nibble of byte i; the sign bit is kept (-0 is code 8)
+//   RHT      for 16 consecutive elements a_0..a_15, the sign vector s and the Sylvester matrix: y_j = bf16(1/4 sum_i s_i a_i (-1)^popcount(i & j)),
+//            the sum in fp32 by a butterfly of four add/sub stages (i ^ 1, i ^ 2, i ^ 4, i ^ 8).  The fp32 sum is exact in ANY order while
+//            the 16 inputs' exponents span fewer than 12 binades (8 significand bits + 4 bits of growth + 12 < 24); outside that the
+//            butterfly's order is this kernel's own and another order may round differently.  A zero sum is +0, also where every term
+//            is -0: the reference's matrix product starts its accumulator at +0.
+//   SR       (the reference draws Triton's Philox stream and rounds with PTX cvt.rs, neither reproducible here: this is this library's
+//            own contract)  a = min(|scaled|, 6);  lo <= a <= hi the e2m1 magnitudes around a (on the grid lo = hi = a);
+//            t = (a - lo) / (hi - lo), exact in fp32 (the steps are powers of two and the subtraction is exact);  the magnitude is hi iff
+//            r16 < t 65536, else lo;  the sign is kept.  P(up) = ceil(t 2^16) / 2^16: the bias is below 2^-16 of a step.
+//   bits     Philox4x32-10 with its published constants;  key = the two 32-bit halves of the int64 seed;  counter = (g_lo, g_hi,
+//            offset & 0xFFFFFFFF, stream), g the index in the output's row-major order of the group of 8 consecutive codes (one packed
+//            dword), stream 0 the row output and 1 the column output;  element j of the group takes bits 16 (j & 1) .. + 15 of output
+//            word j >> 1.  The bytes depend only on (seed, offset), never on the grid.
+// NaN and Inf inputs are outside the contract of the training casts.
+constexpr float kF32Max = 3.4028234663852886e38f;
+
+struct Nvfp4TrainGlobal {
+  float s_enc_sixth;  // S_enc (1/6)
+  float s_dec;        // 1 / S_enc
+};
+__device__ __forceinline__ Nvfp4TrainGlobal nvfp4_train_global(float amax) {
+#pragma clang fp contract(off)
+  float s_enc = fminf(2688.0f / amax, kF32Max);
+  if (amax == 0.0f || s_enc == 0.0f) s_enc = 1.0f;
+  return Nvfp4TrainGlobal{s_enc * (1.0f / 6.0f), 1.0f / s_enc};
+}
+// block amax -> the e4m3 scale byte in s8 and the encode scale
+__device__ __forceinline__ float nvfp4_train_encode(float block_amax, const Nvfp4TrainGlobal& g, uint32_t& s8) {
+#pragma clang fp contract(off)
+  s8 = cvt4_e4m3(fminf(block_amax * g.s_enc_sixth, 448.0f), 0.f, 0.f, 0.f) & 0xffu;
+  return fminf(1.0f / (e4m3_byte_to_f32(s8) * g.s_dec), kF32Max);
+}
+__device__ __forceinline__ float nvfp4_train_scaled(float x, float enc) {
+#pragma clang fp contract(off)
+  return fminf(fmaxf(x * enc, -6.0f), 6.0f);
+}
+
+struct Philox4 {
+  uint32_t w[4];
+};
+__device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0;
+    c1 = lo1;
+    c2 = hi0 ^ c3 ^ k1;
+    c3 = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  return Philox4{{c0, c1, c2, c3}};
+}
+// the SR code of one scaled value (|scaled| <= 6) under 16 random bits
+__device__ __forceinline__ uint32_t e2m1_code_sr(float scaled, uint32_t r16) {
+#pragma clang fp contract(off)
+  const uint32_t sign = (f32_to_bits(scaled) >> 28) & 8u;
+  const float a = fminf(fabsf(scaled), 6.0f);
+  uint32_t c;
+  float t;
+  if (a < 2.0f) {  // steps of 0.5: codes 0..3
+    const float f = floorf(a * 2.0f);
+    c = (uint32_t)f;
+    t = a * 2.0f - f;
+  } else if (a < 4.0f) {  // steps of 1: codes 4, 5
+    const float f = floorf(a);
+    c = (uint32_t)f + 2u;
+    t = a - f;
+  } else if (a < 6.0f) {  // one step of 2: code 6
+    c = 6u;
+    t = (a - 4.0f) * 0.5f;
+  } else {
+    c = 7u;
+    t = 0.0f;
+  }
+  if ((float)r16 < t * 65536.0f) c += 1u;
+  return c | sign;
+}
+// 16 signed values -> their randomized Hadamard transform, each rounded to bf16 (held as fp32); bit i of sign_mask set: s_i = -1
+__device__ __forceinline__ void nvfp4_rht16(float (&a)[16], uint32_t sign_mask) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int i = 0; i < 16; ++i) a[i] = bits_to_f32(f32_to_bits(a[i]) ^ (((sign_mask >> i) & 1u) << 31));
+#pragma unroll
+  for (int h = 1; h < 16; h <<= 1)
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+      if ((i & h) == 0) {
+        const float u = a[i], v = a[i | h];
+        a[i] = u + v;
+        a[i | h] = u - v;
+      }
+#pragma unroll
+  for (int i = 0; i < 16; ++i) a[i] = round_bf16((a[i] + 0.0f) * 0.25f);  // (+ 0: a sum of -0 terms alone is +0, as from an accumulator)
+}
+// 16 values of one block -> 16 codes packed two a byte.  SR: g0 the index of the block's first group of 8 codes (the second is g0 + 1).
+template <bool SR>
+__device__ __forceinline__ u32x2 nvfp4_train_codes16(const float (&a)[16], float enc, uint64_t g0, uint32_t offset, uint32_t stream,
+                                                     uint32_t k0, uint32_t k1) {
+  uint32_t out[2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    Philox4 rnd = {};
+    if (SR) {
+      const uint64_t g = g0 + h;
+      rnd = philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), offset, stream, k0, k1);
+    }
+    uint32_t o = 0u;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float v = nvfp4_train_scaled(a[8 * h + j], enc);
+      const uint32_t c = SR ? e2m1_code_sr(v, (rnd.w[j >> 1] >> (16 * (j & 1))) & 0xffffu) : e2m1_code(f32_to_bits(v));
+      o |= c << (4 * j);
+    }
+    out[h] = o;
+  }
+  return u32x2{out[0], out[1]};
+}
+// the scaled_mm epilogue of the training GEMMs: out = bf16(acc (pa pb)), the product of the two scales in fp32, ONE rounding, no bias
+__device__ __forceinline__ float nvfp4_scaled_mm_out(float c, float P) { return mul_f32_rn(c, P); }
+
 }  // namespace ao

@@ -2280,3 +2280,124 @@ def nvfp4_grouped_mm(kind, a, a_scale, wq, w_scale, offs, a_per_group_scale=None
 
 __all__ += ["nvfp4_grouped_mm", "nvfp4_group_amax_scale", "nvfp4_quantize_grouped", "nvfp4_grouped_mm_route",
             "nvfp4_grouped_mm_kernel_name", "nvfp4_grouped_mm_set_form"]
+
+
+# ---- NVFP4 training: casts and the scaled_mm epilogue (include/ao_mi355.h "NVFP4 training") -------------------------------
+def nvfp4_sign_mask(sign_vector) -> int:
+    """The 16-point Hadamard sign vector as the C ABI's 16-bit mask: bit i set means s_i = -1.  Takes 16 values of +-1 (a sequence or a
+    tensor) or a mask already."""
+    if isinstance(sign_vector, int):
+        if not 0 <= sign_vector < 1 << 16:
+            raise ValueError(f"sign mask must be a 16-bit mask, got {sign_vector:#x}")
+        return sign_vector
+    vals = [int(v) for v in (sign_vector.detach().cpu().tolist() if isinstance(sign_vector, torch.Tensor) else sign_vector)]
+    if len(vals) != 16 or any(v not in (1, -1) for v in vals):
+        raise ValueError(f"the RHT sign vector must be 16 values of +1 or -1, got {vals}")
+    return sum(1 << i for i, v in enumerate(vals) if v < 0)
+
+
+def _nvfp4_train_matrix(name, x):
+    if x.dtype != torch.bfloat16 or x.dim() != 2 or not x.is_contiguous():
+        raise RuntimeError(f"{name}: expected a contiguous 2-D bfloat16 tensor, got {x.dtype} {tuple(x.shape)}")
+    m, n = x.shape
+    if m % 16 != 0 or n % 16 != 0 or n == 0:
+        raise RuntimeError(f"{name}: both dimensions of shape {tuple(x.shape)} must be divisible by 16")
+    return m, n
+
+
+def _nvfp4_train_out(name, what, out, rows, cols, dev):
+    """(codes uint8 [rows, cols/2], scale bytes uint8 [rows, cols/16]): fresh, or the caller's pair checked"""
+    if out is None:
+        return (torch.empty((rows, cols // 2), dtype=torch.uint8, device=dev), torch.empty((rows, cols // 16), dtype=torch.uint8, device=dev))
+    q, s = out
+    for t, shape in ((q, (rows, cols // 2)), (s, (rows, cols // 16))):
+        if t.dtype != torch.uint8 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise RuntimeError(f"{name}: the {what} output must be contiguous uint8 {shape} on {dev}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return q, s
+
+
+def _nvfp4_i64(name, what, t, dev):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.numel() != 1 or t.device != dev:
+        raise RuntimeError(f"{name}: {what} must be an int64 tensor of one element on {dev}")
+    return t.contiguous()
+
+
+def nvfp4_train_amax(x: torch.Tensor, sign_vector, want_rht: bool = True) -> torch.Tensor:
+    """triton_rht_amax (nvfp4_training/hadamard_amax_triton.py): x bf16 [M, N] -> fp32 [2] on the device, [0] = max|bf16(RHT(x^T))| (0 when
+    not want_rht), [1] = max|x|.  No host read (capturable)."""
+    name = "nvfp4_train_amax"
+    dev = _require_gpu(name, x)
+    m, n = _nvfp4_train_matrix(name, x)
+    mask = nvfp4_sign_mask(sign_vector)
+    out = torch.empty((2,), dtype=torch.float32, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_nvfp4_train_amax(_ptr(x), _ptr(out), m, n, mask, int(bool(want_rht)), _stream()))
+    return out
+
+
+def nvfp4_train_quantize_row_col(x: torch.Tensor, amax2: torch.Tensor, sign_vector, sr_seed: Optional[torch.Tensor] = None,
+                                 col_offset: Optional[torch.Tensor] = None, row_offset: Optional[torch.Tensor] = None, *, want_col: bool = True,
+                                 want_row: bool = True, col_out=None, row_out=None):
+    """triton_rht_quantize_row_col (nvfp4_training/hadamard_quantize_row_col_triton.py) in one read of x bf16 [M, N]: returns
+    (col_q [N, M/2], col_s e4m3 [N, M/16], row_q [M, N/2], row_s e4m3 [M, N/16]) -- the 1 x 16 cast of bf16(RHT(x^T)) under amax2[0] and of x
+    under amax2[1], the scales row-major; a direction not wanted is (None, None).  sr_seed None: round to nearest even; otherwise stochastic
+    rounding of both outputs from the int64 device tensors sr_seed, col_offset, row_offset (quant_math.h "NVFP4 training")."""
+    name = "nvfp4_train_quantize_row_col"
+    dev = _require_gpu(name, x, amax2, sr_seed, col_offset, row_offset)
+    m, n = _nvfp4_train_matrix(name, x)
+    mask = nvfp4_sign_mask(sign_vector)
+    if not (want_col or want_row):
+        raise RuntimeError(f"{name}: neither output is wanted")
+    if not isinstance(amax2, torch.Tensor) or amax2.dtype != torch.float32 or amax2.numel() != 2 or not amax2.is_contiguous():
+        raise RuntimeError(f"{name}: amax2 must be a contiguous float32 tensor of two elements (column amax, row amax)")
+    if sr_seed is not None:
+        sr_seed = _nvfp4_i64(name, "sr_seed", sr_seed, dev)
+        col_offset = _nvfp4_i64(name, "col_offset", col_offset, dev) if want_col else None
+        row_offset = _nvfp4_i64(name, "row_offset", row_offset, dev) if want_row else None
+    else:
+        col_offset = row_offset = None
+    cq, cs = _nvfp4_train_out(name, "column", col_out, n, m, dev) if want_col else (None, None)
+    rq, rs = _nvfp4_train_out(name, "row", row_out, m, n, dev) if want_row else (None, None)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_nvfp4_train_quantize_row_col(_ptr(x), _ptr(amax2), mask, _ptr(sr_seed), _ptr(col_offset), _ptr(row_offset),
+                                                              _ptr(cq), _ptr(cs), _ptr(rq), _ptr(rs), m, n, _stream()))
+    f8 = torch.float8_e4m3fn
+    return cq, (None if cs is None else cs.view(f8)), rq, (None if rs is None else rs.view(f8))
+
+
+def nvfp4_train_quantize_weight_2d(w: torch.Tensor, amax: torch.Tensor, *, out=None, out_t=None):
+    """triton_weight_quantize_2d (nvfp4_training/quantize_2d_triton.py): w bf16 [N, K] under 16 x 16 block scales, round to nearest even,
+    amax = max|w| as one fp32 on the device -> (q [N, K/2], s e4m3 [N, K/16], qt [K, N/2], st e4m3 [K, N/16]): the cast of w and, from the
+    same read and the same block scales, of w^T."""
+    name = "nvfp4_train_quantize_weight_2d"
+    dev = _require_gpu(name, w, amax)
+    n, k = _nvfp4_train_matrix(name, w)
+    a = _nvfp4_scalar(name, "amax", amax, dev)
+    q, s = _nvfp4_train_out(name, "weight", out, n, k, dev)
+    qt, st = _nvfp4_train_out(name, "transposed weight", out_t, k, n, dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_nvfp4_train_quantize_weight_2d(_ptr(w), _ptr(a), _ptr(q), _ptr(s), _ptr(qt), _ptr(st), n, k, _stream()))
+    return q, s.view(torch.float8_e4m3fn), qt, st.view(torch.float8_e4m3fn)
+
+
+def nvfp4_scaled_mm(a, a_scale, b, b_scale, a_per_tensor_scale, b_per_tensor_scale, out=None):
+    """torch.nn.functional.scaled_mm on e2m1 codes with BlockWise1x16 + TensorWise scales (nvfp4_training/nvfp4_linear.py:213-223): a
+    [M, K/2], a_scale [M, K/16], b [N, K/2], b_scale [N, K/16], both per-tensor scales one fp32 on the device -> bf16 [M, N] =
+    bf16(acc (pa pb)): fp32 accumulation, the scales' product in fp32, ONE rounding, no bias (nvfp4_mm rounds acc and P to bf16 first)."""
+    name = "nvfp4_scaled_mm"
+    dev = _require_gpu(name, a, a_scale, b, b_scale, a_per_tensor_scale, b_per_tensor_scale, out)
+    a, a_scale, m, ka = _nvfp4_codes(name, "activation", a, a_scale)
+    b, b_scale, n, k = _nvfp4_codes(name, "weight", b, b_scale)
+    if ka != k:
+        raise RuntimeError(f"{name}: K of the activation ({ka}) and of the weight ({k}) differ")
+    pa = _nvfp4_scalar(name, "a_per_tensor_scale", a_per_tensor_scale, dev)
+    pb = _nvfp4_scalar(name, "b_per_tensor_scale", b_per_tensor_scale, dev)
+    if pa is None or pb is None:
+        raise RuntimeError(f"{name}: both per-tensor scales are required")
+    y = _bf16_out(name, out, m, n, dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_nvfp4_scaled_mm(_ptr(a), _ptr(a_scale), _ptr(pa), _ptr(b), _ptr(b_scale), _ptr(pb), _ptr(y), m, n, k, _stream()))
+    return y
+
+
+__all__ += ["nvfp4_sign_mask", "nvfp4_train_amax", "nvfp4_train_quantize_row_col", "nvfp4_train_quantize_weight_2d", "nvfp4_scaled_mm"]

@@ -29,6 +29,13 @@ from .nvfp4_tensor import (  # noqa: F401
     QuantizeTensorToNVFP4Kwargs,
     per_tensor_amax_to_scale,
 )
+from .nvfp4_training import (  # noqa: F401
+    DEFAULT_SIGN_VECTOR,
+    NVFP4Linear,
+    NVFP4TrainingConfig,
+    get_wgrad_sign_vector,
+    nvfp4_linear,
+)
 
 __all__ = ["Float8BlockwiseExpertWeights", "fp8_blockwise_grouped_mm", "NVFP4Tensor", "NVFP4WeightOnlyConfig",
            "NVFP4DynamicActivationNVFP4WeightConfig", "QuantizeTensorToNVFP4Kwargs", "per_tensor_amax_to_scale", "NVFP4ExpertWeights",
@@ -36,4 +43,5 @@ __all__ = ["Float8BlockwiseExpertWeights", "fp8_blockwise_grouped_mm", "NVFP4Ten
            "_to_mxfp8_then_scaled_mm", "mx_mm", "Float8TrainingOpConfig", "Float8TrainingRecipe", "Float8TrainingWeightWrapperTensor",
            "_Float8GroupedMM", "_to_fp8_rowwise_then_scaled_grouped_mm", "fp8_blockwise_mm", "Float8BlockwiseLinear",
            "Float8BlockwiseLinearConfig", "_Float8BlockwiseGroupedMM", "_to_fp8_blockwise_then_scaled_grouped_mm",
-           "_to_fp8_blockwise_then_emulated_scaled_grouped_mm"]
+           "_to_fp8_blockwise_then_emulated_scaled_grouped_mm",
+           "NVFP4Linear", "NVFP4TrainingConfig", "nvfp4_linear", "DEFAULT_SIGN_VECTOR", "get_wgrad_sign_vector"]

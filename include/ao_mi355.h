@@ -907,6 +907,46 @@ const char* ao_nvfp4_linear_kernel_name(int kind, int64_t M, int64_t N, int64_t 
  * linears (0 the product route, 1 streaming, 2 tiled); the route query reports the forced form. */
 int ao_nvfp4_linear_set_form(int form);
 
+/* ---- NVFP4 training: the casts and the GEMM epilogue of prototype/moe_training/nvfp4_training (nvfp4_train_kernels.hip) --
+ * The reference runs on sm100 only (Triton TMA and CuteDSL casts, cuBLAS scaled_mm).  The arithmetic is TransformerEngine's scale chain as
+ * test/prototype/moe_training/nvfp4_training/nvfp4_reference.py states it -- csrc/quant_math.h ("NVFP4 training") -- and NOT
+ * ao_nvfp4_quantize's: the block scale is rounded once and has no lower clamp, and the per-tensor amax is folded into an encode scale.
+ * Codes are packed two a byte, element 2i in the low nibble; block scales are float8_e4m3fn bytes, ROW-MAJOR [rows][cols / 16] (what
+ * ao_nvfp4_scaled_mm reads; the reference's 128 x 4 swizzle exists for cuBLAS).  sign_mask is the 16-point randomized Hadamard transform's
+ * sign vector as a 16-bit mask: bit i set means s_i = -1.  NaN and Inf inputs are outside the contract.  Every per-tensor value is read
+ * through a device pointer: no host read, every entry is graph-capturable.  Null pointers and bad shapes are rejected on the host before
+ * any launch. */
+/* Replaces triton_rht_amax / cutedsl_rht_amax (nvfp4_training/hadamard_amax_triton.py; nvfp4_reference.reference_rht_amax): x bf16 [M][N],
+ * M and N multiples of 16 -> out2[0] = max|bf16(RHT(x^T))|, the transform along M in runs of 16 (0 and no transform when want_rht == 0),
+ * out2[1] = max|x|, both fp32 on the device.  Clear, then an atomic max over the non-negative bit patterns.  x 16-byte, out2 4-byte
+ * aligned. */
+int ao_nvfp4_train_amax(const uint16_t* x, float* out2, int64_t M, int64_t N, uint32_t sign_mask, int want_rht, void* stream);
+/* Replaces triton_rht_quantize_row_col / cutedsl_rht_quantize_row_col (nvfp4_training/hadamard_quantize_row_col_triton.py;
+ * nvfp4_reference.reference_rht_quantize_row_col with layout="plain"): ONE read of x bf16 [M][N] gives the rowwise 1 x 16 cast of x
+ * (row_q [M][N/2], row_s [M][N/16], under the amax amax2[1]) and the 1 x 16 cast of bf16(RHT(x^T)) written transposed (col_q [N][M/2],
+ * col_s [N][M/16], under amax2[0]).  A null pair of outputs skips that direction.  sr_seed == NULL: round to nearest even.  Otherwise
+ * stochastic rounding of BOTH outputs (this library's contract: Philox4x32-10 keyed by *sr_seed, counter (group of 8 codes, offset, stream),
+ * stream 0 the row and 1 the column output, offsets *row_offset and *col_offset, their low 32 bits; quant_math.h), all three device int64
+ * pointers.  The bytes depend on (seed, offset) only.  M and N multiples of 16, N > 0 (M == 0: OK, nothing launched).  x 16-byte, the
+ * codes, the seed and the offsets 8-byte, amax2 4-byte aligned. */
+int ao_nvfp4_train_quantize_row_col(const uint16_t* x, const float* amax2, uint32_t sign_mask, const int64_t* sr_seed, const int64_t* col_offset,
+                                    const int64_t* row_offset, uint8_t* col_q, uint8_t* col_s, uint8_t* row_q, uint8_t* row_s, int64_t M, int64_t N,
+                                    void* stream);
+/* Replaces triton_weight_quantize_2d / cutedsl_weight_quantize_2d (nvfp4_training/quantize_2d_triton.py;
+ * nvfp4_reference.reference_weight_quantize_2d with layout="plain"): w bf16 [N][K] under 16 x 16 block scales, no Hadamard transform,
+ * round to nearest even, *amax = max|w| on the device.  q [N][K/2], s [N][K/16] with a block's scale replicated over its 16 rows; the same
+ * read gives the cast of w^T, qt [K][N/2], st [K][N/16]: the same block scales and the codes of the same values.  N and K multiples of 16,
+ * K > 0.  w 16-byte, the codes 8-byte, amax 4-byte aligned. */
+int ao_nvfp4_train_quantize_weight_2d(const uint16_t* w, const float* amax, uint8_t* q, uint8_t* s, uint8_t* qt, uint8_t* st, int64_t N, int64_t K,
+                                      void* stream);
+/* Replaces torch.nn.functional.scaled_mm on e2m1 codes with BlockWise1x16 + TensorWise scales (nvfp4_training/nvfp4_linear.py:213-223,
+ * :278-306): acc = sum_k (a_code a_s8)(b_code b_s8) in fp32;  out = bf16(acc (pa pb)), the product of the two fp32 scales taken in fp32,
+ * ONE rounding, no bias.  (ao_nvfp4_linear rounds the accumulator and P to bf16 first: the inference reference's chain.)  The kernels
+ * and the route of ao_nvfp4_linear (kind 1); a [M][K/2], a_scale [M][K/16], b [N][K/2], b_scale [N][K/16], pa and pb one fp32 each on the
+ * device, both required.  Shapes and alignment as ao_nvfp4_linear. */
+int ao_nvfp4_scaled_mm(const uint8_t* a, const uint8_t* a_scale, const float* pa, const uint8_t* b, const uint8_t* b_scale, const float* pb,
+                       uint16_t* out, int64_t M, int64_t N, int64_t K, void* stream);
+
 /* ---- NVFP4 grouped GEMM for MoE experts (nvfp4_kernels.hip) -------------------------------------------------------------
  * Replaces NVFP4Tensor's aten._grouped_mm (nvfp4_tensor.py:709-753) on 3-D weights with a per-expert [E, 1, 1] scale
  * (inference_workflow.py:309-319, nvfp4_tensor.py:830-834), which runs only through mslk or scaled_grouped_mm on sm100, and its portable
