@@ -36,9 +36,15 @@ def cast(xb, axis=None, pow2=False):
     """x (bf16 bits [R, C]) cast with one scale per slice along `axis` (-1 / 1: per row, scale [R, 1]; 0: per column, scale [1, C]; None:
     one for the tensor, scale []) -> (codes uint8 [R, C], scale fp32, inv_scale fp32)."""
     x = bf16.from_bits(np.asarray(xb, dtype=np.uint16)).astype(np.float32)
-    amax = np.abs(x).max() if axis is None else np.abs(x).max(axis=axis, keepdims=True)
+    return cast_under(xb, np.abs(x).max() if axis is None else np.abs(x).max(axis=axis, keepdims=True), pow2)
+
+
+def cast_under(xb, amax, pow2=False):
+    """The same cast under a GIVEN amax (fp32, broadcast against x: [R, 1], [1, C] or []), which need not be x's own."""
+    x = bf16.from_bits(np.asarray(xb, dtype=np.uint16)).astype(np.float32)
     scale = amax_to_scale(amax, pow2)
-    t = np.clip((x * scale).astype(np.float32), -fp8_ref.E4M3_MAX, fp8_ref.E4M3_MAX)
+    with np.errstate(over="ignore"):  # (under an amax below x's own a product may overflow: inf, clamped to 448 like any other)
+        t = np.clip((x * scale).astype(np.float32), -fp8_ref.E4M3_MAX, fp8_ref.E4M3_MAX)
     return fp8_ref.f32_to_e4m3(t), scale, (np.float32(1.0) / scale).astype(np.float32)
 
 
