@@ -25,7 +25,7 @@ _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
 _INT = ctypes.c_int
 
-# name -> argtypes (restype is int for all but the two noted)
+# name -> argtypes (restype: const char* for the *_kernel_name queries, int for all others but those lib() notes)
 _SIGNATURES = {
     "ao_abi_version": [],
     "ao_prof_enable": [_INT],
@@ -201,24 +201,9 @@ def lib():
                 continue
             fn = getattr(l, name)  # AttributeError if the .so is stale
             fn.argtypes = argtypes
-            fn.restype = _INT
+            fn.restype = ctypes.c_char_p if name.endswith("_kernel_name") else _INT
         l.ao_last_error.argtypes = []
         l.ao_last_error.restype = ctypes.c_char_p
-        l.ao_int4_mm_kernel_name.restype = ctypes.c_char_p
-        if hasattr(l, "ao_gemm8_kernel_name"):
-            l.ao_gemm8_kernel_name.restype = ctypes.c_char_p
-        if hasattr(l, "ao_mx_linear_kernel_name"):
-            l.ao_mx_linear_kernel_name.restype = ctypes.c_char_p
-        if hasattr(l, "ao_fp8_block_linear_kernel_name"):
-            l.ao_fp8_block_linear_kernel_name.restype = ctypes.c_char_p
-        if hasattr(l, "ao_fp8_block_grouped_mm_kernel_name"):
-            l.ao_fp8_block_grouped_mm_kernel_name.restype = ctypes.c_char_p
-        if hasattr(l, "ao_nvfp4_linear_kernel_name"):
-            l.ao_nvfp4_linear_kernel_name.restype = ctypes.c_char_p
-        if hasattr(l, "ao_nvfp4_grouped_mm_kernel_name"):
-            l.ao_nvfp4_grouped_mm_kernel_name.restype = ctypes.c_char_p
-        if hasattr(l, "ao_fp8_int4_kernel_name"):
-            l.ao_fp8_int4_kernel_name.restype = ctypes.c_char_p
         l.ao_moe_padded_rows.restype = _I64
         l.ao_mx_blocked_rows.restype = _I64
         l.ao_allreduce_flag_bytes.restype = _I64

@@ -26,6 +26,9 @@ const Int4Force& int4_force();  // the calling thread's
 // opt a kernel into > 48 KiB of dynamic LDS on the current device (once per kernel and device; runtime.hip)
 int ensure_dynamic_lds(const void* kernel, size_t bytes, const char* what);
 
+// whether p sits on a multiple of a, a power of two (null does: the entries check their required pointers on their own)
+inline bool aligned_to(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
 #define AO_REQUIRE(cond, ...)                \
   do {                                       \
     if (!(cond)) {                           \

@@ -422,22 +422,14 @@ __global__ __launch_bounds__(64 * WAVES) void fp8_block_grouped_stream_kernel(Gr
 // (4 m-tiles x 16 waves: the meeting buffer would pass the static LDS; the stream-form plan caps 4 m-tiles at 8 waves)
 template <bool CAST>
 int launch_stream(const TwoFormRoute& r, const BlockArgs& a, hipStream_t st) {
-  if (int rc = with_stream_form<false>("fp8_block_stream_kernel", r, [&](auto mt, auto waves) {
-        constexpr int MT = decltype(mt)::value, WAVES = decltype(waves)::value;
-        ao::launch(fp8_block_stream_kernel<CAST, MT, WAVES>, dim3(r.grid_x, r.grid_y), dim3(64 * WAVES), 0, st, a);
-      }))
-    return rc;
-  AO_LAUNCH_CHECK("fp8_block_stream_kernel launch");
-  return AO_OK;
+  return launch_stream_form<false>("fp8_block_stream_kernel", "fp8_block_stream_kernel launch", r, a, st, [](auto mt, auto waves) {
+    return fp8_block_stream_kernel<CAST, decltype(mt)::value, decltype(waves)::value>;
+  });
 }
 
 int launch_tile(const TwoFormRoute& r, const BlockArgs& a, hipStream_t st) {
-  constexpr size_t smem = 2 * kStageBytes;
-  auto kern = fp8_block_tile_kernel<false>;
-  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), smem, "hipFuncSetAttribute(fp8_block_tile_kernel)")) return rc;
-  ao::launch(kern, dim3(r.grid_x, r.grid_y), dim3(256), smem, st, a);
-  AO_LAUNCH_CHECK("fp8_block_tile_kernel launch");
-  return AO_OK;
+  return launch_tile_form(fp8_block_tile_kernel<false>, "fp8_block_tile_kernel launch", r, a, st, 2 * kStageBytes,
+                          "hipFuncSetAttribute(fp8_block_tile_kernel)");
 }
 
 int check_linear(const char* fn, int64_t M, int64_t N, int64_t K) {
@@ -446,10 +438,8 @@ int check_linear(const char* fn, int64_t M, int64_t N, int64_t K) {
   return AO_OK;
 }
 
-bool aligned_to(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 // ---- the grouped route ------------------------------------------------------------------------------------------------------------
-// Without a sync the host knows only M_total and E: the route keys on the mean group size ceil(M_total / E).
+// (on the mean group size: grouped_two_form_route)
 constexpr int kGroupedStreamMaxRows = AO_FP8_BLOCK_GROUPED_STREAM_MAX_ROWS;
 
 thread_local int g_grouped_form = 0;  // ao_fp8_block_grouped_mm_set_form: 0 the product route, 1 stream, 2 tile
@@ -463,33 +453,17 @@ bool grouped_shape_ok(int64_t M_total, int64_t N, int64_t K, int64_t E) {
 // 2: fp8_block_grouped_tile_kernel = fp8_block_tile_kernel<true>, grid (ceil(N / 128), ceil(M_total / 128) + E)
 TwoFormRoute grouped_route(int64_t M_total, int64_t N, int64_t K, int64_t E) {
   if (!grouped_shape_ok(M_total, N, K, E)) return TwoFormRoute{};
-  const int64_t mean = (M_total + E - 1) / E;
-  const int form = g_grouped_form != 0 ? g_grouped_form : (mean <= kGroupedStreamMaxRows ? 1 : 2);
-  TwoFormRoute r = two_form_route(form, form == 1 ? mean : M_total, N, K, 128);
-  if (r.kernel == 0) return TwoFormRoute{};
-  const int64_t gy = form == 1 ? E : (int64_t)r.grid_y + E;
-  if (gy > 65535) return TwoFormRoute{};
-  r.grid_y = (int)gy;
-  return r;
+  return grouped_two_form_route(g_grouped_form, kGroupedStreamMaxRows, M_total, N, K, E, 128);
 }
 
 int launch_grouped_stream(const TwoFormRoute& r, const GroupedArgs& a, hipStream_t st) {
-  if (int rc = with_stream_form<false>("fp8_block_grouped_stream_kernel", r, [&](auto mt, auto waves) {
-        constexpr int MT = decltype(mt)::value, WAVES = decltype(waves)::value;
-        ao::launch(fp8_block_grouped_stream_kernel<MT, WAVES>, dim3(r.grid_x, r.grid_y), dim3(64 * WAVES), 0, st, a);
-      }))
-    return rc;
-  AO_LAUNCH_CHECK("fp8_block_grouped_stream_kernel launch");
-  return AO_OK;
+  return launch_stream_form<false>("fp8_block_grouped_stream_kernel", "fp8_block_grouped_stream_kernel launch", r, a, st,
+                                   [](auto mt, auto waves) { return fp8_block_grouped_stream_kernel<decltype(mt)::value, decltype(waves)::value>; });
 }
 
 int launch_grouped_tile(const TwoFormRoute& r, const GroupedArgs& a, hipStream_t st) {
-  constexpr size_t smem = 2 * kStageBytes;
-  auto kern = fp8_block_tile_kernel<true>;
-  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), smem, "hipFuncSetAttribute(fp8_block_tile_kernel<GROUPED>)")) return rc;
-  ao::launch(kern, dim3(r.grid_x, r.grid_y), dim3(256), smem, st, a);
-  AO_LAUNCH_CHECK("fp8_block_grouped_tile_kernel (fp8_block_tile_kernel<GROUPED>) launch");
-  return AO_OK;
+  return launch_tile_form(fp8_block_tile_kernel<true>, "fp8_block_grouped_tile_kernel (fp8_block_tile_kernel<GROUPED>) launch", r, a, st,
+                          2 * kStageBytes, "hipFuncSetAttribute(fp8_block_tile_kernel<GROUPED>)");
 }
 
 }  // namespace
@@ -531,25 +505,14 @@ extern "C" int ao_fp8_quantize_block_128x128(const uint16_t* w, uint8_t* q, floa
 }
 
 extern "C" int ao_fp8_block_linear_route(int64_t M, int64_t N, int64_t K, int32_t* out, int cap) {
-  AO_REQUIRE_PTR(out);
-  AO_REQUIRE(cap >= 7, "ao_fp8_block_linear_route: cap must be >= 7, got %d", cap);
-  write_route(block_route(M, N, K), out);
-  return AO_OK;
+  return route_export(__func__, block_route(M, N, K), out, cap);
 }
 
 extern "C" const char* ao_fp8_block_linear_kernel_name(int64_t M, int64_t N, int64_t K) {
-  switch (block_route(M, N, K).kernel) {
-    case 1: return "fp8_block_stream_kernel";
-    case 2: return "fp8_block_tile_kernel";
-    default: return "invalid";
-  }
+  return route_kernel_name(block_route(M, N, K), "fp8_block_stream_kernel", "fp8_block_tile_kernel");
 }
 
-extern "C" int ao_fp8_block_linear_set_form(int form) {
-  AO_REQUIRE(form >= 0 && form <= 2, "ao_fp8_block_linear_set_form: form must be 0 (route), 1 (stream) or 2 (tile), got %d", form);
-  g_form = form;
-  return AO_OK;
-}
+extern "C" int ao_fp8_block_linear_set_form(int form) { return set_forced_form(__func__, form, g_form); }
 
 extern "C" int ao_fp8_block_linear(const uint8_t* a, const float* a_scale, const uint8_t* b, const float* b_scale, const uint16_t* bias,
                                    uint16_t* out, int64_t M, int64_t N, int64_t K, void* stream) {
@@ -591,25 +554,14 @@ extern "C" int ao_fp8_block_dynamic_linear(const uint16_t* x, const uint8_t* b, 
 }
 
 extern "C" int ao_fp8_block_grouped_mm_route(int64_t M_total, int64_t N, int64_t K, int64_t E, int32_t* out, int cap) {
-  AO_REQUIRE_PTR(out);
-  AO_REQUIRE(cap >= 7, "ao_fp8_block_grouped_mm_route: cap must be >= 7, got %d", cap);
-  write_route(grouped_route(M_total, N, K, E), out);
-  return AO_OK;
+  return route_export(__func__, grouped_route(M_total, N, K, E), out, cap);
 }
 
 extern "C" const char* ao_fp8_block_grouped_mm_kernel_name(int64_t M_total, int64_t N, int64_t K, int64_t E) {
-  switch (grouped_route(M_total, N, K, E).kernel) {
-    case 1: return "fp8_block_grouped_stream_kernel";
-    case 2: return "fp8_block_grouped_tile_kernel";
-    default: return "invalid";
-  }
+  return route_kernel_name(grouped_route(M_total, N, K, E), "fp8_block_grouped_stream_kernel", "fp8_block_grouped_tile_kernel");
 }
 
-extern "C" int ao_fp8_block_grouped_mm_set_form(int form) {
-  AO_REQUIRE(form >= 0 && form <= 2, "ao_fp8_block_grouped_mm_set_form: form must be 0 (route), 1 (stream) or 2 (tile), got %d", form);
-  g_grouped_form = form;
-  return AO_OK;
-}
+extern "C" int ao_fp8_block_grouped_mm_set_form(int form) { return set_forced_form(__func__, form, g_grouped_form); }
 
 extern "C" int ao_fp8_block_grouped_mm(const uint8_t* a, const float* a_scale, const uint8_t* b, const float* b_scale, const int32_t* offs,
                                        uint16_t* out, int64_t M_total, int64_t N, int64_t K, int64_t E, void* stream) {

@@ -193,8 +193,6 @@ __global__ __launch_bounds__(256, 2) void fp8_block_grouped_wgrad_kernel(BlockWg
   wgrad_tile<BlockPolicy>(p);
 }
 
-bool aligned_to(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 // both weight-gradient entries; dense: no offs, one group of every token
 int block_wgrad(const char* fn, const uint8_t* g_t, const float* g_inv, const uint8_t* x_t, const float* x_inv, const int32_t* offs, uint16_t* out,
                 int64_t M, int64_t N, int64_t K, int64_t E, void* stream) {

@@ -333,23 +333,15 @@ __global__ __launch_bounds__(256) void mxfp4_quant_kernel(const uint16_t* __rest
 // ---- launches -------------------------------------------------------------------------------------------------------------------
 template <int FMT, int CAST>
 int launch_stream(const TwoFormRoute& r, const MxArgs& a, hipStream_t st) {
-  if (int rc = with_stream_form<true>("mx_linear_stream_kernel", r, [&](auto mt, auto waves) {
-        constexpr int MT = decltype(mt)::value, WAVES = decltype(waves)::value;
-        ao::launch(mx_linear_stream_kernel<FMT, CAST, MT, WAVES>, dim3(r.grid_x, r.grid_y), dim3(64 * WAVES), 0, st, a);
-      }))
-    return rc;
-  AO_LAUNCH_CHECK("mx_linear_stream_kernel launch");
-  return AO_OK;
+  return launch_stream_form<true>("mx_linear_stream_kernel", "mx_linear_stream_kernel launch", r, a, st, [](auto mt, auto waves) {
+    return mx_linear_stream_kernel<FMT, CAST, decltype(mt)::value, decltype(waves)::value>;
+  });
 }
 
 template <int FMT>
 int launch_tile(const TwoFormRoute& r, const MxArgs& a, hipStream_t st) {
-  constexpr size_t smem = 2 * TileCfg<FMT>::STAGE;
-  auto kern = mx_linear_tile_kernel<FMT>;
-  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), smem, "hipFuncSetAttribute(mx_linear_tile_kernel)")) return rc;
-  ao::launch(kern, dim3(r.grid_x, r.grid_y), dim3(256), smem, st, a);
-  AO_LAUNCH_CHECK("mx_linear_tile_kernel launch");
-  return AO_OK;
+  return launch_tile_form(mx_linear_tile_kernel<FMT>, "mx_linear_tile_kernel launch", r, a, st, 2 * TileCfg<FMT>::STAGE,
+                          "hipFuncSetAttribute(mx_linear_tile_kernel)");
 }
 
 int check_linear(const char* fn, int fmt, int64_t M, int64_t N, int64_t K) {
@@ -358,8 +350,6 @@ int check_linear(const char* fn, int fmt, int64_t M, int64_t N, int64_t K) {
              fn, (long long)M, (long long)N, (long long)K);
   return AO_OK;
 }
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 }  // namespace
 }  // namespace ao
@@ -376,7 +366,7 @@ extern "C" int ao_mxfp4_quantize_rowwise(const uint16_t* x, uint8_t* q, uint8_t*
   AO_REQUIRE_PTR(x);
   AO_REQUIRE_PTR(q);
   AO_REQUIRE_PTR(scale_e8m0);
-  AO_REQUIRE(aligned16(x) && aligned16(q), "ao_mxfp4_quantize_rowwise: x and q must be 16-byte aligned");
+  AO_REQUIRE(aligned_to(x, 16) && aligned_to(q, 16), "ao_mxfp4_quantize_rowwise: x and q must be 16-byte aligned");
   const int64_t blocks = R * (C / 32);
   const int64_t grid = (blocks + 255) / 256;
   AO_REQUIRE(grid < (1ll << 31), "ao_mxfp4_quantize_rowwise: tensor too large for one launch");
@@ -390,26 +380,14 @@ extern "C" int ao_mxfp4_quantize_rowwise(const uint16_t* x, uint8_t* q, uint8_t*
 }
 
 extern "C" int ao_mx_linear_route(int fmt, int64_t M, int64_t N, int64_t K, int32_t* out, int cap) {
-  AO_REQUIRE_PTR(out);
-  AO_REQUIRE(cap >= 7, "ao_mx_linear_route: cap must be >= 7, got %d", cap);
-  const TwoFormRoute r = mx_route(fmt, M, N, K);
-  write_route(r, out);
-  return AO_OK;
+  return route_export(__func__, mx_route(fmt, M, N, K), out, cap);
 }
 
 extern "C" const char* ao_mx_linear_kernel_name(int fmt, int64_t M, int64_t N, int64_t K) {
-  switch (mx_route(fmt, M, N, K).kernel) {
-    case 1: return "mx_linear_stream_kernel";
-    case 2: return "mx_linear_tile_kernel";
-    default: return "invalid";
-  }
+  return route_kernel_name(mx_route(fmt, M, N, K), "mx_linear_stream_kernel", "mx_linear_tile_kernel");
 }
 
-extern "C" int ao_mx_linear_set_form(int form) {
-  AO_REQUIRE(form >= 0 && form <= 2, "ao_mx_linear_set_form: form must be 0 (route), 1 (stream) or 2 (tile), got %d", form);
-  g_form = form;
-  return AO_OK;
-}
+extern "C" int ao_mx_linear_set_form(int form) { return set_forced_form(__func__, form, g_form); }
 
 extern "C" int ao_mx_linear(int fmt, const uint8_t* a, const uint8_t* a_scale, const uint8_t* b, const uint8_t* b_scale, const uint16_t* bias,
                             uint16_t* out, int64_t M, int64_t N, int64_t K, void* stream) {
@@ -420,7 +398,7 @@ extern "C" int ao_mx_linear(int fmt, const uint8_t* a, const uint8_t* a_scale, c
   AO_REQUIRE_PTR(a);
   AO_REQUIRE_PTR(a_scale);
   AO_REQUIRE_PTR(out);
-  AO_REQUIRE(aligned16(a) && aligned16(b), "%s: the codes must be 16-byte aligned", __func__);
+  AO_REQUIRE(aligned_to(a, 16) && aligned_to(b, 16), "%s: the codes must be 16-byte aligned", __func__);
   const TwoFormRoute r = mx_route(fmt, M, N, K);
   AO_REQUIRE(r.kernel != 0, "%s: no route for M=%lld N=%lld K=%lld", __func__, (long long)M, (long long)N, (long long)K);
   const MxArgs args{a, a_scale, nullptr, b, b_scale, bias, out, (int)M, (int)N, (int)K};
@@ -444,7 +422,7 @@ extern "C" int ao_mx_dynamic_linear(int fmt, const uint16_t* x, const uint8_t* b
   if (M == 0) return AO_OK;
   AO_REQUIRE_PTR(x);
   AO_REQUIRE_PTR(out);
-  AO_REQUIRE(aligned16(x) && aligned16(b), "%s: x and the codes must be 16-byte aligned", __func__);
+  AO_REQUIRE(aligned_to(x, 16) && aligned_to(b, 16), "%s: x and the codes must be 16-byte aligned", __func__);
   const MxArgs args{nullptr, nullptr, x, b, b_scale, bias, out, (int)M, (int)N, (int)K};
   hipStream_t st = static_cast<hipStream_t>(stream);
   const bool rceil = scaling_mode == AO_MX_SCALE_RCEIL;

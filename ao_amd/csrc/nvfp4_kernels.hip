@@ -474,42 +474,29 @@ __global__ void nvfp4_group_amax_scale_kernel(uint32_t* out, int E) {
 // (4 m-tiles x 16 waves: the meeting buffer would pass the static LDS; the stream-form plan caps 4 m-tiles at 8 waves)
 template <int KIND>
 int launch_stream(const TwoFormRoute& r, const Nvfp4Args& a, hipStream_t st) {
-  if (int rc = with_stream_form<false>("nvfp4_stream_kernel", r, [&](auto mt, auto waves) {
-        constexpr int MT = decltype(mt)::value, WAVES = decltype(waves)::value;
-        ao::launch(nvfp4_stream_kernel<KIND, MT, WAVES, false>, dim3(r.grid_x, r.grid_y), dim3(64 * WAVES), 0, st, a);
-      }))
-    return rc;
-  AO_LAUNCH_CHECK("nvfp4_stream_kernel launch");
-  return AO_OK;
+  return launch_stream_form<false>("nvfp4_stream_kernel", "nvfp4_stream_kernel launch", r, a, st, [](auto mt, auto waves) {
+    return nvfp4_stream_kernel<KIND, decltype(mt)::value, decltype(waves)::value, false>;
+  });
 }
 
 template <int KIND>
 int launch_tile(const TwoFormRoute& r, const Nvfp4Args& a, hipStream_t st) {
-  ao::launch(nvfp4_tile_kernel<KIND, false>, dim3(r.grid_x, r.grid_y), dim3(256), 0, st, a);
-  AO_LAUNCH_CHECK("nvfp4_tile_kernel launch");
-  return AO_OK;
+  return launch_tile_form(nvfp4_tile_kernel<KIND, false>, "nvfp4_tile_kernel launch", r, a, st);
 }
 
 template <int KIND>
 int launch_grouped_stream(const TwoFormRoute& r, const Nvfp4Args& a, hipStream_t st) {
-  if (int rc = with_stream_form<false>("nvfp4_grouped_stream_kernel", r, [&](auto mt, auto waves) {
-        constexpr int MT = decltype(mt)::value, WAVES = decltype(waves)::value;
-        ao::launch(nvfp4_stream_kernel<KIND, MT, WAVES, true>, dim3(r.grid_x, r.grid_y), dim3(64 * WAVES), 0, st, a);
-      }))
-    return rc;
-  AO_LAUNCH_CHECK("nvfp4_grouped_stream_kernel (nvfp4_stream_kernel<GROUPED>) launch");
-  return AO_OK;
+  return launch_stream_form<false>("nvfp4_grouped_stream_kernel", "nvfp4_grouped_stream_kernel (nvfp4_stream_kernel<GROUPED>) launch", r, a, st,
+                                   [](auto mt, auto waves) { return nvfp4_stream_kernel<KIND, decltype(mt)::value, decltype(waves)::value, true>; });
 }
 
 template <int KIND>
 int launch_grouped_tile(const TwoFormRoute& r, const Nvfp4Args& a, hipStream_t st) {
-  ao::launch(nvfp4_tile_kernel<KIND, true>, dim3(r.grid_x, r.grid_y), dim3(256), 0, st, a);
-  AO_LAUNCH_CHECK("nvfp4_grouped_tile_kernel (nvfp4_tile_kernel<GROUPED>) launch");
-  return AO_OK;
+  return launch_tile_form(nvfp4_tile_kernel<KIND, true>, "nvfp4_grouped_tile_kernel (nvfp4_tile_kernel<GROUPED>) launch", r, a, st);
 }
 
 // ---- the grouped route ------------------------------------------------------------------------------------------------------------
-// Without a sync the host knows only M_total and E: the route keys on the mean group size ceil(M_total / E).
+// (on the mean group size: grouped_two_form_route)
 constexpr int kGroupedStreamMaxRows = AO_NVFP4_GROUPED_STREAM_MAX_ROWS;
 
 thread_local int g_grouped_form = 0;  // ao_nvfp4_grouped_mm_set_form: 0 the product route, 1 stream, 2 tile
@@ -523,17 +510,8 @@ bool nvfp4_grouped_shape_ok(int kind, int64_t M_total, int64_t N, int64_t K, int
 // 2: nvfp4_grouped_tile_kernel, grid (ceil(N / 64), ceil(M_total / 64) + E)
 TwoFormRoute nvfp4_grouped_route(int kind, int64_t M_total, int64_t N, int64_t K, int64_t E) {
   if (!nvfp4_grouped_shape_ok(kind, M_total, N, K, E)) return TwoFormRoute{};
-  const int64_t mean = (M_total + E - 1) / E;
-  const int form = g_grouped_form != 0 ? g_grouped_form : (mean <= kGroupedStreamMaxRows ? 1 : 2);
-  TwoFormRoute r = two_form_route(form, form == 1 ? mean : M_total, N, K, 64);
-  if (r.kernel == 0) return TwoFormRoute{};
-  const int64_t gy = form == 1 ? E : (int64_t)r.grid_y + E;
-  if (gy > 65535) return TwoFormRoute{};
-  r.grid_y = (int)gy;
-  return r;
+  return grouped_two_form_route(g_grouped_form, kGroupedStreamMaxRows, M_total, N, K, E, 64);
 }
-
-bool aligned_to(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 int check_shape(const char* fn, int kind, int64_t M, int64_t N, int64_t K) {
   AO_REQUIRE(nvfp4_shape_ok(kind, M, N, K),
@@ -593,25 +571,14 @@ extern "C" int ao_nvfp4_quantize(const uint16_t* x, const float* per_tensor_scal
 }
 
 extern "C" int ao_nvfp4_linear_route(int kind, int64_t M, int64_t N, int64_t K, int32_t* out, int cap) {
-  AO_REQUIRE_PTR(out);
-  AO_REQUIRE(cap >= 7, "ao_nvfp4_linear_route: cap must be >= 7, got %d", cap);
-  write_route(nvfp4_route(kind, M, N, K), out);
-  return AO_OK;
+  return route_export(__func__, nvfp4_route(kind, M, N, K), out, cap);
 }
 
 extern "C" const char* ao_nvfp4_linear_kernel_name(int kind, int64_t M, int64_t N, int64_t K) {
-  switch (nvfp4_route(kind, M, N, K).kernel) {
-    case 1: return "nvfp4_stream_kernel";
-    case 2: return "nvfp4_tile_kernel";
-    default: return "invalid";
-  }
+  return route_kernel_name(nvfp4_route(kind, M, N, K), "nvfp4_stream_kernel", "nvfp4_tile_kernel");
 }
 
-extern "C" int ao_nvfp4_linear_set_form(int form) {
-  AO_REQUIRE(form >= 0 && form <= 2, "ao_nvfp4_linear_set_form: form must be 0 (route), 1 (stream) or 2 (tile), got %d", form);
-  g_form = form;
-  return AO_OK;
-}
+extern "C" int ao_nvfp4_linear_set_form(int form) { return set_forced_form(__func__, form, g_form); }
 
 extern "C" int ao_nvfp4_wo_linear(const uint16_t* x, const uint8_t* wq, const uint8_t* w_scale, const float* w_per_tensor_scale,
                                   const uint16_t* bias, uint16_t* out, int64_t M, int64_t N, int64_t K, void* stream) {
@@ -669,25 +636,14 @@ extern "C" int ao_nvfp4_scaled_mm(const uint8_t* a, const uint8_t* a_scale, cons
 
 // ---- grouped (MoE experts) ----------------------------------------------------------------------------------------------------------
 extern "C" int ao_nvfp4_grouped_mm_route(int kind, int64_t M_total, int64_t N, int64_t K, int64_t E, int32_t* out, int cap) {
-  AO_REQUIRE_PTR(out);
-  AO_REQUIRE(cap >= 7, "ao_nvfp4_grouped_mm_route: cap must be >= 7, got %d", cap);
-  write_route(nvfp4_grouped_route(kind, M_total, N, K, E), out);
-  return AO_OK;
+  return route_export(__func__, nvfp4_grouped_route(kind, M_total, N, K, E), out, cap);
 }
 
 extern "C" const char* ao_nvfp4_grouped_mm_kernel_name(int kind, int64_t M_total, int64_t N, int64_t K, int64_t E) {
-  switch (nvfp4_grouped_route(kind, M_total, N, K, E).kernel) {
-    case 1: return "nvfp4_grouped_stream_kernel";
-    case 2: return "nvfp4_grouped_tile_kernel";
-    default: return "invalid";
-  }
+  return route_kernel_name(nvfp4_grouped_route(kind, M_total, N, K, E), "nvfp4_grouped_stream_kernel", "nvfp4_grouped_tile_kernel");
 }
 
-extern "C" int ao_nvfp4_grouped_mm_set_form(int form) {
-  AO_REQUIRE(form >= 0 && form <= 2, "ao_nvfp4_grouped_mm_set_form: form must be 0 (route), 1 (stream) or 2 (tile), got %d", form);
-  g_grouped_form = form;
-  return AO_OK;
-}
+extern "C" int ao_nvfp4_grouped_mm_set_form(int form) { return set_forced_form(__func__, form, g_grouped_form); }
 
 extern "C" int ao_nvfp4_grouped_mm(int kind, const uint16_t* x, const uint8_t* a, const uint8_t* a_scale, const uint8_t* b, const uint8_t* b_scale,
                                    const float* pa, const float* pb, const int32_t* offs, uint16_t* out, int64_t M_total, int64_t N, int64_t K,

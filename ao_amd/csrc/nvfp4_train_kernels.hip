@@ -218,8 +218,6 @@ __global__ __launch_bounds__(kThreads) void nvfp4_train_amax_kernel(const uint16
   }
 }
 
-bool aligned_to(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 int check_mn(const char* fn, int64_t M, int64_t N) {
   AO_REQUIRE(M >= 0 && N > 0 && M % 16 == 0 && N % 16 == 0 && M < (1ll << 31) && N < (1ll << 31) && M * N < (1ll << 40),
              "%s: bad shape %lld x %lld (both multiples of 16, columns > 0, each below 2^31 and the product below 2^40)", fn, (long long)M,

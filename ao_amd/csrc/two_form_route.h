@@ -1,8 +1,15 @@
-// Host only: the route of a linear family that has a weight-streaming form and an LDS-tiled form -- the MX dense linears
-// (mx_linear_kernels.hip) and the int8 / float8 weight-only linears (wo8_kernels.hip).  A family keeps what it measured or what its
+// Host only: the frame of a linear family that has a weight-streaming form and an LDS-tiled form -- the MX dense linears
+// (mx_linear_kernels.hip), the int8 / float8 weight-only linears (wo8_kernels.hip), the blockwise float8 linears, dense and grouped
+// (fp8_block_kernels.hip), and the NVFP4 linears, dense and grouped (nvfp4_kernels.hip).  A family keeps what it measured or what its
 // kernels need: its shape check, the row counts at which it hands over from the stream form to the tiled form, the tile edge of its
-// tiled form and its own thread-local forced form (ao_*_linear_set_form).  The plan of either form, the grid-row cap, the fields
-// ao_*_linear_route report and the compile-time (m-tiles, waves) pair of a stream-form launch are here, once.
+// tiled form, its own thread-local forced form (ao_*_set_form), its argument structs, its kernels, the pointer and alignment checks
+// of its entries and the choice of template arguments.  Here, once:
+//   the route: the plan of either form and the grid-row cap (two_form_route), and the grouped route on the mean group size with its
+//     + E grid rows (grouped_two_form_route);
+//   the bodies of the exports: ao_*_route (route_export, the seven fields of write_route), ao_*_kernel_name (route_kernel_name) and
+//     ao_*_set_form (set_forced_form);
+//   the launches: the compile-time (m-tiles, waves) pair of a stream-form launch (with_stream_form, launch_stream_form) and the
+//     tiled form's launch with or without dynamic LDS (launch_tile_form).
 #pragma once
 #include <stdint.h>
 
@@ -13,7 +20,7 @@
 
 namespace ao {
 
-// ao_mx_linear_route and ao_wo8_linear_route write these seven fields, in this order (write_route)
+// the ao_*_route exports write these seven fields, in this order (write_route)
 struct TwoFormRoute {
   int kernel = 0;  // 0 invalid, 1 the stream form, 2 the tiled form
   int waves = 0;   // waves per workgroup
@@ -67,6 +74,38 @@ inline TwoFormRoute two_form_route(int form, int64_t M, int64_t N, int64_t K, in
   return r;
 }
 
+// The grouped (MoE experts) route.  Without a sync the host knows only M_total and E, so the family's seam meets the mean group size
+// ceil(M_total / E).  The stream form: grid (ceil(N / 16), E), m-tiles and waves of the stream plan at the mean size.  The tiled form:
+// grid (ceil(N / edge), ceil(M_total / edge) + E), a group's last tile being ragged.  forced: the family's forced form, 0 for its seam.
+inline TwoFormRoute grouped_two_form_route(int forced, int seam, int64_t M_total, int64_t N, int64_t K, int64_t E, int tile_edge) {
+  const int64_t mean = (M_total + E - 1) / E;
+  const int form = forced != 0 ? forced : (mean <= seam ? 1 : 2);
+  TwoFormRoute r = two_form_route(form, form == 1 ? mean : M_total, N, K, tile_edge);
+  if (r.kernel == 0) return TwoFormRoute{};
+  const int64_t gy = form == 1 ? E : (int64_t)r.grid_y + E;
+  if (gy > 65535) return TwoFormRoute{};
+  r.grid_y = (int)gy;
+  return r;
+}
+
+// ---- the bodies of a family's exports; fn: the entry's own name, as its errors carry it ---------------------------------------------
+inline int route_export(const char* fn, const TwoFormRoute& r, int32_t* out, int cap) {
+  AO_REQUIRE_PTR_FN(fn, out);
+  AO_REQUIRE(cap >= 7, "%s: cap must be >= 7, got %d", fn, cap);
+  write_route(r, out);
+  return AO_OK;
+}
+
+inline const char* route_kernel_name(const TwoFormRoute& r, const char* stream, const char* tile) {
+  return r.kernel == 1 ? stream : (r.kernel == 2 ? tile : "invalid");
+}
+
+inline int set_forced_form(const char* fn, int form, int& forced) {
+  AO_REQUIRE(form >= 0 && form <= 2, "%s: form must be 0 (route), 1 (stream) or 2 (tile), got %d", fn, form);
+  forced = form;
+  return AO_OK;
+}
+
 // Calls launch(m-tiles, waves) with the stream-form route's pair as std::integral_constants, for the kernel templates of a family; a
 // pair stream_form_plan never produces is an error.  MT4_W16: whether the family has a kernel of 4 m-tiles x 16 waves (the plan caps
 // 4 m-tiles at 8 waves, so nothing reaches it; a family whose meeting buffer would pass the static LDS limit there must not compile it).
@@ -95,6 +134,29 @@ int with_stream_form(const char* kernel, const TwoFormRoute& r, Launch&& launch)
     set_error("%s: no instantiation for %d m-tiles x %d waves", kernel, r.mt, r.waves);
     return AO_ERR_INVALID_ARGUMENT;
   }
+  return AO_OK;
+}
+
+// The stream-form launch of a family: instance(m-tiles, waves) returns the kernel instance of the route's pair (integral constants, as
+// in with_stream_form); `kernel` names it in the no-instantiation error, `what` is the text a failed launch reports.
+template <bool MT4_W16, typename Args, typename Instance>
+int launch_stream_form(const char* kernel, const char* what, const TwoFormRoute& r, const Args& a, hipStream_t st, Instance&& instance) {
+  if (int rc = with_stream_form<MT4_W16>(kernel, r, [&](auto mt, auto waves) {
+        ao::launch(instance(mt, waves), dim3(r.grid_x, r.grid_y), dim3(64 * decltype(waves)::value), 0, st, a);
+      }))
+    return rc;
+  AO_LAUNCH_CHECK(what);
+  return AO_OK;
+}
+
+// The tiled-form launch: four waves on the route's grid.  lds_bytes of dynamic LDS, opted into under the text lds_what (0: none).
+template <typename Kernel, typename Args>
+int launch_tile_form(Kernel kernel, const char* what, const TwoFormRoute& r, const Args& a, hipStream_t st, size_t lds_bytes = 0,
+                     const char* lds_what = nullptr) {
+  if (lds_bytes != 0)
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), lds_bytes, lds_what)) return rc;
+  ao::launch(kernel, dim3(r.grid_x, r.grid_y), dim3(256), lds_bytes, st, a);
+  AO_LAUNCH_CHECK(what);
   return AO_OK;
 }
 

@@ -248,23 +248,15 @@ __global__ __launch_bounds__(256) void wo8_tile_kernel(Wo8Args p) {
 // (4 m-tiles x 16 waves: the meeting buffer would pass the static LDS; the stream-form plan caps 4 m-tiles at 8 waves)
 template <int FMT>
 int launch_stream(const TwoFormRoute& r, const Wo8Args& a, hipStream_t st) {
-  if (int rc = with_stream_form<false>("wo8_stream_kernel", r, [&](auto mt, auto waves) {
-        constexpr int MT = decltype(mt)::value, WAVES = decltype(waves)::value;
-        ao::launch(wo8_stream_kernel<FMT, MT, WAVES>, dim3(r.grid_x, r.grid_y), dim3(64 * WAVES), 0, st, a);
-      }))
-    return rc;
-  AO_LAUNCH_CHECK("wo8_stream_kernel launch");
-  return AO_OK;
+  return launch_stream_form<false>("wo8_stream_kernel", "wo8_stream_kernel launch", r, a, st, [](auto mt, auto waves) {
+    return wo8_stream_kernel<FMT, decltype(mt)::value, decltype(waves)::value>;
+  });
 }
 
 template <int FMT>
 int launch_tile(const TwoFormRoute& r, const Wo8Args& a, hipStream_t st) {
-  ao::launch(wo8_tile_kernel<FMT>, dim3(r.grid_x, r.grid_y), dim3(256), 0, st, a);
-  AO_LAUNCH_CHECK("wo8_tile_kernel launch");
-  return AO_OK;
+  return launch_tile_form(wo8_tile_kernel<FMT>, "wo8_tile_kernel launch", r, a, st);
 }
-
-bool aligned_to(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 }  // namespace
 }  // namespace ao
@@ -272,18 +264,10 @@ bool aligned_to(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) ==
 using namespace ao;
 
 extern "C" int ao_wo8_linear_route(int fmt, int64_t M, int64_t N, int64_t K, int32_t* out, int cap) {
-  AO_REQUIRE_PTR(out);
-  AO_REQUIRE(cap >= 7, "ao_wo8_linear_route: cap must be >= 7, got %d", cap);
-  const TwoFormRoute r = wo8_route(fmt, M, N, K);
-  write_route(r, out);
-  return AO_OK;
+  return route_export(__func__, wo8_route(fmt, M, N, K), out, cap);
 }
 
-extern "C" int ao_wo8_linear_set_form(int form) {
-  AO_REQUIRE(form >= 0 && form <= 2, "ao_wo8_linear_set_form: form must be 0 (route), 1 (stream) or 2 (tile), got %d", form);
-  g_form = form;
-  return AO_OK;
-}
+extern "C" int ao_wo8_linear_set_form(int form) { return set_forced_form(__func__, form, g_form); }
 
 extern "C" int ao_wo8_linear(int fmt, const uint16_t* x, const void* wq, const float* w_scale, int64_t scale_count, const uint16_t* bias,
                              uint16_t* out, int64_t M, int64_t N, int64_t K, void* stream) {

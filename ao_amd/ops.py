@@ -1491,22 +1491,34 @@ def mx_quantize(x: torch.Tensor, fmt: int, scaling_mode="rceil"):
 MX_LINEAR_KERNELS = {0: "invalid", 1: "mx_linear_stream_kernel", 2: "mx_linear_tile_kernel"}
 
 
+# The queries of the two-form linear families (csrc/two_form_route.h): the C entry by name, then its integer arguments.
+def _two_form_route(entry, kernels, *ints):
+    out = (ctypes.c_int32 * 7)()
+    _lib.check(getattr(_lib.lib(), entry)(*map(int, ints), out, 7))
+    kernel, waves, mt, tile_m, tile_n, gx, gy = list(out)
+    return {"kernel": kernels.get(kernel, "invalid"), "waves": waves, "m_tiles": mt, "tile_m": tile_m, "tile_n": tile_n, "grid": (gx, gy)}
+
+
+def _two_form_kernel_name(entry, *ints):
+    return getattr(_lib.lib(), entry)(*map(int, ints)).decode()
+
+
+def _two_form_set_form(entry, form):
+    _lib.check(getattr(_lib.lib(), entry)(int(form)))
+
+
 def mx_linear_route(fmt: int, m: int, n: int, k: int) -> dict:
     """The route mx_mm / mx_linear launch for a shape (host logic only, ao_mx_linear_route)."""
-    out = (ctypes.c_int32 * 7)()
-    _lib.check(_lib.lib().ao_mx_linear_route(int(fmt), int(m), int(n), int(k), out, 7))
-    kernel, waves, mt, tile_m, tile_n, gx, gy = list(out)
-    return {"kernel": MX_LINEAR_KERNELS.get(kernel, "invalid"), "waves": waves, "m_tiles": mt, "tile_m": tile_m, "tile_n": tile_n,
-            "grid": (gx, gy)}
+    return _two_form_route("ao_mx_linear_route", MX_LINEAR_KERNELS, fmt, m, n, k)
 
 
 def mx_linear_kernel_name(fmt: int, m: int, n: int, k: int) -> str:
-    return _lib.lib().ao_mx_linear_kernel_name(int(fmt), int(m), int(n), int(k)).decode()
+    return _two_form_kernel_name("ao_mx_linear_kernel_name", fmt, m, n, k)
 
 
 def mx_linear_set_form(form: int) -> None:
     """Measurement only: 0 the product route, 1 the streaming form, 2 the tiled form (calling thread)."""
-    _lib.check(_lib.lib().ao_mx_linear_set_form(int(form)))
+    _two_form_set_form("ao_mx_linear_set_form", form)
 
 
 def _mx_operands(name, fmt, b, b_scale, bias, k_from_a):
@@ -1582,16 +1594,12 @@ WO8_KERNELS = {0: "invalid", 1: "wo8_stream_kernel", 2: "wo8_tile_kernel"}
 def wo8_route(fmt: int, m: int, n: int, k: int) -> dict:
     """The route int8_wo_linear / fp8_wo_linear launch for a shape (host logic only, ao_wo8_linear_route); kernel "invalid" for shapes
     nothing takes."""
-    out = (ctypes.c_int32 * 7)()
-    _lib.check(_lib.lib().ao_wo8_linear_route(int(fmt), int(m), int(n), int(k), out, 7))
-    kernel, waves, mt, tile_m, tile_n, gx, gy = list(out)
-    return {"kernel": WO8_KERNELS.get(kernel, "invalid"), "waves": waves, "m_tiles": mt, "tile_m": tile_m, "tile_n": tile_n,
-            "grid": (gx, gy)}
+    return _two_form_route("ao_wo8_linear_route", WO8_KERNELS, fmt, m, n, k)
 
 
 def wo8_set_form(form: int) -> None:
     """Measurement only: 0 the product route, 1 the streaming form, 2 the tiled form (calling thread)."""
-    _lib.check(_lib.lib().ao_wo8_linear_set_form(int(form)))
+    _two_form_set_form("ao_wo8_linear_set_form", form)
 
 
 def _wo_linear(name, fmt, x, wq, w_scale, bias, wdtype, out=None):
@@ -1687,20 +1695,16 @@ def fp8_quantize_block_128x128(w: torch.Tensor):
 def fp8_block_linear_route(m: int, n: int, k: int) -> dict:
     """The route fp8_block_linear / fp8_block_mm launch for a shape (host logic only, ao_fp8_block_linear_route); kernel "invalid" for
     shapes nothing takes."""
-    out = (ctypes.c_int32 * 7)()
-    _lib.check(_lib.lib().ao_fp8_block_linear_route(int(m), int(n), int(k), out, 7))
-    kernel, waves, mt, tile_m, tile_n, gx, gy = list(out)
-    return {"kernel": FP8_BLOCK_KERNELS.get(kernel, "invalid"), "waves": waves, "m_tiles": mt, "tile_m": tile_m, "tile_n": tile_n,
-            "grid": (gx, gy)}
+    return _two_form_route("ao_fp8_block_linear_route", FP8_BLOCK_KERNELS, m, n, k)
 
 
 def fp8_block_linear_kernel_name(m: int, n: int, k: int) -> str:
-    return _lib.lib().ao_fp8_block_linear_kernel_name(int(m), int(n), int(k)).decode()
+    return _two_form_kernel_name("ao_fp8_block_linear_kernel_name", m, n, k)
 
 
 def fp8_block_linear_set_form(form: int) -> None:
     """Measurement only: 0 the product route, 1 the streaming form, 2 the tiled form (calling thread)."""
-    _lib.check(_lib.lib().ao_fp8_block_linear_set_form(int(form)))
+    _two_form_set_form("ao_fp8_block_linear_set_form", form)
 
 
 def _fp8_block_weight(name, wq, w_scale, bias, k_from_a):
@@ -1783,20 +1787,16 @@ FP8_BLOCK_GROUPED_KERNELS = {0: "invalid", 1: "fp8_block_grouped_stream_kernel",
 def fp8_block_grouped_mm_route(m_total: int, n: int, k: int, e: int) -> dict:
     """The route fp8_block_grouped_mm launches for a shape (host logic only, ao_fp8_block_grouped_mm_route: it keys on the mean group
     size ceil(M_total / E)); kernel "invalid" for shapes nothing takes."""
-    out = (ctypes.c_int32 * 7)()
-    _lib.check(_lib.lib().ao_fp8_block_grouped_mm_route(int(m_total), int(n), int(k), int(e), out, 7))
-    kernel, waves, mt, tile_m, tile_n, gx, gy = list(out)
-    return {"kernel": FP8_BLOCK_GROUPED_KERNELS.get(kernel, "invalid"), "waves": waves, "m_tiles": mt, "tile_m": tile_m, "tile_n": tile_n,
-            "grid": (gx, gy)}
+    return _two_form_route("ao_fp8_block_grouped_mm_route", FP8_BLOCK_GROUPED_KERNELS, m_total, n, k, e)
 
 
 def fp8_block_grouped_mm_kernel_name(m_total: int, n: int, k: int, e: int) -> str:
-    return _lib.lib().ao_fp8_block_grouped_mm_kernel_name(int(m_total), int(n), int(k), int(e)).decode()
+    return _two_form_kernel_name("ao_fp8_block_grouped_mm_kernel_name", m_total, n, k, e)
 
 
 def fp8_block_grouped_mm_set_form(form: int) -> None:
     """Measurement only: 0 the product route, 1 the streaming form, 2 the tiled form (calling thread)."""
-    _lib.check(_lib.lib().ao_fp8_block_grouped_mm_set_form(int(form)))
+    _two_form_set_form("ao_fp8_block_grouped_mm_set_form", form)
 
 
 def fp8_block_grouped_mm(aq, a_scale, wq, w_scale, offs, out=None):
@@ -2013,20 +2013,16 @@ NVFP4_KERNELS = {0: "invalid", 1: "nvfp4_stream_kernel", 2: "nvfp4_tile_kernel"}
 def nvfp4_linear_route(kind: int, m: int, n: int, k: int) -> dict:
     """The route nvfp4_wo_linear (kind 0) / nvfp4_mm (kind 1) launch for a shape (host logic only, ao_nvfp4_linear_route); kernel
     "invalid" for shapes nothing takes."""
-    out = (ctypes.c_int32 * 7)()
-    _lib.check(_lib.lib().ao_nvfp4_linear_route(int(kind), int(m), int(n), int(k), out, 7))
-    kernel, waves, mt, tile_m, tile_n, gx, gy = list(out)
-    return {"kernel": NVFP4_KERNELS.get(kernel, "invalid"), "waves": waves, "m_tiles": mt, "tile_m": tile_m, "tile_n": tile_n,
-            "grid": (gx, gy)}
+    return _two_form_route("ao_nvfp4_linear_route", NVFP4_KERNELS, kind, m, n, k)
 
 
 def nvfp4_linear_kernel_name(kind: int, m: int, n: int, k: int) -> str:
-    return _lib.lib().ao_nvfp4_linear_kernel_name(int(kind), int(m), int(n), int(k)).decode()
+    return _two_form_kernel_name("ao_nvfp4_linear_kernel_name", kind, m, n, k)
 
 
 def nvfp4_set_form(form: int) -> None:
     """Measurement only: 0 the product route, 1 the streaming form, 2 the tiled form (calling thread)."""
-    _lib.check(_lib.lib().ao_nvfp4_linear_set_form(int(form)))
+    _two_form_set_form("ao_nvfp4_linear_set_form", form)
 
 
 def _nvfp4_rows(name, x):
@@ -2154,20 +2150,16 @@ NVFP4_GROUPED_KERNELS = {0: "invalid", 1: "nvfp4_grouped_stream_kernel", 2: "nvf
 def nvfp4_grouped_mm_route(kind: int, m_total: int, n: int, k: int, e: int) -> dict:
     """The route nvfp4_grouped_mm launches for a kind and shape (host logic only, ao_nvfp4_grouped_mm_route: it keys on the mean group
     size ceil(M_total / E)); kernel "invalid" for shapes nothing takes."""
-    out = (ctypes.c_int32 * 7)()
-    _lib.check(_lib.lib().ao_nvfp4_grouped_mm_route(int(kind), int(m_total), int(n), int(k), int(e), out, 7))
-    kernel, waves, mt, tile_m, tile_n, gx, gy = list(out)
-    return {"kernel": NVFP4_GROUPED_KERNELS.get(kernel, "invalid"), "waves": waves, "m_tiles": mt, "tile_m": tile_m, "tile_n": tile_n,
-            "grid": (gx, gy)}
+    return _two_form_route("ao_nvfp4_grouped_mm_route", NVFP4_GROUPED_KERNELS, kind, m_total, n, k, e)
 
 
 def nvfp4_grouped_mm_kernel_name(kind: int, m_total: int, n: int, k: int, e: int) -> str:
-    return _lib.lib().ao_nvfp4_grouped_mm_kernel_name(int(kind), int(m_total), int(n), int(k), int(e)).decode()
+    return _two_form_kernel_name("ao_nvfp4_grouped_mm_kernel_name", kind, m_total, n, k, e)
 
 
 def nvfp4_grouped_mm_set_form(form: int) -> None:
     """Measurement only: 0 the product route, 1 the streaming form, 2 the tiled form (calling thread)."""
-    _lib.check(_lib.lib().ao_nvfp4_grouped_mm_set_form(int(form)))
+    _two_form_set_form("ao_nvfp4_grouped_mm_set_form", form)
 
 
 def _nvfp4_offs(name, offs, e):

@@ -175,6 +175,22 @@ def test_exact_sums_with_each_form_forced(form, want, M, N, K):
     assert ops.fp8_block_linear_kernel_name(M, N, K) == (STREAM if M <= SEAM else TILE)
 
 
+# The (m-tiles, waves) instances of the stream form that no case above launches.  One column tile (N = 16) asks for the most waves, the
+# K / 128 k steps cap them; M = 1 / 17 / 33 rows take 1 / 2 / 4 m-tiles.
+@pytest.mark.parametrize("M,K,pair", [(1, 512, (1, 4)), (17, 128, (2, 1)), (17, 256, (2, 2)), (17, 512, (2, 4)), (33, 512, (4, 4))],
+                         ids=lambda v: "%dx%d" % v if isinstance(v, tuple) else str(v))
+def test_exact_sums_on_the_remaining_stream_instances(M, K, pair):
+    from ao_amd import ops
+
+    try:
+        ops.fp8_block_linear_set_form(1)
+        route = ops.fp8_block_linear_route(M, 16, K)
+        assert (route["m_tiles"], route["waves"]) == pair
+        _exact_case(M, 16, K, STREAM)
+    finally:
+        ops.fp8_block_linear_set_form(0)
+
+
 def _operands(M, N, K, seed, bias):
     """The operand recipe of test_mx_linear_gpu._operands."""
     g = torch.Generator().manual_seed(seed)

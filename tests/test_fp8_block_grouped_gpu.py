@@ -37,6 +37,12 @@ _SPARSE[0], _SPARSE[100], _SPARSE[255] = 3, 17, 1
 CASES.append((_SPARSE, 128, 128, 0))  # E = 256, three non-empty groups
 FORCED = [CASES[2], CASES[6]]
 IDS = lambda c: f"E{len(c[0])}-M{sum(c[0])}+{c[3]}-N{c[1]}-K{c[2]}"  # noqa: E731
+# The (m-tiles, waves) instances of the stream form that no case above launches, with the form forced: mean group sizes of 2 / 17 / 33
+# rows take 1 / 2 / 4 m-tiles; one column tile (N = 16) asks for the most waves, the K / 128 k steps cap them.  (case, pair)
+STREAM_PAIRS = [(([3, 1], 16, 512, 0), (1, 4)), (([3, 1], 16, 1024, 0), (1, 8)), (([20, 14], 16, 128, 0), (2, 1)),
+                (([20, 14], 16, 256, 0), (2, 2)), (([20, 14], 16, 512, 0), (2, 4)), (([20, 14], 16, 2048, 0), (2, 16)),
+                (([40, 26], 16, 128, 0), (4, 1)), (([40, 26], 16, 512, 0), (4, 4)), (([40, 26], 16, 1024, 0), (4, 8))]
+EXACT_CASES = CASES + [case for case, _ in STREAM_PAIRS]  # what _exact and _exact_case index
 
 
 def _dev():
@@ -95,7 +101,7 @@ def _exact(i):
     are the chain's whatever the kernel's order.  The operands and the chain, computed once per case."""
     from oracle import fp8_ref
 
-    sizes, N, K, tail = CASES[i]
+    sizes, N, K, tail = EXACT_CASES[i]
     E, M = len(sizes), sum(sizes) + tail
     g = np.random.default_rng(2000 + i)
     kb, nb = K // 128, (N + 127) // 128
@@ -114,7 +120,7 @@ def _exact(i):
 def _exact_case(i, want):
     from ao_amd import ops
 
-    sizes, N, K, tail = CASES[i]
+    sizes, N, K, tail = EXACT_CASES[i]
     rows = sum(sizes)
     assert ops.fp8_block_grouped_mm_kernel_name(rows + tail, N, K, len(sizes)) == want
     aq, a_s, wq, ws, offs, ref = _exact(i)
@@ -137,6 +143,17 @@ def test_exact_sums_with_each_form_forced(form, want, case):
         _exact_case(CASES.index(case), want)
     sizes, N, K, tail = case
     assert ops.fp8_block_grouped_mm_kernel_name(sum(sizes) + tail, N, K, len(sizes)) == _want(sizes, tail)
+
+
+@pytest.mark.parametrize("case,pair", STREAM_PAIRS, ids=[IDS(c) for c, _ in STREAM_PAIRS])
+def test_exact_sums_on_the_remaining_stream_instances(case, pair):
+    from ao_amd import ops
+
+    sizes, N, K, tail = case
+    with _forced(1):
+        route = ops.fp8_block_grouped_mm_route(sum(sizes) + tail, N, K, len(sizes))
+        assert (route["m_tiles"], route["waves"]) == pair
+        _exact_case(EXACT_CASES.index(case), STREAM)
 
 
 # ---- Gaussian operands against float64 -----------------------------------------------------------------------------------------------------

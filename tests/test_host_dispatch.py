@@ -474,9 +474,10 @@ def test_queries_ignore_overrides():
 
 
 def test_two_form_routes_match_the_recording():
-    """The seven route fields of the MX dense and the weight-only linears -- every format under every ao_*_linear_set_form value, the
-    shapes a family refuses and the grid-row cap included -- are those recorded in tests/golden/two_form_routes.json
-    (tests/golden/make_two_form_routes.py); and one family's forced form does not move the other family's routes."""
+    """The seven route fields of the six two-form linear families (MX dense, weight-only, blockwise float8 dense and grouped, NVFP4
+    dense and grouped) -- every format under every ao_*_set_form value, the shapes a family refuses and the grid-row cap included --
+    are those recorded in tests/golden/two_form_routes.json (tests/golden/make_two_form_routes.py); and one family's forced form
+    does not move the other five families' routes."""
     import importlib.util
     import os
 
@@ -487,16 +488,23 @@ def test_two_form_routes_match_the_recording():
 
     lib = _lib.lib()
     want = rec.load()
-    assert len(want) == 12 and all(len(cells) == len(rec.M_GRID) * len(rec.N_GRID) * len(rec.K_GRID) for cells in want.values())
+    assert len(rec.FAMILIES) == 6 and len(want) == 30  # (formats x forms: mx 6, wo8 6, fp8_block 3 + 3 grouped, nvfp4 6 + 6 grouped)
+    assert all(len(cells) == len(rec.grid(key.split("/")[0])) for key, cells in want.items())
+    assert len(rec.grid("mx")) == len(rec.M_GRID) * len(rec.N_GRID) * len(rec.K_GRID) and len(rec.grid("nvfp4_grouped")) == 8 * 3 * 4 * 4
     got = rec.record(lib)
+    assert got.keys() == want.keys()
     for key in want:
         assert got[key] == want[key], key
 
-    for forced, other in (("mx", "wo8"), ("wo8", "mx")):
-        try:
+    try:
+        for forced in rec.FAMILIES:
             for form in (1, 2):
                 assert getattr(lib, rec.FAMILIES[forced][1])(form) == 0
-                for key, cells in rec.record_form(lib, other, None).items():
-                    assert cells == want[key], (forced, form, key)
-        finally:
-            getattr(lib, rec.FAMILIES[forced][1])(0)
+                for other in rec.FAMILIES:
+                    if other != forced:
+                        for key, cells in rec.record_form(lib, other, None).items():
+                            assert cells == want[key], (forced, form, key)
+            assert getattr(lib, rec.FAMILIES[forced][1])(0) == 0
+    finally:
+        for family in rec.FAMILIES:
+            getattr(lib, rec.FAMILIES[family][1])(0)

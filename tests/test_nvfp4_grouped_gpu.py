@@ -44,6 +44,12 @@ CASES = [
 ]
 IDS = ["g1", "g0-1-16-17", "g15-0-33+5", "g8x", "g64-1-0+3", "g0-0-40", "g65-64", "g129-0-200", "e256"]
 FORCED = [3, 7, 8]  # a stream form that walks a 200-row group in several passes, a tile form that serves 1-row groups, 256 experts
+# The (m-tiles, waves) instances of the stream form that no case above launches, with the form forced: mean group sizes of 2 / 17 / 33
+# rows take 1 / 2 / 4 m-tiles; one column tile (N = 16) asks for the most waves, the K / 128 k steps cap them.  (case, pair)
+STREAM_PAIRS = [(([3, 1], 16, 512, 0), (1, 4)), (([3, 1], 16, 1024, 0), (1, 8)), (([20, 14], 16, 128, 0), (2, 1)),
+                (([20, 14], 16, 1024, 0), (2, 8)), (([20, 14], 16, 2048, 0), (2, 16)), (([40, 26], 16, 128, 0), (4, 1)),
+                (([40, 26], 16, 512, 0), (4, 4)), (([40, 26], 16, 1024, 0), (4, 8))]
+EXACT_CASES = CASES + [case for case, _ in STREAM_PAIRS]  # what exact_problem indexes
 
 
 def _dev():
@@ -125,7 +131,7 @@ def exact_problem(kind, idx):
     |x| <= 8; any e2m1 codes; block scales in {1/4, 1/2, 1, 2}; a power-of-two scale per expert: group e's terms are multiples of
     2^-3 pb[e], |term| <= 96 pb[e].  Codes x codes: A scales in {1, 2}, any positive fp32 pa[e], pb[e] (applied after the sum): terms are
     multiples of 2^-4, |term| <= 144.  Neighbouring experts get different scales."""
-    sizes, N, K, tail = CASES[idx]
+    sizes, N, K, tail = EXACT_CASES[idx]
     E, M = len(sizes), sum(sizes) + tail
     assert K <= 4096
     g = torch.Generator(device="cpu").manual_seed(1000 + idx)
@@ -198,6 +204,18 @@ def test_exact_with_each_form_forced(kind, idx, form):
     with forced_form(form):
         assert ops.nvfp4_grouped_mm_kernel_name(KIND_ID[kind], sum(sizes) + tail, N, K, len(sizes)) == FORMS[form]
         run_exact(kind, idx)
+
+
+@pytest.mark.parametrize("case,pair", STREAM_PAIRS, ids=["g%s-k%d" % ("-".join(map(str, c[0])), c[2]) for c, _ in STREAM_PAIRS])
+@pytest.mark.parametrize("kind", KINDS)
+def test_exact_on_the_remaining_stream_instances(kind, case, pair):
+    from ao_amd import ops
+
+    sizes, N, K, tail = case
+    with forced_form(1):
+        route = ops.nvfp4_grouped_mm_route(KIND_ID[kind], sum(sizes) + tail, N, K, len(sizes))
+        assert (route["kernel"], route["m_tiles"], route["waves"]) == (FORMS[1],) + pair
+        run_exact(kind, EXACT_CASES.index(case))
 
 
 def test_m_total_zero_launches_nothing():
