@@ -535,16 +535,15 @@ extern "C" int ao_gemm8_overridden(void) {
   return !(f.regstage == d.regstage && f.tiled_only == d.tiled_only && f.tile == d.tile && f.rb == d.rb && f.rb8_1x8 == d.rb8_1x8 &&
            f.mx == d.mx && f.mx_stream == d.mx_stream && f.mx_quad == d.mx_quad && f.dec8 == d.dec8 && f.mid8 == d.mid8 &&
            f.rb8_bn == d.rb8_bn && f.rb8_split == d.rb8_split && f.rb8_bm == d.rb8_bm && f.p8_group_rows == d.p8_group_rows &&
-           f.rb8_ablate == d.rb8_ablate && f.p8_persist == d.p8_persist && f.p8_split == d.p8_split && f.p8h_form == d.p8h_form &&
-           f.mx_proto == d.mx_proto);
+           f.rb8_ablate == d.rb8_ablate && f.p8_persist == d.p8_persist && f.p8_split == d.p8_split && f.mx_proto == d.mx_proto);
 }
 
 extern "C" int ao_gemm8_set_tuning(int key, int value) {
   static int Gemm8Force::*const kKeys[] = {nullptr, &Gemm8Force::rb8_bn, &Gemm8Force::rb8_split, &Gemm8Force::rb8_bm, &Gemm8Force::p8_group_rows,
-                                           &Gemm8Force::rb8_ablate, &Gemm8Force::p8_persist, &Gemm8Force::p8_split, &Gemm8Force::p8h_form,
+                                           &Gemm8Force::rb8_ablate, &Gemm8Force::p8_persist, &Gemm8Force::p8_split, nullptr,
                                            &Gemm8Force::mx_proto};
   AO_REQUIRE(key >= 1 && key <= 9, "ao_gemm8_set_tuning: unknown key %d", key);
-  g_force.*kKeys[key] = value;
+  if (kKeys[key] != nullptr) g_force.*kKeys[key] = value;  // (key 8 selected gemm8_p8h's laboratory loop forms, which left the tree: accepted, ignored)
   return AO_OK;
 }
 

@@ -51,6 +51,135 @@ constexpr int kBuf = 4 * kHalf;       // A-lo, A-hi, B-lo, B-hi of one K tile
 constexpr int kEpiStride = 144;       // bytes per row of a wave's 128 x 64 bf16 staging region (128 + 16: conflict-free b16 writes)
 constexpr int kSmem = 8 * 128 * kEpiStride;  // 147456 B >= 2 * kBuf
 
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// The steps the three kernels below share, each defined once.  What tells the kernels apart -- which phase of a K tile reads, fetches and
+// waits for what -- stays written out in each of them.
+// ---------------------------------------------------------------------------------------------------------------------------------------
+
+// The source swizzle and its inverse.  A DMA instruction writes lane-linear: lane l lands at chunk position l & 7 (16 bytes) of row l >> 3
+// of its 8 rows, so it is the SOURCE that is permuted: chunk position c of half-tile row r holds global chunk c ^ ((r >> 1) & 7).  x -> x ^ s
+// is its own inverse, so the fragment read of global chunk kq of row nl finds it at position kq ^ ((nl >> 1) & 7): 16 lanes x 4 chunks then
+// cover every bank group once.  Rows 16 apart share (r >> 1) & 7, and chunk 4 + kq sits at the position ^ 4, i.e. the byte offset ^ 64.
+__device__ __forceinline__ uint32_t dma_src_chunk(int lane, int row) { return (uint32_t)(((lane & 7) ^ (row >> 1)) & 7) << 4; }  // byte offset in the row
+__device__ __forceinline__ int frag_pos(int nl, int kq) { return (kq ^ (nl >> 1)) << 4; }  // of chunk kq < 4, row nl < 16 (+ 16 i)
+
+// T MFMA tiles (16 rows apart) x {chunk kq, chunk 4 + kq} from off0 = the first tile's row nl at frag_pos
+template <int T>
+__device__ __forceinline__ void load_frags(u32x4 (*f)[2], const char* buf, int off0) {
+#pragma unroll
+  for (int t = 0; t < T; ++t) {
+    const int off = off0 + t * 16 * 128;
+    f[t][0] = *reinterpret_cast<const u32x4*>(buf + off);
+    f[t][1] = *reinterpret_cast<const u32x4*>(buf + (off ^ 64));
+  }
+}
+
+// the barrier between a load segment and a multiply segment (and back): LDS reads retired, nothing moves across
+__device__ __forceinline__ void seam() {
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// One MFMA phase: 4 m-tiles (c4 = their accumulator rows, af) x the n-tile pair nj (bf).  SWAP: weights as the first operand (gemm8_p8p_kernel:
+// lane (nl, kq) then holds columns 4 kq + {0..3} of row nl).  ZERO: C = 0 instead of the accumulator (the first K tile of a persistent tile).
+// int8: one 16x16x64 per k half, the second half of every tile in a second sweep (back-to-back MFMAs on one accumulator would wait for each
+// other).  fp8: one 16x16x128 -- as inline asm, not the builtin: a builtin MFMA is a pure value computation and the instruction selector is
+// free to place it anywhere in the loop body -- it put all 32 at the END of the K tile (round 3 disassembly: "rrrr DD | | DD | | rrrr DD |
+// | DD MMMM...M |"), so both wave rows multiplied at the same time and loaded at the same time, and the fp8 GEMM ran 21 % behind its int8
+// twin.  Volatile asm keeps its place between the seams.  (Unit E8M0 scales in a VGPR; cbsz = blgp = 0: e4m3.  The accumulator's next reader
+// is the asm MFMA one K tile later or the epilogue, behind its explicit s_nop cover: no hazard the compiler has to see.)
+template <bool IS_INT, bool SWAP, bool ZERO>
+__device__ __forceinline__ void mfma_phase(f32x4 (*c4)[4], const u32x4 (*af)[2], const u32x4 (*bf)[2], int nj) {
+  const int unit_scale = 127;  // E8M0 1.0
+#pragma unroll
+  for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+    for (int n2 = 0; n2 < 2; ++n2) {
+      const int nt = nj * 2 + n2;
+      f32x4& c = c4[mt][nt];
+      const u32x4* x = SWAP ? bf[nt] : af[mt];
+      const u32x4* y = SWAP ? af[mt] : bf[nt];
+      if constexpr (IS_INT) {
+        c = __builtin_bit_cast(f32x4, __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, x[0]), __builtin_bit_cast(i32x4, y[0]),
+                                                                           ZERO ? i32x4{0, 0, 0, 0} : __builtin_bit_cast(i32x4, c), 0, 0, 0));
+      } else {
+        const i32x8 xv = {(int)x[0].x, (int)x[0].y, (int)x[0].z, (int)x[0].w, (int)x[1].x, (int)x[1].y, (int)x[1].z, (int)x[1].w};
+        const i32x8 yv = {(int)y[0].x, (int)y[0].y, (int)y[0].z, (int)y[0].w, (int)y[1].x, (int)y[1].y, (int)y[1].z, (int)y[1].w};
+        if constexpr (ZERO)
+          asm volatile("v_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, 0, %3, %3 op_sel_hi:[0,0,0]" : "=&v"(c) : "v"(xv), "v"(yv), "v"(unit_scale));
+        else
+          asm volatile("v_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, %0, %3, %3 op_sel_hi:[0,0,0]" : "+v"(c) : "v"(xv), "v"(yv), "v"(unit_scale));
+      }
+    }
+  if constexpr (IS_INT) {
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+      for (int n2 = 0; n2 < 2; ++n2) {
+        const int nt = nj * 2 + n2;
+        f32x4& c = c4[mt][nt];
+        const u32x4* x = SWAP ? bf[nt] : af[mt];
+        const u32x4* y = SWAP ? af[mt] : bf[nt];
+        c = __builtin_bit_cast(f32x4, __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, x[1]), __builtin_bit_cast(i32x4, y[1]),
+                                                                           __builtin_bit_cast(i32x4, c), 0, 0, 0));
+      }
+  }
+}
+
+// Workgroup -> tile.  xcd_consecutive: workgroups are dealt to the 8 XCDs round-robin (id % 8), so the ids are permuted to give one XCD
+// consecutive work items.  tile_of: the order of the tiles themselves, in groups of group_rows (= 4: round-5 sweep) tile rows that walk the N
+// direction together (a group shares its A panels in the XCD's L2 and streams B once).
+__device__ __forceinline__ int xcd_consecutive(int wg, int nwg) { return (nwg & 7) == 0 ? (wg & 7) * (nwg >> 3) + (wg >> 3) : wg; }
+__device__ __forceinline__ void tile_of(int id, int group_rows, int tiles_m, int tiles_n, int& tm, int& tn) {
+  const int group = group_rows * tiles_n;
+  const int g0 = (id / group) * group_rows;
+  const int gsz = min(group_rows, tiles_m - g0);
+  tm = g0 + (id % group) % gsz;
+  tn = (id % group) / gsz;
+}
+
+// The epilogues of gemm8_p8_kernel (MT = 8) and gemm8_p8h_kernel (MT = 4): a wave's MT x 4 tiles of 16 x 16 from row rbase, column cbase.
+// D layout of the MFMA: lane (col = nl, kq) holds rows 4 kq + {0..3}.  Raw: the accumulator bits, one dword per store.
+template <int MT>
+__device__ __forceinline__ void store_raw32(const f32x4 (*acc)[4], uint32_t* out, int M, int N, int rbase, int cbase, int nl, int kq) {
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int m = rbase + mt * 16 + kq * 4 + r, n = cbase + nt * 16 + nl;
+        if (m < M && n < N) out[(size_t)m * N + n] = __builtin_bit_cast(u32x4, acc[mt][nt])[r];
+      }
+}
+// bf16: scales applied in registers (epilogue8: the reference's rounding sequence), the wave's tile transposed through its own region of
+// the (now free) LDS so that every lane stores 16 contiguous bytes.  row_scales(mt, rs) fills the four row scales of m-tile mt.
+template <bool IS_INT, int MT, class RowScales>
+__device__ __forceinline__ void store_bf16_staged(const f32x4 (*acc)[4], uint16_t* out, int M, int N, char* region, int rbase, int cbase, int lane, int nl, int kq,
+                                                  const float (&cs)[4], bool has_bias, const float (&bias)[4], RowScales row_scales) {
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) {
+    float rs[4];
+    row_scales(mt, rs);
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float c = IS_INT ? (float)__builtin_bit_cast(i32x4, acc[mt][nt])[r] : acc[mt][nt][r];
+        const float v = epilogue8<IS_INT>(c, rs[r], cs[nt], has_bias, bias[nt]);
+        *reinterpret_cast<uint16_t*>(region + (mt * 16 + kq * 4 + r) * kEpiStride + (nt * 16 + nl) * 2) = f32_to_bf16_bits(v);
+      }
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's own writes (DS ops of a wave complete in order)
+#pragma unroll
+  for (int i = 0; i < 2 * MT; ++i) {
+    const int row = i * 8 + (lane >> 3), piece = lane & 7;
+    const u32x4 v = *reinterpret_cast<const u32x4*>(region + row * kEpiStride + piece * 16);
+    const int m = rbase + row, n = cbase + piece * 8;
+    if (m < M && n + 8 <= N) *reinterpret_cast<u32x4*>(out + (size_t)m * N + n) = v;
+  }
+}
+
 template <int EPI>
 __global__ __launch_bounds__(512) void gemm8_p8_kernel(P8Args p) {
   constexpr bool IS_INT = (EPI == P8_INT8_SCALED || EPI == P8_INT32);
@@ -61,18 +190,10 @@ __global__ __launch_bounds__(512) void gemm8_p8_kernel(P8Args p) {
   const int wr = wave >> 2, wc = wave & 3;
   const int nl = lane & 15, kq = lane >> 4;
 
-  // workgroup -> tile: blocks of one XCD (id % 8) take consecutive tiles, tiles ordered in groups of GR (= 4: round-5 sweep) tile rows that walk
-  // the N direction together (a group shares its A panels in the XCD's L2 and streams B once)
-  int wg = blockIdx.x;
-  const int nwg = gridDim.x;
-  if ((nwg & 7) == 0) wg = (wg & 7) * (nwg >> 3) + (wg >> 3);
   // (K parts -- built in round 5 for this tile shape too, never dispatched: a 256 x 256 fp32 partial is 256 KiB, the meeting cost what the
   // shorter loop saved, profiles/p8_split_sweep_r05.jsonl -- live on in the 256 x 128 form below only)
-  const int GR = p.group_rows;
-  const int group = GR * p.tiles_n;
-  const int g0 = (wg / group) * GR;
-  const int gsz = min(GR, p.tiles_m - g0);
-  const int tm = g0 + (wg % group) % gsz, tn = (wg % group) / gsz;
+  int tm, tn;
+  tile_of(xcd_consecutive(blockIdx.x, gridDim.x), p.group_rows, p.tiles_m, p.tiles_n, tm, tn);
   const int m0 = tm * 256, n0 = tn * 256;
   const int kb = 0, ktiles = p.K >> 7;
 
@@ -83,7 +204,7 @@ __global__ __launch_bounds__(512) void gemm8_p8_kernel(P8Args p) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int row = 16 * wave + 8 * i + (lane >> 3);
-      const uint32_t chunk = (uint32_t)(((lane & 7) ^ (row >> 1)) & 7) << 4;
+      const uint32_t chunk = dma_src_chunk(lane, row);
       aoff[h][i] = (uint32_t)(min(m0 + h * 128 + row, p.M - 1) - m0) * (uint32_t)p.K + chunk;
       boff[h][i] = (uint32_t)(min(n0 + h * 128 + row, p.N - 1) - n0) * (uint32_t)p.K + chunk;
     }
@@ -107,7 +228,7 @@ __global__ __launch_bounds__(512) void gemm8_p8_kernel(P8Args p) {
   };
 
   // fragment addresses inside a buffer: A rows of wave row wr (half tile wr), B rows of wave column wc (half tile wc >> 1)
-  const int pos_lo = ((kq ^ (nl >> 1)) & 7) << 4;  // chunk kq of row nl (+ 16 row steps keep (row >> 1) & 7); chunk 4 + kq: ^ 64
+  const int pos_lo = frag_pos(nl, kq);
   const int a_frag = wr * kHalf + nl * 128 + pos_lo;
   const int b_frag = (2 + (wc >> 1)) * kHalf + ((wc & 1) * 64 + nl) * 128 + pos_lo;
 
@@ -118,64 +239,9 @@ __global__ __launch_bounds__(512) void gemm8_p8_kernel(P8Args p) {
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   u32x4 af[4][2], bf[4][2];  // A: the current 64-row half of the wave's rows (4 m-tiles x {chunk kq, chunk 4 + kq}); B: all 4 n-tiles
 
-  auto load_a = [&](const char* buf, int mi) {
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
-      const int off = a_frag + (mi * 64 + mt * 16) * 128;
-      af[mt][0] = *reinterpret_cast<const u32x4*>(buf + off);
-      af[mt][1] = *reinterpret_cast<const u32x4*>(buf + (off ^ 64));
-    }
-  };
-  auto load_b = [&](const char* buf) {
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-      const int off = b_frag + (nt * 16) * 128;
-      bf[nt][0] = *reinterpret_cast<const u32x4*>(buf + off);
-      bf[nt][1] = *reinterpret_cast<const u32x4*>(buf + (off ^ 64));
-    }
-  };
-  const int unit_scale = 127;  // E8M0 1.0
-  auto multiply = [&](int mi, int nj) {
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-      for (int n2 = 0; n2 < 2; ++n2) {
-        const int nt = nj * 2 + n2;
-        f32x4& c = acc[mi * 4 + mt][nt];
-        if constexpr (IS_INT) {
-          // (the second k half of every tile follows in a second sweep below: back-to-back MFMAs on one accumulator would wait for each other)
-          c = __builtin_bit_cast(f32x4, __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, af[mt][0]), __builtin_bit_cast(i32x4, bf[nt][0]),
-                                                                             __builtin_bit_cast(i32x4, c), 0, 0, 0));
-        } else {
-          const i32x8 av = {(int)af[mt][0].x, (int)af[mt][0].y, (int)af[mt][0].z, (int)af[mt][0].w,
-                            (int)af[mt][1].x, (int)af[mt][1].y, (int)af[mt][1].z, (int)af[mt][1].w};
-          const i32x8 bv = {(int)bf[nt][0].x, (int)bf[nt][0].y, (int)bf[nt][0].z, (int)bf[nt][0].w,
-                            (int)bf[nt][1].x, (int)bf[nt][1].y, (int)bf[nt][1].z, (int)bf[nt][1].w};
-          // As inline asm, not the builtin: a builtin MFMA is a pure value computation and the instruction selector is free to place
-          // it anywhere in the loop body -- it put all 32 at the END of the K tile (round 3 disassembly: "rrrr DD | | DD | | rrrr DD |
-          // | DD MMMM...M |"), so both wave rows multiplied at the same time and loaded at the same time, and the fp8 GEMM ran 21 %
-          // behind its int8 twin.  Volatile asm keeps its place between the seams.  (Unit E8M0 scales in a VGPR; cbsz = blgp = 0: e4m3.
-          // The accumulator's next reader is the asm MFMA one K tile later or the epilogue: no hazard the compiler has to see.)
-          asm volatile("v_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, %0, %3, %3 op_sel_hi:[0,0,0]" : "+v"(c) : "v"(av), "v"(bv), "v"(unit_scale));
-        }
-      }
-    if constexpr (IS_INT) {
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-        for (int n2 = 0; n2 < 2; ++n2) {
-          const int nt = nj * 2 + n2;
-          f32x4& c = acc[mi * 4 + mt][nt];
-          c = __builtin_bit_cast(f32x4, __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, af[mt][1]), __builtin_bit_cast(i32x4, bf[nt][1]),
-                                                                             __builtin_bit_cast(i32x4, c), 0, 0, 0));
-        }
-    }
-  };
-  // the barrier between a load segment and a multiply segment (and back): LDS reads retired, nothing moves across
-  auto seam = [&] {
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-  };
+  auto load_a = [&](const char* buf, int mi) { load_frags<4>(af, buf, a_frag + mi * 64 * 128); };
+  auto load_b = [&](const char* buf) { load_frags<4>(bf, buf, b_frag); };
+  auto multiply = [&](int mi, int nj) { mfma_phase<IS_INT, false, false>(acc + mi * 4, af, bf, nj); };
 
   // prologue: K tile 0 entirely and the B halves of tile 1 (as if issued in q2 / q3 of a tile -1); wait for tile 0
   issue(0, 0); issue(0, 3); issue(0, 2); issue(0, 1); issue(1, 2); issue(1, 1);
@@ -221,18 +287,9 @@ __global__ __launch_bounds__(512) void gemm8_p8_kernel(P8Args p) {
   __builtin_amdgcn_sched_barrier(0);
 
   // ---- epilogue --------------------------------------------------------------------------------------------------------
-  // D layout of the 16 x 16 MFMA: lane (col = nl, kq) holds rows 4 kq + {0..3}
   const int rbase = m0 + wr * 128, cbase = n0 + wc * 64;
   if constexpr (EPI == P8_INT32 || EPI == P8_FP8_RAW) {
-#pragma unroll
-    for (int mt = 0; mt < 8; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int m = rbase + mt * 16 + kq * 4 + r, n = cbase + nt * 16 + nl;
-          if (m < p.M && n < p.N) reinterpret_cast<uint32_t*>(p.out)[(size_t)m * p.N + n] = __builtin_bit_cast(u32x4, acc[mt][nt])[r];
-        }
+    store_raw32<8>(acc, reinterpret_cast<uint32_t*>(p.out), p.M, p.N, rbase, cbase, nl, kq);
   } else {
     float cs[4], bias[4];
 #pragma unroll
@@ -241,30 +298,11 @@ __global__ __launch_bounds__(512) void gemm8_p8_kernel(P8Args p) {
       cs[nt] = p.col_scale[n];
       bias[nt] = p.bias != nullptr ? bf16_lo_to_f32(p.bias[n]) : 0.f;
     }
-    char* region = smem + wave * (128 * kEpiStride);
-#pragma unroll
-    for (int mt = 0; mt < 8; ++mt) {
-      float rs[4];
+    store_bf16_staged<IS_INT, 8>(acc, reinterpret_cast<uint16_t*>(p.out), p.M, p.N, smem + wave * (128 * kEpiStride), rbase, cbase, lane, nl, kq, cs,
+                                 p.bias != nullptr, bias, [&](int mt, float (&rs)[4]) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) rs[r] = p.row_scale[min(rbase + mt * 16 + kq * 4 + r, p.M - 1)];
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float c = IS_INT ? (float)__builtin_bit_cast(i32x4, acc[mt][nt])[r] : acc[mt][nt][r];
-          const float v = epilogue8<IS_INT>(c, rs[r], cs[nt], p.bias != nullptr, bias[nt]);
-          *reinterpret_cast<uint16_t*>(region + (mt * 16 + kq * 4 + r) * kEpiStride + (nt * 16 + nl) * 2) = f32_to_bf16_bits(v);
-        }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's own writes (DS ops of a wave complete in order)
-    uint16_t* out = reinterpret_cast<uint16_t*>(p.out);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int row = i * 8 + (lane >> 3), piece = lane & 7;
-      const u32x4 v = *reinterpret_cast<const u32x4*>(region + row * kEpiStride + piece * 16);
-      const int m = rbase + row, n = cbase + piece * 8;
-      if (m < p.M && n + 8 <= p.N) *reinterpret_cast<u32x4*>(out + (size_t)m * p.N + n) = v;
-    }
+    });
   }
 }
 
@@ -311,21 +349,19 @@ __global__ __launch_bounds__(512) void gemm8_p8p_kernel(P8Args p) {
   const int wr = wave >> 2, wc = wave & 3;
   const int nl = lane & 15, kq = lane >> 4;
 
-  // this workgroup's tiles: XCD x (= id % 8) owns the contiguous range [x T / 8, (x + 1) T / 8) of the tile order (groups of GR tile rows
-  // walking N together, as in gemm8_p8_kernel), its workgroups walk it side by side
+  // this workgroup's tiles: XCD x (= id % 8) owns the contiguous range [x T / 8, (x + 1) T / 8) of the tile order (tile_of), its workgroups walk
+  // it side by side
   const int per = (int)gridDim.x >> 3, xcd = (int)blockIdx.x & 7, slot = (int)blockIdx.x >> 3;
   const int T = p.tiles_m * p.tiles_n;
   const int lo = (int)(((int64_t)xcd * T) >> 3), hi = (int)(((int64_t)(xcd + 1) * T) >> 3);
   if (hi - lo <= slot) return;
   const int mine = (hi - lo - slot + per - 1) / per;
   const int ktiles = p.K >> 7;
-  const int GR = p.group_rows, group = GR * p.tiles_n;
   auto origin = [&](int j, int& m0, int& n0) {
-    const int id = lo + slot + j * per;
-    const int g0 = (id / group) * GR;
-    const int gsz = min(GR, p.tiles_m - g0);
-    m0 = (g0 + (id % group) % gsz) * 256;
-    n0 = ((id % group) / gsz) * 256;
+    int tm, tn;
+    tile_of(lo + slot + j * per, p.group_rows, p.tiles_m, p.tiles_n, tm, tn);
+    m0 = tm * 256;
+    n0 = tn * 256;
   };
 
   // DMA sources (full tiles: the same offsets for A and B, both have row pitch K): half-tile rows 16 w + 8 i + (lane >> 3)
@@ -335,7 +371,7 @@ __global__ __launch_bounds__(512) void gemm8_p8p_kernel(P8Args p) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int row = 16 * wave + 8 * i + (lane >> 3);
-      off[h][i] = (uint32_t)(h * 128 + row) * (uint32_t)p.K + ((uint32_t)(((lane & 7) ^ (row >> 1)) & 7) << 4);
+      off[h][i] = (uint32_t)(h * 128 + row) * (uint32_t)p.K + dma_src_chunk(lane, row);
     }
   const uint32_t lds0 = lds_offset(smem);
   auto issue = [&](const uint8_t* asrc, const uint8_t* bsrc, int buf, int which) {  // which: 0 A-lo, 1 B-hi, 2 B-lo, 3 A-hi
@@ -357,83 +393,18 @@ __global__ __launch_bounds__(512) void gemm8_p8p_kernel(P8Args p) {
     }
   };
 
-  const int pos_lo = ((kq ^ (nl >> 1)) & 7) << 4;
+  const int pos_lo = frag_pos(nl, kq);
   const int a_frag = wr * kHalf + nl * 128 + pos_lo;
   const int b_frag = (2 + (wc >> 1)) * kHalf + ((wc & 1) * 64 + nl) * 128 + pos_lo;
 
   f32x4 acc[8][4];
   u32x4 af[4][2], bf[4][2];
-  auto load_a = [&](const char* buf, int mi) {
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
-      const int o = a_frag + (mi * 64 + mt * 16) * 128;
-      af[mt][0] = *reinterpret_cast<const u32x4*>(buf + o);
-      af[mt][1] = *reinterpret_cast<const u32x4*>(buf + (o ^ 64));
-    }
-  };
-  auto load_b = [&](const char* buf) {
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-      const int o = b_frag + (nt * 16) * 128;
-      bf[nt][0] = *reinterpret_cast<const u32x4*>(buf + o);
-      bf[nt][1] = *reinterpret_cast<const u32x4*>(buf + (o ^ 64));
-    }
-  };
-  const int unit_scale = 127;  // E8M0 1.0
+  auto load_a = [&](const char* buf, int mi) { load_frags<4>(af, buf, a_frag + mi * 64 * 128); };
+  auto load_b = [&](const char* buf) { load_frags<4>(bf, buf, b_frag); };
   // operands swapped (weights first): D[i = 4 kq + r][j = nl] = column n = 16 nt + i of row m = 16 mt + j
   auto multiply = [&](int mi, int nj, bool first) {
-    if (first) {
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-        for (int n2 = 0; n2 < 2; ++n2) {
-          const int nt = nj * 2 + n2;
-          f32x4& c = acc[mi * 4 + mt][nt];
-          if constexpr (IS_INT) {
-            c = __builtin_bit_cast(f32x4, __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, bf[nt][0]), __builtin_bit_cast(i32x4, af[mt][0]),
-                                                                               i32x4{0, 0, 0, 0}, 0, 0, 0));
-          } else {
-            const i32x8 av = {(int)af[mt][0].x, (int)af[mt][0].y, (int)af[mt][0].z, (int)af[mt][0].w,
-                              (int)af[mt][1].x, (int)af[mt][1].y, (int)af[mt][1].z, (int)af[mt][1].w};
-            const i32x8 bv = {(int)bf[nt][0].x, (int)bf[nt][0].y, (int)bf[nt][0].z, (int)bf[nt][0].w,
-                              (int)bf[nt][1].x, (int)bf[nt][1].y, (int)bf[nt][1].z, (int)bf[nt][1].w};
-            asm volatile("v_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, 0, %3, %3 op_sel_hi:[0,0,0]" : "=&v"(c) : "v"(bv), "v"(av), "v"(unit_scale));
-          }
-        }
-    } else {
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-        for (int n2 = 0; n2 < 2; ++n2) {
-          const int nt = nj * 2 + n2;
-          f32x4& c = acc[mi * 4 + mt][nt];
-          if constexpr (IS_INT) {
-            c = __builtin_bit_cast(f32x4, __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, bf[nt][0]), __builtin_bit_cast(i32x4, af[mt][0]),
-                                                                               __builtin_bit_cast(i32x4, c), 0, 0, 0));
-          } else {
-            const i32x8 av = {(int)af[mt][0].x, (int)af[mt][0].y, (int)af[mt][0].z, (int)af[mt][0].w,
-                              (int)af[mt][1].x, (int)af[mt][1].y, (int)af[mt][1].z, (int)af[mt][1].w};
-            const i32x8 bv = {(int)bf[nt][0].x, (int)bf[nt][0].y, (int)bf[nt][0].z, (int)bf[nt][0].w,
-                              (int)bf[nt][1].x, (int)bf[nt][1].y, (int)bf[nt][1].z, (int)bf[nt][1].w};
-            asm volatile("v_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, %0, %3, %3 op_sel_hi:[0,0,0]" : "+v"(c) : "v"(bv), "v"(av), "v"(unit_scale));
-          }
-        }
-    }
-    if constexpr (IS_INT) {  // the second k half of every tile in a second sweep (back-to-back MFMAs on one accumulator would wait for each other)
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-        for (int n2 = 0; n2 < 2; ++n2) {
-          const int nt = nj * 2 + n2;
-          f32x4& c = acc[mi * 4 + mt][nt];
-          c = __builtin_bit_cast(f32x4, __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, bf[nt][1]), __builtin_bit_cast(i32x4, af[mt][1]),
-                                                                             __builtin_bit_cast(i32x4, c), 0, 0, 0));
-        }
-    }
-  };
-  auto seam = [&] {
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
+    if (first) mfma_phase<IS_INT, true, true>(acc + mi * 4, af, bf, nj);
+    else mfma_phase<IS_INT, true, false>(acc + mi * 4, af, bf, nj);
   };
 
   int m0, n0, m1 = 0, n1 = 0;
@@ -570,12 +541,12 @@ __global__ __launch_bounds__(512) void gemm8_p8p_kernel(P8Args p) {
 //   * three K tiles of [A-lo | A-hi | B] half tiles resident (144 KiB): tile t + 2 is fetched during tile t into the buffer tile t - 1
 //     left -- every wave finished reading that one a full K tile earlier, whatever the stagger -- 4 DMA instructions in the first phase, 2 in
 //     the second, then vmcnt(6): tile t + 1 has landed, tile t + 2's six stay in flight.
-// Everything else (source swizzle, asm-pinned fp8 MFMAs, LDS-transposed epilogue, workgroup -> tile order) as in the kernel above.
+// Everything else (source swizzle, asm-pinned fp8 MFMAs, LDS-transposed epilogue, workgroup -> tile order): the shared steps at the top.
 // ---------------------------------------------------------------------------------------------------------------------------------------
 constexpr int kHBuf = 3 * kHalf;                    // one K tile: A-lo, A-hi, B
 constexpr int kHSmem = 3 * kHBuf;                   // 147456 B (three K tiles; the epilogue's 8 x 64 x 144 B fit inside)
 
-template <int EPI, int FORM = 0>
+template <int EPI>
 __global__ __launch_bounds__(512) void gemm8_p8h_kernel(P8Args p) {
   constexpr bool IS_INT = (EPI == P8_INT8_SCALED || EPI == P8_INT32);
   extern __shared__ __attribute__((aligned(1024))) char smem[];
@@ -585,17 +556,11 @@ __global__ __launch_bounds__(512) void gemm8_p8h_kernel(P8Args p) {
   const int g = wave >> 2, s = wave & 3;
   const int nl = lane & 15, kq = lane >> 4;
 
-  int wg = blockIdx.x;
-  const int nwg = gridDim.x;
-  if ((nwg & 7) == 0) wg = (wg & 7) * (nwg >> 3) + (wg >> 3);
-  const int S = p.split;  // K parts: consecutive work items (see gemm8_p8_kernel)
+  const int wg = xcd_consecutive(blockIdx.x, gridDim.x);
+  const int S = p.split;  // K parts: consecutive work items
   const int ks = wg % S;
-  wg /= S;
-  const int GR = p.group_rows;
-  const int group = GR * p.tiles_n;
-  const int g0 = (wg / group) * GR;
-  const int gsz = min(GR, p.tiles_m - g0);
-  const int tm = g0 + (wg % group) % gsz, tn = (wg % group) / gsz;
+  int tm, tn;
+  tile_of(wg / S, p.group_rows, p.tiles_m, p.tiles_n, tm, tn);
   const int m0 = tm * 256, n0 = tn * 128;
   const int ktiles_all = p.K >> 7;
   const int kb = (int)((int64_t)ks * ktiles_all / S);
@@ -606,7 +571,7 @@ __global__ __launch_bounds__(512) void gemm8_p8h_kernel(P8Args p) {
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int row = 16 * wave + 8 * i + (lane >> 3);
-    const uint32_t chunk = (uint32_t)(((lane & 7) ^ (row >> 1)) & 7) << 4;
+    const uint32_t chunk = dma_src_chunk(lane, row);
 #pragma unroll
     for (int h = 0; h < 2; ++h) aoff[h][i] = (uint32_t)(min(m0 + h * 128 + row, p.M - 1) - m0) * (uint32_t)p.K + chunk;
     boff[i] = (uint32_t)(min(n0 + row, p.N - 1) - n0) * (uint32_t)p.K + chunk;
@@ -621,7 +586,7 @@ __global__ __launch_bounds__(512) void gemm8_p8h_kernel(P8Args p) {
     else dma_b128_x2(abase + (size_t)tile * 128, aoff[which][0], aoff[which][1], dst);
   };
 
-  const int pos_lo = ((kq ^ (nl >> 1)) & 7) << 4;
+  const int pos_lo = frag_pos(nl, kq);
   const int a_frag = (s >> 1) * kHalf + ((s & 1) * 64 + nl) * 128 + pos_lo;
   const int b_frag = 2 * kHalf + (g * 64 + nl) * 128 + pos_lo;
 
@@ -632,59 +597,9 @@ __global__ __launch_bounds__(512) void gemm8_p8h_kernel(P8Args p) {
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   u32x4 af[4][2], bf[4][2];
 
-  auto load_a = [&](const char* buf) {
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
-      const int off = a_frag + mt * 16 * 128;
-      af[mt][0] = *reinterpret_cast<const u32x4*>(buf + off);
-      af[mt][1] = *reinterpret_cast<const u32x4*>(buf + (off ^ 64));
-    }
-  };
-  auto load_b = [&](const char* buf, int nj) {
-#pragma unroll
-    for (int n2 = 0; n2 < 2; ++n2) {
-      const int nt = nj * 2 + n2;
-      const int off = b_frag + nt * 16 * 128;
-      bf[nt][0] = *reinterpret_cast<const u32x4*>(buf + off);
-      bf[nt][1] = *reinterpret_cast<const u32x4*>(buf + (off ^ 64));
-    }
-  };
-  const int unit_scale = 127;  // E8M0 1.0
-  auto multiply = [&](int nj) {
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-      for (int n2 = 0; n2 < 2; ++n2) {
-        const int nt = nj * 2 + n2;
-        f32x4& c = acc[mt][nt];
-        if constexpr (IS_INT) {
-          c = __builtin_bit_cast(f32x4, __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, af[mt][0]), __builtin_bit_cast(i32x4, bf[nt][0]),
-                                                                             __builtin_bit_cast(i32x4, c), 0, 0, 0));
-        } else {
-          const i32x8 av = {(int)af[mt][0].x, (int)af[mt][0].y, (int)af[mt][0].z, (int)af[mt][0].w,
-                            (int)af[mt][1].x, (int)af[mt][1].y, (int)af[mt][1].z, (int)af[mt][1].w};
-          const i32x8 bv = {(int)bf[nt][0].x, (int)bf[nt][0].y, (int)bf[nt][0].z, (int)bf[nt][0].w,
-                            (int)bf[nt][1].x, (int)bf[nt][1].y, (int)bf[nt][1].z, (int)bf[nt][1].w};
-          // volatile asm keeps the MFMAs inside their phase (see gemm8_p8_kernel)
-          asm volatile("v_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, %0, %3, %3 op_sel_hi:[0,0,0]" : "+v"(c) : "v"(av), "v"(bv), "v"(unit_scale));
-        }
-      }
-    if constexpr (IS_INT) {
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-        for (int n2 = 0; n2 < 2; ++n2) {
-          const int nt = nj * 2 + n2;
-          f32x4& c = acc[mt][nt];
-          c = __builtin_bit_cast(f32x4, __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, af[mt][1]), __builtin_bit_cast(i32x4, bf[nt][1]),
-                                                                             __builtin_bit_cast(i32x4, c), 0, 0, 0));
-        }
-    }
-  };
-  auto seam = [&] {
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-  };
+  auto load_a = [&](const char* buf) { load_frags<4>(af, buf, a_frag); };
+  auto load_b = [&](const char* buf, int nj) { load_frags<2>(bf + nj * 2, buf, b_frag + nj * 2 * 16 * 128); };
+  auto multiply = [&](int nj) { mfma_phase<IS_INT, false, false>(acc, af, bf, nj); };
 
   // The epilogue's scales and bias are requested FIRST (VMEM returns in order: the counted waits below stay right, these being older than every
   // fetch) and kept as raw bits behind empty asm statements until the epilogue, so that no conversion -- and with it a vmcnt(0) -- is hoisted
@@ -711,66 +626,21 @@ __global__ __launch_bounds__(512) void gemm8_p8h_kernel(P8Args p) {
   if (g == 1) asm volatile("s_barrier" ::: "memory");  // the stagger: wave group 1 runs one barrier behind
   __builtin_amdgcn_sched_barrier(0);
 
-  if constexpr (FORM == 2) {  // (lab form) B-lo of tile 0 in registers before the loop
-    load_b(smem, 0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  }
   for (int t = 0; t < ktiles; ++t) {
     const char* buf = smem + (t % 3) * kHBuf;
-    if constexpr (FORM == 0) {
-      // ---- phase 0: all rows x n-lo; reads every A fragment and the n-lo B fragments; fetches the A halves of tile t + 2 ------------------
-      load_b(buf, 0); __builtin_amdgcn_sched_barrier(0); load_a(buf);
-      issue(t + 2, 0); issue(t + 2, 1);
-      seam();
-      __builtin_amdgcn_s_setprio(1); multiply(0); __builtin_amdgcn_s_setprio(0);
-      seam();
-      // ---- phase 1: all rows x n-hi; fetches B of tile t + 2; tile t + 1 must have landed before the next phase reads it --------------------
-      load_b(buf, 1);
-      issue(t + 2, 2);
-      if (t + 2 < ktiles) wait_vmcnt<6>(); else wait_vmcnt<0>();
-      seam();
-      __builtin_amdgcn_s_setprio(1); multiply(1); __builtin_amdgcn_s_setprio(0);
-      seam();
-    } else if constexpr (FORM == 1) {
-      // (lab form) all six fetches of tile t + 2 in phase 0: B gets 1.75 K tiles of flight instead of 1.0 -- 3 - 9 % slower
-      load_b(buf, 0); __builtin_amdgcn_sched_barrier(0); load_a(buf);
-      issue(t + 2, 0); issue(t + 2, 1); issue(t + 2, 2);
-      seam();
-      __builtin_amdgcn_s_setprio(1); multiply(0); __builtin_amdgcn_s_setprio(0);
-      seam();
-      load_b(buf, 1);
-      if (t + 2 < ktiles) wait_vmcnt<6>(); else wait_vmcnt<0>();
-      seam();
-      __builtin_amdgcn_s_setprio(1); multiply(1); __builtin_amdgcn_s_setprio(0);
-      seam();
-    } else if constexpr (FORM == 2) {
-      // (lab form) 8 + 8 fragment reads: phase 0 reads A (t), phase 1 reads B-hi (t) and B-lo (t + 1); tile t + 1 landed by the end of phase 0
-      // -- 5 - 15 % slower
-      load_a(buf);
-      issue(t + 2, 0); issue(t + 2, 1); issue(t + 2, 2);
-      if (t + 2 < ktiles) wait_vmcnt<6>(); else wait_vmcnt<0>();
-      seam();
-      __builtin_amdgcn_s_setprio(1); multiply(0); __builtin_amdgcn_s_setprio(0);
-      seam();
-      load_b(buf, 1);
-      if (t + 1 < ktiles) load_b(smem + ((t + 1) % 3) * kHBuf, 0);
-      seam();
-      __builtin_amdgcn_s_setprio(1); multiply(1); __builtin_amdgcn_s_setprio(0);
-      seam();
-    } else {
-      // (lab form) 12 reads + one fetch in phase 0, 4 reads + two fetches in phase 1: level (+- 2 %)
-      load_b(buf, 0); __builtin_amdgcn_sched_barrier(0); load_a(buf);
-      issue(t + 2, 0);
-      seam();
-      __builtin_amdgcn_s_setprio(1); multiply(0); __builtin_amdgcn_s_setprio(0);
-      seam();
-      load_b(buf, 1);
-      issue(t + 2, 1); issue(t + 2, 2);
-      if (t + 2 < ktiles) wait_vmcnt<6>(); else wait_vmcnt<0>();
-      seam();
-      __builtin_amdgcn_s_setprio(1); multiply(1); __builtin_amdgcn_s_setprio(0);
-      seam();
-    }
+    // ---- phase 0: all rows x n-lo; reads every A fragment and the n-lo B fragments; fetches the A halves of tile t + 2 ------------------
+    load_b(buf, 0); __builtin_amdgcn_sched_barrier(0); load_a(buf);
+    issue(t + 2, 0); issue(t + 2, 1);
+    seam();
+    __builtin_amdgcn_s_setprio(1); multiply(0); __builtin_amdgcn_s_setprio(0);
+    seam();
+    // ---- phase 1: all rows x n-hi; fetches B of tile t + 2; tile t + 1 must have landed before the next phase reads it --------------------
+    load_b(buf, 1);
+    issue(t + 2, 2);
+    if (t + 2 < ktiles) wait_vmcnt<6>(); else wait_vmcnt<0>();
+    seam();
+    __builtin_amdgcn_s_setprio(1); multiply(1); __builtin_amdgcn_s_setprio(0);
+    seam();
   }
   if (g == 0) asm volatile("s_barrier" ::: "memory");  // group 0 catches up: from here on the LDS is free for every wave
   if constexpr (!IS_INT) asm volatile("s_nop 15\n\ts_nop 3" ::: "memory");  // asm MFMA results -> VALU / VMEM readers (see gemm8_p8_kernel)
@@ -783,15 +653,7 @@ __global__ __launch_bounds__(512) void gemm8_p8h_kernel(P8Args p) {
 
   // ---- epilogue: lane (col = nl, kq) holds rows 4 kq + {0..3} of each 16 x 16 tile ---------------------------------------------------------
   if constexpr (EPI == P8_INT32 || EPI == P8_FP8_RAW) {
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int m = rbase + mt * 16 + kq * 4 + r, n = cbase + nt * 16 + nl;
-          if (m < p.M && n < p.N) reinterpret_cast<uint32_t*>(p.out)[(size_t)m * p.N + n] = __builtin_bit_cast(u32x4, acc[mt][nt])[r];
-        }
+    store_raw32<4>(acc, reinterpret_cast<uint32_t*>(p.out), p.M, p.N, rbase, cbase, nl, kq);
   } else {
     float cs[4], bias[4];
 #pragma unroll
@@ -800,33 +662,14 @@ __global__ __launch_bounds__(512) void gemm8_p8h_kernel(P8Args p) {
       cs[nt] = __builtin_bit_cast(float, pre_cs[nt]);
       bias[nt] = bf16_lo_to_f32((uint16_t)pre_bias[nt]);
     }
-    char* region = smem + wave * (64 * kEpiStride);
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
-      float rs[4];
+    store_bf16_staged<IS_INT, 4>(acc, reinterpret_cast<uint16_t*>(p.out), p.M, p.N, smem + wave * (64 * kEpiStride), rbase, cbase, lane, nl, kq, cs,
+                                 p.bias != nullptr, bias, [&](int mt, float (&rs)[4]) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         asm volatile("" : "+v"(pre_rs[mt][r]));
         rs[r] = __builtin_bit_cast(float, pre_rs[mt][r]);
       }
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float c = IS_INT ? (float)__builtin_bit_cast(i32x4, acc[mt][nt])[r] : acc[mt][nt][r];
-          const float v = epilogue8<IS_INT>(c, rs[r], cs[nt], p.bias != nullptr, bias[nt]);
-          *reinterpret_cast<uint16_t*>(region + (mt * 16 + kq * 4 + r) * kEpiStride + (nt * 16 + nl) * 2) = f32_to_bf16_bits(v);
-        }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    uint16_t* out = reinterpret_cast<uint16_t*>(p.out);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int row = i * 8 + (lane >> 3), piece = lane & 7;
-      const u32x4 v = *reinterpret_cast<const u32x4*>(region + row * kEpiStride + piece * 16);
-      const int m = rbase + row, n = cbase + piece * 8;
-      if (m < p.M && n + 8 <= p.N) *reinterpret_cast<u32x4*>(out + (size_t)m * p.N + n) = v;
-    }
+    });
   }
 }
 
@@ -863,24 +706,6 @@ int launch_p8h(P8Args p, int split, hipStream_t stream) {
     const int NG = (p.split + 3) / 4;
     if (int rc = splitk_workspace(stream, &p.ws, &p.tickets, (size_t)p.tiles_m * p.tiles_n * (p.split + NG) * 256 * 128, p.split)) return rc;
   }
-#ifdef AO_LAB  // the measured-and-rejected loop forms (profiles/p8h_loop_forms_r05.jsonl) only exist in the laboratory build
-  const int form = gemm8_force().p8h_form;  // ao_gemm8_set_tuning key 8
-  if (EPI == P8_FP8_ROWWISE && form == 1) {
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(gemm8_p8h_kernel<P8_FP8_ROWWISE, 1>), kHSmem, "hipFuncSetAttribute(gemm8_p8h_kernel)")) return rc;
-    ao::launch(gemm8_p8h_kernel<P8_FP8_ROWWISE, 1>, dim3((unsigned)(p.tiles_m * p.tiles_n * p.split)), dim3(512), kHSmem, stream, p);
-    return AO_OK;
-  }
-  if (EPI == P8_FP8_ROWWISE && form == 3) {
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(gemm8_p8h_kernel<P8_FP8_ROWWISE, 3>), kHSmem, "hipFuncSetAttribute(gemm8_p8h_kernel)")) return rc;
-    ao::launch(gemm8_p8h_kernel<P8_FP8_ROWWISE, 3>, dim3((unsigned)(p.tiles_m * p.tiles_n * p.split)), dim3(512), kHSmem, stream, p);
-    return AO_OK;
-  }
-  if (EPI == P8_FP8_ROWWISE && form == 2) {
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(gemm8_p8h_kernel<P8_FP8_ROWWISE, 2>), kHSmem, "hipFuncSetAttribute(gemm8_p8h_kernel)")) return rc;
-    ao::launch(gemm8_p8h_kernel<P8_FP8_ROWWISE, 2>, dim3((unsigned)(p.tiles_m * p.tiles_n * p.split)), dim3(512), kHSmem, stream, p);
-    return AO_OK;
-  }
-#endif
   if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(gemm8_p8h_kernel<EPI>), kHSmem, "hipFuncSetAttribute(gemm8_p8h_kernel)")) return rc;
   ao::launch(gemm8_p8h_kernel<EPI>, dim3((unsigned)(p.tiles_m * p.tiles_n * p.split)), dim3(512), kHSmem, stream, p);
   AO_LAUNCH_CHECK("gemm8_p8h_kernel launch");
@@ -889,25 +714,15 @@ int launch_p8h(P8Args p, int split, hipStream_t stream) {
 
 constexpr int kP8ChipCUs = 256;     // MI355X: one persistent workgroup per CU, 32 per XCD
 
-// The persistent form takes full tiles when there are more tiles than CUs, and any tile count at K < 4096, where its register-only epilogue and
-// DMA-fetched scales are worth 2 - 7 % even with one tile per workgroup (profiles/p8_persist_ab_r06.jsonl, same process, alternating, cold weights:
-// int8 at M = 16384 qkv 347 -> 331 us, o 222 -> 220, gate / up 784 -> 759, down 705 -> 707; fp8 K = 3584 / 4096 + 5 - 12 %, K = 1024 + 24 %;
-// at <= 256 tiles and K >= 4096 the two are level, +- 1 %).  A loop form that dealt the 24 fragment reads of a K tile 8 / 4 / 8 / 4 over the
-// four phases (the n-lo B fragments prefetched a K tile ahead) instead of 16 / 0 / 8 / 0 was 3 - 13 % SLOWER in every cell of that file
-// ("balanced") and left the tree; so did a form that read the A fragments of the next phase under the wave's OWN MFMAs (a second fragment
-// register set; no load phase but q0 then waits for an LDS round trip): int8 15 - 20 % slower, fp8 4 - 7 % (profiles/p8_persist_form1_ab_r06.jsonl) --
-// the phase structure's premise, one wave row reads while the other multiplies, is where this loop is fastest.
-bool p8_persistent_shape(int64_t M, int64_t N, int64_t K) {
-  return M % 256 == 0 && N % 256 == 0 && K >= 256 && K % 128 == 0 && ((M / 256) * (N / 256) > kP8ChipCUs || K < 4096);
-}
-
 template <int EPI>
 int launch_p8(P8Args p, bool persistent, hipStream_t stream) {
   p.tiles_m = (p.M + 255) / 256;
   p.tiles_n = (p.N + 255) / 256;
+  // round 5 sweep (profiles/p8_group_rows_r05.jsonl): 4 tile rows per group measured 0 .. 7 % ahead of 8 on the Llama-3-8B int8 shapes at
+  // M = 16384 (an XCD's L2 then holds 4 MB of A panels, its size, instead of 8 MB) and level elsewhere
+  p.group_rows = p8_group_rows();
+  p.split = 1;
   if (persistent) {
-    p.group_rows = p8_group_rows();
-    p.split = 1;
     const int64_t tiles = (int64_t)p.tiles_m * p.tiles_n;
     const unsigned grid = (unsigned)std::min<int64_t>(kP8ChipCUs, (tiles + 7) / 8 * 8);
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(gemm8_p8p_kernel<EPI>), kPSmem, "hipFuncSetAttribute(gemm8_p8p_kernel)")) return rc;
@@ -915,14 +730,21 @@ int launch_p8(P8Args p, bool persistent, hipStream_t stream) {
     AO_LAUNCH_CHECK("gemm8_p8p_kernel launch");
     return AO_OK;
   }
-  // round 5 sweep (profiles/p8_group_rows_r05.jsonl): 4 tile rows per group measured 0 .. 7 % ahead of 8 on the Llama-3-8B int8 shapes at
-  // M = 16384 (an XCD's L2 then holds 4 MB of A panels, its size, instead of 8 MB) and level elsewhere
-  p.group_rows = p8_group_rows();
-  p.split = 1;
   if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(gemm8_p8_kernel<EPI>), kSmem, "hipFuncSetAttribute(gemm8_p8_kernel)")) return rc;
   ao::launch(gemm8_p8_kernel<EPI>, dim3((unsigned)(p.tiles_m * p.tiles_n)), dim3(512), kSmem, stream, p);
   AO_LAUNCH_CHECK("gemm8_p8_kernel launch");
   return AO_OK;
+}
+
+// epi (the P8Epi numbering of the entry points below) -> its template instance: f(std::integral_constant<int, EPI>)
+template <class F>
+int with_epi(int epi, F f) {
+  switch (epi) {
+    case P8_INT8_SCALED: return f(std::integral_constant<int, P8_INT8_SCALED>{});
+    case P8_INT32: return f(std::integral_constant<int, P8_INT32>{});
+    case P8_FP8_ROWWISE: return f(std::integral_constant<int, P8_FP8_ROWWISE>{});
+    default: return f(std::integral_constant<int, P8_FP8_RAW>{});
+  }
 }
 
 }  // namespace
@@ -952,30 +774,30 @@ int gemm8_p8h_parts(int64_t M, int64_t N, int64_t K, int forced) {
                                          (int64_t)kSplitMaxTickets / (tiles * 5)});
   return (int)std::max<int64_t>(1, std::min<int64_t>(forced > 0 ? forced : p8h_split_rule(M, N, K), fit));
 }
-bool gemm8_p8_persistent_shape(int64_t M, int64_t N, int64_t K) { return p8_persistent_shape(M, N, K); }
+// The persistent form takes full tiles when there are more tiles than CUs, and any tile count at K < 4096, where its register-only epilogue and
+// DMA-fetched scales are worth 2 - 7 % even with one tile per workgroup (profiles/p8_persist_ab_r06.jsonl, same process, alternating, cold weights:
+// int8 at M = 16384 qkv 347 -> 331 us, o 222 -> 220, gate / up 784 -> 759, down 705 -> 707; fp8 K = 3584 / 4096 + 5 - 12 %, K = 1024 + 24 %;
+// at <= 256 tiles and K >= 4096 the two are level, +- 1 %).  A loop form that dealt the 24 fragment reads of a K tile 8 / 4 / 8 / 4 over the
+// four phases (the n-lo B fragments prefetched a K tile ahead) instead of 16 / 0 / 8 / 0 was 3 - 13 % SLOWER in every cell of that file
+// ("balanced") and left the tree; so did a form that read the A fragments of the next phase under the wave's OWN MFMAs (a second fragment
+// register set; no load phase but q0 then waits for an LDS round trip): int8 15 - 20 % slower, fp8 4 - 7 % (profiles/p8_persist_form1_ab_r06.jsonl) --
+// the phase structure's premise, one wave row reads while the other multiplies, is where this loop is fastest.
+bool gemm8_p8_persistent_shape(int64_t M, int64_t N, int64_t K) {
+  return M % 256 == 0 && N % 256 == 0 && K >= 256 && K % 128 == 0 && ((M / 256) * (N / 256) > kP8ChipCUs || K < 4096);
+}
 
 // the 256 x 128 form with `split` K parts (same epi numbering and shape limits)
 int gemm8_p8h(int epi, const uint8_t* a, const uint8_t* b, const float* row_scale, const float* col_scale, const uint16_t* bias, void* out,
               int64_t M, int64_t N, int64_t K, int split, hipStream_t stream) {
   P8Args p{a, b, row_scale, col_scale, bias, out, (int)M, (int)N, (int)K, 0, 0, 0, 1, nullptr, nullptr};
-  switch (epi) {
-    case P8_INT8_SCALED: return launch_p8h<P8_INT8_SCALED>(p, split, stream);
-    case P8_INT32: return launch_p8h<P8_INT32>(p, split, stream);
-    case P8_FP8_ROWWISE: return launch_p8h<P8_FP8_ROWWISE>(p, split, stream);
-    default: return launch_p8h<P8_FP8_RAW>(p, split, stream);
-  }
+  return with_epi(epi, [&](auto e) { return launch_p8h<decltype(e)::value>(p, split, stream); });
 }
 
 // persistent: the gemm8_p8p_kernel form (full 256 x 256 tiles, 16-byte-aligned scales and output)
 int gemm8_p8(int epi, const uint8_t* a, const uint8_t* b, const float* row_scale, const float* col_scale, const uint16_t* bias, void* out,
              int64_t M, int64_t N, int64_t K, bool persistent, hipStream_t stream) {
   P8Args p{a, b, row_scale, col_scale, bias, out, (int)M, (int)N, (int)K, 0, 0, 0, 1, nullptr, nullptr};
-  switch (epi) {
-    case P8_INT8_SCALED: return launch_p8<P8_INT8_SCALED>(p, persistent, stream);
-    case P8_INT32: return launch_p8<P8_INT32>(p, persistent, stream);
-    case P8_FP8_ROWWISE: return launch_p8<P8_FP8_ROWWISE>(p, persistent, stream);
-    default: return launch_p8<P8_FP8_RAW>(p, persistent, stream);
-  }
+  return with_epi(epi, [&](auto e) { return launch_p8<decltype(e)::value>(p, persistent, stream); });
 }
 
 }  // namespace ao

@@ -5,7 +5,7 @@
 // pair forms; ao_grouped8_route reports it).
 // The band rules it is built from are pure functions of the shape and the forced codes, defined next to their kernels.
 // The A/B knobs that change no route are read by the launchers from gemm8_force(): rb8_kernel's wave arrangement (variant 103) and probe
-// bits (tuning key 5), gemm8_p8(h)'s group rows (key 4), the laboratory loop forms of gemm8_p8h (key 8), the MX stream-K meeting (key 9).
+// bits (tuning key 5), gemm8_p8(h)'s group rows (key 4), the MX stream-K meeting (key 9).
 #pragma once
 #include <stdint.h>
 
@@ -52,8 +52,8 @@ struct Gemm8Force {
   bool mx_quad = true;      // 129 (false): the stream-K kernel's per-step-scales form on every K
   int dec8 = 0;             // 200 .. 299: dec8_kernel's forms (dec8_plan)
   int mid8 = 0;             // 300 .. 329: mid8_kernel's forms (mid8_plan)
-  // ao_gemm8_set_tuning keys 1 .. 9
-  int rb8_bn = 0, rb8_split = 0, rb8_bm = 0, p8_group_rows = 0, rb8_ablate = 0, p8_persist = 0, p8_split = 0, p8h_form = 0, mx_proto = 0;
+  // ao_gemm8_set_tuning keys 1 .. 7 and 9 (key 8 is accepted and ignored: it sets nothing here and does not mark the thread as overridden)
+  int rb8_bn = 0, rb8_split = 0, rb8_bm = 0, p8_group_rows = 0, rb8_ablate = 0, p8_persist = 0, p8_split = 0, mx_proto = 0;
 };
 
 // the calling thread's overrides (gemm8_kernels.hip)

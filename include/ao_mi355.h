@@ -171,7 +171,8 @@ int ao_gemm8_set_variant(int variant);
  *          reads, 2 no weight DMAs, 3 no activation DMAs, 4 DMA wait + barrier on even steps only -- the product build ignores it
  *   key 6  the persistent form of the 256 x 256 GEMM (gemm8_p8p_kernel): 1 never, 2 wherever the shape allows
  *   key 7  K parts of gemm8_p8h_kernel (1 .. 16, clamped to what fits one round of the chip and the split-K workspace)
- *   key 8  loop form of gemm8_p8h_kernel, laboratory build only (the product build ignores it)
+ *   key 8  retired (it chose among laboratory loop forms of gemm8_p8h_kernel, profiles/p8h_loop_forms_r05.jsonl): accepted so that old
+ *          scripts run, sets nothing, and does not make ao_gemm8_overridden() report an override
  *   key 9  the MXFP8 stream-K kernel's meeting, A/B: bit 0 the head piece's ticket after the loop, bit 1 no early read of the tail ticket
  *          (3 = the round-3 protocol)
  * An unknown key is an error.  DESIGN.md 4.5h. */

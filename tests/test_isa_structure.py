@@ -61,7 +61,7 @@ def test_gemm8_p8_mfmas_stay_inside_their_phases(tmp_path):
         assert seq.count("D") >= 6, (epi, seq)  # (8 per K tile; a rotated loop leaves the last pair outside the backward branch's span)
     # the 256 x 128 form (round 5): two phases per K tile, the same seams
     for epi, per_phase in ((0, 16), (1, 16), (2, 8), (3, 8)):
-        seq = _loop_ops(asm, f"_ZN2ao12_GLOBAL__N_116gemm8_p8h_kernelILi{epi}ELi0EEEvNS0_6P8ArgsE")
+        seq = _loop_ops(asm, f"_ZN2ao12_GLOBAL__N_116gemm8_p8h_kernelILi{epi}EEEvNS0_6P8ArgsE")
         groups = [len(g) for g in re.findall(r"M+", seq)]
         assert groups == [per_phase] * 2, f"EPI {epi}: the K tile's MFMAs are not two phases of {per_phase}: {seq}"
         assert seq.count("|") == 4 and seq.count("r") == 16 and seq.count("D") >= 4, (epi, seq)
@@ -169,3 +169,18 @@ def test_kernel_sources_leave_the_wgrad_frame_and_the_cast_tile_walk_to_their_he
         assert not offenders, f"call {instead} instead of {needle}...) in: {', '.join(offenders)}"
     offenders = [f for f, text in sources.items() if re.search(r"\bkTileLds\b", text)]
     assert not offenders, f"call stage_cols_t / flush_cols_t (fp8_train_tile.h) instead of indexing the staged tile in: {', '.join(offenders)}"
+
+
+def test_p8_kernel_source_states_the_mfma_phase_and_the_swizzle_once():
+    """The three phase-interleaved GEMMs share one MFMA phase (mfma_phase: the volatile-asm fp8 MFMA, accumulating and from zero) and one
+    statement of the source swizzle with its inverse (dma_src_chunk, frag_pos).  A kernel that spells the MFMA or the XOR out again is
+    restating them: a fix to the hazard cover or the swizzle would then have to be made in several places."""
+    lines = open(os.path.join(ROOT, "ao_amd", "csrc", "gemm8_p8_kernels.hip")).read().split("\n")
+    code = [l.split("//")[0] for l in lines]
+    assert 1 <= sum(l.count("v_mfma_scale_f32_16x16x128_f8f6f4") for l in code) <= 2
+    # the swizzle: an XOR with a halved row index, on the DMA side and on the fragment side, and the other k half's ^ 64
+    swizzle = [l for l in code if re.search(r"\^ *\(\w+ *>> *1\)", l) or re.search(r"\^ *64\b", l)]
+    assert len(swizzle) == 3, swizzle
+    assert re.match(r"__device__ __forceinline__ uint32_t dma_src_chunk\(", swizzle[0]) and re.match(r"__device__ __forceinline__ int frag_pos\(", swizzle[1])
+    load_frags = "\n".join(code).split("void load_frags(")[1].split("\n}\n")[0]
+    assert swizzle[2] in load_frags
