@@ -5,16 +5,17 @@
 //   fp8 :  y[M,N] = bf16((a . b^T) * scale_a[m] * scale_b[n] + bias[n])     aten::_scaled_mm rowwise, float8/inference.py:104-123
 //   int8:  y[M,N] = bf16(bf16(i32(a . b^T) * sx[m]) * sw[n] + bias[n])      _int_mm + scales, int8_tensor.py:305-359
 //
-// Same structure as the batched int4 kernel (int4_kernels.hip, int4_mm_rb_kernel) without the dequant: a wave owns
-// one 16-wide n-tile and all 128 rows of the slab.  Its weight rows go HBM -> wave-private LDS ring (full 128-byte lines
-// per request) -> registers as the B operand of v_mfma_scale_f32_16x16x128_f8f6f4 (unit block scales) or of two
-// v_mfma_i32_16x16x64_i8 (lane (n, kq) holds k = 16 kq .. +15 and 64 + 16 kq .. +15 of the 128-k step);
-// the activation tile [128 rows][128 B] is staged once per workgroup by
-// LDS-DMA with a source-side swizzle (chunk position c' of row r holds global 16-byte chunk c' ^ ((r >> 1) & 7)) so
-// that the two ds_read_b128 of an A operand are bank-conflict free.  Activations are fetched 2 steps ahead (L2 hits),
-// weights 5 steps ahead (with 2 the loop ran at 0.9 us per step: too few HBM bytes in flight); one hand-counted
-// s_waitcnt vmcnt + one LDS-only barrier per step.  K is cut into parts when the grid is small; the
-// parts meet through the fence-free split-K workspace (splitk.h), the last arriver applies the scales.
+// Same structure as the batched int4 kernel (int4_kernels.hip, int4_mm_rb_kernel) without the dequant.  An n-tile's weight rows go
+// HBM -> LDS ring (full 128-byte lines per request) -> registers as the B operand of v_mfma_scale_f32_16x16x128_f8f6f4 (unit block
+// scales) or of two v_mfma_i32_16x16x64_i8 (lane (n, kq) holds k = 16 kq .. +15 and 64 + 16 kq .. +15 of the 128-k step); the activation
+// tile [128 rows][128 B] is staged once per workgroup by LDS-DMA with a source-side swizzle (chunk position c' of row r holds global
+// 16-byte chunk c' ^ ((r >> 1) & 7)) so that the two ds_read_b128 of an A operand are bank-conflict free.  Three kernels:
+//   rb8_rowwise_kernel  the two rowwise kinds: fetch roles, fragments double-buffered in registers, 1 x WAVES or 2 x 4 waves, K parts
+//                       that meet through the fence-free split-K workspace (splitk.h), LDS-transposed epilogue;
+//   rb8_grouped_kernel  RB8_MX / RB8_FP8_GROUPED: slab found from the group ends, plain loop specialised on the slab's m-tiles, MX scale
+//                       rings, direct stores, K never cut;
+//   mx_stream_kernel    the stream-K form of the MX decode sizes.
+// They share the small steps below (dma_row_offset .. scale_byte); Rb8RowwiseLds / Rb8GroupedLds hold every LDS address and size.
 #include "common.h"
 #include "gemm8_route.h"
 #include "lds_dma.h"
@@ -42,7 +43,6 @@ constexpr int w_stages(int waves, int kind, int mt, bool slim = false) {
 constexpr int a_stages(int waves, int kind, int mt) { return kStages; }
 // RB8_FP8_GROUPED: rowwise e4m3 like RB8_FP8, rows grouped by expert like RB8_MX (Float8Tensor's _grouped_mm, float8_tensor.py:1085-1122)
 enum Rb8Kind { RB8_FP8 = 0, RB8_INT8 = 1, RB8_MX = 2, RB8_FP8_GROUPED = 3 };
-constexpr bool GROUPED_KIND(int kind) { return kind == RB8_MX || kind == RB8_FP8_GROUPED; }
 
 struct Rb8Args {
   const uint8_t* a;       // [M][K] e4m3 / int8
@@ -54,47 +54,97 @@ struct Rb8Args {
   int M, N, K;
   const uint8_t* a_mx;    // MX: [M][K/32] e8m0
   const uint8_t* b_mx;    // MX: [E][N][K/32] e8m0
-  const int32_t* offs;    // MX: [E] cumulative group ends (null: one group)
+  const int32_t* offs;    // grouped kinds: [E] cumulative group ends (null: one group)
   // MX stream-K, round 6: a SECOND weight tensor of the same shape multiplied by the same activations in the same launch (an MoE layer's
   // w1 and w3: x @ w1, x @ w3) -- its column tiles follow the first's in every slab; null: one product
   const uint8_t* b2;
   const uint8_t* b2_mx;
   uint16_t* y2;
-  int slabs, E;           // MX: 128-row slabs per group the grid provides (grid.y = E * slabs)
+  int slabs, E;           // grouped kinds: slabs per group the grid provides (grid.y = E * slabs at most)
   float* ws;
   unsigned* tickets;
   unsigned long long* trace;  // profiling build only
   int ablate;  // profiling build (TRACE) only: 1 no MFMAs, 2 no fragment reads, 4 no weight DMAs, 8 no activation DMAs, 16 DMA wait + barrier on even steps only -- wrong results, timing probes
 };
 
+// ---- the steps the kernels of this file share (rb8_rowwise_kernel, rb8_grouped_kernel, mx_stream_kernel) ----
+// LDS-DMA source of one tile row: the 16-byte chunk lane & 7 requests of global row `grow`, which lands as row `row` of an operand tile
+// (chunk position c' of row r holds global chunk c' ^ ((r >> 1) & 7)), as a byte offset from the tensor's k position
+__device__ __forceinline__ uint32_t dma_row_offset(int grow, int row, int lane, int K) {
+  return (uint32_t)grow * (uint32_t)K + ((((lane & 7) ^ (row >> 1)) & 7) << 4);
+}
+// weight DMA i (0, 1) of a step fetches rows 8 i + (lane >> 3) of the n-tile as FULL 128-byte lines (chunk position lane & 7,
+// same swizzle as the activations); half-line requests -- one lane group per 64 bytes -- ran the stream at 3.7 TB/s
+// (one value per call: handed the boff[2] array by reference, the compiler stopped sharing (lane >> 3) * K between the two)
+__device__ __forceinline__ uint32_t weight_line_offset(int i, int lane, int K) { return dma_row_offset(8 * i + (lane >> 3), 8 * i + (lane >> 3), lane, K); }
+// A operand of lane (row r = nl, kq): chunks kq and 4 + kq of the row, at positions chunk ^ ((r >> 1) & 7); second half: ^ 64; + 2048 per
+// m-tile.  (An n-tile's 16 weight rows are laid out like an m-tile.)
+__device__ __forceinline__ int frag_pos(int nl, int kq) { return nl * 128 + (((kq ^ (nl >> 1)) & 7) << 4); }
+// the k step a fill of step k reads in a K part [k0, k0 + nk): fills past the end re-read the last step (unused)
+__device__ __forceinline__ int fill_step(int k0, int k, int nk) { return k0 + min(k, nk - 1); }
+__device__ __forceinline__ int ring_next(int stage, int n) { return (stage == n - 1) ? 0 : stage + 1; }
+__device__ __forceinline__ int ring_prev(int stage, int n) { return (stage == 0) ? n - 1 : stage - 1; }
+// MX: byte kq of a scale dword in LDS: lane group kq takes the scale of 32-k block kq of the step (layout probed on gfx950, stream8_kernels.hip)
+__device__ __forceinline__ int scale_byte(const char* dword, int kq) { return (int)(*reinterpret_cast<const uint32_t*>(dword) >> (8 * kq)) & 0xff; }
+
+// ---- LDS layouts: every address of the two kernels and the bytes their launchers ask for ----
+constexpr int kTile = 2048;  // one operand tile of a k step: 16 rows x 128 B (an m-tile, or an n-tile's weight rows); a DMA fills half of it (8 rows)
+// rb8_rowwise_kernel: [KA][16 MT rows][128 B] a | [WAVES][KW][2 KiB] b.  The epilogue re-uses the (then idle) bytes from 0: the scaled
+// tile [BM][RS] | row scales [BM] | column scales [BNW] | bias [BNW] (fp32).
+template <int WAVES, int MT>
+struct Rb8RowwiseLds {
+  static constexpr int KW = w_stages(WAVES, RB8_FP8, MT), KA = a_stages(WAVES, RB8_FP8, MT);  // (the same for RB8_INT8)
+  static constexpr int a_stage = MT * kTile;  // one activation stage: 16 MT rows x 128 k bytes
+  static constexpr int w = KA * a_stage, total = w + WAVES * KW * kTile;
+  // (built ON the base -- smem or its LDS offset -- left to right, as the loops always spelled it: base + (offset) moved their device text)
+  template <class B> static constexpr B a_at(B base, int stage) { return base + stage * a_stage; }
+  template <class B> static constexpr B w_at(B base, int ntile, int stage) { return base + w + (ntile * KW + stage) * kTile; }
+  static constexpr int BM = 16 * MT, BNW = 16 * WAVES;  // rows, columns of the workgroup's tile
+  static constexpr int RS = BNW * 2 + 16;               // staging row stride in bytes (+ 16: the 4 kq row groups of a b16 write land 8 banks apart)
+  static constexpr int epi_sa = BM * RS, epi_sb = epi_sa + BM * 4, epi_bias = epi_sb + BNW * 4, epi_total = epi_bias + BNW * 4;
+  static_assert(epi_total <= total, "rb8_rowwise_kernel: the epilogue's staging area lies inside the loop's rings");
+  static_assert(total <= 160 * 1024, "rb8_kernel: LDS");
+};
+// rb8_grouped_kernel: [KA][16 MT rows][128 B] a | [WAVES][KW][2 KiB] b | MX: a scales [ASN][WAVES][ASB] | b scales [WAVES][BSN][BSB]
+template <int WAVES, int KIND, int MT, bool SLIM, int QS>
+struct Rb8GroupedLds {
+  static constexpr int KW = w_stages(WAVES, KIND, MT, SLIM), KA = a_stages(WAVES, KIND, MT);
+  static constexpr int a_stage = MT * kTile;
+  static constexpr int w = KA * a_stage, as = w + WAVES * KW * kTile;
+  static constexpr int SCL = SLIM ? 64 : 256;   // bytes of one per-step scale slot (one dword per row: 16 rows -> 64 B; unmasked DMAs write 256)
+  static constexpr int RPW = 16 * MT / WAVES;   // activation-scale rows fetched per wave
+  // slot bytes, slots per wave -- QS == 1: a dword per row, a slot per ring stage; QS == 4: 16 B per row (a wave's rows), two slots
+  static constexpr int ASB = (QS == 1) ? SCL : RPW * 16, BSB = (QS == 1) ? SCL : 256;
+  static constexpr int ASN = (QS == 1) ? KA : 2, BSN = (QS == 1) ? KW : 2;
+  static constexpr int bs = as + ASN * WAVES * ASB;
+  static constexpr int total = (KIND == RB8_MX) ? bs + WAVES * BSN * BSB : as;
+  template <class B> static constexpr B a_at(B base, int stage) { return base + stage * a_stage; }
+  template <class B> static constexpr B w_at(B base, int wave, int stage) { return base + w + (wave * KW + stage) * kTile; }
+  template <class B> static constexpr B as_at(B base, int slot, int wave) { return base + as + (slot * WAVES + wave) * ASB; }
+  static constexpr int as_slot = WAVES * ASB;  // one slot of every wave's activation scales
+  template <class B> static constexpr B as_bytes(B base, int bytes) { return base + as + bytes; }
+  template <class B> static constexpr B bs_at(B base, int wave, int slot) { return base + bs + (wave * BSN + slot) * BSB; }
+  static_assert(!SLIM || 3 * total <= 160 * 1024, "SLIM: three workgroups per CU");
+  static_assert(total <= 160 * 1024, "rb8_kernel: LDS");
+};
+
 // TRACE (profiling build): s_memtime stamps of wave 0, 16 u64 per workgroup: entry, ring primed, barrier of steps 0..7 passed,
-// loop done, meeting done, exit
-// MT = 16-row m-tiles per slab (8, 4, 2): small batches / token groups stage, read and multiply only the rows they can have.
-// QS (MX): k steps per scale fetch -- 1: a dword DMA per row, step and operand; 4: one 16-byte DMA per row and FOUR steps, two slots
-// per wave and operand (K % 512 == 0, no K split).  The dword DMAs cost a quarter of the decode kernel (mx_stream_kernel below).
-// SM (round 4, rowwise kinds, 8 waves x 128 rows): the waves stand 2 (m halves) x 4 (pairs of n-tiles) instead of 1 x 8 -- wave (wm, wn)
-// multiplies m-tiles 4 wm .. 4 wm + 3 by n-tiles 2 wn, 2 wn + 1.  Same DMAs, same rings, same LDS layout (wave w still FETCHES n-tile w
-// and its eighth of the activation tile; the step's barrier already orders everybody's fetches before anybody's reads), same 8
-// accumulators and MFMAs per wave and step -- but 4 + 2 operand fragments to read per step instead of 8 + 1: 12 ds_read_b128 for 18,
-// on a loop that is bound by the LDS reads (144 KiB per step and workgroup at 128 B / clk against 512 cycles of MFMA per SIMD).
-template <int WAVES, int KIND, int MT = 8, bool TRACE = false, bool SLIM = false, int QS = 1, bool SM = false>
-__global__ __launch_bounds__(64 * WAVES) void rb8_kernel(Rb8Args p) {
-  static_assert(!SM || (WAVES == 8 && MT == 8 && (KIND == RB8_FP8 || KIND == RB8_INT8)), "rb8_kernel: the 2 x 4 wave arrangement is built for 8 waves x 128 rows, rowwise kinds");
-  constexpr int MH = MT / 2;  // SM: m-tiles per wave (wave (wm, wn): m-tiles MH wm .. + MH - 1, n-tiles 2 wn, 2 wn + 1; acc[2 i + j])
-  constexpr int SCL = SLIM ? 64 : 256;  // bytes of one scale slot (one dword per row: 16 rows -> 64 B; unmasked DMAs write 256)
-  static_assert(QS == 1 || (QS == 4 && KIND == RB8_MX && !SLIM), "rb8_kernel: 4-step scale fetches are an MX form");
-  unsigned long long ts[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // [13] group found, [14] addresses ready
+// loop done, meeting done, exit; [13] slab found, [14] addresses ready
+// MT = 16-row m-tiles per slab (8, 4): small batches / token groups stage, read and multiply only the rows they can have.
+// The waves stand MG (m groups) x NG (n groups) in the workgroup's tile: wave (wm, wn) multiplies m-tiles NA wm .. + NA - 1 by n-tiles
+// NB wn .. + NB - 1 into acc[NB i + j].  1 x WAVES: a wave owns one n-tile and all m-tiles.  SM (round 4, 8 waves x 128 rows): 2 (m halves)
+// x 4 (pairs of n-tiles) -- m-tiles 4 wm .. 4 wm + 3 by n-tiles 2 wn, 2 wn + 1.  Same DMAs, same rings, same LDS layout (the step's
+// barrier already orders everybody's fetches before anybody's reads), same 8 accumulators and MFMAs per wave and step -- but 4 + 2 operand
+// fragments to read per step instead of 8 + 1: 12 ds_read_b128 for 18, on a loop that is bound by the LDS reads (144 KiB per step and
+// workgroup at 128 B / clk against 512 cycles of MFMA per SIMD).
+template <int WAVES, bool INT8, int MT = 8, bool TRACE = false, bool SM = false>
+__global__ __launch_bounds__(64 * WAVES) void rb8_rowwise_kernel(Rb8Args p) {
+  static_assert(!SM || (WAVES == 8 && MT == 8), "rb8_kernel: the 2 x 4 wave arrangement is built for 8 waves x 128 rows, rowwise kinds");
+  using L = Rb8RowwiseLds<WAVES, MT>;
+  constexpr int KA = L::KA, KW = L::KW, BM = L::BM, BNW = L::BNW, RS = L::RS;
+  constexpr int MG = SM ? 2 : 1, NG = WAVES / MG, NA = MT / MG, NB = WAVES / NG;
+  unsigned long long ts[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   if (TRACE) ts[0] = __builtin_amdgcn_s_memtime();
-  constexpr bool INT8 = (KIND == RB8_INT8), MX = (KIND == RB8_MX), GROUPED = (KIND == RB8_MX || KIND == RB8_FP8_GROUPED);
-  constexpr int ADMA = 2 * MT / WAVES;  // activation DMAs per wave and stage (8 rows each)
-  static_assert(ADMA >= 1, "every wave issues the same number of DMAs per stage");
-  constexpr int kABuf = MT * 2048;      // one activation stage: 16 MT rows x 128 k bytes
-  constexpr int BM = 16 * MT;
-  constexpr int RPW = BM / WAVES;   // MX: activation-scale rows fetched per wave
-  constexpr int kWStages = w_stages(WAVES, KIND, MT, SLIM);
-  constexpr int KA = a_stages(WAVES, KIND, MT);  // activation ring
-  static_assert(!SLIM || (KIND == RB8_MX && BM / WAVES == 16), "SLIM: 16 activation-scale rows per wave");
-  // [3][128][128 B] a | [WAVES][6][2 KiB] b | MX: [3][WAVES][256 B] a scales | [WAVES][6][256 B] b scales
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int tid = threadIdx.x;
@@ -104,8 +154,6 @@ __global__ __launch_bounds__(64 * WAVES) void rb8_kernel(Rb8Args p) {
   const int ntiles = p.N >> 4;
   // (bx, by): the workgroup's column tile and slab; ks of S: its K part
   const int bx = blockIdx.x, by = blockIdx.y, ks = blockIdx.z, S = gridDim.z, gx = gridDim.x;
-  const int tile = bx * WAVES + wave;
-  const int tile_c = min(tile, ntiles - 1);  // tiles past N alias the last one; never stored
   const int ksteps = p.K >> 7;
   // (32-bit: ksteps < 2^24 and S <= 16 -- the 64-bit division this used to be was ~300 scalar instructions at the head of every workgroup)
   const int k0 = (int)(((unsigned)ksteps * (unsigned)ks) / (unsigned)S);
@@ -114,327 +162,152 @@ __global__ __launch_bounds__(64 * WAVES) void rb8_kernel(Rb8Args p) {
   // DMAs (and the two activation DMAs) of a stage behind ONE M0 write: +- 0.1 us here and on the MX stream-K kernel; the epilogue's
   // scales requested ahead of the meeting (at the head of the kernel, behind the loop, or behind the drain -- handed on through LDS):
   // + 2 us per launch in all three placements.
-  // rows of this workgroup: [m0, m_end) -- a slab of the matrix, or of one expert's token group.  Grouped kinds: blockIdx.y
-  // enumerates the NON-EMPTY slabs in (expert, slab) order -- the y-th one is found from the group ends on the device, so the
-  // grid needs ceil(M / BM) + E rows at most (not E x the slabs of the largest possible group) and an expert without tokens
-  // costs nothing.
-  int m0 = by * BM, m_end = p.M, expert = 0;
-  if constexpr (GROUPED) {
-    if (p.offs != nullptr) {
-      int y = by, found = -1, begin = 0, end = 0;
-      for (int e0 = 0; e0 < p.E && found < 0; e0 += 64) {  // 64 experts per pass: lane e owns expert e0 + e
-        const int e = e0 + lane;
-        const int lo = (e > 0 && e < p.E) ? p.offs[e - 1] : 0;
-        const int hi = (e < p.E) ? p.offs[e] : lo;
-        const int ns = (hi - lo + BM - 1) / BM;  // slabs of this expert (0 when it has no tokens)
-        int incl = ns;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-          const int t = __shfl_up(incl, d);
-          if (lane >= d) incl += t;
-        }
-        const unsigned long long hit = __ballot(incl > y);
-        if (hit != 0ull) {
-          const int l = __builtin_ctzll(hit);
-          found = e0 + l;
-          begin = __builtin_amdgcn_readlane(lo, l);
-          end = __builtin_amdgcn_readlane(hi, l);
-          y -= __builtin_amdgcn_readlane(incl - ns, l);
-        } else {
-          y -= __builtin_amdgcn_readlane(incl, 63);
-        }
-      }
-      if (found < 0) return;  // uniform: past the last non-empty slab (before any DMA or barrier)
-      expert = found;
-      m0 = begin + y * BM;
-      m_end = end;
-    } else if (m0 >= m_end) {
-      return;
-    }
-  }
-  // m-tiles this slab really has, rounded up to a power of two: the k loop below is specialised on it, so a 32-row group in a
-  // 64- or 128-row slab reads and multiplies 32 rows (the DMA counts stay static for the hand-counted waits; rows past the
-  // group re-read its last row)
-  const int mt_have = (min(m_end - m0, BM) + 15) >> 4;
+  const int m0 = by * BM, m_end = p.M;  // rows of this workgroup: [m0, m_end), a slab of the matrix
   if (TRACE) ts[13] = __builtin_amdgcn_s_memtime();
 
-  // weight DMA i (0, 1) of a step fetches rows 8 i + (lane >> 3) of the n-tile as FULL 128-byte lines (chunk position lane & 7,
-  // same swizzle as the activations); half-line requests -- one lane group per 64 bytes -- ran the stream at 3.7 TB/s
   uint32_t boff[2];
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int row = 8 * i + (lane >> 3);
-    boff[i] = (uint32_t)row * (uint32_t)p.K + ((((lane & 7) ^ (row >> 1)) & 7) << 4);
-  }
-  const uint8_t* brows = p.b + ((size_t)expert * p.N + (size_t)tile_c * 16) * p.K;
+  for (int i = 0; i < 2; ++i) boff[i] = weight_line_offset(i, lane, p.K);
   const uint32_t a_lds = lds_offset(smem);
-  const uint32_t w_lds = a_lds + KA * kABuf + wave * (kWStages * 2048);
-  // MX block scales: one dword (4 e8m0 bytes = the 4 blocks of a 128-k step) per row and step.  Wave w fetches the dwords of
-  // activation rows RPW w .. + RPW - 1 (lanes past RPW repeat them into slots nobody reads) and of its own 16 weight rows.
-  const uint32_t kb32 = (uint32_t)(p.K >> 5);
-  const uint32_t asoff = MX ? (uint32_t)min(m0 + RPW * wave + (lane % RPW), m_end - 1) * kb32 : 0u;
-  const uint32_t bsoff = (uint32_t)nl * kb32;
-  const uint8_t* bsrows = MX ? p.b_mx + ((size_t)expert * p.N + (size_t)tile_c * 16) * kb32 : nullptr;
-  const uint32_t as_lds = a_lds + KA * kABuf + WAVES * (kWStages * 2048);
-  constexpr int ASB = (QS == 1) ? SCL : RPW * 16, BSB = 256;  // QS == 4: slot bytes (activation rows of a wave, its 16 weight rows: 16 B each)
-  const uint32_t bs_lds = (QS == 1) ? as_lds + KA * WAVES * SCL + wave * (kWStages * SCL) : as_lds + 2 * WAVES * ASB + wave * (2 * BSB);
-  auto issue_s = [&](int slot, int k) {  // QS == 4: the scales of steps k .. k + 3 (k % 4 == 0); past the end: the last block again
-    const int kk = k0 + min(k, nk - 4);
-    if (lane < RPW) dma_b128_s(p.a_mx + (size_t)kk * 4, asoff, as_lds + (slot * WAVES + wave) * ASB);
-    if (lane < 16) dma_b128_s(bsrows + (size_t)kk * 4, bsoff, bs_lds + slot * BSB);
-  };
-  auto issue_w = [&](int stage, int k) {
-    const int kk = k0 + min(k, nk - 1);
-    dma_b128_nt_s(brows + (size_t)kk * 128, boff[0], w_lds + stage * 2048);
-    dma_b128_nt_s(brows + (size_t)kk * 128, boff[1], w_lds + stage * 2048 + 1024);
-    if constexpr (MX && QS == 1) {
-      if (!SLIM || lane < 16) dma_b32_s(bsrows + (size_t)kk * 4, bsoff, bs_lds + stage * SCL);
-    }
-  };
 
-  // ROLES (round 5, rowwise kinds): the lower half of the waves fetches the activation tile, the upper half the weights (two n-tiles
-  // each).  VMEM retires in order per wave: a wave that requests w(k + 5) and then a(k + 2) cannot see a(k + 2) land before w(k + 5) has,
-  // so the weight ring's five stages of HBM latency cover were really two (the round-5 trace: 1100 ticks per step whatever the tile
-  // width -- half an HBM round trip).  With the kinds apart, an activation wave waits for L2 hits only and a weight wave has its whole
-  // ring in flight; the step's barrier publishes both, as before.  Same LDS layout, same MFMAs, same bits.
-  constexpr bool ROLES = !GROUPED;
+  // Roles (round 5): the lower half of the waves fetches the activation tile, the upper half the weights (two n-tiles each; tiles past
+  // N alias the last one, never stored).  VMEM retires in order per wave: a wave that requests w(k + 5) and then a(k + 2) cannot see
+  // a(k + 2) land before w(k + 5) has, so the weight ring's five stages of HBM latency cover were really two (the round-5 trace: 1100
+  // ticks per step whatever the tile width -- half an HBM round trip).  With the kinds apart, an activation wave waits for L2 hits only and
+  // a weight wave has its whole ring in flight; the step's barrier publishes both, as before.  Same LDS layout, same MFMAs, same bits.
   const bool is_a = wave < WAVES / 2;
-  const uint8_t* brows2[2] = {nullptr, nullptr};
+  const uint8_t* brows2[2] = {nullptr, nullptr};  // a weight wave's two n-tiles: their rows, their rings
   uint32_t w_lds2[2] = {0u, 0u};
-  if constexpr (ROLES) {
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int nt = max(2 * (wave - WAVES / 2) + j, 0);  // (activation waves: unused)
-      brows2[j] = p.b + (size_t)min(bx * WAVES + nt, ntiles - 1) * 16 * p.K;
-      w_lds2[j] = a_lds + KA * kABuf + nt * (kWStages * 2048);
-    }
+  for (int j = 0; j < 2; ++j) {
+    const int nt = max(2 * (wave - WAVES / 2) + j, 0);  // (activation waves: unused)
+    brows2[j] = p.b + (size_t)min(bx * WAVES + nt, ntiles - 1) * 16 * p.K;
+    w_lds2[j] = L::w_at(a_lds, nt, 0);
   }
   // the epilogue's scales, requested before anything else (one row scale, one column scale, one bias value per thread at most) and
   // handed on through LDS after the loop: by then they have long landed, and the tail has no memory round trip left but its stores
+  // (every part: any of them may turn out to be the last arriver)
   float pre_sa = 0.f, pre_sb = 0.f;
   uint32_t pre_bias = 0u;  // bf16 bits: converted in the epilogue (a use here would make the compiler wait for the load at the kernel's head)
-  if constexpr (!GROUPED) {
-    // (every part: any of them may turn out to be the last arriver)
-    if (tid < BM) pre_sa = p.scale_a[min(m0 + tid, p.M - 1)];
-    if (tid < 16 * WAVES) {
-      const int col = min(bx * (16 * WAVES) + tid, p.N - 1);
-      pre_sb = p.scale_b[col];
-      if (p.bias != nullptr) pre_bias = p.bias[col];
-    }
+  if (tid < BM) pre_sa = p.scale_a[min(m0 + tid, p.M - 1)];
+  if (tid < 16 * WAVES) {
+    const int col = min(bx * (16 * WAVES) + tid, p.N - 1);
+    pre_sb = p.scale_b[col];
+    if (p.bias != nullptr) pre_bias = p.bias[col];
   }
 
   f32x4 acc[MT];
 #pragma unroll
   for (int i = 0; i < MT; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-  // A operand of lane (row r = nl, kq): chunks kq and 4 + kq of the row, at positions chunk ^ ((r >> 1) & 7)
-  const int pa = nl * 128 + (((kq ^ (nl >> 1)) & 7) << 4);  // second half: ^ 64; + 2048 per m-tile
+  const int pa = frag_pos(nl, kq);
 
-  // Issue order (6 stages) is w(0..2) | a(0) w(3) | a(1) w(4), then per step a(k+2) w(k+5): when step k starts, the youngest requests
-  // are a(k+1), w(k+4) (one stage: LPSC) and w(k+3) (2 DMAs, 3 with MX scales); everything older -- a(k), w(k) .. w(k+2) -- has landed.
-  auto k_loop = [&](auto mtc) {
-  constexpr int MTC = decltype(mtc)::value;
-  // activation DMAs per wave and stage for the m-tiles this slab really has (8 rows each; with fewer 8-row blocks than waves
-  // the last waves re-fetch the group's last row into rows nobody reads): a 32-row group in a 64-row slab costs the workgroup
-  // 4 activation DMAs per step, not 8 -- the activation tile is half of what a CU's texture path moves per step
-  // (ROLES: the activation tile's 2 MTC DMAs are shared out among the WAVES / 2 activation waves)
-  constexpr int AD = ROLES ? 4 * MTC / WAVES : (2 * MTC >= WAVES) ? 2 * MTC / WAVES : 1;
+  // (a lambda as in the grouped kernel: written straight into the body, the loop's device text moves -- profiles/rb8_split_device_diff.txt)
+  auto k_loop = [&] {
+  // the activation tile's 2 MT DMAs per stage (8 rows each) are shared out among the WAVES / 2 activation waves; the weight waves never issue these
+  constexpr int AD = 4 * MT / WAVES;
   static_assert(AD >= 1, "rb8_kernel: every fetching wave issues the same number of DMAs per stage");
-  constexpr int LPSC = AD + 2 + ((MX && QS == 1) ? 2 : 0);
   uint32_t aoff[AD];
 #pragma unroll
   for (int i = 0; i < AD; ++i) {
-    const int row = 8 * (AD * wave + i) + (lane >> 3);  // (ROLES: wave < WAVES / 2 covers the tile; the weight waves never issue these)
-    aoff[i] = (uint32_t)min(m0 + min(row, BM - 1), m_end - 1) * (uint32_t)p.K + ((((lane & 7) ^ (row >> 1)) & 7) << 4);
+    const int row = 8 * (AD * wave + i) + (lane >> 3);
+    aoff[i] = dma_row_offset(min(m0 + min(row, BM - 1), m_end - 1), row, lane, p.K);
   }
-  auto issue_a = [&](int stage, int k) {  // k clamped: the fills past the end re-read the last step (unused)
-    const int kk = k0 + min(k, nk - 1);
+  auto issue_a = [&](int stage, int k) {
+    const int kk = fill_step(k0, k, nk);
     if (TRACE && (p.ablate & 8)) return;
 #pragma unroll
-    for (int i = 0; i < AD; ++i) dma_b128_s(p.a + (size_t)kk * 128, aoff[i], a_lds + stage * kABuf + (AD * wave + i) * 1024);
-    if constexpr (MX && QS == 1) {
-      if (!SLIM || lane < 16) dma_b32_s(p.a_mx + (size_t)kk * 4, asoff, as_lds + (stage * WAVES + wave) * SCL);
-    }
+    for (int i = 0; i < AD; ++i) dma_b128_s(p.a + (size_t)kk * 128, aoff[i], L::a_at(a_lds, stage) + (AD * wave + i) * (kTile / 2));
   };
-  auto issue_w2 = [&](int stage, int k) {  // ROLES: a weight wave's two n-tiles
-    const int kk = k0 + min(k, nk - 1);
+  auto issue_w2 = [&](int stage, int k) {  // a weight wave's two n-tiles
+    const int kk = fill_step(k0, k, nk);
     if (TRACE && (p.ablate & 4)) return;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      dma_b128_nt_s(brows2[j] + (size_t)kk * 128, boff[0], w_lds2[j] + stage * 2048);
-      dma_b128_nt_s(brows2[j] + (size_t)kk * 128, boff[1], w_lds2[j] + stage * 2048 + 1024);
+      dma_b128_nt_s(brows2[j] + (size_t)kk * 128, boff[0], w_lds2[j] + stage * kTile);
+      dma_b128_nt_s(brows2[j] + (size_t)kk * 128, boff[1], w_lds2[j] + stage * kTile + kTile / 2);
     }
   };
   if (TRACE) ts[14] = __builtin_amdgcn_s_memtime();
-  if constexpr (QS == 4) issue_s(0, 0);  // then the block of steps 4 j + 4 .. at the head of step 4 j + 1 (older than a(4 j + 3): landed by then)
-  if constexpr (ROLES) {
-    if (is_a) {
+  if (is_a) {
 #pragma unroll
-      for (int i = 0; i < KA - 1; ++i) issue_a(i, i);
-    } else {
-#pragma unroll
-      for (int i = 0; i < kWStages - 1; ++i) issue_w2(i, i);
-    }
+    for (int i = 0; i < KA - 1; ++i) issue_a(i, i);
   } else {
 #pragma unroll
-    for (int i = 0; i < kWStages - 3; ++i) issue_w(i, i);
-    issue_a(0, 0); issue_w(kWStages - 3, kWStages - 3);
-    issue_a(1, 1); issue_w(kWStages - 2, kWStages - 2);
+    for (int i = 0; i < KW - 1; ++i) issue_w2(i, i);
   }
   if (TRACE) ts[1] = __builtin_amdgcn_s_memtime();
   int stage = 0, wstage = 0;
-  if constexpr (ROLES) {
-    // Round 5: the step's operand fragments are double-buffered in REGISTERS.  The round-5 trace showed 1000 - 1200 ticks per step for every
-    // tile width, ring depth and fetch split -- the time of one wave's own instruction chain: the compiler emitted the step as four
-    // "ds_read x 4-6, wait, MFMA x 2" groups, an LDS round trip in front of each (one or two waves per SIMD, all parked at the same
-    // barrier: nothing else to issue).  Now step k + 1's barrier, its ring refills and ALL its fragment reads are issued before step
-    // k's MFMAs, which run from registers read a step earlier: the LDS latency sits under 8 MFMAs (256 matrix cycles) instead of
-    // between them.  Same products into the same accumulators in the same order: same bits.
-    constexpr int NA = SM ? MH : MTC, NB = SM ? 2 : 1;
-    struct Frags { u32x4 a0[NA], a1[NA], b0[NB], b1[NB]; };
-    const int wm = wave & 1, wn = wave >> 1;  // (SM)
-    int ksync = 0;  // the next step to synchronise
-    auto sync_issue_read = [&](Frags& f) {
-      // step ksync's operands have landed (an activation wave may have a(k + 1) .. a(k + KA - 2) in flight, a weight wave
-      // w(k + 1) .. w(k + kWStages - 2), four DMAs a stage) and everyone has finished READING step ksync - 1 (lgkmcnt(0) before the
-      // barrier): its slots are refilled, then this step's fragments are requested
-      static_assert(AD * (KA - 2) <= 63 && 4 * (kWStages - 2) <= 63, "rb8_kernel: vmcnt is a 6-bit counter");
-      // (timing probe 16 of the traced build: the DMA wait and the barrier on even steps only -- what a 256-byte K step would save at best)
-      const bool skip_sync = TRACE && (p.ablate & 16) && (ksync & 1);
-      if (!skip_sync) { if (is_a) wait_vmcnt<AD * (KA - 2)>(); else wait_vmcnt<4 * (kWStages - 2)>(); }
-      // (the LDS wait as a BUILTIN, not inside the asm: the compiler's wait-count pass has to see it, or it takes the fragments read
-      // a step ago for still in flight behind the new reads and waits for those in front of every MFMA -- lgkmcnt(13) .. (0))
-      __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0); vmcnt, expcnt untouched
-      if (!skip_sync) asm volatile("s_barrier" ::: "memory");
-      if (TRACE && ksync < 8) ts[2 + ksync] = __builtin_amdgcn_s_memtime();
-      if (is_a) issue_a((stage == 0) ? KA - 1 : stage - 1, ksync + KA - 1);
-      else issue_w2((wstage == 0) ? kWStages - 1 : wstage - 1, ksync + kWStages - 1);
-      const char* A = smem + stage * kABuf;
-      if (TRACE && (p.ablate & 2)) {
-      } else if constexpr (SM) {
+  // Round 5: the step's operand fragments are double-buffered in REGISTERS.  The round-5 trace showed 1000 - 1200 ticks per step for every
+  // tile width, ring depth and fetch split -- the time of one wave's own instruction chain: the compiler emitted the step as four
+  // "ds_read x 4-6, wait, MFMA x 2" groups, an LDS round trip in front of each (one or two waves per SIMD, all parked at the same
+  // barrier: nothing else to issue).  Now step k + 1's barrier, its ring refills and ALL its fragment reads are issued before step
+  // k's MFMAs, which run from registers read a step earlier: the LDS latency sits under 8 MFMAs (256 matrix cycles) instead of
+  // between them.  Same products into the same accumulators in the same order: same bits.
+  struct Frags { u32x4 a0[NA], a1[NA], b0[NB], b1[NB]; };
+  const int wm = (int)((unsigned)wave % MG), wn = (int)((unsigned)wave / MG);
+  int ksync = 0;  // the next step to synchronise  ((wm, wn) here and again at the epilogue: declared once at the top, the 2 x 4 loops change)
+  auto sync_issue_read = [&](Frags& f) {
+    // step ksync's operands have landed (an activation wave may have a(k + 1) .. a(k + KA - 2) in flight, a weight wave
+    // w(k + 1) .. w(k + KW - 2), four DMAs a stage) and everyone has finished READING step ksync - 1 (lgkmcnt(0) before the
+    // barrier): its slots are refilled, then this step's fragments are requested
+    static_assert(AD * (KA - 2) <= 63 && 4 * (KW - 2) <= 63, "rb8_kernel: vmcnt is a 6-bit counter");
+    // (timing probe 16 of the traced build: the DMA wait and the barrier on even steps only -- what a 256-byte K step would save at best)
+    const bool skip_sync = TRACE && (p.ablate & 16) && (ksync & 1);
+    if (!skip_sync) { if (is_a) wait_vmcnt<AD * (KA - 2)>(); else wait_vmcnt<4 * (KW - 2)>(); }
+    // (the LDS wait as a BUILTIN, not inside the asm: the compiler's wait-count pass has to see it, or it takes the fragments read
+    // a step ago for still in flight behind the new reads and waits for those in front of every MFMA -- lgkmcnt(13) .. (0))
+    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0); vmcnt, expcnt untouched
+    if (!skip_sync) asm volatile("s_barrier" ::: "memory");
+    if (TRACE && ksync < 8) {  // (static indices: the stamps stay in registers -- indexed by ksync, the array went to scratch)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const char* Wj = smem + KA * kABuf + ((2 * wn + j) * kWStages + wstage) * 2048;
-          f.b0[j] = *reinterpret_cast<const u32x4*>(Wj + pa);
-          f.b1[j] = *reinterpret_cast<const u32x4*>(Wj + (pa ^ 64));
-        }
+      for (int i = 0; i < 8; ++i) if (ksync == i) ts[2 + i] = __builtin_amdgcn_s_memtime();
+    }
+    if (is_a) issue_a(ring_prev(stage, KA), ksync + KA - 1);
+    else issue_w2(ring_prev(wstage, KW), ksync + KW - 1);
+    const char* A = L::a_at(smem, stage);
+    if (TRACE && (p.ablate & 2)) {
+    } else {
 #pragma unroll
-        for (int i = 0; i < MH; ++i) {
-          f.a0[i] = *reinterpret_cast<const u32x4*>(A + (MH * wm + i) * 2048 + pa);
-          f.a1[i] = *reinterpret_cast<const u32x4*>(A + (MH * wm + i) * 2048 + (pa ^ 64));
-        }
-      } else {
-        const char* W = smem + KA * kABuf + (wave * kWStages + wstage) * 2048;
-        f.b0[0] = *reinterpret_cast<const u32x4*>(W + pa);
-        f.b1[0] = *reinterpret_cast<const u32x4*>(W + (pa ^ 64));
-#pragma unroll
-        for (int mt = 0; mt < MTC; ++mt) {
-          f.a0[mt] = *reinterpret_cast<const u32x4*>(A + mt * 2048 + pa);
-          f.a1[mt] = *reinterpret_cast<const u32x4*>(A + mt * 2048 + (pa ^ 64));
-        }
+      for (int j = 0; j < NB; ++j) {  // (n-tile NB wn + j was fetched by the weight wave that owns it)
+        const char* Wj = L::w_at(smem, NB * wn + j, wstage);
+        f.b0[j] = *reinterpret_cast<const u32x4*>(Wj + pa);
+        f.b1[j] = *reinterpret_cast<const u32x4*>(Wj + (pa ^ 64));
       }
-      stage = (stage == KA - 1) ? 0 : stage + 1;
-      wstage = (wstage == kWStages - 1) ? 0 : wstage + 1;
-      ++ksync;
-      __builtin_amdgcn_sched_barrier(0);  // the reads are ISSUED here, ahead of the MFMAs of the step before
-    };
-    auto mma = [&](const Frags& f) {
-      if (TRACE && (p.ablate & 3)) {
-      } else if constexpr (SM) {
 #pragma unroll
-        for (int i = 0; i < MH; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) acc[2 * i + j] = mfma8_k128<INT8>(f.a0[i], f.a1[i], f.b0[j], f.b1[j], acc[2 * i + j]);
-      } else {
-#pragma unroll
-        for (int mt = 0; mt < MTC; ++mt) acc[mt] = mfma8_k128<INT8>(f.a0[mt], f.a1[mt], f.b0[0], f.b1[0], acc[mt]);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    };
-    Frags f0, f1;
-    sync_issue_read(f0);
-    // (the explicit LDS waits on the paths WITHOUT new reads are for the compiler's wait-count pass: where paths merge it assumes the
-    // worst of them, and would put lgkmcnt waits for the NEW reads in front of every MFMA of the old fragments)
-    for (int k = 0; k < nk; k += 2) {
-      if (k + 1 < nk) sync_issue_read(f1); else __builtin_amdgcn_s_waitcnt(0xC07F);
-      mma(f0);
-      if (k + 1 < nk) {
-        if (k + 2 < nk) sync_issue_read(f0); else __builtin_amdgcn_s_waitcnt(0xC07F);
-        mma(f1);
+      for (int i = 0; i < NA; ++i) {
+        f.a0[i] = *reinterpret_cast<const u32x4*>(A + (NA * wm + i) * kTile + pa);
+        f.a1[i] = *reinterpret_cast<const u32x4*>(A + (NA * wm + i) * kTile + (pa ^ 64));
       }
     }
-    return;
-  }
-  for (int k = 0; k < nk; ++k) {
-    // (3 weight stages: w(k) is issued right behind a(k), so only a(k + 1) and w(k + 1) -- one stage -- may still be in flight)
-    // (QS == 4: at k % 4 == 2 the two scale requests of step k - 1 are younger than a(k) too)
-    if constexpr (QS == 4) { if ((k & 3) == 2) wait_vmcnt<LPSC + 2 + 2>(); else wait_vmcnt<LPSC + 2>(); }
-    else if constexpr (kWStages >= 4) wait_vmcnt<LPSC + 2 + (MX ? 1 : 0)>(); else wait_vmcnt<LPSC>();
-    // everyone's share of the activation tile has landed, and everyone has finished reading step k - 1
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    if (TRACE && k < 8) ts[2 + k] = __builtin_amdgcn_s_memtime();
-    if constexpr (QS == 4) {
-      if ((k & 3) == 1) issue_s(((k >> 2) + 1) & 1, (k & ~3) + 4);
+    stage = ring_next(stage, KA);
+    wstage = ring_next(wstage, KW);
+    ++ksync;
+    __builtin_amdgcn_sched_barrier(0);  // the reads are ISSUED here, ahead of the MFMAs of the step before
+  };
+  auto mma = [&](const Frags& f) {
+    if (TRACE && (p.ablate & 3)) {
+    } else {
+#pragma unroll
+      for (int i = 0; i < NA; ++i)
+#pragma unroll
+        for (int j = 0; j < NB; ++j) acc[NB * i + j] = mfma8_k128<INT8>(f.a0[i], f.a1[i], f.b0[j], f.b1[j], acc[NB * i + j]);  // (INT8: acc holds int32 bit patterns)
     }
-    issue_a((stage == 0) ? KA - 1 : stage - 1, k + KA - 1);
-    issue_w((wstage == 0) ? kWStages - 1 : wstage - 1, k + kWStages - 1);
-    const char* A = smem + stage * kABuf;
-    if constexpr (SM) {
-      // wave (wm, wn): n-tiles 2 wn + j (fetched by waves 2 wn + j), m-tiles 4 wm + i; acc[2 i + j]
-      const int wm = wave & 1, wn = wave >> 1;
-      u32x4 b0[2], b1[2];
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const char* Wj = smem + KA * kABuf + ((2 * wn + j) * kWStages + wstage) * 2048;
-        b0[j] = *reinterpret_cast<const u32x4*>(Wj + pa);
-        b1[j] = *reinterpret_cast<const u32x4*>(Wj + (pa ^ 64));
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const u32x4 a0 = *reinterpret_cast<const u32x4*>(A + (4 * wm + i) * 2048 + pa);
-        const u32x4 a1 = *reinterpret_cast<const u32x4*>(A + (4 * wm + i) * 2048 + (pa ^ 64));
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[2 * i + j] = mfma8_k128<INT8>(a0, a1, b0[j], b1[j], acc[2 * i + j]);
-      }
-      stage = (stage == KA - 1) ? 0 : stage + 1;
-      wstage = (wstage == kWStages - 1) ? 0 : wstage + 1;
-      continue;
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  Frags f0, f1;
+  sync_issue_read(f0);
+  // (the explicit LDS waits on the paths WITHOUT new reads are for the compiler's wait-count pass: where paths merge it assumes the
+  // worst of them, and would put lgkmcnt waits for the NEW reads in front of every MFMA of the old fragments)
+  for (int k = 0; k < nk; k += 2) {
+    if (k + 1 < nk) sync_issue_read(f1); else __builtin_amdgcn_s_waitcnt(0xC07F);
+    mma(f0);
+    if (k + 1 < nk) {
+      if (k + 2 < nk) sync_issue_read(f0); else __builtin_amdgcn_s_waitcnt(0xC07F);
+      mma(f1);
     }
-    const char* W = smem + KA * kABuf + (wave * kWStages + wstage) * 2048;
-    const u32x4 b0 = *reinterpret_cast<const u32x4*>(W + pa);  // the n-tile's 16 rows are laid out like an m-tile
-    const u32x4 b1 = *reinterpret_cast<const u32x4*>(W + (pa ^ 64));
-    // MX: the scale byte of lane group kq is that of 32-k block kq of the step (operand layout probed on gfx950, stream8_kernels.hip)
-    [[maybe_unused]] const char* AS = smem + KA * kABuf + WAVES * (kWStages * 2048) +
-                                      ((QS == 1) ? stage * WAVES * SCL : ((k >> 2) & 1) * WAVES * ASB + (k & 3) * 4);
-    int sb = 127;
-    if constexpr (MX && QS == 1)
-      sb = (int)(*reinterpret_cast<const uint32_t*>(smem + KA * kABuf + WAVES * (kWStages * 2048) + KA * WAVES * SCL +
-                                                    (wave * kWStages + wstage) * SCL + nl * 4) >> (8 * kq)) & 0xff;
-    if constexpr (MX && QS == 4)
-      sb = (int)(*reinterpret_cast<const uint32_t*>(smem + KA * kABuf + WAVES * (kWStages * 2048) + 2 * WAVES * ASB +
-                                                    (wave * 2 + ((k >> 2) & 1)) * BSB + nl * 16 + (k & 3) * 4) >> (8 * kq)) & 0xff;
-#pragma unroll
-    for (int mt = 0; mt < MTC; ++mt) {
-      const u32x4 a0 = *reinterpret_cast<const u32x4*>(A + mt * 2048 + pa);
-      const u32x4 a1 = *reinterpret_cast<const u32x4*>(A + mt * 2048 + (pa ^ 64));
-      int sa = 127;
-      if constexpr (MX) {  // row mt * 16 + nl sits in the region of wave row / RPW, slot row % RPW
-        const int row = mt * 16 + nl;
-        sa = (int)(*reinterpret_cast<const uint32_t*>(AS + (row / RPW) * ((QS == 1) ? SCL : ASB) + (row % RPW) * ((QS == 1) ? 4 : 16)) >> (8 * kq)) & 0xff;
-      }
-      acc[mt] = mfma8_k128<INT8>(a0, a1, b0, b1, acc[mt], sa, sb);  // (INT8: acc holds int32 bit patterns)
-    }
-    stage = (stage == KA - 1) ? 0 : stage + 1;
-    wstage = (wstage == kWStages - 1) ? 0 : wstage + 1;
   }
   };
-  if constexpr (GROUPED && MT >= 4) {
-    if (mt_have <= 1) k_loop(std::integral_constant<int, 1>{});
-    else if (mt_have <= 2) k_loop(std::integral_constant<int, 2>{});
-    else if (MT == 4 || mt_have <= 4) k_loop(std::integral_constant<int, 4>{});
-    else k_loop(std::integral_constant<int, MT>{});
-  } else {
-    k_loop(std::integral_constant<int, MT>{});
-  }
+  k_loop();
   wait_vmcnt<0>();  // the clamped fills past the end still write LDS
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 
@@ -446,146 +319,273 @@ __global__ __launch_bounds__(64 * WAVES) void rb8_kernel(Rb8Args p) {
       for (int i = 0; i < 16; ++i) t[i] = ts[i];
     }
   };
-  // more than four K parts (rowwise kinds): the two-level meeting of splitk.h (round 4) -- groups of four parts, so the last arriver
-  // reads 3 + 3 parked tiles in two round trips instead of S - 1 in S / 4 (the 70B / TP8 qkv shard at M = 128 cuts K 16 ways: 15 x 64 KiB
-  // through one CU's memory path)
-  bool go_on = true;
+  // The K parts meet through the fence-free split-K workspace; the last arriver goes on.  More than four parts: the two-level meeting of
+  // splitk.h (round 4) -- groups of four parts, so the last arriver reads 3 + 3 parked tiles in two round trips instead of S - 1 in S / 4
+  // (the 70B / TP8 qkv shard at M = 128 cuts K 16 ways: 15 x 64 KiB through one CU's memory path)
   if (S > 1) {
     const int otile = by * gx + bx;
     int* flag = reinterpret_cast<int*>(smem);
-    if constexpr (!GROUPED) {
-      go_on = (S > 4) ? split_k_meet2<MT, 64 * WAVES, INT8, 4>(acc, p.ws, p.tickets, otile, S, ks, tid, flag)
-                      : split_k_meet<MT, 64 * WAVES, INT8>(acc, p.ws, p.tickets, otile, S, ks, tid, flag);
-    } else {
-      go_on = split_k_meet<MT, 64 * WAVES, INT8>(acc, p.ws, p.tickets, otile, S, ks, tid, flag);
-    }
-  }
-  if (!go_on) {
-    dump();
-    return;
+    const bool last = (S > 4) ? split_k_meet2<MT, 64 * WAVES, INT8, 4>(acc, p.ws, p.tickets, otile, S, ks, tid, flag)
+                              : split_k_meet<MT, 64 * WAVES, INT8>(acc, p.ws, p.tickets, otile, S, ks, tid, flag);
+    if (!last) { dump(); return; }
   }
   if (TRACE) ts[11] = __builtin_amdgcn_s_memtime();
 
+  // Round 5: the scaled tile goes through the (now idle) LDS and leaves as 16-byte row pieces.  A direct form stores two bytes
+  // per lane and instruction -- 32 store instructions per wave, 256 per workgroup, each a pass through the CU's one address path
+  // (~5.7 k cycles of the round-4 trace) -- this one 4 per wave.  Row scales come in once per workgroup (one load per row, through LDS)
+  // instead of 16 - 32 loads per lane.  Same arithmetic, same bits.  (N % 16 == 0 on every route here: whole 16-byte pieces.)
+  float* sa_lds = reinterpret_cast<float*>(smem + L::epi_sa);
+  float* sb_lds = reinterpret_cast<float*>(smem + L::epi_sb);
+  float* bias_lds = reinterpret_cast<float*>(smem + L::epi_bias);
+  __syncthreads();  // (the meeting's flag word is dead; every wave is past the loop's last LDS read)
+  if (tid < BM) sa_lds[tid] = pre_sa;
+  asm volatile("" : "+v"(pre_bias));  // (opaque until here: the compiler otherwise converts -- and waits for the load -- at the kernel's head)
+  if (tid < BNW) { sb_lds[tid] = pre_sb; bias_lds[tid] = bf16_lo_to_f32(pre_bias); }
+  __syncthreads();
   // D layout: lane (col = nl, kq) holds rows 4 kq + {0..3} of each 16 x 16 tile
-  if constexpr (!GROUPED) {
-    // Round 5: the scaled tile goes through the (now idle) LDS and leaves as 16-byte row pieces.  The direct form below stores two bytes
-    // per lane and instruction -- 32 store instructions per wave, 256 per workgroup, each a pass through the CU's one address path
-    // (~5.7 k cycles of the round-4 trace) -- this one 4 per wave.  Row scales come in once per workgroup (one load per row, through LDS)
-    // instead of 16 - 32 loads per lane.  Same arithmetic, same bits.
-    if (p.N % 8 == 0) {
-      constexpr int BNW = 16 * WAVES;            // columns of the workgroup's tile
-      constexpr int RS = BNW * 2 + 16;           // staging row stride in bytes (+ 16: the 4 kq row groups of a b16 write land 8 banks apart)
-      float* sa_lds = reinterpret_cast<float*>(smem + BM * RS);
-      float* sb_lds = sa_lds + BM;
-      float* bias_lds = sb_lds + BNW;
-      __syncthreads();  // (the meeting's flag word is dead; every wave is past the loop's last LDS read)
-      if (tid < BM) sa_lds[tid] = pre_sa;
-      asm volatile("" : "+v"(pre_bias));  // (opaque until here: the compiler otherwise converts -- and waits for the load -- at the kernel's head)
-      if (tid < BNW) { sb_lds[tid] = pre_sb; bias_lds[tid] = bf16_lo_to_f32(pre_bias); }
-      __syncthreads();
-      auto put = [&](int mt, int ntl, const f32x4& c) {  // m-tile mt of the slab, n-tile ntl of the workgroup's tile
-        const float sbv = sb_lds[ntl * 16 + nl];
-        const float bv = bias_lds[ntl * 16 + nl];
-        const f32x4 sa4 = *reinterpret_cast<const f32x4*>(sa_lds + mt * 16 + kq * 4);
+  auto put = [&](int mt, int ntl, const f32x4& c) {  // m-tile mt of the slab, n-tile ntl of the workgroup's tile
+    const float sbv = sb_lds[ntl * 16 + nl];
+    const float bv = bias_lds[ntl * 16 + nl];
+    const f32x4 sa4 = *reinterpret_cast<const f32x4*>(sa_lds + mt * 16 + kq * 4);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float v = epilogue8<INT8>(INT8 ? (float)__builtin_bit_cast(i32x4, c)[r] : c[r], sa4[r], sbv, p.bias != nullptr, bv);
-          *reinterpret_cast<uint16_t*>(smem + (mt * 16 + kq * 4 + r) * RS + (ntl * 16 + nl) * 2) = f32_to_bf16_bits(v);
-        }
-      };
-      if constexpr (SM) {
-        const int wm = wave & 1, wn = wave >> 1;
-#pragma unroll
-        for (int i = 0; i < MH; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) put(MH * wm + i, 2 * wn + j, acc[2 * i + j]);
-      } else {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) put(mt, wave, acc[mt]);
-      }
-      __syncthreads();
-      constexpr int PPR = BNW / 8;  // 16-byte pieces per row
-      uint16_t* __restrict__ yo = p.y;
-#pragma unroll
-      for (int it = 0; it < (BM * PPR) / (64 * WAVES); ++it) {
-        const int c = it * (64 * WAVES) + tid;
-        const int row = c / PPR, piece = c - row * PPR;
-        const int m = m0 + row, n = bx * BNW + piece * 8;
-        if (m < m_end && n + 8 <= p.N)
-          *reinterpret_cast<u32x4*>(yo + (size_t)m * p.N + n) = *reinterpret_cast<const u32x4*>(smem + row * RS + piece * 16);
-      }
-      dump();
-      return;
+    for (int r = 0; r < 4; ++r) {
+      const float v = epilogue8<INT8>(INT8 ? (float)__builtin_bit_cast(i32x4, c)[r] : c[r], sa4[r], sbv, p.bias != nullptr, bv);
+      *reinterpret_cast<uint16_t*>(smem + (mt * 16 + kq * 4 + r) * RS + (ntl * 16 + nl) * 2) = f32_to_bf16_bits(v);
     }
-  }
-  if constexpr (SM) {
-    const int wm = wave & 1, wn = wave >> 1;
-    uint16_t* __restrict__ y = p.y;
-    float sbj[2], biasj[2];
-    int nj[2];
+  };
+  const int wm = (int)((unsigned)wave % MG), wn = (int)((unsigned)wave / MG);
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int tj = bx * WAVES + 2 * wn + j;
-      nj[j] = (tj < ntiles) ? tj * 16 + nl : -1;
-      sbj[j] = p.scale_b[min(tj, ntiles - 1) * 16 + nl];
-      biasj[j] = p.bias != nullptr ? bf16_lo_to_f32(p.bias[min(tj, ntiles - 1) * 16 + nl]) : 0.f;
-    }
-    float sa[16];  // all row scales first: the stores below must not sit between dependent loads
+  for (int i = 0; i < NA; ++i)
 #pragma unroll
-    for (int i = 0; i < 16; ++i) sa[i] = p.scale_a[min(m0 + (4 * wm + (i >> 2)) * 16 + kq * 4 + (i & 3), p.M - 1)];
+    for (int j = 0; j < NB; ++j) put(NA * wm + i, NB * wn + j, acc[NB * i + j]);
+  __syncthreads();
+  constexpr int PPR = BNW / 8;  // 16-byte pieces per row
+  uint16_t* __restrict__ yo = p.y;
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int m = m0 + (4 * wm + i) * 16 + kq * 4 + r;
-          if (m < m_end && nj[j] >= 0) {
-            const float c = INT8 ? (float)__builtin_bit_cast(i32x4, acc[2 * i + j])[r] : acc[2 * i + j][r];
-            const float v = epilogue8<INT8>(c, sa[i * 4 + r], sbj[j], p.bias != nullptr, biasj[j]);
-            y[(size_t)m * p.N + nj[j]] = f32_to_bf16_bits(v);
-          }
-        }
-    dump();
-    return;
-  }
-  if (tile >= ntiles) { dump(); return; }
-  const int n = tile * 16 + nl;
-  uint16_t* __restrict__ y = p.y;
-  if constexpr (MX) {  // scales were applied by the MFMA: out = bf16(acc)
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = m0 + mt * 16 + kq * 4 + r;
-        if (m < m_end) y[(size_t)m * p.N + n] = f32_to_bf16_bits(acc[mt][r]);
-      }
-  } else {
-    const float* __restrict__ scale_a = p.scale_a;
-    const float sb = p.scale_b[(size_t)expert * p.N + n];
-    const float bias = p.bias != nullptr ? bf16_lo_to_f32(p.bias[n]) : 0.f;
-    float sa[4 * MT];  // all row scales first: the stores below must not sit between dependent loads
-#pragma unroll
-    for (int i = 0; i < 4 * MT; ++i) sa[i] = scale_a[min(m0 + (i >> 2) * 16 + kq * 4 + (i & 3), p.M - 1)];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = m0 + mt * 16 + kq * 4 + r;
-        if (m < m_end) {  // (= p.M for the ungrouped kinds)
-          const float c = INT8 ? (float)__builtin_bit_cast(i32x4, acc[mt])[r] : acc[mt][r];
-          const float v = epilogue8<INT8>(c, sa[mt * 4 + r], sb, p.bias != nullptr, bias);
-          y[(size_t)m * p.N + n] = f32_to_bf16_bits(v);
-        }
-      }
+  for (int it = 0; it < (BM * PPR) / (64 * WAVES); ++it) {
+    const int c = it * (64 * WAVES) + tid;
+    const int row = c / PPR, piece = c - row * PPR;
+    const int m = m0 + row, n = bx * BNW + piece * 8;
+    if (m < m_end && n + 8 <= p.N)
+      *reinterpret_cast<u32x4*>(yo + (size_t)m * p.N + n) = *reinterpret_cast<const u32x4*>(smem + row * RS + piece * 16);
   }
   dump();
+}
+
+// The grouped kinds: rows grouped by expert, every (non-empty slab, column tile) its own workgroup, K never cut (grouped8_route).
+// SLIM (MX, 64-row slabs of 4 waves): 64-byte scale slots and a 3-stage weight ring -- three workgroups per CU.
+// QS (MX): k steps per scale fetch -- 1: a dword DMA per row, step and operand; 4: one 16-byte DMA per row and FOUR steps, two slots
+// per wave and operand (K % 512 == 0).  The dword DMAs cost a quarter of the decode kernel (mx_stream_kernel below).
+template <int WAVES, int KIND, int MT = 8, bool TRACE = false, bool SLIM = false, int QS = 1>
+__global__ __launch_bounds__(64 * WAVES) void rb8_grouped_kernel(Rb8Args p) {
+  static_assert((KIND == RB8_MX || KIND == RB8_FP8_GROUPED) && (MT == 4 || MT == 8), "rb8_grouped_kernel: the grouped kinds, 64- or 128-row slabs");
+  static_assert(QS == 1 || (QS == 4 && KIND == RB8_MX && !SLIM), "rb8_kernel: 4-step scale fetches are an MX form");
+  using L = Rb8GroupedLds<WAVES, KIND, MT, SLIM, QS>;
+  constexpr bool MX = (KIND == RB8_MX);
+  constexpr int KA = L::KA, KW = L::KW, BM = 16 * MT, RPW = L::RPW;
+  static_assert(!SLIM || (MX && RPW == 16), "SLIM: 16 activation-scale rows per wave");
+  unsigned long long ts[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  if (TRACE) ts[0] = __builtin_amdgcn_s_memtime();
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int nl = lane & 15, kq = lane >> 4;
+  const int ntiles = p.N >> 4;
+  const int bx = blockIdx.x, by = blockIdx.y;  // the workgroup's column tile and its slab's number
+  const int tile = bx * WAVES + wave;
+  const int tile_c = min(tile, ntiles - 1);  // tiles past N alias the last one; never stored
+  const int nk = p.K >> 7;
+  // rows of this workgroup: [m0, m_end) -- a slab of one expert's token group.  blockIdx.y
+  // enumerates the NON-EMPTY slabs in (expert, slab) order -- the y-th one is found from the group ends on the device, so the
+  // grid needs ceil(M / BM) + E rows at most (not E x the slabs of the largest possible group) and an expert without tokens
+  // costs nothing.
+  int m0 = by * BM, m_end = p.M, expert = 0;
+  if (p.offs != nullptr) {
+    int y = by, found = -1, begin = 0, end = 0;
+    for (int e0 = 0; e0 < p.E && found < 0; e0 += 64) {  // 64 experts per pass: lane e owns expert e0 + e
+      const int e = e0 + lane;
+      const int lo = (e > 0 && e < p.E) ? p.offs[e - 1] : 0;
+      const int hi = (e < p.E) ? p.offs[e] : lo;
+      const int ns = (hi - lo + BM - 1) / BM;  // slabs of this expert (0 when it has no tokens)
+      int incl = ns;
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const int t = __shfl_up(incl, d);
+        if (lane >= d) incl += t;
+      }
+      const unsigned long long hit = __ballot(incl > y);
+      if (hit != 0ull) {
+        const int l = __builtin_ctzll(hit);
+        found = e0 + l;
+        begin = __builtin_amdgcn_readlane(lo, l);
+        end = __builtin_amdgcn_readlane(hi, l);
+        y -= __builtin_amdgcn_readlane(incl - ns, l);
+      } else {
+        y -= __builtin_amdgcn_readlane(incl, 63);
+      }
+    }
+    if (found < 0) return;  // uniform: past the last non-empty slab (before any DMA or barrier)
+    expert = found;
+    m0 = begin + y * BM;
+    m_end = end;
+  } else if (m0 >= m_end) { return; }
+  // m-tiles this slab really has, rounded up to a power of two: the k loop below is specialised on it, so a 32-row group in a
+  // 64- or 128-row slab reads and multiplies 32 rows (the DMA counts stay static for the hand-counted waits; rows past the
+  // group re-read its last row)
+  const int mt_have = (min(m_end - m0, BM) + 15) >> 4;
+  if (TRACE) ts[13] = __builtin_amdgcn_s_memtime();
+
+  uint32_t boff[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) boff[i] = weight_line_offset(i, lane, p.K);
+  const uint8_t* brows = p.b + ((size_t)expert * p.N + (size_t)tile_c * 16) * p.K;
+  const uint32_t a_lds = lds_offset(smem);
+  const uint32_t w_lds = L::w_at(a_lds, wave, 0);
+  // MX block scales: one dword (4 e8m0 bytes = the 4 blocks of a 128-k step) per row and step.  Wave w fetches the dwords of
+  // activation rows RPW w .. + RPW - 1 (lanes past RPW repeat them into slots nobody reads) and of its own 16 weight rows.
+  const uint32_t kb32 = (uint32_t)(p.K >> 5);
+  const uint32_t asoff = MX ? (uint32_t)min(m0 + RPW * wave + (lane % RPW), m_end - 1) * kb32 : 0u;
+  const uint32_t bsoff = (uint32_t)nl * kb32;
+  const uint8_t* bsrows = MX ? p.b_mx + ((size_t)expert * p.N + (size_t)tile_c * 16) * kb32 : nullptr;
+  const uint32_t bs_lds = L::bs_at(a_lds, wave, 0);
+  auto issue_s = [&](int slot, int k) {  // QS == 4: the scales of steps k .. k + 3 (k % 4 == 0); past the end: the last block again
+    const int kk = min(k, nk - 4);
+    if (lane < RPW) dma_b128_s(p.a_mx + (size_t)kk * 4, asoff, L::as_at(a_lds, slot, wave));
+    if (lane < 16) dma_b128_s(bsrows + (size_t)kk * 4, bsoff, bs_lds + slot * L::BSB);
+  };
+  auto issue_w = [&](int stage, int k) {
+    const int kk = fill_step(0, k, nk);
+    dma_b128_nt_s(brows + (size_t)kk * 128, boff[0], w_lds + stage * kTile);
+    dma_b128_nt_s(brows + (size_t)kk * 128, boff[1], w_lds + stage * kTile + kTile / 2);
+    if constexpr (MX && QS == 1) {
+      if (!SLIM || lane < 16) dma_b32_s(bsrows + (size_t)kk * 4, bsoff, bs_lds + stage * L::BSB);
+    }
+  };
+
+  f32x4 acc[MT];
+#pragma unroll
+  for (int i = 0; i < MT; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int pa = frag_pos(nl, kq);
+
+  // Issue order (6 stages) is w(0..2) | a(0) w(3) | a(1) w(4), then per step a(k+2) w(k+5): when step k starts, the youngest requests
+  // are a(k+1), w(k+4) (one stage: LPSC) and w(k+3) (2 DMAs, 3 with MX scales); everything older -- a(k), w(k) .. w(k+2) -- has landed.
+  // Activations are fetched 2 steps ahead (L2 hits), weights KW - 1 steps ahead (with 2 the loop ran at 0.9 us per step: too few HBM
+  // bytes in flight); one hand-counted s_waitcnt vmcnt + one LDS-only barrier per step.
+  auto k_loop = [&](auto mtc) {
+  constexpr int MTC = decltype(mtc)::value;
+  // activation DMAs per wave and stage for the m-tiles this slab really has (8 rows each; with fewer 8-row blocks than waves
+  // the last waves re-fetch the group's last row into rows nobody reads): a 32-row group in a 64-row slab costs the workgroup
+  // 4 activation DMAs per step, not 8 -- the activation tile is half of what a CU's texture path moves per step
+  constexpr int AD = (2 * MTC >= WAVES) ? 2 * MTC / WAVES : 1;
+  constexpr int LPSC = AD + 2 + ((MX && QS == 1) ? 2 : 0);
+  uint32_t aoff[AD];
+#pragma unroll
+  for (int i = 0; i < AD; ++i) {
+    const int row = 8 * (AD * wave + i) + (lane >> 3);
+    aoff[i] = dma_row_offset(min(m0 + min(row, BM - 1), m_end - 1), row, lane, p.K);
+  }
+  auto issue_a = [&](int stage, int k) {
+    const int kk = fill_step(0, k, nk);
+    if (TRACE && (p.ablate & 8)) return;
+#pragma unroll
+    for (int i = 0; i < AD; ++i) dma_b128_s(p.a + (size_t)kk * 128, aoff[i], L::a_at(a_lds, stage) + (AD * wave + i) * (kTile / 2));
+    if constexpr (MX && QS == 1) {
+      if (!SLIM || lane < 16) dma_b32_s(p.a_mx + (size_t)kk * 4, asoff, L::as_at(a_lds, stage, wave));
+    }
+  };
+  if (TRACE) ts[14] = __builtin_amdgcn_s_memtime();
+  if constexpr (QS == 4) issue_s(0, 0);  // then the block of steps 4 j + 4 .. at the head of step 4 j + 1 (older than a(4 j + 3): landed by then)
+#pragma unroll
+  for (int i = 0; i < KW - 3; ++i) issue_w(i, i);
+  issue_a(0, 0); issue_w(KW - 3, KW - 3);
+  issue_a(1, 1); issue_w(KW - 2, KW - 2);
+  if (TRACE) ts[1] = __builtin_amdgcn_s_memtime();
+  int stage = 0, wstage = 0;
+  for (int k = 0; k < nk; ++k) {
+    // (3 weight stages: w(k) is issued right behind a(k), so only a(k + 1) and w(k + 1) -- one stage -- may still be in flight)
+    // (QS == 4: at k % 4 == 2 the two scale requests of step k - 1 are younger than a(k) too)
+    if constexpr (QS == 4) { if ((k & 3) == 2) wait_vmcnt<LPSC + 2 + 2>(); else wait_vmcnt<LPSC + 2>(); }
+    else if constexpr (KW >= 4) wait_vmcnt<LPSC + 2 + (MX ? 1 : 0)>(); else wait_vmcnt<LPSC>();
+    // everyone's share of the activation tile has landed, and everyone has finished reading step k - 1
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    if (TRACE && k < 8) ts[2 + k] = __builtin_amdgcn_s_memtime();
+    if constexpr (QS == 4) {
+      if ((k & 3) == 1) issue_s(((k >> 2) + 1) & 1, (k & ~3) + 4);
+    }
+    issue_a(ring_prev(stage, KA), k + KA - 1);
+    issue_w(ring_prev(wstage, KW), k + KW - 1);
+    const char* A = L::a_at(smem, stage);
+    const char* W = L::w_at(smem, wave, wstage);
+    const u32x4 b0 = *reinterpret_cast<const u32x4*>(W + pa);
+    const u32x4 b1 = *reinterpret_cast<const u32x4*>(W + (pa ^ 64));
+    // MX: this step's scale dwords -- QS == 1: the slot of the step's ring stage; QS == 4: slot (k / 4) % 2, dword k % 4 of a row's 16 bytes
+    [[maybe_unused]] const char* AS = L::as_bytes(smem, (QS == 1) ? stage * L::as_slot : ((k >> 2) & 1) * L::as_slot + (k & 3) * 4);
+    int sb = 127;
+    if constexpr (MX && QS == 1) sb = scale_byte(L::bs_at(smem, wave, wstage) + nl * 4, kq);
+    if constexpr (MX && QS == 4) sb = scale_byte(L::bs_at(smem, wave, (k >> 2) & 1) + nl * 16 + (k & 3) * 4, kq);
+#pragma unroll
+    for (int mt = 0; mt < MTC; ++mt) {
+      const u32x4 a0 = *reinterpret_cast<const u32x4*>(A + mt * kTile + pa);
+      const u32x4 a1 = *reinterpret_cast<const u32x4*>(A + mt * kTile + (pa ^ 64));
+      int sa = 127;
+      if constexpr (MX) {  // row mt * 16 + nl sits in the region of wave row / RPW, slot row % RPW
+        const int row = mt * 16 + nl;
+        sa = scale_byte(AS + (row / RPW) * L::ASB + (row % RPW) * ((QS == 1) ? 4 : 16), kq);
+      }
+      acc[mt] = mfma8_k128<false>(a0, a1, b0, b1, acc[mt], sa, sb);
+    }
+    stage = ring_next(stage, KA);
+    wstage = ring_next(wstage, KW);
+  }
+  };
+  if (mt_have <= 1) k_loop(std::integral_constant<int, 1>{});
+  else if (mt_have <= 2) k_loop(std::integral_constant<int, 2>{});
+  else if (MT == 4 || mt_have <= 4) k_loop(std::integral_constant<int, 4>{});
+  else k_loop(std::integral_constant<int, MT>{});
+  wait_vmcnt<0>();  // the clamped fills past the end still write LDS
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+
+  if (TRACE) ts[10] = ts[11] = __builtin_amdgcn_s_memtime();  // (no K parts: no meeting)
+  if (tile < ntiles) {
+    // direct stores of the D layout (lane (col = nl, kq): rows 4 kq + {0..3} of each 16 x 16 tile) -- MX: scales were applied by the MFMA, out = bf16(acc); RB8_FP8_GROUPED: bf16(acc * scale_a[m] * scale_b[expert][n])
+    const int n = tile * 16 + nl;
+    uint16_t* __restrict__ y = p.y;
+    [[maybe_unused]] float sb = 0.f, bias = 0.f, sa[4 * MT];
+    if constexpr (!MX) {
+      const float* __restrict__ scale_a = p.scale_a;
+      sb = p.scale_b[(size_t)expert * p.N + n];
+      bias = p.bias != nullptr ? bf16_lo_to_f32(p.bias[n]) : 0.f;
+#pragma unroll
+      for (int i = 0; i < 4 * MT; ++i) sa[i] = scale_a[min(m0 + (i >> 2) * 16 + kq * 4 + (i & 3), p.M - 1)];  // all row scales first: the stores below must not sit between dependent loads
+    }
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+      f32x4 v = acc[mt];
+      if constexpr (!MX) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = epilogue8<false>(acc[mt][r], sa[mt * 4 + r], sb, p.bias != nullptr, bias);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int m = m0 + mt * 16 + kq * 4 + r;
+        if (m < m_end) y[(size_t)m * p.N + n] = f32_to_bf16_bits(v[r]);
+      }
+    }
+  }
+  if (TRACE && p.trace != nullptr && tid == 0) {
+    ts[12] = __builtin_amdgcn_s_memtime();
+    unsigned long long* t = p.trace + ((size_t)by * gridDim.x + bx) * 16;
+    for (int i = 0; i < 16; ++i) t[i] = ts[i];
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Stream-K form of the MX decode kernel (round 3; 4 waves, 64-row slabs, 64-column tiles).
 //
-// rb8_kernel above gives every (non-empty slab, 64-column tile) its own workgroup.  At decode sizes a workgroup then lives
+// rb8_grouped_kernel above gives every (non-empty slab, 64-column tile) its own workgroup.  At decode sizes a workgroup then lives
 // for only 32 - 112 k steps, of which (s_memtime traces, profiles/mx_rb_trace_r03.txt) 3 300 - 5 600 cycles go to finding its
 // group, 1 000 - 6 000 to priming the rings, 600 - 1 300 to the first data and ~2 000 to the epilogue; and the grid is whatever the
 // router made it -- 672 workgroups on 512 slots (w1 with three experts hit), 192 on 256 CUs (w2).  In the k loop itself a CU
@@ -711,10 +711,7 @@ __global__ __launch_bounds__(64 * WAVES) void mx_stream_kernel(Rb8Args p) {
   // ---- weight cursor
   uint32_t boff[2];
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int row = 8 * i + (lane >> 3);
-    boff[i] = (uint32_t)row * (uint32_t)p.K + ((((lane & 7) ^ (row >> 1)) & 7) << 4);
-  }
+  for (int i = 0; i < 2; ++i) boff[i] = weight_line_offset(i, lane, p.K);
   const uint32_t bsoff = (uint32_t)nl * kb32;
   const uint8_t* brows = nullptr;
   const uint8_t* bsrows = nullptr;
@@ -752,7 +749,7 @@ __global__ __launch_bounds__(64 * WAVES) void mx_stream_kernel(Rb8Args p) {
 #pragma unroll
     for (int i = 0; i < AD; ++i) {
       const int row = 8 * (AD * wave + i) + (lane >> 3);  // rows past the group re-read its last row (one line, never used)
-      aoff[i] = (uint32_t)min(m0 + row, m_end - 1) * (uint32_t)p.K + ((((lane & 7) ^ (row >> 1)) & 7) << 4);
+      aoff[i] = dma_row_offset(min(m0 + row, m_end - 1), row, lane, p.K);
     }
     asoff = (uint32_t)min(m0 + RPW * wave + (lane % RPW), m_end - 1) * kb32;
     if constexpr (QS == 4) a_cnt = __builtin_amdgcn_readfirstlane(max(0, min(AD, (min(m_end - m0, BM) - 8 * AD * wave + 7) >> 3)));
@@ -875,7 +872,7 @@ __global__ __launch_bounds__(64 * WAVES) void mx_stream_kernel(Rb8Args p) {
   const bool tail_is_piece = !(tile_last * ksteps >= g0 && (tile_last + 1) * ksteps == g1);
   const int g_peek = (tail_is_piece && g1 - g0 >= 3 && !(p.ablate & 2)) ? g1 - 2 : -1;
   const __amdgpu_buffer_rsrc_t rtk = __builtin_amdgcn_make_buffer_rsrc(p.tickets, 0, 0x7fffffff, 0x00020000);
-  const int pa = nl * 128 + (((kq ^ (nl >> 1)) & 7) << 4);
+  const int pa = frag_pos(nl, kq);
 
   // Issue order (SW >= 4): w(0 .. SW-4) | a(0) w(SW-3) | a(1) w(SW-2), then per step a(i+2) w(i+SW-1): when step i starts the youngest
   // requests are a(i+1), w(i+SW-2) (one stage: LPSC) and w(i+SW-3) (3 DMAs); everything older has landed.  SW == 3: a(0) w(0) |
@@ -931,7 +928,7 @@ __global__ __launch_bounds__(64 * WAVES) void mx_stream_kernel(Rb8Args p) {
     }
     [[maybe_unused]] const int a_landed = a_prev;  // CAST: whether this wave fetched rows of step i + 1's tile (requested a step ago)
     a_prev = issue_a(kCast ? stage : (stage == 0) ? 2 : stage - 1);  // (CAST: raw(i + 2) into the raw stage cast a step ago)
-    issue_w((wstage == 0) ? SW - 1 : wstage - 1);
+    issue_w(ring_prev(wstage, SW));
     if constexpr (kCast) {
       if (a_landed) convert(stage ^ 1, stage ^ 1);
     }
@@ -963,7 +960,7 @@ __global__ __launch_bounds__(64 * WAVES) void mx_stream_kernel(Rb8Args p) {
     const int blk = ((g - gv) >> 2) & 1, ph = (g - gv) & 3;  // QS == 4: slot and position of this step's scale dword
     const char* AS = smem + kWOff + WAVES * (SW * 2048) + (kCast ? stage * 256 : ((QS == 1) ? stage : blk) * WAVES * ASB + ((QS == 1) ? 0 : ph * 4));
     const char* BS = smem + kWOff + WAVES * (SW * 2048) + ASN * WAVES * ASB + (wave * BSN + ((QS == 1) ? wstage : blk)) * BSB;
-    const int sb = (int)(*reinterpret_cast<const uint32_t*>(BS + ((QS == 1) ? nl * 4 : nl * 16 + ph * 4)) >> (8 * kq)) & 0xff;
+    const int sb = scale_byte(BS + ((QS == 1) ? nl * 4 : nl * 16 + ph * 4), kq);
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
       if (mt < mt_have) {  // uniform: a 32-row group reads and multiplies two m-tiles
@@ -971,12 +968,12 @@ __global__ __launch_bounds__(64 * WAVES) void mx_stream_kernel(Rb8Args p) {
         const u32x4 a1 = *reinterpret_cast<const u32x4*>(A + mt * 2048 + (pa ^ 64));
         const i32x8 af = pack_k128(a0, a1);
         const int row = mt * 16 + nl;  // its scales sit in the slot of wave row / RPW (CAST: [row][4 B])
-        const int sa = (int)(*reinterpret_cast<const uint32_t*>(AS + (kCast ? row * 4 : (row / RPW) * ASB + (row % RPW) * ((QS == 1) ? 4 : 16))) >> (8 * kq)) & 0xff;
+        const int sa = scale_byte(AS + (kCast ? row * 4 : (row / RPW) * ASB + (row % RPW) * ((QS == 1) ? 4 : 16)), kq);
         acc[mt] = mfma8_k128_packed(af, bf, acc[mt], sa, sb);
       }
     }
-    stage = (stage == KA - 1) ? 0 : stage + 1;
-    wstage = (wstage == SW - 1) ? 0 : wstage + 1;
+    stage = ring_next(stage, KA);
+    wstage = ring_next(wstage, SW);
     ++kc;
     if (kc == ksteps && g + 1 < g1) {  // a tile ends inside the share
       if (kb == 0) {
@@ -1090,43 +1087,45 @@ __global__ __launch_bounds__(64 * WAVES) void mx_stream_kernel(Rb8Args p) {
 
 thread_local unsigned long long* g_fp8_rb_trace = nullptr;  // profiling only (ao_int4_set_trace shares the pointer)
 
-template <int WAVES, int KIND, int MT = 8, bool SLIM = false, int QS = 1>
-int launch_rb8(Rb8Args p, int split, hipStream_t stream) {
-  constexpr int BN = WAVES * 16;
-  constexpr int BM = 16 * MT;
-  constexpr bool kGrouped = (KIND == RB8_MX || KIND == RB8_FP8_GROUPED);
-  // grouped: at most ceil(M / BM) + E non-empty slabs exist whatever the group sizes are (and no more than E x slabs-per-group)
-  const unsigned gy = !kGrouped ? (unsigned)((p.M + BM - 1) / BM)
-                      : (p.offs == nullptr) ? (unsigned)p.slabs
-                                            : (unsigned)std::min<int64_t>((int64_t)p.slabs * p.E, (p.M + BM - 1) / BM + p.E);
-  dim3 grid((unsigned)((p.N + BN - 1) / BN), gy, (unsigned)split), block(64 * WAVES);
-  constexpr int kWStages = w_stages(WAVES, KIND, MT, SLIM);
-  constexpr int KA = a_stages(WAVES, KIND, MT);
-  constexpr size_t smem = (size_t)KA * MT * 2048 + (size_t)WAVES * kWStages * 2048 +
-                          ((KIND != RB8_MX) ? 0 : (QS == 4) ? (size_t)2 * 16 * MT * 16 + (size_t)WAVES * 2 * 256
-                                                            : (size_t)(KA + kWStages) * WAVES * (SLIM ? 64 : 256));
-  static_assert(!SLIM || 3 * smem <= 160 * 1024, "SLIM: three workgroups per CU");
-  static_assert(smem <= 160 * 1024, "rb8_kernel: LDS");
+// the launch both kinds of kernel end in (profiling: the stamp buffer and the timing probes of tuning key 5)
+template <class Kern>
+int launch_rb8_kernel(Kern traced, Kern plain, dim3 grid, int waves, size_t smem, Rb8Args p, hipStream_t stream) {
+  p.trace = g_fp8_rb_trace;
+  p.ablate = gemm8_force().rb8_ablate;
+  Kern kern = (p.trace != nullptr) ? traced : plain;
+  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), smem, "hipFuncSetAttribute(rb8_kernel)")) return rc;
+  ao::launch(kern, grid, dim3(64 * waves), smem, stream, p);
+  AO_LAUNCH_CHECK("rb8_kernel launch");
+  return AO_OK;
+}
+
+template <int WAVES, bool INT8, int MT>
+int launch_rb8_rowwise(Rb8Args p, int split, hipStream_t stream) {
+  constexpr int BN = WAVES * 16, BM = 16 * MT;
+  dim3 grid((unsigned)((p.N + BN - 1) / BN), (unsigned)((p.M + BM - 1) / BM), (unsigned)split);
+  constexpr size_t smem = Rb8RowwiseLds<WAVES, MT>::total;
   if (split > 1) {
-    // (two-level meeting for > 4 parts of the rowwise kinds: S + ceil(S / 4) parked tiles and 1 + ceil(S / 4) tickets per output tile)
-    const bool two_level = !kGrouped && split > 4;
-    const int64_t slots = two_level ? split + (split + 3) / 4 : split, tks = two_level ? 1 + (split + 3) / 4 : 1;
+    // (two-level meeting for > 4 parts: S + ceil(S / 4) parked tiles and 1 + ceil(S / 4) tickets per output tile)
+    const int64_t slots = split > 4 ? split + (split + 3) / 4 : split, tks = split > 4 ? 1 + (split + 3) / 4 : 1;
     AO_REQUIRE((int64_t)grid.x * grid.y * slots * BN * BM <= (int64_t)kSplitMaxTiles * 128 * 128, "rb8: %u x %u tiles x %d parts exceed the split-K workspace",
                grid.x, grid.y, split);
     AO_REQUIRE((int64_t)grid.x * grid.y * tks <= kSplitMaxTickets - 8, "rb8: %u x %u output tiles exceed the split-K tickets", grid.x, grid.y);
     if (int rc = splitk_workspace(stream, &p.ws, &p.tickets, (size_t)grid.x * grid.y * slots * BN * BM, split)) return rc;
   }
-  p.trace = g_fp8_rb_trace;
-  p.ablate = gemm8_force().rb8_ablate;
-  auto kern = (p.trace != nullptr) ? rb8_kernel<WAVES, KIND, MT, true, SLIM, QS> : rb8_kernel<WAVES, KIND, MT, false, SLIM, QS>;
-  if constexpr (WAVES == 8 && MT == 8 && (KIND == RB8_FP8 || KIND == RB8_INT8) && !SLIM && QS == 1) {
+  if constexpr (WAVES == 8 && MT == 8) {
     // the 2 x 4 wave arrangement (fewer operand fragments per MFMA); ao_gemm8_set_variant(103): the 1 x 8 form, for A/B
-    if (!gemm8_force().rb8_1x8) kern = (p.trace != nullptr) ? rb8_kernel<WAVES, KIND, MT, true, SLIM, QS, true> : rb8_kernel<WAVES, KIND, MT, false, SLIM, QS, true>;
+    if (!gemm8_force().rb8_1x8) return launch_rb8_kernel(rb8_rowwise_kernel<WAVES, INT8, MT, true, true>, rb8_rowwise_kernel<WAVES, INT8, MT, false, true>, grid, WAVES, smem, p, stream);
   }
-  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), smem, "hipFuncSetAttribute(rb8_kernel)")) return rc;
-  ao::launch(kern, grid, block, smem, stream, p);
-  AO_LAUNCH_CHECK("rb8_kernel launch");
-  return AO_OK;
+  return launch_rb8_kernel(rb8_rowwise_kernel<WAVES, INT8, MT, true>, rb8_rowwise_kernel<WAVES, INT8, MT, false>, grid, WAVES, smem, p, stream);
+}
+
+template <int WAVES, int KIND, int MT = 8, bool SLIM = false, int QS = 1>
+int launch_rb8_grouped(Rb8Args p, hipStream_t stream) {
+  constexpr int BN = WAVES * 16, BM = 16 * MT;
+  // at most ceil(M / BM) + E non-empty slabs exist whatever the group sizes are (and no more than E x slabs-per-group)
+  const unsigned gy = (p.offs == nullptr) ? (unsigned)p.slabs : (unsigned)std::min<int64_t>((int64_t)p.slabs * p.E, (p.M + BM - 1) / BM + p.E);
+  return launch_rb8_kernel(rb8_grouped_kernel<WAVES, KIND, MT, true, SLIM, QS>, rb8_grouped_kernel<WAVES, KIND, MT, false, SLIM, QS>,
+                           dim3((unsigned)((p.N + BN - 1) / BN), gy), WAVES, Rb8GroupedLds<WAVES, KIND, MT, SLIM, QS>::total, p, stream);
 }
 
 // Launch of the stream-K form: one workgroup per resident slot of the chip.
@@ -1257,15 +1256,15 @@ void rb8_launch_plan(int64_t M, int64_t N, int64_t K, const Gemm8Force& f, int* 
 
 namespace {
 
-template <int KIND>
+template <bool INT8>
 int rb8_run(const uint8_t* a, const uint8_t* b, const float* scale_a, const float* scale_b, const uint16_t* bias, uint16_t* y, int64_t M,
             int64_t N, int64_t K, int bm, int bn, int split, hipStream_t stream) {
   Rb8Args p{};
   p.a = a; p.b = b; p.scale_a = scale_a; p.scale_b = scale_b; p.bias = bias; p.y = y;
   p.M = (int)M; p.N = (int)N; p.K = (int)K;
-  if (bn == 32) return (bm == 64) ? launch_rb8<2, KIND, 4>(p, split, stream) : launch_rb8<2, KIND, 8>(p, split, stream);
-  if (bm == 64) return bn == 64 ? launch_rb8<4, KIND, 4>(p, split, stream) : launch_rb8<8, KIND, 4>(p, split, stream);
-  return bn == 64 ? launch_rb8<4, KIND, 8>(p, split, stream) : launch_rb8<8, KIND, 8>(p, split, stream);
+  if (bn == 32) return (bm == 64) ? launch_rb8_rowwise<2, INT8, 4>(p, split, stream) : launch_rb8_rowwise<2, INT8, 8>(p, split, stream);
+  if (bm == 64) return bn == 64 ? launch_rb8_rowwise<4, INT8, 4>(p, split, stream) : launch_rb8_rowwise<8, INT8, 4>(p, split, stream);
+  return bn == 64 ? launch_rb8_rowwise<4, INT8, 8>(p, split, stream) : launch_rb8_rowwise<8, INT8, 8>(p, split, stream);
 }
 
 }  // namespace
@@ -1275,8 +1274,8 @@ int rb8_scaled(bool int8, const void* a, const void* b, const float* scale_a, co
                int64_t N, int64_t K, int bm, int bn, int split, hipStream_t stream) {
   const uint8_t* a8 = static_cast<const uint8_t*>(a);
   const uint8_t* b8 = static_cast<const uint8_t*>(b);
-  return int8 ? rb8_run<RB8_INT8>(a8, b8, scale_a, scale_b, bias, y, M, N, K, bm, bn, split, stream)
-              : rb8_run<RB8_FP8>(a8, b8, scale_a, scale_b, bias, y, M, N, K, bm, bn, split, stream);
+  return int8 ? rb8_run<true>(a8, b8, scale_a, scale_b, bias, y, M, N, K, bm, bn, split, stream)
+              : rb8_run<false>(a8, b8, scale_a, scale_b, bias, y, M, N, K, bm, bn, split, stream);
 }
 
 // ---- the grouped GEMMs: MXFP8 (aten::_scaled_grouped_mm as called from mxfp8_grouped_mm.py:541, numerics of :959-1023) and rowwise fp8
@@ -1379,9 +1378,9 @@ int mxfp8_grouped_rb(const Grouped8Route& r, const void* a, const uint8_t* a_sca
     if (r.cast == 0) return launch_mx_stream<16, 3, 4>(p, stream);
     return r.cast == 2 ? launch_mx_stream<16, 3, 4, 2>(p, stream) : launch_mx_stream<16, 3, 4, 1>(p, stream);
   }
-  if (r.mt == 4) return r.qs == 4 ? launch_rb8<4, RB8_MX, 4, false, 4>(p, 1, stream) : launch_rb8<4, RB8_MX, 4, true>(p, 1, stream);
-  if (r.waves == 4) return r.qs == 4 ? launch_rb8<4, RB8_MX, 8, false, 4>(p, 1, stream) : launch_rb8<4, RB8_MX, 8>(p, 1, stream);
-  return r.qs == 4 ? launch_rb8<8, RB8_MX, 8, false, 4>(p, 1, stream) : launch_rb8<8, RB8_MX, 8>(p, 1, stream);
+  if (r.mt == 4) return r.qs == 4 ? launch_rb8_grouped<4, RB8_MX, 4, false, 4>(p, stream) : launch_rb8_grouped<4, RB8_MX, 4, true>(p, stream);
+  if (r.waves == 4) return r.qs == 4 ? launch_rb8_grouped<4, RB8_MX, 8, false, 4>(p, stream) : launch_rb8_grouped<4, RB8_MX, 8>(p, stream);
+  return r.qs == 4 ? launch_rb8_grouped<8, RB8_MX, 8, false, 4>(p, stream) : launch_rb8_grouped<8, RB8_MX, 8>(p, stream);
 }
 
 // The rowwise fp8 grouped GEMM: out[rows of group e] = bf16((a . b[e]^T) * scale_a[m] * scale_b[e][n]) -- the grouping of the MXFP8
@@ -1391,8 +1390,8 @@ int fp8_rowwise_grouped_rb(const Grouped8Route& r, const uint8_t* a, const uint8
   Rb8Args p{};
   p.a = a; p.b = b; p.scale_a = scale_a; p.scale_b = scale_b; p.y = out; p.offs = offs;
   p.M = (int)M_total; p.N = (int)N; p.K = (int)K; p.E = (int)E; p.slabs = r.slabs;
-  if (r.mt == 4) return launch_rb8<4, RB8_FP8_GROUPED, 4>(p, 1, stream);
-  return r.waves == 4 ? launch_rb8<4, RB8_FP8_GROUPED, 8>(p, 1, stream) : launch_rb8<8, RB8_FP8_GROUPED, 8>(p, 1, stream);
+  if (r.mt == 4) return launch_rb8_grouped<4, RB8_FP8_GROUPED, 4>(p, stream);
+  return r.waves == 4 ? launch_rb8_grouped<4, RB8_FP8_GROUPED, 8>(p, stream) : launch_rb8_grouped<8, RB8_FP8_GROUPED, 8>(p, stream);
 }
 
 }  // namespace ao

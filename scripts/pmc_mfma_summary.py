@@ -22,8 +22,9 @@ def label(n):
         return "gemm8_p8_kernel<" + ("int8" if "<0>" in n or "<1>" in n else "fp8") + ">"
     if "gemm8_dma_kernel" in n:
         return "gemm8_dma_kernel"
-    if "rb8_kernel" in n:
-        return "rb8_kernel"
+    for k in ("rb8_rowwise_kernel", "rb8_grouped_kernel"):
+        if k in n:
+            return k
     return None
 
 

@@ -364,6 +364,35 @@ def test_dyn8_override_form(product_dispatch, entry, M, bias):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("entry", ("fp8_scaled", "int8_scaled"))
+@pytest.mark.parametrize("parts", (1, 2))
+def test_rb8_1x8_override_form(product_dispatch, entry, parts):
+    """The 1 x 8 wave arrangement of the 8-wave x 128-row rowwise form (ao_gemm8_set_variant(103); the product stands 2 x 4), forced with
+    128-row slabs (key 3) and 128-column tiles (key 1): M = 130 leaves a second slab of 2 rows, N = 144 a second column tile with one
+    live n-tile (the aliased tiles past N), K = 896 seven k steps (every ring wraps), key 2 one meeting of two K parts."""
+    lib = product_dispatch
+    case = rc.Case("gemm8", entry, 130, 144, 896, 0, True, True)
+    assert case.K // 128 > rc.KLOOP_STEPS
+    dev = torch.device("cuda", 0)
+    run = Run(case, 103 + parts, dev)
+    buf = _parity.Guarded(case.M, case.N, run.out_dtype, dev)
+    lib.ao_gemm8_set_variant(103)
+    lib.ao_gemm8_set_tuning(3, 128)
+    lib.ao_gemm8_set_tuning(1, 128)
+    lib.ao_gemm8_set_tuning(2, parts)
+    try:
+        run.launch(buf)
+    finally:
+        lib.ao_gemm8_set_variant(0)
+        for key in (3, 1, 2):
+            lib.ao_gemm8_set_tuning(key, 0)
+    # ao_gemm8_route reports the product route (no override): the shape is rb8_kernel's; variant 103 and keys 1 - 3 change no route, only the
+    # launch shape inside it (rb8_launch_plan), which no query reports under an override
+    assert rc.route8(lib, entry, case.M, case.N, case.K, True)["kernel"] == "rb8"
+    _parity.check(buf, **run.ref)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("entry,M,N,form", [
     ("e4m3_codes", 100, 1000, 1), ("e4m3_fused", 100, 1000, 1), ("e2m1_codes", 100, 257, 1), ("e2m1_fused", 70, 257, 1),
     ("e4m3_codes", 5, 1000, 2), ("e2m1_codes", 32, 257, 2),

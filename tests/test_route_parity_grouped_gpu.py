@@ -239,3 +239,39 @@ def test_grouped_mx_variant_113_one_workgroup_per_tile(product_dispatch, sizes, 
     bufs = run.buffers()
     _forced(lib, 113, run, bufs)
     run.check(bufs)
+
+
+# ---- every (instance, m-tile specialisation) of rb8_grouped_kernel (profiles/rb8_split_instances_tests.txt) ----
+# (entry, waves, slab rows, k steps per scale fetch): key 3 forces the slab height; variant 113 keeps 64-row MX groups off the stream-K
+# form; K = 1024 (a multiple of 512, more than six steps) takes the per-4-step scales, K = 896 (seven steps) the per-step ones; 8 waves
+# need 400 (slab, tile) pairs, so M_total provides 134 slabs per group (the rows past offs[-1] keep the sentinel).
+_RB8_GROUPED_FORMS = [("mx", 4, 64, 1), ("mx", 4, 64, 4), ("mx", 4, 128, 1), ("mx", 4, 128, 4), ("mx", 8, 128, 1), ("mx", 8, 128, 4),
+                      ("fp8", 4, 64, 1), ("fp8", 4, 128, 1), ("fp8", 8, 128, 1)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("entry,waves,rows,qs,g", [(e, w, r, q, g) for e, w, r, q in _RB8_GROUPED_FORMS for g in (1, 17, 33, 65) if g < r])
+def test_rb8_grouped_instances(product_dispatch, entry, waves, rows, qs, g):
+    """Three experts with {0, g, 1} rows: the second group's slab has 1, 2, 3 or 5 m-tiles (the loop specialised on 1, 2, 4 or 8), the
+    third one row.  N = 80: with 4 waves the second tile has one live n-tile, with 8 waves the single tile has three idle waves."""
+    lib = product_dispatch
+    N, K, E = 80, 1024 if qs == 4 else 896, 3
+    M = g + 2 if waves == 4 else 133 * 128 + 1
+    case = rc.GCase("grouped", entry, M, N, K, E, True, "spread", "")
+    dev = torch.device("cuda", 0)
+    run = GRun(case, 9000 + 10 * rows + g, dev, [0, g, 1])
+    bufs = run.buffers()
+    lib.ao_gemm8_set_variant(113)
+    lib.ao_gemm8_set_tuning(3, rows)
+    try:
+        run.launch(bufs)
+    finally:
+        lib.ao_gemm8_set_variant(0)
+        lib.ao_gemm8_set_tuning(3, 0)
+    # ao_grouped8_route reports the product route only.  It is the forced form where grouped8_route needs no override for it: the 8-wave
+    # cases (M_total > 48 E: 128-row slabs; 402 (slab, tile) pairs) and rowwise fp8 at 64 rows (decode-size groups, no stream-K form).
+    # The other forms follow from key 3 and variant 113 by the same rules and cannot be read back.
+    if waves == 8 or (entry == "fp8" and rows == 64):
+        r = rc.route_grouped(lib, entry, M, N, K, E)
+        assert (r["kernel"], r["slab_rows"], r["waves"], r["mt"], r["qs"]) == ("rb8", rows, waves, rows // 16, qs), r
+    run.check(bufs)
