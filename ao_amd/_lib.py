@@ -166,6 +166,10 @@ _SIGNATURES = {
     "ao_nvfp4_train_quantize_row_col": [_P, _P, ctypes.c_uint32, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P],
     "ao_nvfp4_train_quantize_weight_2d": [_P, _P, _P, _P, _P, _P, _I64, _I64, _P],
     "ao_nvfp4_scaled_mm": [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _P],
+    "ao_qat_int4_fake_quantize": [_P, _P, _I64, _I64, _INT, _P],
+    "ao_qat_int4_fake_quantize_bwd": [_P, _P, _P, _I64, _I64, _INT, _P],
+    "ao_qat_fp8_fake_quantize_rowwise": [_P, _P, _I64, _I64, ctypes.c_float, ctypes.c_float, _P],
+    "ao_qat_fp8_fake_quantize_rowwise_bwd": [_P, _P, _P, _I64, _I64, ctypes.c_float, ctypes.c_float, _P],
 }
 
 

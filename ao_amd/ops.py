@@ -2393,3 +2393,103 @@ def nvfp4_scaled_mm(a, a_scale, b, b_scale, a_per_tensor_scale, b_per_tensor_sca
 
 
 __all__ += ["nvfp4_sign_mask", "nvfp4_train_amax", "nvfp4_train_quantize_row_col", "nvfp4_train_quantize_weight_2d", "nvfp4_scaled_mm"]
+
+
+# ---------------------------------------------------------------------------
+# Quantization-aware training (torchao.quantization.qat): each fake quantizer and its gradient as one launch, bf16 -> bf16.  The backward
+# ops take the forward's INPUT and the incoming gradient; nothing else is saved.
+# ---------------------------------------------------------------------------
+def _qat_bf16(name, what, t):
+    if t.dtype != torch.bfloat16:
+        raise RuntimeError(f"{name}: {what} must be bfloat16, got {t.dtype}")
+
+
+def _qat_int4_args(name, w, group_size, grad_out=None):
+    _qat_bf16(name, "w", w)
+    if w.dim() != 2:
+        raise RuntimeError(f"{name}: w must be 2-D [N, K], got {w.dim()}-D")
+    if group_size not in (32, 64, 128, 256):
+        raise ValueError(f"{name}: group_size must be one of 32, 64, 128, 256, got {group_size}")
+    n, k = w.shape
+    if k == 0 or k % group_size != 0:
+        raise ValueError(f"{name}: K={k} must be a multiple of group_size={group_size}")
+    if grad_out is not None:
+        _qat_bf16(name, "grad_out", grad_out)
+        if grad_out.shape != w.shape:
+            raise RuntimeError(f"{name}: grad_out has shape {tuple(grad_out.shape)} but w has {tuple(w.shape)}")
+        grad_out = grad_out.contiguous()
+    dev = _require_gpu(name, w, grad_out)
+    return dev, w.contiguous(), grad_out, n, k
+
+
+def qat_int4_fake_quantize(w: torch.Tensor, group_size: int = 128) -> torch.Tensor:
+    """Int4WeightFakeQuantizer._bf16_activations_forward (torchao/quantization/qat/fake_quantizer.py:167-187): w bf16 [N, K] -> bf16 [N, K],
+    every group of `group_size` along K replaced by the values its asymmetric int4 codes stand for: s = max(max - min, 1e-6) / 15,
+    q = clamp(rint((w - min) / s), 0, 15), out = (q - 8) s + (min + 8 s), in fp32.  The codes are int4_plain_quantize's."""
+    name = "qat_int4_fake_quantize"
+    dev, w, _, n, k = _qat_int4_args(name, w, group_size)
+    out = torch.empty_like(w)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_qat_int4_fake_quantize(_ptr(w), _ptr(out), n, k, group_size, _stream()))
+    return out
+
+
+def qat_int4_fake_quantize_bwd(w: torch.Tensor, grad_out: torch.Tensor, group_size: int = 128) -> torch.Tensor:
+    """The gradient autograd gives through the same lines (fake_quantizer.py:167-187): the straight-through term inside the clamp, plus
+    the share of the group's maximum and minimum through the scale and the zero point (ties share it evenly).  w, grad_out bf16 [N, K]
+    -> grad_w bf16 [N, K]; the range and the codes are made again from w."""
+    name = "qat_int4_fake_quantize_bwd"
+    dev, w, grad_out, n, k = _qat_int4_args(name, w, group_size, grad_out)
+    grad_w = torch.empty_like(w)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_qat_int4_fake_quantize_bwd(_ptr(w), _ptr(grad_out), _ptr(grad_w), n, k, group_size, _stream()))
+    return grad_w
+
+
+def _qat_fp8_args(name, x, hp_value_lb, hp_value_ub, grad_out=None):
+    _qat_bf16(name, "x", x)
+    if x.dim() < 1:
+        raise RuntimeError(f"{name}: x must have at least one dimension")
+    c = x.shape[-1]
+    if c == 0 or c % 16 != 0:
+        raise ValueError(f"{name}: C={c} must be a multiple of 16")
+    lb = float("-inf") if hp_value_lb is None else float(hp_value_lb)
+    ub = float("inf") if hp_value_ub is None else float(hp_value_ub)
+    if not lb <= ub:
+        raise ValueError(f"{name}: hp_value_lb={hp_value_lb} must not exceed hp_value_ub={hp_value_ub}")
+    if grad_out is not None:
+        _qat_bf16(name, "grad_out", grad_out)
+        if grad_out.shape != x.shape:
+            raise RuntimeError(f"{name}: grad_out has shape {tuple(grad_out.shape)} but x has {tuple(x.shape)}")
+        grad_out = grad_out.contiguous()
+    dev = _require_gpu(name, x, grad_out)
+    x = x.contiguous()
+    return dev, x, grad_out, x.numel() // c, c, lb, ub
+
+
+def qat_fp8_fake_quantize_rowwise(x: torch.Tensor, hp_value_lb: Optional[float] = None, hp_value_ub: Optional[float] = None) -> torch.Tensor:
+    """Float8FakeQuantizer.forward with PerRow() and float8_e4m3fn (fake_quantizer.py:84-98; quant_primitives.py:2173-2304): x bf16
+    [..., C] -> bf16 [..., C], every row (all leading dimensions flattened) through scale = bf16(clamp(max|x|, lb, ub) / 448),
+    q = e4m3(clamp(x / scale, -448, 448)), out = q scale.  A row whose clamped maximum is 0 comes back NaN, as in the reference."""
+    name = "qat_fp8_fake_quantize_rowwise"
+    dev, x, _, r, c, lb, ub = _qat_fp8_args(name, x, hp_value_lb, hp_value_ub)
+    out = torch.empty_like(x)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_qat_fp8_fake_quantize_rowwise(_ptr(x), _ptr(out), r, c, lb, ub, _stream()))
+    return out
+
+
+def qat_fp8_fake_quantize_rowwise_bwd(x: torch.Tensor, grad_out: torch.Tensor, hp_value_lb: Optional[float] = None,
+                                      hp_value_ub: Optional[float] = None) -> torch.Tensor:
+    """The gradient of that chain with every cast straight-through (the reference's own autograd rounds the incoming
+    gradient to e4m3): the identity inside the +-448 clamp, plus the row maximum's share through the scale where the amax lies inside
+    [lb, ub].  x, grad_out bf16 [..., C] -> grad_x bf16 [..., C]."""
+    name = "qat_fp8_fake_quantize_rowwise_bwd"
+    dev, x, grad_out, r, c, lb, ub = _qat_fp8_args(name, x, hp_value_lb, hp_value_ub, grad_out)
+    grad_x = torch.empty_like(x)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_qat_fp8_fake_quantize_rowwise_bwd(_ptr(x), _ptr(grad_out), _ptr(grad_x), r, c, lb, ub, _stream()))
+    return grad_x
+
+
+__all__ += ["qat_int4_fake_quantize", "qat_int4_fake_quantize_bwd", "qat_fp8_fake_quantize_rowwise", "qat_fp8_fake_quantize_rowwise_bwd"]

@@ -1003,6 +1003,38 @@ const char* ao_nvfp4_grouped_mm_kernel_name(int kind, int64_t M_total, int64_t N
  * 1 streaming, 2 tiled); the route queries report the forced form. */
 int ao_nvfp4_grouped_mm_set_form(int form);
 
+/* ---- quantization-aware training: the fake quantizers of torchao.quantization.qat, one launch per direction ----------
+ * bf16 in, bf16 out, fp32 in between in the reference's order; every division correctly rounded; the only rounding to bf16 is the last.
+ * The backward entries take only the forward's INPUT and the incoming gradient: the range, the scale and the codes are made again, no
+ * mask is stored.  No atomics: the same bytes every launch.  No allocation, no synchronisation: capturable in a graph.  Pointers
+ * 16-byte aligned. */
+
+/* Replaces Int4WeightFakeQuantizer._bf16_activations_forward (qat/fake_quantizer.py:167-187), some fifteen tensor ops: per group of
+ * group_size along K,  M = max, m = min, s = max(M - m, 1e-6) / 15,  q = clamp(rint((w - m) / s), 0, 15),
+ * out = bf16((q - 8) s + (m + 8 s)) -- the value bf16-dequantised codes of ao_int4_plain_quantize stand for.
+ * w, out bf16 [N][K].  group_size in {32, 64, 128, 256}, K % group_size == 0 (K % 128 is NOT required); N == 0 launches nothing. */
+int ao_qat_int4_fake_quantize(const uint16_t* w, uint16_t* out, int64_t N, int64_t K, int group_size, void* stream);
+/* Replaces autograd through the same lines (qat/fake_quantizer.py:167-187; _Round, qat/utils.py, is straight-through): with G = grad_out,
+ * t the unclamped quotient, c = 1 where 0 <= rint(t) <= 15,
+ *   ds = sum G (q - c t),  dm = sum G (1 - c),  dr = ds / 15 where M - m >= 1e-6 else 0,
+ *   grad_w = bf16(G c + [w = M] dr / #{w = M} + [w = m] (dm - dr) / #{w = m})       (sums over the group; ties share evenly) */
+int ao_qat_int4_fake_quantize_bwd(const uint16_t* w, const uint16_t* grad_out, uint16_t* grad_w, int64_t N, int64_t K, int group_size,
+                                  void* stream);
+/* Replaces Float8FakeQuantizer.forward with PerRow() and float8_e4m3fn (qat/fake_quantizer.py:84-98 over _choose_scale_float8,
+ * _quantize_affine_float8, _dequantize_affine_float8, quant_primitives.py:2173-2304): per row,
+ *   a = clamp(max|x|, lb, ub) as bf16 values (the reference clamps the bf16 amax),  s = f32(bf16(a / 448)),
+ *   out = bf16(f32(e4m3_rne(clamp(f32(x) / s, -448, 448))) s)
+ * lb, ub: hp_value_lb / hp_value_ub; -INFINITY / +INFINITY when absent.  A row whose clamped amax is 0 is NaN (0 / 0), as in the reference,
+ * written as 0xFFFF.  x, out bf16 [R][C], C % 16 == 0; R == 0 launches nothing.  Rows of up to 16384 elements stay in registers between
+ * the amax and the cast; longer rows are walked twice. */
+int ao_qat_fp8_fake_quantize_rowwise(const uint16_t* x, uint16_t* out, int64_t R, int64_t C, float lb, float ub, void* stream);
+/* The gradient of that chain (qat/fake_quantizer.py:84-98, quant_primitives.py:2173-2304) with EVERY cast straight-through -- not the
+ * reference's autograd, which rounds the incoming gradient to e4m3.  With t = f32(x) / s, c = 1 where |t| <= 448:
+ *   ds = sum G (q - c t),  da = ds / 448 where lb <= max|x| <= ub else 0,
+ *   grad_x = bf16(G c + [|x| = max|x|] sign(x) da / #{|x| = max|x|})                 (sums over the row; ties share evenly) */
+int ao_qat_fp8_fake_quantize_rowwise_bwd(const uint16_t* x, const uint16_t* grad_out, uint16_t* grad_x, int64_t R, int64_t C, float lb,
+                                         float ub, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
