@@ -170,6 +170,13 @@ _SIGNATURES = {
     "ao_qat_int4_fake_quantize_bwd": [_P, _P, _P, _I64, _I64, _INT, _P],
     "ao_qat_fp8_fake_quantize_rowwise": [_P, _P, _I64, _I64, ctypes.c_float, ctypes.c_float, _P],
     "ao_qat_fp8_fake_quantize_rowwise_bwd": [_P, _P, _P, _I64, _I64, ctypes.c_float, ctypes.c_float, _P],
+    "ao_nf4_block_absmax": [_P, _P, _I64, _INT, _P],
+    "ao_nf4_quantize": [_P, _P, _P, _P, _P, _P, _I64, _INT, _I64, _P],
+    "ao_nf4_dequantize": [_P, _P, _P, _P, _P, _I64, _INT, _I64, _P],
+    "ao_nf4_linear": [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _INT, _I64, _P],
+    "ao_nf4_linear_route": [_I64, _I64, _I64, _INT, _I64, _P, _INT],
+    "ao_nf4_linear_kernel_name": [_I64, _I64, _I64, _INT, _I64],
+    "ao_nf4_linear_set_form": [_INT],
 }
 
 

@@ -544,4 +544,67 @@ __device__ __forceinline__ u32x2 nvfp4_train_codes16(const float (&a)[16], float
 // the scaled_mm epilogue of the training GEMMs: out = bf16(acc (pa pb)), the product of the two scales in fp32, ONE rounding, no bias
 __device__ __forceinline__ float nvfp4_scaled_mm_out(float c, float P) { return mul_f32_rn(c, P); }
 
+// ---- NF4 (nf4_kernels.hip): the QLoRA weight of torchao's NF4Tensor (quantization/quantize_/workflows/nf4/nf4_tensor.py) ----------------
+// Every tensor is bf16; bf16(...) is an fp32 operation rounded ONCE to bf16, nearest even; divisions are correctly rounded fp32
+// divisions; subnormals are kept.  A flattened tensor, blocks of B elements, scaler blocks of SB consecutive blocks:
+//   cast (from_tensor :649-718; double_quantize_scalers :721-778; convert_to_norm_float_weight :806-843):
+//     a[b]  = max |x| over block b (exact);   mean = bf16(mean of a) -- the only order-dependent value: torch computes it, the kernels
+//     read it through a device pointer;   c[b] = bf16(a[b] - mean)
+//     per scaler block:  m = max |c|;  qf = bf16(256 / bf16(2 m));  q[b] = int8(clamp(rint(bf16(c[b] qf)), -128, 127)), rint to even
+//       -- m = 0: qf = inf, the product is NaN and the reference's NaN -> int8 is undefined; a NaN product writes 0 here
+//     per element:  v = bf16(x / a[b]);  code = the FIRST i that minimises |bf16(v - table[i])| (quantize_tensor_nearest :874-880); a
+//       NaN v (an all-zero block: 0 / 0) compares below nothing, code 0, as torch.min;  elements 2i | 2i + 1 share byte i, 2i in the
+//       HIGH nibble
+//   dequantize (get_original_weight :845-871; dequantize_scalers :780-803):
+//     s[b] = bf16(bf16(f32(q[b]) / qf[b / SB]) + mean);   w = bf16(table[code] s[b]) (the product of two bf16 is exact in fp32)
+//   linear (LinearNF4 :1053-1064):  y = bf16(sum_k x[m, k] w[n, k]), exact products, fp32 accumulation in any order
+// The table (:666-684) rounded to bf16, as bits; every entry is a multiple of 2^-11.
+__device__ __forceinline__ float nf4_value(uint32_t code) {
+  constexpr uint32_t bits[16] = {0xbf800000u, 0xbf320000u, 0xbf060000u, 0xbeca0000u, 0xbe920000u, 0xbe3d0000u, 0xbdbb0000u, 0x00000000u,
+                                 0x3da30000u, 0x3e250000u, 0x3e7c0000u, 0x3ead0000u, 0x3ee20000u, 0x3f100000u, 0x3f390000u, 0x3f800000u};
+  return bits_to_f32(bits[code]);
+}
+// v (an fp32 holding a bf16) -> its code
+__device__ __forceinline__ uint32_t nf4_code(float v) {
+#pragma clang fp contract(off)
+  uint32_t best = 0u;
+  float bd = fabsf(round_bf16(v - nf4_value(0)));
+#pragma unroll
+  for (uint32_t i = 1; i < 16; ++i) {
+    const float d = fabsf(round_bf16(v - nf4_value(i)));
+    if (d < bd) {  // (false for a NaN: the first index stays)
+      bd = d;
+      best = i;
+    }
+  }
+  return best;
+}
+// 8 bf16 of ONE block -> 8 codes, 4 bytes in memory order; a: the block's maximum
+__device__ __forceinline__ uint32_t nf4_cast8(const u32x4& x, float a) {
+  const uint32_t w[4] = {x.x, x.y, x.z, x.w};
+  uint32_t o = 0u;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const uint32_t hi = nf4_code(round_bf16(bf16_lo_to_f32(w[j]) / a)), lo = nf4_code(round_bf16(bf16_hi_to_f32(w[j]) / a));
+    o |= ((hi << 4) | lo) << (8 * j);
+  }
+  return o;
+}
+// the centred scaler of a block and, from a scaler block's m, its quantization factor and a block's int8 scaler
+__device__ __forceinline__ float nf4_centred(float a, float mean) { return round_bf16(a - mean); }
+__device__ __forceinline__ float nf4_factor(float m) { return round_bf16(256.0f / round_bf16(2.0f * m)); }
+__device__ __forceinline__ int nf4_scaler_q(float c, float qf) {
+  const float p = round_bf16(mul_f32_rn(c, qf));
+  return (p != p) ? 0 : (int)fminf(fmaxf(rintf(p), -128.f), 127.f);
+}
+// dequantize's scaler of a block: q its int8 scaler, qf the factor of its scaler block
+__device__ __forceinline__ float nf4_scaler(int q, float qf, float mean) { return round_bf16(round_bf16((float)q / qf) + mean); }
+// 8 codes (4 bytes in memory order) -> 8 bf16 = bf16(table[code] s); tab: the 16 fp32 table values in LDS
+__device__ __forceinline__ u32x4 nf4_decode8(uint32_t c, float s, const float* tab) {
+  uint32_t o[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) o[j] = pack_bf16x2(tab[(c >> (8 * j + 4)) & 15u] * s, tab[(c >> (8 * j)) & 15u] * s);
+  return u32x4{o[0], o[1], o[2], o[3]};
+}
+
 }  // namespace ao

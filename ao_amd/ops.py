@@ -2493,3 +2493,143 @@ def qat_fp8_fake_quantize_rowwise_bwd(x: torch.Tensor, grad_out: torch.Tensor, h
 
 
 __all__ += ["qat_int4_fake_quantize", "qat_int4_fake_quantize_bwd", "qat_fp8_fake_quantize_rowwise", "qat_fp8_fake_quantize_rowwise_bwd"]
+
+
+# ---- NF4 (QLoRA) weights: NF4Tensor's cast, dequantize and linear (include/ao_mi355.h "NF4") ---------------------------------
+NF4_KERNELS = {0: "not fused", 1: "nf4_stream_kernel"}
+NF4_BLOCK_SIZES = (32, 64, 128)
+
+
+def _nf4_format(name, numel, block_size, scaler_block_size):
+    """The sizes the kernels take, refused by reason before the library is touched."""
+    if block_size not in NF4_BLOCK_SIZES:
+        raise ValueError(f"{name}: block_size must be one of 32, 64, 128, got {block_size}")
+    if not isinstance(scaler_block_size, int) or scaler_block_size < 1 or scaler_block_size & (scaler_block_size - 1):
+        raise ValueError(f"{name}: scaler_block_size must be a power of two >= 1, got {scaler_block_size}")
+    if numel % (block_size * scaler_block_size) != 0:
+        raise ValueError(f"{name}: numel={numel} must be a multiple of block_size x scaler_block_size = {block_size} x {scaler_block_size}")
+    if numel >= 1 << 31:
+        raise ValueError(f"{name}: numel={numel} must be below 2^31")
+
+
+def _nf4_bf16(name, what, t):
+    if t.dtype != torch.bfloat16:
+        raise RuntimeError(f"{name}: {what} must be bfloat16, got {t.dtype}")
+
+
+def _nf4_mean(name, mean, dev):
+    """scaler_mean as one bf16 on the device: read by the kernels through its pointer, never on the host."""
+    if not isinstance(mean, torch.Tensor) or mean.numel() != 1 or mean.dtype != torch.bfloat16:
+        raise RuntimeError(f"{name}: mean must be a bfloat16 tensor of one element")
+    if mean.device != dev:
+        raise RuntimeError(f"{name}: mean is on {mean.device}, the operands on {dev}")
+    return mean.reshape(()).contiguous()
+
+
+def _nf4_fields(name, codes, scalers, factors, block_size, scaler_block_size):
+    """The three per-element / per-block fields of an NF4Tensor, flat and contiguous; returns them and numel."""
+    if codes.dtype != torch.uint8 or codes.dim() != 1:
+        raise RuntimeError(f"{name}: the codes must be a 1-D uint8 tensor [numel / 2], got {codes.dtype} {tuple(codes.shape)}")
+    numel = codes.numel() * 2
+    _nf4_format(name, numel, block_size, scaler_block_size)
+    if scalers.dtype != torch.int8 or tuple(scalers.shape) != (numel // block_size,):
+        raise RuntimeError(f"{name}: the scalers must be int8 [numel / block_size] = {(numel // block_size,)}, got {scalers.dtype} {tuple(scalers.shape)}")
+    nsb = numel // (block_size * scaler_block_size)
+    if factors.dtype != torch.bfloat16 or tuple(factors.shape) != (nsb,):
+        raise RuntimeError(f"{name}: the factors must be bfloat16 [numel / (block_size x scaler_block_size)] = {(nsb,)}, got {factors.dtype} "
+                           f"{tuple(factors.shape)}")
+    return codes.contiguous(), scalers.contiguous(), factors.contiguous(), numel
+
+
+def nf4_block_absmax(x: torch.Tensor, block_size: int = 64) -> torch.Tensor:
+    """get_block_absmax (nf4_tensor.py:560-577) on the flattened tensor: x bf16, any shape -> bf16 [numel / block_size]."""
+    name = "nf4_block_absmax"
+    _nf4_bf16(name, "x", x)
+    _nf4_format(name, x.numel(), block_size, 1)
+    dev = _require_gpu(name, x)
+    x = x.contiguous()
+    out = torch.empty((x.numel() // block_size,), dtype=torch.bfloat16, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_nf4_block_absmax(_ptr(x), _ptr(out), x.numel(), block_size, _stream()))
+    return out
+
+
+def nf4_quantize(x: torch.Tensor, absmax: torch.Tensor, mean: torch.Tensor, block_size: int = 64, scaler_block_size: int = 256):
+    """The rest of NF4Tensor.from_tensor (nf4_tensor.py:649-718) in one launch, the reference's bytes: x bf16 (any shape, flattened),
+    absmax = nf4_block_absmax(x), mean = absmax.mean() (torch's, on the device) -> (quantized_data uint8 [numel / 2], quantized_scalers
+    int8 [numel / block_size], quantization_factor bf16 [numel / (block_size x scaler_block_size)])."""
+    name = "nf4_quantize"
+    _nf4_bf16(name, "x", x)
+    _nf4_bf16(name, "absmax", absmax)
+    numel = x.numel()
+    _nf4_format(name, numel, block_size, scaler_block_size)
+    if tuple(absmax.shape) != (numel // block_size,):
+        raise RuntimeError(f"{name}: absmax must be [numel / block_size] = {(numel // block_size,)}, got {tuple(absmax.shape)}")
+    dev = _require_gpu(name, x, absmax, mean)
+    mean = _nf4_mean(name, mean, dev)
+    x, absmax = x.contiguous(), absmax.contiguous()
+    codes = torch.empty((numel // 2,), dtype=torch.uint8, device=dev)
+    scalers = torch.empty((numel // block_size,), dtype=torch.int8, device=dev)
+    factors = torch.empty((numel // (block_size * scaler_block_size),), dtype=torch.bfloat16, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_nf4_quantize(_ptr(x), _ptr(absmax), _ptr(mean), _ptr(codes), _ptr(scalers), _ptr(factors), numel, block_size,
+                                              scaler_block_size, _stream()))
+    return codes, scalers, factors
+
+
+def nf4_dequantize(codes, scalers, factors, mean, block_size: int = 64, scaler_block_size: int = 256) -> torch.Tensor:
+    """NF4Tensor.get_original_weight (nf4_tensor.py:845-871) in one launch, flat: -> bf16 [numel] (the caller views it as the weight)."""
+    name = "nf4_dequantize"
+    codes, scalers, factors, numel = _nf4_fields(name, codes, scalers, factors, block_size, scaler_block_size)
+    dev = _require_gpu(name, codes, scalers, factors, mean)
+    mean = _nf4_mean(name, mean, dev)
+    w = torch.empty((numel,), dtype=torch.bfloat16, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_nf4_dequantize(_ptr(codes), _ptr(scalers), _ptr(factors), _ptr(mean), _ptr(w), numel, block_size, scaler_block_size,
+                                                _stream()))
+    return w
+
+
+def nf4_linear_route(m: int, n: int, k: int, block_size: int = 64, scaler_block_size: int = 256) -> dict:
+    """The route nf4_linear takes for a shape (host logic only, ao_nf4_linear_route): kernel "nf4_stream_kernel", or "not fused" --
+    dequantize, then multiply -- above the seam and for shapes the kernel does not take (K % block_size != 0)."""
+    return _two_form_route("ao_nf4_linear_route", NF4_KERNELS, m, n, k, block_size, scaler_block_size)
+
+
+def nf4_linear_kernel_name(m: int, n: int, k: int, block_size: int = 64, scaler_block_size: int = 256) -> str:
+    return _two_form_kernel_name("ao_nf4_linear_kernel_name", m, n, k, block_size, scaler_block_size)
+
+
+def nf4_set_form(form: int) -> None:
+    """Measurement only: 0 the product route, 1 the stream kernel at any M (calling thread).  There is no tiled form."""
+    _two_form_set_form("ao_nf4_linear_set_form", form)
+
+
+def nf4_linear(x2, codes, scalers, factors, mean, n: int, k: int, block_size: int = 64, scaler_block_size: int = 256, out=None):
+    """LinearNF4.forward (nf4_tensor.py:1053-1058) on a 2-D bf16 activation: bf16(x . w^T) with w [n, k] the bits of nf4_dequantize, fp32
+    accumulation, no bias.  By the route: one launch that streams the fields once, or nf4_dequantize + F.linear."""
+    name = "nf4_linear"
+    if x2.dim() != 2 or x2.dtype != torch.bfloat16:
+        raise RuntimeError(f"{name}: x must be a 2-D bfloat16 tensor, got {tuple(x2.shape)} {x2.dtype}")
+    codes, scalers, factors, numel = _nf4_fields(name, codes, scalers, factors, block_size, scaler_block_size)
+    if n < 1 or k < 1 or n * k != numel:
+        raise RuntimeError(f"{name}: the weight shape [{n}, {k}] does not hold the {numel} elements of the fields")
+    m, kx = x2.shape
+    if kx != k:
+        raise RuntimeError(f"{name}: K mismatch {kx} vs {k}")
+    dev = _require_gpu(name, x2, codes, scalers, factors, mean)
+    mean = _nf4_mean(name, mean, dev)
+    x2 = x2.contiguous()
+    if nf4_linear_route(m, n, k, block_size, scaler_block_size)["kernel"] != NF4_KERNELS[1]:
+        w = nf4_dequantize(codes, scalers, factors, mean, block_size, scaler_block_size).view(n, k)
+        y = torch.nn.functional.linear(x2, w)
+        return y if out is None else _bf16_out(name, out, m, n, dev).copy_(y)
+    y = _bf16_out(name, out, m, n, dev)
+    if m > 0:
+        with _on(dev):
+            _lib.check(_lib.lib().ao_nf4_linear(_ptr(x2), _ptr(codes), _ptr(scalers), _ptr(factors), _ptr(mean), _ptr(y), m, n, k, block_size,
+                                                scaler_block_size, _stream()))
+    return y
+
+
+__all__ += ["nf4_block_absmax", "nf4_quantize", "nf4_dequantize", "nf4_linear", "nf4_linear_route", "nf4_linear_kernel_name", "nf4_set_form"]

@@ -21,6 +21,7 @@ from .mx_training import (  # noqa: F401
     _to_mxfp8_then_scaled_mm,
     mx_mm,
 )
+from .nf4_api import NF4WeightOnlyConfig, nf4_weight_only  # noqa: F401
 from .nvfp4_grouped import NVFP4ExpertWeights, nvfp4_grouped_mm  # noqa: F401
 from .nvfp4_tensor import (  # noqa: F401
     NVFP4DynamicActivationNVFP4WeightConfig,
@@ -44,4 +45,5 @@ __all__ = ["Float8BlockwiseExpertWeights", "fp8_blockwise_grouped_mm", "NVFP4Ten
            "_Float8GroupedMM", "_to_fp8_rowwise_then_scaled_grouped_mm", "fp8_blockwise_mm", "Float8BlockwiseLinear",
            "Float8BlockwiseLinearConfig", "_Float8BlockwiseGroupedMM", "_to_fp8_blockwise_then_scaled_grouped_mm",
            "_to_fp8_blockwise_then_emulated_scaled_grouped_mm",
-           "NVFP4Linear", "NVFP4TrainingConfig", "nvfp4_linear", "DEFAULT_SIGN_VECTOR", "get_wgrad_sign_vector"]
+           "NVFP4Linear", "NVFP4TrainingConfig", "nvfp4_linear", "DEFAULT_SIGN_VECTOR", "get_wgrad_sign_vector",
+           "NF4WeightOnlyConfig", "nf4_weight_only"]

@@ -23,4 +23,5 @@ from .float8_tensor import Float8Tensor, QuantizeTensorToFloat8Kwargs  # noqa: F
 from .int4_plain_tensor import Int4Tensor  # noqa: F401
 from .int4_tensor import Int4TilePackedTo4dTensor  # noqa: F401
 from .int8_tensor import Int8Tensor, QuantizeTensorToInt8Kwargs  # noqa: F401
+from .nf4_tensor import LinearNF4, NF4Tensor, linear_nf4, to_nf4  # noqa: F401
 from .quant_api import quantize_  # noqa: F401

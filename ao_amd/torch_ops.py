@@ -555,4 +555,44 @@ def install_aten_overrides(int_mm: bool = False) -> None:
     _aten_impl = lib
 
 
+# ---- NF4 (QLoRA) weights (ops.py "NF4"): definitions, CUDA kernels, fakes, autograd fallthrough -----------------------------
+# (the gradient of linear_nf4 lives in LinearNF4, ao_amd/quantization/nf4_tensor.py: these ops are its forward pieces)
+_lib_def.define("nf4_block_absmax(Tensor x, int block_size) -> Tensor")
+_lib_def.define("nf4_quantize(Tensor x, Tensor absmax, Tensor mean, int block_size, int scaler_block_size) -> (Tensor, Tensor, Tensor)")
+_lib_def.define("nf4_dequantize(Tensor codes, Tensor scalers, Tensor factors, Tensor mean, int block_size, int scaler_block_size) -> Tensor")
+_lib_def.define("nf4_linear(Tensor x, Tensor codes, Tensor scalers, Tensor factors, Tensor mean, int n, int k, int block_size, "
+                "int scaler_block_size) -> Tensor")
+_lib_impl.impl("nf4_block_absmax", ops.nf4_block_absmax)
+_lib_impl.impl("nf4_quantize", ops.nf4_quantize)
+_lib_impl.impl("nf4_dequantize", ops.nf4_dequantize)
+_lib_impl.impl("nf4_linear", lambda x, codes, scalers, factors, mean, n, k, block_size, scaler_block_size: ops.nf4_linear(
+    x, codes, scalers, factors, mean, n, k, block_size, scaler_block_size))
+
+
+@torch.library.register_fake("ao_mi355::nf4_block_absmax")
+def _(x, block_size):
+    return x.new_empty((x.numel() // block_size,), dtype=torch.bfloat16)
+
+
+@torch.library.register_fake("ao_mi355::nf4_quantize")
+def _(x, absmax, mean, block_size, scaler_block_size):
+    n = x.numel()
+    return (x.new_empty((n // 2,), dtype=torch.uint8), x.new_empty((n // block_size,), dtype=torch.int8),
+            x.new_empty((n // (block_size * scaler_block_size),), dtype=torch.bfloat16))
+
+
+@torch.library.register_fake("ao_mi355::nf4_dequantize")
+def _(codes, scalers, factors, mean, block_size, scaler_block_size):
+    return codes.new_empty((codes.numel() * 2,), dtype=torch.bfloat16)
+
+
+@torch.library.register_fake("ao_mi355::nf4_linear")
+def _(x, codes, scalers, factors, mean, n, k, block_size, scaler_block_size):
+    return x.new_empty((x.shape[0], n), dtype=torch.bfloat16)
+
+
+for _name in ("nf4_block_absmax", "nf4_quantize", "nf4_dequantize", "nf4_linear"):
+    _lib_autograd.impl(_name, torch.library.fallthrough_kernel)
+
+
 load_ops_library()

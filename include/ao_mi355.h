@@ -1035,6 +1035,39 @@ int ao_qat_fp8_fake_quantize_rowwise(const uint16_t* x, uint16_t* out, int64_t R
 int ao_qat_fp8_fake_quantize_rowwise_bwd(const uint16_t* x, const uint16_t* grad_out, uint16_t* grad_x, int64_t R, int64_t C, float lb,
                                          float ub, void* stream);
 
+/* ---- NF4 (QLoRA) weights: NF4Tensor of quantization/quantize_/workflows/nf4/nf4_tensor.py (nf4_kernels.hip) -------------
+ * A flattened bf16 tensor of numel elements in blocks of block_size (32, 64 or 128); scaler blocks of scaler_block_size (a power of two)
+ * consecutive blocks; numel a multiple of block_size x scaler_block_size, below 2^31.  The tensor's fields as the reference stores them:
+ * codes uint8 [numel / 2] (quantized_data, element 2i in the HIGH nibble), scalers int8 [numel / block_size] (quantized_scalers), factors
+ * bf16 [numel / (block_size x scaler_block_size)] (quantization_factor), mean one bf16 on the device (scaler_mean).  The arithmetic is
+ * stated once, in csrc/quant_math.h ("NF4"), and gives the reference's bytes.  Anything else is rejected on the host before any launch;
+ * no allocation, no synchronisation: capturable in a graph. */
+/* Replaces get_block_absmax (nf4_tensor.py:560-577): absmax[b] = max |x| over block b, NaN if the block holds one. */
+int ao_nf4_block_absmax(const uint16_t* x, uint16_t* absmax, int64_t numel, int block_size, void* stream);
+/* Replaces the rest of NF4Tensor.from_tensor (nf4_tensor.py:649-718: double_quantize_scalers :721-778 and convert_to_norm_float_weight
+ * :806-843 with quantize_tensor_nearest :874-880) in ONE launch, given absmax and its mean -- bf16(absmax.mean()), the only value that
+ * depends on a summation order, which the caller takes from torch on the device.  A scaler block whose centred scalers are all zero has an
+ * infinite factor and NaN products, whose int8 the reference leaves undefined: 0 here. */
+int ao_nf4_quantize(const uint16_t* x, const uint16_t* absmax, const uint16_t* mean, uint8_t* codes, int8_t* scalers, uint16_t* factors,
+                    int64_t numel, int block_size, int64_t scaler_block_size, void* stream);
+/* Replaces NF4Tensor.get_original_weight (nf4_tensor.py:845-871 with dequantize_scalers :780-803): w bf16 [numel], 16-byte aligned. */
+int ao_nf4_dequantize(const uint8_t* codes, const int8_t* scalers, const uint16_t* factors, const uint16_t* mean, uint16_t* w, int64_t numel,
+                      int block_size, int64_t scaler_block_size, void* stream);
+/* Replaces LinearNF4.forward (nf4_tensor.py:1053-1058: F.linear(input, weight.to(input.dtype))) at decode row counts, the weight-streaming
+ * form only: x bf16 [M][K] times the fields of W [N][K] -> out bf16 [M][N] = bf16(sum_k x w), w the bits of ao_nf4_dequantize, fp32
+ * accumulation, no bias (the reference adds it outside).  The weight is read once, straight from the fields.  K % block_size == 0 (blocks
+ * inside rows); x and codes 16-byte aligned; M == 0 launches nothing.  A shape whose route is "not fused" is an error here. */
+int ao_nf4_linear(const uint16_t* x, const uint8_t* codes, const int8_t* scalers, const uint16_t* factors, const uint16_t* mean, uint16_t* out,
+                  int64_t M, int64_t N, int64_t K, int block_size, int64_t scaler_block_size, void* stream);
+/* The route of LinearNF4.forward (nf4_tensor.py:1053-1058 has one path; host logic only): out[cap >= 7] = kernel (1 nf4_stream_kernel;
+ * 0 not fused -- above the row count up to which the fused form wins, or a shape ao_nf4_linear does not take: ao_nf4_dequantize, then a
+ * bf16 GEMM), waves, m-tiles, tile rows, tile columns, grid x, grid y. */
+int ao_nf4_linear_route(int64_t M, int64_t N, int64_t K, int block_size, int64_t scaler_block_size, int32_t* out, int cap);
+/* "nf4_stream_kernel" or "not fused": the kernel of that route. */
+const char* ao_nf4_linear_kernel_name(int64_t M, int64_t N, int64_t K, int block_size, int64_t scaler_block_size);
+/* Measurement only (no reference counterpart): 1 forces the stream kernel at any M for the calling thread, 0 restores the route. */
+int ao_nf4_linear_set_form(int form);
+
 #ifdef __cplusplus
 }
 #endif
