@@ -177,7 +177,17 @@ _SIGNATURES = {
     "ao_nf4_linear_route": [_I64, _I64, _I64, _INT, _I64, _P, _INT],
     "ao_nf4_linear_kernel_name": [_I64, _I64, _I64, _INT, _I64],
     "ao_nf4_linear_set_form": [_INT],
+    "ao_optim_quantize": [_P, _INT, _P, _P, _P, _I64, _INT, _INT, _P],
+    "ao_optim_dequantize": [_P, _P, _P, _P, _INT, _I64, _INT, _INT, _P],
+    "ao_optim_adam_step": [_P, _P, _INT, _P, _P, _P, _P, _P, _P, _P, _P, _P, _INT, _I64, _INT, _P, _INT, _INT, _I64, _I64, _I64, _INT, _P],
+    "ao_optim_grid": [_I64, _INT, _P],
 }
+
+
+class OptimScalars(ctypes.Structure):
+    """ao_optim_scalars (include/ao_mi355.h): the fp32 scalars of one optimizer step, passed by value to the kernel."""
+    _fields_ = [(n, ctypes.c_float) for n in ("lr", "lr_wd", "wd", "one_minus_beta1", "one_minus_beta2", "bias_correction1",
+                                              "sqrt_bias_correction2", "eps")]
 
 
 class BackendUnavailable(RuntimeError):

@@ -607,4 +607,87 @@ __device__ __forceinline__ u32x4 nf4_decode8(uint32_t c, float s, const float* t
   return u32x4{o[0], o[1], o[2], o[3]};
 }
 
+// ---- low-bit optimizer states (optim_kernels.hip): torchao/optim's block-quantized Adam moments and its single_param_adam ----------------
+// The reference's EAGER CPU run (adam.py:163-209 on the subclasses of subclass_8bit.py / subclass_4bit.py / subclass_fp8.py, helpers in
+// quant_utils.py) is a fixed sequence of fp32 operations, each rounded ONCE; divisions and sqrt are correctly rounded; subnormals are kept;
+// NaN and Inf are outside the contract.  A tensor is taken flat, in blocks of B elements (a power of two, 64 .. 2048):
+//   tables     four qmaps (8-bit signed / unsigned dynamic maps of 256 entries, the 4-bit signed dynamic map and the 4-bit unsigned
+//              linspace(0, 1, 17)[1:] of 16: no zero, a zero second moment decodes to scale / 16 -- the reference's behaviour, kept).  No kernel
+//              holds a table: each reads the qmap field of the state it is given.
+//   quantize   scale = max(amax |x|, 1e-12);  y = x / scale (a division, not a reciprocal multiply);  the branch-free descent
+//              c += (y >= qmap[c + step]) ? step : 0 over step = 128 .. 1 (8 .. 1 for 4 bits);  then up = min(c + 1, last) and the code is up
+//              iff y - qmap[c] >= (qmap[up] - qmap[c]) * 0.5 (ties go up);  4 bits: element 2i in the HIGH nibble of byte i (not NVFP4's order)
+//   fp8        scale = max(amax |x|, 1e-12) / 448;  code = e4m3fn_rne(x / scale)
+//   dequantize qmap[code] * scale;  fp8: f32(code) * scale
+//   plain      (fewer than 4096 elements, or a count that B does not divide: moments in the parameter's dtype)  read: to fp32;  write: RNE
+//   step       the host passes lr, lr wd, wd, 1 - b1, 1 - b2 (rounded from the Python doubles), bc1 = 1 - b1^t, sqrt(1 - b2^t), eps, computed
+//              with the torch CPU operations the reference runs on its 0-dim tensors:
+//                AdamW  p = p - (lr wd) p          Adam  g = g + wd p
+//                m = lerp(m_old, g, 1 - b1);  v = lerp(v_old, g g, 1 - b2);  amsgrad: vmax = max(vmax_old, v), used below for v
+//                denom = sqrt(v) / sqrt_bc2 + eps;  p = p - (lr (m / bc1)) / denom
+//              m, v, vmax are quantized from the fp32 values the update used; p is stored RNE (or SR below)
+//   lerp       ATen's CPU kernel: |w| < 0.5: fma(w, e - s, s), else fma(w - 1, e - s, e): ONE fused operation, an explicit fmaf here.  The
+//              fixture maker (tests/golden/make_golden_optim.py) compares the reference's recording with the fused and the unfused form:
+//              with betas (0.9, 0.999) the recorded bytes are the fused form's in every case and the unfused form misses some in each of
+//              the 11 cases of 4096 elements or more; with (0.75, 0.9375) the product is exact and both agree.
+//   sqrt       the IEEE one.  ATen's CPU sqrt of a contiguous tensor is MKL's vsSqrt, under an ulp but not correctly rounded (0.6% of
+//              random inputs an ulp off; 7 recorded values of 3 fixture cases), on inputs that depend on the MKL build: the maker records
+//              the reference with aten.sqrt taken through float64, and counts what MKL's root would have changed.
+//   amsgrad    on a quantized state the reference's eager run raises (its subclasses implement no aten.maximum); the maker registers the
+//              dequantizing form its lerp has, which is the line above.  On plain states the reference runs as it is.
+//   SR         (bf16 p; the reference draws torch.randint, not reproducible here: this library's own contract)  away from zero iff
+//              r16 < (bits & 0xFFFF): (bits & 0xFFFF0000) + 0x10000, else the truncation.  Philox4x32-10 (above), key = the halves of the
+//              optimizer's int64 seed, counter = (g_lo, g_hi, step, param_index), g the flat index of the group of 8 consecutive elements;
+//              element j takes bits 16 (j & 1) .. + 15 of output word j >> 1.  The bytes depend on (seed, step, param_index, element) only.
+template <int BITS>
+__device__ __forceinline__ uint32_t optim_table_code(float y, const float* tab) {
+#pragma clang fp contract(off)
+  uint32_t c = 0u;
+#pragma unroll
+  for (uint32_t step = 1u << (BITS - 1); step != 0u; step >>= 1) c += (y >= tab[c + step]) ? step : 0u;
+  const uint32_t up = min(c + 1u, (1u << BITS) - 1u);
+  const float dv = tab[c], uv = tab[up];
+  return (y - dv >= (uv - dv) * 0.5f) ? up : c;
+}
+__device__ __forceinline__ float optim_block_scale(float amax) { return fmaxf(amax, 1e-12f); }
+__device__ __forceinline__ float optim_fp8_scale(float amax) {
+#pragma clang fp contract(off)
+  return fmaxf(amax, 1e-12f) / 448.0f;
+}
+__device__ __forceinline__ float optim_lerp(float s, float e, float w) {
+#pragma clang fp contract(off)
+  const float d = e - s;
+  return (fabsf(w) < 0.5f) ? __builtin_fmaf(w, d, s) : __builtin_fmaf(w - 1.0f, d, e);
+}
+// one element of the step: p, m, v, vmax in and out (fp32); returns nothing the states do not hold
+__device__ __forceinline__ void optim_adam_element(float& p, float g, float& m, float& v, float& vmax, bool has_vmax, bool is_adamw,
+                                                   const ao_optim_scalars& s) {
+#pragma clang fp contract(off)
+  if (is_adamw) {
+    const float d = s.lr_wd * p;
+    p = p - d;
+  } else {
+    const float d = s.wd * p;
+    g = g + d;
+  }
+  m = optim_lerp(m, g, s.one_minus_beta1);
+  const float g2 = g * g;
+  v = optim_lerp(v, g2, s.one_minus_beta2);
+  float den = v;
+  if (has_vmax) {
+    vmax = fmaxf(vmax, v);
+    den = vmax;
+  }
+  const float denom = __builtin_sqrtf(den) / s.sqrt_bias_correction2 + s.eps;
+  const float mh = m / s.bias_correction1;
+  const float num = s.lr * mh;
+  const float upd = num / denom;
+  p = p - upd;
+}
+// fp32 -> bf16 bits under 16 random bits
+__device__ __forceinline__ uint32_t optim_sr_bf16(float x, uint32_t r16) {
+  const uint32_t b = f32_to_bits(x);
+  return ((b & 0xffff0000u) + ((r16 < (b & 0xffffu)) ? 0x10000u : 0u)) >> 16;
+}
+
 }  // namespace ao

@@ -2633,3 +2633,138 @@ def nf4_linear(x2, codes, scalers, factors, mean, n: int, k: int, block_size: in
 
 
 __all__ += ["nf4_block_absmax", "nf4_quantize", "nf4_dequantize", "nf4_linear", "nf4_linear_route", "nf4_linear_kernel_name", "nf4_set_form"]
+
+
+# ---- low-bit optimizers: torchao/optim's state casts and its Adam step (include/ao_mi355.h "Low-bit optimizers") ---------------
+OPTIM_FORMATS = {"Q8_SIGNED": 0, "Q8_UNSIGNED": 1, "Q4_SIGNED": 2, "Q4_UNSIGNED": 3, "FP8": 4, "PLAIN": 5}
+OPTIM_BLOCK_SIZES = (64, 128, 256, 512, 1024, 2048)
+OPTIM_SCALARS = ("lr", "lr_wd", "wd", "one_minus_beta1", "one_minus_beta2", "bias_correction1", "sqrt_bias_correction2", "eps")
+_OPTIM_Q8, _OPTIM_Q4, _OPTIM_FP8, _OPTIM_PLAIN = (0, 1), (2, 3), (4,), (5,)
+
+
+def _optim_format(name, fmt, n, block_size, allowed):
+    """The formats and sizes the kernels take, refused by reason before the library is touched."""
+    if fmt not in allowed:
+        names = ", ".join(k for k, v in OPTIM_FORMATS.items() if v in allowed)
+        raise ValueError(f"{name}: format must be one of {names}, got {fmt}")
+    if fmt in _OPTIM_PLAIN:
+        return
+    if block_size not in OPTIM_BLOCK_SIZES:
+        raise ValueError(f"{name}: block_size must be a power of two from 64 to 2048, got {block_size}")
+    if n % block_size != 0:
+        raise ValueError(f"{name}: numel={n} must be a multiple of block_size={block_size}")
+
+
+def _optim_fields(name, what, codes, scale, qmap, fmt, n, block_size, dev):
+    """One quantized state's fields against its format: contiguous codes (as bytes), fp32 scale [n / block_size], the state's own table."""
+    want = n // 2 if fmt in _OPTIM_Q4 else n
+    ok_dtype = (torch.float8_e4m3fn, torch.uint8) if fmt in _OPTIM_FP8 else (torch.uint8,)
+    if codes.dtype not in ok_dtype or codes.numel() != want or not codes.is_contiguous():
+        raise RuntimeError(f"{name}: {what} codes must be contiguous {ok_dtype[0]} with {want} elements, got {codes.dtype} {tuple(codes.shape)}")
+    if scale is None or scale.dtype != torch.float32 or tuple(scale.shape) != (n // block_size,) or not scale.is_contiguous():
+        raise RuntimeError(f"{name}: {what} scale must be contiguous float32 [numel / block_size] = {(n // block_size,)}")
+    if fmt in _OPTIM_FP8:
+        if qmap is not None:
+            raise RuntimeError(f"{name}: the FP8 format has no qmap")
+    else:
+        entries = 16 if fmt in _OPTIM_Q4 else 256
+        if qmap is None or qmap.dtype != torch.float32 or tuple(qmap.shape) != (entries,) or not qmap.is_contiguous():
+            raise RuntimeError(f"{name}: {what} qmap must be contiguous float32 [{entries}]")
+    for t in (codes, scale, qmap):
+        if t is not None and t.device != dev:
+            raise RuntimeError(f"{name}: {what} fields are on {t.device}, the operands on {dev}")
+
+
+def optim_grid(n: int, max_workgroups: int = 0) -> dict:
+    """The grid rule of the optimizer kernels (ao_optim_grid, host logic only): elements a workgroup takes per trip of its loop, trips in
+    all, workgroups launched."""
+    out = (ctypes.c_int64 * 3)()
+    _lib.check(_lib.lib().ao_optim_grid(int(n), int(max_workgroups), out))
+    return {"tile": out[0], "tiles": out[1], "workgroups": out[2]}
+
+
+def optim_quantize(src: torch.Tensor, format: int, block_size: int, qmap: Optional[torch.Tensor] = None, codes=None, scale=None):
+    """The subclasses' copy_ from a float tensor (subclass_8bit.py:137-141, subclass_4bit.py:155-159, subclass_fp8.py:115-118) in one
+    launch, the reference's bytes: src fp32 or bf16 (any shape, taken flat) -> (codes, scale); written into `codes` / `scale` when given."""
+    name = "optim_quantize"
+    if src.dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError(f"{name}: src must be float32 or bfloat16, got {src.dtype}")
+    n = src.numel()
+    _optim_format(name, format, n, block_size, _OPTIM_Q8 + _OPTIM_Q4 + _OPTIM_FP8)
+    dev = _require_gpu(name, src, qmap, codes, scale)
+    src = src.contiguous()
+    if codes is None:
+        codes = torch.empty((n // 2,) if format in _OPTIM_Q4 else tuple(src.shape), dtype=torch.float8_e4m3fn if format in _OPTIM_FP8 else torch.uint8,
+                            device=dev)
+    if scale is None:
+        scale = torch.empty((n // block_size,), dtype=torch.float32, device=dev)
+    _optim_fields(name, "the", codes, scale, qmap, format, n, block_size, dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_optim_quantize(_ptr(src), int(src.dtype == torch.bfloat16), _ptr(codes), _ptr(scale), _ptr(qmap), n, block_size,
+                                                format, _stream()))
+    return codes, scale
+
+
+def optim_dequantize(codes, scale, format: int, block_size: int, qmap: Optional[torch.Tensor] = None, dtype=torch.float32) -> torch.Tensor:
+    """dequantize() of the three state subclasses in one launch, flat: -> fp32 [numel] (or that rounded to bf16)."""
+    name = "optim_dequantize"
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError(f"{name}: dtype must be float32 or bfloat16, got {dtype}")
+    n = codes.numel() * (2 if format in _OPTIM_Q4 else 1)
+    _optim_format(name, format, n, block_size, _OPTIM_Q8 + _OPTIM_Q4 + _OPTIM_FP8)
+    dev = _require_gpu(name, codes, scale, qmap)
+    _optim_fields(name, "the", codes, scale, qmap, format, n, block_size, dev)
+    out = torch.empty((n,), dtype=dtype, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_optim_dequantize(_ptr(codes), _ptr(scale), _ptr(qmap), _ptr(out), int(dtype == torch.bfloat16), n, block_size,
+                                                  format, _stream()))
+    return out
+
+
+def optim_adam_step(p, grad, m_codes, m_scale, m_qmap, v_codes, v_scale, v_qmap, vmax_codes, vmax_scale, vmax_qmap, format: int,
+                    block_size: int, scalars, is_adamw: bool, sr: bool = False, seed: int = 0, step: int = 0, param_index: int = 0,
+                    max_workgroups: int = 0) -> None:
+    """single_param_adam (torchao/optim/adam.py:163-209) for one parameter in ONE launch, the bytes of the reference's eager CPU run: p (bf16
+    or fp32, contiguous) and the moments' codes and scales are updated in place.  format: Q8_SIGNED / Q4_SIGNED / FP8 (the first moment's),
+    or PLAIN, where m_codes / v_codes / vmax_codes are the moments themselves in p's dtype.  vmax_codes None: no amsgrad.  scalars: the eight
+    fp32 values of OPTIM_SCALARS for this step (ao_amd.optim.adam.step_scalars).  sr: stochastic rounding of a bf16 p from (seed, step,
+    param_index, element).  max_workgroups caps the grid (0: the default); the bytes do not depend on it."""
+    name = "optim_adam_step"
+    if p.dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError(f"{name}: p must be float32 or bfloat16, got {p.dtype}")
+    if grad.dtype != p.dtype:
+        raise RuntimeError(f"{name}: grad must have p's dtype {p.dtype}, got {grad.dtype}")
+    if grad.shape != p.shape:
+        raise RuntimeError(f"{name}: grad {tuple(grad.shape)} must have p's shape {tuple(p.shape)}")
+    if not p.is_contiguous():
+        raise RuntimeError(f"{name}: p is updated in place and must be contiguous")
+    if sr and p.dtype != torch.bfloat16:
+        raise RuntimeError(f"{name}: stochastic rounding is for bfloat16 parameters, got {p.dtype}")
+    if len(scalars) != len(OPTIM_SCALARS):
+        raise ValueError(f"{name}: scalars must hold {len(OPTIM_SCALARS)} values ({', '.join(OPTIM_SCALARS)}), got {len(scalars)}")
+    n = p.numel()
+    _optim_format(name, format, n, block_size, (0, 2, 4, 5))
+    dev = _require_gpu(name, p, grad, m_codes, v_codes, vmax_codes)
+    grad = grad.contiguous()
+    states = [("exp_avg", m_codes, m_scale, m_qmap, format), ("exp_avg_sq", v_codes, v_scale, v_qmap, format + (1 if format in (0, 2) else 0))]
+    if vmax_codes is not None:
+        states.append(("max_exp_avg_sq", vmax_codes, vmax_scale, vmax_qmap, states[1][4]))
+    for what, codes, scale, qmap, fmt in states:
+        if format in _OPTIM_PLAIN:
+            if codes.dtype != p.dtype or codes.numel() != n or not codes.is_contiguous() or codes.device != dev:
+                raise RuntimeError(f"{name}: a plain {what} must be contiguous {p.dtype} with p's {n} elements on {dev}")
+            if scale is not None or qmap is not None:
+                raise RuntimeError(f"{name}: a plain {what} has no scale and no qmap")
+        else:
+            _optim_fields(name, what, codes, scale, qmap, fmt, n, block_size, dev)
+    s = _lib.OptimScalars(*[float(x) for x in scalars])
+    seed = int(seed) & (2 ** 64 - 1)  # torch.initial_seed() is unsigned; the entry takes the same 64 bits as an int64
+    seed -= 2 ** 64 if seed >= 2 ** 63 else 0
+    with _on(dev):
+        _lib.check(_lib.lib().ao_optim_adam_step(
+            _ptr(p), _ptr(grad), int(p.dtype == torch.bfloat16), _ptr(m_codes), _ptr(m_scale), _ptr(m_qmap), _ptr(v_codes), _ptr(v_scale),
+            _ptr(v_qmap), _ptr(vmax_codes), _ptr(vmax_scale), _ptr(vmax_qmap), format, n, block_size if format not in _OPTIM_PLAIN else 0,
+            ctypes.byref(s), int(bool(is_adamw)), int(bool(sr)), int(seed), int(step), int(param_index), int(max_workgroups), _stream()))
+
+
+__all__ += ["optim_grid", "optim_quantize", "optim_dequantize", "optim_adam_step", "OPTIM_FORMATS", "OPTIM_BLOCK_SIZES", "OPTIM_SCALARS"]

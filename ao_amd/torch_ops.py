@@ -595,4 +595,41 @@ for _name in ("nf4_block_absmax", "nf4_quantize", "nf4_dequantize", "nf4_linear"
     _lib_autograd.impl(_name, torch.library.fallthrough_kernel)
 
 
+# ---- low-bit optimizers (ops.py "low-bit optimizers"): the two casts and the in-place step ----------------------------------
+# (the (x!) annotations are the schema form of mutates_args: p and every moment's codes and scale are written in place)
+_lib_def.define("optim_quantize(Tensor src, int format, int block_size, Tensor? qmap) -> (Tensor, Tensor)")
+_lib_def.define("optim_dequantize(Tensor codes, Tensor scale, int format, int block_size, Tensor? qmap, ScalarType dtype) -> Tensor")
+_lib_def.define("optim_adam_step(Tensor(a!) p, Tensor grad, Tensor(b!) m_codes, Tensor(c!)? m_scale, Tensor? m_qmap, Tensor(d!) v_codes, "
+                "Tensor(e!)? v_scale, Tensor? v_qmap, Tensor(f!)? vmax_codes, Tensor(g!)? vmax_scale, Tensor? vmax_qmap, int format, int block_size, "
+                "float[] scalars, bool is_adamw, bool sr, int seed, int step, int param_index, int max_workgroups) -> ()")
+_lib_impl.impl("optim_quantize", lambda src, format, block_size, qmap: ops.optim_quantize(src, format, block_size, qmap))
+_lib_impl.impl("optim_dequantize", lambda codes, scale, format, block_size, qmap, dtype: ops.optim_dequantize(codes, scale, format, block_size, qmap, dtype))
+_lib_impl.impl("optim_adam_step", ops.optim_adam_step)
+
+
+@torch.library.register_fake("ao_mi355::optim_quantize")
+def _(src, format, block_size, qmap):
+    n = src.numel()
+    if format in (2, 3):
+        codes = src.new_empty((n // 2,), dtype=torch.uint8)
+    else:
+        codes = src.new_empty(src.shape, dtype=torch.float8_e4m3fn if format == 4 else torch.uint8)
+    return codes, src.new_empty((n // block_size,), dtype=torch.float32)
+
+
+@torch.library.register_fake("ao_mi355::optim_dequantize")
+def _(codes, scale, format, block_size, qmap, dtype):
+    return codes.new_empty((codes.numel() * (2 if format in (2, 3) else 1),), dtype=dtype)
+
+
+@torch.library.register_fake("ao_mi355::optim_adam_step")
+def _(p, grad, m_codes, m_scale, m_qmap, v_codes, v_scale, v_qmap, vmax_codes, vmax_scale, vmax_qmap, format, block_size, scalars, is_adamw, sr,
+      seed, step, param_index, max_workgroups):
+    return None
+
+
+for _name in ("optim_quantize", "optim_dequantize", "optim_adam_step"):
+    _lib_autograd.impl(_name, torch.library.fallthrough_kernel)
+
+
 load_ops_library()

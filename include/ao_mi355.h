@@ -1068,6 +1068,51 @@ const char* ao_nf4_linear_kernel_name(int64_t M, int64_t N, int64_t K, int block
 /* Measurement only (no reference counterpart): 1 forces the stream kernel at any M for the calling thread, 0 restores the route. */
 int ao_nf4_linear_set_form(int form);
 
+/* ---- Low-bit optimizers: torchao/optim's block-quantized Adam moments and its single_param_adam (adam.py:163-209) ---------------------------
+ * A state is taken flat in blocks of block_size elements (a power of two, 64 .. 2048, n a multiple of it): codes (uint8 one an element;
+ * 4-bit: two a byte, element 2i in the high nibble; fp8: e4m3fn bytes), scale fp32 [n / block_size], and for the table formats the state's
+ * own qmap (fp32 [256] or [16], on the device: no kernel holds a table).  The arithmetic is stated once, in csrc/quant_math.h ("low-bit
+ * optimizer states"), and gives the bytes of the reference's eager CPU run.  Data pointers 16-byte aligned.  No allocation, no
+ * synchronisation; anything else is rejected on the host before any launch. */
+enum {
+  AO_OPTIM_Q8_SIGNED = 0,
+  AO_OPTIM_Q8_UNSIGNED = 1,
+  AO_OPTIM_Q4_SIGNED = 2,
+  AO_OPTIM_Q4_UNSIGNED = 3,
+  AO_OPTIM_FP8 = 4,
+  AO_OPTIM_PLAIN = 5 /* ao_optim_adam_step only: moments in the parameter's dtype, any n */
+};
+/* The scalars of one step, computed on the host with the torch CPU operations the reference runs on its 0-dim tensors. */
+typedef struct {
+  float lr;
+  float lr_wd;                 /* lr * weight_decay */
+  float wd;
+  float one_minus_beta1;       /* fp32(1 - beta1), the Python double rounded */
+  float one_minus_beta2;
+  float bias_correction1;      /* 1 - beta1^step */
+  float sqrt_bias_correction2; /* sqrt(1 - beta2^step) */
+  float eps;
+} ao_optim_scalars;
+/* Replaces the subclasses' copy_ from a float tensor (subclass_8bit.py:137-141, subclass_4bit.py:155-159, subclass_fp8.py:115-118): src
+ * fp32 or bf16 [n] -> codes, scale.  The signed and the unsigned format of a width differ in the qmap alone (null for fp8). */
+int ao_optim_quantize(const void* src, int src_bf16, void* codes, float* scale, const float* qmap, int64_t n, int block_size, int format,
+                      void* stream);
+/* Replaces dequantize() (subclass_8bit.py:97-101, subclass_4bit.py:107-112, subclass_fp8.py:77-83): dst fp32 [n], or that rounded to bf16. */
+int ao_optim_dequantize(const void* codes, const float* scale, const float* qmap, void* dst, int dst_bf16, int64_t n, int block_size,
+                        int format, void* stream);
+/* Replaces single_param_adam for ONE parameter in ONE launch: p and grad [n] of one dtype (bf16 or fp32), updated in place with the moments'
+ * codes and scales.  format: the first moment's (AO_OPTIM_Q8_SIGNED, AO_OPTIM_Q4_SIGNED, AO_OPTIM_FP8) or AO_OPTIM_PLAIN, where m_codes /
+ * v_codes / vmax_codes are the moments themselves in p's dtype and scales and qmaps are null.  vmax_codes null: no amsgrad.  sr != 0 (bf16 p
+ * only): p is rounded stochastically from (seed, step, param_index, element).  max_workgroups > 0 caps the grid (0: the default of
+ * ao_optim_grid); the bytes never depend on it.  The scalars go by value and change every step: a captured launch would replay stale ones. */
+int ao_optim_adam_step(void* p, const void* grad, int bf16, void* m_codes, float* m_scale, const float* m_qmap, void* v_codes, float* v_scale,
+                       const float* v_qmap, void* vmax_codes, float* vmax_scale, const float* vmax_qmap, int format, int64_t n, int block_size,
+                       const ao_optim_scalars* scalars, int is_adamw, int sr, int64_t seed, int64_t step, int64_t param_index,
+                       int max_workgroups, void* stream);
+/* The grid rule of the three entries above (host logic only): out[0] = elements a workgroup takes per trip of its loop (a multiple of every
+ * block size), out[1] = trips in all (tiles), out[2] = workgroups launched = min(tiles, max_workgroups or the default cap). */
+int ao_optim_grid(int64_t n, int max_workgroups, int64_t* out);
+
 #ifdef __cplusplus
 }
 #endif
