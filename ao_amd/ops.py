@@ -2768,3 +2768,68 @@ def optim_adam_step(p, grad, m_codes, m_scale, m_qmap, v_codes, v_scale, v_qmap,
 
 
 __all__ += ["optim_grid", "optim_quantize", "optim_dequantize", "optim_adam_step", "OPTIM_FORMATS", "OPTIM_BLOCK_SIZES", "OPTIM_SCALARS"]
+
+
+# ---------------------------------------------------------------------------
+# GPTQ: one block of the column loop in one launch
+# ---------------------------------------------------------------------------
+GPTQ_INT4, GPTQ_INT8, GPTQ_NVFP4 = 0, 1, 2
+GPTQ_MAX_BLOCK = 256
+
+
+def gptq_block(W: torch.Tensor, Hinv: torch.Tensor, k0: int, block_cols: int, format: int, qdata: torch.Tensor, *, group_size: int = 0,
+               scale: Optional[torch.Tensor] = None, zero_point: Optional[torch.Tensor] = None, row_scale: Optional[torch.Tensor] = None,
+               per_tensor_scale: Optional[torch.Tensor] = None, err: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The column loop of gptq_quantize (prototype/gptq/api.py:446-532) over the GPTQ block of columns [k0, k0 + block_cols), and the final
+    codes of those columns (:537-569), in one launch (csrc/gptq_kernels.hip states the arithmetic).  In place: W (bf16 or fp32 [N, K],
+    contiguous) is updated in the block's columns; the block's part of the outputs is written -- qdata (GPTQ_INT4 / GPTQ_NVFP4: uint8
+    [N, K/2], even k in the low nibble; GPTQ_INT8: int8 [N, K]), GPTQ_INT4: scale / zero_point [K/g, N] in W's dtype, GPTQ_NVFP4: scale
+    float8_e4m3fn [N, K/16] under per_tensor_scale (one fp32 on the device), GPTQ_INT8: under row_scale (fp32 [N], given).  Hinv: fp32
+    [K, K], the upper Cholesky factor of the inverse Hessian.  Returns Err, fp32 [N, block_cols]: what the lazy batch update multiplies."""
+    name = "gptq_block"
+    dev = _require_gpu(name, W, Hinv, qdata, scale, zero_point, row_scale, per_tensor_scale, err)
+    if W.dtype not in (torch.bfloat16, torch.float32):
+        raise NotImplementedError(f"{name}: weights are bfloat16 or float32, got {W.dtype}")
+    if W.dim() != 2 or not W.is_contiguous():
+        raise RuntimeError(f"{name}: W must be a contiguous 2-D tensor (it is updated in place)")
+    n, k = W.shape
+    if Hinv.dtype != torch.float32 or tuple(Hinv.shape) != (k, k) or not Hinv.is_contiguous():
+        raise RuntimeError(f"{name}: Hinv must be a contiguous float32 [{k}, {k}] tensor")
+    if block_cols > GPTQ_MAX_BLOCK:
+        raise ValueError(f"{name}: a GPTQ block holds at most {GPTQ_MAX_BLOCK} columns (its tile of W and Err stay in LDS), got {block_cols}")
+
+    def field(what, t, dtypes, shape):
+        if t is None or t.dtype not in dtypes or tuple(t.shape) != shape or not t.is_contiguous():
+            raise RuntimeError(f"{name}: {what} must be a contiguous {' / '.join(str(d) for d in dtypes)} tensor of shape {shape}")
+        return t
+
+    aux = None
+    if format == GPTQ_INT4:
+        field("qdata", qdata, (torch.uint8,), (n, k // 2))
+        if group_size <= 0 or k % group_size != 0:
+            raise ValueError(f"{name}: group_size {group_size} must divide K={k}")
+        field("scale", scale, (W.dtype,), (k // group_size, n))
+        field("zero_point", zero_point, (W.dtype,), (k // group_size, n))
+    elif format == GPTQ_NVFP4:
+        group_size = 16
+        field("qdata", qdata, (torch.uint8,), (n, k // 2))
+        field("scale", scale, (torch.float8_e4m3fn, torch.uint8), (n, k // 16))
+        aux = _nvfp4_scalar(name, "per_tensor_scale", per_tensor_scale, dev)
+        if aux is None:
+            raise RuntimeError(f"{name}: NVFP4 needs the per-tensor scale")
+    elif format == GPTQ_INT8:
+        field("qdata", qdata, (torch.int8,), (n, k))
+        aux = field("row_scale", None if row_scale is None else row_scale.reshape(-1), (torch.float32,), (n,))
+    else:
+        raise ValueError(f"{name}: unknown format {format}")
+    if err is None:
+        err = torch.empty((n, block_cols), dtype=torch.float32, device=dev)
+    else:
+        field("err", err, (torch.float32,), (n, block_cols))
+    with _on(dev):
+        _lib.check(_lib.lib().ao_gptq_block(_ptr(W), int(W.dtype == torch.bfloat16), _ptr(Hinv), _ptr(err), format, group_size, _ptr(qdata),
+                                            _ptr(scale), _ptr(zero_point), _ptr(aux), n, k, int(k0), int(block_cols), _stream()))
+    return err
+
+
+__all__ += ["gptq_block", "GPTQ_INT4", "GPTQ_INT8", "GPTQ_NVFP4", "GPTQ_MAX_BLOCK"]

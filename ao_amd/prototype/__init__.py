@@ -13,6 +13,7 @@ from .fp8_grouped_training import (  # noqa: F401
     _Float8GroupedMM,
     _to_fp8_rowwise_then_scaled_grouped_mm,
 )
+from .gptq import GPTQConfig, GPTQObserverTensor, gptq_quantize  # noqa: F401
 from .mx_training import (  # noqa: F401
     MXFP8Linear,
     MXFP8TrainingOpConfig,

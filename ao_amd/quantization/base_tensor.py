@@ -16,6 +16,7 @@ class LowBitTensorBase(torch.Tensor):
     tensor_data_names: List[str] = []
     tensor_attribute_names: List[str] = []
     optional_tensor_data_names: List[str] = []
+    _quantized_weight = True  # False on wrappers that only observe a high-precision weight (quantize_'s default filter reads it)
 
     _ATEN_TABLE: Dict[Any, Callable]
     _TORCH_FN_TABLE: Dict[Any, Callable]

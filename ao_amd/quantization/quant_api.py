@@ -44,7 +44,8 @@ def _is_linear(mod, *args):
     return (
         isinstance(mod, nn.Linear)
         and hasattr(mod, "weight")
-        and not isinstance(mod.weight, LowBitTensorBase)
+        # (a weight under observation -- GPTQObserverTensor, _quantized_weight False -- is still to be quantized)
+        and not (isinstance(mod.weight, LowBitTensorBase) and mod.weight._quantized_weight)
     )
 
 

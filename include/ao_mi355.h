@@ -1113,6 +1113,26 @@ int ao_optim_adam_step(void* p, const void* grad, int bf16, void* m_codes, float
  * block size), out[1] = trips in all (tiles), out[2] = workgroups launched = min(tiles, max_workgroups or the default cap). */
 int ao_optim_grid(int64_t n, int max_workgroups, int64_t* out);
 
+/* ---- GPTQ (torchao/prototype/gptq) ------------------------------------------------------------------------------------------------------------
+ * Replaces the column loop of gptq_quantize for ONE GPTQ block (prototype/gptq/api.py:446-532: per column a dozen eager launches on [N, 1]
+ * slices) and the final re-quantization of that block's columns (:537-569), in ONE launch.  The arithmetic is stated once, at the head of
+ * csrc/gptq_kernels.hip: every step one fp32 operation rounded once, no fma, IEEE division, rint to even; bf16 weights round at every update.
+ *   W       [N][K] bf16 (w_bf16 != 0) or fp32, updated IN PLACE in columns [k0, k0 + block_cols)
+ *   Hinv    fp32 [K][K], the upper Cholesky factor api.py:400-403 calls Hinv; rows and columns [k0, k0 + block_cols) are read; 16-byte aligned
+ *   Err     fp32 [N][block_cols], written: err of every column, the operand of the host's lazy batch update (:530-532)
+ *   AO_GPTQ_INT4   (_int4_row_quantize_zp_precomputed_qparams / _int4_row_dequantize_zp, api.py:167-221; group_size 32 | 64 | 128 | 256)
+ *                  qdata uint8 [N][K/2], even k in the low nibble; scale / zero_point [K/g][N] in W's dtype (rounded on store; fp32 inside
+ *                  the loop: PARITY UNPINNED, mslk is un-vendored); aux unused
+ *   AO_GPTQ_NVFP4  (_nvfp4_with_precalculated_scales_qdq / _q, api.py:224-274; nvfp4_quantize's block scales, nvfp4_tensor.py:772-854)
+ *                  qdata uint8 [N][K/2], scale e4m3 bytes [N][K/16] row-major, aux = the fp32 per-tensor scale (one element, on the device),
+ *                  group_size 16; zero_point unused
+ *   AO_GPTQ_INT8   (Int8Tensor.from_hp(scale=) + dequantize(float), int8_tensor.py:176-259) qdata int8 [N][K], aux = fp32 [N] row scales
+ *                  (given, not measured: see DESIGN.md for the deviation from api.py:471-478); scale, zero_point and group_size unused
+ * block_cols <= 256 (the block's tile of W and Err stay in LDS), a multiple of 16 and of the group size, as are k0 and K; any N. */
+enum { AO_GPTQ_INT4 = 0, AO_GPTQ_INT8 = 1, AO_GPTQ_NVFP4 = 2 };
+int ao_gptq_block(void* W, int w_bf16, const float* Hinv, float* Err, int format, int group_size, void* qdata, void* scale, void* zero_point,
+                  const float* aux, int64_t N, int64_t K, int64_t k0, int64_t block_cols, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
