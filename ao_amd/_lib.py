@@ -182,6 +182,7 @@ _SIGNATURES = {
     "ao_optim_adam_step": [_P, _P, _INT, _P, _P, _P, _P, _P, _P, _P, _P, _P, _INT, _I64, _INT, _P, _INT, _INT, _I64, _I64, _I64, _INT, _P],
     "ao_optim_grid": [_I64, _INT, _P],
     "ao_gptq_block": [_P, _INT, _P, _P, _INT, _INT, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P],
+    "ao_awq_scaled_error": [_P, _P, _P, _I64, _I64, _I64, _INT, _P],
 }
 
 

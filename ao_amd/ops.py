@@ -2833,3 +2833,40 @@ def gptq_block(W: torch.Tensor, Hinv: torch.Tensor, k0: int, block_cols: int, fo
 
 
 __all__ += ["gptq_block", "GPTQ_INT4", "GPTQ_INT8", "GPTQ_NVFP4", "GPTQ_MAX_BLOCK"]
+
+
+# ---------------------------------------------------------------------------
+# AWQ: the error matrices of R candidate scale vectors in one launch
+# ---------------------------------------------------------------------------
+AWQ_GROUP_SIZES = (32, 64, 128, 256)
+
+
+def awq_scaled_error(W: torch.Tensor, S: torch.Tensor, group_size: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The weight's side of AWQObserver.calculate_qparams' search (prototype/awq/core.py:70-86) for the R candidate scale vectors S at
+    once (csrc/awq_kernels.hip states the arithmetic).  W bf16 [N, K]; S bf16 [R, K], finite and positive; returns D fp32 [R, N, K] with
+    D[r] = W - Int4Tensor.from_hp(W * S[r], [1, group_size]).dequantize() / S[r], every step one fp32 operation rounded once, so that the
+    reference's loss of ratio r is tr(D[r] G D[r]^T) / (rows N) with G = X^T X.  out: an exact-size contiguous fp32 buffer to write into."""
+    name = "awq_scaled_error"
+    dev = _require_gpu(name, W, S, out)
+    if W.dtype != torch.bfloat16 or S.dtype != torch.bfloat16:
+        raise NotImplementedError(f"{name}: W and S are bfloat16, got {W.dtype} and {S.dtype}")
+    if W.dim() != 2 or not W.is_contiguous():
+        raise RuntimeError(f"{name}: W must be a contiguous 2-D tensor [N, K], got shape {tuple(W.shape)}")
+    n, k = W.shape
+    if S.dim() != 2 or S.shape[1] != k or not S.is_contiguous():
+        raise RuntimeError(f"{name}: S must be a contiguous [R, {k}] tensor, got shape {tuple(S.shape)}")
+    r = S.shape[0]
+    if group_size not in AWQ_GROUP_SIZES:
+        raise ValueError(f"{name}: group_size must be one of 32, 64, 128, 256, got {group_size}")
+    if k == 0 or k % group_size != 0:
+        raise ValueError(f"{name}: K={k} must be a multiple of group_size={group_size}")
+    if out is None:
+        out = torch.empty((r, n, k), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (r, n, k) or not out.is_contiguous():
+        raise RuntimeError(f"{name}: out must be a contiguous float32 tensor of shape {(r, n, k)}")
+    with _on(dev):
+        _lib.check(_lib.lib().ao_awq_scaled_error(_ptr(W), _ptr(S), _ptr(out), n, k, r, group_size, _stream()))
+    return out
+
+
+__all__ += ["awq_scaled_error", "AWQ_GROUP_SIZES"]

@@ -1,4 +1,5 @@
 """Prototype-namespace mirrors (torchao/prototype/*) that sit on the SURVEY.md section 8 path."""
+from .awq import AWQConfig, AWQObservedLinear, AWQObserver  # noqa: F401
 from .blockwise_fp8 import Float8BlockwiseExpertWeights, fp8_blockwise_grouped_mm  # noqa: F401
 from .blockwise_fp8_grouped_training import (  # noqa: F401
     _Float8BlockwiseGroupedMM,
@@ -47,4 +48,4 @@ __all__ = ["Float8BlockwiseExpertWeights", "fp8_blockwise_grouped_mm", "NVFP4Ten
            "Float8BlockwiseLinearConfig", "_Float8BlockwiseGroupedMM", "_to_fp8_blockwise_then_scaled_grouped_mm",
            "_to_fp8_blockwise_then_emulated_scaled_grouped_mm",
            "NVFP4Linear", "NVFP4TrainingConfig", "nvfp4_linear", "DEFAULT_SIGN_VECTOR", "get_wgrad_sign_vector",
-           "NF4WeightOnlyConfig", "nf4_weight_only"]
+           "NF4WeightOnlyConfig", "nf4_weight_only", "AWQConfig", "AWQObserver", "AWQObservedLinear"]

@@ -45,6 +45,7 @@ class QuantizationStep(str, enum.Enum):
     """reference quantize_/common/quantization_step.py"""
     PREPARE = "prepare"
     CONVERT = "convert"
+    PREPARE_FOR_LOADING = "prepare_for_loading"
 
 
 @dataclass

@@ -1133,6 +1133,20 @@ enum { AO_GPTQ_INT4 = 0, AO_GPTQ_INT8 = 1, AO_GPTQ_NVFP4 = 2 };
 int ao_gptq_block(void* W, int w_bf16, const float* Hinv, float* Err, int format, int group_size, void* qdata, void* scale, void* zero_point,
                   const float* aux, int64_t N, int64_t K, int64_t k0, int64_t block_cols, void* stream);
 
+/* ---- AWQ (torchao/prototype/awq) --------------------------------------------------------------------------------------------------------------
+ * The weight's side of AWQObserver.calculate_qparams' search loop (prototype/awq/core.py:70-86: per ratio a scaled weight, the whole int4
+ * quantize_ handler and two F.linear over every calibration token), for R candidate scale vectors in ONE launch that reads W once.  Per
+ * ratio r, row n and group of group_size columns, every step one fp32 operation rounded once, no fma, IEEE division, rint to even:
+ *   ws = bf16(W[n][k] * S[r][k]);  M, m = max, min of ws over the group;  s = max(M - m, 1e-6) / 15;  z = m + 8 s
+ *   q  = clamp(rint((ws - m) / s), 0, 15) - 8                          (the codes of ao_int4_plain_quantize)
+ *   dq = bf16(f32(bf16(q * f32(bf16(s)))) + f32(bf16(z)))              (Int4Tensor.from_hp(W * S[r]).dequantize(), byte for byte)
+ *   D[r][n][k] = f32(W[n][k]) - f32(dq) / f32(S[r][k])
+ * so that the reference's loss mean((X W^T - (X / S[r]) Wq^T)^2) is tr(D[r] G D[r]^T) / (rows N) with G = X^T X (the host's matmul).
+ *   W bf16 [N][K];  S bf16 [R][K], every entry finite and > 0;  D fp32 [R][N][K], exactly that size;  all 16-byte aligned.
+ * group_size in {32, 64, 128, 256}, K % group_size == 0 (K % 128 is NOT required); any N and R; N == 0 or R == 0 launches nothing.  No LDS,
+ * no atomics: the same bytes every launch.  No allocation, no synchronisation: capturable in a graph. */
+int ao_awq_scaled_error(const uint16_t* W, const uint16_t* S, float* D, int64_t N, int64_t K, int64_t R, int group_size, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
