@@ -183,6 +183,11 @@ _SIGNATURES = {
     "ao_optim_grid": [_I64, _INT, _P],
     "ao_gptq_block": [_P, _INT, _P, _P, _INT, _INT, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P],
     "ao_awq_scaled_error": [_P, _P, _P, _I64, _I64, _I64, _INT, _P],
+    "ao_sq_col_absmax_update": [_P, _P, _I64, _I64, _P],
+    "ao_sq_smoothed_amax_update": [_P, _P, _P, _I64, _I64, _P],
+    "ao_int8_quantize_rowwise_prescaled": [_P, _P, _P, _P, _I64, _I64, _P],
+    "ao_int8_quantize_tensorwise_prescaled": [_P, _P, _P, _P, _P, _I64, _I64, _P],
+    "ao_int8_quantize_static_prescaled": [_P, _P, _P, _P, _INT, _P, _I64, _I64, _P],
 }
 
 

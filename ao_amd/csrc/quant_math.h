@@ -55,6 +55,18 @@ __device__ __forceinline__ u32x2 int8_quant8_zp(const u32x4& v, float inv, float
   return u32x2{out[0], out[1]};
 }
 
+// an activation pre-scale (AWQ / SmoothQuant: `x * act_pre_scale`, a bf16 tensor op) folded into a cast: 8 bf16 x 8 bf16 -> 8 bf16,
+// t = bf16_rne(f32(x) * f32(pre)).  Two 8-bit significands give a product of 16 bits, exact in fp32, so the rounding to bf16 is the only
+// one, as in torch's bf16 multiply (fp32 opmath, one conversion).  The casts above then run on t as they do on x (smoothquant_kernels.hip).
+__device__ __forceinline__ u32x4 prescale8(const u32x4& x, const u32x4& pre) {
+  const uint32_t a[4] = {x.x, x.y, x.z, x.w}, b[4] = {pre.x, pre.y, pre.z, pre.w};
+  uint32_t t[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    t[j] = pack_bf16x2(mul_f32_rn(bf16_lo_to_f32(a[j]), bf16_lo_to_f32(b[j])), mul_f32_rn(bf16_hi_to_f32(a[j]), bf16_hi_to_f32(b[j])));
+  return u32x4{t[0], t[1], t[2], t[3]};
+}
+
 __device__ __forceinline__ float fp8_row_scale(float amax) { return round_bf16(amax / 448.0f); }
 __device__ __forceinline__ uint32_t cvt4_e4m3(float a, float b, float c, float d) {
   uint32_t r = 0;

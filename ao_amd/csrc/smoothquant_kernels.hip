@@ -1,0 +1,325 @@
+// SmoothQuant for gfx950: the two calibration reductions and the int8 activation casts with the smoothing pre-scale folded in.
+//
+// Reference (torchao 0.19.0 snapshot): prototype/smoothquant/core.py:41-75 (x_abs_max, w_abs_max, the amax of example_input / smoothing_factor),
+// :162-206 (the running observer's two passes), and the Int8Tensor linear's `x * act_pre_scale` followed by the activation cast
+// (quantize_/workflows/int8/int8_tensor.py:266-300).  All five kernels are bandwidth-bound streams of 16-byte loads.
+//
+//   A  ao_sq_col_absmax_update      state[k] = max(state[k], max_m |x[m,k]|)                    fp32 [K], in place
+//   B  ao_sq_smoothed_amax_update   amax     = max(amax, max_mk |bf16(f32(x[m,k]) / f32(s[k]))|)  fp32 [1], in place
+//   C  ao_int8_quantize_{rowwise,tensorwise,static}_prescaled: the casts of quant_kernels.hip fed t = bf16(f32(x) * f32(pre[k])) (prescale8,
+//      quant_math.h) instead of x, so the bf16 product is never written to memory: byte for byte the twin run on `x * pre`.
+//
+// A and B fold into their state with atomicMax on the BIT PATTERN: a non-negative float's bits order as unsigned integers, every operand is
+// non-negative (|.| clears the sign, so -0.0 counts as 0) and max is exact, so the result does not depend on the order in which workgroups
+// arrive: two launches give the same bytes.  The state must hold non-negative floats (zeros before the first update).  NaN and Inf inputs are
+// outside the contract, as in the casts.
+//
+// A: a workgroup owns 512 columns (64 lanes x one 16-byte slice) and a range of rows; its four waves take different rows, four rows in flight
+// each, and a lane keeps the eight running maxima of its slice as packed bf16 bit patterns (v_pk_max_u16 on |x|: the same ordering argument).
+// The waves meet in LDS, then thread t owns columns t and t + 256 of the tile, so that every atomic wave-instruction covers 256 contiguous
+// bytes of `state` (the shape the memory-side atomics run fastest at); zeros are not sent.  The row range is split so that about 2048
+// workgroups exist however small K / 512 is.
+// B: a thread owns one 16-byte column slice, keeps its eight divisors in registers and walks rows; IEEE division (hipcc's default for fp32
+// `/`, no fast reciprocal), one rounding to bf16, a block reduction and ONE atomic per workgroup.
+#include <algorithm>
+
+#include "common.h"
+#include "quant_math.h"
+
+namespace ao {
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kColTile = 512;     // kernel A: columns per workgroup
+constexpr int kRowsInFlight = 4;  // kernel A: rows a wave has in flight
+constexpr int64_t kTargetBlocks = 2048;  // 8 per CU
+
+typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ uint32_t pk_max_u16(uint32_t a, uint32_t b) {
+  return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
+}
+
+// running packed |bf16| maxima of a 16-byte slice
+__device__ __forceinline__ void absmax8_update(u32x4& m, const u32x4& v) {
+  m.x = pk_max_u16(m.x, v.x & 0x7fff7fffu);
+  m.y = pk_max_u16(m.y, v.y & 0x7fff7fffu);
+  m.z = pk_max_u16(m.z, v.z & 0x7fff7fffu);
+  m.w = pk_max_u16(m.w, v.w & 0x7fff7fffu);
+}
+
+__device__ __forceinline__ float block_max(float v, float* red) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) red[wave] = v;
+  __syncthreads();
+  v = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  __syncthreads();
+  return v;
+}
+
+// ---- A: running per-column absmax ------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void sq_col_absmax_kernel(const uint16_t* __restrict__ x, uint32_t* __restrict__ state, int64_t M, int64_t K,
+                                                                 int64_t rows_per_block) {
+  __shared__ __attribute__((aligned(16))) uint16_t red[kThreads / 64][kColTile];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t c0 = (int64_t)blockIdx.x * kColTile;
+  const int64_t c = c0 + lane * 8;  // K % 8 == 0: a slice that starts inside a row ends inside it
+  const int64_t r_begin = (int64_t)blockIdx.y * rows_per_block;
+  const int64_t r_end = r_begin + rows_per_block < M ? r_begin + rows_per_block : M;
+  u32x4 m = {0u, 0u, 0u, 0u};
+  if (c < K) {
+    constexpr int kStep = (kThreads / 64) * kRowsInFlight;
+    for (int64_t r = r_begin + wave; r < r_end; r += kStep) {
+      u32x4 v[kRowsInFlight];
+#pragma unroll
+      for (int j = 0; j < kRowsInFlight; ++j) {
+        const int64_t rj = r + j * (kThreads / 64);
+        v[j] = rj < r_end ? *reinterpret_cast<const u32x4*>(x + rj * K + c) : u32x4{0u, 0u, 0u, 0u};
+      }
+#pragma unroll
+      for (int j = 0; j < kRowsInFlight; ++j) absmax8_update(m, v[j]);
+    }
+  }
+  *reinterpret_cast<u32x4*>(&red[wave][lane * 8]) = m;
+  __syncthreads();
+#pragma unroll
+  for (int h = 0; h < kColTile / kThreads; ++h) {
+    const int col = threadIdx.x + h * kThreads;
+    uint16_t b = red[0][col];
+#pragma unroll
+    for (int w = 1; w < kThreads / 64; ++w) b = red[w][col] > b ? red[w][col] : b;
+    if (c0 + col < K && b != 0) atomicMax(state + c0 + col, (uint32_t)b << 16);  // fp32 bits of a bf16 value
+  }
+}
+
+// ---- B: running amax of the smoothed activation -------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void sq_smoothed_amax_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ s,
+                                                                    uint32_t* __restrict__ amax, int64_t M, int64_t K, int64_t rows_per_block) {
+#pragma clang fp contract(off)
+  __shared__ float red[4];
+  const int64_t c = ((int64_t)blockIdx.x * kThreads + threadIdx.x) * 8;
+  const int64_t r_begin = (int64_t)blockIdx.y * rows_per_block;
+  const int64_t r_end = r_begin + rows_per_block < M ? r_begin + rows_per_block : M;
+  float m = 0.f;
+  if (c < K) {
+    const u32x4 sv = *reinterpret_cast<const u32x4*>(s + c);
+    const uint32_t sw[4] = {sv.x, sv.y, sv.z, sv.w};
+    float d[8];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) d[2 * j] = bf16_lo_to_f32(sw[j]), d[2 * j + 1] = bf16_hi_to_f32(sw[j]);
+#pragma unroll 2
+    for (int64_t r = r_begin; r < r_end; ++r) {
+      const u32x4 v = *reinterpret_cast<const u32x4*>(x + r * K + c);
+      const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float a = round_bf16(bf16_lo_to_f32(w[j]) / d[2 * j]), b = round_bf16(bf16_hi_to_f32(w[j]) / d[2 * j + 1]);
+        m = fmaxf(m, fmaxf(fabsf(a), fabsf(b)));
+      }
+    }
+  }
+  m = block_max(m, red);
+  if (threadIdx.x == 0 && m != 0.f) atomicMax(amax, f32_to_bits(m));
+}
+
+// ---- C: the int8 activation casts on t = bf16(x * pre) ----------------------------------------------------------------------------------------------
+// amax_all (optional): ONE amax for every row, the PerTensor cast's (measured by prescaled_amax_kernel below).  Otherwise the twins of
+// quant_rowwise_reg_kernel<true, NV> and int8_quant_rowwise_kernel (quant_kernels.hip): the same lines on prescale8(x, pre).  `pre` is read
+// again by every row's workgroup; it is 2 K bytes and stays in L2.
+template <int NV>
+__global__ __launch_bounds__(kThreads) void int8_quant_rowwise_prescaled_reg_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ pre,
+                                                                                    const float* __restrict__ amax_all, int8_t* __restrict__ q,
+                                                                                    float* __restrict__ scale, int64_t K) {
+  __shared__ float red[4];
+  const int64_t row = blockIdx.x;
+  const u32x4* xr = reinterpret_cast<const u32x4*>(x + row * K);
+  const u32x4* pr = reinterpret_cast<const u32x4*>(pre);
+  const int nvec = (int)(K >> 3);
+  u32x4 v[NV];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int idx = threadIdx.x + i * kThreads;
+    v[i] = (idx < nvec) ? prescale8(xr[idx], pr[idx]) : u32x4{0u, 0u, 0u, 0u};
+  }
+  float m = 0.f;
+  if (amax_all != nullptr) {
+    m = amax_all[0];
+  } else {
+    bool has_nan = false;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) m = fmaxf(m, amax8(v[i], has_nan));
+    m = block_max(has_nan ? INFINITY : m, red);  // (NaN rows are outside the contract)
+  }
+  const float s = int8_row_scale(m);
+  const float inv = 1.0f / s;
+  if (threadIdx.x == 0) scale[row] = s;
+  u32x2* qr = reinterpret_cast<u32x2*>(q + row * K);
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int idx = threadIdx.x + i * kThreads;
+    if (idx < nvec) qr[idx] = int8_quant8(v[i], inv);
+  }
+}
+
+// longer rows: two sweeps, the second through L2
+__global__ __launch_bounds__(kThreads) void int8_quant_rowwise_prescaled_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ pre,
+                                                                                const float* __restrict__ amax_all, int8_t* __restrict__ q,
+                                                                                float* __restrict__ scale, int64_t K) {
+  __shared__ float red[4];
+  const int64_t row = blockIdx.x;
+  const u32x4* xr = reinterpret_cast<const u32x4*>(x + row * K);
+  const u32x4* pr = reinterpret_cast<const u32x4*>(pre);
+  const int64_t nvec = K >> 3;
+  float m = 0.f;
+  if (amax_all != nullptr) {
+    m = amax_all[0];
+  } else {
+    bool has_nan = false;
+    for (int64_t i = threadIdx.x; i < nvec; i += kThreads) m = fmaxf(m, amax8(prescale8(xr[i], pr[i]), has_nan));
+    m = block_max(has_nan ? INFINITY : m, red);
+  }
+  const float s = int8_row_scale(m);
+  const float inv = 1.0f / s;
+  if (threadIdx.x == 0) scale[row] = s;
+  u32x2* qr = reinterpret_cast<u32x2*>(q + row * K);
+  for (int64_t i = threadIdx.x; i < nvec; i += kThreads) qr[i] = int8_quant8(prescale8(xr[i], pr[i]), inv);
+}
+
+// the PerTensor cast's first half: max |t| over the whole activation, one atomic per row (ops.int8_quantize_tensorwise takes the same maximum
+// with rowwise_amax + amax; max is exact, so the order does not matter)
+__global__ __launch_bounds__(kThreads) void prescaled_amax_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ pre,
+                                                                  uint32_t* __restrict__ amax, int64_t K) {
+  __shared__ float red[4];
+  const u32x4* xr = reinterpret_cast<const u32x4*>(x + (int64_t)blockIdx.x * K);
+  const u32x4* pr = reinterpret_cast<const u32x4*>(pre);
+  float m = 0.f;
+  bool has_nan = false;
+  for (int64_t i = threadIdx.x; i < (K >> 3); i += kThreads) m = fmaxf(m, amax8(prescale8(xr[i], pr[i]), has_nan));
+  m = block_max(has_nan ? INFINITY : m, red);
+  if (threadIdx.x == 0 && m != 0.f) atomicMax(amax, f32_to_bits(m));
+}
+
+// the twin of int8_quant_static_kernel
+__global__ __launch_bounds__(kThreads) void int8_quant_static_prescaled_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ pre,
+                                                                               const float* __restrict__ scale, const int8_t* __restrict__ zero_point,
+                                                                               int stride, int8_t* __restrict__ q, int64_t K) {
+  const int64_t row = blockIdx.x;
+  const u32x4* xr = reinterpret_cast<const u32x4*>(x + row * K);
+  const u32x4* pr = reinterpret_cast<const u32x4*>(pre);
+  const float inv = 1.0f / scale[row * stride];
+  const float zp = zero_point != nullptr ? (float)zero_point[row * stride] : 0.0f;
+  u32x2* qr = reinterpret_cast<u32x2*>(q + row * K);
+  for (int64_t i = threadIdx.x; i < (K >> 3); i += kThreads) qr[i] = int8_quant8_zp(prescale8(xr[i], pr[i]), inv, zp);
+}
+
+void launch_rowwise_prescaled(const uint16_t* x, const uint16_t* pre, const float* amax_all, int8_t* q, float* scale, int64_t M, int64_t K,
+                              hipStream_t s) {
+  const int64_t per_thread = ((K >> 3) + kThreads - 1) / kThreads;
+  const dim3 grid((unsigned)M), block(kThreads);
+  if (per_thread <= 1) ao::launch(int8_quant_rowwise_prescaled_reg_kernel<1>, grid, block, 0, s, x, pre, amax_all, q, scale, K);
+  else if (per_thread <= 2) ao::launch(int8_quant_rowwise_prescaled_reg_kernel<2>, grid, block, 0, s, x, pre, amax_all, q, scale, K);
+  else if (per_thread <= 4) ao::launch(int8_quant_rowwise_prescaled_reg_kernel<4>, grid, block, 0, s, x, pre, amax_all, q, scale, K);
+  else if (per_thread <= 8) ao::launch(int8_quant_rowwise_prescaled_reg_kernel<8>, grid, block, 0, s, x, pre, amax_all, q, scale, K);
+  else ao::launch(int8_quant_rowwise_prescaled_kernel, grid, block, 0, s, x, pre, amax_all, q, scale, K);
+}
+
+int check_rows(const char* fn, int64_t M, int64_t K) {
+  AO_REQUIRE(M >= 0 && K > 0, "%s: bad shape M=%lld K=%lld", fn, (long long)M, (long long)K);
+  AO_REQUIRE(K % 8 == 0, "%s: K=%lld must be a multiple of 8", fn, (long long)K);
+  AO_REQUIRE(M < (1ll << 31) && K < (1ll << 31), "%s: M=%lld K=%lld too large", fn, (long long)M, (long long)K);
+  return AO_OK;
+}
+
+// rows per workgroup so that about kTargetBlocks workgroups exist over `col_blocks` column tiles; at least `min_rows` rows each
+int64_t rows_per_block(int64_t M, int64_t col_blocks, int64_t min_rows) {
+  const int64_t splits = std::max<int64_t>(1, std::min<int64_t>(kTargetBlocks / col_blocks, (M + min_rows - 1) / min_rows));
+  return (M + splits - 1) / splits;
+}
+
+}  // namespace
+}  // namespace ao
+
+using namespace ao;
+
+extern "C" int ao_sq_col_absmax_update(const uint16_t* x, float* state, int64_t M, int64_t K, void* stream) {
+  if (int rc = check_rows(__func__, M, K)) return rc;
+  if (M == 0) return AO_OK;
+  AO_REQUIRE_PTR(x);
+  AO_REQUIRE_PTR(state);
+  AO_REQUIRE(aligned_to(x, 16) && aligned_to(state, 4), "%s: x must be 16-byte aligned and state 4-byte aligned", __func__);
+  const int64_t gx = (K + kColTile - 1) / kColTile;
+  const int64_t rows = rows_per_block(M, gx, (kThreads / 64) * kRowsInFlight);
+  const int64_t gy = (M + rows - 1) / rows;
+  ao::launch(sq_col_absmax_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(kThreads), 0, (hipStream_t)stream, x,
+             reinterpret_cast<uint32_t*>(state), M, K, rows);
+  AO_LAUNCH_CHECK("sq_col_absmax_kernel launch");
+  return AO_OK;
+}
+
+extern "C" int ao_sq_smoothed_amax_update(const uint16_t* x, const uint16_t* s, float* amax, int64_t M, int64_t K, void* stream) {
+  if (int rc = check_rows(__func__, M, K)) return rc;
+  if (M == 0) return AO_OK;
+  AO_REQUIRE_PTR(x);
+  AO_REQUIRE_PTR(s);
+  AO_REQUIRE_PTR(amax);
+  AO_REQUIRE(aligned_to(x, 16) && aligned_to(s, 16) && aligned_to(amax, 4), "%s: x and s must be 16-byte aligned and amax 4-byte aligned", __func__);
+  const int64_t gx = ((K >> 3) + kThreads - 1) / kThreads;
+  const int64_t rows = rows_per_block(M, gx, 1);
+  const int64_t gy = (M + rows - 1) / rows;
+  ao::launch(sq_smoothed_amax_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(kThreads), 0, (hipStream_t)stream, x, s,
+             reinterpret_cast<uint32_t*>(amax), M, K, rows);
+  AO_LAUNCH_CHECK("sq_smoothed_amax_kernel launch");
+  return AO_OK;
+}
+
+extern "C" int ao_int8_quantize_rowwise_prescaled(const uint16_t* x, const uint16_t* pre, int8_t* q, float* scale, int64_t M, int64_t K,
+                                                  void* stream) {
+  if (int rc = check_rows(__func__, M, K)) return rc;
+  if (M == 0) return AO_OK;
+  AO_REQUIRE_PTR(x);
+  AO_REQUIRE_PTR(pre);
+  AO_REQUIRE_PTR(q);
+  AO_REQUIRE_PTR(scale);
+  AO_REQUIRE(aligned_to(x, 16) && aligned_to(pre, 16) && aligned_to(q, 8), "%s: x and pre must be 16-byte aligned and q 8-byte aligned", __func__);
+  launch_rowwise_prescaled(x, pre, nullptr, q, scale, M, K, (hipStream_t)stream);
+  AO_LAUNCH_CHECK("int8_quant_rowwise_prescaled_kernel launch");
+  return AO_OK;
+}
+
+extern "C" int ao_int8_quantize_tensorwise_prescaled(const uint16_t* x, const uint16_t* pre, float* amax, int8_t* q, float* scale, int64_t M,
+                                                     int64_t K, void* stream) {
+  if (int rc = check_rows(__func__, M, K)) return rc;
+  if (M == 0) return AO_OK;
+  AO_REQUIRE_PTR(x);
+  AO_REQUIRE_PTR(pre);
+  AO_REQUIRE_PTR(amax);
+  AO_REQUIRE_PTR(q);
+  AO_REQUIRE_PTR(scale);
+  AO_REQUIRE(aligned_to(x, 16) && aligned_to(pre, 16) && aligned_to(q, 8) && aligned_to(amax, 4),
+             "%s: x and pre must be 16-byte aligned, q 8-byte and amax 4-byte aligned", __func__);
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t e = hipMemsetAsync(amax, 0, sizeof(float), s);
+  if (e != hipSuccess) return ::ao::hip_failed(e, "hipMemsetAsync(amax)");
+  ao::launch(prescaled_amax_kernel, dim3((unsigned)M), dim3(kThreads), 0, s, x, pre, reinterpret_cast<uint32_t*>(amax), K);
+  AO_LAUNCH_CHECK("prescaled_amax_kernel launch");
+  launch_rowwise_prescaled(x, pre, amax, q, scale, M, K, s);
+  AO_LAUNCH_CHECK("int8_quant_rowwise_prescaled_kernel launch");
+  return AO_OK;
+}
+
+extern "C" int ao_int8_quantize_static_prescaled(const uint16_t* x, const uint16_t* pre, const float* scale, const int8_t* zero_point, int per_row,
+                                                 int8_t* q, int64_t M, int64_t K, void* stream) {
+  if (int rc = check_rows(__func__, M, K)) return rc;
+  if (M == 0) return AO_OK;
+  AO_REQUIRE_PTR(x);
+  AO_REQUIRE_PTR(pre);
+  AO_REQUIRE_PTR(scale);
+  AO_REQUIRE_PTR(q);
+  AO_REQUIRE(aligned_to(x, 16) && aligned_to(pre, 16) && aligned_to(q, 8), "%s: x and pre must be 16-byte aligned and q 8-byte aligned", __func__);
+  ao::launch(int8_quant_static_prescaled_kernel, dim3((unsigned)M), dim3(kThreads), 0, (hipStream_t)stream, x, pre, scale, zero_point,
+             per_row ? 1 : 0, q, K);
+  AO_LAUNCH_CHECK("int8_quant_static_prescaled_kernel launch");
+  return AO_OK;
+}

@@ -2870,3 +2870,143 @@ def awq_scaled_error(W: torch.Tensor, S: torch.Tensor, group_size: int, out: Opt
 
 
 __all__ += ["awq_scaled_error", "AWQ_GROUP_SIZES"]
+
+
+# ---------------------------------------------------------------------------
+# SmoothQuant: the calibration reductions, and the int8 activation casts with the activation pre-scale folded in
+# (csrc/smoothquant_kernels.hip states the arithmetic)
+# ---------------------------------------------------------------------------
+def _sq_rows(name, x):
+    if x.dtype != torch.bfloat16:
+        raise NotImplementedError(f"{name}: x is bfloat16, got {x.dtype}")
+    if x.dim() != 2:
+        raise RuntimeError(f"{name}: expected a 2-D tensor, got {x.dim()}-D")
+    if x.shape[1] == 0 or x.shape[1] % 8 != 0:
+        raise ValueError(f"{name}: K={x.shape[1]} must be a multiple of 8")
+    return x if x.is_contiguous() else x.contiguous()
+
+
+def _sq_vector(name, what, v, k):
+    """A bf16 [K] vector (the smoothing factor or the activation pre-scale), contiguous."""
+    if v.dtype != torch.bfloat16 or v.numel() != k:
+        raise RuntimeError(f"{name}: {what} must be a bfloat16 vector of K = {k} elements, got {v.dtype} {tuple(v.shape)}")
+    return v.reshape(-1).contiguous()
+
+
+def sq_col_absmax_update(x: torch.Tensor, state: torch.Tensor) -> torch.Tensor:
+    """state[k] = max(state[k], max_m |x[m, k]|) in place (SmoothQuantObserver's x_abs_max, prototype/smoothquant/core.py:53, as a running
+    maximum).  x bf16 [M, K]; state fp32 [K], contiguous, non-negative (zeros before the first update).  Exact and order-independent."""
+    name = "sq_col_absmax_update"
+    dev = _require_gpu(name, x, state)
+    x = _sq_rows(name, x)
+    m, k = x.shape
+    if state.dtype != torch.float32 or tuple(state.shape) != (k,) or not state.is_contiguous():
+        raise RuntimeError(f"{name}: state must be a contiguous float32 vector of K = {k} elements, got {state.dtype} {tuple(state.shape)}")
+    with _on(dev):
+        _lib.check(_lib.lib().ao_sq_col_absmax_update(_ptr(x), _ptr(state), m, k, _stream()))
+    return state
+
+
+def sq_smoothed_amax_update(x: torch.Tensor, s: torch.Tensor, amax: torch.Tensor) -> torch.Tensor:
+    """amax = max(amax, max |bf16(x / s)|) in place: the amax of the smoothed activation `x / smoothing_factor` (core.py:66-68, 192-195)
+    without writing it.  x bf16 [M, K]; s bf16 [K]; amax fp32, one element, non-negative."""
+    name = "sq_smoothed_amax_update"
+    dev = _require_gpu(name, x, s, amax)
+    x = _sq_rows(name, x)
+    m, k = x.shape
+    s = _sq_vector(name, "s", s, k)
+    if amax.dtype != torch.float32 or amax.numel() != 1:
+        raise RuntimeError(f"{name}: amax must be a float32 tensor of one element, got {amax.dtype} {tuple(amax.shape)}")
+    with _on(dev):
+        _lib.check(_lib.lib().ao_sq_smoothed_amax_update(_ptr(x), _ptr(s), _ptr(amax), m, k, _stream()))
+    return amax
+
+
+def int8_quantize_rowwise_prescaled(x: torch.Tensor, pre: torch.Tensor):
+    """int8_quantize_rowwise(x * pre) in one launch, the product never written: x bf16 [M, K], pre bf16 [K] ->
+    (qdata int8 [M, K], scale fp32 [M, 1])."""
+    name = "int8_quantize_rowwise_prescaled"
+    dev = _require_gpu(name, x, pre)
+    x = _sq_rows(name, x)
+    m, k = x.shape
+    pre = _sq_vector(name, "pre", pre, k)
+    q = torch.empty((m, k), dtype=torch.int8, device=dev)
+    s = torch.empty((m, 1), dtype=torch.float32, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_int8_quantize_rowwise_prescaled(_ptr(x), _ptr(pre), _ptr(q), _ptr(s), m, k, _stream()))
+    return q, s
+
+
+def _int8_quantize_tensorwise_prescaled_rows(x, pre):
+    """(qdata int8 [M, K], scale fp32 [M] with the tensor's scale in every entry: what the GEMM's row-scale operand takes as it is)"""
+    name = "int8_quantize_tensorwise_prescaled"
+    dev = _require_gpu(name, x, pre)
+    x = _sq_rows(name, x)
+    m, k = x.shape
+    pre = _sq_vector(name, "pre", pre, k)
+    q = torch.empty((m, k), dtype=torch.int8, device=dev)
+    s = torch.empty((m + 1,), dtype=torch.float32, device=dev)  # the last entry is the call's amax work buffer
+    with _on(dev):
+        _lib.check(_lib.lib().ao_int8_quantize_tensorwise_prescaled(_ptr(x), _ptr(pre), _ptr(s[m:]), _ptr(q), _ptr(s), m, k, _stream()))
+    return q, s[:m]
+
+
+def int8_quantize_tensorwise_prescaled(x: torch.Tensor, pre: torch.Tensor):
+    """int8_quantize_tensorwise(x * pre) without writing the product: x bf16 [M, K], pre bf16 [K] -> (qdata int8 [M, K], scale fp32 [1, 1])."""
+    q, s = _int8_quantize_tensorwise_prescaled_rows(x, pre)
+    return q, s[:1].reshape(1, 1)
+
+
+def int8_quantize_static_prescaled(x: torch.Tensor, pre: torch.Tensor, scale: torch.Tensor, zero_point: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int8_quantize_static(x * pre, scale, zero_point) in one launch: x bf16 [M, K], pre bf16 [K], scale fp32 of 1 or M elements (and an int8
+    zero-point of the same shape, or None) -> qdata int8 [M, K]."""
+    name = "int8_quantize_static_prescaled"
+    dev = _require_gpu(name, x, pre, scale, zero_point)
+    x = _sq_rows(name, x)
+    m, k = x.shape
+    pre = _sq_vector(name, "pre", pre, k)
+    scale = scale.reshape(-1).to(torch.float32).contiguous()
+    if scale.numel() not in (1, m):
+        raise RuntimeError(f"{name}: scale must have 1 or M = {m} elements, got {scale.numel()}")
+    if zero_point is not None:
+        zero_point = zero_point.reshape(-1).to(torch.int8).contiguous()
+        if zero_point.numel() != scale.numel():
+            raise RuntimeError(f"{name}: zero_point must have the shape of scale")
+    q = torch.empty((m, k), dtype=torch.int8, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_int8_quantize_static_prescaled(_ptr(x), _ptr(pre), _ptr(scale), _ptr(zero_point),
+                                                                int(scale.numel() == m and m > 1), _ptr(q), m, k, _stream()))
+    return q
+
+
+def int8_linear_prescaled(x2, pre, wq, w_scale, bias=None):
+    """int8_linear(x2 * pre, ...) for an Int8Tensor with a per-input-feature act_pre_scale (SmoothQuant): the pre-scaled cast, then
+    ao_int8_scaled_mm.  Same bits as the multiply followed by int8_linear.  (The Int8Tensor linear does not come here with one row: there
+    the multiply and the one-launch fused cast + matmul kernel stay)"""
+    xq, xs = int8_quantize_rowwise_prescaled(x2, pre)
+    return int8_scaled_mm(xq, xs, wq, w_scale, bias)
+
+
+def int8_linear_tensorwise_prescaled(x2, pre, wq, w_scale, bias=None):
+    """int8_linear_tensorwise(x2 * pre, ...) without writing the product."""
+    xq, xs = _int8_quantize_tensorwise_prescaled_rows(x2, pre)
+    return int8_scaled_mm(xq, xs, wq, w_scale, bias)
+
+
+def int8_linear_static_prescaled(x2, pre, wq, w_scale, act_scale, act_zero_point=None, w_row_sums=None, bias=None):
+    """int8_linear_static(x2 * pre, ...) without writing the product."""
+    m = x2.shape[0]
+    xq = int8_quantize_static_prescaled(x2, pre, act_scale, act_zero_point)
+    xs = act_scale.reshape(-1).to(torch.float32)
+    xs = xs.expand(m) if xs.numel() == 1 else xs
+    if act_zero_point is None:
+        return int8_scaled_mm(xq, xs, wq, w_scale, bias)
+    zp = act_zero_point.reshape(-1)
+    zp = zp.expand(m) if zp.numel() == 1 else zp
+    if w_row_sums is None:
+        w_row_sums = int8_row_sums(wq)
+    return int8_scale_epilogue_asym(int_mm(xq, wq.t()), xs, zp, w_row_sums, w_scale, bias)
+
+
+__all__ += ["sq_col_absmax_update", "sq_smoothed_amax_update", "int8_quantize_rowwise_prescaled", "int8_quantize_tensorwise_prescaled",
+            "int8_quantize_static_prescaled", "int8_linear_prescaled", "int8_linear_tensorwise_prescaled", "int8_linear_static_prescaled"]

@@ -39,6 +39,13 @@ from .nvfp4_training import (  # noqa: F401
     get_wgrad_sign_vector,
     nvfp4_linear,
 )
+from .smoothquant import (  # noqa: F401
+    RunningAbsMaxSmoothQuantObserver,
+    SmoothQuantConfig,
+    SmoothQuantObservedLinear,
+    SmoothQuantObserver,
+    SmoothQuantStep,
+)
 
 __all__ = ["Float8BlockwiseExpertWeights", "fp8_blockwise_grouped_mm", "NVFP4Tensor", "NVFP4WeightOnlyConfig",
            "NVFP4DynamicActivationNVFP4WeightConfig", "QuantizeTensorToNVFP4Kwargs", "per_tensor_amax_to_scale", "NVFP4ExpertWeights",
@@ -48,4 +55,5 @@ __all__ = ["Float8BlockwiseExpertWeights", "fp8_blockwise_grouped_mm", "NVFP4Ten
            "Float8BlockwiseLinearConfig", "_Float8BlockwiseGroupedMM", "_to_fp8_blockwise_then_scaled_grouped_mm",
            "_to_fp8_blockwise_then_emulated_scaled_grouped_mm",
            "NVFP4Linear", "NVFP4TrainingConfig", "nvfp4_linear", "DEFAULT_SIGN_VECTOR", "get_wgrad_sign_vector",
-           "NF4WeightOnlyConfig", "nf4_weight_only", "AWQConfig", "AWQObserver", "AWQObservedLinear"]
+           "NF4WeightOnlyConfig", "nf4_weight_only", "AWQConfig", "AWQObserver", "AWQObservedLinear",
+           "SmoothQuantConfig", "SmoothQuantStep", "SmoothQuantObserver", "RunningAbsMaxSmoothQuantObserver", "SmoothQuantObservedLinear"]

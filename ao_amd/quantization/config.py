@@ -346,7 +346,7 @@ def _resolve(name):
 
     for mod in ("ao_amd.quantization.config", "ao_amd.quantization.granularity", "ao_amd.quantization.quant_primitives",
                 "ao_amd.quantization.int8_tensor", "ao_amd.quantization.float8_tensor", "ao_amd.prototype.mx", "ao_amd.prototype.nvfp4_tensor",
-                "ao_amd.prototype.gptq.api", "ao_amd.prototype.awq.api"):
+                "ao_amd.prototype.gptq.api", "ao_amd.prototype.awq.api", "ao_amd.prototype.smoothquant.api"):
         try:
             cls = getattr(importlib.import_module(mod), name)
         except (ImportError, AttributeError):

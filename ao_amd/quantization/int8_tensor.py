@@ -201,6 +201,29 @@ def _weight_only_linear(x, w, bias, out_dtype):
     return y.to(out_dtype)
 
 
+def _prescale_fuses(x, w) -> bool:
+    """True where `x * act_pre_scale` need not be computed on its own: a bf16 activation, a bf16 [K] pre-scale (SmoothQuant's, one entry
+    per input feature) and an activation cast that has a pre-scaled form (ops.int8_quantize_{rowwise,tensorwise,static}_prescaled: the
+    symmetric dynamic casts and the static one).  The cast then reads x and the pre-scale and rounds their product to bf16 in registers:
+    the same bytes as the multiply, one launch and a bf16 write and read of the activation fewer.  Everything else -- fp16 / fp32
+    activations, the ASYMMETRIC dynamic cast, weight-only, a scalar or broadcast pre-scale -- keeps the torch multiply.  So does ONE row
+    under the dynamic PerRow cast: there the parent route is the multiply and the one-launch fused cast + matmul kernel
+    (ops.int8_dynamic_linear), and pre-scaled cast + matmul measured level with it or behind."""
+    pre, act = w.act_pre_scale, w.act_quant_kwargs
+    if act is None or x.dtype != torch.bfloat16 or pre.dtype != torch.bfloat16 or pre.device != x.device:
+        return False
+    k = x.shape[-1]
+    if pre.dim() != 1 or pre.numel() != k or k % 8 != 0 or w.qdata.dim() != 2 or x.numel() == 0:
+        return False
+    if not isinstance(act.granularity, (PerRow, PerTensor)):
+        return False
+    if w.act_quant_scale is not None:
+        return True
+    if _mapping(act.mapping_type) != MappingType.SYMMETRIC:
+        return False
+    return isinstance(act.granularity, PerTensor) or x.numel() > k
+
+
 @implements(aten.linear.default)
 @implements_torch_function(F.linear)
 def _(func, types, args, kwargs):
@@ -210,8 +233,12 @@ def _(func, types, args, kwargs):
     bias = args[2] if len(args) > 2 else kwargs.get("bias", None)
     assert isinstance(w, Int8Tensor), f"Expected weight to be Int8Tensor, got {type(w)}"
     out_dtype = x.dtype
+    pre = None  # the pre-scale the activation cast takes in (SmoothQuant); every other case multiplies here, as before
     if w.act_pre_scale is not None:
-        x = x * w.act_pre_scale
+        if _prescale_fuses(x, w):
+            pre = w.act_pre_scale
+        else:
+            x = x * w.act_pre_scale
     if w.act_quant_kwargs is None:
         return _weight_only_linear(x, w, bias, out_dtype)
     act = w.act_quant_kwargs
@@ -234,7 +261,15 @@ def _(func, types, args, kwargs):
             zp = w.act_quant_zero_point
             if zp is not None and w.w_row_sums is None:
                 w.w_row_sums = ops.int8_row_sums(w.qdata)
-            y = k.int8_linear_static(x2, w.qdata, w._row_scale(), w.act_quant_scale, zp, w.w_row_sums, bias)
+            if pre is not None:
+                y = k.int8_linear_static_prescaled(x2, pre, w.qdata, w._row_scale(), w.act_quant_scale, zp, w.w_row_sums, bias)
+            else:
+                y = k.int8_linear_static(x2, w.qdata, w._row_scale(), w.act_quant_scale, zp, w.w_row_sums, bias)
+        elif pre is not None:  # (_prescale_fuses: a symmetric dynamic cast)
+            if isinstance(act.granularity, PerTensor):
+                y = k.int8_linear_tensorwise_prescaled(x2, pre, w.qdata, w._row_scale(), bias)
+            else:
+                y = k.int8_linear_prescaled(x2, pre, w.qdata, w._row_scale(), bias)
         elif _mapping(act.mapping_type) == MappingType.ASYMMETRIC:
             if not isinstance(act.granularity, PerRow):
                 raise NotImplementedError("Int8Tensor on MI355X implements ASYMMETRIC activation quantization per row only")

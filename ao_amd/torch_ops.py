@@ -632,4 +632,34 @@ for _name in ("optim_quantize", "optim_dequantize", "optim_adam_step"):
     _lib_autograd.impl(_name, torch.library.fallthrough_kernel)
 
 
+# ---- SmoothQuant (ops.py "SmoothQuant"): the int8 linears with the activation pre-scale folded into the cast -----------------
+# (the twins of int8_linear / int8_linear_tensorwise / int8_linear_static, with `pre` bf16 [K] after the activation)
+_lib_def.define("int8_linear_prescaled(Tensor x, Tensor pre, Tensor wq, Tensor w_scale, Tensor? bias) -> Tensor")
+_lib_def.define("int8_linear_tensorwise_prescaled(Tensor x, Tensor pre, Tensor wq, Tensor w_scale, Tensor? bias) -> Tensor")
+_lib_def.define("int8_linear_static_prescaled(Tensor x, Tensor pre, Tensor wq, Tensor w_scale, Tensor act_scale, Tensor? act_zero_point, "
+                "Tensor? w_row_sums, Tensor? bias) -> Tensor")
+_lib_impl.impl("int8_linear_prescaled", ops.int8_linear_prescaled)
+_lib_impl.impl("int8_linear_tensorwise_prescaled", ops.int8_linear_tensorwise_prescaled)
+_lib_impl.impl("int8_linear_static_prescaled", ops.int8_linear_static_prescaled)
+
+
+@torch.library.register_fake("ao_mi355::int8_linear_prescaled")
+def _(x, pre, wq, w_scale, bias):
+    return x.new_empty((x.shape[0], wq.shape[0]), dtype=torch.bfloat16)
+
+
+@torch.library.register_fake("ao_mi355::int8_linear_tensorwise_prescaled")
+def _(x, pre, wq, w_scale, bias):
+    return x.new_empty((x.shape[0], wq.shape[0]), dtype=torch.bfloat16)
+
+
+@torch.library.register_fake("ao_mi355::int8_linear_static_prescaled")
+def _(x, pre, wq, w_scale, act_scale, act_zero_point, w_row_sums, bias):
+    return x.new_empty((x.shape[0], wq.shape[0]), dtype=torch.bfloat16)
+
+
+for _name in ("int8_linear_prescaled", "int8_linear_tensorwise_prescaled", "int8_linear_static_prescaled"):
+    _lib_autograd.impl(_name, torch.library.fallthrough_kernel)
+
+
 load_ops_library()

@@ -1147,6 +1147,29 @@ int ao_gptq_block(void* W, int w_bf16, const float* Hinv, float* Err, int format
  * no atomics: the same bytes every launch.  No allocation, no synchronisation: capturable in a graph. */
 int ao_awq_scaled_error(const uint16_t* W, const uint16_t* S, float* D, int64_t N, int64_t K, int64_t R, int group_size, void* stream);
 
+/* ---- SmoothQuant (torchao/prototype/smoothquant) ---------------------------------------------------------------------------------------------
+ * Calibration (prototype/smoothquant/core.py:41-75, 162-206), as running reductions that never hold more than their state:
+ *   ao_sq_col_absmax_update     state[k] = max(state[k], max_m |x[m][k]|)                         x bf16 [M][K], state fp32 [K]
+ *   ao_sq_smoothed_amax_update  amax[0]  = max(amax[0], max_mk |bf16(f32(x[m][k]) / f32(s[k]))|)   s bf16 [K] (> 0, finite), amax fp32 [1]
+ * Both fold with an integer atomic max on the bit pattern of non-negative floats: exact, independent of the order of arrival, the same bytes
+ * every launch.  The state must hold non-negative floats (zeros before the first update); -0.0 counts as 0; IEEE division; NaN / Inf inputs
+ * are outside the contract.
+ * Run time: the int8 activation casts with the activation pre-scale folded in, t = bf16(f32(x[m][k]) * f32(pre[k])) (the bf16 tensor op
+ * `x * act_pre_scale`: the product is exact in fp32, so one rounding), pre bf16 [K]:
+ *   ao_int8_quantize_rowwise_prescaled     ao_int8_quantize_rowwise on t:  q int8 [M][K], scale fp32 [M]
+ *   ao_int8_quantize_tensorwise_prescaled  one amax over all of t (Int8Tensor.from_hp(t, PerTensor())): `amax` fp32 [1] is a work buffer the
+ *                                          call zeroes and fills; scale fp32 [M], every entry the tensor's scale
+ *   ao_int8_quantize_static_prescaled      ao_int8_quantize_static on t (given scale / zero-point, one per tensor or, per_row != 0, per row)
+ * Byte for byte what the unscaled cast gives on `x * pre` computed by a bf16 multiply.  t is never written to memory.
+ * All: K % 8 == 0, x / s / pre 16-byte aligned, M == 0 launches nothing.  No allocation, no synchronisation: capturable in a graph. */
+int ao_sq_col_absmax_update(const uint16_t* x, float* state, int64_t M, int64_t K, void* stream);
+int ao_sq_smoothed_amax_update(const uint16_t* x, const uint16_t* s, float* amax, int64_t M, int64_t K, void* stream);
+int ao_int8_quantize_rowwise_prescaled(const uint16_t* x, const uint16_t* pre, int8_t* q, float* scale, int64_t M, int64_t K, void* stream);
+int ao_int8_quantize_tensorwise_prescaled(const uint16_t* x, const uint16_t* pre, float* amax, int8_t* q, float* scale, int64_t M, int64_t K,
+                                          void* stream);
+int ao_int8_quantize_static_prescaled(const uint16_t* x, const uint16_t* pre, const float* scale, const int8_t* zero_point, int per_row,
+                                      int8_t* q, int64_t M, int64_t K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
