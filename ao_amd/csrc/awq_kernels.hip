@@ -5,55 +5,36 @@
 // mean((X W^T - (X / s) Wq^T)^2), is tr(D G D^T) / (rows N) with D = W - Wq / s and G = X^T X, so what the search needs of the weight is D.
 // Per ratio r, row n and group of g columns, every step ONE fp32 operation rounded once (IEEE division, no fma contraction):
 //   ws  = bf16(f32(W[n,k]) * f32(S[r,k]))                          core.py:78 `self.weight * scales`, a bf16 tensor op
-//   M, m = max, min of ws over the group;  s = max(M - m, 1e-6) / 15;  z = m + 8 s
-//   q   = clamp(rint((ws - m) / s), 0, 15) - 8                      the codes of ao_int4_plain_quantize (int4_plain_kernels.hip)
+//   M, m = max, min of ws over the group;  s = max(M - m, 1e-6) / 15;  z = m + 8 s       int4_group_qparams (quant_math.h)
+//   q   = clamp(rint((ws - m) / s), 0, 15) - 8                      int4_group_code: the codes of ao_int4_plain_quantize
 //   dq  = bf16(f32(bf16(q * f32(bf16(s)))) + f32(bf16(z)))          the weight int4_plain_kernels.hip's header states: the qparams are STORED
 //                                                                   as bf16, and the product and the sum are bf16 tensor ops
 //   D[r,n,k] = f32(W[n,k]) - f32(dq) / f32(S[r,k])                  the division, then the subtraction
 // so dq is Int4Tensor.from_hp(W * S[r], [1, g]).dequantize() byte for byte: the codes `convert` will store are the codes the search judged.
 // (q * bf16(s) has 4 x 8 significand bits and W * S 8 x 8: both products are exact in fp32, their one rounding is the one to bf16.)
 //
-// Structure: that of qat_int4_fake_quantize_kernel (qat_kernels.hip).  The weight is a flat run of 16-byte vectors, one per lane; a group is
+// Structure: the weight is a flat run of 16-byte vectors, one per lane (quant_math.h's lane helpers, shared with the fake quantizer); a group is
 // g / 8 adjacent lanes (K % g == 0 keeps groups whole inside a row) and its range a butterfly over lanes: no LDS, no atomics, the same bytes
 // every launch.  The lane keeps its 8 weights in registers and loops over r; row r of S is read as one 16-byte piece per lane (R K bf16, it
 // stays in L2) and D is written as two 16-byte stores per lane that together fill whole 32-byte runs.  The loop is unrolled by two, so that
 // the next row of S is in flight during the divisions of this one; 40 - 43 VGPRs, no scratch, 8 waves a SIMD.  Measured:
 // 2.4 - 3.3 TB/s of its (2 + 4 R) bytes an element on the Llama-3-8B shapes, 1 - 2 % of a search, whose time is the host's fp32 matmul.
 //
-// unpack_bf16x8 and group_range are COPIES of qat_kernels.hip's (the same lines, the same arithmetic): sharing them through a header would
-// move them out of that file's anonymous namespace, and this change leaves what qat_kernels.hip compiles to alone.  int4_fq_value is not
-// used: it is the fake quantizer's (q - 8) s + z with fp32 qparams, one rounding fewer than the stored weight above.
+// The lane helpers (unpack_bf16x8, group_range) and the recipe (int4_group_qparams, int4_group_code) are quant_math.h's, the lines
+// ao_int4_plain_quantize runs.  The fake quantizer's int4_fq_value is not used: it is (q - 8) s + z with fp32 qparams, one rounding fewer
+// than the stored weight above.
 #include "common.h"
+#include "quant_math.h"
 
 namespace ao {
 namespace {
 
 constexpr int kThreads = 256;
 
-__device__ __forceinline__ void unpack_bf16x8(const u32x4& v, float (&f)[8]) {
-  f[0] = bf16_lo_to_f32(v.x), f[1] = bf16_hi_to_f32(v.x), f[2] = bf16_lo_to_f32(v.y), f[3] = bf16_hi_to_f32(v.y);
-  f[4] = bf16_lo_to_f32(v.z), f[5] = bf16_hi_to_f32(v.z), f[6] = bf16_lo_to_f32(v.w), f[7] = bf16_hi_to_f32(v.w);
-}
-
-template <int LANES>
-__device__ __forceinline__ void group_range(const float (&x)[8], float& mx, float& mn) {
-  mx = x[0], mn = x[0];
-#pragma unroll
-  for (int j = 1; j < 8; ++j) {
-    mx = fmaxf(mx, x[j]);
-    mn = fminf(mn, x[j]);
-  }
-#pragma unroll
-  for (int off = 1; off < LANES; off <<= 1) {
-    mx = fmaxf(mx, __shfl_xor(mx, off));
-    mn = fminf(mn, __shfl_xor(mn, off));
-  }
-}
-
 // one element's D from its weight w, its scaled weight ws, its candidate scale sc and the group's m, s, bf16(s), bf16(z)
 __device__ __forceinline__ float awq_error_value(float w, float ws, float sc, float m, float s, float sb, float zb) {
 #pragma clang fp contract(off)
-  const float q = fminf(fmaxf(rintf((ws - m) / s), 0.f), 15.f) - 8.f;
+  const float q = int4_group_code(ws, m, s) - 8.f;
   const float p = round_bf16(q * sb);
   const float dq = round_bf16(p + zb);
   const float back = dq / sc;
@@ -73,13 +54,12 @@ __global__ __launch_bounds__(kThreads) void awq_scaled_error_kernel(const u32x4*
   unpack_bf16x8(raw, x);
 #pragma unroll 2
   for (int r = 0; r < R; ++r) {
-    float sc[8], ws[8], M, m;
+    float sc[8], ws[8], M, m, s, z;
     unpack_bf16x8(srow[(int64_t)r * kvec], sc);
 #pragma unroll
     for (int j = 0; j < 8; ++j) ws[j] = round_bf16(x[j] * sc[j]);
     group_range<G / 8>(ws, M, m);
-    const float s = fmaxf(M - m, 1e-6f) / 15.0f;
-    const float z = m + s * 8.0f;  // (8 s is exact: one rounding)
+    int4_group_qparams(M, m, s, z);
     const float sb = round_bf16(s), zb = round_bf16(z);
 #pragma unroll
     for (int j = 0; j < 8; ++j) ws[j] = awq_error_value(x[j], ws[j], sc[j], m, s, sb, zb);
@@ -116,12 +96,9 @@ extern "C" int ao_awq_scaled_error(const uint16_t* w, const uint16_t* scales, fl
   const u32x4* wv = reinterpret_cast<const u32x4*>(w);
   const u32x4* sv = reinterpret_cast<const u32x4*>(scales);
   f32x4* dv = reinterpret_cast<f32x4*>(d);
-  switch (group_size) {
-    case 32: ao::launch(awq_scaled_error_kernel<32>, grid, block, 0, st, wv, sv, dv, nvec, kvec, (int)R); break;
-    case 64: ao::launch(awq_scaled_error_kernel<64>, grid, block, 0, st, wv, sv, dv, nvec, kvec, (int)R); break;
-    case 128: ao::launch(awq_scaled_error_kernel<128>, grid, block, 0, st, wv, sv, dv, nvec, kvec, (int)R); break;
-    default: ao::launch(awq_scaled_error_kernel<256>, grid, block, 0, st, wv, sv, dv, nvec, kvec, (int)R); break;
-  }
+  with_group_size(group_size, [&](auto g) {
+    ao::launch(awq_scaled_error_kernel<decltype(g)::value>, grid, block, 0, st, wv, sv, dv, nvec, kvec, (int)R);
+  });
   AO_LAUNCH_CHECK("awq_scaled_error_kernel launch");
   return AO_OK;
 }

@@ -69,6 +69,41 @@ inline void launch(K kernel, dim3 grid, dim3 block, size_t smem, hipStream_t str
   }
 }
 
+// ---- host side: the two launch ladders -----------------------------------------
+// A group size of {32, 64, 128, 256} (the entry has checked the set) as a compile-time G: f(std::integral_constant<int, G>{}).
+template <typename F>
+inline auto with_group_size(int group_size, F&& f) {
+  switch (group_size) {
+    case 32: return f(std::integral_constant<int, 32>{});
+    case 64: return f(std::integral_constant<int, 64>{});
+    case 128: return f(std::integral_constant<int, 128>{});
+    default: return f(std::integral_constant<int, 256>{});
+  }
+}
+
+constexpr int kRowThreads = 256;  // the workgroup of the kernels that own a row: four waves (block_max / block_sum below)
+
+// The register depth of a row kernel: NV = 1, 2, 4 or 8 16-byte vectors a thread, the least that holds a row of `row_elems` 2-byte elements
+// in the registers of kRowThreads threads: f(std::integral_constant<int, NV>{}).  False, and f not called, where the row is longer (K > 16384).
+template <typename F>
+inline bool with_row_depth(int64_t row_elems, F&& f) {
+  const int64_t per_thread = ((row_elems >> 3) + kRowThreads - 1) / kRowThreads;
+  if (per_thread <= 1) f(std::integral_constant<int, 1>{});
+  else if (per_thread <= 2) f(std::integral_constant<int, 2>{});
+  else if (per_thread <= 4) f(std::integral_constant<int, 4>{});
+  else if (per_thread <= 8) f(std::integral_constant<int, 8>{});
+  else return false;
+  return true;
+}
+
+// the shape rules of the entries that take M rows of K elements, K a multiple of `mult`
+inline int check_rows(const char* fn, int64_t M, int64_t K, int64_t mult) {
+  AO_REQUIRE(M >= 0 && K > 0, "%s: bad shape M=%lld K=%lld", fn, (long long)M, (long long)K);
+  AO_REQUIRE(K % mult == 0, "%s: K=%lld must be a multiple of %lld", fn, (long long)K, (long long)mult);
+  AO_REQUIRE(M < (1ll << 31), "%s: M=%lld too large", fn, (long long)M);
+  return AO_OK;
+}
+
 // ---- device side -----------------------------------------------------------
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -139,6 +174,26 @@ __device__ __forceinline__ float wave_max(float m) {
   const float c = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, m), 32));
   const float d = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, m), 48));
   return fmaxf(fmaxf(a, b), fmaxf(c, d));
+}
+
+// max / sum over the kRowThreads threads of a workgroup, in every one of them: the wave's own reduction, then the four waves meet in `red`
+// (4 floats of LDS, free again on return).  max is exact, and the sum's order is fixed, so every launch gives the same bytes.
+__device__ __forceinline__ float block_max(float v, float* red) {
+  v = wave_max(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  v = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  __syncthreads();
+  return v;
+}
+__device__ __forceinline__ float block_sum(float v, float* red) {
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off);  // every lane ends with the same bits: a + b and b + a round alike
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  v = (red[0] + red[1]) + (red[2] + red[3]);
+  __syncthreads();
+  return v;
 }
 
 }  // namespace ao

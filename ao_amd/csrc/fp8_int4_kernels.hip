@@ -343,12 +343,9 @@ int launch_fp8_int4(const uint8_t* xq, const float* x_scale, const int32_t* qdat
 
 int fp8_int4_dispatch(const uint8_t* xq, const float* x_scale, const int32_t* qdata, const uint16_t* sz, const uint16_t* bias, uint16_t* y, int64_t M,
                       int64_t N, int64_t K, int group_size, hipStream_t s, bool fused) {
-  switch (group_size) {
-    case 32: return launch_fp8_int4<32>(xq, x_scale, qdata, sz, bias, y, M, N, K, s, fused);
-    case 64: return launch_fp8_int4<64>(xq, x_scale, qdata, sz, bias, y, M, N, K, s, fused);
-    case 128: return launch_fp8_int4<128>(xq, x_scale, qdata, sz, bias, y, M, N, K, s, fused);
-    default: return launch_fp8_int4<256>(xq, x_scale, qdata, sz, bias, y, M, N, K, s, fused);
-  }
+  return with_group_size(group_size, [&](auto g) {
+    return launch_fp8_int4<decltype(g)::value>(xq, x_scale, qdata, sz, bias, y, M, N, K, s, fused);
+  });
 }
 
 int fp8_int4_check(const char* fn, int64_t M, int64_t N, int64_t K, int group_size) {

@@ -257,12 +257,9 @@ extern "C" int ao_fp8_train_quantize_rowwise(const uint16_t* x, uint8_t* q, floa
   AO_REQUIRE_PTR(inv_s);
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)R), block(kThreads);
-  const int64_t per_thread = ((C >> 3) + kThreads - 1) / kThreads;
-  if (per_thread <= 1) ao::launch(fp8_train_quant_rowwise_kernel<1>, grid, block, 0, st, x, q, s, inv_s, pow2, C);
-  else if (per_thread <= 2) ao::launch(fp8_train_quant_rowwise_kernel<2>, grid, block, 0, st, x, q, s, inv_s, pow2, C);
-  else if (per_thread <= 4) ao::launch(fp8_train_quant_rowwise_kernel<4>, grid, block, 0, st, x, q, s, inv_s, pow2, C);
-  else if (per_thread <= 8) ao::launch(fp8_train_quant_rowwise_kernel<8>, grid, block, 0, st, x, q, s, inv_s, pow2, C);
-  else ao::launch(fp8_train_quant_rowwise_kernel<0>, grid, block, 0, st, x, q, s, inv_s, pow2, C);
+  static_assert(kThreads == kRowThreads, "with_row_depth sizes NV for kRowThreads threads");
+  auto go = [&](auto nv) { ao::launch(fp8_train_quant_rowwise_kernel<decltype(nv)::value>, grid, block, 0, st, x, q, s, inv_s, pow2, C); };
+  if (!with_row_depth(C, go)) go(std::integral_constant<int, 0>{});  // longer rows: the walking form
   AO_LAUNCH_CHECK("fp8_train_quant_rowwise_kernel launch");
   return AO_OK;
 }

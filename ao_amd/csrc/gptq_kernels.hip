@@ -15,7 +15,8 @@
 //   the code of column k: quantize(its value after its own update) under the frozen qparams
 // The formats:
 //   int4 (zero-point flavour, api.py:167-221; qparams of mslk's int4_row_quantize_zp as include/ao_mi355.h states them for
-//     ao_int4_plain_quantize):  scale = max(max - min, 1e-6) / 15;  zero = min + 8 scale;  m = zero - 8 scale;
+//     ao_int4_plain_quantize):  scale = max(max - min, 1e-6) / 15;  zero = min + 8 scale  (int4_group_qparams, quant_math.h: the one
+//     definition);  m = zero - 8 scale, which is this file's own and not always the group's min, so the code lines stay here too:
 //     q = clamp(rint((w - m) / scale), 0, 15) - 8;  dq = (q + 8) scale + m.   PARITY UNPINNED: that the in-loop qparams stay fp32 (they are
 //     rounded to the weight dtype only where they are stored) is this library's reading of the un-vendored mslk package.
 //   NVFP4 (api.py:224-274; nvfp4_tensor.py:772-854), p the per-tensor scale:  s8 = e4m3(clamp((amax / 6) / p, 2^-6, 448));
@@ -75,11 +76,8 @@ __device__ __forceinline__ QP group_qparams(float mx, float mn, float p_or_s) {
 #pragma clang fp contract(off)
   QP q;
   if (FMT == F_INT4) {
-    const float s = fmaxf(mx - mn, 1e-6f) / 15.0f;
-    const float t = s * 8.0f;
-    q.z = mn + t;
-    q.a = s;
-    q.b = q.z - t;  // min_val = zero - scale * 8 (api.py:183, :217), not the group's min
+    int4_group_qparams(mx, mn, q.a, q.z);  // the shared (scale, zero)
+    q.b = q.z - q.a * 8.0f;                // min_val = zero - scale * 8 (api.py:183, :217), not the group's min: GPTQ codes against its own m
   } else if (FMT == F_NVFP4) {
     const float amax = fmaxf(mx, -mn);
     const float bs = (amax / 6.0f) / p_or_s;

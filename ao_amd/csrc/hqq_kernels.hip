@@ -157,10 +157,5 @@ extern "C" int ao_int4_quantize_hqq(const uint16_t* w, uint8_t* nibble_bytes, ui
   double* err = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + ((2 * groups * sizeof(float) + 7) & ~(size_t)7));
   uint32_t* sz = reinterpret_cast<uint32_t*>(scale_and_zero);
   hipStream_t s = (hipStream_t)stream;
-  switch (group_size) {
-    case 32: return run_hqq<32>(w, nibble_bytes, sz, params, err, N, K, s);
-    case 64: return run_hqq<64>(w, nibble_bytes, sz, params, err, N, K, s);
-    case 128: return run_hqq<128>(w, nibble_bytes, sz, params, err, N, K, s);
-    default: return run_hqq<256>(w, nibble_bytes, sz, params, err, N, K, s);
-  }
+  return with_group_size(group_size, [&](auto g) { return run_hqq<decltype(g)::value>(w, nibble_bytes, sz, params, err, N, K, s); });
 }

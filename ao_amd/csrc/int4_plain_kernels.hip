@@ -5,7 +5,8 @@
 // int4_row_quantize / pack_int4, pinned mslk==1.3.0 in .github/workflows/1xH100_tests.yml:33).  Its published algorithm is
 // restated inside the reference itself -- torchao/quantization/qat/fake_quantizer.py:148-190 ("simulates the numerics of
 // mslk.quantize.shuffle.int4_row_quantize[_zp]") and torchao/prototype/gptq/api.py:167-221 -- and that is what this kernel
-// replays, in fp32 like them:
+// replays, in fp32 like them.  The recipe has ONE definition, quant_math.h's int4_group_qparams / int4_group_scale_sym / int4_group_code, which
+// the QAT fake quantizer, the AWQ search and GPTQ run as well:
 //   asymmetric (bf16 activations):  scale = max(max - min, 1e-6) / 15;  zero = min + 8 scale;
 //                                   q = clamp(rint((w - min) / scale), 0, 15) - 8
 //   symmetric  (fp8 activations):   scale = max(max|w| / 8, 1e-6);  zero = 0;  q = clamp(rint(w / scale), -8, 7)
@@ -16,6 +17,7 @@
 // host side re-lays a PLAIN weight into the tile-packed layout once (ao_amd/quantization/int4_plain_tensor.py) and the
 // existing _weight_int4pack_mm kernels serve it.
 #include "common.h"
+#include "quant_math.h"
 
 namespace ao {
 namespace {
@@ -38,12 +40,7 @@ __global__ __launch_bounds__(64) void int4_plain_quantize_kernel(const uint16_t*
   for (int b = 0; b < KB; ++b) {
     u32x4 raw = {0u, 0u, 0u, 0u};
     if (live) raw = *reinterpret_cast<const u32x4*>(w + row * K + k0 + b * 128);
-    const uint32_t r[4] = {raw.x, raw.y, raw.z, raw.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      v[b][2 * i] = bf16_lo_to_f32(r[i]);
-      v[b][2 * i + 1] = bf16_hi_to_f32(r[i]);
-    }
+    unpack_bf16x8(raw, v[b]);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const float a = SYM ? fabsf(v[b][i]) : v[b][i];
@@ -56,23 +53,15 @@ __global__ __launch_bounds__(64) void int4_plain_quantize_kernel(const uint16_t*
     mx = fmaxf(mx, __shfl_xor(mx, off));
     mn = fminf(mn, __shfl_xor(mn, off));
   }
-  float s, z, base;
-  if (SYM) {
-    s = fmaxf(mx / 8.0f, 1e-6f);
-    z = 0.f;
-    base = 0.f;
-  } else {
-    s = fmaxf(mx - mn, 1e-6f) / 15.0f;
-    z = mn + s * 8.0f;
-    base = mn;
-  }
+  float s, z = 0.f;
+  if (SYM) s = int4_group_scale_sym(mx);
+  else int4_group_qparams(mx, mn, s, z);
 #pragma unroll
   for (int b = 0; b < KB; ++b) {
     uint32_t word = 0;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-      float q = rintf((v[b][i] - base) / s);  // IEEE division, like torch
-      q = SYM ? fminf(fmaxf(q, -8.f), 7.f) : (fminf(fmaxf(q, 0.f), 15.f) - 8.f);
+      const float q = SYM ? fminf(fmaxf(rintf(v[b][i] / s), -8.f), 7.f) : int4_group_code(v[b][i], mn, s) - 8.f;  // IEEE division, like torch
       word |= ((uint32_t)(int)q & 0xFu) << (4 * i);  // even k -> low nibble of its byte
     }
     if (live) *reinterpret_cast<uint32_t*>(qdata + row * (K / 2) + (k0 + b * 128) / 2) = word;
@@ -90,12 +79,9 @@ int launch_plain_quantize(const uint16_t* w, uint8_t* qdata, uint16_t* scale, ui
   const int64_t blocks = ((N + 3) / 4) * (K / (128 * kb));
   AO_REQUIRE(blocks < (1ll << 31), "ao_int4_plain_quantize: tensor too large for one launch");
   dim3 grid((unsigned)blocks), block(64);
-  switch (g) {
-    case 32: ao::launch(int4_plain_quantize_kernel<32, SYM>, grid, block, 0, s, w, qdata, scale, zero, N, K); break;
-    case 64: ao::launch(int4_plain_quantize_kernel<64, SYM>, grid, block, 0, s, w, qdata, scale, zero, N, K); break;
-    case 128: ao::launch(int4_plain_quantize_kernel<128, SYM>, grid, block, 0, s, w, qdata, scale, zero, N, K); break;
-    default: ao::launch(int4_plain_quantize_kernel<256, SYM>, grid, block, 0, s, w, qdata, scale, zero, N, K); break;
-  }
+  with_group_size(g, [&](auto gs) {
+    ao::launch(int4_plain_quantize_kernel<decltype(gs)::value, SYM>, grid, block, 0, s, w, qdata, scale, zero, N, K);
+  });
   AO_LAUNCH_CHECK("int4_plain_quantize_kernel launch");
   return AO_OK;
 }

@@ -4,7 +4,8 @@
 //   int4 : qat/fake_quantizer.py:167-187 (Int4WeightFakeQuantizer._bf16_activations_forward), in fp32, per group of g along K:
 //            M = max, m = min;  s = max(M - m, 1e-6) / 15;  z = m + 8 s
 //            q = clamp(rint((w - m) / s), 0, 15);  out = bf16((q - 8) s + z)        (two roundings: the product, then the sum)
-//          The codes are those of ao_int4_plain_quantize (int4_plain_kernels.hip), which is what `convert` stores.
+//          s, z and q are int4_group_qparams and int4_group_code (quant_math.h), the lines ao_int4_plain_quantize runs: the codes are the
+//          ones `convert` stores.
 //   fp8  : qat/fake_quantizer.py:84-98 (Float8FakeQuantizer.forward, PerRow, e4m3) over quant_primitives.py:2173-2304, per row:
 //            a = clamp(max|x|, lb, ub)                     in the INPUT's dtype: bf16, so lb and ub take effect as bf16 values
 //            s = f32(bf16(a / 448))                        (_choose_scale_float8 divides the bf16 amax: the scale is a bf16 value)
@@ -27,45 +28,15 @@
 namespace ao {
 namespace {
 
-constexpr int kThreads = 256;
+constexpr int kThreads = kRowThreads;
 
-__device__ __forceinline__ void unpack_bf16x8(const u32x4& v, float (&f)[8]) {
-  f[0] = bf16_lo_to_f32(v.x), f[1] = bf16_hi_to_f32(v.x), f[2] = bf16_lo_to_f32(v.y), f[3] = bf16_hi_to_f32(v.y);
-  f[4] = bf16_lo_to_f32(v.z), f[5] = bf16_hi_to_f32(v.z), f[6] = bf16_lo_to_f32(v.w), f[7] = bf16_hi_to_f32(v.w);
-}
-__device__ __forceinline__ u32x4 pack_bf16x8(const float (&f)[8]) {
-  return u32x4{pack_bf16x2(f[0], f[1]), pack_bf16x2(f[2], f[3]), pack_bf16x2(f[4], f[5]), pack_bf16x2(f[6], f[7])};
-}
-
-// ---- int4: the tensor as a flat run of 16-byte vectors, one per lane; a group is LANES = g / 8 adjacent lanes (K % g == 0 keeps groups
-// whole inside a row, and LANES divides the wave), so every group reduction is a butterfly over lanes: no LDS, no atomics ---------------
-template <int LANES>
-__device__ __forceinline__ void group_range(const float (&x)[8], float& mx, float& mn) {
-  mx = x[0], mn = x[0];
-#pragma unroll
-  for (int j = 1; j < 8; ++j) {
-    mx = fmaxf(mx, x[j]);
-    mn = fminf(mn, x[j]);
-  }
-#pragma unroll
-  for (int off = 1; off < LANES; off <<= 1) {
-    mx = fmaxf(mx, __shfl_xor(mx, off));
-    mn = fminf(mn, __shfl_xor(mn, off));
-  }
-}
-// every lane of the group ends with the same bits: a + b and b + a round alike
-template <int LANES>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-  for (int off = 1; off < LANES; off <<= 1) v += __shfl_xor(v, off);
-  return v;
-}
+// ---- int4: the tensor as a flat run of 16-byte vectors, one per lane; a group is G / 8 adjacent lanes.  The lane helpers (unpack_bf16x8,
+// group_range, group_sum) and the recipe (int4_group_qparams, int4_group_code) are quant_math.h's -------------------------------------------
 
 // (q - 8) s + z as the reference's two tensor ops: the product rounded, then the sum
 __device__ __forceinline__ float int4_fq_value(float x, float m, float s, float z) {
 #pragma clang fp contract(off)
-  const float q = fminf(fmaxf(rintf((x - m) / s), 0.f), 15.f);
-  const float p = (q - 8.f) * s;
+  const float p = (int4_group_code(x, m, s) - 8.f) * s;
   return p + z;
 }
 
@@ -75,11 +46,10 @@ __global__ __launch_bounds__(kThreads) void qat_int4_fake_quantize_kernel(const 
   const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   const bool live = i < nvec;  // (a group is live or dead as a whole; dead lanes still take part in the butterflies)
   const u32x4 raw = live ? w[i] : u32x4{0u, 0u, 0u, 0u};
-  float x[8], M, m;
+  float x[8], M, m, s, z;
   unpack_bf16x8(raw, x);
   group_range<G / 8>(x, M, m);
-  const float s = fmaxf(M - m, 1e-6f) / 15.0f;
-  const float z = m + s * 8.0f;  // (8 s is exact: contracted or not, one rounding)
+  int4_group_qparams(M, m, s, z);
 #pragma unroll
   for (int j = 0; j < 8; ++j) x[j] = int4_fq_value(x[j], m, s, z);
   if (live) out[i] = pack_bf16x8(x);
@@ -93,17 +63,17 @@ __global__ __launch_bounds__(kThreads) void qat_int4_fake_quantize_bwd_kernel(co
   const bool live = i < nvec;
   const u32x4 zero4 = {0u, 0u, 0u, 0u};
   const u32x4 raw = live ? w[i] : zero4, graw = live ? go[i] : zero4;
-  float x[8], g[8], M, m;
+  float x[8], g[8], M, m, s, z;
   unpack_bf16x8(raw, x);
   unpack_bf16x8(graw, g);
   group_range<LANES>(x, M, m);
-  const float s = fmaxf(M - m, 1e-6f) / 15.0f;
+  int4_group_qparams(M, m, s, z);  // (z is not used: only the scale and the codes enter the gradient)
   float ds = 0.f, dm = 0.f, n_max = 0.f, n_min = 0.f;
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const float t = (x[j] - m) / s, r = rintf(t);
     const bool inside = r >= 0.f && r <= 15.f;
-    const float q = fminf(fmaxf(r, 0.f), 15.f);
+    const float q = int4_group_code(x[j], m, s);  // (= clamp(r, 0, 15): the same quotient)
     ds += g[j] * (inside ? q - t : q);
     dm += inside ? 0.f : g[j];
     n_max += x[j] == M ? 1.f : 0.f;
@@ -122,24 +92,7 @@ __global__ __launch_bounds__(kThreads) void qat_int4_fake_quantize_bwd_kernel(co
 }
 
 // ---- fp8: a workgroup owns a row.  NV = 16-byte vectors a thread holds (the row stays in registers between the amax and the second
-// use); NV = 0 walks the row again, out of L2 ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float block_max(float m, float* red) {
-  m = wave_max(m);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-  __syncthreads();
-  m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  __syncthreads();  // red is used again
-  return m;
-}
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  v = group_sum<64>(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  v = (red[0] + red[1]) + (red[2] + red[3]);
-  __syncthreads();
-  return v;
-}
-
+// use); NV = 0 walks the row again, out of L2.  block_max / block_sum: common.h ----------------------------------------------------------------
 __device__ __forceinline__ float vec_amax(const u32x4& v) {
   bool has_nan = false;  // (non-finite inputs are outside the contract; amax8 asks for the flag)
   return amax8(v, has_nan);
@@ -317,25 +270,6 @@ int check_fp8(const char* fn, int64_t R, int64_t C, float lb, float ub) {
 
 using namespace ao;
 
-#define AO_QAT_INT4_LAUNCH(KERNEL, ...)                                      \
-  switch (group_size) {                                                      \
-    case 32: ao::launch(KERNEL<32>, grid, block, 0, st, __VA_ARGS__); break;  \
-    case 64: ao::launch(KERNEL<64>, grid, block, 0, st, __VA_ARGS__); break;  \
-    case 128: ao::launch(KERNEL<128>, grid, block, 0, st, __VA_ARGS__); break; \
-    default: ao::launch(KERNEL<256>, grid, block, 0, st, __VA_ARGS__); break; \
-  }
-
-// the register depth that holds ceil(C / 8 / 256) vectors a thread, or the walking form past 8
-#define AO_QAT_FP8_LAUNCH(KERNEL, ...)                                                       \
-  do {                                                                                       \
-    const int64_t per_thread = ((C >> 3) + kThreads - 1) / kThreads;                         \
-    if (per_thread <= 1) ao::launch(KERNEL<1>, grid, block, 0, st, __VA_ARGS__);             \
-    else if (per_thread <= 2) ao::launch(KERNEL<2>, grid, block, 0, st, __VA_ARGS__);        \
-    else if (per_thread <= 4) ao::launch(KERNEL<4>, grid, block, 0, st, __VA_ARGS__);        \
-    else if (per_thread <= 8) ao::launch(KERNEL<8>, grid, block, 0, st, __VA_ARGS__);        \
-    else ao::launch(KERNEL<0>, grid, block, 0, st, __VA_ARGS__);                             \
-  } while (0)
-
 extern "C" int ao_qat_int4_fake_quantize(const uint16_t* w, uint16_t* out, int64_t N, int64_t K, int group_size, void* stream) {
   if (int rc = check_int4(__func__, N, K, group_size)) return rc;
   if (N == 0) return AO_OK;
@@ -345,7 +279,10 @@ extern "C" int ao_qat_int4_fake_quantize(const uint16_t* w, uint16_t* out, int64
   hipStream_t st = (hipStream_t)stream;
   const int64_t nvec = N * K / 8;
   const dim3 grid((unsigned)((nvec + kThreads - 1) / kThreads)), block(kThreads);
-  AO_QAT_INT4_LAUNCH(qat_int4_fake_quantize_kernel, reinterpret_cast<const u32x4*>(w), reinterpret_cast<u32x4*>(out), nvec);
+  with_group_size(group_size, [&](auto g) {
+    ao::launch(qat_int4_fake_quantize_kernel<decltype(g)::value>, grid, block, 0, st, reinterpret_cast<const u32x4*>(w),
+               reinterpret_cast<u32x4*>(out), nvec);
+  });
   AO_LAUNCH_CHECK("qat_int4_fake_quantize_kernel launch");
   return AO_OK;
 }
@@ -362,8 +299,10 @@ extern "C" int ao_qat_int4_fake_quantize_bwd(const uint16_t* w, const uint16_t* 
   hipStream_t st = (hipStream_t)stream;
   const int64_t nvec = N * K / 8;
   const dim3 grid((unsigned)((nvec + kThreads - 1) / kThreads)), block(kThreads);
-  AO_QAT_INT4_LAUNCH(qat_int4_fake_quantize_bwd_kernel, reinterpret_cast<const u32x4*>(w), reinterpret_cast<const u32x4*>(grad_out),
-                     reinterpret_cast<u32x4*>(grad_w), nvec);
+  with_group_size(group_size, [&](auto g) {
+    ao::launch(qat_int4_fake_quantize_bwd_kernel<decltype(g)::value>, grid, block, 0, st, reinterpret_cast<const u32x4*>(w),
+               reinterpret_cast<const u32x4*>(grad_out), reinterpret_cast<u32x4*>(grad_w), nvec);
+  });
   AO_LAUNCH_CHECK("qat_int4_fake_quantize_bwd_kernel launch");
   return AO_OK;
 }
@@ -376,7 +315,8 @@ extern "C" int ao_qat_fp8_fake_quantize_rowwise(const uint16_t* x, uint16_t* out
   AO_REQUIRE(aligned_to(x, 16) && aligned_to(out, 16), "%s: x and out must be 16-byte aligned", __func__);
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)R), block(kThreads);
-  AO_QAT_FP8_LAUNCH(qat_fp8_fake_quantize_rowwise_kernel, x, out, C, lb, ub);
+  auto go = [&](auto nv) { ao::launch(qat_fp8_fake_quantize_rowwise_kernel<decltype(nv)::value>, grid, block, 0, st, x, out, C, lb, ub); };
+  if (!with_row_depth(C, go)) go(std::integral_constant<int, 0>{});  // longer rows: the walking form
   AO_LAUNCH_CHECK("qat_fp8_fake_quantize_rowwise_kernel launch");
   return AO_OK;
 }
@@ -392,7 +332,10 @@ extern "C" int ao_qat_fp8_fake_quantize_rowwise_bwd(const uint16_t* x, const uin
              __func__);
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)R), block(kThreads);
-  AO_QAT_FP8_LAUNCH(qat_fp8_fake_quantize_rowwise_bwd_kernel, x, grad_out, grad_x, C, lb, ub);
+  auto go = [&](auto nv) {
+    ao::launch(qat_fp8_fake_quantize_rowwise_bwd_kernel<decltype(nv)::value>, grid, block, 0, st, x, grad_out, grad_x, C, lb, ub);
+  };
+  if (!with_row_depth(C, go)) go(std::integral_constant<int, 0>{});
   AO_LAUNCH_CHECK("qat_fp8_fake_quantize_rowwise_bwd_kernel launch");
   return AO_OK;
 }

@@ -2,7 +2,8 @@
 // per-row int8, per-row float8 e4m3fn (OCP), and MXFP8 (1x32 blocks, E8M0 scales).
 // Each replays the reference's op sequence exactly (same intermediate dtypes and
 // roundings) in ONE pass over HBM: the row is read once (kept L2-hot for the
-// second sweep), reduced, and written once as 1 B/element.
+// second sweep), reduced, and written once as 1 B/element.  The int8 casts also come with an activation pre-scale folded in
+// (ao_int8_quantize_*_prescaled: SmoothQuant's `x * act_pre_scale`): the same kernels, PRE = true (load8 below).
 //
 // Reference (torchao 0.19.0 snapshot):
 //   int8 : quantization/quantize_/workflows/int8/int8_tensor.py:191-230,
@@ -18,45 +19,47 @@
 namespace ao {
 namespace {
 
-constexpr int kThreads = 256;
+constexpr int kThreads = kRowThreads;  // (block_max: common.h)
 
-__device__ __forceinline__ float block_max(float v, float* red) {
-  // wave reduce then across the 4 waves of the block
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) red[wave] = v;
-  __syncthreads();
-  v = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  __syncthreads();
-  return v;
+// The one place the casts of x and the casts of t = bf16(x * pre) differ (SmoothQuant / AWQ's `x * act_pre_scale` followed by the activation
+// cast, int8_tensor.py:266-300): PRE feeds prescale8(x, pre) (quant_math.h) where the plain cast feeds x, so the bf16 product is never written
+// and the PRE casts are byte for byte the plain ones run on `x * pre`.  `pre` is read again by every row's workgroup; it is 2 K bytes and
+// stays in L2.  Instantiated: int8 with and without `pre`, fp8 without.
+template <bool PRE>
+__device__ __forceinline__ u32x4 load8(const u32x4* xr, const u32x4* pr, int64_t i) {
+  if constexpr (PRE) return prescale8(xr[i], pr[i]);
+  else return xr[i];
 }
 
 // ---- int8 per-row symmetric ----------------------------------------------------
 // scale = f32(max(bf16(amax / 127.5), bf16(f32_eps)));  q = clamp(rint(x * (1/scale)), -128, 127)
-// `amax_in` (optional): the row's amax over the FULL K when x is only a K shard of the activation (row-parallel TP linears:
-// the scale must be the unsharded one); `ldx`: row stride of x in elements.
+// `amax_in` (optional), read at [row * amax_stride]: stride 1, the row's amax over the FULL K when x is only a K shard of the activation
+// (row-parallel TP linears: the scale must be the unsharded one); stride 0, ONE amax for every row (the PerTensor cast's, measured by
+// prescaled_amax_kernel below).  `ldx`: row stride of x in elements.
+template <bool PRE>
 __global__ __launch_bounds__(kThreads) void int8_quant_rowwise_kernel(const uint16_t* __restrict__ x, int64_t ldx,
-                                                                      const float* __restrict__ amax_in,
+                                                                      const uint16_t* __restrict__ pre,
+                                                                      const float* __restrict__ amax_in, int amax_stride,
                                                                       int8_t* __restrict__ q,
                                                                       float* __restrict__ scale, int64_t K) {
   __shared__ float red[4];
   const int64_t row = blockIdx.x;
   const u32x4* xr = reinterpret_cast<const u32x4*>(x + row * ldx);
+  const u32x4* pr = reinterpret_cast<const u32x4*>(pre);
   const int64_t nvec = K >> 3;  // 8 bf16 per 16 B
   float m = 0.f;
   if (amax_in != nullptr) {
-    m = amax_in[row];
+    m = amax_in[blockIdx.x * (uint32_t)amax_stride];  // (M < 2^31 and a stride of 0 or 1: 32 bits hold the product)
   } else {
     bool has_nan = false;
-    for (int64_t i = threadIdx.x; i < nvec; i += kThreads) m = fmaxf(m, amax8(xr[i], has_nan));
+    for (int64_t i = threadIdx.x; i < nvec; i += kThreads) m = fmaxf(m, amax8(load8<PRE>(xr, pr, i), has_nan));
     m = block_max(has_nan ? INFINITY : m, red);  // (NaN rows are outside the contract)
   }
   const float s = int8_row_scale(m);
   const float inv = 1.0f / s;
   if (threadIdx.x == 0) scale[row] = s;
   u32x2* qr = reinterpret_cast<u32x2*>(q + row * K);
-  for (int64_t i = threadIdx.x; i < nvec; i += kThreads) qr[i] = int8_quant8(xr[i], inv);
+  for (int64_t i = threadIdx.x; i < nvec; i += kThreads) qr[i] = int8_quant8(load8<PRE>(xr, pr, i), inv);
 }
 
 // ---- fp8 e4m3fn per-row ----------------------------------------------------------
@@ -85,23 +88,25 @@ __global__ __launch_bounds__(kThreads) void fp8_quant_rowwise_kernel(const uint1
 
 // ---- the same two casts with the row held in registers between the amax reduction and the cast (K <= 16384): one read of x
 // instead of a second sweep through L2.  NV = 16-byte vectors per thread.
-template <bool INT8, int NV>
+template <bool INT8, int NV, bool PRE>
 __global__ __launch_bounds__(kThreads) void quant_rowwise_reg_kernel(const uint16_t* __restrict__ x, int64_t ldx,
-                                                                     const float* __restrict__ amax_in, uint8_t* __restrict__ q,
-                                                                     float* __restrict__ scale, int64_t K) {
+                                                                     const uint16_t* __restrict__ pre,
+                                                                     const float* __restrict__ amax_in, int amax_stride,
+                                                                     uint8_t* __restrict__ q, float* __restrict__ scale, int64_t K) {
   __shared__ float red[4];
   const int64_t row = blockIdx.x;
   const u32x4* xr = reinterpret_cast<const u32x4*>(x + row * ldx);
+  const u32x4* pr = reinterpret_cast<const u32x4*>(pre);
   const int nvec = (int)(K >> 3);
   u32x4 v[NV];
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int idx = threadIdx.x + i * kThreads;
-    v[i] = (idx < nvec) ? xr[idx] : u32x4{0u, 0u, 0u, 0u};
+    v[i] = (idx < nvec) ? load8<PRE>(xr, pr, idx) : u32x4{0u, 0u, 0u, 0u};
   }
   float m = 0.f;
   if (amax_in != nullptr) {
-    m = amax_in[row];
+    m = amax_in[blockIdx.x * (uint32_t)amax_stride];  // (M < 2^31 and a stride of 0 or 1: 32 bits hold the product)
   } else {
     bool has_nan = false;
 #pragma unroll
@@ -119,17 +124,22 @@ __global__ __launch_bounds__(kThreads) void quant_rowwise_reg_kernel(const uint1
   }
 }
 
-template <bool INT8>
-bool launch_quant_rowwise_reg(const uint16_t* x, int64_t ldx, const float* amax, void* q, float* scale, int64_t M, int64_t K, hipStream_t s) {
-  const int64_t per_thread = ((K >> 3) + kThreads - 1) / kThreads;
-  const dim3 grid((unsigned)M), block(kThreads);
-  uint8_t* qb = reinterpret_cast<uint8_t*>(q);
-  if (per_thread <= 1) ao::launch(quant_rowwise_reg_kernel<INT8, 1>, grid, block, 0, s, x, ldx, amax, qb, scale, K);
-  else if (per_thread <= 2) ao::launch(quant_rowwise_reg_kernel<INT8, 2>, grid, block, 0, s, x, ldx, amax, qb, scale, K);
-  else if (per_thread <= 4) ao::launch(quant_rowwise_reg_kernel<INT8, 4>, grid, block, 0, s, x, ldx, amax, qb, scale, K);
-  else if (per_thread <= 8) ao::launch(quant_rowwise_reg_kernel<INT8, 8>, grid, block, 0, s, x, ldx, amax, qb, scale, K);
-  else return false;  // longer rows: the two-sweep kernels
-  return true;
+// the register form where the row fits (K <= 16384); false where it does not: the caller launches its two-sweep kernel
+template <bool INT8, bool PRE>
+bool launch_quant_rowwise_reg(const uint16_t* x, int64_t ldx, const uint16_t* pre, const float* amax, int amax_stride, void* q, float* scale,
+                              int64_t M, int64_t K, hipStream_t s) {
+  return with_row_depth(K, [&](auto nv) {
+    ao::launch(quant_rowwise_reg_kernel<INT8, decltype(nv)::value, PRE>, dim3((unsigned)M), dim3(kThreads), 0, s, x, ldx, pre, amax, amax_stride,
+               reinterpret_cast<uint8_t*>(q), scale, K);
+  });
+}
+
+// the int8 cast of x (PRE = false, pre unused) or of bf16(x * pre), in whichever form the row takes
+template <bool PRE>
+void launch_int8_rowwise(const uint16_t* x, int64_t ldx, const uint16_t* pre, const float* amax, int amax_stride, int8_t* q, float* scale,
+                         int64_t M, int64_t K, hipStream_t s) {
+  if (!launch_quant_rowwise_reg<true, PRE>(x, ldx, pre, amax, amax_stride, q, scale, M, K, s))
+    ao::launch(int8_quant_rowwise_kernel<PRE>, dim3((unsigned)M), dim3(kThreads), 0, s, x, ldx, pre, amax, amax_stride, q, scale, K);
 }
 
 // ---- per-row amax of a (possibly strided) bf16 matrix: the local half of a full-K activation scale under K sharding -----
@@ -143,6 +153,21 @@ __global__ __launch_bounds__(kThreads) void rowwise_amax_kernel(const uint16_t* 
   for (int64_t i = threadIdx.x; i < (K >> 3); i += kThreads) m = fmaxf(m, amax8(xr[i], has_nan));
   m = block_max(has_nan ? INFINITY : m, red);
   if (threadIdx.x == 0) amax[row] = m;
+}
+
+// the PerTensor cast's first half on t = bf16(x * pre): max |t| over the whole activation, one atomic per row on the BIT PATTERN (a
+// non-negative float's bits order as unsigned integers; `amax` holds zero before the launch).  ops.int8_quantize_tensorwise takes the same
+// maximum with rowwise_amax + amax; max is exact, so the order does not matter.
+__global__ __launch_bounds__(kThreads) void prescaled_amax_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ pre,
+                                                                  uint32_t* __restrict__ amax, int64_t K) {
+  __shared__ float red[4];
+  const u32x4* xr = reinterpret_cast<const u32x4*>(x + (int64_t)blockIdx.x * K);
+  const u32x4* pr = reinterpret_cast<const u32x4*>(pre);
+  float m = 0.f;
+  bool has_nan = false;
+  for (int64_t i = threadIdx.x; i < (K >> 3); i += kThreads) m = fmaxf(m, amax8(load8<true>(xr, pr, i), has_nan));
+  m = block_max(has_nan ? INFINITY : m, red);
+  if (threadIdx.x == 0 && m != 0.f) atomicMax(amax, f32_to_bits(m));
 }
 
 // ---- scale epilogues over all-reduced accumulators (row-parallel TP linears): the arithmetic of the fused GEMM epilogues ----
@@ -174,13 +199,12 @@ __global__ __launch_bounds__(kThreads) void int8_quant_rowwise_asym_kernel(const
   const int64_t nvec = K >> 3;
   float mx = 0.f, mn = 0.f;  // the zero each is clamped against is the identity here
   for (int64_t i = threadIdx.x; i < nvec; i += kThreads) {
-    const u32x4 v = xr[i];
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    float f[8];
+    unpack_bf16x8(xr[i], f);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float a = bf16_lo_to_f32(w[j]), b = bf16_hi_to_f32(w[j]);
-      mx = fmaxf(mx, fmaxf(a, b));
-      mn = fminf(mn, fminf(a, b));
+    for (int j = 0; j < 8; j += 2) {
+      mx = fmaxf(mx, fmaxf(f[j], f[j + 1]));
+      mn = fminf(mn, fminf(f[j], f[j + 1]));
     }
   }
   mx = block_max(mx, red);
@@ -198,15 +222,17 @@ __global__ __launch_bounds__(kThreads) void int8_quant_rowwise_asym_kernel(const
 
 // static activation quantization (Int8StaticActivationInt8WeightConfig: Int8Tensor.from_hp(x, scale=..., zero_point=...), int8_tensor.py:
 // 212-231): q = clamp(rint(x * (1 / scale)) + zp, -128, 127) with the GIVEN scale / zero-point, one per tensor (stride 0) or per row
-__global__ __launch_bounds__(kThreads) void int8_quant_static_kernel(const uint16_t* __restrict__ x, const float* __restrict__ scale,
-                                                                     const int8_t* __restrict__ zero_point, int stride,
-                                                                     int8_t* __restrict__ q, int64_t K) {
+template <bool PRE>
+__global__ __launch_bounds__(kThreads) void int8_quant_static_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ pre,
+                                                                     const float* __restrict__ scale, const int8_t* __restrict__ zero_point,
+                                                                     int stride, int8_t* __restrict__ q, int64_t K) {
   const int64_t row = blockIdx.x;
   const u32x4* xr = reinterpret_cast<const u32x4*>(x + row * K);
+  const u32x4* pr = reinterpret_cast<const u32x4*>(pre);
   const float inv = 1.0f / scale[row * stride];
   const float zp = zero_point != nullptr ? (float)zero_point[row * stride] : 0.0f;
   u32x2* qr = reinterpret_cast<u32x2*>(q + row * K);
-  for (int64_t i = threadIdx.x; i < (K >> 3); i += kThreads) qr[i] = int8_quant8_zp(xr[i], inv, zp);
+  for (int64_t i = threadIdx.x; i < (K >> 3); i += kThreads) qr[i] = int8_quant8_zp(load8<PRE>(xr, pr, i), inv, zp);
 }
 
 // row sums of an int8 [N][K] weight (the zero-point correction's rowsum(W), int8_tensor.py:326): one wave per row
@@ -357,13 +383,6 @@ __global__ __launch_bounds__(kThreads) void mxfp8_quant_colwise_kernel(const uin
   }
 }
 
-int check_rows(const char* fn, int64_t M, int64_t K, int64_t mult) {
-  AO_REQUIRE(M >= 0 && K > 0, "%s: bad shape M=%lld K=%lld", fn, (long long)M, (long long)K);
-  AO_REQUIRE(K % mult == 0, "%s: K=%lld must be a multiple of %lld", fn, (long long)K, (long long)mult);
-  AO_REQUIRE(M < (1ll << 31), "%s: M=%lld too large", fn, (long long)M);
-  return AO_OK;
-}
-
 }  // namespace
 }  // namespace ao
 
@@ -376,8 +395,7 @@ extern "C" int ao_int8_quantize_rowwise(const uint16_t* x, int8_t* q, float* sca
   AO_REQUIRE_PTR(x);
   AO_REQUIRE_PTR(q);
   AO_REQUIRE_PTR(scale);
-  if (!launch_quant_rowwise_reg<true>(x, K, nullptr, q, scale, M, K, (hipStream_t)stream))
-    ao::launch(int8_quant_rowwise_kernel, dim3((unsigned)M), dim3(kThreads), 0, (hipStream_t)stream, x, K, (const float*)nullptr, q, scale, K);
+  launch_int8_rowwise<false>(x, K, nullptr, nullptr, 1, q, scale, M, K, (hipStream_t)stream);
   AO_LAUNCH_CHECK("int8_quant_rowwise_kernel launch");
   return AO_OK;
 }
@@ -389,7 +407,7 @@ extern "C" int ao_fp8_quantize_rowwise(const uint16_t* x, uint8_t* q, float* sca
   AO_REQUIRE_PTR(x);
   AO_REQUIRE_PTR(q);
   AO_REQUIRE_PTR(scale);
-  if (!launch_quant_rowwise_reg<false>(x, K, nullptr, q, scale, M, K, (hipStream_t)stream))
+  if (!launch_quant_rowwise_reg<false, false>(x, K, nullptr, nullptr, 1, q, scale, M, K, (hipStream_t)stream))
     ao::launch(fp8_quant_rowwise_kernel, dim3((unsigned)M), dim3(kThreads), 0, (hipStream_t)stream, x, K, (const float*)nullptr, q, scale, K);
   AO_LAUNCH_CHECK("fp8_quant_rowwise_kernel launch");
   return AO_OK;
@@ -472,8 +490,7 @@ extern "C" int ao_int8_quantize_rowwise_amax(const uint16_t* x, int64_t ldx, con
   AO_REQUIRE_PTR(amax);
   AO_REQUIRE_PTR(q);
   AO_REQUIRE_PTR(scale);
-  if (!launch_quant_rowwise_reg<true>(x, ldx, amax, q, scale, M, K, (hipStream_t)stream))
-    ao::launch(int8_quant_rowwise_kernel, dim3((unsigned)M), dim3(kThreads), 0, (hipStream_t)stream, x, ldx, amax, q, scale, K);
+  launch_int8_rowwise<false>(x, ldx, nullptr, amax, 1, q, scale, M, K, (hipStream_t)stream);
   AO_LAUNCH_CHECK("int8_quant_rowwise_kernel launch");
   return AO_OK;
 }
@@ -486,7 +503,7 @@ extern "C" int ao_fp8_quantize_rowwise_amax(const uint16_t* x, int64_t ldx, cons
   AO_REQUIRE_PTR(amax);
   AO_REQUIRE_PTR(q);
   AO_REQUIRE_PTR(scale);
-  if (!launch_quant_rowwise_reg<false>(x, ldx, amax, q, scale, M, K, (hipStream_t)stream))
+  if (!launch_quant_rowwise_reg<false, false>(x, ldx, nullptr, amax, 1, q, scale, M, K, (hipStream_t)stream))
     ao::launch(fp8_quant_rowwise_kernel, dim3((unsigned)M), dim3(kThreads), 0, (hipStream_t)stream, x, ldx, amax, q, scale, K);
   AO_LAUNCH_CHECK("fp8_quant_rowwise_kernel launch");
   return AO_OK;
@@ -544,7 +561,59 @@ extern "C" int ao_int8_quantize_static(const uint16_t* x, const float* scale, co
   AO_REQUIRE_PTR(x);
   AO_REQUIRE_PTR(scale);
   AO_REQUIRE_PTR(q);
-  ao::launch(int8_quant_static_kernel, dim3((unsigned)M), dim3(kThreads), 0, (hipStream_t)stream, x, scale, zero_point, per_row ? 1 : 0, q, K);
+  ao::launch(int8_quant_static_kernel<false>, dim3((unsigned)M), dim3(kThreads), 0, (hipStream_t)stream, x, (const uint16_t*)nullptr, scale,
+             zero_point, per_row ? 1 : 0, q, K);
+  AO_LAUNCH_CHECK("int8_quant_static_kernel launch");
+  return AO_OK;
+}
+
+// ---- the int8 casts on t = bf16(x * pre), the product never written (SmoothQuant's act_pre_scale): the PRE = true kernels ----------------
+extern "C" int ao_int8_quantize_rowwise_prescaled(const uint16_t* x, const uint16_t* pre, int8_t* q, float* scale, int64_t M, int64_t K,
+                                                  void* stream) {
+  if (int rc = check_rows(__func__, M, K, 8)) return rc;
+  if (M == 0) return AO_OK;
+  AO_REQUIRE_PTR(x);
+  AO_REQUIRE_PTR(pre);
+  AO_REQUIRE_PTR(q);
+  AO_REQUIRE_PTR(scale);
+  AO_REQUIRE(aligned_to(x, 16) && aligned_to(pre, 16) && aligned_to(q, 8), "%s: x and pre must be 16-byte aligned and q 8-byte aligned", __func__);
+  launch_int8_rowwise<true>(x, K, pre, nullptr, 0, q, scale, M, K, (hipStream_t)stream);
+  AO_LAUNCH_CHECK("int8_quant_rowwise_kernel launch");
+  return AO_OK;
+}
+
+extern "C" int ao_int8_quantize_tensorwise_prescaled(const uint16_t* x, const uint16_t* pre, float* amax, int8_t* q, float* scale, int64_t M,
+                                                     int64_t K, void* stream) {
+  if (int rc = check_rows(__func__, M, K, 8)) return rc;
+  if (M == 0) return AO_OK;
+  AO_REQUIRE_PTR(x);
+  AO_REQUIRE_PTR(pre);
+  AO_REQUIRE_PTR(amax);
+  AO_REQUIRE_PTR(q);
+  AO_REQUIRE_PTR(scale);
+  AO_REQUIRE(aligned_to(x, 16) && aligned_to(pre, 16) && aligned_to(q, 8) && aligned_to(amax, 4),
+             "%s: x and pre must be 16-byte aligned, q 8-byte and amax 4-byte aligned", __func__);
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t e = hipMemsetAsync(amax, 0, sizeof(float), s);
+  if (e != hipSuccess) return ::ao::hip_failed(e, "hipMemsetAsync(amax)");
+  ao::launch(prescaled_amax_kernel, dim3((unsigned)M), dim3(kThreads), 0, s, x, pre, reinterpret_cast<uint32_t*>(amax), K);
+  AO_LAUNCH_CHECK("prescaled_amax_kernel launch");
+  launch_int8_rowwise<true>(x, K, pre, amax, 0, q, scale, M, K, s);  // stride 0: the one amax for every row
+  AO_LAUNCH_CHECK("int8_quant_rowwise_kernel launch");
+  return AO_OK;
+}
+
+extern "C" int ao_int8_quantize_static_prescaled(const uint16_t* x, const uint16_t* pre, const float* scale, const int8_t* zero_point, int per_row,
+                                                 int8_t* q, int64_t M, int64_t K, void* stream) {
+  if (int rc = check_rows(__func__, M, K, 8)) return rc;
+  if (M == 0) return AO_OK;
+  AO_REQUIRE_PTR(x);
+  AO_REQUIRE_PTR(pre);
+  AO_REQUIRE_PTR(scale);
+  AO_REQUIRE_PTR(q);
+  AO_REQUIRE(aligned_to(x, 16) && aligned_to(pre, 16) && aligned_to(q, 8), "%s: x and pre must be 16-byte aligned and q 8-byte aligned", __func__);
+  ao::launch(int8_quant_static_kernel<true>, dim3((unsigned)M), dim3(kThreads), 0, (hipStream_t)stream, x, pre, scale, zero_point,
+             per_row ? 1 : 0, q, K);
   AO_LAUNCH_CHECK("int8_quant_static_kernel launch");
   return AO_OK;
 }

@@ -57,7 +57,7 @@ __device__ __forceinline__ u32x2 int8_quant8_zp(const u32x4& v, float inv, float
 
 // an activation pre-scale (AWQ / SmoothQuant: `x * act_pre_scale`, a bf16 tensor op) folded into a cast: 8 bf16 x 8 bf16 -> 8 bf16,
 // t = bf16_rne(f32(x) * f32(pre)).  Two 8-bit significands give a product of 16 bits, exact in fp32, so the rounding to bf16 is the only
-// one, as in torch's bf16 multiply (fp32 opmath, one conversion).  The casts above then run on t as they do on x (smoothquant_kernels.hip).
+// one, as in torch's bf16 multiply (fp32 opmath, one conversion).  The casts above then run on t as they do on x (quant_kernels.hip, load8).
 __device__ __forceinline__ u32x4 prescale8(const u32x4& x, const u32x4& pre) {
   const uint32_t a[4] = {x.x, x.y, x.z, x.w}, b[4] = {pre.x, pre.y, pre.z, pre.w};
   uint32_t t[4];
@@ -700,6 +700,56 @@ __device__ __forceinline__ void optim_adam_element(float& p, float g, float& m, 
 __device__ __forceinline__ uint32_t optim_sr_bf16(float x, uint32_t r16) {
   const uint32_t b = f32_to_bits(x);
   return ((b & 0xffff0000u) + ((r16 < (b & 0xffffu)) ? 0x10000u : 0u)) >> 16;
+}
+
+// ---- the int4 group recipe (mslk's int4_row_quantize_zp / int4_row_quantize as the reference restates them: qat/fake_quantizer.py:148-190,
+// prototype/gptq/api.py:167-221), in fp32, every step ONE operation rounded once, the divisions IEEE.  Over a group of g elements along K:
+//   asymmetric:  s = max(max - min, 1e-6) / 15;  z = min + 8 s;  q = clamp(rint((w - min) / s), 0, 15)      (stored as q - 8)
+//   symmetric:   s = max(max|w| / 8, 1e-6);      z = 0;          q = clamp(rint(w / s), -8, 7)
+// The ONE definition: ao_int4_plain_quantize (what `convert` stores), the QAT fake quantizer and its backward, the AWQ search and GPTQ's
+// qparams all come here, so "the codes are those of ao_int4_plain_quantize" is a statement about these lines.  What a caller does with a
+// code -- (q - 8) s + z in fp32, the stored weight through bf16(s) and bf16(z), GPTQ's own m = z - 8 s -- is that caller's arithmetic.
+__device__ __forceinline__ void int4_group_qparams(float mx, float mn, float& s, float& z) {
+#pragma clang fp contract(off)
+  s = fmaxf(mx - mn, 1e-6f) / 15.0f;
+  z = mn + s * 8.0f;  // (8 s is exact: contracted or not, one rounding)
+}
+__device__ __forceinline__ float int4_group_scale_sym(float amax) { return fmaxf(amax / 8.0f, 1e-6f); }
+// the unsigned code 0 .. 15 of x in a group of minimum m and scale s
+__device__ __forceinline__ float int4_group_code(float x, float m, float s) {
+#pragma clang fp contract(off)
+  return fminf(fmaxf(rintf((x - m) / s), 0.f), 15.f);
+}
+
+// ---- a tensor as a flat run of 16-byte vectors of 8 bf16, one per lane; a group is LANES = g / 8 adjacent lanes (K % g == 0 keeps groups
+// whole inside a row, and LANES divides the wave), so every group reduction is a butterfly over lanes: no LDS, no atomics -----------------
+__device__ __forceinline__ void unpack_bf16x8(const u32x4& v, float (&f)[8]) {
+  f[0] = bf16_lo_to_f32(v.x), f[1] = bf16_hi_to_f32(v.x), f[2] = bf16_lo_to_f32(v.y), f[3] = bf16_hi_to_f32(v.y);
+  f[4] = bf16_lo_to_f32(v.z), f[5] = bf16_hi_to_f32(v.z), f[6] = bf16_lo_to_f32(v.w), f[7] = bf16_hi_to_f32(v.w);
+}
+__device__ __forceinline__ u32x4 pack_bf16x8(const float (&f)[8]) {
+  return u32x4{pack_bf16x2(f[0], f[1]), pack_bf16x2(f[2], f[3]), pack_bf16x2(f[4], f[5]), pack_bf16x2(f[6], f[7])};
+}
+template <int LANES>
+__device__ __forceinline__ void group_range(const float (&x)[8], float& mx, float& mn) {
+  mx = x[0], mn = x[0];
+#pragma unroll
+  for (int j = 1; j < 8; ++j) {
+    mx = fmaxf(mx, x[j]);
+    mn = fminf(mn, x[j]);
+  }
+#pragma unroll
+  for (int off = 1; off < LANES; off <<= 1) {
+    mx = fmaxf(mx, __shfl_xor(mx, off));
+    mn = fminf(mn, __shfl_xor(mn, off));
+  }
+}
+// every lane of the group ends with the same bits: a + b and b + a round alike
+template <int LANES>
+__device__ __forceinline__ float group_sum(float v) {
+#pragma unroll
+  for (int off = 1; off < LANES; off <<= 1) v += __shfl_xor(v, off);
+  return v;
 }
 
 }  // namespace ao

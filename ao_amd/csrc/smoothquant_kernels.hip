@@ -1,13 +1,11 @@
-// SmoothQuant for gfx950: the two calibration reductions and the int8 activation casts with the smoothing pre-scale folded in.
+// SmoothQuant for gfx950: the two calibration reductions.  (The int8 activation casts with the smoothing pre-scale folded in are the PRE = true
+// instantiations of the casts in quant_kernels.hip, and their entry points live there.)
 //
 // Reference (torchao 0.19.0 snapshot): prototype/smoothquant/core.py:41-75 (x_abs_max, w_abs_max, the amax of example_input / smoothing_factor),
-// :162-206 (the running observer's two passes), and the Int8Tensor linear's `x * act_pre_scale` followed by the activation cast
-// (quantize_/workflows/int8/int8_tensor.py:266-300).  All five kernels are bandwidth-bound streams of 16-byte loads.
+// :162-206 (the running observer's two passes).  Both kernels are bandwidth-bound streams of 16-byte loads.
 //
 //   A  ao_sq_col_absmax_update      state[k] = max(state[k], max_m |x[m,k]|)                    fp32 [K], in place
 //   B  ao_sq_smoothed_amax_update   amax     = max(amax, max_mk |bf16(f32(x[m,k]) / f32(s[k]))|)  fp32 [1], in place
-//   C  ao_int8_quantize_{rowwise,tensorwise,static}_prescaled: the casts of quant_kernels.hip fed t = bf16(f32(x) * f32(pre[k])) (prescale8,
-//      quant_math.h) instead of x, so the bf16 product is never written to memory: byte for byte the twin run on `x * pre`.
 //
 // A and B fold into their state with atomicMax on the BIT PATTERN: a non-negative float's bits order as unsigned integers, every operand is
 // non-negative (|.| clears the sign, so -0.0 counts as 0) and max is exact, so the result does not depend on the order in which workgroups
@@ -29,7 +27,7 @@
 namespace ao {
 namespace {
 
-constexpr int kThreads = 256;
+constexpr int kThreads = kRowThreads;  // (block_max: common.h)
 constexpr int kColTile = 512;     // kernel A: columns per workgroup
 constexpr int kRowsInFlight = 4;  // kernel A: rows a wave has in flight
 constexpr int64_t kTargetBlocks = 2048;  // 8 per CU
@@ -46,17 +44,6 @@ __device__ __forceinline__ void absmax8_update(u32x4& m, const u32x4& v) {
   m.y = pk_max_u16(m.y, v.y & 0x7fff7fffu);
   m.z = pk_max_u16(m.z, v.z & 0x7fff7fffu);
   m.w = pk_max_u16(m.w, v.w & 0x7fff7fffu);
-}
-
-__device__ __forceinline__ float block_max(float v, float* red) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) red[wave] = v;
-  __syncthreads();
-  v = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  __syncthreads();
-  return v;
 }
 
 // ---- A: running per-column absmax ------------------------------------------------------------------------------------------------------------------
@@ -104,132 +91,20 @@ __global__ __launch_bounds__(kThreads) void sq_smoothed_amax_kernel(const uint16
   const int64_t r_end = r_begin + rows_per_block < M ? r_begin + rows_per_block : M;
   float m = 0.f;
   if (c < K) {
-    const u32x4 sv = *reinterpret_cast<const u32x4*>(s + c);
-    const uint32_t sw[4] = {sv.x, sv.y, sv.z, sv.w};
-    float d[8];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) d[2 * j] = bf16_lo_to_f32(sw[j]), d[2 * j + 1] = bf16_hi_to_f32(sw[j]);
+    float d[8], f[8];
+    unpack_bf16x8(*reinterpret_cast<const u32x4*>(s + c), d);
 #pragma unroll 2
     for (int64_t r = r_begin; r < r_end; ++r) {
-      const u32x4 v = *reinterpret_cast<const u32x4*>(x + r * K + c);
-      const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+      unpack_bf16x8(*reinterpret_cast<const u32x4*>(x + r * K + c), f);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float a = round_bf16(bf16_lo_to_f32(w[j]) / d[2 * j]), b = round_bf16(bf16_hi_to_f32(w[j]) / d[2 * j + 1]);
+      for (int j = 0; j < 8; j += 2) {
+        const float a = round_bf16(f[j] / d[j]), b = round_bf16(f[j + 1] / d[j + 1]);
         m = fmaxf(m, fmaxf(fabsf(a), fabsf(b)));
       }
     }
   }
   m = block_max(m, red);
   if (threadIdx.x == 0 && m != 0.f) atomicMax(amax, f32_to_bits(m));
-}
-
-// ---- C: the int8 activation casts on t = bf16(x * pre) ----------------------------------------------------------------------------------------------
-// amax_all (optional): ONE amax for every row, the PerTensor cast's (measured by prescaled_amax_kernel below).  Otherwise the twins of
-// quant_rowwise_reg_kernel<true, NV> and int8_quant_rowwise_kernel (quant_kernels.hip): the same lines on prescale8(x, pre).  `pre` is read
-// again by every row's workgroup; it is 2 K bytes and stays in L2.
-template <int NV>
-__global__ __launch_bounds__(kThreads) void int8_quant_rowwise_prescaled_reg_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ pre,
-                                                                                    const float* __restrict__ amax_all, int8_t* __restrict__ q,
-                                                                                    float* __restrict__ scale, int64_t K) {
-  __shared__ float red[4];
-  const int64_t row = blockIdx.x;
-  const u32x4* xr = reinterpret_cast<const u32x4*>(x + row * K);
-  const u32x4* pr = reinterpret_cast<const u32x4*>(pre);
-  const int nvec = (int)(K >> 3);
-  u32x4 v[NV];
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int idx = threadIdx.x + i * kThreads;
-    v[i] = (idx < nvec) ? prescale8(xr[idx], pr[idx]) : u32x4{0u, 0u, 0u, 0u};
-  }
-  float m = 0.f;
-  if (amax_all != nullptr) {
-    m = amax_all[0];
-  } else {
-    bool has_nan = false;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) m = fmaxf(m, amax8(v[i], has_nan));
-    m = block_max(has_nan ? INFINITY : m, red);  // (NaN rows are outside the contract)
-  }
-  const float s = int8_row_scale(m);
-  const float inv = 1.0f / s;
-  if (threadIdx.x == 0) scale[row] = s;
-  u32x2* qr = reinterpret_cast<u32x2*>(q + row * K);
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const int idx = threadIdx.x + i * kThreads;
-    if (idx < nvec) qr[idx] = int8_quant8(v[i], inv);
-  }
-}
-
-// longer rows: two sweeps, the second through L2
-__global__ __launch_bounds__(kThreads) void int8_quant_rowwise_prescaled_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ pre,
-                                                                                const float* __restrict__ amax_all, int8_t* __restrict__ q,
-                                                                                float* __restrict__ scale, int64_t K) {
-  __shared__ float red[4];
-  const int64_t row = blockIdx.x;
-  const u32x4* xr = reinterpret_cast<const u32x4*>(x + row * K);
-  const u32x4* pr = reinterpret_cast<const u32x4*>(pre);
-  const int64_t nvec = K >> 3;
-  float m = 0.f;
-  if (amax_all != nullptr) {
-    m = amax_all[0];
-  } else {
-    bool has_nan = false;
-    for (int64_t i = threadIdx.x; i < nvec; i += kThreads) m = fmaxf(m, amax8(prescale8(xr[i], pr[i]), has_nan));
-    m = block_max(has_nan ? INFINITY : m, red);
-  }
-  const float s = int8_row_scale(m);
-  const float inv = 1.0f / s;
-  if (threadIdx.x == 0) scale[row] = s;
-  u32x2* qr = reinterpret_cast<u32x2*>(q + row * K);
-  for (int64_t i = threadIdx.x; i < nvec; i += kThreads) qr[i] = int8_quant8(prescale8(xr[i], pr[i]), inv);
-}
-
-// the PerTensor cast's first half: max |t| over the whole activation, one atomic per row (ops.int8_quantize_tensorwise takes the same maximum
-// with rowwise_amax + amax; max is exact, so the order does not matter)
-__global__ __launch_bounds__(kThreads) void prescaled_amax_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ pre,
-                                                                  uint32_t* __restrict__ amax, int64_t K) {
-  __shared__ float red[4];
-  const u32x4* xr = reinterpret_cast<const u32x4*>(x + (int64_t)blockIdx.x * K);
-  const u32x4* pr = reinterpret_cast<const u32x4*>(pre);
-  float m = 0.f;
-  bool has_nan = false;
-  for (int64_t i = threadIdx.x; i < (K >> 3); i += kThreads) m = fmaxf(m, amax8(prescale8(xr[i], pr[i]), has_nan));
-  m = block_max(has_nan ? INFINITY : m, red);
-  if (threadIdx.x == 0 && m != 0.f) atomicMax(amax, f32_to_bits(m));
-}
-
-// the twin of int8_quant_static_kernel
-__global__ __launch_bounds__(kThreads) void int8_quant_static_prescaled_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ pre,
-                                                                               const float* __restrict__ scale, const int8_t* __restrict__ zero_point,
-                                                                               int stride, int8_t* __restrict__ q, int64_t K) {
-  const int64_t row = blockIdx.x;
-  const u32x4* xr = reinterpret_cast<const u32x4*>(x + row * K);
-  const u32x4* pr = reinterpret_cast<const u32x4*>(pre);
-  const float inv = 1.0f / scale[row * stride];
-  const float zp = zero_point != nullptr ? (float)zero_point[row * stride] : 0.0f;
-  u32x2* qr = reinterpret_cast<u32x2*>(q + row * K);
-  for (int64_t i = threadIdx.x; i < (K >> 3); i += kThreads) qr[i] = int8_quant8_zp(prescale8(xr[i], pr[i]), inv, zp);
-}
-
-void launch_rowwise_prescaled(const uint16_t* x, const uint16_t* pre, const float* amax_all, int8_t* q, float* scale, int64_t M, int64_t K,
-                              hipStream_t s) {
-  const int64_t per_thread = ((K >> 3) + kThreads - 1) / kThreads;
-  const dim3 grid((unsigned)M), block(kThreads);
-  if (per_thread <= 1) ao::launch(int8_quant_rowwise_prescaled_reg_kernel<1>, grid, block, 0, s, x, pre, amax_all, q, scale, K);
-  else if (per_thread <= 2) ao::launch(int8_quant_rowwise_prescaled_reg_kernel<2>, grid, block, 0, s, x, pre, amax_all, q, scale, K);
-  else if (per_thread <= 4) ao::launch(int8_quant_rowwise_prescaled_reg_kernel<4>, grid, block, 0, s, x, pre, amax_all, q, scale, K);
-  else if (per_thread <= 8) ao::launch(int8_quant_rowwise_prescaled_reg_kernel<8>, grid, block, 0, s, x, pre, amax_all, q, scale, K);
-  else ao::launch(int8_quant_rowwise_prescaled_kernel, grid, block, 0, s, x, pre, amax_all, q, scale, K);
-}
-
-int check_rows(const char* fn, int64_t M, int64_t K) {
-  AO_REQUIRE(M >= 0 && K > 0, "%s: bad shape M=%lld K=%lld", fn, (long long)M, (long long)K);
-  AO_REQUIRE(K % 8 == 0, "%s: K=%lld must be a multiple of 8", fn, (long long)K);
-  AO_REQUIRE(M < (1ll << 31) && K < (1ll << 31), "%s: M=%lld K=%lld too large", fn, (long long)M, (long long)K);
-  return AO_OK;
 }
 
 // rows per workgroup so that about kTargetBlocks workgroups exist over `col_blocks` column tiles; at least `min_rows` rows each
@@ -244,7 +119,7 @@ int64_t rows_per_block(int64_t M, int64_t col_blocks, int64_t min_rows) {
 using namespace ao;
 
 extern "C" int ao_sq_col_absmax_update(const uint16_t* x, float* state, int64_t M, int64_t K, void* stream) {
-  if (int rc = check_rows(__func__, M, K)) return rc;
+  if (int rc = check_rows(__func__, M, K, 8)) return rc;
   if (M == 0) return AO_OK;
   AO_REQUIRE_PTR(x);
   AO_REQUIRE_PTR(state);
@@ -259,7 +134,7 @@ extern "C" int ao_sq_col_absmax_update(const uint16_t* x, float* state, int64_t 
 }
 
 extern "C" int ao_sq_smoothed_amax_update(const uint16_t* x, const uint16_t* s, float* amax, int64_t M, int64_t K, void* stream) {
-  if (int rc = check_rows(__func__, M, K)) return rc;
+  if (int rc = check_rows(__func__, M, K, 8)) return rc;
   if (M == 0) return AO_OK;
   AO_REQUIRE_PTR(x);
   AO_REQUIRE_PTR(s);
@@ -271,55 +146,5 @@ extern "C" int ao_sq_smoothed_amax_update(const uint16_t* x, const uint16_t* s, 
   ao::launch(sq_smoothed_amax_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(kThreads), 0, (hipStream_t)stream, x, s,
              reinterpret_cast<uint32_t*>(amax), M, K, rows);
   AO_LAUNCH_CHECK("sq_smoothed_amax_kernel launch");
-  return AO_OK;
-}
-
-extern "C" int ao_int8_quantize_rowwise_prescaled(const uint16_t* x, const uint16_t* pre, int8_t* q, float* scale, int64_t M, int64_t K,
-                                                  void* stream) {
-  if (int rc = check_rows(__func__, M, K)) return rc;
-  if (M == 0) return AO_OK;
-  AO_REQUIRE_PTR(x);
-  AO_REQUIRE_PTR(pre);
-  AO_REQUIRE_PTR(q);
-  AO_REQUIRE_PTR(scale);
-  AO_REQUIRE(aligned_to(x, 16) && aligned_to(pre, 16) && aligned_to(q, 8), "%s: x and pre must be 16-byte aligned and q 8-byte aligned", __func__);
-  launch_rowwise_prescaled(x, pre, nullptr, q, scale, M, K, (hipStream_t)stream);
-  AO_LAUNCH_CHECK("int8_quant_rowwise_prescaled_kernel launch");
-  return AO_OK;
-}
-
-extern "C" int ao_int8_quantize_tensorwise_prescaled(const uint16_t* x, const uint16_t* pre, float* amax, int8_t* q, float* scale, int64_t M,
-                                                     int64_t K, void* stream) {
-  if (int rc = check_rows(__func__, M, K)) return rc;
-  if (M == 0) return AO_OK;
-  AO_REQUIRE_PTR(x);
-  AO_REQUIRE_PTR(pre);
-  AO_REQUIRE_PTR(amax);
-  AO_REQUIRE_PTR(q);
-  AO_REQUIRE_PTR(scale);
-  AO_REQUIRE(aligned_to(x, 16) && aligned_to(pre, 16) && aligned_to(q, 8) && aligned_to(amax, 4),
-             "%s: x and pre must be 16-byte aligned, q 8-byte and amax 4-byte aligned", __func__);
-  hipStream_t s = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(amax, 0, sizeof(float), s);
-  if (e != hipSuccess) return ::ao::hip_failed(e, "hipMemsetAsync(amax)");
-  ao::launch(prescaled_amax_kernel, dim3((unsigned)M), dim3(kThreads), 0, s, x, pre, reinterpret_cast<uint32_t*>(amax), K);
-  AO_LAUNCH_CHECK("prescaled_amax_kernel launch");
-  launch_rowwise_prescaled(x, pre, amax, q, scale, M, K, s);
-  AO_LAUNCH_CHECK("int8_quant_rowwise_prescaled_kernel launch");
-  return AO_OK;
-}
-
-extern "C" int ao_int8_quantize_static_prescaled(const uint16_t* x, const uint16_t* pre, const float* scale, const int8_t* zero_point, int per_row,
-                                                 int8_t* q, int64_t M, int64_t K, void* stream) {
-  if (int rc = check_rows(__func__, M, K)) return rc;
-  if (M == 0) return AO_OK;
-  AO_REQUIRE_PTR(x);
-  AO_REQUIRE_PTR(pre);
-  AO_REQUIRE_PTR(scale);
-  AO_REQUIRE_PTR(q);
-  AO_REQUIRE(aligned_to(x, 16) && aligned_to(pre, 16) && aligned_to(q, 8), "%s: x and pre must be 16-byte aligned and q 8-byte aligned", __func__);
-  ao::launch(int8_quant_static_prescaled_kernel, dim3((unsigned)M), dim3(kThreads), 0, (hipStream_t)stream, x, pre, scale, zero_point,
-             per_row ? 1 : 0, q, K);
-  AO_LAUNCH_CHECK("int8_quant_static_prescaled_kernel launch");
   return AO_OK;
 }

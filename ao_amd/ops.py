@@ -312,18 +312,35 @@ def _as_rows(name, x, dtype):
     return x if x.is_contiguous() else x.contiguous()
 
 
-def int8_quantize_rowwise(x: torch.Tensor):
-    """Int8Tensor.from_hp(x, PerRow()) (symmetric, eps = fp32 eps):
-    torchao/quantization/quantize_/workflows/int8/int8_tensor.py:176-248.
-    x bf16 [M, K] -> (qdata int8 [M, K], scale fp32 [M, 1])."""
-    dev = _require_gpu("int8_quantize_rowwise", x)
-    x = _as_rows("int8_quantize_rowwise", x, torch.bfloat16)
+def _int8_rows_and_pre(name, x, pre):
+    """x as contiguous bf16 rows under the checks of the plain casts (pre is None) or, with an activation pre-scale, of the pre-scaled
+    ones; and `pre` as its contiguous bf16 [K] vector."""
+    if pre is None:
+        return _as_rows(name, x, torch.bfloat16), None
+    x = _sq_rows(name, x)
+    return x, _sq_vector(name, "pre", pre, x.shape[1])
+
+
+def _int8_quantize_rowwise(name, x, pre=None):
+    """The per-row cast of x or, with `pre`, of x * pre (the product never written)."""
+    dev = _require_gpu(name, x, pre)
+    x, pre = _int8_rows_and_pre(name, x, pre)
     m, k = x.shape
     q = torch.empty((m, k), dtype=torch.int8, device=dev)
     s = torch.empty((m, 1), dtype=torch.float32, device=dev)
     with _on(dev):
-        _lib.check(_lib.lib().ao_int8_quantize_rowwise(_ptr(x), _ptr(q), _ptr(s), m, k, _stream()))
+        if pre is None:
+            _lib.check(_lib.lib().ao_int8_quantize_rowwise(_ptr(x), _ptr(q), _ptr(s), m, k, _stream()))
+        else:
+            _lib.check(_lib.lib().ao_int8_quantize_rowwise_prescaled(_ptr(x), _ptr(pre), _ptr(q), _ptr(s), m, k, _stream()))
     return q, s
+
+
+def int8_quantize_rowwise(x: torch.Tensor):
+    """Int8Tensor.from_hp(x, PerRow()) (symmetric, eps = fp32 eps):
+    torchao/quantization/quantize_/workflows/int8/int8_tensor.py:176-248.
+    x bf16 [M, K] -> (qdata int8 [M, K], scale fp32 [M, 1])."""
+    return _int8_quantize_rowwise("int8_quantize_rowwise", x)
 
 
 def int8_scaled_mm(xq, x_scale, wq, w_scale, bias=None):
@@ -754,30 +771,37 @@ def int8_quantize_rowwise_asym(x: torch.Tensor):
     return q, s, zp
 
 
-def int8_quantize_static(x: torch.Tensor, scale: torch.Tensor, zero_point: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Int8Tensor.from_hp(x, ..., scale=scale, zero_point=zero_point) (static quantization, int8_tensor.py:212-231): bf16 [M, K] with an fp32
-    scale of 1 or M elements (and an int8 zero-point of the same shape, or None) -> qdata int8 [M, K]."""
-    dev = _require_gpu("int8_quantize_static", x, scale, zero_point)
-    x = _as_rows("int8_quantize_static", x, torch.bfloat16)
+def _int8_quantize_static(name, x, scale, zero_point, pre=None):
+    """The cast of x or, with `pre`, of x * pre under the given scale / zero-point."""
+    dev = _require_gpu(name, x, pre, scale, zero_point)
+    x, pre = _int8_rows_and_pre(name, x, pre)
     m, k = x.shape
     scale = scale.reshape(-1).to(torch.float32).contiguous()
     if scale.numel() not in (1, m):
-        raise RuntimeError(f"int8_quantize_static: scale must have 1 or M = {m} elements, got {scale.numel()}")
+        raise RuntimeError(f"{name}: scale must have 1 or M = {m} elements, got {scale.numel()}")
     if zero_point is not None:
         zero_point = zero_point.reshape(-1).to(torch.int8).contiguous()
         if zero_point.numel() != scale.numel():
-            raise RuntimeError("int8_quantize_static: zero_point must have the shape of scale")
+            raise RuntimeError(f"{name}: zero_point must have the shape of scale")
     q = torch.empty((m, k), dtype=torch.int8, device=dev)
+    per_row = int(scale.numel() == m and m > 1)
     with _on(dev):
-        _lib.check(_lib.lib().ao_int8_quantize_static(_ptr(x), _ptr(scale), _ptr(zero_point), int(scale.numel() == m and m > 1), _ptr(q), m, k, _stream()))
+        if pre is None:
+            _lib.check(_lib.lib().ao_int8_quantize_static(_ptr(x), _ptr(scale), _ptr(zero_point), per_row, _ptr(q), m, k, _stream()))
+        else:
+            _lib.check(_lib.lib().ao_int8_quantize_static_prescaled(_ptr(x), _ptr(pre), _ptr(scale), _ptr(zero_point), per_row, _ptr(q), m, k,
+                                                                    _stream()))
     return q
 
 
-def int8_linear_static(x2, wq, w_scale, act_scale, act_zero_point=None, w_row_sums=None, bias=None):
-    """The Int8Tensor F.linear with STATIC activation qparams (Int8StaticActivationInt8WeightConfig): cast with the given scale /
-    zero-point, then the dynamic path's GEMM + epilogue (zero-point-corrected when one is given)."""
-    m = x2.shape[0]
-    xq = int8_quantize_static(x2, act_scale, act_zero_point)
+def int8_quantize_static(x: torch.Tensor, scale: torch.Tensor, zero_point: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Int8Tensor.from_hp(x, ..., scale=scale, zero_point=zero_point) (static quantization, int8_tensor.py:212-231): bf16 [M, K] with an fp32
+    scale of 1 or M elements (and an int8 zero-point of the same shape, or None) -> qdata int8 [M, K]."""
+    return _int8_quantize_static("int8_quantize_static", x, scale, zero_point)
+
+
+def _int8_linear_static(xq, m, wq, w_scale, act_scale, act_zero_point, w_row_sums, bias):
+    """The GEMM + epilogue behind a statically cast activation xq (zero-point-corrected when one is given)."""
     xs = act_scale.reshape(-1).to(torch.float32)
     xs = xs.expand(m) if xs.numel() == 1 else xs
     if act_zero_point is None:
@@ -787,6 +811,13 @@ def int8_linear_static(x2, wq, w_scale, act_scale, act_zero_point=None, w_row_su
     if w_row_sums is None:
         w_row_sums = int8_row_sums(wq)
     return int8_scale_epilogue_asym(int_mm(xq, wq.t()), xs, zp, w_row_sums, w_scale, bias)
+
+
+def int8_linear_static(x2, wq, w_scale, act_scale, act_zero_point=None, w_row_sums=None, bias=None):
+    """The Int8Tensor F.linear with STATIC activation qparams (Int8StaticActivationInt8WeightConfig): cast with the given scale /
+    zero-point, then the dynamic path's GEMM + epilogue (zero-point-corrected when one is given)."""
+    m = x2.shape[0]
+    return _int8_linear_static(int8_quantize_static(x2, act_scale, act_zero_point), m, wq, w_scale, act_scale, act_zero_point, w_row_sums, bias)
 
 
 def int8_row_sums(wq: torch.Tensor) -> torch.Tensor:
@@ -2874,7 +2905,7 @@ __all__ += ["awq_scaled_error", "AWQ_GROUP_SIZES"]
 
 # ---------------------------------------------------------------------------
 # SmoothQuant: the calibration reductions, and the int8 activation casts with the activation pre-scale folded in
-# (csrc/smoothquant_kernels.hip states the arithmetic)
+# (csrc/smoothquant_kernels.hip states the reductions' arithmetic, csrc/quant_kernels.hip the casts')
 # ---------------------------------------------------------------------------
 def _sq_rows(name, x):
     if x.dtype != torch.bfloat16:
@@ -2925,16 +2956,7 @@ def sq_smoothed_amax_update(x: torch.Tensor, s: torch.Tensor, amax: torch.Tensor
 def int8_quantize_rowwise_prescaled(x: torch.Tensor, pre: torch.Tensor):
     """int8_quantize_rowwise(x * pre) in one launch, the product never written: x bf16 [M, K], pre bf16 [K] ->
     (qdata int8 [M, K], scale fp32 [M, 1])."""
-    name = "int8_quantize_rowwise_prescaled"
-    dev = _require_gpu(name, x, pre)
-    x = _sq_rows(name, x)
-    m, k = x.shape
-    pre = _sq_vector(name, "pre", pre, k)
-    q = torch.empty((m, k), dtype=torch.int8, device=dev)
-    s = torch.empty((m, 1), dtype=torch.float32, device=dev)
-    with _on(dev):
-        _lib.check(_lib.lib().ao_int8_quantize_rowwise_prescaled(_ptr(x), _ptr(pre), _ptr(q), _ptr(s), m, k, _stream()))
-    return q, s
+    return _int8_quantize_rowwise("int8_quantize_rowwise_prescaled", x, pre)
 
 
 def _int8_quantize_tensorwise_prescaled_rows(x, pre):
@@ -2960,23 +2982,7 @@ def int8_quantize_tensorwise_prescaled(x: torch.Tensor, pre: torch.Tensor):
 def int8_quantize_static_prescaled(x: torch.Tensor, pre: torch.Tensor, scale: torch.Tensor, zero_point: Optional[torch.Tensor] = None) -> torch.Tensor:
     """int8_quantize_static(x * pre, scale, zero_point) in one launch: x bf16 [M, K], pre bf16 [K], scale fp32 of 1 or M elements (and an int8
     zero-point of the same shape, or None) -> qdata int8 [M, K]."""
-    name = "int8_quantize_static_prescaled"
-    dev = _require_gpu(name, x, pre, scale, zero_point)
-    x = _sq_rows(name, x)
-    m, k = x.shape
-    pre = _sq_vector(name, "pre", pre, k)
-    scale = scale.reshape(-1).to(torch.float32).contiguous()
-    if scale.numel() not in (1, m):
-        raise RuntimeError(f"{name}: scale must have 1 or M = {m} elements, got {scale.numel()}")
-    if zero_point is not None:
-        zero_point = zero_point.reshape(-1).to(torch.int8).contiguous()
-        if zero_point.numel() != scale.numel():
-            raise RuntimeError(f"{name}: zero_point must have the shape of scale")
-    q = torch.empty((m, k), dtype=torch.int8, device=dev)
-    with _on(dev):
-        _lib.check(_lib.lib().ao_int8_quantize_static_prescaled(_ptr(x), _ptr(pre), _ptr(scale), _ptr(zero_point),
-                                                                int(scale.numel() == m and m > 1), _ptr(q), m, k, _stream()))
-    return q
+    return _int8_quantize_static("int8_quantize_static_prescaled", x, scale, zero_point, pre)
 
 
 def int8_linear_prescaled(x2, pre, wq, w_scale, bias=None):
@@ -2997,15 +3003,7 @@ def int8_linear_static_prescaled(x2, pre, wq, w_scale, act_scale, act_zero_point
     """int8_linear_static(x2 * pre, ...) without writing the product."""
     m = x2.shape[0]
     xq = int8_quantize_static_prescaled(x2, pre, act_scale, act_zero_point)
-    xs = act_scale.reshape(-1).to(torch.float32)
-    xs = xs.expand(m) if xs.numel() == 1 else xs
-    if act_zero_point is None:
-        return int8_scaled_mm(xq, xs, wq, w_scale, bias)
-    zp = act_zero_point.reshape(-1)
-    zp = zp.expand(m) if zp.numel() == 1 else zp
-    if w_row_sums is None:
-        w_row_sums = int8_row_sums(wq)
-    return int8_scale_epilogue_asym(int_mm(xq, wq.t()), xs, zp, w_row_sums, w_scale, bias)
+    return _int8_linear_static(xq, m, wq, w_scale, act_scale, act_zero_point, w_row_sums, bias)
 
 
 __all__ += ["sq_col_absmax_update", "sq_smoothed_amax_update", "int8_quantize_rowwise_prescaled", "int8_quantize_tensorwise_prescaled",

@@ -14,7 +14,7 @@ Host-side mirror of torchao/prototype/smoothquant/api.py (same public names, sam
 SmoothQuant (https://arxiv.org/abs/2211.10438) moves activation outliers into the weight: input channel k of the weight is multiplied by
 s[k] = max|x_k|^alpha / max|w_k|^(1 - alpha) before it is quantized and the activation is divided by s[k] at run time.  The product is the
 existing Int8Tensor with act_pre_scale = 1 / s; its F.linear folds the pre-scale into the activation cast (quantization/int8_tensor.py
-_prescale_fuses, csrc/smoothquant_kernels.hip).
+_prescale_fuses, csrc/quant_kernels.hip).
 
 Deviations, on purpose:
   * SmoothQuantStep: the reference adds prepare_for_smoothquant_smoothing_factor / _activation_scales to QuantizationStep; here that enum
