@@ -30,6 +30,14 @@ FLAGS = [
     "-fno-vectorize",
     "-Wno-unused-result",
 ]
+# Flags of single sources.  nvfp4_grouped_train_kernels.hip is compiled without packed fp32 VALU operations (v_pk_add / mul / fma_f32):
+# its fp32 arithmetic is quant_math.h's chain of single operations, and the packed pairing of the two 16-point Hadamard transforms a lane
+# holds costs registers instead of saving issue slots -- nvfp4_train_group_amax_kernel takes 84 VGPRs (5 waves a SIMD) with them and 61
+# (8 waves) without, nvfp4_wgrad_kernel 88 and 86.  It is a cc1 feature switch that a compiler may stop honouring without failing the
+# build: the check is the resource report (-Rpass-analysis=kernel-resource-usage), 61 and 86 VGPRs.
+SOURCE_FLAGS = {
+    "nvfp4_grouped_train_kernels.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+}
 
 
 def sources():
@@ -92,7 +100,7 @@ def build(force=False, verbose=False, lab=False):
     os.makedirs(bdir, exist_ok=True)
     for src in sources():
         obj = os.path.join(bdir, os.path.basename(src) + ".o")
-        cmd = [HIPCC] + [f for f in FLAGS if f != "-shared"] + ["-c", src, "-o", obj]
+        cmd = [HIPCC] + [f for f in FLAGS if f != "-shared"] + SOURCE_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj]
         if verbose:
             print(" ".join(cmd))
         procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
@@ -118,7 +126,7 @@ def _build_lab(verbose=False):
     objs, procs = [], []
     for src in sources():
         obj = os.path.join(bdir, os.path.basename(src) + ".o")
-        cmd = [HIPCC] + [f for f in FLAGS if f != "-shared"] + ["-DAO_LAB=1", "-c", src, "-o", obj]
+        cmd = [HIPCC] + [f for f in FLAGS if f != "-shared"] + SOURCE_FLAGS.get(os.path.basename(src), []) + ["-DAO_LAB=1", "-c", src, "-o", obj]
         if verbose:
             print(" ".join(cmd))
         procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))

@@ -683,6 +683,37 @@ extern "C" int ao_nvfp4_grouped_mm(int kind, const uint16_t* x, const uint8_t* a
   return r.kernel == 1 ? launch_grouped_stream<kKindDyn>(r, args, st) : launch_grouped_tile<kKindDyn>(r, args, st);
 }
 
+// The grouped training GEMMs (prototype/moe_training/nvfp4_training/nvfp4_grouped_mm.py:198-210 forward, :302-314 dgrad:
+// F.scaled_grouped_mm on e2m1 codes with BlockWise1x16 + TensorWise scales): kind 1's grouped route, forced form and bodies above under the
+// scaled_mm epilogue, P_e = pa[e] pb[e].
+extern "C" int ao_nvfp4_scaled_grouped_mm(const uint8_t* a, const uint8_t* a_scale, const float* pa, const uint8_t* b, const uint8_t* b_scale,
+                                          const float* pb, const int32_t* offs, uint16_t* out, int64_t M_total, int64_t N, int64_t K, int64_t E,
+                                          void* stream) {
+  AO_REQUIRE(nvfp4_grouped_shape_ok(kKindDyn, M_total, N, K, E),
+             "%s: bad shape M_total=%lld N=%lld K=%lld E=%lld (M_total >= 0, N >= 1, K a positive multiple of 16, 1 <= E <= 65535, M_total K "
+             "and the per-expert N K < 2^31)",
+             __func__, (long long)M_total, (long long)N, (long long)K, (long long)E);
+  AO_REQUIRE_PTR(b);
+  AO_REQUIRE_PTR(b_scale);
+  AO_REQUIRE_PTR(pa);
+  AO_REQUIRE_PTR(pb);
+  AO_REQUIRE_PTR(offs);
+  if (M_total == 0) return AO_OK;
+  AO_REQUIRE_PTR(a);
+  AO_REQUIRE_PTR(a_scale);
+  AO_REQUIRE_PTR(out);
+  AO_REQUIRE(aligned_to(a, K % 32 ? 8 : 16) && aligned_to(b, K % 32 ? 8 : 16) && aligned_to(a_scale, K % 32 ? 1 : 2) && aligned_to(b_scale, K % 32 ? 1 : 2),
+             "%s: the codes must be 16-byte and the block scales 2-byte aligned (K %% 32 != 0: 8-byte and 1-byte)", __func__);
+  AO_REQUIRE(aligned_to(pa, 4) && aligned_to(pb, 4) && aligned_to(offs, 4) && aligned_to(out, 2),
+             "%s: the per-expert scales and offs must be 4-byte, out 2-byte aligned", __func__);
+  const TwoFormRoute r = nvfp4_grouped_route(kKindDyn, M_total, N, K, E);
+  AO_REQUIRE(r.kernel != 0, "%s: no route for M_total=%lld N=%lld K=%lld E=%lld (more than 65535 grid rows)", __func__, (long long)M_total,
+             (long long)N, (long long)K, (long long)E);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const Nvfp4Args args{nullptr, a, a_scale, b, b_scale, pa, pb, nullptr, out, (int)M_total, (int)N, (int)K, offs, (int)E, 1};
+  return r.kernel == 1 ? launch_grouped_stream<kKindDyn>(r, args, st) : launch_grouped_tile<kKindDyn>(r, args, st);
+}
+
 namespace {
 int check_grouped_rows(const char* fn, int64_t M_total, int64_t K, int64_t E) {
   AO_REQUIRE(M_total >= 0 && K > 0 && K % 16 == 0 && E >= 1 && E <= 65535 && M_total < (1ll << 31) && K < (1ll << 31) && M_total * K < (1ll << 40),

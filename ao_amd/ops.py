@@ -2426,6 +2426,161 @@ def nvfp4_scaled_mm(a, a_scale, b, b_scale, a_per_tensor_scale, b_per_tensor_sca
 __all__ += ["nvfp4_sign_mask", "nvfp4_train_amax", "nvfp4_train_quantize_row_col", "nvfp4_train_quantize_weight_2d", "nvfp4_scaled_mm"]
 
 
+# ---- NVFP4 training of the MoE grouped GEMM (include/ao_mi355.h "NVFP4 training of the MoE grouped GEMM") -----------------
+# offs: int32 [E] cumulative group ends, multiples of 16, read on the device only.
+def _nvfp4_train_experts(name, w):
+    if w.dtype != torch.bfloat16 or w.dim() != 3 or not w.is_contiguous():
+        raise RuntimeError(f"{name}: expected a contiguous 3-D bfloat16 tensor [E, N, K], got {w.dtype} {tuple(w.shape)}")
+    e, n, k = w.shape
+    if e < 1 or n % 16 != 0 or k % 16 != 0 or k == 0:
+        raise RuntimeError(f"{name}: shape {tuple(w.shape)} needs E >= 1 and N and K divisible by 16")
+    return e, n, k
+
+
+def _nvfp4_train_offs(name, offs):
+    if not isinstance(offs, torch.Tensor) or offs.dim() != 1 or offs.numel() < 1:
+        raise RuntimeError(f"{name}: offs must be an int32 tensor [E] of cumulative group ends")
+    return _nvfp4_offs(name, offs, offs.numel())
+
+
+def _nvfp4_train_group_amaxes(name, amax, e, dev):
+    if not isinstance(amax, torch.Tensor) or amax.dtype != torch.float32 or tuple(amax.shape) != (e, 2) or not amax.is_contiguous() or amax.device != dev:
+        raise RuntimeError(f"{name}: amax must be a contiguous float32 tensor [E, 2] = {(e, 2)} on {dev} (column amax, row amax a group)")
+    return amax
+
+
+def nvfp4_train_group_amax(x: torch.Tensor, offs: torch.Tensor, sign_vector, want_rht: bool = True) -> torch.Tensor:
+    """triton_group_rht_amax (nvfp4_training/group_hadamard_amax_triton.py): nvfp4_train_amax per token group in one read of x bf16
+    [M_total, N] -> fp32 [E, 2] on the device, [e, 0] = max|bf16(RHT(x_e^T))| (0 when not want_rht), [e, 1] = max|x_e|.  Rows at or past
+    offs[-1] reach no reduction; an empty group gives 0.  No host read (capturable)."""
+    name = "nvfp4_train_group_amax"
+    dev = _require_gpu(name, x, offs)
+    m, n = _nvfp4_train_matrix(name, x)
+    offs = _nvfp4_train_offs(name, offs)
+    e = offs.numel()
+    mask = nvfp4_sign_mask(sign_vector)
+    out = torch.empty((e, 2), dtype=torch.float32, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_nvfp4_train_group_amax(_ptr(x), _ptr(offs), _ptr(out), m, n, e, mask, int(bool(want_rht)), _stream()))
+    return out
+
+
+def nvfp4_train_quantize_row_col_grouped(x: torch.Tensor, amax: torch.Tensor, offs: torch.Tensor, sign_vector,
+                                         sr_seed: Optional[torch.Tensor] = None, col_offset: Optional[torch.Tensor] = None,
+                                         row_offset: Optional[torch.Tensor] = None, *, want_col: bool = True, want_row: bool = True,
+                                         col_out=None, row_out=None):
+    """triton_group_rht_quantize_row_col (nvfp4_training/group_rht_quantize_row_col_triton.py): nvfp4_train_quantize_row_col with every
+    16-row run of x bf16 [M_total, N] cast under the amax pair amax[e] (fp32 [E, 2]: column, row) of the group that holds it.  Returns
+    (col_q [N, M_total/2], col_s [N, M_total/16], row_q [M_total, N/2], row_s [M_total, N/16]); rows at or past offs[-1] are zero codes and
+    zero scale bytes in both.  sr_seed as in the dense op: with one group of every row, or equal amax pairs, the bytes are the dense op's."""
+    name = "nvfp4_train_quantize_row_col_grouped"
+    dev = _require_gpu(name, x, amax, offs, sr_seed, col_offset, row_offset)
+    m, n = _nvfp4_train_matrix(name, x)
+    offs = _nvfp4_train_offs(name, offs)
+    e = offs.numel()
+    amax = _nvfp4_train_group_amaxes(name, amax, e, dev)
+    mask = nvfp4_sign_mask(sign_vector)
+    if not (want_col or want_row):
+        raise RuntimeError(f"{name}: neither output is wanted")
+    if sr_seed is not None:
+        sr_seed = _nvfp4_i64(name, "sr_seed", sr_seed, dev)
+        col_offset = _nvfp4_i64(name, "col_offset", col_offset, dev) if want_col else None
+        row_offset = _nvfp4_i64(name, "row_offset", row_offset, dev) if want_row else None
+    else:
+        col_offset = row_offset = None
+    cq, cs = _nvfp4_train_out(name, "column", col_out, n, m, dev) if want_col else (None, None)
+    rq, rs = _nvfp4_train_out(name, "row", row_out, m, n, dev) if want_row else (None, None)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_nvfp4_train_quantize_row_col_grouped(_ptr(x), _ptr(amax), _ptr(offs), mask, _ptr(sr_seed), _ptr(col_offset),
+                                                                      _ptr(row_offset), _ptr(cq), _ptr(cs), _ptr(rq), _ptr(rs), m, n, e, _stream()))
+    f8 = torch.float8_e4m3fn
+    return cq, (None if cs is None else cs.view(f8)), rq, (None if rs is None else rs.view(f8))
+
+
+def nvfp4_train_weight_amax_3d(w: torch.Tensor) -> torch.Tensor:
+    """triton_group_weight_amax (nvfp4_training/group_weight_amax_triton.py): w bf16 [E, N, K] -> fp32 [E] on the device, max|w[e]|."""
+    name = "nvfp4_train_weight_amax_3d"
+    dev = _require_gpu(name, w)
+    e, n, k = _nvfp4_train_experts(name, w)
+    out = torch.empty((e,), dtype=torch.float32, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_nvfp4_train_weight_amax_3d(_ptr(w), _ptr(out), e, n, k, _stream()))
+    return out
+
+
+def nvfp4_train_quantize_weight_3d(w: torch.Tensor, amax: torch.Tensor):
+    """triton_group_weight_quantize_2d (nvfp4_training/group_quantize_2d_triton.py): nvfp4_train_quantize_weight_2d on every expert of w
+    bf16 [E, N, K] under amax fp32 [E], one launch -> (q [E, N, K/2], s e4m3 [E, N, K/16], qt [E, K, N/2], st e4m3 [E, K, N/16])."""
+    name = "nvfp4_train_quantize_weight_3d"
+    dev = _require_gpu(name, w, amax)
+    e, n, k = _nvfp4_train_experts(name, w)
+    a = _nvfp4_expert_scales(name, "amax", amax, e, dev)
+    if a is None:
+        raise RuntimeError(f"{name}: amax is required")
+    u8 = dict(dtype=torch.uint8, device=dev)
+    q, s = torch.empty((e, n, k // 2), **u8), torch.empty((e, n, k // 16), **u8)
+    qt, st = torch.empty((e, k, n // 2), **u8), torch.empty((e, k, n // 16), **u8)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_nvfp4_train_quantize_weight_3d(_ptr(w), _ptr(a), _ptr(q), _ptr(s), _ptr(qt), _ptr(st), e, n, k, _stream()))
+    return q, s.view(torch.float8_e4m3fn), qt, st.view(torch.float8_e4m3fn)
+
+
+def nvfp4_scaled_grouped_mm(a, a_scale, b, b_scale, offs, a_per_group_scale, b_per_expert_scale, out=None):
+    """F.scaled_grouped_mm on e2m1 codes with BlockWise1x16 + TensorWise scales (nvfp4_training/nvfp4_grouped_mm.py:198-210, :302-314): a
+    codes [M_total, K/2], a_scale [M_total, K/16], b codes [E, N, K/2], b_scale [E, N, K/16], offs int32 [E], both scales fp32 [E] on the
+    device -> bf16 [M_total, N], group e = bf16(acc (pa[e] pb[e])), ONE rounding (nvfp4_grouped_mm's route, forced form and kernels).
+    Rows past offs[-1] are not written: a fresh output is zero-filled."""
+    name = "nvfp4_scaled_grouped_mm"
+    dev = _require_gpu(name, a, a_scale, b, b_scale, offs, a_per_group_scale, b_per_expert_scale, out)
+    b, b_scale, e, n, k = _nvfp4_expert_codes(name, b, b_scale)
+    a, a_scale, m, ka = _nvfp4_codes(name, "activation", a, a_scale)
+    if ka != k:
+        raise RuntimeError(f"{name}: K of the activation ({ka}) and of the weight ({k}) differ")
+    offs = _nvfp4_offs(name, offs, e)
+    pa = _nvfp4_expert_scales(name, "a_per_group_scale", a_per_group_scale, e, dev)
+    pb = _nvfp4_expert_scales(name, "b_per_expert_scale", b_per_expert_scale, e, dev)
+    if pa is None or pb is None:
+        raise RuntimeError(f"{name}: both per-group scales are required")
+    y = torch.zeros((m, n), dtype=torch.bfloat16, device=dev) if out is None else _bf16_out(name, out, m, n, dev)
+    if m > 0:
+        with _on(dev):
+            _lib.check(_lib.lib().ao_nvfp4_scaled_grouped_mm(_ptr(a), _ptr(a_scale), _ptr(pa), _ptr(b), _ptr(b_scale), _ptr(pb), _ptr(offs), _ptr(y),
+                                                             m, n, k, e, _stream()))
+    return y
+
+
+def nvfp4_grouped_mm_wgrad(g_t, g_scale, x_t, x_scale, g_per_group_scale, x_per_group_scale, offs=None):
+    """The weight gradient of the NVFP4 grouped GEMM (nvfp4_grouped_mm.py:315-326), contracting each group's tokens: g_t codes
+    [N, M_total/2], g_scale e4m3 [N, M_total/16], x_t codes [K, M_total/2], x_scale [K, M_total/16] (the column outputs of the casts), both
+    scales fp32 [E] on the device, offs int32 [E] or None (one group of every token: a dense weight gradient) -> bf16 [E, N, K] =
+    bf16(acc_e (pg[e] px[e])).  An empty group is zeros."""
+    name = "nvfp4_grouped_mm_wgrad"
+    dev = _require_gpu(name, g_t, g_scale, x_t, x_scale, g_per_group_scale, x_per_group_scale, offs)
+    g_t, g_scale, n, m = _nvfp4_codes(name, "gradient", g_t, g_scale)
+    x_t, x_scale, k, mx = _nvfp4_codes(name, "activation", x_t, x_scale)
+    if m != mx:
+        raise RuntimeError(f"{name}: the token counts of the gradient ({m}) and of the activation ({mx}) differ")
+    if n % 16 != 0 or k % 16 != 0:
+        raise RuntimeError(f"{name}: N={n} and K={k} must be divisible by 16")
+    e = 1
+    if offs is not None:
+        offs = _nvfp4_train_offs(name, offs)
+        e = offs.numel()
+    pg = _nvfp4_expert_scales(name, "g_per_group_scale", g_per_group_scale, e, dev)
+    px = _nvfp4_expert_scales(name, "x_per_group_scale", x_per_group_scale, e, dev)
+    if pg is None or px is None:
+        raise RuntimeError(f"{name}: both per-group scales are required")
+    out = torch.empty((e, n, k), dtype=torch.bfloat16, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_nvfp4_grouped_mm_wgrad(_ptr(g_t), _ptr(g_scale), _ptr(x_t), _ptr(x_scale), _ptr(pg), _ptr(px), _ptr(offs), _ptr(out),
+                                                        m, n, k, e, _stream()))
+    return out
+
+
+__all__ += ["nvfp4_train_group_amax", "nvfp4_train_quantize_row_col_grouped", "nvfp4_train_weight_amax_3d", "nvfp4_train_quantize_weight_3d",
+            "nvfp4_scaled_grouped_mm", "nvfp4_grouped_mm_wgrad"]
+
+
 # ---------------------------------------------------------------------------
 # Quantization-aware training (torchao.quantization.qat): each fake quantizer and its gradient as one launch, bf16 -> bf16.  The backward
 # ops take the forward's INPUT and the incoming gradient; nothing else is saved.

@@ -25,6 +25,7 @@ from .mx_training import (  # noqa: F401
 )
 from .nf4_api import NF4WeightOnlyConfig, nf4_weight_only  # noqa: F401
 from .nvfp4_grouped import NVFP4ExpertWeights, nvfp4_grouped_mm  # noqa: F401
+from .nvfp4_grouped_training import _NVFP4GroupedMM, _to_nvfp4_rht_rs_then_scaled_grouped_mm  # noqa: F401
 from .nvfp4_tensor import (  # noqa: F401
     NVFP4DynamicActivationNVFP4WeightConfig,
     NVFP4Tensor,
@@ -55,5 +56,6 @@ __all__ = ["Float8BlockwiseExpertWeights", "fp8_blockwise_grouped_mm", "NVFP4Ten
            "Float8BlockwiseLinearConfig", "_Float8BlockwiseGroupedMM", "_to_fp8_blockwise_then_scaled_grouped_mm",
            "_to_fp8_blockwise_then_emulated_scaled_grouped_mm",
            "NVFP4Linear", "NVFP4TrainingConfig", "nvfp4_linear", "DEFAULT_SIGN_VECTOR", "get_wgrad_sign_vector",
+           "_NVFP4GroupedMM", "_to_nvfp4_rht_rs_then_scaled_grouped_mm",
            "NF4WeightOnlyConfig", "nf4_weight_only", "AWQConfig", "AWQObserver", "AWQObservedLinear",
            "SmoothQuantConfig", "SmoothQuantStep", "SmoothQuantObserver", "RunningAbsMaxSmoothQuantObserver", "SmoothQuantObservedLinear"]

@@ -99,6 +99,13 @@ _lib_def.define("nvfp4_linear(Tensor x, Tensor wq, Tensor w_scale, Tensor? w_per
 _lib_def.define("nvfp4_group_amax_scale(Tensor x, Tensor offs) -> Tensor")
 _lib_def.define("nvfp4_quantize_grouped(Tensor x, Tensor? per_group_scale, Tensor offs) -> (Tensor, Tensor)")
 _lib_def.define("nvfp4_grouped_mm(int kind, Tensor a, Tensor? a_scale, Tensor wq, Tensor w_scale, Tensor offs, Tensor? a_per_group_scale, Tensor? w_per_expert_scale) -> Tensor")
+# NVFP4 training of the MoE grouped GEMM; sign_mask: the RHT sign vector as ops.nvfp4_sign_mask gives it
+_lib_def.define("nvfp4_train_group_amax(Tensor x, Tensor offs, int sign_mask, bool want_rht) -> Tensor")
+_lib_def.define("nvfp4_train_quantize_row_col_grouped(Tensor x, Tensor amax, Tensor offs, int sign_mask, Tensor? sr_seed, Tensor? col_offset, Tensor? row_offset) -> (Tensor, Tensor, Tensor, Tensor)")
+_lib_def.define("nvfp4_train_weight_amax_3d(Tensor w) -> Tensor")
+_lib_def.define("nvfp4_train_quantize_weight_3d(Tensor w, Tensor amax) -> (Tensor, Tensor, Tensor, Tensor)")
+_lib_def.define("nvfp4_scaled_grouped_mm(Tensor a, Tensor a_scale, Tensor b, Tensor b_scale, Tensor offs, Tensor a_per_group_scale, Tensor b_per_expert_scale) -> Tensor")
+_lib_def.define("nvfp4_grouped_mm_wgrad(Tensor g_t, Tensor g_scale, Tensor x_t, Tensor x_scale, Tensor g_per_group_scale, Tensor x_per_group_scale, Tensor? offs) -> Tensor")
 # same schemas as torchao::fused_pad_token_groups / fused_unpad_token_groups (kernels/mxfp8/quant.py:1244-1246, 1319-1321)
 _lib_def.define("fused_pad_token_groups(Tensor inputs, Tensor offsets, int alignment_size) -> (Tensor, Tensor, Tensor)")
 _lib_def.define(
@@ -161,6 +168,13 @@ _lib_impl.impl("nvfp4_linear", ops.nvfp4_linear)
 _lib_impl.impl("nvfp4_group_amax_scale", ops.nvfp4_group_amax_scale)
 _lib_impl.impl("nvfp4_quantize_grouped", ops.nvfp4_quantize_grouped)
 _lib_impl.impl("nvfp4_grouped_mm", lambda kind, a, a_scale, wq, w_scale, offs, pa, pb: ops.nvfp4_grouped_mm(kind, a, a_scale, wq, w_scale, offs, pa, pb))
+_lib_impl.impl("nvfp4_train_group_amax", lambda x, offs, mask, want_rht: ops.nvfp4_train_group_amax(x, offs, int(mask), bool(want_rht)))
+_lib_impl.impl("nvfp4_train_quantize_row_col_grouped",
+               lambda x, amax, offs, mask, seed, col_off, row_off: ops.nvfp4_train_quantize_row_col_grouped(x, amax, offs, int(mask), seed, col_off, row_off))
+_lib_impl.impl("nvfp4_train_weight_amax_3d", ops.nvfp4_train_weight_amax_3d)
+_lib_impl.impl("nvfp4_train_quantize_weight_3d", ops.nvfp4_train_quantize_weight_3d)
+_lib_impl.impl("nvfp4_scaled_grouped_mm", lambda a, a_scale, b, b_scale, offs, pa, pb: ops.nvfp4_scaled_grouped_mm(a, a_scale, b, b_scale, offs, pa, pb))
+_lib_impl.impl("nvfp4_grouped_mm_wgrad", lambda g_t, g_s, x_t, x_s, pg, px, offs: ops.nvfp4_grouped_mm_wgrad(g_t, g_s, x_t, x_s, pg, px, offs))
 _lib_impl.impl("fused_pad_token_groups", ops.fused_pad_token_groups)
 _lib_impl.impl("fused_unpad_token_groups", ops.fused_unpad_token_groups)
 
@@ -415,6 +429,43 @@ def _(kind, a, a_scale, wq, w_scale, offs, a_per_group_scale, w_per_expert_scale
     return a.new_empty((a.shape[0], wq.shape[1]), dtype=torch.bfloat16)
 
 
+def _nvfp4_fake_pair(t, rows, cols):
+    return t.new_empty((*rows, cols // 2), dtype=torch.uint8), t.new_empty((*rows, cols // 16), dtype=torch.float8_e4m3fn)
+
+
+@torch.library.register_fake("ao_mi355::nvfp4_train_group_amax")
+def _(x, offs, sign_mask, want_rht):
+    return x.new_empty((offs.shape[0], 2), dtype=torch.float32)
+
+
+@torch.library.register_fake("ao_mi355::nvfp4_train_quantize_row_col_grouped")
+def _(x, amax, offs, sign_mask, sr_seed, col_offset, row_offset):
+    m, n = x.shape
+    return (*_nvfp4_fake_pair(x, (n,), m), *_nvfp4_fake_pair(x, (m,), n))
+
+
+@torch.library.register_fake("ao_mi355::nvfp4_train_weight_amax_3d")
+def _(w):
+    return w.new_empty((w.shape[0],), dtype=torch.float32)
+
+
+@torch.library.register_fake("ao_mi355::nvfp4_train_quantize_weight_3d")
+def _(w, amax):
+    e, n, k = w.shape
+    return (*_nvfp4_fake_pair(w, (e, n), k), *_nvfp4_fake_pair(w, (e, k), n))
+
+
+@torch.library.register_fake("ao_mi355::nvfp4_scaled_grouped_mm")
+def _(a, a_scale, b, b_scale, offs, a_per_group_scale, b_per_expert_scale):
+    return a.new_empty((a.shape[0], b.shape[1]), dtype=torch.bfloat16)
+
+
+@torch.library.register_fake("ao_mi355::nvfp4_grouped_mm_wgrad")
+def _(g_t, g_scale, x_t, x_scale, g_per_group_scale, x_per_group_scale, offs):
+    e = 1 if offs is None else offs.shape[0]
+    return g_t.new_empty((e, g_t.shape[0], x_t.shape[0]), dtype=torch.bfloat16)
+
+
 @torch.library.register_fake("ao_mi355::fused_pad_token_groups")
 def _(inputs, offsets, alignment_size):
     rows = inputs.shape[0] + offsets.shape[0] * alignment_size
@@ -444,7 +495,9 @@ for _name in ("weight_int4pack_mm", "convert_weight_to_int4pack", "int8_scaled_m
               "fp8_block_train_cast", "fp8_block_train_cast_weight", "fp8_block_mm_wgrad",
               "fp8_block_train_cast_weight_3d", "fp8_block_grouped_mm_wgrad",
               "nvfp4_amax_scale", "nvfp4_quantize", "nvfp4_wo_linear", "nvfp4_mm", "nvfp4_linear",
-              "nvfp4_group_amax_scale", "nvfp4_quantize_grouped", "nvfp4_grouped_mm"):
+              "nvfp4_group_amax_scale", "nvfp4_quantize_grouped", "nvfp4_grouped_mm",
+              "nvfp4_train_group_amax", "nvfp4_train_quantize_row_col_grouped", "nvfp4_train_weight_amax_3d",
+              "nvfp4_train_quantize_weight_3d", "nvfp4_scaled_grouped_mm", "nvfp4_grouped_mm_wgrad"):
     _lib_autograd.impl(_name, torch.library.fallthrough_kernel)
 
 

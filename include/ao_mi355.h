@@ -948,6 +948,54 @@ int ao_nvfp4_train_quantize_weight_2d(const uint16_t* w, const float* amax, uint
 int ao_nvfp4_scaled_mm(const uint8_t* a, const uint8_t* a_scale, const float* pa, const uint8_t* b, const uint8_t* b_scale, const float* pb,
                        uint16_t* out, int64_t M, int64_t N, int64_t K, void* stream);
 
+/* ---- NVFP4 training of the MoE grouped GEMM (nvfp4_grouped_train_kernels.hip, nvfp4_kernels.hip) --------------------------
+ * The grouped casts and GEMMs of prototype/moe_training/nvfp4_training/nvfp4_grouped_mm.py (_NVFP4GroupedMM), sm100 only in the
+ * reference.  Every group is cast like a dense tensor under its own amaxes, so the arithmetic, the code packing and the ROW-MAJOR scale
+ * layout are those of the dense training entries above.  No entry allocates or synchronises: all are graph-capturable.
+ * offs int32 [E], cumulative group ends along the tokens, read on the device only.  CONTRACT: every end is a multiple of 16 (the
+ * transform's 16-row runs and the 1 x 16 blocks along the tokens must not straddle a group; the reference needs 128 for its swizzled
+ * scales), non-decreasing, within [0, M_total].  For any other int32 contents the kernels stay inside their buffers and the values are
+ * unspecified.  1 <= E <= 65535. */
+/* Replaces triton_group_rht_amax (group_hadamard_amax_triton.py): x bf16 [M_total][N] in ONE read -> out fp32 [E][2],
+ * [e][0] = max|bf16(RHT(x_e^T))| (0 when want_rht == 0), [e][1] = max|x_e| over group e's rows: ao_nvfp4_train_amax per group.  The call
+ * clears out, then atomic maxima over the non-negative bit patterns.  Rows at or past offs[E-1] reach no reduction; an empty group
+ * gives 0. */
+int ao_nvfp4_train_group_amax(const uint16_t* x, const int32_t* offs, float* out, int64_t M_total, int64_t N, int64_t E, uint32_t sign_mask,
+                              int want_rht, void* stream);
+/* Replaces triton_group_rht_quantize_row_col (group_rht_quantize_row_col_triton.py): ao_nvfp4_train_quantize_row_col with every 16-row
+ * run cast under the amax pair amax[e][0] (column output) / amax[e][1] (row output) of the group e that holds it (resolved per run: a
+ * 128-row tile may hold several groups).  The outputs keep the dense shapes, row_q [M_total][N/2], row_s [M_total][N/16],
+ * col_q [N][M_total/2], col_s [N][M_total/16]; rows at or past offs[E-1] (the reference's capacity rows) are written as zero codes and
+ * zero scale bytes in both.  Stochastic rounding keeps the dense counter contract, g the dword's index in the WHOLE output's row-major
+ * order: with E = 1 and offs = [M_total], or with equal amax pairs for all groups, every byte equals the dense entry's.  Alignment as the
+ * dense entry; amax and offs 4-byte. */
+int ao_nvfp4_train_quantize_row_col_grouped(const uint16_t* x, const float* amax, const int32_t* offs, uint32_t sign_mask, const int64_t* sr_seed,
+                                            const int64_t* col_offset, const int64_t* row_offset, uint8_t* col_q, uint8_t* col_s, uint8_t* row_q,
+                                            uint8_t* row_s, int64_t M_total, int64_t N, int64_t E, void* stream);
+/* Replace triton_group_weight_amax (group_weight_amax_triton.py) and triton_group_weight_quantize_2d (group_quantize_2d_triton.py):
+ * w bf16 [E][N][K] -> out fp32 [E], out[e] = max|w[e]|; and q [E][N][K/2], s [E][N][K/16], qt [E][K][N/2], st [E][K][N/16] under amax[E].
+ * Expert e is byte for byte ao_nvfp4_train_amax(want_rht = 0)[1] and ao_nvfp4_train_quantize_weight_2d on w[e]; one launch each, the expert
+ * a grid dimension with 64-bit strides.  Shapes and alignment per expert as the 2-D entry. */
+int ao_nvfp4_train_weight_amax_3d(const uint16_t* w, float* out, int64_t E, int64_t N, int64_t K, void* stream);
+int ao_nvfp4_train_quantize_weight_3d(const uint16_t* w, const float* amax, uint8_t* q, uint8_t* s, uint8_t* qt, uint8_t* st, int64_t E, int64_t N,
+                                      int64_t K, void* stream);
+/* Replaces F.scaled_grouped_mm on e2m1 codes with BlockWise1x16 + TensorWise scales (nvfp4_grouped_mm.py:198-210 forward, :302-314 dgrad):
+ * ao_nvfp4_grouped_mm's kind 1 -- its route, forced form and kernels -- under ao_nvfp4_scaled_mm's epilogue, out = bf16(acc (pa[e] pb[e])),
+ * ONE rounding; pa and pb fp32 [E], both required.  Serves the forward (x_row against the W codes) and dgrad (dy_row against the W^T codes
+ * [E][K][N/2]).  Group sizes need no alignment here; rows past offs[E-1] are not written. */
+int ao_nvfp4_scaled_grouped_mm(const uint8_t* a, const uint8_t* a_scale, const float* pa, const uint8_t* b, const uint8_t* b_scale, const float* pb,
+                               const int32_t* offs, uint16_t* out, int64_t M_total, int64_t N, int64_t K, int64_t E, void* stream);
+/* Replaces the weight-gradient F.scaled_grouped_mm (nvfp4_grouped_mm.py:315-326), a GEMM whose contraction is the jagged token dimension:
+ *   out[e][n][k] = bf16( (sum over m in [offs[e-1], offs[e]) of dq(g_t)[n][m] dq(x_t)[k][m]) (pg[e] px[e]) ),
+ * dq = f32(code) f32(scale byte), fp32 accumulation, the scale product in fp32, ONE rounding.  g_t codes [N][M_total/2], g_scale e4m3
+ * [N][M_total/16], x_t codes [K][M_total/2], x_scale [K][M_total/16] (the column outputs of the casts above), pg, px fp32 [E], out bf16
+ * [E][N][K].  Tokens of a neighbour group, or past M_total, that share a 64-token step with the group enter as scale byte 0 in BOTH
+ * operands: e2m1 has no NaN or Inf, so a neighbour's NaN scale byte cannot reach this group.  An empty group stores zeros.  offs == NULL
+ * with E == 1: one group of every token, a dense weight gradient.  No split along the tokens and no atomics: a launch is reproducible.
+ * M_total, N, K multiples of 16; sizes and both operands' byte counts below 2^31; the codes 16-byte aligned. */
+int ao_nvfp4_grouped_mm_wgrad(const uint8_t* g_t, const uint8_t* g_scale, const uint8_t* x_t, const uint8_t* x_scale, const float* pg,
+                              const float* px, const int32_t* offs, uint16_t* out, int64_t M_total, int64_t N, int64_t K, int64_t E, void* stream);
+
 /* ---- NVFP4 grouped GEMM for MoE experts (nvfp4_kernels.hip) -------------------------------------------------------------
  * Replaces NVFP4Tensor's aten._grouped_mm (nvfp4_tensor.py:709-753) on 3-D weights with a per-expert [E, 1, 1] scale
  * (inference_workflow.py:309-319, nvfp4_tensor.py:830-834), which runs only through mslk or scaled_grouped_mm on sm100, and its portable
