@@ -194,6 +194,9 @@ _SIGNATURES = {
     "ao_int8_quantize_rowwise_prescaled": [_P, _P, _P, _P, _I64, _I64, _P],
     "ao_int8_quantize_tensorwise_prescaled": [_P, _P, _P, _P, _P, _I64, _I64, _P],
     "ao_int8_quantize_static_prescaled": [_P, _P, _P, _P, _INT, _P, _I64, _I64, _P],
+    "ao_fp8_attn_fits": [_INT, _P, _INT, _P, _INT, _P],
+    "ao_fp8_attn_quantize": [_P, _P, _P, _P, _P, _P, _INT, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P],
+    "ao_fp8_attn_fwd": [_P, _P, _P, _P, _P, _P, _P, _INT, _I64, _I64, _I64, _I64, _I64, _I64, _INT, ctypes.c_float, _P],
 }
 
 

@@ -6,6 +6,7 @@ reference call site.  Tensors must live on the GPU ("cuda" == HIP device on
 ROCm); there is no CPU fallback.
 """
 import ctypes
+import math
 from typing import Optional
 
 import torch
@@ -3163,3 +3164,82 @@ def int8_linear_static_prescaled(x2, pre, wq, w_scale, act_scale, act_zero_point
 
 __all__ += ["sq_col_absmax_update", "sq_smoothed_amax_update", "int8_quantize_rowwise_prescaled", "int8_quantize_tensorwise_prescaled",
             "int8_quantize_static_prescaled", "int8_linear_prescaled", "int8_linear_tensorwise_prescaled", "int8_linear_static_prescaled"]
+
+
+# ---------------------------------------------------------------------------
+# FP8 attention: the per-head e4m3 cast of Q / K / V and the flash-attention forward (csrc/attention_kernels.hip states the arithmetic)
+# ---------------------------------------------------------------------------
+def fp8_attn_fits(q_shape, k_shape, v_shape):
+    """None where the FP8 attention entries serve these shapes, else the reason of the refusal (ao_fp8_attn_fits: host logic, no GPU)."""
+    arrs = [(ctypes.c_int64 * max(len(s), 1))(*[int(d) for d in s]) for s in (q_shape, k_shape, v_shape)]
+    ok = _lib.lib().ao_fp8_attn_fits(len(q_shape), arrs[0], len(k_shape), arrs[1], len(v_shape), arrs[2])
+    return None if ok == 1 else _lib.last_error()
+
+
+def _fp8_attn_check(name, q, k, v):
+    reason = fp8_attn_fits(tuple(q.shape), tuple(k.shape), tuple(v.shape))
+    if reason is not None:
+        raise ValueError(f"{name}: {reason}")
+
+
+def fp8_attn_quantize(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor):
+    """Per-head FP8 cast of Q [B, Hq, Sq, D], K and V [B, Hkv, Skv, D] (bf16 or fp16, one dtype; D contiguous, any strides on B / H / S: a
+    [B, S, H, D].transpose(1, 2) view is read in place) -> (q8, k8, v8 float8_e4m3fn contiguous, dq, dk, dv fp32 [B, Hkv]).  The bits of the
+    reference's triton_fp8_sdpa_quantize: amax per (batch, kv head) -- for Q over the group's query heads --, scale = 448 / amax and
+    descale = amax / 448 (1 where amax <= 1e-12), code = e4m3(x * scale).  Two launches, no host read-back."""
+    name = "fp8_attn_quantize"
+    dev = _require_gpu(name, q, k, v)
+    if q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise NotImplementedError(f"{name}: q, k and v are all bfloat16 or all float16, got {q.dtype}, {k.dtype}, {v.dtype}")
+    _fp8_attn_check(name, q, k, v)
+    b, hq, sq, d = q.shape
+    hkv, skv = k.shape[1], k.shape[2]
+
+    def rows(t):  # the kernel's layout rule; anything else is copied once
+        ok = t.stride(3) == 1 and all(s % 8 == 0 and s >= 0 for s in t.stride()[:3]) and t.data_ptr() % 16 == 0
+        return t if ok or t.numel() == 0 else t.contiguous()
+
+    q, k, v = rows(q), rows(k), rows(v)
+    q8, k8, v8 = (torch.empty(t.shape, dtype=torch.float8_e4m3fn, device=dev) for t in (q, k, v))
+    if q.numel() == 0 or k.numel() == 0:
+        if q.numel() != 0 or k.numel() != 0:
+            raise ValueError(f"{name}: one of q and k / v is empty and the other is not: {tuple(q.shape)}, {tuple(k.shape)}")
+        ones = torch.ones((3, b, hkv), dtype=torch.float32, device=dev)
+        return q8, k8, v8, ones[0], ones[1], ones[2]
+    state = torch.zeros((3, b, hkv), dtype=torch.float32, device=dev)  # (a fill kernel: capturable)
+    descale = torch.empty((3, b, hkv), dtype=torch.float32, device=dev)
+    strides = [(ctypes.c_int64 * 3)(*t.stride()[:3]) for t in (q, k, v)]
+    with _on(dev):
+        _lib.check(_lib.lib().ao_fp8_attn_quantize(_ptr(q), _ptr(k), _ptr(v), strides[0], strides[1], strides[2], int(q.dtype == torch.float16),
+                                                   _ptr(state), _ptr(q8), _ptr(k8), _ptr(v8), _ptr(descale), b, hq, hkv, sq, skv, d, _stream()))
+    return q8, k8, v8, descale[0], descale[1], descale[2]
+
+
+def fp8_attn_fwd(q8: torch.Tensor, k8: torch.Tensor, v8: torch.Tensor, dq: torch.Tensor, dk: torch.Tensor, dv: torch.Tensor,
+                 is_causal: bool = False, scale: Optional[float] = None, out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """Flash attention on FP8 codes: out[b, h, i] = softmax_j(scale dq dk <q8[i], k8[j]>) dv v8[j], fp32 softmax and accumulation, one
+    rounding to out_dtype (bf16 or fp16).  q8 [B, Hq, Sq, D], k8 / v8 [B, Hkv, Skv, D] float8_e4m3fn, D in {64, 128}; dq / dk / dv fp32
+    [B, Hkv], of kv head h // (Hq // Hkv).  is_causal as F.scaled_dot_product_attention (key j visible to query i iff j <= i); scale
+    defaults to 1 / sqrt(D)."""
+    name = "fp8_attn_fwd"
+    dev = _require_gpu(name, q8, k8, v8, dq, dk, dv)
+    if any(t.dtype != torch.float8_e4m3fn for t in (q8, k8, v8)):
+        raise NotImplementedError(f"{name}: q8, k8 and v8 are float8_e4m3fn, got {q8.dtype}, {k8.dtype}, {v8.dtype}")
+    if out_dtype not in (torch.bfloat16, torch.float16):
+        raise NotImplementedError(f"{name}: out_dtype is bfloat16 or float16, got {out_dtype}")
+    _fp8_attn_check(name, q8, k8, v8)
+    b, hq, sq, d = q8.shape
+    hkv, skv = k8.shape[1], k8.shape[2]
+    for what, t in (("dq", dq), ("dk", dk), ("dv", dv)):
+        if t.dtype != torch.float32 or tuple(t.shape) != (b, hkv):
+            raise RuntimeError(f"{name}: {what} must be float32 [B, Hkv] = [{b}, {hkv}], got {t.dtype} {tuple(t.shape)}")
+    q8, k8, v8, dq, dk, dv = (t.contiguous() for t in (q8, k8, v8, dq, dk, dv))
+    out = torch.empty((b, hq, sq, d), dtype=out_dtype, device=dev)
+    scale = 1.0 / math.sqrt(d) if scale is None else float(scale)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_fp8_attn_fwd(_ptr(q8), _ptr(k8), _ptr(v8), _ptr(dq), _ptr(dk), _ptr(dv), _ptr(out), int(out_dtype == torch.float16),
+                                              b, hq, hkv, sq, skv, d, int(bool(is_causal)), scale, _stream()))
+    return out
+
+
+__all__ += ["fp8_attn_fits", "fp8_attn_quantize", "fp8_attn_fwd"]

@@ -40,6 +40,7 @@ from .nvfp4_training import (  # noqa: F401
     get_wgrad_sign_vector,
     nvfp4_linear,
 )
+from .attention import AttentionBackend, HadamardMode, apply_low_precision_attention, fp8_sdpa  # noqa: F401
 from .smoothquant import (  # noqa: F401
     RunningAbsMaxSmoothQuantObserver,
     SmoothQuantConfig,
@@ -58,4 +59,5 @@ __all__ = ["Float8BlockwiseExpertWeights", "fp8_blockwise_grouped_mm", "NVFP4Ten
            "NVFP4Linear", "NVFP4TrainingConfig", "nvfp4_linear", "DEFAULT_SIGN_VECTOR", "get_wgrad_sign_vector",
            "_NVFP4GroupedMM", "_to_nvfp4_rht_rs_then_scaled_grouped_mm",
            "NF4WeightOnlyConfig", "nf4_weight_only", "AWQConfig", "AWQObserver", "AWQObservedLinear",
-           "SmoothQuantConfig", "SmoothQuantStep", "SmoothQuantObserver", "RunningAbsMaxSmoothQuantObserver", "SmoothQuantObservedLinear"]
+           "SmoothQuantConfig", "SmoothQuantStep", "SmoothQuantObserver", "RunningAbsMaxSmoothQuantObserver", "SmoothQuantObservedLinear",
+           "AttentionBackend", "HadamardMode", "apply_low_precision_attention", "fp8_sdpa"]

@@ -715,4 +715,25 @@ for _name in ("int8_linear_prescaled", "int8_linear_tensorwise_prescaled", "int8
     _lib_autograd.impl(_name, torch.library.fallthrough_kernel)
 
 
+# ---- FP8 attention (ops.py "FP8 attention"): the cast of Q / K / V and the flash-attention forward as one opaque node ----------
+# (scale == 0.0 stands for the default 1 / sqrt(D), the convention of the reference's custom op)
+_lib_def.define("fp8_sdpa(Tensor query, Tensor key, Tensor value, bool is_causal, float scale) -> Tensor")
+
+
+def _fp8_sdpa(query, key, value, is_causal, scale):
+    q8, k8, v8, dq, dk, dv = ops.fp8_attn_quantize(query, key, value)
+    return ops.fp8_attn_fwd(q8, k8, v8, dq, dk, dv, is_causal, None if scale == 0.0 else scale, query.dtype)
+
+
+_lib_impl.impl("fp8_sdpa", _fp8_sdpa)
+
+
+@torch.library.register_fake("ao_mi355::fp8_sdpa")
+def _(query, key, value, is_causal, scale):
+    return query.new_empty(query.shape)
+
+
+_lib_autograd.impl("fp8_sdpa", torch.library.fallthrough_kernel)
+
+
 load_ops_library()

@@ -1218,6 +1218,33 @@ int ao_int8_quantize_tensorwise_prescaled(const uint16_t* x, const uint16_t* pre
 int ao_int8_quantize_static_prescaled(const uint16_t* x, const uint16_t* pre, const float* scale, const int8_t* zero_point, int per_row,
                                       int8_t* q, int64_t M, int64_t K, void* stream);
 
+/* ---- FP8 attention (torchao/prototype/attention) ------------------------------------------------------------------------------------------------
+ * ao_fp8_attn_quantize replaces triton_fp8_sdpa_quantize (prototype/attention/quantization/triton_qkv_quantization.py:102-166, 240, 264-460:
+ * nine Triton launches) by two: one amax launch and one cast launch, each over all three tensors.
+ *   q bf16 / fp16 (is_fp16) [B][Hq][Sq][D], k and v [B][Hkv][Skv][D], Hq % Hkv == 0, D in {64, 128} contiguous; *_strides = the element strides
+ *   of {batch, head, row}, any non-negative multiples of 8 (the [B, S, H, D].transpose(1, 2) view is read in place); 16-byte aligned.
+ *   amax per (batch, kv head): for q over the Hq / Hkv query heads of the group and all rows.
+ *   scale = amax > 1e-12 ? 448 / amax : 1;  descale = amax > 1e-12 ? amax / 448 : 1   (IEEE fp32 divisions)
+ *   code  = e4m3fn_rne(clamp(f32(x) * scale, -448, 448))
+ *   q8 / k8 / v8: the codes, contiguous [B][H][S][D];  descale fp32 [3][B][Hkv] (q, k, v);  state fp32 [3][B][Hkv]: work memory the caller has
+ *   ZEROED -- the amax launch folds into it with an integer atomic max on the bit pattern of non-negative floats (exact, order-independent).
+ * ao_fp8_attn_fwd replaces _scaled_dot_product_attention_quantized under the FA3 implementation (shared_utils/attention.py:81-93), which the
+ * reference reaches only on Hopper:
+ *   out[b][h][i][:] = softmax_j(scale dq dk sum_d q8[i][d] k8[j][d]) dv v8[j][:]     descales of kv head h / (Hq / Hkv), fp32 [B][Hkv] each
+ *   fp32 accumulation and softmax; P goes to the matrix pipe as e4m3(256 p), the row sum is taken from the fp32 p; one rounding to out
+ *   (bf16, or fp16 with out_fp16) [B][Hq][Sq][D].  is_causal: key j visible to query i iff j <= i (top-left aligned, as
+ *   F.scaled_dot_product_attention).  Codes contiguous and 16-byte aligned; Skv >= 1; a finite scale.
+ * ao_fp8_attn_fits (host logic, no launch): 1 where both entries serve the shapes, else 0 with the reason in ao_last_error(): a rank other
+ * than 4, K and V of different shapes, batch or head-dimension mismatch, D outside {64, 128}, Hq % Hkv != 0, B or Hq above 65535,
+ * Sq or Skv from 2^23.  The entries refuse the same shapes with AO_ERR_INVALID_ARGUMENT before any launch.
+ * Empty tensors launch nothing.  No allocation, no synchronisation, no host read-back: capturable in a graph. */
+int ao_fp8_attn_fits(int q_rank, const int64_t* q_shape, int k_rank, const int64_t* k_shape, int v_rank, const int64_t* v_shape);
+int ao_fp8_attn_quantize(const void* q, const void* k, const void* v, const int64_t* q_strides, const int64_t* k_strides,
+                         const int64_t* v_strides, int is_fp16, float* state, uint8_t* q8, uint8_t* k8, uint8_t* v8, float* descale, int64_t B,
+                         int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, void* stream);
+int ao_fp8_attn_fwd(const uint8_t* q8, const uint8_t* k8, const uint8_t* v8, const float* dq, const float* dk, const float* dv, void* out,
+                    int out_fp16, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, int is_causal, float scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
