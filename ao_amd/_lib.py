@@ -197,6 +197,12 @@ _SIGNATURES = {
     "ao_fp8_attn_fits": [_INT, _P, _INT, _P, _INT, _P],
     "ao_fp8_attn_quantize": [_P, _P, _P, _P, _P, _P, _INT, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P],
     "ao_fp8_attn_fwd": [_P, _P, _P, _P, _P, _P, _P, _INT, _I64, _I64, _I64, _I64, _I64, _I64, _INT, ctypes.c_float, _P],
+    "ao_bitnet_absmean": [_P, _I64, _P, _P, _P, _P],
+    "ao_bitnet_quantize_weight": [_P, _P, _P, _P, _I64, _I64, _P],
+    "ao_bitnet_dequantize": [_P, _P, _I64, _I64, _P],
+    "ao_bitnet_quantize_act": [_P, _P, _P, _I64, _I64, _P],
+    "ao_bitnet_mm_fits": [_I64, _I64, _I64],
+    "ao_bitnet_mm": [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _INT, _P],
 }
 
 

@@ -721,6 +721,18 @@ __device__ __forceinline__ float int4_group_code(float x, float m, float s) {
   return fminf(fmaxf(rintf((x - m) / s), 0.f), 15.f);
 }
 
+// ---- BitNet b1.58 (bitnet_kernels.hip): torchao/prototype/quantized_training/bitnet.py, every step ONE fp32 operation, divisions IEEE ------
+//   weight  q = clip(rint(f32(w) / max(scale, 1e-5)), -1, 1), rint to even (quantize_bitnet_weight :156-159); s below is the clipped scale
+//   output  y = bf16((f32(acc) * f32(row_scale)) * f32(tensor_scale)), ONE rounding (scaled_int8_mm); with a bias a second one,
+//           y = bf16(f32(y) + f32(bias)) (the reference's separate add).  Returns the bf16 bits.
+constexpr float kBitnetEps = 1e-5f;
+__device__ __forceinline__ uint32_t bitnet_ternary(float w, float s) { return (uint32_t)(int)fminf(fmaxf(rintf(w / s), -1.f), 1.f); }
+__device__ __forceinline__ uint16_t bitnet_out(int acc, float rs, float ts, bool has_bias, float bias) {
+  float v = mul_f32_rn(mul_f32_rn((float)acc, rs), ts);
+  if (has_bias) v = round_bf16(v) + bias;
+  return f32_to_bf16_bits(v);
+}
+
 // ---- a tensor as a flat run of 16-byte vectors of 8 bf16, one per lane; a group is LANES = g / 8 adjacent lanes (K % g == 0 keeps groups
 // whole inside a row, and LANES divides the wave), so every group reduction is a butterfly over lanes: no LDS, no atomics -----------------
 __device__ __forceinline__ void unpack_bf16x8(const u32x4& v, float (&f)[8]) {

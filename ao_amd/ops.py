@@ -3243,3 +3243,129 @@ def fp8_attn_fwd(q8: torch.Tensor, k8: torch.Tensor, v8: torch.Tensor, dq: torch
 
 
 __all__ += ["fp8_attn_fits", "fp8_attn_quantize", "fp8_attn_fwd"]
+
+
+# ---------------------------------------------------------------------------
+# BitNet b1.58: the ternary weight cast, the int8 activation cast and the 2-bit-weight int8 matmul (csrc/bitnet_kernels.hip states the arithmetic)
+# ---------------------------------------------------------------------------
+BITNET_MM_AUTO, BITNET_MM_STREAM, BITNET_MM_TILED = 0, 1, 2
+_BITNET_ABSMEAN_WORKSPACE = 1024  # float64 partials (AO_BITNET_ABSMEAN_WORKSPACE)
+
+
+def _bitnet_2d(name, what, t, dtype):
+    if t.dim() != 2:
+        raise RuntimeError(f"{name}: {what} must be 2-D, got {t.dim()}-D")
+    if t.dtype != dtype:
+        hint = " (float16 and float32 are not built: BitNet here is bfloat16 only)" if dtype == torch.bfloat16 else ""
+        raise NotImplementedError(f"{name}: {what} must be {dtype}, got {t.dtype}{hint}")
+    return t.contiguous()
+
+
+def bitnet_mm_fits(m: int, n: int, k: int):
+    """None where bitnet_mm serves the shape, else the reason of the refusal (ao_bitnet_mm_fits: host logic, no GPU)."""
+    return None if _lib.lib().ao_bitnet_mm_fits(int(m), int(n), int(k)) == 1 else _lib.last_error()
+
+
+def bitnet_absmean(w: torch.Tensor, with_bf16: bool = False):
+    """get_bitnet_scale: the tensor-wise mean of |w| of a bf16 [N, K] weight as a 0-dim fp32 tensor on the device, summed in float64 in a fixed
+    order (the same bits on every run, within one fp32 ulp of the float64 mean).  with_bf16: also the value rounded to bf16, what bitnet_mm
+    takes.  No host read-back."""
+    name = "bitnet_absmean"
+    dev = _require_gpu(name, w)
+    w = _bitnet_2d(name, "w", w, torch.bfloat16)
+    if w.numel() == 0 or w.shape[1] % 4 != 0:
+        raise ValueError(f"{name}: w {tuple(w.shape)} must be non-empty with K a multiple of 4")
+    work = torch.empty(_BITNET_ABSMEAN_WORKSPACE, dtype=torch.float64, device=dev)
+    out = torch.empty((), dtype=torch.float32, device=dev)
+    out16 = torch.empty((), dtype=torch.bfloat16, device=dev) if with_bf16 else None
+    with _on(dev):
+        _lib.check(_lib.lib().ao_bitnet_absmean(_ptr(w), w.numel(), _ptr(work), _ptr(out), _ptr(out16), _stream()))
+    return (out, out16) if with_bf16 else out
+
+
+def bitnet_quantize_weight(w: torch.Tensor, scale: torch.Tensor, with_int8: bool = False):
+    """quantize_bitnet_weight + _pack_i2_in_i8 in one read: bf16 w [N, K] (K % 4 == 0) and a 0-dim fp32 device scale -> int8 [N, K / 4] holding
+    the reference's packed bytes; with_int8: also the ternary int8 [N, K]."""
+    name = "bitnet_quantize_weight"
+    dev = _require_gpu(name, w, scale)
+    w = _bitnet_2d(name, "w", w, torch.bfloat16)
+    if scale.dtype != torch.float32 or scale.numel() != 1:
+        raise RuntimeError(f"{name}: scale must be one float32 value on the device, got {scale.dtype} {tuple(scale.shape)}")
+    n, k = w.shape
+    if k % 4 != 0 or k == 0:
+        raise ValueError(f"{name}: K={k} must be a positive multiple of 4 (four weights to a byte)")
+    packed = torch.empty((n, k // 4), dtype=torch.int8, device=dev)
+    q8 = torch.empty((n, k), dtype=torch.int8, device=dev) if with_int8 else None
+    with _on(dev):
+        _lib.check(_lib.lib().ao_bitnet_quantize_weight(_ptr(w), _ptr(scale), _ptr(packed), _ptr(q8), n, k, _stream()))
+    return (packed, q8) if with_int8 else packed
+
+
+def bitnet_dequantize(packed: torch.Tensor) -> torch.Tensor:
+    """_unpack_i2_in_i8(packed).to(bf16): int8 [N, K / 4] packed bytes -> bf16 [N, K] of -1 / 0 / 1, no scale applied."""
+    name = "bitnet_dequantize"
+    dev = _require_gpu(name, packed)
+    packed = _bitnet_2d(name, "packed", packed, torch.int8)
+    n, kb = packed.shape
+    out = torch.empty((n, kb * 4), dtype=torch.bfloat16, device=dev)
+    if out.numel():
+        with _on(dev):
+            _lib.check(_lib.lib().ao_bitnet_dequantize(_ptr(packed), _ptr(out), n, kb * 4, _stream()))
+    return out
+
+
+def bitnet_quantize_act(x: torch.Tensor):
+    """quantize_int8_rowwise(x, eps=1e-5) of bf16 x [M, K] (K % 8 == 0) in one launch -> (int8 [M, K], bf16 scales [M])."""
+    name = "bitnet_quantize_act"
+    dev = _require_gpu(name, x)
+    x = _bitnet_2d(name, "x", x, torch.bfloat16)
+    m, k = x.shape
+    if k % 8 != 0 or k == 0:
+        raise ValueError(f"{name}: K={k} must be a positive multiple of 8")
+    q = torch.empty((m, k), dtype=torch.int8, device=dev)
+    s = torch.empty((m,), dtype=torch.bfloat16, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_bitnet_quantize_act(_ptr(x), _ptr(q), _ptr(s), m, k, _stream()))
+    return q, s
+
+
+def bitnet_mm(a: torch.Tensor, packed: torch.Tensor, row_scale: torch.Tensor, tensor_scale: torch.Tensor,
+              bias: Optional[torch.Tensor] = None, form: int = BITNET_MM_AUTO) -> torch.Tensor:
+    """scaled_int8_mm(a, _unpack_i2_in_i8(packed).T, row_scale, tensor_scale) (+ bias) without the int8 copy of the weight: int8 a [M, K],
+    packed int8 [N, K / 4], bf16 row_scale [M], a 0-dim bf16 tensor_scale on the device, bf16 bias [N] or None -> bf16 [M, N] =
+    bf16((f32(acc) * row_scale) * tensor_scale), then bf16(that + bias).  K % 64 == 0.  form: BITNET_MM_AUTO (streaming up to 16 rows, tiled
+    above) or one form forced (measurement and tests)."""
+    name = "bitnet_mm"
+    dev = _require_gpu(name, a, packed, row_scale, tensor_scale, bias)
+    a = _bitnet_2d(name, "a", a, torch.int8)
+    packed = _bitnet_2d(name, "packed", packed, torch.int8)
+    m, k = a.shape
+    n = packed.shape[0]
+    if packed.shape[1] * 4 != k:
+        raise RuntimeError(f"{name}: packed {tuple(packed.shape)} does not hold K={k} weights a row")
+    reason = bitnet_mm_fits(m, n, k)
+    if reason is not None:
+        raise ValueError(f"{name}: {reason}")
+    if row_scale.dtype != torch.bfloat16 or row_scale.numel() != m:
+        raise RuntimeError(f"{name}: row_scale must be bfloat16 with M={m} values, got {row_scale.dtype} {tuple(row_scale.shape)}")
+    if tensor_scale.dtype != torch.bfloat16 or tensor_scale.numel() != 1:
+        raise RuntimeError(f"{name}: tensor_scale must be one bfloat16 value on the device, got {tensor_scale.dtype} {tuple(tensor_scale.shape)}")
+    if bias is not None and (bias.dtype != torch.bfloat16 or tuple(bias.shape) != (n,)):
+        raise RuntimeError(f"{name}: bias must be bfloat16 [{n}], got {bias.dtype} {tuple(bias.shape)}")
+    out = torch.empty((m, n), dtype=torch.bfloat16, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_bitnet_mm(_ptr(a), _ptr(packed), _ptr(row_scale.contiguous()), _ptr(tensor_scale),
+                                           _ptr(bias.contiguous() if bias is not None else None), _ptr(out), m, n, k, int(form), _stream()))
+    return out
+
+
+def bitnet_linear(x: torch.Tensor, packed: torch.Tensor, tensor_scale: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                  form: int = BITNET_MM_AUTO) -> torch.Tensor:
+    """The BitNet forward on a packed weight: the activation cast, then bitnet_mm.  x bf16 [..., K] -> bf16 [..., N]."""
+    if x.dtype != torch.bfloat16:
+        raise NotImplementedError(f"bitnet_linear: x must be bfloat16, got {x.dtype} (float16 and float32 activations are not built)")
+    q, s = bitnet_quantize_act(x.reshape(-1, x.shape[-1]))
+    return bitnet_mm(q, packed, s, tensor_scale, bias, form).view(*x.shape[:-1], packed.shape[0])
+
+
+__all__ += ["bitnet_mm_fits", "bitnet_absmean", "bitnet_quantize_weight", "bitnet_dequantize", "bitnet_quantize_act", "bitnet_mm", "bitnet_linear"]

@@ -736,4 +736,17 @@ def _(query, key, value, is_causal, scale):
 _lib_autograd.impl("fp8_sdpa", torch.library.fallthrough_kernel)
 
 
+# ---- BitNet b1.58 (ops.py "BitNet"): the activation cast and the 2-bit-weight matmul on a packed weight as one opaque node -----
+_lib_def.define("bitnet_linear(Tensor x, Tensor packed, Tensor tensor_scale, Tensor? bias) -> Tensor")
+_lib_impl.impl("bitnet_linear", lambda x, packed, tensor_scale, bias: ops.bitnet_linear(x, packed, tensor_scale, bias))
+
+
+@torch.library.register_fake("ao_mi355::bitnet_linear")
+def _(x, packed, tensor_scale, bias):
+    return x.new_empty((*x.shape[:-1], packed.shape[0]))
+
+
+_lib_autograd.impl("bitnet_linear", torch.library.fallthrough_kernel)
+
+
 load_ops_library()

@@ -1245,6 +1245,40 @@ int ao_fp8_attn_quantize(const void* q, const void* k, const void* v, const int6
 int ao_fp8_attn_fwd(const uint8_t* q8, const uint8_t* k8, const uint8_t* v8, const float* dq, const float* dk, const float* dv, void* out,
                     int out_fp16, int64_t B, int64_t Hq, int64_t Hkv, int64_t Sq, int64_t Skv, int64_t D, int is_causal, float scale, void* stream);
 
+/* ---- BitNet b1.58 (torchao/prototype/quantized_training/bitnet.py) ---------------------------------------------------------------------------------
+ * Ternary weights packed four to a byte against int8 activations.  Every fp32 step is one operation rounded once; divisions are IEEE.
+ * ao_bitnet_absmean (get_bitnet_scale, :151-153): out = f32(sum |w| / numel), sum and quotient in float64, w bf16, numel % 4 == 0.  Each
+ *   workgroup writes one float64 partial into workspace (AO_BITNET_ABSMEAN_WORKSPACE doubles, the caller's), a second launch adds them in index
+ *   order: no floating-point atomics, the same bits on every run, within one fp32 ulp of the float64 mean.  out_bf16 (may be null): the
+ *   same value rounded to bf16, the scalar ao_bitnet_mm takes (tensor_scale.to(weight.dtype), :205).
+ * ao_bitnet_quantize_weight (quantize_bitnet_weight :156-159 + _pack_i2_in_i8 :261-273 in one read of w): w bf16 [N][K], K % 4 == 0, scale one
+ *   fp32 on the device;  q = clip(rint(f32(w) / max(scale, 1e-5)), -1, 1), rint to even;  packed [N][K / 4]: byte j of a row =
+ *   q[4j] << 6 | (q[4j+1] & 3) << 4 | (q[4j+2] & 3) << 2 | (q[4j+3] & 3) -- the reference's bytes;  q8 (may be null): the int8 values [N][K].
+ * ao_bitnet_dequantize (_unpack_i2_in_i8 :276-281, .to(bf16)): packed [N][K / 4] -> bf16 [N][K], each 2-bit field sign-extended, no scale.
+ * ao_bitnet_quantize_act (quantize_int8_rowwise(x, eps=1e-5), int8.py:25-53): x bf16 [M][K], K % 8 == 0;  scale[m] = bf16(amax_m / 127);
+ *   inv = 1 / max(f32(scale[m]), 1e-5);  q = clip(rint(f32(x) * inv), -128, 127).  One launch.
+ * ao_bitnet_mm (scaled_int8_mm on _unpack_i2_in_i8(w).T with a scalar column scale, :370-379): a int8 [M][K], w packed [N][K / 4],
+ *   row_scale bf16 [M], tensor_scale ONE bf16 on the device, bias bf16 [N] or null, out bf16 [M][N]:
+ *     out = bf16((f32(acc) * f32(row_scale[m])) * f32(tensor_scale));  with a bias, a second rounding out = bf16(f32(out) + f32(bias[n]))
+ *   acc the exact int32 sum, so both forms give the same bits.  form: AO_BITNET_MM_AUTO (streaming up to AO_BITNET_MM_STREAM_MAX_M rows,
+ *   tiled above), or one of the two forced (measurement and tests; both serve every M).  The weights are unpacked in registers inside the
+ *   kernels: no int8 copy of w exists.
+ * ao_bitnet_mm_fits (host logic, no launch): 1 where ao_bitnet_mm serves the shape, else 0 with the reason in ao_last_error(): K no
+ *   multiple of 64, M above 2^19, N or K above 2^24.  ao_bitnet_mm refuses the same shapes with AO_ERR_INVALID_ARGUMENT before any launch.
+ * Pointers 16-byte aligned (packed bytes of the casts: 4).  No allocation, no synchronisation, no host read-back: capturable in a graph. */
+#define AO_BITNET_ABSMEAN_WORKSPACE 1024
+#define AO_BITNET_MM_AUTO 0
+#define AO_BITNET_MM_STREAM 1
+#define AO_BITNET_MM_TILED 2
+#define AO_BITNET_MM_STREAM_MAX_M 16
+int ao_bitnet_absmean(const uint16_t* w, int64_t numel, double* workspace, float* out, uint16_t* out_bf16, void* stream);
+int ao_bitnet_quantize_weight(const uint16_t* w, const float* scale, uint8_t* packed, int8_t* q8, int64_t N, int64_t K, void* stream);
+int ao_bitnet_dequantize(const uint8_t* packed, uint16_t* out, int64_t N, int64_t K, void* stream);
+int ao_bitnet_quantize_act(const uint16_t* x, int8_t* q, uint16_t* scale, int64_t M, int64_t K, void* stream);
+int ao_bitnet_mm_fits(int64_t M, int64_t N, int64_t K);
+int ao_bitnet_mm(const int8_t* a, const uint8_t* w, const uint16_t* row_scale, const uint16_t* tensor_scale, const uint16_t* bias, uint16_t* out,
+                 int64_t M, int64_t N, int64_t K, int form, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
