@@ -203,6 +203,15 @@ _SIGNATURES = {
     "ao_bitnet_quantize_act": [_P, _P, _P, _I64, _I64, _P],
     "ao_bitnet_mm_fits": [_I64, _I64, _I64],
     "ao_bitnet_mm": [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _INT, _P],
+    "ao_intx_quantize": [_P, _P, _P, _P, _I64, _I64, _I64, _INT, _INT, _INT, _P],
+    "ao_int8_fake_quantize_per_token_asym": [_P, _P, _I64, _I64, _P],
+    "ao_intx_pack": [_P, _P, _I64, _I64, _INT, _P],
+    "ao_intx_unpack": [_P, _P, _I64, _I64, _INT, _P],
+    "ao_intx_dequantize": [_P, _P, _P, _P, _I64, _I64, _I64, _INT, _P],
+    "ao_intx_linear_fits": [_INT, _I64, _I64, _I64, _I64],
+    "ao_intx_linear_route": [_INT, _I64, _I64, _I64, _I64, _P, _INT],
+    "ao_intx_linear_set_form": [_INT],
+    "ao_intx_linear": [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _INT, _P],
 }
 
 

@@ -37,11 +37,13 @@ FLAGS = [
 # build: the check is the resource report (-Rpass-analysis=kernel-resource-usage), 61 and 86 VGPRs.
 # attention_kernels.hip likewise: its fp32 work is the softmax's single multiplies, subtractions and v_exp_f32 between two MFMA products.
 # bitnet_kernels.hip likewise: its fp32 work is the casts' chain of single IEEE operations and a two-multiply epilogue.
+# intx_kernels.hip likewise: the affine cast's chain of single operations and the decode's add and multiply per weight.
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SOURCE_FLAGS = {
     "nvfp4_grouped_train_kernels.hip": _NO_PACKED_FP32,
     "attention_kernels.hip": _NO_PACKED_FP32,
     "bitnet_kernels.hip": _NO_PACKED_FP32,
+    "intx_kernels.hip": _NO_PACKED_FP32,
 }
 
 

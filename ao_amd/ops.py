@@ -3369,3 +3369,193 @@ def bitnet_linear(x: torch.Tensor, packed: torch.Tensor, tensor_scale: torch.Ten
 
 
 __all__ += ["bitnet_mm_fits", "bitnet_absmean", "bitnet_quantize_weight", "bitnet_dequantize", "bitnet_quantize_act", "bitnet_mm", "bitnet_linear"]
+
+
+# ---------------------------------------------------------------------------
+# Intx weights, int1 .. int8: the affine cast, the bit-packed layout, the per-token activation fake quantization and the fused linear
+# (csrc/intx_kernels.hip states the arithmetic and the layout)
+# ---------------------------------------------------------------------------
+INTX_MAPPINGS = {"SYMMETRIC": 0, "SYMMETRIC_NO_CLIPPING_ERR": 1, "ASYMMETRIC": 2}
+
+
+def _intx_2d(name, what, t, dtype):
+    if t.dim() != 2:
+        raise RuntimeError(f"{name}: {what} must be 2-D, got {t.dim()}-D")
+    if t.dtype != dtype:
+        hint = " (float16 and float32 are not built: Intx here is bfloat16 only)" if dtype == torch.bfloat16 else ""
+        raise NotImplementedError(f"{name}: {what} must be {dtype}, got {t.dtype}{hint}")
+    return t.contiguous()
+
+
+def _intx_bits(name, bits):
+    if not 1 <= int(bits) <= 8:
+        raise ValueError(f"{name}: bits must be 1 .. 8, got {bits}")
+    return int(bits)
+
+
+def intx_linear_fits(bits: int, m: int, n: int, k: int, group_size: int):
+    """None where intx_linear serves the shape, else the reason of the refusal (ao_intx_linear_fits: host logic, no GPU)."""
+    return None if _lib.lib().ao_intx_linear_fits(int(bits), int(m), int(n), int(k), int(group_size)) == 1 else _lib.last_error()
+
+
+def intx_linear_route(bits: int, m: int, n: int, k: int, group_size: int):
+    """The route of intx_linear: (kernel 1 stream / 2 tile / 0 none, waves, m-tiles, tile_m, tile_n, grid_x, grid_y)."""
+    out = (ctypes.c_int32 * 7)()
+    _lib.check(_lib.lib().ao_intx_linear_route(int(bits), int(m), int(n), int(k), int(group_size), out, 7))
+    return tuple(out)
+
+
+def intx_linear_set_form(form: int):
+    """Force one form of intx_linear on the calling thread: 0 the route, 1 stream, 2 tile (measurement and tests)."""
+    _lib.check(_lib.lib().ao_intx_linear_set_form(int(form)))
+
+
+def intx_quantize(w: torch.Tensor, group_size: int, bits: int, mapping: str = "SYMMETRIC", scale: Optional[torch.Tensor] = None,
+                  zero_point: Optional[torch.Tensor] = None):
+    """choose_qparams_affine + quantize_affine of a bf16 weight [N, K] in one launch, in the reference's bf16 arithmetic -> (int8 codes [N, K],
+    bf16 scale [N, K / g], int8 zero_point [N, K / g]).  mapping: a name of INTX_MAPPINGS.  With scale and zero_point given (bf16 / int8,
+    [N, K / g]) only the codes are computed: quantize_affine under custom qparams."""
+    name = "intx_quantize"
+    dev = _require_gpu(name, w, scale, zero_point)
+    w = _intx_2d(name, "w", w, torch.bfloat16)
+    bits = _intx_bits(name, bits)
+    if mapping not in INTX_MAPPINGS:
+        raise ValueError(f"{name}: mapping must be one of {sorted(INTX_MAPPINGS)}, got {mapping!r}")
+    n, k = w.shape
+    g = int(group_size)
+    if g < 8 or g % 8 != 0 or k % g != 0:
+        raise ValueError(f"{name}: group_size={g} must be a multiple of 8 that divides K={k}")
+    given = scale is not None or zero_point is not None
+    if given:
+        if scale is None or zero_point is None:
+            raise ValueError(f"{name}: scale and zero_point are given together")
+        if scale.dtype != torch.bfloat16 or zero_point.dtype != torch.int8 or tuple(scale.shape) != (n, k // g) or tuple(zero_point.shape) != (n, k // g):
+            raise RuntimeError(f"{name}: custom scale must be bfloat16 and zero_point int8, both [{n}, {k // g}], got {scale.dtype} "
+                               f"{tuple(scale.shape)} / {zero_point.dtype} {tuple(zero_point.shape)}")
+        scale, zero_point = scale.contiguous(), zero_point.contiguous()
+    else:
+        scale = torch.empty((n, k // g), dtype=torch.bfloat16, device=dev)
+        zero_point = torch.empty((n, k // g), dtype=torch.int8, device=dev)
+    q = torch.empty((n, k), dtype=torch.int8, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_intx_quantize(_ptr(w), _ptr(q), _ptr(scale), _ptr(zero_point), n, k, g, bits, INTX_MAPPINGS[mapping],
+                                               int(given), _stream()))
+    return q, scale, zero_point
+
+
+def int8_fake_quantize_per_token_asym(x: torch.Tensor) -> torch.Tensor:
+    """_apply_int8_act_asym_per_token_quant_dequant: bf16 x [..., K] (K % 8 == 0) -> its asymmetric per-token int8 quantization, dequantized,
+    in one launch."""
+    name = "int8_fake_quantize_per_token_asym"
+    dev = _require_gpu(name, x)
+    if x.dtype != torch.bfloat16:
+        raise NotImplementedError(f"{name}: x must be bfloat16, got {x.dtype} (float16 and float32 activations are not built)")
+    x2 = x.reshape(-1, x.shape[-1]).contiguous()
+    m, k = x2.shape
+    if k % 8 != 0 or k == 0:
+        raise ValueError(f"{name}: K={k} must be a positive multiple of 8")
+    out = torch.empty_like(x2)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_int8_fake_quantize_per_token_asym(_ptr(x2), _ptr(out), m, k, _stream()))
+    return out.view(x.shape)
+
+
+def intx_pack(q: torch.Tensor, bits: int) -> torch.Tensor:
+    """int8 codes [N, K] (K % 32 == 0) in the range of int{bits} -> the device layout, int32 [N, K / 32 * bits]."""
+    name = "intx_pack"
+    dev = _require_gpu(name, q)
+    q = _intx_2d(name, "q", q, torch.int8)
+    bits = _intx_bits(name, bits)
+    n, k = q.shape
+    if k % 32 != 0 or k == 0:
+        raise ValueError(f"{name}: K={k} must be a positive multiple of 32 (a packed run is 32 weights)")
+    packed = torch.empty((n, k // 32 * bits), dtype=torch.int32, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_intx_pack(_ptr(q), _ptr(packed), n, k, bits, _stream()))
+    return packed
+
+
+def intx_unpack(packed: torch.Tensor, bits: int) -> torch.Tensor:
+    """The inverse of intx_pack: int32 [N, K / 32 * bits] -> int8 codes [N, K]."""
+    name = "intx_unpack"
+    dev = _require_gpu(name, packed)
+    packed = _intx_2d(name, "packed", packed, torch.int32)
+    bits = _intx_bits(name, bits)
+    n, d = packed.shape
+    if d % bits != 0 or d == 0:
+        raise ValueError(f"{name}: packed {tuple(packed.shape)} is no whole number of {bits}-dword runs a row")
+    k = d // bits * 32
+    q = torch.empty((n, k), dtype=torch.int8, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_intx_unpack(_ptr(packed), _ptr(q), n, k, bits, _stream()))
+    return q
+
+
+def _intx_weight(name, w, scale, zero_point, bits, dev):
+    """(codes, scale, zero_point, N, K, g, layout bits) of an Intx weight: int8 [N, K] unpacked codes (read in place by the 8-bit loader) or
+    int32 [N, K / 32 * bits] packed ones."""
+    bits = _intx_bits(name, bits)
+    if w.dim() != 2:
+        raise RuntimeError(f"{name}: the weight codes must be 2-D, got {w.dim()}-D")
+    if w.dtype == torch.int8:
+        n, k, layout = w.shape[0], w.shape[1], 8
+    elif w.dtype == torch.int32:
+        if w.shape[1] % bits != 0:
+            raise RuntimeError(f"{name}: packed {tuple(w.shape)} is no whole number of {bits}-dword runs a row")
+        n, k, layout = w.shape[0], w.shape[1] // bits * 32, bits
+    else:
+        raise RuntimeError(f"{name}: the weight codes must be int8 (unpacked) or int32 (packed), got {w.dtype}")
+    if scale.dtype != torch.bfloat16:
+        raise NotImplementedError(f"{name}: scale must be bfloat16, got {scale.dtype} (float16 and float32 are not built: Intx here is bfloat16 only)")
+    if zero_point.dtype != torch.int8:
+        raise NotImplementedError(f"{name}: zero_point must be int8, got {zero_point.dtype} (float zero-points are not built)")
+    if scale.dim() != 2 or scale.shape[0] != n or scale.shape[1] == 0 or k % scale.shape[1] != 0 or tuple(zero_point.shape) != tuple(scale.shape):
+        raise RuntimeError(f"{name}: scale {tuple(scale.shape)} and zero_point {tuple(zero_point.shape)} must both be [N={n}, K / g] for K={k}")
+    return w.contiguous(), scale.contiguous(), zero_point.contiguous(), n, k, k // scale.shape[1], layout
+
+
+def intx_dequantize(w: torch.Tensor, scale: torch.Tensor, zero_point: torch.Tensor, bits: int) -> torch.Tensor:
+    """dequantize_affine of an Intx weight (unpacked int8 or packed int32 codes) -> bf16 [N, K] = bf16((q - zero_point) * scale)."""
+    name = "intx_dequantize"
+    dev = _require_gpu(name, w, scale, zero_point)
+    w, scale, zero_point, n, k, g, layout = _intx_weight(name, w, scale, zero_point, bits, dev)
+    if k % 32 != 0 or g % 32 != 0:
+        raise ValueError(f"{name}: K={k} and the group size {g} must be multiples of 32")
+    out = torch.empty((n, k), dtype=torch.bfloat16, device=dev)
+    if out.numel():
+        with _on(dev):
+            _lib.check(_lib.lib().ao_intx_dequantize(_ptr(w), _ptr(scale), _ptr(zero_point), _ptr(out), n, k, g, layout, _stream()))
+    return out
+
+
+def intx_linear(x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor, zero_point: torch.Tensor, bits: int,
+                bias: Optional[torch.Tensor] = None, act_quant: bool = False) -> torch.Tensor:
+    """F.linear(x, dequantize_affine(w), bias) in one launch without the bf16 copy of the weight: x bf16 [..., K]; w unpacked int8 [N, K] or
+    packed int32 [N, K / 32 * bits] codes of int{bits}; scale bf16 and zero_point int8 [N, K / g]; bias bf16 [N] or None -> bf16 [..., N],
+    fp32 accumulation, one rounding.  K and g multiples of 32.  act_quant: x goes through int8_fake_quantize_per_token_asym first (a launch
+    of its own), the reference's chain for Int8DynamicActivationIntxWeightConfig."""
+    name = "intx_linear"
+    dev = _require_gpu(name, x, w, scale, zero_point, bias)
+    if x.dtype != torch.bfloat16:
+        raise NotImplementedError(f"{name}: x must be bfloat16, got {x.dtype} (float16 and float32 activations are not built)")
+    w, scale, zero_point, n, k, g, layout = _intx_weight(name, w, scale, zero_point, bits, dev)
+    if x.shape[-1] != k:
+        raise RuntimeError(f"{name}: x {tuple(x.shape)} does not end in K={k}")
+    x2 = x.reshape(-1, k).contiguous()
+    m = x2.shape[0]
+    if act_quant and m:
+        x2 = int8_fake_quantize_per_token_asym(x2)
+    reason = intx_linear_fits(layout, m, n, k, g)
+    if reason is not None:
+        raise ValueError(f"{name}: {reason}")
+    if bias is not None and (bias.dtype != torch.bfloat16 or tuple(bias.shape) != (n,)):
+        raise RuntimeError(f"{name}: bias must be bfloat16 [{n}], got {bias.dtype} {tuple(bias.shape)}")
+    out = torch.empty((m, n), dtype=torch.bfloat16, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_intx_linear(_ptr(x2), _ptr(w), _ptr(scale), _ptr(zero_point), _ptr(bias.contiguous() if bias is not None else None),
+                                             _ptr(out), m, n, k, g, layout, _stream()))
+    return out.view(*x.shape[:-1], n)
+
+
+__all__ += ["INTX_MAPPINGS", "intx_linear_fits", "intx_linear_route", "intx_linear_set_form", "intx_quantize", "int8_fake_quantize_per_token_asym",
+            "intx_pack", "intx_unpack", "intx_dequantize", "intx_linear"]

@@ -23,6 +23,7 @@ from .mx_training import (  # noqa: F401
     _to_mxfp8_then_scaled_mm,
     mx_mm,
 )
+from ..quantization.intx_tensor import IntxBitPackedTensor  # noqa: F401  (the device-packed sibling of IntxUnpackedToInt8Tensor)
 from .nf4_api import NF4WeightOnlyConfig, nf4_weight_only  # noqa: F401
 from .nvfp4_grouped import NVFP4ExpertWeights, nvfp4_grouped_mm  # noqa: F401
 from .nvfp4_grouped_training import _NVFP4GroupedMM, _to_nvfp4_rht_rs_then_scaled_grouped_mm  # noqa: F401
@@ -60,4 +61,5 @@ __all__ = ["Float8BlockwiseExpertWeights", "fp8_blockwise_grouped_mm", "NVFP4Ten
            "_NVFP4GroupedMM", "_to_nvfp4_rht_rs_then_scaled_grouped_mm",
            "NF4WeightOnlyConfig", "nf4_weight_only", "AWQConfig", "AWQObserver", "AWQObservedLinear",
            "SmoothQuantConfig", "SmoothQuantStep", "SmoothQuantObserver", "RunningAbsMaxSmoothQuantObserver", "SmoothQuantObservedLinear",
-           "AttentionBackend", "HadamardMode", "apply_low_precision_attention", "fp8_sdpa"]
+           "AttentionBackend", "HadamardMode", "apply_low_precision_attention", "fp8_sdpa",
+           "IntxBitPackedTensor"]

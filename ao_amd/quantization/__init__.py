@@ -13,15 +13,20 @@ from .config import (  # noqa: F401
     Int4PackingFormat,
     Int4WeightOnlyConfig,
     Int8DynamicActivationInt8WeightConfig,
+    Int8DynamicActivationIntxWeightConfig,
+    IntxChooseQParamsAlgorithm,
+    IntxPackingFormat,
+    IntxWeightOnlyConfig,
     Int8StaticActivationInt8WeightConfig,
     Int8WeightOnlyConfig,
     ModuleFqnToConfig,
 )
-from .granularity import PerBlock, PerGroup, PerRow, PerTensor  # noqa: F401
+from .granularity import PerAxis, PerBlock, PerGroup, PerRow, PerTensor  # noqa: F401
 from .quant_primitives import MappingType  # noqa: F401
 from .float8_tensor import Float8Tensor, QuantizeTensorToFloat8Kwargs  # noqa: F401
 from .int4_plain_tensor import Int4Tensor  # noqa: F401
 from .int4_tensor import Int4TilePackedTo4dTensor  # noqa: F401
 from .int8_tensor import Int8Tensor, QuantizeTensorToInt8Kwargs  # noqa: F401
+from .intx_tensor import IntxUnpackedToInt8Tensor  # noqa: F401
 from .nf4_tensor import LinearNF4, NF4Tensor, linear_nf4, to_nf4  # noqa: F401
 from .quant_api import quantize_  # noqa: F401

@@ -4,7 +4,7 @@ import enum
 from dataclasses import dataclass, field
 from typing import List, Optional, Union
 
-from .granularity import Granularity, PerBlock, PerGroup, PerRow, PerTensor
+from .granularity import Granularity, PerAxis, PerBlock, PerGroup, PerRow, PerTensor
 from .quant_primitives import MappingType
 
 
@@ -270,6 +270,87 @@ class Float8DynamicActivationInt4WeightConfig(AOBaseConfig):
 
     def __post_init__(self):
         self.int4_packing_format = Int4PackingFormat(self.int4_packing_format)
+
+
+class IntxPackingFormat(str, enum.Enum):
+    """reference intx_packing_format.py:17-50, plus BIT_PACKED: this backend's device layout (IntxBitPackedTensor, b / 8 of a byte a weight).
+    The OPAQUE_* formats are CPU kernels' layouts: they parse, and quantize_ refuses them."""
+    UNPACKED_TO_INT8 = "unpacked_to_int8"
+    OPAQUE_ATEN_KLEIDIAI = "opaque_aten_kleidiai"
+    OPAQUE_TORCHAO_AUTO = "opaque_torchao_auto"
+    OPAQUE_TORCHAO_KLEIDIAI = "opaque_torchao_kleidiai"
+    OPAQUE_TORCHAO_LOWBIT = "opaque_torchao_lowbit"
+    BIT_PACKED = "bit_packed"
+
+
+class IntxChooseQParamsAlgorithm(str, enum.Enum):
+    """reference intx_choose_qparams_algorithm.py:13-31.  HQQ_SCALE_ONLY parses and is refused."""
+    AFFINE = "affine"
+    HQQ_SCALE_ONLY = "hqq_scale_only"
+
+
+def _intx_dtypes():
+    import torch
+
+    return [getattr(torch, f"int{b}") for b in range(1, 9)]
+
+
+def _int8_default():
+    import torch
+
+    return torch.int8
+
+
+@dataclass
+class IntxWeightOnlyConfig(AOBaseConfig):
+    """int1 .. int8 weight-only, PerGroup or PerAxis(0) (reference quant_api.py:1365-1414: same fields, defaults and assertions).
+    intx_packing_format BIT_PACKED (this backend's) stores b bits a weight; UNPACKED_TO_INT8 is the reference's checkpoint format."""
+
+    weight_dtype: object = field(default_factory=_int8_default)
+    granularity: Granularity = PerAxis(0)
+    mapping_type: MappingType = MappingType.SYMMETRIC
+    scale_dtype: Optional[object] = None
+    intx_packing_format: IntxPackingFormat = IntxPackingFormat.UNPACKED_TO_INT8
+    intx_choose_qparams_algorithm: IntxChooseQParamsAlgorithm = IntxChooseQParamsAlgorithm.AFFINE
+    version: int = 2
+
+    def __post_init__(self):
+        assert self.weight_dtype in _intx_dtypes(), f"weight_dtype must be torch.intx, where 1 <= x <= 8, but got {self.weight_dtype}"
+        assert isinstance(self.granularity, (PerAxis, PerGroup)), f"granularity must be PerAxis or PerGroup, but got {self.granularity}"
+        if isinstance(self.granularity, PerAxis):
+            assert self.granularity.axis == 0, f"axis must be 0 with PerAxis, but got {self.granularity.axis}"
+        assert self.mapping_type in [MappingType.ASYMMETRIC, MappingType.SYMMETRIC, MappingType.SYMMETRIC_NO_CLIPPING_ERR], (
+            f"mapping_type must be MappingType.ASYMMETRIC, MappingType.SYMMETRIC, or MappingType.SYMMETRIC_NO_CLIPPING_ERR, but got {self.mapping_type}")
+        self.intx_packing_format = IntxPackingFormat(self.intx_packing_format)
+        self.intx_choose_qparams_algorithm = IntxChooseQParamsAlgorithm(self.intx_choose_qparams_algorithm)
+
+
+@dataclass
+class Int8DynamicActivationIntxWeightConfig(AOBaseConfig):
+    """int8 dynamic per-token asymmetric activations x int1 .. int8 weights, "8da4w" at int4 (reference quant_api.py:325-392: same fields,
+    defaults and assertions).  The activation is fake-quantized in bf16 and the product is the reference's: bf16 operands, fp32 sums."""
+
+    weight_dtype: object = field(default_factory=_int8_default)
+    weight_granularity: Granularity = PerGroup(32)
+    weight_mapping_type: MappingType = MappingType.SYMMETRIC
+    weight_scale_dtype: Optional[object] = None
+    act_mapping_type: MappingType = MappingType.ASYMMETRIC
+    intx_packing_format: IntxPackingFormat = IntxPackingFormat.UNPACKED_TO_INT8
+    intx_choose_qparams_algorithm: IntxChooseQParamsAlgorithm = IntxChooseQParamsAlgorithm.AFFINE
+    version: int = 2
+
+    def __post_init__(self):
+        assert self.weight_dtype in _intx_dtypes(), f"weight_dtype must be torch.intx, where 1 <= x <= 8, but got {self.weight_dtype}"
+        assert isinstance(self.weight_granularity, (PerAxis, PerGroup)), (
+            f"weight_granularity must be PerAxis or PerGroup, but got {self.weight_granularity}")
+        if isinstance(self.weight_granularity, PerAxis):
+            assert self.weight_granularity.axis == 0, f"axis must be 0, but got {self.weight_granularity.axis}"
+        assert self.weight_mapping_type in [MappingType.ASYMMETRIC, MappingType.SYMMETRIC, MappingType.SYMMETRIC_NO_CLIPPING_ERR], (
+            f"weight_mapping_type must be MappingType.ASYMMETRIC or MappingType.SYMMETRIC or MappingType.SYMMETRIC_NO_CLIPPING_ERR, but got {self.weight_mapping_type}")
+        assert self.act_mapping_type in [MappingType.ASYMMETRIC, MappingType.SYMMETRIC], (
+            f"act_mapping_type must be MappingType.ASYMMETRIC or MappingType.SYMMETRIC, but got {self.act_mapping_type}")
+        self.intx_packing_format = IntxPackingFormat(self.intx_packing_format)
+        self.intx_choose_qparams_algorithm = IntxChooseQParamsAlgorithm(self.intx_choose_qparams_algorithm)
 
 
 @dataclass

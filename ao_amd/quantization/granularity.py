@@ -23,6 +23,13 @@ class PerGroup(Granularity):
     group_size: int = 128
 
 
+@dataclass(frozen=True)
+class PerAxis(Granularity):
+    """One scale per index of `axis`, every other dimension reduced (reference granularity.py:38-51).  The Intx configs take PerAxis(0): a
+    scale per output row."""
+    axis: int
+
+
 @dataclass(frozen=True, eq=False)
 class PerBlock(Granularity):
     """Multidimensional blocks (reference granularity.py:116-142): block_size [X, Y] on a tensor [A, B] gives scales [A // X, B // Y];
@@ -67,4 +74,4 @@ def get_block_size(shape, granularity):
 import torch as _torch  # noqa: E402
 
 # granularities ride along in the quantized tensors' attributes: allow them under torch.load(weights_only=True)
-_torch.serialization.add_safe_globals([Granularity, PerTensor, PerRow, PerGroup, PerBlock])
+_torch.serialization.add_safe_globals([Granularity, PerTensor, PerRow, PerGroup, PerAxis, PerBlock])

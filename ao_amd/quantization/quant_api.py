@@ -19,6 +19,10 @@ from .config import (
     Int4PackingFormat,
     Int4WeightOnlyConfig,
     Int8DynamicActivationInt8WeightConfig,
+    Int8DynamicActivationIntxWeightConfig,
+    IntxChooseQParamsAlgorithm,
+    IntxPackingFormat,
+    IntxWeightOnlyConfig,
     FqnToConfig,
     Int8StaticActivationInt8WeightConfig,
     Int8WeightOnlyConfig,
@@ -356,4 +360,70 @@ def _float8_weight_only_transform(module, config, *, parameter_name="weight"):
     assert config.version == 2, f"Unexpected version: {config.version}"
     _refuse_per_group(config)
     new_weight = Float8Tensor.from_hp(getattr(module, parameter_name), float8_dtype=config.weight_dtype, granularity=config.granularity)
+    return _set_weight_only(module, parameter_name, new_weight)
+
+
+def _intx_quantize_tensor(what, weight, weight_dtype, granularity, mapping_type, scale_dtype, packing_format, algorithm, activation_quantization,
+                          custom_scale, custom_zero_point):
+    """reference quant_api.py:394-465 and :1417-1476, with this backend's refusals made by name before anything is launched."""
+    import torch
+
+    from .granularity import PerAxis, PerGroup
+    from .intx_tensor import IntxBitPackedTensor, IntxUnpackedToInt8Tensor
+
+    if weight.dim() == 4:
+        raise NotImplementedError(f"{what} on MI355X: 4-D conv weights are not built (linear weights only)")
+    assert weight.dim() == 2, f"{what} only works for 2-d Tensor, got: {weight.dim()}"
+    if isinstance(granularity, PerGroup):
+        group_size = granularity.group_size
+    elif isinstance(granularity, PerAxis):
+        assert granularity.axis == 0, f"axis must be 0 with PerAxis, but got {granularity.axis}"
+        group_size = weight.shape[-1]
+    else:
+        raise ValueError(f"granularity must be PerGroup or PerAxis, got {granularity}")
+    if packing_format not in (IntxPackingFormat.UNPACKED_TO_INT8, IntxPackingFormat.BIT_PACKED):
+        raise NotImplementedError(f"{what} on MI355X: intx_packing_format {packing_format.value} is a CPU kernel's opaque layout and is not built; "
+                                  "use unpacked_to_int8 or bit_packed")
+    if scale_dtype is not None and scale_dtype != torch.bfloat16:
+        raise NotImplementedError(f"{what} on MI355X: a scale dtype of {scale_dtype} is not built; leave it None or use torch.bfloat16")
+    if custom_zero_point is not None and custom_zero_point.dtype == torch.int32:
+        custom_zero_point = custom_zero_point.to(torch.int8)
+    if custom_scale is not None or custom_zero_point is not None:
+        algorithm = None  # the reference's callers (QAT convert) hand the qparams in place of an algorithm
+    new_weight = IntxUnpackedToInt8Tensor.from_hp(weight, (1, group_size), weight_dtype, mapping_type=mapping_type,
+                                                  activation_quantization=activation_quantization, intx_choose_qparams_algorithm=algorithm,
+                                                  custom_scale=custom_scale, custom_zero_point=custom_zero_point)
+    if packing_format == IntxPackingFormat.BIT_PACKED:
+        new_weight = IntxBitPackedTensor.from_intx_unpacked_to_int8_tensor(new_weight)
+    return new_weight
+
+
+@register_quantize_module_handler(IntxWeightOnlyConfig)
+def _intx_weight_only_transform(module, config, *, parameter_name="weight", custom_scale=None, custom_zero_point=None):
+    """reference quant_api.py:1479-1512"""
+    assert hasattr(module, parameter_name), (
+        f"applying intx weight only quant requires module to have {parameter_name} attribute but {module} does not have one")
+    assert config.version == 2
+    if isinstance(module, nn.Embedding):
+        raise NotImplementedError("IntxWeightOnlyConfig on MI355X: embedding weights (F.embedding) are not built (linear weights only)")
+    new_weight = _intx_quantize_tensor("IntxWeightOnlyConfig", getattr(module, parameter_name), config.weight_dtype, config.granularity,
+                                       config.mapping_type, config.scale_dtype, config.intx_packing_format, config.intx_choose_qparams_algorithm,
+                                       None, custom_scale, custom_zero_point)
+    return _set_weight_only(module, parameter_name, new_weight)
+
+
+@register_quantize_module_handler(Int8DynamicActivationIntxWeightConfig)
+def _int8_dynamic_activation_intx_weight_transform(module, config, *, parameter_name="weight", custom_scale=None, custom_zero_point=None):
+    """reference quant_api.py:468-499"""
+    from .quant_primitives import MappingType
+
+    assert hasattr(module, parameter_name), (
+        f"applying int8 dynamic activation intx weight quant requires module to have {parameter_name} attribute but {module} does not have one")
+    assert config.version == 2
+    if config.act_mapping_type != MappingType.ASYMMETRIC:
+        raise NotImplementedError("Int8DynamicActivationIntxWeightConfig on MI355X: act_mapping_type=SYMMETRIC is not built (the reference asserts "
+                                  "ASYMMETRIC here too)")
+    new_weight = _intx_quantize_tensor("Int8DynamicActivationIntxWeightConfig", getattr(module, parameter_name), config.weight_dtype,
+                                       config.weight_granularity, config.weight_mapping_type, config.weight_scale_dtype, config.intx_packing_format,
+                                       config.intx_choose_qparams_algorithm, "int8_asym_per_token", custom_scale, custom_zero_point)
     return _set_weight_only(module, parameter_name, new_weight)

@@ -749,4 +749,18 @@ def _(x, packed, tensor_scale, bias):
 _lib_autograd.impl("bitnet_linear", torch.library.fallthrough_kernel)
 
 
+# ---- Intx weights (ops.py "Intx"): the activation fake quantization (where asked for) and the b-bit linear as one opaque node --
+_lib_def.define("intx_linear(Tensor x, Tensor codes, Tensor scale, Tensor zero_point, int bits, Tensor? bias, bool act_quant) -> Tensor")
+_lib_impl.impl("intx_linear", lambda x, codes, scale, zero_point, bits, bias, act_quant: ops.intx_linear(x, codes, scale, zero_point, bits, bias,
+                                                                                                         act_quant))
+
+
+@torch.library.register_fake("ao_mi355::intx_linear")
+def _(x, codes, scale, zero_point, bits, bias, act_quant):
+    return x.new_empty((*x.shape[:-1], codes.shape[0]))
+
+
+_lib_autograd.impl("intx_linear", torch.library.fallthrough_kernel)
+
+
 load_ops_library()

@@ -1279,6 +1279,39 @@ int ao_bitnet_mm_fits(int64_t M, int64_t N, int64_t K);
 int ao_bitnet_mm(const int8_t* a, const uint8_t* w, const uint16_t* row_scale, const uint16_t* tensor_scale, const uint16_t* bias, uint16_t* out,
                  int64_t M, int64_t N, int64_t K, int form, void* stream);
 
+/* ---- Intx weights, int1 .. int8 (torchao/quantization/quantize_/workflows/intx; csrc/intx_kernels.hip states the arithmetic and the layout) -----
+ * Every entry checks its shapes, then its pointers, before any launch.  bf16 tensors are uint16_t bit patterns; a NaN is stored as 0x7FC0.
+ * ao_intx_quantize (choose_qparams_affine + quantize_affine in the reference's bf16 arithmetic, one launch): w bf16 [N][K] in groups of
+ *   group_size along K (a multiple of 8 dividing K) -> q int8 [N][K] in [-2^(bits-1), 2^(bits-1) - 1], scale bf16 and zero_point int8
+ *   [N][K / group_size].  mapping: AO_INTX_MAP_*.  qparams_given != 0: scale and zero_point are INPUTS (from_hp's custom branch) and only the
+ *   codes are written.
+ * ao_int8_fake_quantize_per_token_asym (_apply_int8_act_asym_per_token_quant_dequant): x bf16 [M][K], K % 8 == 0 -> out bf16 [M][K], the
+ *   asymmetric int8 quantization of each row, dequantized.
+ * ao_intx_pack / ao_intx_unpack: q int8 [N][K], K % 32 == 0 <-> packed [N][K / 32][bits] dwords (bits = 8: the bytes themselves).
+ * ao_intx_dequantize: dequantize_affine from a layout of `bits` bits a code (8: the unpacked qdata of any target dtype): out bf16 [N][K] =
+ *   bf16((q - zero_point) * scale), group_size a multiple of 32 dividing K.
+ * ao_intx_linear: out bf16 [M][N] = bf16(sum_k x[m][k] w[n][k] + bias[n]), x bf16 [M][K], w as ao_intx_dequantize reads it, fp32 accumulation,
+ *   bias bf16 [N] or null.  Two forms behind one route (ao_intx_linear_route: the seven fields of the two-form routes): the streaming form up to
+ *   AO_INTX_LINEAR_STREAM_MAX_M rows, the LDS-tiled form beyond; ao_intx_linear_set_form forces one on the calling thread (0: the route).
+ * ao_intx_linear_fits (host logic, no launch): 1 where ao_intx_linear serves the shape, else 0 with the reason in ao_last_error(); the linear
+ *   refuses the same shapes with AO_ERR_INVALID_ARGUMENT. */
+#define AO_INTX_MAP_SYMMETRIC 0
+#define AO_INTX_MAP_SYMMETRIC_NO_CLIPPING_ERR 1
+#define AO_INTX_MAP_ASYMMETRIC 2
+#define AO_INTX_LINEAR_STREAM_MAX_M 64
+int ao_intx_quantize(const uint16_t* w, int8_t* q, uint16_t* scale, int8_t* zero_point, int64_t N, int64_t K, int64_t group_size, int bits,
+                     int mapping, int qparams_given, void* stream);
+int ao_int8_fake_quantize_per_token_asym(const uint16_t* x, uint16_t* out, int64_t M, int64_t K, void* stream);
+int ao_intx_pack(const int8_t* q, uint32_t* packed, int64_t N, int64_t K, int bits, void* stream);
+int ao_intx_unpack(const uint32_t* packed, int8_t* q, int64_t N, int64_t K, int bits, void* stream);
+int ao_intx_dequantize(const uint32_t* packed, const uint16_t* scale, const int8_t* zero_point, uint16_t* out, int64_t N, int64_t K,
+                       int64_t group_size, int bits, void* stream);
+int ao_intx_linear_fits(int bits, int64_t M, int64_t N, int64_t K, int64_t group_size);
+int ao_intx_linear_route(int bits, int64_t M, int64_t N, int64_t K, int64_t group_size, int32_t* out, int cap);
+int ao_intx_linear_set_form(int form);
+int ao_intx_linear(const uint16_t* x, const uint32_t* w, const uint16_t* scale, const int8_t* zero_point, const uint16_t* bias, uint16_t* out,
+                   int64_t M, int64_t N, int64_t K, int64_t group_size, int bits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
