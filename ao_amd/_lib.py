@@ -212,6 +212,16 @@ _SIGNATURES = {
     "ao_intx_linear_route": [_INT, _I64, _I64, _I64, _I64, _P, _INT],
     "ao_intx_linear_set_form": [_INT],
     "ao_intx_linear": [_P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _INT, _P],
+    "ao_codebook_assign": [_P, _P, _P, _I64, _INT, _INT, _P],
+    "ao_codebook_lloyd_workspace_bytes": [_I64, _INT, _INT],
+    "ao_codebook_lloyd_step": [_P, _P, _P, _P, _P, _P, _I64, _I64, _INT, _INT, _P],
+    "ao_codebook_pack_u4": [_P, _P, _I64, _P],
+    "ao_codebook_dequantize": [_P, _P, _P, _P, _I64, _I64, _INT, _INT, _I64, _P],
+    "ao_codebook_linear_fits": [_I64, _I64, _I64, _INT, _INT, _I64],
+    "ao_codebook_linear_route": [_I64, _I64, _I64, _INT, _INT, _I64, _P, _INT],
+    "ao_codebook_linear_kernel_name": [_I64, _I64, _I64, _INT, _INT, _I64],
+    "ao_codebook_linear_set_form": [_INT],
+    "ao_codebook_linear": [_P, _P, _P, _P, _P, _I64, _I64, _I64, _INT, _INT, _I64, _P],
 }
 
 
@@ -264,6 +274,8 @@ def lib():
             l.ao_moe_a2a_flag_bytes.restype = _I64
             l.ao_moe_a2a_state_bytes.restype = _I64
         l.ao_int4_hqq_workspace_bytes.restype = _I64
+        if hasattr(l, "ao_codebook_lloyd_workspace_bytes"):
+            l.ao_codebook_lloyd_workspace_bytes.restype = _I64
         _lib = l
     return _lib
 

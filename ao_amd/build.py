@@ -38,12 +38,18 @@ FLAGS = [
 # attention_kernels.hip likewise: its fp32 work is the softmax's single multiplies, subtractions and v_exp_f32 between two MFMA products.
 # bitnet_kernels.hip likewise: its fp32 work is the casts' chain of single IEEE operations and a two-multiply epilogue.
 # intx_kernels.hip likewise: the affine cast's chain of single operations and the decode's add and multiply per weight.
+# codebook_kernels.hip likewise: the score is quant_math.h's chain of single v_fma_f32 in index order, the decode one multiply per weight.
+# With packed operations allowed the compiler pairs the rows a lane holds and codebook_assign_kernel grows: 256 VGPRs against 212 at d = 8,
+# k = 16 and 204 against 124 at d = 4, k = 16 (the 16-entry table is kept in registers across tiles either way), 106 against 68 for the Lloyd
+# step at d = 8, k = 256 (4 waves a SIMD against 7).  The resource report of this source is the check, as above; the two builds were not
+# timed against each other.
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SOURCE_FLAGS = {
     "nvfp4_grouped_train_kernels.hip": _NO_PACKED_FP32,
     "attention_kernels.hip": _NO_PACKED_FP32,
     "bitnet_kernels.hip": _NO_PACKED_FP32,
     "intx_kernels.hip": _NO_PACKED_FP32,
+    "codebook_kernels.hip": _NO_PACKED_FP32,
 }
 
 

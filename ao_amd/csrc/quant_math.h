@@ -733,6 +733,33 @@ __device__ __forceinline__ uint16_t bitnet_out(int acc, float rs, float ts, bool
   return f32_to_bf16_bits(v);
 }
 
+// ---- Codebook (k-means) weights (codebook_kernels.hip): torchao/prototype/quantization/codebook, the contract -----------------------------
+//   weight   W bf16 [N][K]; block_size (1, d), d in {1, 2, 4, 8}; k = 256 entries (torch.uint8 codes) or 16 (torch.uint4); one scale per
+//            run of sb elements of a row, d | sb | K
+//   fields   codebook bf16 [k][1][d];  scales bf16 [N][K / sb][1];  codes uint8 [N][K / d] (k = 256), or two codes a byte, uint8
+//            [N][K / (2 d)] with block 2 i in the LOW nibble (k = 16; K / d even) -- in place of the reference's UintxTensor
+//   decode   w[n][c] = bf16(f32(codebook[code[n][c / d]][c % d]) * f32(scales[n][c / sb])): the fp32 product of two bf16 values is exact,
+//            so ONE rounding (dequantize_codebook, codebook_ops.py:98-149, on the bf16 fields from_float leaves)
+//   scales   fp32, in tensor ops (choose_qparams_codebook :192-204): d = 1 the SIGNED max of the scale block, else its L2 norm, clamped at 1e-9
+//   data     f32(W) / scales as rows of d; k-means and the codes run on the fp32 table and scales, rounded to bf16 only afterwards
+//   score    of entry j for a row x (quantize_codebook :81-90, fit_kmeans :294-301: addmm(beta = -0.5).argmax(1), with the order fixed):
+//            q = 0, q = fma(c_ji, c_ji, q) for i = 0 .. d - 1;  h_j = -0.5 q;  s = h_j, s = fma(x_i, c_ji, s) for i = 0 .. d - 1
+//   code     the LOWEST index among the maximal scores; a NaN score never wins; 0 if every score is NaN
+__device__ __forceinline__ float codebook_half_norm(const float* c, int d) {
+  float q = 0.f;
+  for (int i = 0; i < d; ++i) q = __builtin_fmaf(c[i], c[i], q);
+  return -0.5f * q;
+}
+template <int D>
+__device__ __forceinline__ float codebook_score(const float (&x)[D], const float (&c)[D], float h) {
+  float s = h;
+#pragma unroll
+  for (int i = 0; i < D; ++i) s = __builtin_fmaf(x[i], c[i], s);
+  return s;
+}
+// two bf16 table values (a dword of the table) times the scale -> two bf16 weights
+__device__ __forceinline__ uint32_t codebook_decode2(uint32_t pair, float s) { return pack_bf16x2(bf16_lo_to_f32(pair) * s, bf16_hi_to_f32(pair) * s); }
+
 // ---- a tensor as a flat run of 16-byte vectors of 8 bf16, one per lane; a group is LANES = g / 8 adjacent lanes (K % g == 0 keeps groups
 // whole inside a row, and LANES divides the wave), so every group reduction is a butterfly over lanes: no LDS, no atomics -----------------
 __device__ __forceinline__ void unpack_bf16x8(const u32x4& v, float (&f)[8]) {

@@ -3559,3 +3559,138 @@ def intx_linear(x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor, zero_poin
 
 __all__ += ["INTX_MAPPINGS", "intx_linear_fits", "intx_linear_route", "intx_linear_set_form", "intx_quantize", "int8_fake_quantize_per_token_asym",
             "intx_pack", "intx_unpack", "intx_dequantize", "intx_linear"]
+
+
+# ---- Codebook (k-means) weights: the Lloyd step, the casts and the linear (include/ao_mi355.h "Codebook") --------------------
+CODEBOOK_KERNELS = {0: "not fused", 1: "codebook_stream_kernel"}
+CODEBOOK_BLOCK_WIDTHS = (1, 2, 4, 8)
+CODEBOOK_SIZES = (16, 256)  # torch.uint4 (two codes a byte), torch.uint8
+
+
+def _codebook_rows(name, x, table):
+    """The fp32 data [n, d] and table [k, d] of the assignment kernels."""
+    for what, t in (("x", x), ("table", table)):
+        if t.dtype != torch.float32 or t.dim() != 2:
+            raise RuntimeError(f"{name}: {what} must be a 2-D float32 tensor, got {t.dtype} {tuple(t.shape)}")
+    (n, d), (k, dt) = x.shape, table.shape
+    if d not in CODEBOOK_BLOCK_WIDTHS or dt != d:
+        raise ValueError(f"{name}: x [n, d] and table [k, d] must share d in {CODEBOOK_BLOCK_WIDTHS}, got d={d} and {dt}")
+    if k not in CODEBOOK_SIZES:
+        raise ValueError(f"{name}: the table must hold 16 (uint4 codes) or 256 (uint8 codes) entries, got {k}")
+    dev = _require_gpu(name, x, table)
+    return x.contiguous(), table.contiguous(), n, d, k, dev
+
+
+def codebook_assign(x: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
+    """The chunk loop of quantize_codebook (codebook_ops.py:74-90: addmm(beta=-0.5) + argmax per chunk) in one launch, no score matrix:
+    x fp32 [n, d], table fp32 [k, d] -> codes uint8 [n], the lowest index of the highest score (csrc/quant_math.h "Codebook")."""
+    x, table, n, d, k, dev = _codebook_rows("codebook_assign", x, table)
+    codes = torch.empty((n,), dtype=torch.uint8, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_codebook_assign(_ptr(x), _ptr(table), _ptr(codes), n, d, k, _stream()))
+    return codes
+
+
+def codebook_lloyd_step(x: torch.Tensor, table: torch.Tensor, return_codes: bool = False):
+    """One iteration of fit_kmeans (codebook_ops.py:290-316) in two launches: the assignment, per-workgroup sums in LDS, and the means.
+    -> (new table fp32 [k, d]: an entry without a member keeps its bits, counts int32 [k][, codes uint8 [n]])."""
+    x, table, n, d, k, dev = _codebook_rows("codebook_lloyd_step", x, table)
+    new = torch.empty_like(table)
+    counts = torch.empty((k,), dtype=torch.int32, device=dev)
+    codes = torch.empty((n,), dtype=torch.uint8, device=dev) if return_codes else None
+    nbytes = _lib.lib().ao_codebook_lloyd_workspace_bytes(n, d, k)
+    ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.int32, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_codebook_lloyd_step(_ptr(x), _ptr(table), _ptr(new), _ptr(counts), _ptr(codes), _ptr(ws), ws.numel() * 4, n, d, k,
+                                                     _stream()))
+    return (new, counts, codes) if return_codes else (new, counts)
+
+
+def codebook_pack_u4(codes: torch.Tensor) -> torch.Tensor:
+    """uint8 codes below 16, an even count a row -> two a byte, the even one in the low nibble (pack_uint4 of prototype/mx): [..., c / 2]."""
+    name = "codebook_pack_u4"
+    if codes.dtype != torch.uint8 or codes.dim() < 1 or codes.shape[-1] % 2 != 0:
+        raise ValueError(f"{name}: expected uint8 codes with an even last dimension, got {codes.dtype} {tuple(codes.shape)}")
+    dev = _require_gpu(name, codes)
+    codes = codes.contiguous()
+    out = torch.empty((*codes.shape[:-1], codes.shape[-1] // 2), dtype=torch.uint8, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_codebook_pack_u4(_ptr(codes), _ptr(out), codes.numel(), _stream()))
+    return out
+
+
+def _codebook_fields(name, codes, codebook, scales):
+    """The three fields of a codebook weight (csrc/quant_math.h "Codebook") -> contiguous fields, N, K, d, k, sb."""
+    if codebook.dtype != torch.bfloat16 or codebook.dim() != 3 or codebook.shape[1] != 1:
+        raise RuntimeError(f"{name}: the codebook must be bfloat16 [k, 1, d], got {codebook.dtype} {tuple(codebook.shape)}")
+    k, _, d = codebook.shape
+    if d not in CODEBOOK_BLOCK_WIDTHS or k not in CODEBOOK_SIZES:
+        raise ValueError(f"{name}: the codebook [k, 1, d] needs k in {CODEBOOK_SIZES} and d in {CODEBOOK_BLOCK_WIDTHS}, got k={k} d={d}")
+    if codes.dtype != torch.uint8 or codes.dim() != 2:
+        raise RuntimeError(f"{name}: the codes must be 2-D uint8 ([N, K / d], or [N, K / (2 d)] for 16 entries), got {codes.dtype} {tuple(codes.shape)}")
+    n = codes.shape[0]
+    kk = codes.shape[1] * d * (2 if k == 16 else 1)
+    if scales.dtype != torch.bfloat16 or scales.dim() != 3 or scales.shape[0] != n or scales.shape[2] != 1 or scales.shape[1] < 1 \
+            or kk % scales.shape[1] != 0:
+        raise RuntimeError(f"{name}: the scales must be bfloat16 [N, K / sb, 1] with N={n} and K={kk}, got {scales.dtype} {tuple(scales.shape)}")
+    sb = kk // scales.shape[1]
+    if sb % d != 0:
+        raise ValueError(f"{name}: scale_block_size={sb} must be a multiple of the block width d={d}")
+    return codes.contiguous(), codebook.contiguous(), scales.contiguous(), n, kk, d, k, sb
+
+
+def codebook_dequantize(codes: torch.Tensor, codebook: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """dequantize_codebook (codebook_ops.py:98-149) in one launch, its bits: -> bf16 [N, K] = bf16(codebook[code] * scale)."""
+    name = "codebook_dequantize"
+    codes, codebook, scales, n, k_, d, k, sb = _codebook_fields(name, codes, codebook, scales)
+    dev = _require_gpu(name, codes, codebook, scales)
+    w = torch.empty((n, k_), dtype=torch.bfloat16, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_codebook_dequantize(_ptr(codes), _ptr(codebook), _ptr(scales), _ptr(w), n, k_, d, k, sb, _stream()))
+    return w
+
+
+def codebook_linear_fits(m: int, n: int, k: int, d: int, entries: int, sb: int):
+    """None where the fused linear takes the shape, else the reason (host logic, ao_codebook_linear_fits)."""
+    return None if _lib.lib().ao_codebook_linear_fits(m, n, k, d, entries, sb) == 1 else _lib.last_error()
+
+
+def codebook_linear_route(m: int, n: int, k: int, d: int, entries: int, sb: int) -> dict:
+    """The route codebook_linear takes (host logic only): kernel "codebook_stream_kernel", or "not fused" -- dequantize, then multiply --
+    above the seam and for shapes the kernel does not take (K or sb off the 32 grid)."""
+    return _two_form_route("ao_codebook_linear_route", CODEBOOK_KERNELS, m, n, k, d, entries, sb)
+
+
+def codebook_linear_kernel_name(m: int, n: int, k: int, d: int, entries: int, sb: int) -> str:
+    return _two_form_kernel_name("ao_codebook_linear_kernel_name", m, n, k, d, entries, sb)
+
+
+def codebook_linear_set_form(form: int) -> None:
+    """Measurement only: 0 the product route, 1 the stream kernel at any M (calling thread).  There is no tiled form."""
+    _two_form_set_form("ao_codebook_linear_set_form", form)
+
+
+def codebook_linear(x2: torch.Tensor, codes: torch.Tensor, codebook: torch.Tensor, scales: torch.Tensor, out=None) -> torch.Tensor:
+    """F.linear(x, dequantize_codebook(...)) on a 2-D bf16 activation: bf16(x . w^T), fp32 accumulation, no bias.  By the route: one launch
+    that streams the codes once and gathers MFMA operands from the table in LDS, or codebook_dequantize + F.linear."""
+    name = "codebook_linear"
+    if x2.dim() != 2 or x2.dtype != torch.bfloat16:
+        raise RuntimeError(f"{name}: x must be a 2-D bfloat16 tensor, got {tuple(x2.shape)} {x2.dtype}")
+    codes, codebook, scales, n, k_, d, k, sb = _codebook_fields(name, codes, codebook, scales)
+    m, kx = x2.shape
+    if kx != k_:
+        raise RuntimeError(f"{name}: K mismatch {kx} vs {k_}")
+    dev = _require_gpu(name, x2, codes, codebook, scales)
+    x2 = x2.contiguous()
+    if codebook_linear_route(m, n, k_, d, k, sb)["kernel"] != CODEBOOK_KERNELS[1]:
+        y = torch.nn.functional.linear(x2, codebook_dequantize(codes, codebook, scales))
+        return y if out is None else _bf16_out(name, out, m, n, dev).copy_(y)
+    y = _bf16_out(name, out, m, n, dev)
+    if m > 0:
+        with _on(dev):
+            _lib.check(_lib.lib().ao_codebook_linear(_ptr(x2), _ptr(codes), _ptr(codebook), _ptr(scales), _ptr(y), m, n, k_, d, k, sb, _stream()))
+    return y
+
+
+__all__ += ["CODEBOOK_KERNELS", "codebook_assign", "codebook_lloyd_step", "codebook_pack_u4", "codebook_dequantize", "codebook_linear",
+            "codebook_linear_fits", "codebook_linear_route", "codebook_linear_kernel_name", "codebook_linear_set_form"]

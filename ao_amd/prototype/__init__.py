@@ -24,6 +24,14 @@ from .mx_training import (  # noqa: F401
     mx_mm,
 )
 from ..quantization.intx_tensor import IntxBitPackedTensor  # noqa: F401  (the device-packed sibling of IntxUnpackedToInt8Tensor)
+from .codebook import (  # noqa: F401
+    CodebookQuantizedTensor,
+    CodebookWeightOnlyConfig,
+    choose_qparams_codebook,
+    codebook_weight_only,
+    dequantize_codebook,
+    quantize_codebook,
+)
 from .nf4_api import NF4WeightOnlyConfig, nf4_weight_only  # noqa: F401
 from .nvfp4_grouped import NVFP4ExpertWeights, nvfp4_grouped_mm  # noqa: F401
 from .nvfp4_grouped_training import _NVFP4GroupedMM, _to_nvfp4_rht_rs_then_scaled_grouped_mm  # noqa: F401
@@ -62,4 +70,6 @@ __all__ = ["Float8BlockwiseExpertWeights", "fp8_blockwise_grouped_mm", "NVFP4Ten
            "NF4WeightOnlyConfig", "nf4_weight_only", "AWQConfig", "AWQObserver", "AWQObservedLinear",
            "SmoothQuantConfig", "SmoothQuantStep", "SmoothQuantObserver", "RunningAbsMaxSmoothQuantObserver", "SmoothQuantObservedLinear",
            "AttentionBackend", "HadamardMode", "apply_low_precision_attention", "fp8_sdpa",
-           "IntxBitPackedTensor"]
+           "IntxBitPackedTensor",
+           "CodebookWeightOnlyConfig", "codebook_weight_only", "CodebookQuantizedTensor", "choose_qparams_codebook", "quantize_codebook",
+           "dequantize_codebook"]

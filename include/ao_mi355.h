@@ -1312,6 +1312,40 @@ int ao_intx_linear_set_form(int form);
 int ao_intx_linear(const uint16_t* x, const uint32_t* w, const uint16_t* scale, const int8_t* zero_point, const uint16_t* bias, uint16_t* out,
                    int64_t M, int64_t N, int64_t K, int64_t group_size, int bits, void* stream);
 
+/* ---- Codebook (k-means) weights: torchao/prototype/quantization/codebook (codebook_kernels.hip) ---------------------------
+ * The format and the arithmetic are stated once, in csrc/quant_math.h ("Codebook"): block_size (1, d), d in {1, 2, 4, 8}; k = 256 entries
+ * with uint8 codes [N][K / d], or k = 16 with two codes a byte, uint8 [N][K / (2 d)], block 2 i in the low nibble; codebook bf16 [k][d];
+ * scales bf16 [N][K / sb], d | sb | K.  Every entry checks its shapes, then its pointers, before any launch; no allocation, no
+ * synchronisation: capturable in a graph.
+ * ao_codebook_assign (the chunk loop of quantize_codebook, codebook_ops.py:74-90): x fp32 [n][d], table fp32 [k][d] -> codes uint8 [n],
+ *   unpacked: the lowest index of the highest score; no score matrix is written.
+ * ao_codebook_lloyd_step (one iteration of fit_kmeans :290-316): the same assignment, then new_table fp32 [k][d] = the mean of each
+ *   entry's members (an entry without one keeps its old bits), counts int32 [k], and the codes where `codes` is not null.  The workspace
+ *   holds one partial table a workgroup: ao_codebook_lloyd_workspace_bytes(n, d, k) device bytes (-1 for a bad format), 4-byte aligned.
+ * ao_codebook_pack_u4: codes uint8 [n] (values below 16), n even -> packed uint8 [n / 2].
+ * ao_codebook_dequantize (dequantize_codebook :98-149): the fields -> out bf16 [N][K], 16-byte aligned.
+ * ao_codebook_linear: out bf16 [M][N] = bf16(sum_k x[m][k] w[n][k]), x bf16 [M][K], w the bits of ao_codebook_dequantize, fp32
+ *   accumulation, no bias; the weight-streaming form only, for K % 32 == 0, sb % 32 == 0, K <= 2^20 and operands below 2^31 elements
+ *   (ao_codebook_linear_fits: 1, or 0 with the reason in ao_last_error()).  A shape whose route is "not fused" is an error here.
+ * ao_codebook_linear_route: out[cap >= 7] = kernel (1 codebook_stream_kernel; 0 not fused -- more than AO_CODEBOOK_LINEAR_STREAM_MAX_M
+ *   rows (AO_CODEBOOK_LINEAR_STREAM_MAX_M_NARROW for d <= 2), or a shape the linear does not take: ao_codebook_dequantize, then a bf16 GEMM), waves, m-tiles, tile rows, tile columns, grid x,
+ *   grid y.  ao_codebook_linear_set_form (measurement only): 1 forces the stream kernel at any M for the calling thread, 0 the route. */
+#define AO_CODEBOOK_LINEAR_STREAM_MAX_M 64
+#define AO_CODEBOOK_LINEAR_STREAM_MAX_M_NARROW 48
+int ao_codebook_assign(const float* x, const float* table, uint8_t* codes, int64_t n, int d, int k, void* stream);
+int64_t ao_codebook_lloyd_workspace_bytes(int64_t n, int d, int k);
+int ao_codebook_lloyd_step(const float* x, const float* table, float* new_table, int32_t* counts, uint8_t* codes, void* workspace,
+                           int64_t workspace_bytes, int64_t n, int d, int k, void* stream);
+int ao_codebook_pack_u4(const uint8_t* codes, uint8_t* packed, int64_t n, void* stream);
+int ao_codebook_dequantize(const uint8_t* codes, const uint16_t* codebook, const uint16_t* scales, uint16_t* out, int64_t N, int64_t K, int d,
+                           int k, int64_t sb, void* stream);
+int ao_codebook_linear_fits(int64_t M, int64_t N, int64_t K, int d, int k, int64_t sb);
+int ao_codebook_linear_route(int64_t M, int64_t N, int64_t K, int d, int k, int64_t sb, int32_t* out, int cap);
+const char* ao_codebook_linear_kernel_name(int64_t M, int64_t N, int64_t K, int d, int k, int64_t sb);
+int ao_codebook_linear_set_form(int form);
+int ao_codebook_linear(const uint16_t* x, const uint8_t* codes, const uint16_t* codebook, const uint16_t* scales, uint16_t* out, int64_t M,
+                       int64_t N, int64_t K, int d, int k, int64_t sb, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
