@@ -222,6 +222,14 @@ _SIGNATURES = {
     "ao_codebook_linear_kernel_name": [_I64, _I64, _I64, _INT, _INT, _I64],
     "ao_codebook_linear_set_form": [_INT],
     "ao_codebook_linear": [_P, _P, _P, _P, _P, _I64, _I64, _I64, _INT, _INT, _I64, _P],
+    "ao_da8w4_quantize_weight": [_P, _P, _P, _P, _P, _I64, _I64, _I64, _P],
+    "ao_da8w4_dequantize": [_P, _P, _P, _I64, _I64, _I64, _P],
+    "ao_da8w4_quantize_act": [_P, _P, _P, _P, _P, _I64, _I64, _I64, _INT, _P],
+    "ao_da8w4_linear_fits": [_I64, _I64, _I64, _I64],
+    "ao_da8w4_linear_route": [_I64, _I64, _I64, _I64, _P, _INT],
+    "ao_da8w4_linear_kernel_name": [_I64, _I64, _I64, _I64],
+    "ao_da8w4_linear_set_form": [_INT],
+    "ao_da8w4_linear": [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P],
 }
 
 

@@ -43,6 +43,7 @@ FLAGS = [
 # k = 16 and 204 against 124 at d = 4, k = 16 (the 16-entry table is kept in registers across tiles either way), 106 against 68 for the Lloyd
 # step at d = 8, k = 256 (4 waves a SIMD against 7).  The resource report of this source is the check, as above; the two builds were not
 # timed against each other.
+# da8w4_kernels.hip likewise: the casts' chain of single operations and one v_fma_f32 a register at a group boundary.
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SOURCE_FLAGS = {
     "nvfp4_grouped_train_kernels.hip": _NO_PACKED_FP32,
@@ -50,6 +51,7 @@ SOURCE_FLAGS = {
     "bitnet_kernels.hip": _NO_PACKED_FP32,
     "intx_kernels.hip": _NO_PACKED_FP32,
     "codebook_kernels.hip": _NO_PACKED_FP32,
+    "da8w4_kernels.hip": _NO_PACKED_FP32,
 }
 
 

@@ -733,6 +733,13 @@ __device__ __forceinline__ uint16_t bitnet_out(int acc, float rs, float ts, bool
   return f32_to_bf16_bits(v);
 }
 
+// ---- W4A8 (da8w4_kernels.hip): y = bf16(f32(acc * sa) + bias), acc the fp32 sum of the groups' exact integer sums times their scales ----------
+__device__ __forceinline__ uint16_t da8w4_out(float acc, float sa, bool has_bias, float bias) {
+  float v = mul_f32_rn(acc, sa);
+  if (has_bias) v = v + bias;
+  return f32_to_bf16_bits(v);
+}
+
 // ---- Codebook (k-means) weights (codebook_kernels.hip): torchao/prototype/quantization/codebook, the contract -----------------------------
 //   weight   W bf16 [N][K]; block_size (1, d), d in {1, 2, 4, 8}; k = 256 entries (torch.uint8 codes) or 16 (torch.uint4); one scale per
 //            run of sb elements of a row, d | sb | K

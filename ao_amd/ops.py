@@ -3694,3 +3694,143 @@ def codebook_linear(x2: torch.Tensor, codes: torch.Tensor, codebook: torch.Tenso
 
 __all__ += ["CODEBOOK_KERNELS", "codebook_assign", "codebook_lloyd_step", "codebook_pack_u4", "codebook_dequantize", "codebook_linear",
             "codebook_linear_fits", "codebook_linear_route", "codebook_linear_kernel_name", "codebook_linear_set_form"]
+
+
+# ---- W4A8: int8 dynamic activations x int4 weights on the int8 MFMA (include/ao_mi355.h "W4A8", csrc/da8w4_kernels.hip) --------
+DA8W4_KERNELS = {0: "invalid", 1: "da8w4_stream_kernel", 2: "da8w4_tile_kernel"}
+DA8W4_GROUP_SIZES = (32, 64, 128)
+
+
+def _da8w4_padded(k: int, g: int):
+    """(K rounded up to a superblock of 128, groups, groups rounded up to 4): the extents of the device tensors"""
+    return (k + 127) // 128 * 128, k // g, (k // g + 3) // 4 * 4
+
+
+def _da8w4_check(name, t, what, dtype, shape):
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape):
+        raise RuntimeError(f"{name}: {what} must be {dtype} {list(shape)}, got {t.dtype} {list(t.shape)}")
+    return t.contiguous()
+
+
+def da8w4_linear_fits(m: int, n: int, k: int, group_size: int):
+    """None where da8w4_linear serves the shape, else the reason of the refusal (ao_da8w4_linear_fits: host logic, no GPU)."""
+    return None if _lib.lib().ao_da8w4_linear_fits(int(m), int(n), int(k), int(group_size)) == 1 else _lib.last_error()
+
+
+def da8w4_linear_route(m: int, n: int, k: int, group_size: int) -> dict:
+    """The route da8w4_linear launches for a shape (host logic only, ao_da8w4_linear_route)."""
+    return _two_form_route("ao_da8w4_linear_route", DA8W4_KERNELS, m, n, k, group_size)
+
+
+def da8w4_linear_kernel_name(m: int, n: int, k: int, group_size: int) -> str:
+    return _two_form_kernel_name("ao_da8w4_linear_kernel_name", m, n, k, group_size)
+
+
+def da8w4_linear_set_form(form: int) -> None:
+    """Measurement and tests: 0 the route, 1 the streaming form, 2 the tiled form (calling thread)."""
+    _two_form_set_form("ao_da8w4_linear_set_form", form)
+
+
+def da8w4_quantize_weight(w: torch.Tensor, group_size: int = 32):
+    """from_hp_da8w4's cast in one read of a bf16 weight [N, K]: asymmetric 4-bit codes 0 .. 15 per group of group_size along K ->
+    (qdata int32 [N, Kp / 8], the packed layout of DESIGN.md 4.36; scale_and_zero float32 [G, N, 2]: the scale, then zero-point and
+    compensation as two int16 in the second word's bits; qzeros int8 [G, N]; compensation int16 [G, N] = sum_k (q - zero_point))."""
+    name = "da8w4_quantize_weight"
+    dev = _require_gpu(name, w)
+    if w.dim() != 2 or w.dtype != torch.bfloat16:
+        raise NotImplementedError(f"{name}: w must be a 2-D bfloat16 weight, got {w.dtype} {tuple(w.shape)} (float16 and float32 are not built)")
+    n, k = w.shape
+    reason = da8w4_linear_fits(0, n, k, group_size)
+    if reason is not None:
+        raise ValueError(f"{name}: {reason}")
+    kp, g, _ = _da8w4_padded(k, group_size)
+    qdata = torch.empty((n, kp // 8), dtype=torch.int32, device=dev)
+    sz = torch.empty((g, n, 2), dtype=torch.float32, device=dev)
+    qzeros = torch.empty((g, n), dtype=torch.int8, device=dev)
+    comp = torch.empty((g, n), dtype=torch.int16, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_da8w4_quantize_weight(_ptr(w.contiguous()), _ptr(qdata), _ptr(sz), _ptr(qzeros), _ptr(comp), n, k, int(group_size),
+                                                       _stream()))
+    return qdata, sz, qzeros, comp
+
+
+def da8w4_dequantize(qdata: torch.Tensor, scale_and_zero: torch.Tensor, k: int) -> torch.Tensor:
+    """The packed weight -> bf16 [N, K] = bf16((q - zero_point) * scale), exact."""
+    name = "da8w4_dequantize"
+    dev = _require_gpu(name, qdata, scale_and_zero)
+    n, g = qdata.shape[0], scale_and_zero.shape[0]
+    if g == 0 or k % g != 0:
+        raise RuntimeError(f"{name}: scale_and_zero {tuple(scale_and_zero.shape)} holds no whole groups of K={k}")
+    reason = da8w4_linear_fits(0, n, k, k // g)
+    if reason is not None:
+        raise ValueError(f"{name}: {reason}")
+    qdata = _da8w4_check(name, qdata, "qdata", torch.int32, (n, _da8w4_padded(k, k // g)[0] // 8))
+    scale_and_zero = _da8w4_check(name, scale_and_zero, "scale_and_zero", torch.float32, (g, n, 2))
+    out = torch.empty((n, k), dtype=torch.bfloat16, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_da8w4_dequantize(_ptr(qdata), _ptr(scale_and_zero), _ptr(out), n, k, k // g, _stream()))
+    return out
+
+
+def da8w4_quantize_act(x: torch.Tensor, group_size: int = 32, symmetric: bool = False):
+    """The per-token int8 cast of _da8w4_linear in one launch: bf16 x [M, K] -> (codes int8 [M, Kp]: the reference's uint8 code - 128 when
+    asymmetric, its int8 code when symmetric, zero past K; scale float32 [M]; zero_point int32 [M], the reference's; act_meta int32 [M, Gp]:
+    per group of group_size the negated code sum and zero-point the linear takes)."""
+    name = "da8w4_quantize_act"
+    dev = _require_gpu(name, x)
+    if x.dim() != 2 or x.dtype != torch.bfloat16:
+        raise NotImplementedError(f"{name}: x must be 2-D bfloat16, got {x.dtype} {tuple(x.shape)} (float16 and float32 activations are not built)")
+    m, k = x.shape
+    reason = da8w4_linear_fits(m, 32, k, group_size)
+    if reason is not None:
+        raise ValueError(f"{name}: {reason}")
+    kp, _, gp = _da8w4_padded(k, group_size)
+    q = torch.empty((m, kp), dtype=torch.int8, device=dev)
+    scale = torch.empty((m,), dtype=torch.float32, device=dev)
+    zp = torch.empty((m,), dtype=torch.int32, device=dev)
+    meta = torch.empty((m, gp), dtype=torch.int32, device=dev)
+    with _on(dev):
+        _lib.check(_lib.lib().ao_da8w4_quantize_act(_ptr(x.contiguous()), _ptr(q), _ptr(scale), _ptr(zp), _ptr(meta), m, k, int(group_size),
+                                                    int(bool(symmetric)), _stream()))
+    return q, scale, zp, meta
+
+
+def da8w4_linear(x: torch.Tensor, qdata: torch.Tensor, scale_and_zero: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                 symmetric: bool = False, act: Optional[tuple] = None) -> torch.Tensor:
+    """The W4A8 forward on a packed weight, two launches: da8w4_quantize_act, then int8 codes x 4-bit codes on the int8 MFMA with an exact
+    int32 sum per group.  x bf16 [..., K]; qdata / scale_and_zero as da8w4_quantize_weight leaves them; bias bf16 [N] or None -> bf16
+    [..., N].  act: the (codes, scale, act_meta) of an activation already cast at this group size, in place of x's cast (tests)."""
+    name = "da8w4_linear"
+    dev = _require_gpu(name, x, qdata, scale_and_zero, bias)
+    if x.dtype != torch.bfloat16:
+        raise NotImplementedError(f"{name}: x must be bfloat16, got {x.dtype} (float16 and float32 activations are not built)")
+    k = x.shape[-1]
+    if scale_and_zero.dim() != 3 or scale_and_zero.shape[0] == 0 or k % scale_and_zero.shape[0] != 0:
+        raise RuntimeError(f"{name}: scale_and_zero {tuple(scale_and_zero.shape)} holds no whole groups of K={k}")
+    g, n = scale_and_zero.shape[0], scale_and_zero.shape[1]
+    x2 = x.reshape(-1, k)
+    m = x2.shape[0]
+    reason = da8w4_linear_fits(m, n, k, k // g)
+    if reason is not None:
+        raise ValueError(f"{name}: {reason}")
+    kp, _, gp = _da8w4_padded(k, k // g)
+    qdata = _da8w4_check(name, qdata, "qdata", torch.int32, (n, kp // 8))
+    scale_and_zero = _da8w4_check(name, scale_and_zero, "scale_and_zero", torch.float32, (g, n, 2))
+    if bias is not None:
+        bias = _da8w4_check(name, bias, "bias", torch.bfloat16, (n,))
+    out = torch.empty((m, n), dtype=torch.bfloat16, device=dev)
+    if m:
+        if act is None:
+            q, scale, _, meta = da8w4_quantize_act(x2, k // g, symmetric)
+        else:
+            q = _da8w4_check(name, act[0], "act codes", torch.int8, (m, kp))
+            scale = _da8w4_check(name, act[1], "act scale", torch.float32, (m,))
+            meta = _da8w4_check(name, act[2], "act_meta", torch.int32, (m, gp))
+        with _on(dev):
+            _lib.check(_lib.lib().ao_da8w4_linear(_ptr(q), _ptr(qdata), _ptr(scale_and_zero), _ptr(meta), _ptr(scale), _ptr(bias), _ptr(out),
+                                                  m, n, k, k // g, _stream()))
+    return out.view(*x.shape[:-1], n)
+
+
+__all__ += ["DA8W4_KERNELS", "DA8W4_GROUP_SIZES", "da8w4_linear_fits", "da8w4_linear_route", "da8w4_linear_kernel_name", "da8w4_linear_set_form",
+            "da8w4_quantize_weight", "da8w4_dequantize", "da8w4_quantize_act", "da8w4_linear"]

@@ -32,6 +32,7 @@ from .codebook import (  # noqa: F401
     dequantize_codebook,
     quantize_codebook,
 )
+from .int4_opaque_tensor import Int4OpaqueTensor, Int8DynamicActivationInt4WeightConfig  # noqa: F401
 from .nf4_api import NF4WeightOnlyConfig, nf4_weight_only  # noqa: F401
 from .nvfp4_grouped import NVFP4ExpertWeights, nvfp4_grouped_mm  # noqa: F401
 from .nvfp4_grouped_training import _NVFP4GroupedMM, _to_nvfp4_rht_rs_then_scaled_grouped_mm  # noqa: F401
@@ -72,4 +73,4 @@ __all__ = ["Float8BlockwiseExpertWeights", "fp8_blockwise_grouped_mm", "NVFP4Ten
            "AttentionBackend", "HadamardMode", "apply_low_precision_attention", "fp8_sdpa",
            "IntxBitPackedTensor",
            "CodebookWeightOnlyConfig", "codebook_weight_only", "CodebookQuantizedTensor", "choose_qparams_codebook", "quantize_codebook",
-           "dequantize_codebook"]
+           "dequantize_codebook", "Int4OpaqueTensor", "Int8DynamicActivationInt4WeightConfig"]

@@ -1346,6 +1346,36 @@ int ao_codebook_linear_set_form(int form);
 int ao_codebook_linear(const uint16_t* x, const uint8_t* codes, const uint16_t* codebook, const uint16_t* scales, uint16_t* out, int64_t M,
                        int64_t N, int64_t K, int d, int k, int64_t sb, void* stream);
 
+/* ---- W4A8: int8 dynamic activations x int4 weights on the int8 MFMA (torchao/prototype/quantization/int4; csrc/da8w4_kernels.hip states the
+ * arithmetic and the packed layout) -------------------------------------------------------------------------------------------
+ * group_size in {32, 64, 128} dividing K, N % 32 == 0 (the reference's conditions, int4_opaque_tensor.py:236-244).  Kp = K rounded up to 128,
+ * G = K / group_size, Gp = G rounded up to 4.  Every entry checks its shapes, then its pointers, before any launch; no allocation, no
+ * synchronisation: capturable in a graph.
+ * ao_da8w4_quantize_weight (from_hp_da8w4 :248-277: choose_qparams_affine + quantize_affine + da8w4_linear_prepack_cpu, one read of w): w bf16
+ *   [N][K] -> packed [N][Kp / 8] dwords (this library's layout), scale_and_zero [G][N][2] (fp32 scale; zero-point and compensation as two
+ *   int16 in a dword: what the kernels read), qzeros int8 [G][N], compensation int16 [G][N] = sum_k (q - zero_point) of the group.
+ * ao_da8w4_dequantize: out bf16 [N][K] = bf16((q - zero_point) * scale).
+ * ao_da8w4_quantize_act (_da8w4_linear :307-350, one launch): x bf16 [M][K] -> q int8 [M][Kp] (ASYMMETRIC: the reference's uint8 code - 128;
+ *   zero past K), scale fp32 [M], zero_point int32 [M] (the reference's), act_meta [M][Gp] (the per-group code sums and the zero-point the
+ *   linear takes).  symmetric != 0: MappingType.SYMMETRIC, codes in +-127.
+ * ao_da8w4_linear (da8w4_linear_cpu, csrc/cpu/aten_kernels/da8w4_linear.cpp): out bf16 [M][N] from the outputs of the two casts, bias bf16 [N]
+ *   or null.  Two forms behind one route (ao_da8w4_linear_route: the seven fields of the two-form routes): the streaming form up to
+ *   AO_DA8W4_LINEAR_STREAM_MAX_M rows, the LDS-tiled form (128 x 64 tiles) beyond; ao_da8w4_linear_set_form forces one on the calling thread.
+ * ao_da8w4_linear_fits (host logic, no launch): 1 where ao_da8w4_linear serves the shape, else 0 with the reason in ao_last_error(): a group
+ *   size outside {32, 64, 128} or not dividing K, N no multiple of 32, K above 2^24, operands at or above 2^31 bytes. */
+#define AO_DA8W4_LINEAR_STREAM_MAX_M 64 /* fitted (profiles/da8w4_linear.jsonl); the first guess was 16 */
+int ao_da8w4_quantize_weight(const uint16_t* w, uint32_t* packed, float* scale_and_zero, int8_t* qzeros, int16_t* compensation, int64_t N, int64_t K,
+                             int64_t group_size, void* stream);
+int ao_da8w4_dequantize(const uint32_t* packed, const float* scale_and_zero, uint16_t* out, int64_t N, int64_t K, int64_t group_size, void* stream);
+int ao_da8w4_quantize_act(const uint16_t* x, int8_t* q, float* scale, int32_t* zero_point, uint32_t* act_meta, int64_t M, int64_t K,
+                          int64_t group_size, int symmetric, void* stream);
+int ao_da8w4_linear_fits(int64_t M, int64_t N, int64_t K, int64_t group_size);
+int ao_da8w4_linear_route(int64_t M, int64_t N, int64_t K, int64_t group_size, int32_t* out, int cap);
+const char* ao_da8w4_linear_kernel_name(int64_t M, int64_t N, int64_t K, int64_t group_size);
+int ao_da8w4_linear_set_form(int form);
+int ao_da8w4_linear(const int8_t* q, const uint32_t* packed, const float* scale_and_zero, const uint32_t* act_meta, const float* act_scale,
+                    const uint16_t* bias, uint16_t* out, int64_t M, int64_t N, int64_t K, int64_t group_size, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
