@@ -230,6 +230,11 @@ _SIGNATURES = {
     "ao_da8w4_linear_kernel_name": [_I64, _I64, _I64, _I64],
     "ao_da8w4_linear_set_form": [_INT],
     "ao_da8w4_linear": [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P],
+    "ao_int8_train_quantize_workspace_bytes": [_I64, _I64],
+    "ao_int8_train_quantize": [_P, _P, _P, _P, _P, _P, _I64, _I64, ctypes.c_float, _INT, _I64, _I64, _P],
+    "ao_int8_train_mm_fits": [_I64, _I64, _I64, _INT, _INT],
+    "ao_int8_train_mm_kernel_name": [_INT, _INT],
+    "ao_int8_train_mm": [_P, _P, _P, _P, _P, _I64, _I64, _I64, _INT, _INT, _P],
 }
 
 
@@ -284,6 +289,8 @@ def lib():
         l.ao_int4_hqq_workspace_bytes.restype = _I64
         if hasattr(l, "ao_codebook_lloyd_workspace_bytes"):
             l.ao_codebook_lloyd_workspace_bytes.restype = _I64
+        if hasattr(l, "ao_int8_train_quantize_workspace_bytes"):
+            l.ao_int8_train_quantize_workspace_bytes.restype = _I64
         _lib = l
     return _lib
 

@@ -3372,6 +3372,85 @@ __all__ += ["bitnet_mm_fits", "bitnet_absmean", "bitnet_quantize_weight", "bitne
 
 
 # ---------------------------------------------------------------------------
+# Int8 mixed-precision training: the absmax casts in either direction and the layout-free scaled int8 GEMM (csrc/int8_train_kernels.hip)
+# ---------------------------------------------------------------------------
+def _int8_train_2d(name, what, t, dtype):
+    if t.dim() != 2:
+        raise RuntimeError(f"{name}: {what} must be 2-D, got {t.dim()}-D")
+    if t.dtype != dtype:
+        hint = " (float16 and float32 are not built: int8 training here is bfloat16 only)" if dtype == torch.bfloat16 else ""
+        raise NotImplementedError(f"{name}: {what} must be {dtype}, got {t.dtype}{hint}")
+    return t.contiguous()
+
+
+def int8_train_quantize(x: torch.Tensor, rows: bool = True, cols: bool = False, sr_seed: Optional[int] = None, sr_offset: int = 0,
+                        eps: float = 1e-12):
+    """quantize_int8_rowwise (int8.py:25-53) of bf16 x [R, C] (C % 16 == 0) along its rows, down its columns, or both from the same two reads.
+    rows -> (q int8 [R, C], scale bf16 [R]); cols -> (q int8 [R, C], scale bf16 [C]), the codes where the elements lay: quantize_int8_rowwise(x.T)
+    without the transposed copy; both -> the four tensors, rows first.  sr_seed (row direction only): stochastic rounding, floor(v + u) with u
+    from Philox4x32-10 keyed by (sr_seed, sr_offset, element index)."""
+    name = "int8_train_quantize"
+    dev = _require_gpu(name, x)
+    x = _int8_train_2d(name, "x", x, torch.bfloat16)
+    if not (rows or cols):
+        raise ValueError(f"{name}: neither rows nor cols is asked for")
+    if sr_seed is not None and not rows:
+        raise ValueError(f"{name}: sr_seed selects stochastic rounding, which is the row cast's; rows is False")
+    r, c = x.shape
+    if c % 16 != 0 or c == 0:
+        raise ValueError(f"{name}: x has C={c} columns, which must be a positive multiple of 16")
+    q_row = torch.empty((r, c), dtype=torch.int8, device=dev) if rows else None
+    s_row = torch.empty((r,), dtype=torch.bfloat16, device=dev) if rows else None
+    q_col = torch.empty((r, c), dtype=torch.int8, device=dev) if cols else None
+    s_col = torch.empty((c,), dtype=torch.bfloat16, device=dev) if cols else None
+    work = torch.empty(_lib.lib().ao_int8_train_quantize_workspace_bytes(r, c), dtype=torch.uint8, device=dev) if cols and r else None
+    with _on(dev):
+        _lib.check(_lib.lib().ao_int8_train_quantize(_ptr(x), _ptr(q_row), _ptr(s_row), _ptr(q_col), _ptr(s_col), _ptr(work), r, c, float(eps),
+                                                     int(sr_seed is not None), int(sr_seed or 0) & (2 ** 63 - 1), int(sr_offset) & (2 ** 63 - 1),
+                                                     _stream()))
+    return tuple(t for t in (q_row, s_row, q_col, s_col) if t is not None)
+
+
+def int8_train_mm_fits(m: int, n: int, kc: int, a_t: bool = False, b_t: bool = False):
+    """None where int8_train_mm serves the shape, else the reason of the refusal (ao_int8_train_mm_fits: host logic, no GPU)."""
+    return None if _lib.lib().ao_int8_train_mm_fits(int(m), int(n), int(kc), int(bool(a_t)), int(bool(b_t))) == 1 else _lib.last_error()
+
+
+def int8_train_mm_kernel_name(a_t: bool = False, b_t: bool = False) -> str:
+    return _lib.lib().ao_int8_train_mm_kernel_name(int(bool(a_t)), int(bool(b_t))).decode()
+
+
+def int8_train_mm(a: torch.Tensor, b: torch.Tensor, a_scale: torch.Tensor, b_scale: torch.Tensor, a_t: bool = False, b_t: bool = False) -> torch.Tensor:
+    """scaled_int8_mm of the training recipe (int8_mm.py:105-134): bf16 [M, N] = bf16((f32(sum_c A[m, c] B[n, c]) * a_scale[m]) * b_scale[n]), one
+    rounding.  a int8 [M, Kc] (a_t: [Kc, M]), b int8 [N, Kc] (b_t: [Kc, N]), a_scale bf16 [M], b_scale bf16 [N].  The flags name the layout in
+    memory; nothing is transposed outside the kernel."""
+    name = "int8_train_mm"
+    dev = _require_gpu(name, a, b, a_scale, b_scale)
+    a = _int8_train_2d(name, "a", a, torch.int8)
+    b = _int8_train_2d(name, "b", b, torch.int8)
+    kc, m = a.shape if a_t else a.shape[::-1]
+    kcb, n = b.shape if b_t else b.shape[::-1]
+    if kc != kcb:
+        raise RuntimeError(f"{name}: a {tuple(a.shape)} (a_t={bool(a_t)}) and b {tuple(b.shape)} (b_t={bool(b_t)}) contract over {kc} and {kcb} elements")
+    if m and n:
+        reason = int8_train_mm_fits(m, n, kc, a_t, b_t)
+        if reason is not None:
+            raise ValueError(f"{name}: {reason}")
+    for what, s, size in (("a_scale", a_scale, m), ("b_scale", b_scale, n)):
+        if s.dtype != torch.bfloat16 or s.numel() != size:
+            raise RuntimeError(f"{name}: {what} must be bfloat16 with {size} values, got {s.dtype} {tuple(s.shape)}")
+    out = torch.empty((m, n), dtype=torch.bfloat16, device=dev)
+    if m and n:
+        with _on(dev):
+            _lib.check(_lib.lib().ao_int8_train_mm(_ptr(a), _ptr(b), _ptr(a_scale.contiguous()), _ptr(b_scale.contiguous()), _ptr(out), m, n, kc,
+                                                   int(bool(a_t)), int(bool(b_t)), _stream()))
+    return out
+
+
+__all__ += ["int8_train_quantize", "int8_train_mm_fits", "int8_train_mm_kernel_name", "int8_train_mm"]
+
+
+# ---------------------------------------------------------------------------
 # Intx weights, int1 .. int8: the affine cast, the bit-packed layout, the per-token activation fake quantization and the fused linear
 # (csrc/intx_kernels.hip states the arithmetic and the layout)
 # ---------------------------------------------------------------------------

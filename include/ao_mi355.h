@@ -1376,6 +1376,32 @@ int ao_da8w4_linear_set_form(int form);
 int ao_da8w4_linear(const int8_t* q, const uint32_t* packed, const float* scale_and_zero, const uint32_t* act_meta, const float* act_scale,
                     const uint16_t* bias, uint16_t* out, int64_t M, int64_t N, int64_t K, int64_t group_size, void* stream);
 
+/* ---- Int8 mixed-precision training (torchao/prototype/quantized_training/int8.py, int8_mixed_precision.py; csrc/int8_train_kernels.hip states
+ * the arithmetic and the layouts) -------------------------------------------------------------------------------------------------
+ * ao_int8_train_quantize (quantize_int8_rowwise, int8.py:25-53, in either direction): x bf16 [R][C], C % 16 == 0, any R >= 0.
+ *     scale = bf16(amax / 127);  inv = 1 / max(f32(scale), eps);  q = clip(rint(f32(x) * inv), -128, 127)
+ *   The row cast (q_row int8 [R][C], s_row bf16 [R]) takes the amax along a row, the column cast (q_col int8 [R][C], s_col bf16 [C]) down a
+ *   column; BOTH leave the code of x[r][c] at [r][c] -- nothing is written transposed.  A null pair skips that direction.  Rows alone: one
+ *   launch, one read of x.  With columns: an amax pass, the column scales, a cast pass; both directions share the two reads, and workspace
+ *   (ao_int8_train_quantize_workspace_bytes(R, C) device bytes, 16-byte aligned; unused for rows alone) holds the passes' partial maxima.
+ *   sr != 0 (row direction only): q = clip(floor(f32(x) * inv + u), -128, 127), u = (w >> 8) 2^-24 with w word (e & 3) of
+ *   philox4x32_10(counter (e >> 2, sr_offset), key sr_seed), e = r C + c.  An all-zero row or column: scale 0, codes 0 (through eps).
+ * ao_int8_train_mm (_dynamic_int8_mm's scaled_int8_mm, int8_mm.py:105-134): out bf16 [M][N] = bf16((f32(acc) * f32(sa[m])) * f32(sb[n])),
+ *   acc = sum_c A[m, c] B[n, c] in int32 on v_mfma_i32_16x16x64_i8, ONE rounding; sa bf16 [M], sb bf16 [N].  a_t / b_t say how an operand lies
+ *   in memory: 0 the contraction innermost (a [M][Kc], b [N][Kc]), 1 outermost (a [Kc][M], b [Kc][N]) -- the transposition happens on the way
+ *   from LDS to registers.  N % 16 == 0, Kc >= 1, the contiguous dimension of each operand a multiple of 16, Kc <= 2^17 (the int32 range),
+ *   M and N <= 2^22.  Empty M: success without a launch.
+ * ao_int8_train_mm_fits (host logic, no launch): 1 where ao_int8_train_mm serves the shape, else 0 with the reason in ao_last_error();
+ *   ao_int8_train_mm_kernel_name: the kernel of a flag pair ("" for a bad flag).
+ * Pointers 16-byte aligned.  No allocation, no synchronisation, no host read-back: capturable in a graph. */
+int64_t ao_int8_train_quantize_workspace_bytes(int64_t R, int64_t C);
+int ao_int8_train_quantize(const uint16_t* x, int8_t* q_row, uint16_t* s_row, int8_t* q_col, uint16_t* s_col, void* workspace, int64_t R, int64_t C,
+                           float eps, int sr, int64_t sr_seed, int64_t sr_offset, void* stream);
+int ao_int8_train_mm_fits(int64_t M, int64_t N, int64_t Kc, int a_t, int b_t);
+const char* ao_int8_train_mm_kernel_name(int a_t, int b_t);
+int ao_int8_train_mm(const int8_t* a, const int8_t* b, const uint16_t* sa, const uint16_t* sb, uint16_t* out, int64_t M, int64_t N, int64_t Kc,
+                     int a_t, int b_t, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
